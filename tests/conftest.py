@@ -10,7 +10,6 @@ if ROOT not in sys.path:
 
 def pytest_configure(config):
     config.addinivalue_line('markers', 'gpu: needs an MI355X (run with -m gpu on the GPU box)')
-    config.addinivalue_line('markers', 'reference: needs /root/reference (build container only)')
 
 
 @pytest.fixture(scope='session', autouse=True)
@@ -18,14 +17,6 @@ def _oracle_c_lib():
     """The oracle's C restatement is test infrastructure: (re)build it once per session."""
     import __graft_entry__ as g
     g.build_oracle()
-
-
-def pytest_collection_modifyitems(config, items):
-    have_ref = os.path.isdir('/root/reference/multipoint')
-    skip_ref = pytest.mark.skip(reason='/root/reference not present (GPU box)')
-    for item in items:
-        if 'reference' in item.keywords and not have_ref:
-            item.add_marker(skip_ref)
 
 
 @pytest.fixture(scope='session')

@@ -412,16 +412,16 @@ def test_failed_hazard_check_leaves_no_object(tmp_path, monkeypatch):
 
 def test_hardware_queue_default_is_set_by_the_multi_gpu_module_only():
     """GPU_MAX_HW_QUEUES must be in the environment before the runtime initialises for every user of the MULTI-GPU path (an RCCL
-    communicator is what makes the default of 4 queues hurt): importing multipoint_amd.dist sets it (an explicit setting wins),
+    communicator adds streams of its own): importing multipoint_amd.dist sets it (an explicit setting wins),
     importing the package alone leaves the host application's runtime configuration alone."""
     cwd = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     run = lambda code: subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, cwd=cwd, timeout=300)
     r = run('import os; os.environ.pop("GPU_MAX_HW_QUEUES", None); import multipoint_amd; print(os.environ.get("GPU_MAX_HW_QUEUES"))')
     assert r.returncode == 0 and r.stdout.strip() == 'None', r.stderr[-500:]
     r = run('import os; os.environ.pop("GPU_MAX_HW_QUEUES", None); import multipoint_amd.dist; print(os.environ["GPU_MAX_HW_QUEUES"])')
-    assert r.returncode == 0 and r.stdout.strip() == '8', r.stderr[-500:]
-    r = run('import os; os.environ["GPU_MAX_HW_QUEUES"] = "2"; import multipoint_amd.dist; print(os.environ["GPU_MAX_HW_QUEUES"])')
     assert r.returncode == 0 and r.stdout.strip() == '2', r.stderr[-500:]
+    r = run('import os; os.environ["GPU_MAX_HW_QUEUES"] = "1"; import multipoint_amd.dist; print(os.environ["GPU_MAX_HW_QUEUES"])')
+    assert r.returncode == 0 and r.stdout.strip() == '1', r.stderr[-500:]
 
 
 def test_bench_traffic_figure_only_next_to_the_kernel_it_was_measured_on(tmp_path, monkeypatch):
@@ -596,3 +596,37 @@ def test_max_pool_commutes_with_the_fp32_activation_under_the_sign_fold(bn_first
     assert np.array_equal(got, want)                                    # values ...
     same_bits = got.view(np.int32) == want.view(np.int32)
     assert np.all(same_bits | ((got == 0) & (want == 0)))               # ... and bits, up to the sign of an exact zero
+
+
+def test_bench_dump_outputs_masks_unread_slots_and_caps_the_size(tmp_path):
+    """bench.py --dump-outputs: what the caller may read of a PairResults (slots past a list's count and unmatched queries
+    masked to fixed values), float32 / float64 only, and a fixed seeded sample once the arrays exceed the byte budget."""
+    import importlib.util
+    from multipoint_amd.pipeline import PairResults
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    B, K, D = 4, 5, 3
+    g = torch.Generator().manual_seed(0)
+    cnt = torch.tensor([2, 5, 0, 7], dtype=torch.int32)                       # 7 > K: a list that overflowed is read up to K
+    midx = torch.tensor([[1, -1, 3, 0, 4], [2, 2, 2, 2, 2]], dtype=torch.int32)
+    res = PairResults(torch.randint(0, 100, (B, K, 2), generator=g, dtype=torch.int32), torch.rand(B, K, generator=g), cnt,
+                      torch.rand(B, K, D, generator=g), midx, torch.rand(2, K, generator=g), torch.tensor([1, 0], dtype=torch.int32),
+                      16, 16)
+    a = bench.step_outputs(res, forward_only=False)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a['kp_count'].tolist() == [2, 5, 0, 7]
+    assert np.array_equal(a['kp_yx'][0, :2], res.kp_yx[0, :2].numpy()) and (a['kp_yx'][0, 2:] == -1).all()
+    assert (a['kp_yx'][2] == -1).all() and np.array_equal(a['kp_yx'][3], res.kp_yx[3].numpy())
+    assert (a['desc'][0, 2:] == 0).all() and np.array_equal(a['desc'][1], res.desc[1].numpy())
+    assert a['match_train'].tolist() == [[1, -1, -1, -1, -1], [-1, -1, -1, -1, -1]]       # pair 1: optical list empty
+    assert a['match_dist'][0, 0] == res.match_dist[0, 0].item() and (a['match_dist'][0, 1:] == 0).all()
+
+    big = {'x': np.arange(3000, dtype=np.float64), 'y': np.ones(10, np.float32)}
+    w = bench.dump_outputs(big, str(tmp_path / 'o'), budget=8000)
+    assert w == {'x': [500], 'y': [10]}
+    x = np.load(tmp_path / 'o' / 'x.npy')
+    assert np.array_equal(x, np.sort(x)) and len(set(x.tolist())) == 500                # distinct sorted flat indices of arange
+    bench.dump_outputs(big, str(tmp_path / 'p'), budget=8000)
+    assert np.array_equal(np.load(tmp_path / 'p' / 'x.npy'), x)                          # the same sample every run
+    assert bench.dump_outputs(big, str(tmp_path / 'q')) == {'x': [3000], 'y': [10]}      # under the budget: whole arrays
