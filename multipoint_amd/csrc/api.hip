@@ -9,6 +9,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -56,28 +57,46 @@ struct ProfEntry {
     double flop;
 };
 
+// the MP_DEBUG developer switches, read once by mp_create: each field is the key of that name, or the key that turns it off
+// (debug_switch() documents them).  A loaded model's own settings are its ConvPolicy.
+struct DebugSwitches {
+    bool winograd = true, wino43 = true, fuse_first = true, fuse43 = true, head_fuse = true, vin = true, planar = true;
+    bool f16_res = true, f16_fuse1 = true;
+    int wino43_gen = 0, persist = 8, splitk_max = 8, f16_res_groups = 3;
+};
+
+// The convolution algorithm of the loaded model: conv_policy() of the switches and the model config, recomputed at every
+// mp_load_weights (a reload never inherits the previous model's).
+struct ConvPolicy {
+    bool direct = false;            // the direct kernels for every 3x3 layer, the first block fused into conv2's (conv_algorithm
+                                    // 'direct', MP_DEBUG=no_winograd)
+    bool wino43 = true;             // F(4x4,3x3) kernels for the 3x3 layers where they apply (MP_DEBUG=wino43=0 alone: none, and
+                                    // the first block keeps its own launch)
+    int wino43_gen = 0;             // 0 conv_wino43.hip where it applies and conv_wino43b.hip elsewhere; 1 / 2: only that kernel
+    int splitk_max = 8;             // most ranges the input channels of a small launch are cut into (1: never)
+};
+
 }  // namespace
 
 struct mp_handle {
-    int device = 0;
-    int ncu = 256, xcd_shift = 3;   // machine shape derived in mp_create: compute units, log2(XCDs) (MP_DEBUG=ncu / MP_DEBUG=nxcd override)
+    mp_handle(int device_, int ncu_, int xcd_shift_, const DebugSwitches& dbg_)
+        : device(device_), ncu(ncu_), xcd_shift(xcd_shift_), dbg(dbg_) {}
+    const int device;
+    const int ncu, xcd_shift;       // machine shape: compute units, log2(XCDs) (mp_create: from the device, MP_DEBUG=ncu / nxcd override)
+    const DebugSwitches dbg;
     std::string err;
     bool loaded = false;
     mp_model_config cfg{};
+    ConvPolicy policy;              // ... of cfg
     std::vector<void*> weight_allocs;
     Encoder enc[2];                 // [0] = encoder / encoder_thermal, [1] = encoder_optical
     ConvLayer heads3, det1, desc1;
-    DevBuf ws;                      // forward workspace
+    DevBuf ws;                      // forward workspace (fwd_workspace())
     DevBuf ws2;                     // NMS work map + kept lists
     DevBuf ws3;                     // matching arg-min arrays
     DevBuf ws4;                     // pair metrics: warped keypoints + inverse match map
     DevBuf split_ws;                // F(4x4,3x3) split launches: the ranges' pre-bias output tiles
-    DevBuf vin_ws;                  // F(4x4,3x3) layers with >= 4 output slices: the pre-transformed input (ConvParams::vglobal)
-    int vin_min_slices = 4;         // ... from this many slices on (the 3x3 head convolutions: 8): GEMM pass 0.865 ms at 75 % of the matrix pipe +
-                                    // 0.106 ms for the producer against 1.03 ms with the in-kernel transform per slice; MP_DEBUG=no_vin: never
-    int splitk_max = 8;             // most ranges the input channels of a small launch are cut into (MP_DEBUG=splitk_max; 1: never)
-    int fwd_batch = 0;              // images of the forward in flight: the split launches are gated on THIS, not on an encoder's share of it
-    int splitk_env = 8;             // ... as mp_create set it (model.batch_invariant overrides it per loaded model)
+    DevBuf vin_ws;                  // F(4x4,3x3) VIN launches: the pre-transformed input (ConvParams::vglobal)
     DevBuf nms_state;               // 64 round counters + tile flags
     DevBuf kp_scratch;              // segment counts + list totals of the keypoint compaction
     int* nms_total = nullptr;       // device: undecided candidates summed over all calls since the last read
@@ -91,21 +110,7 @@ struct mp_handle {
     int tie_pairs_min = 16;         // ... an image is flagged when at least this many of its NMS decisions fell between scores within tie_eps; 0: off
     int head_channels = 256;        // width of each 3x3 head convolution (MultiPoint.py:38-53)
     void* dummy = nullptr;          // scratch line for masked-off store lanes of the fp16 kernels
-    bool wino = true;               // Winograd F(4x4,3x3) for the 3x3 layers (MP_DEBUG=no_winograd / conv_algorithm 'direct': the direct kernels)
-    int persist = 8;                // persistent conv workgroups for launches with >= this many items per CU
-                                    // (MP_DEBUG=no_persist: never; MP_DEBUG=persist_min_items=n overrides the threshold)
-    bool fuse_first = true;         // fuse the Cin=1 block into the second convolution (MP_DEBUG=no_fuse disables)
-    int planar = 1;                 // 0 (MP_DEBUG=no_planar): NHWC everywhere; 1: channel-quad-planar tensors where they pay (behind conv1 and pooled F(4x4,3x3) producers)
-    int wino43 = 2;                 // MP_DEBUG=wino43: 0 off (direct kernels), 1 F(4x4,3x3) for the 3x3 layers with 64 input channels only, 2 (default) every 3x3 layer
-    bool head_fuse = true;          // MP_DEBUG=no_head_fuse: separate 1x1 convolution / softmax / normalisation launches
-    bool fuse43 = true;             // first block evaluated inside the F(4x4,3x3) conv2 kernel (MP_DEBUG=no_fuse43: its own launch)
-    int wino43_gen = 0;             // MP_DEBUG=wino43_gen: 0 conv_wino43.hip where it applies, conv_wino43b.hip for every other shape; 1 / 2: only that kernel
-    bool wino_env = true;           // wino / wino43 / wino43_gen as mp_create read them: mp_load_weights starts from these and
-    int wino43_env = 2, wino43_gen_env = 0;   // applies the model's conv_algorithm on top (a reload never inherits the previous model's)
     int* pinned = nullptr;          // small pinned host scratch (img lists, counters)
-    bool f16_res = true;            // MP_DEBUG=f16_no_res: the streaming kernel (conv_f16.hip) also for the 64 -> 64 layers
-    bool f16_fuse1 = true;          // MP_DEBUG=f16_no_fuse1: the first block of the fp16 path as its own launch
-    int f16_res_groups = 3;         // MP_DEBUG=f16_res_groups=2: two instead of three wave groups per CU in conv_f16_res.hip
     bool prof = false;
     bool head_fallback_noted = false;
     std::vector<ProfEntry> prof_entries;
@@ -383,7 +388,7 @@ int build_conv(mp_handle* h, TensorMap& tm, ConvLayer& L, const char* name,
     if ((rc = upload(h, bias, &L.bias))) return rc;
     if ((rc = upload(h, scale, &L.scale))) return rc;
     if ((rc = upload(h, shift, &L.shift))) return rc;
-    if (taps == 9 && h->wino && h->wino43 && cin % 8 == 0) {
+    if (taps == 9 && h->policy.wino43 && cin % 8 == 0) {
         std::vector<float> u4;
         pack_wino43_weights(srcs, couts, cin, cin_real, u4);
         if ((rc = upload(h, u4, &L.u43pack))) return rc;
@@ -540,237 +545,345 @@ void prof_end(mp_handle* h, hipStream_t s)
     ++h->prof_used;
 }
 
-// 0, or MP_EINVAL (with the handle's error text set) when the launch is beyond the kernels' 32-bit tile decode
-int too_large(mp_handle* h, const char* name, int B, int H, int W)
-{
-    return fail(h, MP_EINVAL, std::string("mp_forward: layer ") + name + " has too many work items for one launch (B=" +
-                                  std::to_string(B) + ", " + std::to_string(H) + "x" + std::to_string(W) +
-                                  "): split the batch");
-}
-
 // launcher return codes: 0 launched; 1 more work items than the 32-bit tile decode addresses; 2 a layer shape the selected
-// kernel is not instantiated for (a dispatch bug: run_conv only selects kernels whose *_supports() said yes)
+// kernel is not instantiated for (a dispatch bug: the planner only selects kernels whose *_supports() said yes)
 int launch_failed(mp_handle* h, int code, const char* name, int B, int H, int W)
 {
-    if (code == 1) return too_large(h, name, B, H, W);
-    return fail(h, MP_EINVAL, std::string("mp_forward: layer ") + name + ": the selected convolution kernel does not cover this "
-                                  "layer shape (" + std::to_string(H) + "x" + std::to_string(W) + ")");
+    const std::string layer = std::string("mp_forward: layer ") + name;
+    if (code == 1)
+        return fail(h, MP_EINVAL, layer + " has too many work items for one launch (B=" + std::to_string(B) + ", " +
+                                      std::to_string(H) + "x" + std::to_string(W) + "): split the batch");
+    return fail(h, MP_EINVAL, layer + ": the selected convolution kernel does not cover this layer shape (" + std::to_string(H) +
+                                  "x" + std::to_string(W) + ")");
 }
 
-// which F(4x4,3x3) kernel run_conv() sends this 3x3 layer at H x W to: 0 none, 1 conv_wino43.hip (two waves per SIMD; reflection
-// padding and frames that are multiples of the 4x4 tile; the only one that evaluates the first block inside the launch), 2
-// conv_wino43b.hip (one wave per SIMD; any frame size, reflection or zero padding).  MP_DEBUG=wino43_gen: 0 (default) the first where
-// it applies and the second otherwise, 1 / 2 only that one.
-int wino43_kind(const mp_handle* h, const ConvLayer& L, int H, int W, bool fuse, int in_cstride = 0, int in_coff = 0,
-                int out_cstride = 0, int out_coff = 0)
+// ---- the launch plan: which kernel runs which convolution ----------------------------------------------------------------------
+// plan_encoder() (run_forward() for the heads) makes every kernel choice of a forward; run_conv() executes one record.
+
+enum class Kernel { direct, wino43, wino43b, f16, f16_res, f16_res_slices };
+
+struct ConvLaunch {
+    Kernel kernel = Kernel::direct;
+    bool fuse_first = false;                    // the encoder's first block is evaluated inside this launch (enc.conv2)
+    bool in_planar = false, out_planar = false; // channel-quad-planar input / output tensor (fp32 F(4x4,3x3) launches only)
+    int ks_shift = 0;                           // split-K: the input channels run as 2^ks_shift ranges (split_ws)
+    bool vin = false;                           // the input is transformed once, by a pass of its own (vin_ws)
+};
+
+// conv[0].fuse_first false: the encoder's first block is a launch of its own (enc.conv1)
+struct EncoderPlan { ConvLaunch conv[7]; };
+
+// which F(4x4,3x3) kernel a 3x3 layer at H x W goes to: wino43 = conv_wino43.hip (two waves per SIMD; reflection padding and
+// frames that are multiples of the 4x4 tile; the only one that evaluates the first block inside the launch), wino43b =
+// conv_wino43b.hip (one wave per SIMD; any frame size, reflection or zero padding); direct where neither does
+Kernel wino43_kind(const mp_handle* h, const ConvLayer& L, int H, int W, int in_cstride, int in_coff, int out_cstride, int out_coff)
 {
-    if (!(L.taps == 9 && L.u43pack && h->wino && h->wino43 == 2)) return 0;
+    if (!(L.taps == 9 && L.u43pack && h->policy.wino43)) return Kernel::direct;
     ConvParams q{};
     q.pad_zero = h->cfg.reflection_pad ? 0 : 1; q.cin = L.cin; q.cout = L.cout; q.H = H; q.W = W;
     q.in_cstride = in_cstride; q.in_coff = in_coff; q.out_cstride = out_cstride; q.out_coff = out_coff;
-    const bool g1 = h->wino43_gen != 2 && conv_wino43_supports(q), g2 = h->wino43_gen != 1 && conv_wino43b_supports(q);
-    // fuse: the first block is evaluated by the layer's kernel -- only by the pooled 64 -> 64 layer, 64 real channels
-    if (fuse) return h->fuse43 && g1 && L.pool && L.cin == 64 && L.cout == 64 && h->cfg.channel_version == 0 && L.u43pack_f1 ? 1 : 0;
-    return g1 ? 1 : g2 ? 2 : 0;
-}
-bool uses_wino43(const mp_handle* h, const ConvLayer& L, int H, int W, bool fuse, int in_cstride = 0, int in_coff = 0,
-                 int out_cstride = 0, int out_coff = 0)
-{
-    return wino43_kind(h, L, H, W, fuse, in_cstride, in_coff, out_cstride, out_coff) != 0;
+    if (h->policy.wino43_gen != 2 && conv_wino43_supports(q)) return Kernel::wino43;
+    if (h->policy.wino43_gen != 1 && conv_wino43b_supports(q)) return Kernel::wino43b;
+    return Kernel::direct;
 }
 
-int run_conv(mp_handle* h, const ConvLayer& L, const float* in, int in_cstride, int in_coff, float* out,
-              int out_cstride, int out_coff, int B, int H, int W, const int* img_list, hipStream_t s,
-              const FirstLayer* fuse = nullptr, const float* images = nullptr, int in_planar = 0, int out_planar = 0)
+// split-K and the pre-transformed input of an fp32 launch whose kernel, fuse_first and in_planar are decided
+void plan_split_vin(const mp_handle* h, const ConvLayer& L, int B, int H, int W, int fwd_batch, ConvLaunch& c)
 {
-    ConvParams p{};
-    p.in = in; p.out = out; p.wpack = L.wpack; p.bias = L.bias; p.scale = L.scale; p.shift = L.shift;
-    p.img_list = img_list;
-    p.B = B; p.H = H; p.W = W;
-    p.in_cstride = in_cstride; p.in_coff = in_coff; p.cin = L.cin;
-    p.out_cstride = out_cstride; p.out_coff = out_coff; p.cout = L.cout;
-    p.nslices = L.nslices;
-    p.pad_zero = h->cfg.reflection_pad ? 0 : 1;
-    p.bn_first = h->cfg.bn_first;
-    p.relu = L.relu ? 1 : 0;
-    p.persist = h->persist;
-    p.ncu = h->ncu; p.xcd_shift = h->xcd_shift;
-    int mbw = 32;
-    if (L.taps == 9) {
-        mbw = pick_mbw(H, W);
-        const int tw = mbw, th = 256 / mbw;
-        p.tiles_x = (W + tw - 1) / tw; p.tiles_y = (H + th - 1) / th;
-    } else {
-        p.total_px = (long long)B * H * W;
+    if ((c.kernel != Kernel::wino43 && c.kernel != Kernel::wino43b) || c.fuse_first) return;
+    if (fwd_batch <= 2 && h->policy.splitk_max > 1) {
+        // single-pair latency (the reference's shipped batchsize: 1): a launch with fewer items than half the CUs (conv7 /
+        // conv8 of one 480x640 pair: 40 items of 32 units on 256 CUs) cuts the input channels into 2, 4 or 8 ranges --
+        // (cin / 4) / ranges units each, even and >= 4 -- as long as the items still fit the machine once.  Only for
+        // forwards of one or two images (fwd_batch: the whole forward's, not an encoder's share of it): the ranges are summed
+        // in another order than one accumulator chain would, and a batched forward must not change its bits with the batch
+        // size (tests: HA grouping, sharded == single-rank)
+        ConvParams q{};
+        q.B = B; q.H = H; q.W = W; q.nslices = L.nslices;
+        const long long items = conv_wino43_items(q);
+        const int units = L.cin / 4;
+        int ks = 0;
+        while ((items << (ks + 1)) <= h->ncu && (2 << ks) <= h->policy.splitk_max && (units >> (ks + 1)) >= 4 &&
+               ((units >> (ks + 1)) & 1) == 0 && ((units >> (ks + 1)) << (ks + 1)) == units) ++ks;
+        if (ks > 0 && items <= 1024) c.ks_shift = ks;
     }
-    const int f43 = wino43_kind(h, L, H, W, fuse != nullptr, in_cstride, in_coff, out_cstride, out_coff);
-    prof_begin(h, fuse ? "enc.conv1+2" : L.name,
-               2.0 * L.taps * L.cin * L.cout * (double)B * H * W + (fuse ? 2.0 * 9 * 64 * (double)B * H * W : 0.0), s);
-    if (fuse) { p.img = images; p.w1 = fuse->w; p.b1 = fuse->bias; p.s1 = fuse->scale; p.t1 = fuse->shift; }
-    int big;
-    if (f43) {
-        p.wpack = L.u43pack; p.in_planar = in_planar; p.out_planar = out_planar;
-        if (fuse) {       // the fused launch: the first block's BatchNorm is folded away (build_encoder)
-            p.wpack = L.u43pack_f1; p.bias = L.bias_f1; p.w1 = fuse->w_f1; p.b1 = fuse->bias_f1; p.s1 = nullptr; p.t1 = nullptr;
+    // many output slices over one input (heads: 512 couts = 8 slices): transform the input ONCE (conv_wino43.hip VIN), from 4
+    // slices on -- GEMM pass 0.865 ms at 75 % of the matrix pipe + 0.106 ms for the producer against 1.03 ms with the in-kernel
+    // transform per slice
+    c.vin = c.kernel == Kernel::wino43 && !L.pool && c.ks_shift == 0 && !c.in_planar && L.cin % 16 == 0 && L.cin <= 256 &&
+            256 % (L.cin / 2) == 0 && L.cin >= 16 && h->dbg.vin && L.nslices >= 4;
+}
+
+// which fp16 kernel a layer goes to
+Kernel f16_kind(const mp_handle* h, const ConvLayer& L, int in_cstride, int in_coff, bool fuse_first)
+{
+    ConvParamsH q{};
+    q.cin = L.cin; q.cout = L.cout; q.nslices = L.nslices; q.in_cstride = in_cstride; q.in_coff = in_coff;
+    if (h->dbg.f16_res && conv_f16_res_supports(q, L.taps)) return Kernel::f16_res;
+    // 64 input channels, several 64-channel output slices (enc.conv5): a slice's packed weights are 72 KiB, so the
+    // LDS-resident-weights kernel runs once per slice (the input is read once per slice: cheaper than streaming the weights)
+    if (h->dbg.f16_res && !fuse_first && L.taps == 9 && L.cin == 64 && L.nslices > 1 && L.cout == 64 * L.nslices)
+        return Kernel::f16_res_slices;
+    return Kernel::f16;
+}
+
+// the launches of one encoder over nb of the forward's fwd_batch images at H x W (tensors: NHWC, channel stride = the layer's cin / cout)
+EncoderPlan plan_encoder(const mp_handle* h, const Encoder& E, int nb, int fwd_batch, int H, int W)
+{
+    EncoderPlan P;
+    if (h->cfg.mixed_precision) {
+        const ConvLayer& L0 = E.conv[0];
+        // the first block inside the conv2 launch (conv_f16_res.hip F1): reflection padding, the LDS-resident-weights kernel
+        P.conv[0].fuse_first = h->dbg.f16_res && h->dbg.f16_fuse1 && h->cfg.reflection_pad && !E.first_pool && L0.pool &&
+                               L0.cin == 64 && L0.cout == 64 && L0.nslices == 1;
+        for (int i = 0; i < E.nconv; ++i) P.conv[i].kernel = f16_kind(h, E.conv[i], E.conv[i].cin, 0, P.conv[i].fuse_first);
+        return P;
+    }
+    for (int i = 0, hh = E.first_pool ? H / 2 : H, ww = E.first_pool ? W / 2 : W; i < E.nconv; ++i) {
+        const ConvLayer& L = E.conv[i];
+        ConvLaunch& c = P.conv[i];
+        c.kernel = wino43_kind(h, L, hh, ww, L.cin, 0, L.cout, 0);
+        if (i == 0) {
+            // the first block evaluated inside the conv2 launch: by conv_wino43.hip for the pooled 64 -> 64 layer with 64 real
+            // channels; the direct kernels' fused loader is a 64-channel direct convolution, and with Winograd on, the standalone
+            // first block + Winograd second convolution is faster than the fused direct kernel
+            const bool fuse43 = c.kernel == Kernel::wino43 && h->dbg.fuse43 && L.pool && L.cin == 64 && L.cout == 64 &&
+                                h->cfg.channel_version == 0 && L.u43pack_f1;
+            c.fuse_first = h->dbg.fuse_first && h->cfg.channel_version == 0 && !E.first_pool && (h->policy.direct || fuse43);
         }
-        if (!fuse && h->fwd_batch <= 2 && h->splitk_max > 1) {
-            // single-pair latency (the reference's shipped batchsize: 1): a launch with fewer items than half the CUs (conv7 /
-            // conv8 of one 480x640 pair: 40 items of 32 units on 256 CUs) cuts the input channels into 2, 4 or 8 ranges --
-            // (cin / 4) / ranges units each, even and >= 4 -- as long as the items still fit the machine once.  Only for
-            // forwards of one or two images: the ranges are summed in another order than one accumulator chain would, and a
-            // batched forward must not change its bits with the batch size (tests: HA grouping, sharded == single-rank)
-            const long long items = conv_wino43_items(p);
-            const int units = L.cin / 4;
-            int ks = 0;
-            while ((items << (ks + 1)) <= h->ncu && (2 << ks) <= h->splitk_max && (units >> (ks + 1)) >= 4 &&
-                   ((units >> (ks + 1)) & 1) == 0 && ((units >> (ks + 1)) << (ks + 1)) == units) ++ks;
-            if (ks > 0 && items <= 1024) {
-                int rc = ensure(h, h->split_ws, (size_t)(items << ks) * (2 * 16 * 512 * 8));
-                if (rc) return rc;
-                p.ks_shift = ks; p.split_scratch = static_cast<float*>(h->split_ws.p);
-            }
+        // a tensor written by conv1 or an F(4x4,3x3) layer AND read by an F(4x4,3x3) layer is channel-quad planar
+        // -- when the producer's stores are few: conv1, or a POOLED F(4x4,3x3) layer.  (An un-pooled layer stores 16 pixels per
+        // lane and tile; planar, a store instruction then writes 16-byte pieces 64 bytes apart instead of 64-byte runs, which
+        // costs the producer more than the consumer's patch DMAs gain: conv3 1.29 vs 1.17 ms.)  The encoder output stays NHWC
+        // (a planar one was measured for the head convolution: slower).
+        const bool producer = i == 0 ? !E.first_pool : P.conv[i - 1].kernel != Kernel::direct && E.conv[i - 1].pool;
+        c.in_planar = h->dbg.planar && c.kernel != Kernel::direct && producer;
+        if (i > 0) P.conv[i - 1].out_planar = c.in_planar;
+        plan_split_vin(h, L, nb, hh, ww, fwd_batch, c);
+        if (L.pool) { hh /= 2; ww /= 2; }
+    }
+    return P;
+}
+
+// ---- executors ------------------------------------------------------------------------------------------------------------------
+
+// one convolution launch as planned, either precision.  first: the encoder's first block (read when c.fuse_first), images: the
+// forward's input
+template <typename T>
+int run_conv(mp_handle* h, const ConvLayer& L, const ConvLaunch& c, const T* in, int in_cstride, int in_coff, T* out,
+             int out_cstride, int out_coff, int B, int H, int W, const int* img_list, hipStream_t s,
+             const FirstLayer* first = nullptr, const float* images = nullptr)
+{
+    constexpr bool f16 = std::is_same<T, _Float16>::value;
+    typename std::conditional<f16, ConvParamsH, ConvParams>::type p{};
+    p.in = in; p.out = out; p.scale = L.scale; p.shift = L.shift;
+    p.img_list = img_list; p.B = B; p.H = H; p.W = W;
+    p.in_cstride = in_cstride; p.in_coff = in_coff; p.cin = L.cin;
+    p.out_cstride = out_cstride; p.out_coff = out_coff; p.cout = L.cout; p.nslices = L.nslices;
+    p.pad_zero = h->cfg.reflection_pad ? 0 : 1; p.bn_first = h->cfg.bn_first;
+    p.ncu = h->ncu; p.xcd_shift = h->xcd_shift;
+    const int mbw = L.taps == 9 ? pick_mbw(H, W) : 32, th = 256 / mbw;
+    if (L.taps == 9) { p.tiles_x = (W + mbw - 1) / mbw; p.tiles_y = (H + th - 1) / th; }
+    else p.total_px = (long long)B * H * W;
+    if (c.fuse_first) {
+        p.img = images; p.w1 = f16 ? first->w_h : first->w; p.b1 = f16 ? first->bias_h : first->bias;
+        p.s1 = first->scale; p.t1 = first->shift;
+    }
+    if constexpr (f16) {
+        p.wpack = L.wpack_h; p.bias = L.bias_h;
+        p.dummy = static_cast<_Float16*>(h->dummy);
+        p.res_groups = h->dbg.f16_res_groups;
+    } else {
+        p.wpack = c.kernel == Kernel::direct ? L.wpack : L.u43pack; p.bias = L.bias;
+        p.relu = L.relu ? 1 : 0;
+        p.persist = h->dbg.persist;
+        p.in_planar = c.in_planar; p.out_planar = c.out_planar;
+        if (c.fuse_first && c.kernel != Kernel::direct) {      // the fused F(4x4,3x3) launch: the first block's BatchNorm is folded away (build_encoder)
+            p.wpack = L.u43pack_f1; p.bias = L.bias_f1; p.w1 = first->w_f1; p.b1 = first->bias_f1; p.s1 = nullptr; p.t1 = nullptr;
         }
-        if (f43 == 1 && !fuse && !L.pool && p.ks_shift == 0 && !in_planar && L.cin % 16 == 0 && L.cin <= 256 && 256 % (L.cin / 2) == 0 &&
-            L.cin >= 16 && h->vin_min_slices > 0 &&
-            L.nslices >= h->vin_min_slices) {
-            // many output slices over one input (heads: 512 couts = 8 slices): transform the input ONCE (conv_wino43.hip VIN)
+        if (c.ks_shift) {
+            const int rc = ensure(h, h->split_ws, (size_t)(conv_wino43_items(p) << c.ks_shift) * (2 * 16 * 512 * 8));
+            if (rc) return rc;
+            p.ks_shift = c.ks_shift; p.split_scratch = static_cast<float*>(h->split_ws.p);
+        }
+        if (c.vin) {
             // The pre-transformed input is an OPTIONAL workspace (2.25 x the layer's input, linear in B): without it the kernel
             // transforms per slice, bit-identically -- so an allocation failure here is not a failure of the forward
-            const int rc = ensure(h, h->vin_ws, (size_t)conv_wino43_vglobal_floats(p) * 4);
-            if (rc == MP_OK) p.vglobal = static_cast<float*>(h->vin_ws.p);
+            if (ensure(h, h->vin_ws, (size_t)conv_wino43_vglobal_floats(p) * 4) == MP_OK) p.vglobal = static_cast<float*>(h->vin_ws.p);
             else { (void)hipGetLastError(); h->err.clear(); }
         }
-        big = f43 == 2 ? launch_conv_wino43b(p, L.pool, s) : launch_conv_wino43(p, L.pool, s, fuse != nullptr);
-    } else {
-        big = launch_conv_mfma(p, L.taps, mbw, L.pool, fuse != nullptr, s);
     }
-    prof_end(h, s);
-    return big ? launch_failed(h, big, L.name, B, H, W) : MP_OK;
-}
-
-int run_conv_h(mp_handle* h, const ConvLayer& L, const _Float16* in, int in_cstride, int in_coff, _Float16* out,
-                int out_cstride, int out_coff, int B, int H, int W, const int* img_list, hipStream_t s,
-                const FirstLayer* fuse = nullptr, const float* images = nullptr)
-{
-    ConvParamsH p{};
-    p.in = in; p.out = out; p.wpack = L.wpack_h; p.bias = L.bias_h; p.scale = L.scale; p.shift = L.shift;
-    p.img_list = img_list;
-    p.B = B; p.H = H; p.W = W;
-    p.in_cstride = in_cstride; p.in_coff = in_coff; p.cin = L.cin;
-    p.out_cstride = out_cstride; p.out_coff = out_coff; p.cout = L.cout;
-    p.nslices = L.nslices;
-    p.pad_zero = h->cfg.reflection_pad ? 0 : 1;
-    p.bn_first = h->cfg.bn_first;
-    p.dummy = static_cast<_Float16*>(h->dummy);
-    p.ncu = h->ncu; p.xcd_shift = h->xcd_shift; p.res_groups = h->f16_res_groups;
-    int mbw = 32;
-    if (L.taps == 9) {
-        mbw = pick_mbw(H, W);
-        const int tw = mbw, th = 256 / mbw;
-        p.tiles_x = (W + tw - 1) / tw; p.tiles_y = (H + th - 1) / th;
-    } else {
-        p.total_px = (long long)B * H * W;
-    }
-    if (fuse) { p.img = images; p.w1 = fuse->w_h; p.b1 = fuse->bias_h; p.s1 = fuse->scale; p.t1 = fuse->shift; }
-    prof_begin(h, fuse ? "enc.conv1+2" : L.name,
-               2.0 * L.taps * L.cin * L.cout * (double)B * H * W + (fuse ? 2.0 * 9 * 64 * (double)B * H * W : 0.0), s);
+    prof_begin(h, c.fuse_first ? "enc.conv1+2" : L.name,
+               2.0 * L.taps * L.cin * L.cout * (double)B * H * W + (c.fuse_first ? 2.0 * 9 * 64 * (double)B * H * W : 0.0), s);
     int big = 0;
-    if (h->f16_res && conv_f16_res_supports(p, L.taps)) {
-        big = launch_conv_f16_res(p, mbw, L.pool, s);
-    } else if (h->f16_res && !fuse && L.taps == 9 && L.cin == 64 && L.nslices > 1 && L.cout == 64 * L.nslices) {
-        // 64 input channels, several 64-channel output slices (enc.conv5): a slice's packed weights are 72 KiB, so the
-        // LDS-resident-weights kernel runs once per slice (the input is read once per slice: cheaper than streaming the weights)
-        for (int sl = 0; sl < L.nslices && !big; ++sl) {
-            ConvParamsH q = p;
-            q.wpack = p.wpack + (size_t)sl * 36 * 2 * 64 * 8;
-            q.bias = p.bias + 64 * sl; q.scale = p.scale + 64 * sl; q.shift = p.shift + 64 * sl;
-            q.out_coff = out_coff + 64 * sl; q.cout = 64; q.nslices = 1;
-            big = conv_f16_res_supports(q, L.taps) ? launch_conv_f16_res(q, mbw, L.pool, s) : 2;
+    if constexpr (f16) {
+        if (c.kernel == Kernel::f16_res) {
+            big = launch_conv_f16_res(p, mbw, L.pool, s);
+        } else if (c.kernel == Kernel::f16_res_slices) {
+            for (int sl = 0; sl < L.nslices && !big; ++sl) {
+                ConvParamsH q = p;
+                q.wpack = p.wpack + (size_t)sl * 36 * 2 * 64 * 8;
+                q.bias = p.bias + 64 * sl; q.scale = p.scale + 64 * sl; q.shift = p.shift + 64 * sl;
+                q.out_coff = out_coff + 64 * sl; q.cout = 64; q.nslices = 1;
+                big = conv_f16_res_supports(q, L.taps) ? launch_conv_f16_res(q, mbw, L.pool, s) : 2;
+            }
+        } else {
+            big = launch_conv_f16(p, L.taps, mbw, L.pool, s);
         }
     } else {
-        big = launch_conv_f16(p, L.taps, mbw, L.pool, s);
+        big = c.kernel == Kernel::wino43b ? launch_conv_wino43b(p, L.pool, s)
+            : c.kernel == Kernel::wino43  ? launch_conv_wino43(p, L.pool, s, c.fuse_first)
+                                          : launch_conv_mfma(p, L.taps, mbw, L.pool, c.fuse_first, s);
     }
     prof_end(h, s);
     return big ? launch_failed(h, big, L.name, B, H, W) : MP_OK;
 }
 
-// mixed_precision forward: fp16 activations end to end, fp32 softmax / descriptor normalisation
-int forward_f16(mp_handle* h, const float* images, int B, int H, int W, int nsets, const int* counts,
-                const int* const* lptr, float* prob, float* logits, float* desc, hipStream_t s)
+// the first block as a launch of its own; out_planar: its consumer reads channel-quad-planar (fp32 only)
+template <typename T>
+void run_first(mp_handle* h, const Encoder& E, bool out_planar, const float* images, T* out, int B, int H, int W,
+               const int* img_list, hipStream_t s)
 {
-    const int Hc = H / 8, Wc = W / 8;
+    constexpr bool f16 = std::is_same<T, _Float16>::value;
+    typename std::conditional<f16, Conv1ParamsH, Conv1Params>::type c1{};
+    c1.in = images; c1.out = out; c1.w = f16 ? E.first.w_h : E.first.w; c1.bias = f16 ? E.first.bias_h : E.first.bias;
+    c1.scale = E.first.scale; c1.shift = E.first.shift; c1.img_list = img_list; c1.B = B; c1.H = H; c1.W = W;
+    c1.pad_zero = h->cfg.reflection_pad ? 0 : 1; c1.bn_first = h->cfg.bn_first;
+    c1.pool = E.first_pool ? 1 : 0;                          // double_convolution: false -- MaxPool2d follows the block directly
+    prof_begin(h, "enc.conv1", 2.0 * 9 * 64 * (double)B * H * W, s);
+    if constexpr (f16) {
+        launch_conv_first_f16(c1, s);
+    } else {
+        c1.channels = E.first.channels; c1.out_planar = out_planar ? 1 : 0;
+        launch_conv_first(c1, s);
+    }
+    prof_end(h, s);
+}
+
+// forward workspace, byte offsets of: P (B*H*W*64 elements) | Q (B*H*W*16) ping-pong activations | Lg detector logits | X encoder
+// output (separate from the ping-pong buffers: with two encoders the second pass would overwrite the first pass's result) | R raw
+// descriptors (fp16) | lists: image ids of the two encoders of a multispectral model
+struct FwdWorkspace { size_t P, Q, Lg, X, R, lists, bytes; };
+FwdWorkspace fwd_workspace(bool f16, int B, int H, int W)
+{
+    const size_t el = f16 ? 2 : 4, px = (size_t)B * H * W, npx = px / 64;
+    FwdWorkspace w{};
+    w.Q = w.P + px * 64 * el;
+    w.Lg = w.Q + px * 16 * el;
+    w.X = w.Lg + npx * (f16 ? 128 : 80) * el;
+    w.R = w.X + npx * 128 * el;
+    w.lists = w.R + (f16 ? npx * 256 * el : 0);
+    w.bytes = w.lists + 2 * 1024 * 4 + 256;
+    return w;
+}
+
+// the forward, either precision (fp16: fp16 activations, fp32 softmax / descriptor normalisation), of arguments forward_checked
+// accepted
+template <typename T>
+int run_forward(mp_handle* h, const float* images, const unsigned char* is_optical, int B, int H, int W, float* prob,
+                float* logits, float* desc, hipStream_t s)
+{
+    constexpr bool f16 = std::is_same<T, _Float16>::value;
+    const FwdWorkspace w = fwd_workspace(f16, B, H, W);
+    int rc;
+    if ((rc = ensure(h, h->ws, w.bytes))) return rc;
+    if (f16 && !h->dummy) MP_HIP(hipMalloc(&h->dummy, 4096));
+    char* ws = static_cast<char*>(h->ws.p);
+    T *P = reinterpret_cast<T*>(ws + w.P), *Q = reinterpret_cast<T*>(ws + w.Q), *X = reinterpret_cast<T*>(ws + w.X);
+    T *Lg = reinterpret_cast<T*>(ws + w.Lg), *R = reinterpret_cast<T*>(ws + w.R);
+    int* lists = reinterpret_cast<int*>(ws + w.lists);
+    if (h->prof_used > 4000) h->prof_used = 0;      // profile ring: entries accumulate until read
+
+    // encoder(s): multispectral routes each image by is_optical (MultiPoint.py:107-122)
+    int nsets = 1, counts[2] = {B, 0};
+    const int* lptr[2] = {nullptr, nullptr};
+    if (h->cfg.multispectral) {
+        nsets = 2;
+        std::vector<int> host(1024, 0);      // [0..512) thermal image ids, [512..1024) optical ids
+        counts[0] = counts[1] = 0;
+        for (int b = 0; b < B; ++b) {
+            if (is_optical[b]) host[512 + counts[1]++] = b;
+            else host[counts[0]++] = b;
+        }
+        // pageable source: the runtime stages it before returning, so `host` may die here
+        MP_HIP(hipMemcpyAsync(lists, host.data(), 1024 * 4, hipMemcpyHostToDevice, s));
+        lptr[0] = lists; lptr[1] = lists + 512;
+    }
+    for (int e = 0; e < nsets; ++e) {
+        const int nb = counts[e];
+        if (nb == 0) continue;
+        const Encoder& E = h->enc[e];
+        const EncoderPlan plan = plan_encoder(h, E, nb, B, H, W);
+        if (!plan.conv[0].fuse_first) run_first(h, E, plan.conv[0].in_planar, images, P, nb, H, W, lptr[e], s);
+        int hh = E.first_pool ? H / 2 : H, ww = E.first_pool ? W / 2 : W;
+        T* src = P;
+        T* dst = Q;
+        for (int i = 0; i < E.nconv; ++i) {
+            const ConvLayer& L = E.conv[i];
+            if ((rc = run_conv(h, L, plan.conv[i], src, L.cin, 0, i == E.nconv - 1 ? X : dst, L.cout, 0, nb, hh, ww, lptr[e], s,
+                               &E.first, images))) return rc;
+            if (L.pool) { hh /= 2; ww /= 2; }
+            T* t = src; src = dst; dst = t;
+        }
+    }
+
+    // heads
+    const int Hc = H / 8, Wc = W / 8, lstride = f16 ? 128 : 80;
     const long long npx = (long long)B * Hc * Wc;
     const int D = h->cfg.descriptor_size;
     const int hc = h->head_channels;                                 // 256 (channel_version 0) or descriptor_size
     const int headc = h->cfg.descriptor_head ? 2 * hc : hc;
     const int encc = h->heads3.cin;                                  // encoder output channels incl. padding: 128 (64 for channel_version 2)
-    // same carve-up as the fp32 path (sizes in elements), element type fp16
-    const size_t nP = (size_t)B * H * W * 64, nQ = (size_t)B * H * W * 16;
-    const size_t nL = (size_t)npx * 128, nD = (size_t)npx * 128, nR = (size_t)npx * 256;
-    int rc;
-    if (!h->dummy) MP_HIP(hipMalloc(&h->dummy, 4096));
-    _Float16* P = static_cast<_Float16*>(h->ws.p);
-    _Float16* Q = P + nP;
-    _Float16* Lg = Q + nQ;
-    _Float16* X = Lg + nL;
-    _Float16* R = X + nD;        // raw (un-normalised) descriptors
-    (void)nR;
-    for (int e = 0; e < nsets; ++e) {
-        const int nb = counts[e];
-        if (nb == 0) continue;
-        const Encoder& E = h->enc[e];
-        // the first block inside the conv2 launch (conv_f16_res.hip F1): reflection padding, the LDS-resident-weights kernel
-        const bool fuse1 = h->f16_res && h->f16_fuse1 && h->cfg.reflection_pad && !E.first_pool && E.conv[0].pool &&
-                           E.conv[0].cin == 64 && E.conv[0].cout == 64 && E.conv[0].nslices == 1;
-        if (!fuse1) {
-            Conv1ParamsH c1{};
-            c1.in = images; c1.out = P; c1.w = E.first.w_h; c1.bias = E.first.bias_h; c1.scale = E.first.scale;
-            c1.shift = E.first.shift; c1.img_list = lptr[e]; c1.B = nb; c1.H = H; c1.W = W;
-            c1.pad_zero = h->cfg.reflection_pad ? 0 : 1; c1.bn_first = h->cfg.bn_first;
-            c1.pool = E.first_pool ? 1 : 0;                          // double_convolution: false -- MaxPool2d follows the block directly
-            prof_begin(h, "enc.conv1", 2.0 * 9 * 64 * (double)nb * H * W, s);
-            launch_conv_first_f16(c1, s);
-            prof_end(h, s);
-        }
-        int hh = E.first_pool ? H / 2 : H, ww = E.first_pool ? W / 2 : W;
-        _Float16* src = P;
-        _Float16* dst = Q;
-        for (int i = 0; i < E.nconv; ++i) {
-            const ConvLayer& L = E.conv[i];
-            if ((rc = run_conv_h(h, L, src, L.cin, 0, i == E.nconv - 1 ? X : dst, L.cout, 0, nb, hh, ww, lptr[e], s,
-                                 (i == 0 && fuse1) ? &E.first : nullptr, images))) return rc;
-            if (L.pool) { hh /= 2; ww /= 2; }
-            _Float16* t = src; src = dst; dst = t;
-        }
+    ConvLaunch c3, c1x1;            // both 3x3 head convolutions in one launch; the 1x1 ones: the direct / streaming fp16 kernel
+    if constexpr (f16) {
+        c3.kernel = f16_kind(h, h->heads3, encc, 0, false);
+        c1x1.kernel = Kernel::f16;
+    } else {
+        c3.kernel = wino43_kind(h, h->heads3, Hc, Wc, encc, 0, headc, 0);
+        plan_split_vin(h, h->heads3, B, Hc, Wc, B, c3);
     }
-    if ((rc = run_conv_h(h, h->heads3, X, encc, 0, P, headc, 0, B, Hc, Wc, nullptr, s))) return rc;
-    if (h->head_fuse) {
-        // both 1x1 convolutions + BN + softmax / shuffle + normalisation in ONE launch that reads P once (head_tail_f16.hip)
-        HeadTailParamsH t{};
+    if ((rc = run_conv(h, h->heads3, c3, X, encc, 0, P, headc, 0, B, Hc, Wc, nullptr, s))) return rc;
+    if (h->dbg.head_fuse && (!f16 || prob || logits || desc)) {
+        // both 1x1 convolutions + BN + softmax / shuffle + normalisation in ONE launch that reads P once (head_tail*.hip).  Not
+        // instantiated for every model: then its profile entry is taken back, the separate launches below are profiled instead,
+        // and a note goes to stderr once per handle
+        typename std::conditional<f16, HeadTailParamsH, HeadTailParams>::type t{};
         t.x = P; t.xstride = headc; t.K = hc;
-        t.wdet = h->det1.wpack_h; t.bdet = h->det1.bias_h; t.sdet = h->det1.scale; t.tdet = h->det1.shift;
-        t.wdesc = h->desc1.wpack_h; t.bdesc = h->desc1.bias_h; t.sdesc = h->desc1.scale; t.tdesc = h->desc1.shift;
+        if constexpr (f16) {
+            t.wdet = h->det1.wpack_h; t.bdet = h->det1.bias_h; t.wdesc = h->desc1.wpack_h; t.bdesc = h->desc1.bias_h;
+        } else {
+            t.wdet = h->det1.wpack; t.bdet = h->det1.bias; t.wdesc = h->desc1.wpack; t.bdesc = h->desc1.bias;
+        }
+        t.sdet = h->det1.scale; t.tdet = h->det1.shift; t.sdesc = h->desc1.scale; t.tdesc = h->desc1.shift;
         t.D = D; t.npx = npx; t.B = B; t.Hc = Hc; t.Wc = Wc;
-        t.prob = prob; t.logits_nchw = logits; t.desc = h->cfg.descriptor_head ? desc : nullptr;
+        t.prob = prob; t.logits_nchw = logits; t.desc = desc;
         t.softmax_mode = h->cfg.softmax_mode; t.normalize = h->cfg.normalize_descriptors ? 1 : 0; t.ncu = h->ncu;
-        if (t.wdet && (!t.desc || t.wdesc) && (prob || logits || t.desc)) {
-            prof_begin(h, "heads.tail", 2.0 * hc * (65.0 + (t.desc ? D : 0)) * (double)npx, s);
-            const int miss = launch_head_tail_f16(t, s);
-            prof_end(h, s);
-            if (!miss) { MP_HIP(hipGetLastError()); return MP_OK; }
-            if (h->prof && h->prof_used) --h->prof_used;      // not covered: the separate launches below are profiled instead
+        prof_begin(h, "heads.tail", 2.0 * hc * (65.0 + (desc ? D : 0)) * (double)npx, s);
+        int miss;
+        if constexpr (f16) miss = launch_head_tail_f16(t, s); else miss = launch_head_tail(t, s);
+        prof_end(h, s);
+        if (!miss) { MP_HIP(hipGetLastError()); return MP_OK; }
+        if (h->prof) --h->prof_used;
+        if (!h->head_fallback_noted) {
+            h->head_fallback_noted = true;
+            fprintf(stderr, "[multipoint_hip] note: fused head tail not instantiated for %d head channels / descriptor size %d: "
+                            "using the separate 1x1 convolution, softmax and normalisation launches\n", hc, D);
         }
     }
-    if ((rc = run_conv_h(h, h->det1, P, headc, 0, Lg, 128, 0, B, Hc, Wc, nullptr, s))) return rc;
+    if ((rc = run_conv(h, h->det1, c1x1, P, headc, 0, Lg, lstride, 0, B, Hc, Wc, nullptr, s))) return rc;
     if (prob || logits) {
         prof_begin(h, "det.softmax_shuffle", 0.0, s);
-        launch_det_post_f16(Lg, 128, B, Hc, Wc, prob, logits, h->cfg.softmax_mode, s);
+        if constexpr (f16) launch_det_post_f16(Lg, lstride, B, Hc, Wc, prob, logits, h->cfg.softmax_mode, s);
+        else launch_det_post(Lg, lstride, B, Hc, Wc, prob, logits, h->cfg.softmax_mode, s);
         prof_end(h, s);
     }
     if (desc) {
-        if ((rc = run_conv_h(h, h->desc1, P, headc, hc, R, D, 0, B, Hc, Wc, nullptr, s))) return rc;
+        T* raw;                      // fp32: the descriptors are normalised in place
+        if constexpr (f16) raw = R; else raw = desc;
+        if ((rc = run_conv(h, h->desc1, c1x1, P, headc, hc, raw, D, 0, B, Hc, Wc, nullptr, s))) return rc;
         prof_begin(h, "desc.l2norm", 0.0, s);
-        launch_desc_l2norm_f16(R, desc, npx, D, h->cfg.normalize_descriptors ? 1 : 0, s);
+        if constexpr (f16) launch_desc_l2norm_f16(R, desc, npx, D, h->cfg.normalize_descriptors ? 1 : 0, s);
+        else if (h->cfg.normalize_descriptors) launch_desc_l2norm(desc, desc, npx, D, 1, s);
         prof_end(h, s);
     }
     MP_HIP(hipGetLastError());
@@ -932,6 +1045,18 @@ bool debug_switch(const char* key, int* value = nullptr, int dflt = 1)
     return false;
 }
 
+// the convolution algorithm of the 3x3 layers is a MODEL setting (yaml model.conv_algorithm: 0 auto, 1 winograd43, 2
+// winograd43_general, 3 direct); the MP_DEBUG switches only choose for 'auto'.  batch_invariant: never split the input channels
+ConvPolicy conv_policy(const DebugSwitches& d, const mp_model_config& cfg)
+{
+    ConvPolicy p;
+    p.direct = cfg.conv_algorithm == 3 || (cfg.conv_algorithm == 0 && !d.winograd);
+    p.wino43 = !p.direct && (cfg.conv_algorithm != 0 || d.wino43);
+    p.wino43_gen = cfg.conv_algorithm == 1 ? 0 : cfg.conv_algorithm == 2 ? 2 : d.wino43_gen;
+    p.splitk_max = cfg.batch_invariant ? 1 : d.splitk_max;
+    return p;
+}
+
 int kfd_num_xcc(const char* bus_id)
 {
     unsigned dom = 0, bus = 0, dev = 0, fn = 0;
@@ -1018,30 +1143,25 @@ int mp_create(mp_handle** out, int device)
     if (ncu < 1 || nxcd < 1 || (nxcd & (nxcd - 1)) != 0 || nxcd > ncu)
         return fail(h, MP_EINVAL, "mp_create: unsupported machine shape: " + std::to_string(ncu) + " compute units in " +
                                       std::to_string(nxcd) + " XCDs (the XCD count must be a power of two <= the CU count)");
-    mp_handle* hh = new mp_handle();
-    hh->device = device;
-    hh->ncu = ncu;
-    hh->xcd_shift = 0;
-    while ((1 << hh->xcd_shift) < nxcd) ++hh->xcd_shift;
-    {
-        int v = 0;
-        hh->fuse_first = !debug_switch("no_fuse");
-        hh->wino = !debug_switch("no_winograd");
-        hh->fuse43 = !debug_switch("no_fuse43");
-        hh->head_fuse = !debug_switch("no_head_fuse");
-        hh->f16_res = !debug_switch("f16_no_res");
-        hh->f16_fuse1 = !debug_switch("f16_no_fuse1");
-        if (debug_switch("f16_res_groups", &v) && v == 2) hh->f16_res_groups = 2;
-        if (debug_switch("no_planar")) hh->planar = 0;
-        if (debug_switch("wino43", &v) && v == 0) hh->wino43 = 0;
-        if (debug_switch("wino43_gen", &v) && v >= 0 && v <= 2) hh->wino43_gen = v;
-        if (debug_switch("persist_min_items", &v) && v > 0) hh->persist = v;
-        if (debug_switch("no_persist")) hh->persist = 0;
-        if (debug_switch("splitk_max", &v) && v >= 1 && v <= 8) hh->splitk_max = v;
-        if (debug_switch("no_vin")) hh->vin_min_slices = 0;
-    }
-    hh->splitk_env = hh->splitk_max;
-    hh->wino_env = hh->wino; hh->wino43_env = hh->wino43; hh->wino43_gen_env = hh->wino43_gen;
+    int xcd_shift = 0;
+    while ((1 << xcd_shift) < nxcd) ++xcd_shift;
+    DebugSwitches d;                                          // every other MP_DEBUG key
+    int v = 0;
+    d.winograd = !debug_switch("no_winograd");
+    if (debug_switch("wino43", &v) && v == 0) d.wino43 = false;
+    if (debug_switch("wino43_gen", &v) && v >= 0 && v <= 2) d.wino43_gen = v;
+    d.fuse_first = !debug_switch("no_fuse");
+    d.fuse43 = !debug_switch("no_fuse43");
+    d.head_fuse = !debug_switch("no_head_fuse");
+    d.vin = !debug_switch("no_vin");
+    d.planar = !debug_switch("no_planar");
+    if (debug_switch("persist_min_items", &v) && v > 0) d.persist = v;
+    if (debug_switch("no_persist")) d.persist = 0;
+    if (debug_switch("splitk_max", &v) && v >= 1 && v <= 8) d.splitk_max = v;
+    d.f16_res = !debug_switch("f16_no_res");
+    d.f16_fuse1 = !debug_switch("f16_no_fuse1");
+    if (debug_switch("f16_res_groups", &v) && v == 2) d.f16_res_groups = 2;
+    mp_handle* hh = new mp_handle(device, ncu, xcd_shift, d);
     if (hipHostMalloc(reinterpret_cast<void**>(&hh->pinned), 4096) != hipSuccess) {
         delete hh;
         return fail(h, MP_ENOMEM, "mp_create: hipHostMalloc failed");
@@ -1060,6 +1180,7 @@ void mp_destroy(mp_handle* h)
     if (h->ws3.p) (void)hipFree(h->ws3.p);
     if (h->ws4.p) (void)hipFree(h->ws4.p);
     if (h->split_ws.p) (void)hipFree(h->split_ws.p);
+    if (h->vin_ws.p) (void)hipFree(h->vin_ws.p);
     if (h->nms_state.p) (void)hipFree(h->nms_state.p);
     if (h->kp_scratch.p) (void)hipFree(h->kp_scratch.p);
     if (h->nms_total) (void)hipFree(h->nms_total);
@@ -1089,13 +1210,7 @@ int mp_load_weights(mp_handle* h, const mp_model_config* cfg, const mp_tensor* t
     MP_HIP(hipSetDevice(h->device));
     free_weights(h);
     h->cfg = *cfg;
-    // the convolution algorithm of the 3x3 layers is a MODEL setting (yaml model.conv_algorithm); the MP_DEBUG developer switches of
-    // mp_create only apply to 'auto'
-    h->wino = h->wino_env; h->wino43 = h->wino43_env; h->wino43_gen = h->wino43_gen_env;     // 0 auto: what mp_create chose
-    if (cfg->conv_algorithm == 1) { h->wino = true; h->wino43 = 2; h->wino43_gen = 0; }
-    else if (cfg->conv_algorithm == 2) { h->wino = true; h->wino43 = 2; h->wino43_gen = 2; }
-    else if (cfg->conv_algorithm == 3) { h->wino = false; }
-    h->splitk_max = cfg->batch_invariant ? 1 : h->splitk_env;
+    h->policy = conv_policy(h->dbg, *cfg);
     TensorMap tm;
     for (int i = 0; i < n_tensors; ++i) {
         if (!tensors[i].name || (!tensors[i].data && tensors[i].numel > 0))
@@ -1159,127 +1274,11 @@ static int forward_checked(mp_handle* h, const float* images, const unsigned cha
     if (desc && !h->cfg.descriptor_head) return fail(h, MP_EINVAL, "mp_forward: model has no descriptor head");
     if (h->cfg.multispectral && !is_optical)
         return fail(h, MP_EINVAL, "mp_forward: multispectral model needs is_optical");
+    if (h->cfg.multispectral && B > 512) return fail(h, MP_EINVAL, "mp_forward: multispectral B > 512 unsupported");
     hipStream_t s = static_cast<hipStream_t>(stream);
     MP_HIP(hipSetDevice(h->device));
-    const int Hc = H / 8, Wc = W / 8;
-    const long long npx = (long long)B * Hc * Wc;
-    const int D = h->cfg.descriptor_size;
-    const int hc = h->head_channels;
-    const int headc = h->cfg.descriptor_head ? 2 * hc : hc;
-    // workspace: P (B*H*W*64) | Q (B*H*W*16) | X encoder output (npx*128) | logits (npx*80) | img lists
-    const size_t nP = (size_t)B * H * W * 64, nQ = (size_t)B * H * W * 16;
-    const size_t nL = (size_t)npx * 80, nD = (size_t)npx * 128;
-    int rc;
-    if ((rc = ensure(h, h->ws, (nP + nQ + nL + nD) * 4 + 2 * 1024 * 4 + 256))) return rc;
-    float* P = static_cast<float*>(h->ws.p);
-    float* Q = P + nP;
-    float* Lg = Q + nQ;
-    float* X = Lg + nL;      // encoder output: separate from the ping-pong buffers, because with two
-                             // encoders the second pass would overwrite the first pass's result
-    int* lists = reinterpret_cast<int*>(X + nD);
-    if (h->prof_used > 4000) h->prof_used = 0;      // profile ring: entries accumulate until read
-
-    // encoder(s): multispectral routes each image by is_optical (MultiPoint.py:107-122)
-    int nsets = 1, counts[2] = {B, 0};
-    const int* lptr[2] = {nullptr, nullptr};
-    h->fwd_batch = B;
-    if (h->cfg.multispectral) {
-        if (B > 512) return fail(h, MP_EINVAL, "mp_forward: multispectral B > 512 unsupported");
-        nsets = 2;
-        std::vector<int> host(1024, 0);      // [0..512) thermal image ids, [512..1024) optical ids
-        counts[0] = counts[1] = 0;
-        for (int b = 0; b < B; ++b) {
-            if (is_optical[b]) host[512 + counts[1]++] = b;
-            else host[counts[0]++] = b;
-        }
-        // pageable source: the runtime stages it before returning, so `host` may die here
-        MP_HIP(hipMemcpyAsync(lists, host.data(), 1024 * 4, hipMemcpyHostToDevice, s));
-        lptr[0] = lists; lptr[1] = lists + 512;
-    }
-    if (h->cfg.mixed_precision) return forward_f16(h, images, B, H, W, nsets, counts, lptr, prob, logits, desc, s);
-    for (int e = 0; e < nsets; ++e) {
-        const int nb = counts[e];
-        if (nb == 0) continue;
-        const Encoder& E = h->enc[e];
-        Conv1Params c1{};
-        c1.in = images; c1.out = P; c1.w = E.first.w; c1.bias = E.first.bias; c1.scale = E.first.scale;
-        c1.shift = E.first.shift; c1.img_list = lptr[e]; c1.B = nb; c1.H = H; c1.W = W;
-        c1.pad_zero = h->cfg.reflection_pad ? 0 : 1; c1.bn_first = h->cfg.bn_first;
-        c1.channels = E.first.channels;
-        // the fused loader is a 64-channel direct-convolution kernel; with Winograd on, the standalone first block +
-        // Winograd second convolution is faster than the fused direct kernel
-        const bool fuse1 = h->fuse_first && h->cfg.channel_version == 0 && !E.first_pool &&
-                           (!h->wino || uses_wino43(h, E.conv[0], H, W, true));
-        // a tensor written by conv1 or an F(4x4,3x3) layer AND read by an F(4x4,3x3) layer is channel-quad planar
-        // -- when the producer's stores are few: conv1, or a POOLED F(4x4,3x3) layer.  (An un-pooled layer stores 16 pixels per
-        // lane and tile; planar, a store instruction then writes 16-byte pieces 64 bytes apart instead of 64-byte runs, which
-        // costs the producer more than the consumer's patch DMAs gain: conv3 1.29 vs 1.17 ms.)
-        bool f43[8] = {}, pl[9] = {};               // pl[i]: the input tensor of E.conv[i] is planar
-        const int H1 = E.first_pool ? H / 2 : H, W1 = E.first_pool ? W / 2 : W;      // frame of the first block's output
-        for (int i = 0, hh = H1, ww = W1; i < E.nconv; ++i) {
-            f43[i] = uses_wino43(h, E.conv[i], hh, ww, i == 0 && fuse1);
-            if (E.conv[i].pool) { hh /= 2; ww /= 2; }
-        }
-        pl[0] = h->planar && f43[0] && !E.first_pool;
-        for (int i = 1; i < E.nconv; ++i) pl[i] = h->planar && f43[i - 1] && f43[i] && E.conv[i - 1].pool;
-        c1.out_planar = pl[0] ? 1 : 0;
-        c1.pool = E.first_pool ? 1 : 0;
-        if (!fuse1) {
-            prof_begin(h, "enc.conv1", 2.0 * 9 * 64 * (double)nb * H * W, s);
-            launch_conv_first(c1, s);
-            prof_end(h, s);
-        }
-        int hh = H1, ww = W1;
-        float* src = P;
-        float* dst = Q;
-        for (int i = 0; i < E.nconv; ++i) {
-            const ConvLayer& L = E.conv[i];
-            if ((rc = run_conv(h, L, src, L.cin, 0, i == E.nconv - 1 ? X : dst, L.cout, 0, nb, hh, ww, lptr[e], s,
-                     (i == 0 && fuse1) ? &E.first : nullptr, images, pl[i], pl[i + 1]))) return rc;
-            if (L.pool) { hh /= 2; ww /= 2; }
-            float* t = src; src = dst; dst = t;
-        }
-    }
-    // heads
-    if ((rc = run_conv(h, h->heads3, X, h->heads3.cin, 0, P, headc, 0, B, Hc, Wc, nullptr, s))) return rc;       // (a planar encoder output was measured: slower)
-    if (h->head_fuse) {
-        // both 1x1 convolutions + BN + softmax / shuffle + normalisation in ONE launch that reads P once (head_tail.hip)
-        HeadTailParams t{};
-        t.ncu = h->ncu;
-        t.x = P; t.xstride = headc; t.K = hc;
-        t.wdet = h->det1.wpack; t.bdet = h->det1.bias; t.sdet = h->det1.scale; t.tdet = h->det1.shift;
-        t.wdesc = h->desc1.wpack; t.bdesc = h->desc1.bias; t.sdesc = h->desc1.scale; t.tdesc = h->desc1.shift;
-        t.D = D; t.npx = npx; t.B = B; t.Hc = Hc; t.Wc = Wc;
-        t.prob = prob; t.logits_nchw = logits; t.desc = desc;
-        t.softmax_mode = h->cfg.softmax_mode; t.normalize = h->cfg.normalize_descriptors ? 1 : 0;
-        prof_begin(h, "heads.tail", 2.0 * hc * (65.0 + (desc ? D : 0)) * (double)npx, s);
-        const int miss = launch_head_tail(t, s);
-        prof_end(h, s);
-        if (!miss) {
-            MP_HIP(hipGetLastError());
-            return MP_OK;
-        }
-        if (h->prof) --h->prof_used;    // not covered: fall through to the separate kernels
-        if (!h->head_fallback_noted) {  // ... visibly: once per handle on stderr, and the profile then lists "det.conv1x1" etc.
-            h->head_fallback_noted = true;
-            fprintf(stderr, "[multipoint_hip] note: fused head tail not instantiated for %d head channels / descriptor size %d: "
-                            "using the separate 1x1 convolution, softmax and normalisation launches\n", hc, D);
-        }
-    }
-    if ((rc = run_conv(h, h->det1, P, headc, 0, Lg, 80, 0, B, Hc, Wc, nullptr, s))) return rc;
-    if (prob || logits) {
-        prof_begin(h, "det.softmax_shuffle", 0.0, s);
-        launch_det_post(Lg, 80, B, Hc, Wc, prob, logits, h->cfg.softmax_mode, s);
-        prof_end(h, s);
-    }
-    if (desc) {
-        if ((rc = run_conv(h, h->desc1, P, headc, hc, desc, D, 0, B, Hc, Wc, nullptr, s))) return rc;
-        prof_begin(h, "desc.l2norm", 0.0, s);
-        if (h->cfg.normalize_descriptors) launch_desc_l2norm(desc, desc, npx, D, 1, s);
-        prof_end(h, s);
-    }
-    MP_HIP(hipGetLastError());
-    return MP_OK;
+    return h->cfg.mixed_precision ? run_forward<_Float16>(h, images, is_optical, B, H, W, prob, logits, desc, s)
+                                  : run_forward<float>(h, images, is_optical, B, H, W, prob, logits, desc, s);
 }
 
 int mp_forward(mp_handle* h, const float* images, const unsigned char* is_optical, int B, int H, int W,
