@@ -294,6 +294,37 @@ int mp_ha_finalize(mp_handle* h, const float* prob, const float* count, int B, i
 int mp_gaussian_filter(mp_handle* h, const float* in, int B, int H, int W, int ksize, const float* weights, float* out,
                        void* stream);
 
+/* ---- SuperPointLoss, forward-only evaluation (multipoint/utils/losses.py:8-272) ----
+ * Shapes: logits fp32 [B][65][Hc][Wc] (mp_forward with force_return_logits); keypoint / valid maps uint8 [B][H][W],
+ * nonzero = keypoint / valid pixel; desc1 / desc2 channels-last fp32 [B][Hc][Wc][D] like mp_forward's descriptors;
+ * homographies fp32 [B][9] row-major, acting on (x, y, 1).  H == 8 Hc and W == 8 Wc are required (MP_EINVAL otherwise, as
+ * for D outside {64, 128, 256}).  Both losses write per-image double results; the caller forms the batch means.  The
+ * results are bit-identical from run to run (fixed-order reductions, no float atomics).
+ *
+ * mp_loss_workspace_bytes: bytes of the caller-owned device workspace both losses need for B images of H x W. */
+int mp_loss_workspace_bytes(int B, int H, int W, long long* bytes);
+
+/* replaces SuperPointLoss.detector_loss (losses.py:85-122).  A cell is valid when all 64 of its pixels are (valid == NULL:
+ * every cell).  use_cross_entropy 1: label = argmax([3 kp_c + noise_c (c < 64), 2.0]), loss = logsumexp - logit[label];
+ * noise fp32 [B][64][Hc][Wc] is the reference's torch.rand draw, or NULL for a counter-based hash of
+ * (noise_seed, b, c, h, w).  0: BCE on softmax(logits) against the normalised multi-hot labels plus dustbin (:110-119).
+ * out double [B][2]: sum over cells of loss * valid, number of valid cells (loss = mean_b(out[b][0] / out[b][1])). */
+int mp_detector_loss(mp_handle* h, const float* logits, int B, int Hc, int Wc, const unsigned char* keypoints,
+                     const unsigned char* valid_mask, int H, int W, int use_cross_entropy, const float* noise,
+                     unsigned long long noise_seed, void* workspace, long long workspace_bytes, double* out, void* stream);
+
+/* replaces the dense branch of SuperPointLoss.descriptor_loss (losses.py:207-272) without its B x (Hc Wc)^2 tensors:
+ * cell centres (8h+4, 8w+4) warped by inverse(hom) (hom NULL: identity), corr = |w1[j] - w2[i]| <= threshold,
+ * dot = desc2[i] . desc1[j], pos = lambda_d corr max(0, positive_margin - dot), neg = (1 - corr) max(0, dot - negative_margin),
+ * with use_mask both times valid2[i] valid1[j] (cell validity as above; valid NULL: every cell).
+ * out double [B][4]: sum pos, sum neg, corresponding valid pairs, normalisation (valid1 cells x valid2 cells with the
+ * mask, (Hc Wc)^2 without).  warped: optional fp32 [2][B][Hc Wc][2], the warped centres (y, x) of side 1 then side 2. */
+int mp_descriptor_loss(mp_handle* h, const float* desc1, const float* desc2, int B, int Hc, int Wc, int D,
+                       const float* hom1, const float* hom2, const unsigned char* valid1, const unsigned char* valid2,
+                       int H, int W, float threshold, float positive_margin, float negative_margin, float lambda_d,
+                       int use_mask, void* workspace, long long workspace_bytes, double* out, float* warped,
+                       void* stream);
+
 /* per-launch timing of mp_forward with hipEvents on the caller's stream (bench.py roofline leg).
  * mp_profile_read synchronises; names[i] points to static strings. */
 int mp_profile_enable(mp_handle* h, int enable);

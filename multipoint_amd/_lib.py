@@ -85,6 +85,12 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p]),
     'mp_ha_finalize': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     'mp_gaussian_filter': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'mp_loss_workspace_bytes': (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
+    'mp_detector_loss': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                 c_void_p, ctypes.c_ulonglong, c_void_p, c_ll, c_void_p, c_void_p]),
+    'mp_descriptor_loss': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_int, c_void_p, c_ll,
+                                   c_void_p, c_void_p, c_void_p]),
     'mp_profile_enable': (c_int, [c_void_p, c_int]),
     'mp_profile_read': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_float),
                                 ctypes.POINTER(ctypes.c_double), c_int, ctypes.POINTER(c_int)]),

@@ -1672,4 +1672,72 @@ int mp_profile_read(mp_handle* h, const char** names, float* ms, double* flop, i
     return MP_OK;
 }
 
+int mp_loss_workspace_bytes(int B, int H, int W, long long* bytes)
+{
+    if (!bytes || B <= 0 || B > 65535 || H <= 0 || W <= 0 || H % 8 || W % 8) return MP_EINVAL;
+    *bytes = (long long)loss_workspace_bytes(B, H, W);
+    return MP_OK;
+}
+
+static int loss_check(mp_handle* h, const char* fn, int B, int Hc, int Wc, int H, int W, void* workspace,
+                      long long workspace_bytes)
+{
+    if (B <= 0 || B > 65535 || Hc <= 0 || Wc <= 0)
+        return fail(h, MP_EINVAL, std::string(fn) + ": need 0 < B <= 65535 and Hc, Wc > 0");
+    if (H % 8 || W % 8) return fail(h, MP_EINVAL, std::string(fn) + ": H and W must be multiples of 8");
+    if (H != 8 * Hc || W != 8 * Wc)
+        return fail(h, MP_EINVAL, std::string(fn) + ": the " + std::to_string(H) + "x" + std::to_string(W) +
+                                      " label maps do not match the " + std::to_string(Hc) + "x" + std::to_string(Wc) + " cell grid");
+    if ((long long)Hc * Wc > 0x7fffffffLL / 8) return fail(h, MP_EINVAL, std::string(fn) + ": frame too large");
+    if (!workspace || workspace_bytes < (long long)loss_workspace_bytes(B, H, W))
+        return fail(h, MP_EINVAL, std::string(fn) + ": workspace smaller than mp_loss_workspace_bytes");
+    return MP_OK;
+}
+
+int mp_detector_loss(mp_handle* h, const float* logits, int B, int Hc, int Wc, const unsigned char* keypoints,
+                     const unsigned char* valid_mask, int H, int W, int use_cross_entropy, const float* noise,
+                     unsigned long long noise_seed, void* workspace, long long workspace_bytes, double* out, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!logits || !keypoints || !out) return fail(h, MP_EINVAL, "mp_detector_loss: NULL tensor");
+    const int rc = loss_check(h, "mp_detector_loss", B, Hc, Wc, H, W, workspace, workspace_bytes);
+    if (rc != MP_OK) return rc;
+    MP_HIP(hipSetDevice(h->device));
+    launch_detector_loss(logits, keypoints, valid_mask, noise, noise_seed, B, H, W, use_cross_entropy != 0, workspace, out,
+                         static_cast<hipStream_t>(stream));
+    MP_HIP(hipGetLastError());
+    return MP_OK;
+}
+
+// largest float s with sqrt_rn(s) <= thr (sqrt_rn is monotone: dist <= thr  <=>  dy^2 + dx^2 <= s); -1 when no distance is
+// <= thr (thr negative or NaN)
+static float corr_bound(float thr)
+{
+    if (!(thr >= 0.f)) return -1.f;
+    if (std::isinf(thr)) return thr;
+    float s = (float)((double)thr * thr);
+    while (s > 0.f && !(std::sqrt(s) <= thr)) s = std::nextafter(s, 0.f);
+    while (!std::isinf(s) && std::sqrt(std::nextafter(s, INFINITY)) <= thr) s = std::nextafter(s, INFINITY);
+    return s;
+}
+
+int mp_descriptor_loss(mp_handle* h, const float* desc1, const float* desc2, int B, int Hc, int Wc, int D,
+                       const float* hom1, const float* hom2, const unsigned char* valid1, const unsigned char* valid2,
+                       int H, int W, float threshold, float positive_margin, float negative_margin, float lambda_d,
+                       int use_mask, void* workspace, long long workspace_bytes, double* out, float* warped,
+                       void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!desc1 || !desc2 || !out) return fail(h, MP_EINVAL, "mp_descriptor_loss: NULL tensor");
+    if (D != 64 && D != 128 && D != 256) return fail(h, MP_EINVAL, "mp_descriptor_loss: D must be 64, 128 or 256");
+    const int rc = loss_check(h, "mp_descriptor_loss", B, Hc, Wc, H, W, workspace, workspace_bytes);
+    if (rc != MP_OK) return rc;
+    MP_HIP(hipSetDevice(h->device));
+    launch_descriptor_loss(desc1, desc2, hom1, hom2, valid1, valid2, B, H, W, D, corr_bound(threshold), positive_margin,
+                           negative_margin, (double)lambda_d, use_mask != 0, workspace, out, warped,
+                           static_cast<hipStream_t>(stream));
+    MP_HIP(hipGetLastError());
+    return MP_OK;
+}
+
 }  // extern "C"

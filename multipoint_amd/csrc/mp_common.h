@@ -333,3 +333,18 @@ void launch_ha_accumulate(const float* pa, const float* pb, const unsigned char*
 void launch_ha_finalize(const float* prob, const float* count, long long n, int aggregation, float min_count, float* out,
                         hipStream_t s);
 void launch_gaussian_filter(const float* in, int B, int H, int W, int k, const float* wgt, float* out, hipStream_t s);
+
+// SuperPointLoss evaluation (losses.hip; reference multipoint/utils/losses.py:85-122, 207-272).  Label / mask maps uint8
+// [B][H][W] (nonzero = set), logits fp32 [B][65][Hc][Wc], descriptors channels-last fp32 [B][Hc*Wc][D], homographies fp32
+// [B][9].  `workspace` holds loss_workspace_bytes(B, H, W) bytes.
+//   detector:   noise fp32 [B][64][Hc][Wc] or NULL (hash of (seed, b, c, h, w)); out double [B][2]: sum of loss * valid, count
+//   descriptor: s_max = largest float s with sqrt_rn(s) <= threshold; out double [B][4]: lambda_d * positive sum, negative
+//               sum, corresponding valid pairs, normalisation; warped fp32 [2][B][Hc*Wc][2] (y, x) or NULL
+size_t loss_workspace_bytes(int B, int H, int W);
+void launch_detector_loss(const float* logits, const unsigned char* kp, const unsigned char* valid, const float* noise,
+                          unsigned long long seed, int B, int H, int W, int use_ce, void* workspace, double* out,
+                          hipStream_t s);
+void launch_descriptor_loss(const float* desc1, const float* desc2, const float* hom1, const float* hom2,
+                            const unsigned char* valid1, const unsigned char* valid2, int B, int H, int W, int D,
+                            float s_max, float pos_margin, float neg_margin, double lambda_d, int use_mask,
+                            void* workspace, double* out, float* warped, hipStream_t s);
