@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Validation loss of one or more checkpoints: the validation loop of the reference's train.py (:44-50, :127-150) without
-the training, to choose a checkpoint.  Forward (mp_forward) and SuperPointLoss (multipoint_amd.utils.losses) run on the
+the training, to choose a checkpoint.  Forward (mp_forward, or mp_forward_batch_stats with --batch-statistics) and SuperPointLoss (multipoint_amd.utils.losses) run on the
 GPU; the per-batch losses are accumulated on the device and read once per checkpoint."""
 import argparse
 import copy
@@ -21,10 +21,13 @@ from predict_align_image_pair import load_network
 
 DESCRIPTION = """Validation loss of the checkpoints of a training run (train.py's compute_validation_loss loop).
 
-Stated deviation: train.py validates with the network still in training mode, so its BatchNorm layers use the statistics
-of each validation batch.  This implementation runs the forward in eval mode only (running statistics), so the loss
-reported here is the loss of the eval-mode forward -- the outputs a deployment actually sees.  It therefore differs from
-the validation loss train.py logs for networks with BatchNorm."""
+train.py validates with the network still in training mode, so its BatchNorm layers use the statistics of each
+validation batch.  By default this tool runs the forward in eval mode (running statistics): the loss reported is the
+loss of the eval-mode forward -- the outputs a deployment actually sees -- and differs from the validation loss train.py
+logs for networks with BatchNorm.  With --batch-statistics the forward normalises with the statistics of each batch, as
+train.py's does, and reports train.py's validation loss (fp32 models only; the running statistics are not updated).
+A remaining difference: train.py under multi-GPU DataParallel computes the statistics per replica's chunk of the batch,
+this tool over the whole batch."""
 
 
 def build_parser():
@@ -42,6 +45,9 @@ def build_parser():
     parser.add_argument('--no-photometric', action='store_true',
                         help='Validate without the photometric augmentation the config asks for (the dataset refuses it: '
                              'it is a training-time feature)')
+    parser.add_argument('--batch-statistics', action='store_true',
+                        help="Run the forward as train.py's validation loop does: BatchNorm with the statistics of each "
+                             'batch (training mode, forward only) instead of the running statistics')
     parser.add_argument('--save-json', default=None, help='Write the averages of every checkpoint to this JSON file')
     return parser
 
@@ -134,6 +140,8 @@ def main(argv=None):
         net = load_network(config, args.model_dir, version, device, args.seed)
         if hasattr(net, 'set_force_return_logits'):
             net.set_force_return_logits(True)
+        if args.batch_statistics:
+            net.set_batch_statistics(True)
         loss, comp = evaluate_checkpoint(net, loader, loss_fn, device, dataset.returns_pair())
         results[version] = dict(loss=loss, **comp)
         print('%s: loss %.6g  %s' % (version, loss, '  '.join('%s %.6g' % (k, v) for k, v in comp.items())), flush=True)
@@ -142,7 +150,8 @@ def main(argv=None):
     print('best: %s' % best)
     if args.save_json:
         with open(args.save_json, 'w') as f:
-            json.dump({'versions': results, 'best': best, 'seed': args.seed, 'eval_mode': True}, f, indent=1)
+            json.dump({'versions': results, 'best': best, 'seed': args.seed,
+                       'eval_mode': not args.batch_statistics}, f, indent=1)
     return 0
 
 

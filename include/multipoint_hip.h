@@ -104,6 +104,25 @@ int mp_load_weights(mp_handle* h, const mp_model_config* cfg, const mp_tensor* t
 int mp_forward(mp_handle* h, const float* images, const unsigned char* is_optical, int B, int H,
                int W, float* prob, float* logits, float* desc, void* stream);
 
+/* replaces MultiPoint.forward in TRAINING mode, forward only (the reference's train.py never calls net.eval(), so its validation
+ * loop, train.py:127-150, runs this): every BatchNorm2d normalises with the mean and biased variance of this batch (eps 1e-5);
+ * the detector head returns logits only (MultiPoint.py:150-158).  fp32 models with BatchNorm only: mixed_precision models and
+ * models without BatchNorm (SuperPointMagicLeap) are refused with MP_EINVAL, as is a batch in which some BatchNorm layer sees
+ * a single value per channel (torch raises ValueError there: e.g. B = 1 at 8x8).  Multispectral: each encoder's statistics
+ * cover the images routed to it; an encoder that receives no images does not run and its statistics are left unwritten.
+ * Every layer runs on the direct convolution kernels plus three batchnorm_stats.hip passes; the results are bit-identical from
+ * run to run.  The running statistics of the model are not touched.
+ *   logits [B][65][H/8][W/8] (required), desc [B][H/8][W/8][D] or NULL (channels-last, as mp_forward)
+ *   stats  NULL, or fp32: per BatchNorm layer i (mp_batch_stats_layer), in state_dict order, [2][C_i] = the batch mean and the
+ *          unbiased variance (what torch blends into running_mean / running_var with momentum 0.1); layer i starts at float
+ *          offset 2 * (C_0 + ... + C_{i-1}) */
+int mp_forward_batch_stats(mp_handle* h, const float* images, const unsigned char* is_optical, int B, int H, int W,
+                           float* logits, float* desc, float* stats, void* stream);
+/* the BatchNorm layers of the loaded model in state_dict order: their number (0 without BatchNorm), and layer i's state_dict
+ * prefix (e.g. "encoder.2", "detector_head_convolutions.5"; valid until the next mp_load_weights) and channel count C_i */
+int mp_batch_stats_count(const mp_handle* h, int* count);
+int mp_batch_stats_layer(const mp_handle* h, int i, const char** name, int* channels);
+
 /* replaces utils.box_nms (multipoint/utils/utils.py:78-122) incl. the `prob * valid_mask`
  * multiply of its callers (predict_align_image_pair.py:128,133).
  *   valid_mask  uint8 [B][H][W] or NULL

@@ -50,6 +50,10 @@ SIGNATURES = {
     'mp_load_weights': (c_int, [c_void_p, ctypes.POINTER(ModelConfig), ctypes.POINTER(Tensor), c_int]),
     'mp_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                            c_void_p, c_void_p]),
+    'mp_forward_batch_stats': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+    'mp_batch_stats_count': (c_int, [c_void_p, ctypes.POINTER(c_int)]),
+    'mp_batch_stats_layer': (c_int, [c_void_p, c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_int)]),
     'mp_box_nms': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, ctypes.c_double,
                            c_int, c_void_p, c_int, c_void_p]),
     'mp_detect_keypoints': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,

@@ -51,6 +51,15 @@ struct Encoder {
     bool first_pool = false;        // ... where MaxPool2d(2,2) follows the first block directly
 };
 
+// one BatchNorm2d layer for the batch-statistics forward (mp_forward_batch_stats): its state_dict prefix, real channels, and the
+// un-folded affine parameters
+struct BnLayer {
+    std::string name;
+    int channels = 0;
+    float *gamma = nullptr, *beta = nullptr;     // device [channels]
+    long long offset = 0;                        // float offset of its [2][channels] statistics in the caller's array
+};
+
 struct ProfEntry {
     const char* name;
     hipEvent_t a, b;
@@ -97,6 +106,9 @@ struct mp_handle {
     DevBuf ws4;                     // pair metrics: warped keypoints + inverse match map
     DevBuf split_ws;                // F(4x4,3x3) split launches: the ranges' pre-bias output tiles
     DevBuf vin_ws;                  // F(4x4,3x3) VIN launches: the pre-transformed input (ConvParams::vglobal)
+    DevBuf bs_ws;                   // batch-statistics forward workspace (bs_workspace())
+    std::vector<BnLayer> bn_layers; // every BatchNorm2d of the loaded model, state_dict order (mp_batch_stats_layer)
+    float* bn_ident = nullptr;      // device [1024]: 512 ones | 512 zeros, the identity epilogue of the batch-statistics convolutions
     DevBuf nms_state;               // 64 round counters + tile flags
     DevBuf kp_scratch;              // segment counts + list totals of the keypoint compaction
     int* nms_total = nullptr;       // device: undecided candidates summed over all calls since the last read
@@ -159,6 +171,8 @@ void free_weights(mp_handle* h)
 {
     for (void* p : h->weight_allocs) (void)hipFree(p);
     h->weight_allocs.clear();
+    h->bn_layers.clear();
+    h->bn_ident = nullptr;
     h->loaded = false;
 }
 
@@ -408,6 +422,22 @@ int build_conv(mp_handle* h, TensorMap& tm, ConvLayer& L, const char* name,
     return MP_OK;
 }
 
+// the batch-statistics forward's record of BatchNorm layer `prefix` (appended: call in state_dict order)
+int add_bn_layer(mp_handle* h, TensorMap& tm, const std::string& prefix, int channels)
+{
+    std::string err;
+    const float* g = tm.get(prefix + ".weight", channels, err); if (!g) return fail(h, MP_EINVAL, err);
+    const float* b = tm.get(prefix + ".bias", channels, err); if (!b) return fail(h, MP_EINVAL, err);
+    BnLayer L;
+    L.name = prefix; L.channels = channels;
+    L.offset = h->bn_layers.empty() ? 0 : h->bn_layers.back().offset + 2LL * h->bn_layers.back().channels;
+    int rc;
+    if ((rc = upload(h, std::vector<float>(g, g + channels), &L.gamma))) return rc;
+    if ((rc = upload(h, std::vector<float>(b, b + channels), &L.beta))) return rc;
+    h->bn_layers.push_back(L);
+    return MP_OK;
+}
+
 const char* kEncNames[7] = {"enc.conv2", "enc.conv3", "enc.conv4", "enc.conv5", "enc.conv6", "enc.conv7",
                             "enc.conv8"};
 
@@ -471,6 +501,10 @@ int build_encoder(mp_handle* h, TensorMap& tm, Encoder& E, const std::string& pr
     for (int i = 1; i <= E.nconv; ++i) {
         int rc = build_conv(h, tm, E.conv[i - 1], kEncNames[i - 1], {conv_key(i)}, {bn_key(i)}, {chan[i + 1]}, pad32(chan[i]), 9,
                             pool[i], true, chan[i], true);
+        if (rc) return rc;
+    }
+    for (int i = 0; i <= E.nconv && h->cfg.batchnorm; ++i) {
+        const int rc = add_bn_layer(h, tm, bn_key(i), chan[i + 1]);
         if (rc) return rc;
     }
     // The fused F(4x4,3x3) conv1+conv2 launch (conv_wino43.hip F1: channel_version 0, double convolution, reflection padding) produces
@@ -890,6 +924,201 @@ int run_forward(mp_handle* h, const float* images, const unsigned char* is_optic
     return MP_OK;
 }
 
+// ---- the batch-statistics forward (mp_forward_batch_stats): MultiPoint.forward in training mode, forward only -------------------
+// Every BatchNorm normalises with the statistics of the batch, so no BatchNorm can be folded into a convolution: each layer is
+// conv (direct kernel, identity epilogue: conv + bias [+ ReLU for conv -> ReLU -> BN models], never pooled) -> bn.stats ->
+// bn.finalize -> bn.apply (affine [+ ReLU for bn_first models] [+ 2x2 max-pool]).  The direct kernels serve every layer shape, so
+// the plan is the same for every model: no Winograd, no fused first block, no planar tensors, no split-K, no fused head tail.
+
+// workspace, byte offsets of: A, Bf ping-pong activations (B*H*W*64 floats each: the largest un-pooled layer output, conv1 / conv2
+// at full resolution) | X encoder output | G gathered images of one encoder (multispectral) | part stats partials | ss scale and
+// shift (512 each) | lists
+struct BsWorkspace { size_t A, Bf, X, G, part, ss, lists, bytes; };
+BsWorkspace bs_workspace(int B, int H, int W, bool multispectral)
+{
+    const size_t px = (size_t)B * H * W, npx = px / 64;
+    BsWorkspace w{};
+    w.Bf = w.A + px * 64 * 4;
+    w.X = w.Bf + px * 64 * 4;
+    w.G = w.X + npx * 128 * 4;
+    w.part = w.G + (multispectral ? px * 4 : 0);
+    w.ss = w.part + (size_t)MP_BN_MAX_PARTS * 2 * 512 * 8;
+    w.lists = w.ss + 1024 * 4;
+    w.bytes = w.lists + 2 * 1024 * 4 + 256;
+    return w;
+}
+
+struct BsContext {
+    mp_handle* h;
+    double* part;
+    float *scale, *shift;
+    float* stats;                   // caller's statistics array or nullptr
+    hipStream_t s;
+};
+
+// statistics of x [npx][C] (C = the tensor's channels incl. padding) -> scale / shift of channels [c0, c0 + nc) for BatchNorm
+// layer `layer` (real channels: its own; the rest of the range is padding)
+void bs_stats(BsContext& c, const float* x, long long npx, int C)
+{
+    prof_begin(c.h, "bn.stats", 0.0, c.s);
+    launch_bn_stats(x, npx, C, C, c.part, c.s);
+    prof_end(c.h, c.s);
+}
+
+void bs_finalize(BsContext& c, const float* x, long long npx, int C, int c0, int nc, int layer)
+{
+    const BnLayer& L = c.h->bn_layers[layer];
+    prof_begin(c.h, "bn.finalize", 0.0, c.s);
+    launch_bn_finalize(c.part, npx, C, x, c0, nc, L.channels, L.gamma, L.beta, c.scale, c.shift,
+                       c.stats ? c.stats + L.offset : nullptr, c.stats ? c.stats + L.offset + L.channels : nullptr, c.s);
+    prof_end(c.h, c.s);
+}
+
+void bs_apply(BsContext& c, const float* x, float* y, int B, int H, int W, int C, bool relu, bool pool, const int* out_list)
+{
+    prof_begin(c.h, "bn.apply", 0.0, c.s);
+    launch_bn_apply(x, y, B, H, W, C, c.scale, c.shift, relu, pool, out_list, c.s);
+    prof_end(c.h, c.s);
+}
+
+// one convolution with the identity epilogue (direct kernel; linear: no ReLU either)
+int bs_conv(mp_handle* h, const ConvLayer& L, const float* in, int in_cstride, int in_coff, float* out, int out_cstride, int B, int H,
+            int W, hipStream_t s)
+{
+    ConvParams p{};
+    p.in = in; p.out = out; p.wpack = L.wpack; p.bias = L.bias; p.scale = h->bn_ident; p.shift = h->bn_ident + 512;
+    p.B = B; p.H = H; p.W = W;
+    p.in_cstride = in_cstride; p.in_coff = in_coff; p.cin = L.cin;
+    p.out_cstride = out_cstride; p.out_coff = 0; p.cout = L.cout; p.nslices = L.nslices;
+    p.pad_zero = h->cfg.reflection_pad ? 0 : 1; p.bn_first = h->cfg.bn_first;
+    p.relu = L.taps == 9 && !h->cfg.bn_first;
+    p.persist = h->dbg.persist; p.ncu = h->ncu; p.xcd_shift = h->xcd_shift;
+    const int mbw = L.taps == 9 ? pick_mbw(H, W) : 32, th = 256 / mbw;
+    if (L.taps == 9) { p.tiles_x = (W + mbw - 1) / mbw; p.tiles_y = (H + th - 1) / th; }
+    else p.total_px = (long long)B * H * W;
+    prof_begin(h, L.name, 2.0 * L.taps * L.cin * L.cout * (double)B * H * W, s);
+    const int big = L.taps == 9 && h->cfg.bn_first ? launch_conv_mfma_linear(p, mbw, s) : launch_conv_mfma(p, L.taps, mbw, false, false, s);
+    prof_end(h, s);
+    return big ? launch_failed(h, big, L.name, B, H, W) : MP_OK;
+}
+
+int run_forward_batch_stats(mp_handle* h, const float* images, const unsigned char* is_optical, int B, int H, int W, float* logits,
+                            float* desc, float* stats, hipStream_t s)
+{
+    const BsWorkspace w = bs_workspace(B, H, W, h->cfg.multispectral != 0);
+    int rc;
+    if ((rc = ensure(h, h->bs_ws, w.bytes))) return rc;
+    char* ws = static_cast<char*>(h->bs_ws.p);
+    float *A = reinterpret_cast<float*>(ws + w.A), *Bf = reinterpret_cast<float*>(ws + w.Bf), *X = reinterpret_cast<float*>(ws + w.X);
+    float* G = reinterpret_cast<float*>(ws + w.G);
+    int* lists = reinterpret_cast<int*>(ws + w.lists);
+    BsContext c{h, reinterpret_cast<double*>(ws + w.part), reinterpret_cast<float*>(ws + w.ss), reinterpret_cast<float*>(ws + w.ss) + 512,
+                stats, s};
+    if (h->prof_used > 4000) h->prof_used = 0;
+    const bool bnf = h->cfg.bn_first != 0;
+
+    int nsets = 1, counts[2] = {B, 0};
+    const int* lptr[2] = {nullptr, nullptr};
+    if (h->cfg.multispectral) {
+        nsets = 2;
+        std::vector<int> host(1024, 0);      // [0..512) thermal image ids, [512..1024) optical ids
+        counts[0] = counts[1] = 0;
+        for (int b = 0; b < B; ++b) {
+            if (is_optical[b]) host[512 + counts[1]++] = b;
+            else host[counts[0]++] = b;
+        }
+        MP_HIP(hipMemcpyAsync(lists, host.data(), 1024 * 4, hipMemcpyHostToDevice, s));
+        lptr[0] = lists; lptr[1] = lists + 512;
+    }
+    for (int e = 0; e < nsets; ++e) {
+        const int nb = counts[e];
+        if (nb == 0) continue;               // an encoder without images does not run and reports no statistics
+        const Encoder& E = h->enc[e];
+        const int bn0 = e * (E.nconv + 1);   // its first BatchNorm layer
+        const float* img = images;
+        if (lptr[e]) {                       // its images as a contiguous batch
+            prof_begin(h, "bn.gather", 0.0, s);
+            launch_bn_gather(images, lptr[e], nb, H, W, G, s);
+            prof_end(h, s);
+            img = G;
+        }
+        Conv1Params c1{};
+        c1.in = img; c1.out = A; c1.w = E.first.w; c1.bias = E.first.bias; c1.scale = h->bn_ident; c1.shift = h->bn_ident + 512;
+        c1.B = nb; c1.H = H; c1.W = W; c1.pad_zero = h->cfg.reflection_pad ? 0 : 1; c1.bn_first = h->cfg.bn_first;
+        c1.channels = E.first.channels;
+        prof_begin(h, "enc.conv1", 2.0 * 9 * E.first.channels * (double)nb * H * W, s);
+        if (bnf) launch_conv_first_linear(c1, s); else launch_conv_first(c1, s);
+        prof_end(h, s);
+        float* buf[2] = {A, Bf};
+        int cur = 0;                         // buf[cur] holds the next layer's input
+        int hh = H, ww = W;
+        auto bn_layer = [&](int layer, int C, bool pool, bool last) {
+            // batch statistics of buf[1 - cur] (the layer's un-pooled output), then the affine into the next input
+            float* y = buf[1 - cur];
+            const long long npx = (long long)nb * hh * ww;
+            bs_stats(c, y, npx, C);
+            bs_finalize(c, y, npx, C, 0, C, bn0 + layer);
+            if (last) {
+                bs_apply(c, y, X, nb, hh, ww, C, bnf, pool, lptr[e]);
+            } else if (pool) {
+                bs_apply(c, y, buf[cur], nb, hh, ww, C, bnf, true, nullptr);
+            } else {
+                bs_apply(c, y, y, nb, hh, ww, C, bnf, false, nullptr);
+                cur = 1 - cur;
+            }
+            if (pool) { hh /= 2; ww /= 2; }
+        };
+        cur = 1;                             // conv1 wrote buf[0] = buf[1 - cur]
+        bn_layer(0, E.first.channels, E.first_pool, false);
+        for (int i = 0; i < E.nconv; ++i) {
+            const ConvLayer& L = E.conv[i];
+            if ((rc = bs_conv(h, L, buf[cur], L.cin, 0, buf[1 - cur], L.cout, nb, hh, ww, s))) return rc;
+            bn_layer(i + 1, L.cout, L.pool, i == E.nconv - 1);
+        }
+    }
+
+    // heads: both 3x3 convolutions in one launch (A), the 1x1 ones into Bf (detector, row stride 80) and desc / Bf + 80 npx
+    const int Hc = H / 8, Wc = W / 8, lstride = 80;
+    const long long npx = (long long)B * Hc * Wc;
+    const int D = h->cfg.descriptor_size, hc = h->head_channels;
+    const int headc = h->cfg.descriptor_head ? 2 * hc : hc;
+    const int encc = h->heads3.cin;
+    const int hb = nsets * (h->enc[0].nconv + 1);      // the heads' first BatchNorm layer
+    const int fb = h->cfg.final_batchnorm ? 1 : 0;
+    if ((rc = bs_conv(h, h->heads3, X, encc, 0, A, headc, B, Hc, Wc, s))) return rc;
+    bs_stats(c, A, npx, headc);
+    bs_finalize(c, A, npx, headc, 0, hc, hb);
+    if (h->cfg.descriptor_head) bs_finalize(c, A, npx, headc, hc, hc, hb + 1 + fb);
+    bs_apply(c, A, A, B, Hc, Wc, headc, bnf, false, nullptr);
+    float* Lg = Bf;
+    if ((rc = bs_conv(h, h->det1, A, headc, 0, Lg, lstride, B, Hc, Wc, s))) return rc;
+    if (fb) {
+        bs_stats(c, Lg, npx, lstride);          // channels 65..79 are not written: their statistics are discarded (padding)
+        bs_finalize(c, Lg, npx, lstride, 0, lstride, hb + 1);
+        bs_apply(c, Lg, Lg, B, Hc, Wc, lstride, false, false, nullptr);
+    }
+    prof_begin(h, "det.softmax_shuffle", 0.0, s);
+    launch_det_post(Lg, lstride, B, Hc, Wc, nullptr, logits, h->cfg.softmax_mode, s);
+    prof_end(h, s);
+    if (h->cfg.descriptor_head) {
+        // the descriptor head runs without a desc output too: its statistics are part of the forward's
+        float* raw = desc ? desc : Bf + npx * lstride;
+        if ((rc = bs_conv(h, h->desc1, A, headc, hc, raw, D, B, Hc, Wc, s))) return rc;
+        if (fb) {
+            bs_stats(c, raw, npx, D);
+            bs_finalize(c, raw, npx, D, 0, D, hb + 3);
+            bs_apply(c, raw, raw, B, Hc, Wc, D, false, false, nullptr);
+        }
+        if (desc && h->cfg.normalize_descriptors) {
+            prof_begin(h, "desc.l2norm", 0.0, s);
+            launch_desc_l2norm(desc, desc, npx, D, 1, s);
+            prof_end(h, s);
+        }
+    }
+    MP_HIP(hipGetLastError());
+    return MP_OK;
+}
+
 bool footprint(float size, double iou, NmsFootprint& fp)
 {
     // torchvision nms CPU kernel arithmetic (fp32) for two size x size boxes offset by (dy,dx):
@@ -1181,6 +1410,7 @@ void mp_destroy(mp_handle* h)
     if (h->ws4.p) (void)hipFree(h->ws4.p);
     if (h->split_ws.p) (void)hipFree(h->split_ws.p);
     if (h->vin_ws.p) (void)hipFree(h->vin_ws.p);
+    if (h->bs_ws.p) (void)hipFree(h->bs_ws.p);
     if (h->nms_state.p) (void)hipFree(h->nms_state.p);
     if (h->kp_scratch.p) (void)hipFree(h->kp_scratch.p);
     if (h->nms_total) (void)hipFree(h->nms_total);
@@ -1252,6 +1482,15 @@ int mp_load_weights(mp_handle* h, const mp_model_config* cfg, const mp_tensor* t
     if (cfg->descriptor_head &&
         (rc = build_conv(h, tm, h->desc1, "desc.conv1x1", {dsc1k}, {dsc1bn}, {cfg->descriptor_size}, hc, 1, false, false)))
         return rc;
+    if (cfg->batchnorm) {           // the heads' BatchNorm layers, state_dict order: detector (3x3, final), descriptor (3x3, final)
+        if ((rc = add_bn_layer(h, tm, det3bn, hc))) return rc;
+        if (cfg->final_batchnorm && (rc = add_bn_layer(h, tm, det1bn, 65))) return rc;
+        if (cfg->descriptor_head && (rc = add_bn_layer(h, tm, dsc3bn, hc))) return rc;
+        if (cfg->descriptor_head && cfg->final_batchnorm && (rc = add_bn_layer(h, tm, dsc1bn, cfg->descriptor_size))) return rc;
+        std::vector<float> ident(1024, 0.f);
+        for (int i = 0; i < 512; ++i) ident[i] = 1.f;
+        if ((rc = upload(h, ident, &h->bn_ident))) return rc;
+    }
     // strict=True semantics of load_state_dict: no unexpected keys
     for (auto& kv : tm.m)
         if (!tm.used.count(kv.first)) {
@@ -1286,6 +1525,61 @@ int mp_forward(mp_handle* h, const float* images, const unsigned char* is_optica
 {
     if (!h) return MP_EINVAL;
     return forward_checked(h, images, is_optical, B, H, W, prob, logits, desc, stream);
+}
+
+int mp_batch_stats_count(const mp_handle* h, int* count)
+{
+    if (!h || !count) return MP_EINVAL;
+    if (!h->loaded) return MP_ESTATE;
+    *count = (int)h->bn_layers.size();
+    return MP_OK;
+}
+
+int mp_batch_stats_layer(const mp_handle* h, int i, const char** name, int* channels)
+{
+    if (!h || !name || !channels) return MP_EINVAL;
+    if (!h->loaded) return MP_ESTATE;
+    if (i < 0 || i >= (int)h->bn_layers.size()) return MP_EINVAL;
+    *name = h->bn_layers[i].name.c_str();
+    *channels = h->bn_layers[i].channels;
+    return MP_OK;
+}
+
+int mp_forward_batch_stats(mp_handle* h, const float* images, const unsigned char* is_optical, int B, int H, int W, float* logits,
+                           float* desc, float* stats, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!h->loaded) return fail(h, MP_ESTATE, "mp_forward_batch_stats: no weights loaded (call mp_load_weights)");
+    if (h->cfg.mixed_precision)
+        return fail(h, MP_EINVAL, "mp_forward_batch_stats: mixed_precision models are not supported (BatchNorm with batch statistics "
+                                  "runs on the fp32 path only)");
+    if (!h->cfg.batchnorm || h->bn_layers.empty())
+        return fail(h, MP_EINVAL, "mp_forward_batch_stats: the model has no BatchNorm layers (batch statistics change nothing)");
+    if (!images || B <= 0 || H <= 0 || W <= 0) return fail(h, MP_EINVAL, "mp_forward_batch_stats: bad image tensor");
+    if (!logits) return fail(h, MP_EINVAL, "mp_forward_batch_stats: logits is required");
+    if ((H % 8) != 0 || (W % 8) != 0)
+        return fail(h, MP_EINVAL, "mp_forward_batch_stats: H and W must be divisible by 8 (got " + std::to_string(H) + "x" +
+                                      std::to_string(W) + ")");
+    if (desc && !h->cfg.descriptor_head) return fail(h, MP_EINVAL, "mp_forward_batch_stats: model has no descriptor head");
+    if (h->cfg.multispectral && !is_optical)
+        return fail(h, MP_EINVAL, "mp_forward_batch_stats: multispectral model needs is_optical");
+    if (h->cfg.multispectral && B > 512) return fail(h, MP_EINVAL, "mp_forward_batch_stats: multispectral B > 512 unsupported");
+    // torch.nn.functional.batch_norm(training=True) refuses a layer that sees one value per channel; the smallest layers are the
+    // last encoder layers and the heads at H/8 x W/8 (an encoder's share of a multispectral batch: its own images)
+    const long long cells = (long long)(H / 8) * (W / 8);
+    int nmin = B;
+    if (h->cfg.multispectral) {
+        int n[2] = {0, 0};
+        for (int b = 0; b < B; ++b) ++n[is_optical[b] ? 1 : 0];
+        for (int e = 0; e < 2; ++e)
+            if (n[e] > 0 && n[e] < nmin) nmin = n[e];
+    }
+    if (nmin * cells <= 1)
+        return fail(h, MP_EINVAL, "Expected more than 1 value per channel when training, got input size [" + std::to_string(nmin) +
+                                      ", " + std::to_string(h->bn_layers.back().channels) + ", 1, 1]");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MP_HIP(hipSetDevice(h->device));
+    return run_forward_batch_stats(h, images, is_optical, B, H, W, logits, desc, stats, s);
 }
 
 int mp_box_nms(mp_handle* h, const float* prob, const unsigned char* valid_mask, int B, int H, int W,

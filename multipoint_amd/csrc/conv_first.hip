@@ -19,8 +19,9 @@ __device__ __forceinline__ int reflect_clamp1(int v, int n)
     return v >= n ? n - 1 : v;
 }
 
-// C1 = output channels (64, or 32 for channel_version 1 / 2): C1/4 lanes share a pixel
-template <int C1>
+// C1 = output channels (64, or 32 for channel_version 1 / 2): C1/4 lanes share a pixel.  LINEAR: conv + bias only (the
+// batch-statistics forward of bn_first models: their BatchNorm needs the pre-ReLU output; scale / shift are not read)
+template <int C1, bool LINEAR = false>
 __global__ __launch_bounds__(256) void conv_first_kernel(const Conv1Params p)
 {
     __shared__ float tile[LH * LW];
@@ -86,8 +87,10 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const Conv1Params p)
 #pragma unroll
             for (int k = 0; k < 9; ++k) a = fmaf(x[k], w[k][e], a);
             a += bia[e];
-            if (p.bn_first) a = fmaxf(a * scl[e] + sft[e], 0.f);
-            else a = fmaxf(a, 0.f) * scl[e] + sft[e];
+            if constexpr (!LINEAR) {
+                if (p.bn_first) a = fmaxf(a * scl[e] + sft[e], 0.f);
+                else a = fmaxf(a, 0.f) * scl[e] + sft[e];
+            }
             o[e] = a;
         }
         const int oy = y0 + py, ox = x0 + px;
@@ -264,4 +267,13 @@ void launch_conv_first(const Conv1Params& p, hipStream_t s)
     }
     if (p.channels == 32) hipLaunchKernelGGL(conv_first_kernel<32>, dim3((unsigned)nblk), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(conv_first_kernel<64>, dim3((unsigned)nblk), dim3(256), 0, s, p);
+}
+
+void launch_conv_first_linear(const Conv1Params& p, hipStream_t s)
+{
+    const int tiles_x = (p.W + TW - 1) / TW, tiles_y = (p.H + TH - 1) / TH;
+    const long long nblk = (long long)p.B * tiles_x * tiles_y;
+    if (nblk <= 0) return;
+    if (p.channels == 32) hipLaunchKernelGGL((conv_first_kernel<32, true>), dim3((unsigned)nblk), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((conv_first_kernel<64, true>), dim3((unsigned)nblk), dim3(256), 0, s, p);
 }

@@ -93,12 +93,14 @@ __device__ __forceinline__ float max4_f(float a, float b, float c, float d)
     return r;
 }
 
-template <int TAPS, int MBW, bool POOL, bool FUSE1, bool BNF>
+// LINEAR: no activation at all (conv + bias only): the batch-statistics forward of bn_first models, whose BatchNorm needs the
+// pre-ReLU output (api.hip: run_forward_batch_stats); launched with the identity scale / shift
+template <int TAPS, int MBW, bool POOL, bool FUSE1, bool BNF, bool LINEAR = false>
 __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
 {
     using G = Geo<TAPS, MBW>;
     static_assert(!FUSE1 || TAPS == 9, "first-layer fusion is a 3x3 feature");
-    constexpr bool RELU = (TAPS == 9);      // the 1x1 head convolutions have no ReLU (p.relu == 0)
+    constexpr bool RELU = (TAPS == 9) && !LINEAR;      // the 1x1 head convolutions have no ReLU (p.relu == 0)
     constexpr int ITW = G::TW + 4, ITH = G::TH + 4;          // image patch of the fused first layer
     constexpr int FUSE_FLOATS = FUSE1 ? (ITH * ITW + 9 * 64 + 3 * 64) : 0;
     // SWAP: weights as the MFMA A operand -> lane = pixel, register quad = 4 consecutive channels
@@ -503,11 +505,11 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
 //   * the weight stream runs on from one item into the next, bias/scale/shift sit in LDS, and the staged registers
 //     are written to LDS BEFORE the epilogue, so the epilogue runs with them dead (no extra register pressure).
 // The inner step loop is the per-tile kernel's, unchanged.
-template <int TAPS, int MBW, bool POOL, bool BNF>
+template <int TAPS, int MBW, bool POOL, bool BNF, bool LINEAR = false>
 __global__ __launch_bounds__(256, 1) void conv_mfma_persist_kernel(const ConvParams p)
 {
     using G = Geo<TAPS, MBW>;
-    constexpr bool RELU = (TAPS == 9);
+    constexpr bool RELU = (TAPS == 9) && !LINEAR;
     constexpr bool SWAP = !POOL;
     // ONE workgroup per CU (a second MFMA stream per SIMD only gets in the first one's way, see docs/HISTORY.md A.5), which
     // leaves room for a double-buffered LDS image: chunk c+1 is written into the other buffer while chunk c is being
@@ -876,7 +878,7 @@ __global__ __launch_bounds__(256, 1) void conv_mfma_persist_kernel(const ConvPar
     }
 }
 
-template <int TAPS, int MBW, bool POOL, bool FUSE1>
+template <int TAPS, int MBW, bool POOL, bool FUSE1, bool LINEAR = false>
 int launch_t(const ConvParams& p, hipStream_t s)
 {
     long long ntiles;
@@ -898,18 +900,19 @@ int launch_t(const ConvParams& p, hipStream_t s)
             // tail not to matter
             if (p.persist && nblk >= (long long)p.ncu * p.persist) {
                 const unsigned grid = persistent_grid(nblk, p.ncu, p.xcd_shift);
-                if (p.bn_first)
-                    hipLaunchKernelGGL((conv_mfma_persist_kernel<TAPS, MBW, POOL, true>), dim3(grid), dim3(256), 0, s, pp);
+                // (LINEAR: one instantiation, the BatchNorm order does not matter without an activation)
+                if (p.bn_first && !LINEAR)
+                    hipLaunchKernelGGL((conv_mfma_persist_kernel<TAPS, MBW, POOL, !LINEAR, LINEAR>), dim3(grid), dim3(256), 0, s, pp);
                 else
-                    hipLaunchKernelGGL((conv_mfma_persist_kernel<TAPS, MBW, POOL, false>), dim3(grid), dim3(256), 0, s, pp);
+                    hipLaunchKernelGGL((conv_mfma_persist_kernel<TAPS, MBW, POOL, false, LINEAR>), dim3(grid), dim3(256), 0, s, pp);
                 return 0;
             }
         }
     }
-    if (p.bn_first)
-        hipLaunchKernelGGL((conv_mfma_kernel<TAPS, MBW, POOL, FUSE1, true>), dim3((unsigned)nblk), dim3(256), 0, s, pp);
+    if (p.bn_first && !LINEAR)
+        hipLaunchKernelGGL((conv_mfma_kernel<TAPS, MBW, POOL, FUSE1, !LINEAR, LINEAR>), dim3((unsigned)nblk), dim3(256), 0, s, pp);
     else
-        hipLaunchKernelGGL((conv_mfma_kernel<TAPS, MBW, POOL, FUSE1, false>), dim3((unsigned)nblk), dim3(256), 0, s, pp);
+        hipLaunchKernelGGL((conv_mfma_kernel<TAPS, MBW, POOL, FUSE1, false, LINEAR>), dim3((unsigned)nblk), dim3(256), 0, s, pp);
     return 0;
 }
 
@@ -926,4 +929,11 @@ int launch_conv_mfma(const ConvParams& p, int taps, int mbw, bool pool, bool fus
     if (mbw == 32) return pool ? launch_t<9, 32, true, false>(p, s) : launch_t<9, 32, false, false>(p, s);
     if (mbw == 16) return pool ? launch_t<9, 16, true, false>(p, s) : launch_t<9, 16, false, false>(p, s);
     return pool ? launch_t<9, 8, true, false>(p, s) : launch_t<9, 8, false, false>(p, s);
+}
+
+int launch_conv_mfma_linear(const ConvParams& p, int mbw, hipStream_t s)
+{
+    if (mbw == 32) return launch_t<9, 32, false, false, true>(p, s);
+    if (mbw == 16) return launch_t<9, 16, false, false, true>(p, s);
+    return launch_t<9, 8, false, false, true>(p, s);
 }

@@ -99,6 +99,10 @@ struct Conv1Params {
 // can address (items * max divisor >= 2^32): nothing is launched and the caller reports MP_EINVAL
 int launch_conv_mfma(const ConvParams& p, int taps, int mbw, bool pool, bool fuse1, hipStream_t s);
 void launch_conv_first(const Conv1Params& p, hipStream_t s);
+// the batch-statistics forward's un-pooled 3x3 convolution of bn_first models, and their first block: conv + bias, no activation
+// (the BatchNorm that follows needs the pre-ReLU values)
+int launch_conv_mfma_linear(const ConvParams& p, int mbw, hipStream_t s);
+void launch_conv_first_linear(const Conv1Params& p, hipStream_t s);
 // Winograd F(4x4,3x3) (conv_wino43.hip): p.wpack = pack_wino43_weights() output; supports() says whether the shape is covered
 // Interpolation points of the F(4x4,3x3) transforms: {0, +-a, +-b, inf}.  The textbook choice a = 1, b = 2 (Lavin & Gray) has
 // integer transform matrices but the worst conditioning of the family: its fp32 error is ~20x that of a direct fp32
@@ -348,3 +352,18 @@ void launch_descriptor_loss(const float* desc1, const float* desc2, const float*
                             const unsigned char* valid1, const unsigned char* valid2, int B, int H, int W, int D,
                             float s_max, float pos_margin, float neg_margin, double lambda_d, int use_mask,
                             void* workspace, double* out, float* warped, hipStream_t s);
+
+// BatchNorm2d with the statistics of the batch (batchnorm_stats.hip).  Activations NHWC fp32 [npx][cstride], C (a multiple of 4,
+// 8..1024) channels per pixel; part: double [bn_stats_parts(npx, C)][2][C] scratch (at most MP_BN_MAX_PARTS slots)
+#define MP_BN_MAX_PARTS 2048
+int bn_stats_parts(long long npx, int C);
+// images [*][H][W] -> out [nb][H][W]: image list[b] to place b (H * W a multiple of 4)
+void launch_bn_gather(const float* img, const int* list, int nb, int H, int W, float* out, hipStream_t s);
+void launch_bn_stats(const float* x, long long npx, int C, int cstride, double* part, hipStream_t s);
+// channels [c0, c0 + nc) of the launch's C: scale / shift [C] (indexed by the tensor channel), gamma / beta / mean_out / var_out
+// indexed from c0; channels c0 + c with c >= c_real are padding (scale = shift = 0).  mean_out / var_out may be NULL
+void launch_bn_finalize(const double* part, long long npx, int C, const float* x, int c0, int nc, int c_real, const float* gamma,
+                        const float* beta, float* scale, float* shift, float* mean_out, float* var_out, hipStream_t s);
+// x [B][H][W][C] -> y [B][H or H/2][W or W/2][C], image b to out_list[b] (NULL: b); x == y allowed without pool and list
+void launch_bn_apply(const float* x, float* y, int B, int H, int W, int C, const float* scale, const float* shift, bool relu,
+                     bool pool, const int* out_list, hipStream_t s);

@@ -53,6 +53,9 @@ class MultiPoint:
         self._uploaded = False
         self._fwd_event = None       # last forward's completion, for callers that alternate streams
         self._fwd_stream = None
+        self._batch_statistics = False   # set_batch_statistics: the training-mode forward (BatchNorm with batch statistics)
+        self._bn_layout = None           # [(state_dict prefix, channels)] of the uploaded model's BatchNorm layers
+        self._last_stats = None          # (device fp32 statistics array, names of the layers the last such forward wrote)
         if self.config['verbose']:
             n = sum(int(np.prod(s)) for k, s, d in self.state_dict_spec() if d == torch.float32
                     and not k.endswith(('running_mean', 'running_var')))
@@ -208,6 +211,71 @@ class MultiPoint:
             raise ValueError('set_force_return_logits: The input value needs to be a bool')
         self.config['force_return_logits'] = value
 
+    def set_batch_statistics(self, value):
+        """True: `forward` runs the reference's TRAINING-mode forward (train.py never calls net.eval(), so its validation loop
+        runs this): every BatchNorm normalises with the statistics of the batch, and the result is the reference's
+        {'prob': None, 'logits': (B,65,Hc,Wc), 'desc': (B,D,Hc,Wc)}.  Forward only: `training` stays False, train() still
+        raises, and the running statistics are not updated (last_batch_statistics() returns what torch would blend into them).
+        fp32 models with BatchNorm only."""
+        if not isinstance(value, bool):
+            raise ValueError('set_batch_statistics: The input value needs to be a bool')
+        self._batch_statistics = value
+
+    def batch_statistics_layout(self):
+        """[(state_dict prefix, channels)] of the model's BatchNorm layers, state_dict order (mp_batch_stats_layer)."""
+        if self._bn_layout is None:
+            h = self._handle
+            if h is None or not self._uploaded:
+                raise RuntimeError('MultiPoint: move the model to the GPU with weights loaded first')
+            n = ctypes.c_int(0)
+            h.check(h.lib.mp_batch_stats_count(h.ptr, ctypes.byref(n)))
+            layout = []
+            for i in range(n.value):
+                name, ch = ctypes.c_char_p(), ctypes.c_int(0)
+                h.check(h.lib.mp_batch_stats_layer(h.ptr, i, ctypes.byref(name), ctypes.byref(ch)))
+                layout.append((name.value.decode(), ch.value))
+            self._bn_layout = layout
+        return self._bn_layout
+
+    def last_batch_statistics(self):
+        """{state_dict prefix: (mean, unbiased variance)} of the BatchNorm layers in the last batch-statistics forward, as
+        device tensors -- what torch blends into running_mean / running_var (momentum 0.1).  A multispectral encoder that
+        received no images has no entry.  The model's running statistics are not modified."""
+        if self._last_stats is None:
+            raise RuntimeError('last_batch_statistics: no forward with set_batch_statistics(True) has run yet')
+        buf, written = self._last_stats
+        out = collections.OrderedDict()
+        off = 0
+        for name, ch in self.batch_statistics_layout():
+            if name in written:
+                out[name] = (buf[off:off + ch], buf[off + ch:off + 2 * ch])
+            off += 2 * ch
+        return out
+
+    def _check_batch_statistics(self, B, H, W, is_opt):
+        """The refusals of mp_forward_batch_stats, raised before any launch."""
+        if self.config['mixed_precision']:
+            raise NotImplementedError('set_batch_statistics: BatchNorm with batch statistics runs on the fp32 path only '
+                                      '(mixed_precision models are not supported)')
+        if not self._abi_extra['batchnorm']:
+            raise NotImplementedError('set_batch_statistics: %s has no BatchNorm layers' % type(self).__name__)
+        counts = [B]
+        if is_opt is not None:
+            n_opt = int(is_opt.sum())
+            counts = [n for n in (n_opt, B - n_opt) if n > 0]
+        n = min(counts) * (H // 8) * (W // 8)
+        if n <= 1:
+            raise ValueError('Expected more than 1 value per channel when training, got input size [%d, %d, 1, 1]'
+                             % (min(counts), self.config['descriptor_size'] if self.config['final_batchnorm'] and
+                                self.config['descriptor_head'] else 65))
+
+    def _encoder_prefixes(self, is_opt, B):
+        """State_dict prefixes of the encoders a forward runs."""
+        if not self.config['multispectral']:
+            return ('encoder.',)
+        n_opt = int(is_opt.sum())
+        return tuple(p for p, n in (('encoder_thermal.', B - n_opt), ('encoder_optical.', n_opt)) if n > 0)
+
     # extra mp_model_config fields of this model class (include/multipoint_hip.h)
     _abi_extra = {'batchnorm': 1, 'key_layout': 0, 'softmax_mode': 0}
 
@@ -231,6 +299,8 @@ class MultiPoint:
         h = self._handle
         h.check(h.lib.mp_load_weights(h.ptr, ctypes.byref(cfg), tens, len(arr)))
         self._uploaded = True
+        self._bn_layout = None
+        self._last_stats = None
 
     # -- forward (MultiPoint.py:99-135) -----------------------------------------------------------
     def forward(self, data):
@@ -252,6 +322,9 @@ class MultiPoint:
             flags = data['is_optical'][:, 0].to('cpu', torch.uint8).contiguous()
             is_opt = flags
         Hc, Wc = H // 8, W // 8
+        if self._batch_statistics:
+            self._check_batch_statistics(B, H, W, is_opt)
+            return self._forward_batch_statistics(image, is_opt, B, H, W)
         want_logits = bool(self.config['force_return_logits'])
         prob = None if want_logits else torch.empty((B, 1, H, W), dtype=torch.float32, device=self.device)
         logits = torch.empty((B, 65, Hc, Wc), dtype=torch.float32, device=self.device) if want_logits else None
@@ -281,6 +354,36 @@ class MultiPoint:
         return out
 
     __call__ = forward
+
+    def _forward_batch_statistics(self, image, is_opt, B, H, W):
+        Hc, Wc = H // 8, W // 8
+        logits = torch.empty((B, 65, Hc, Wc), dtype=torch.float32, device=self.device)
+        desc_cl = None
+        if self.config['descriptor_head']:
+            desc_cl = torch.empty((B, Hc, Wc, self.config['descriptor_size']), dtype=torch.float32, device=self.device)
+        layout = self.batch_statistics_layout()
+        stats = torch.empty((2 * sum(ch for _, ch in layout),), dtype=torch.float32, device=self.device)
+        h = self._handle
+        cur = torch.cuda.current_stream(self.device)
+        if self._fwd_event is not None and self._fwd_stream != cur:
+            cur.wait_event(self._fwd_event)
+        with torch.cuda.device(self.device):
+            h.check(h.lib.mp_forward_batch_stats(h.ptr, _lib.ptr(image),
+                                                 ctypes.c_void_p(is_opt.data_ptr()) if is_opt is not None else None,
+                                                 B, H, W, _lib.ptr(logits), _lib.ptr(desc_cl), _lib.ptr(stats),
+                                                 _lib.stream_ptr(self.device)))
+        if self._fwd_stream != cur:
+            self._fwd_event = torch.cuda.Event()
+        if self._fwd_event is not None:
+            self._fwd_event.record(cur)
+        self._fwd_stream = cur
+        ran = self._encoder_prefixes(is_opt, B)
+        self._last_stats = (stats, frozenset(n for n, _ in layout if not n.startswith('encoder') or
+                                             any(n.startswith(p) for p in ran)))
+        out = {'prob': None, 'logits': logits}
+        if desc_cl is not None:
+            out['desc'] = desc_cl.permute(0, 3, 1, 2)
+        return out
 
     # profiling hook used by bench.py (per-launch hipEvent timing)
     def profile(self, enable=True):

@@ -42,6 +42,8 @@ class SuperPointMagicLeap(MultiPoint):
         """SuperPointMagicLeap.forward (:31-66): {'logits' (B,65,H/8,W/8), 'desc' (B,256,H/8,W/8), 'prob' (B,1,H,W)}."""
         if self._state is None:
             raise RuntimeError('SuperPointMagicLeap has no weights: call load_state_dict() or init_random_weights()')
+        if self._batch_statistics:
+            self._check_batch_statistics(0, 0, 0, None)          # no BatchNorm: refused
         image = data['image']
         if self.device is None:
             self.to(image.device)
