@@ -15,6 +15,11 @@ GPU: encoder + detector/descriptor heads (fp32; 3x3 layers as Winograd F(4x4,3x3
 `--workload c5` switches to BASELINE.json configs[4]'s per-GPU share instead: 8 pairs of 1024x1280 images on the
 fp16 MFMA path (`mixed_precision`), top-k 2000 (a secondary line; the default run is the headline metric).
 
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` and prints its line: the headline and what the timed
+steps themselves measured (per-step and per-layer hipEvent times, the dominant launch's roofline).  `--full` adds everything that
+takes work of its own after the timed region: one untimed step with stage timings and the gathered per-pair records
+(`pair_metrics`), and on N = 1 the CPU baseline, the parity legs against the oracle and the `secondary` rates.
+
 Prints ONE JSON line on rank 0 (see README / DESIGN.md section "Measurement").
 """
 import argparse
@@ -111,8 +116,8 @@ def workload_name(P, world, height, width, topk, c5=False, forward_only=False):
 
 
 def runs_extra_legs(world, use_dist, no_cpu_baseline=False, no_secondary=False, forward_only=False, host_input=False, c5=False):
-    """(cpu_baseline + parity, secondary): the legs rank 0 runs AFTER the timed region, on N = 1 only -- on N > 1 the job is the ranks
-    and nothing else (the driver's clock around an N-GPU run must not include a CPU baseline on rank 0's host cores)."""
+    """(cpu_baseline + parity, secondary): the legs rank 0 of a --full run adds AFTER the timed region, on N = 1 only -- on N > 1 the
+    job is the ranks and nothing else (the driver's clock around an N-GPU run must not include a CPU baseline on rank 0's host cores)."""
     cpu = world == 1 and not no_cpu_baseline
     sec = cpu and not use_dist and not no_secondary and not forward_only and not host_input and not c5
     return cpu, sec
@@ -489,7 +494,10 @@ def main():
     ap.add_argument('--steps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--pairs-per-gpu', type=int, default=PAIRS_PER_GPU)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region also run what takes work of its own: the untimed stage-timing step and the gathered '
+                         'per-pair records (pair_metrics), and on N = 1 the CPU baseline, the parity legs and the `secondary` rates')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline / parity legs (nor `secondary`)')
     ap.add_argument('--forward-only', action='store_true', help='configs[1]: encoder+heads only')
     ap.add_argument('--ordered-caller', action='store_true',
                     help='A/B: order the caller\'s stream behind each forward (PairPipeline.run_interleaved\'s default; the bench never '
@@ -499,7 +507,7 @@ def main():
                          'host memory on a copy stream, double-buffered, overlapping the previous step (PCIe-inclusive rate)')
     ap.add_argument('--nms-rounds', type=int, default=8, help='fixed asynchronous NMS rounds of the throughput entry (developer A/B)')
     ap.add_argument('--no-secondary', action='store_true',
-                    help='skip the `secondary` object of the plain N = 1 line (c5 / direct / batchsize-1 rates, ~15 s; also skipped with '
+                    help='skip the `secondary` object of the --full N = 1 line (c5 / direct / batchsize-1 rates, ~15 s; also skipped with '
                          '--no-cpu-baseline, --forward-only, --host-input, --workload c5 and under torchrun)')
     ap.add_argument('--workload', choices=['c3', 'c5'], default='c3',
                     help='c3 (default, headline): 480x640 fp32 top-k 1000; c5: 1024x1280 fp16 MFMA path top-k 2000')
@@ -616,12 +624,13 @@ def main():
     per_rank_ms = [round(v / args.steps * 1e3, 3) for v in gather_scalar(dt_local, device)]
     n_ranks_seen = ranks_seen(device) if use_dist else 1
 
-    # per-pair metric records, gathered over RCCL (the only collective of the path)
     metrics = None
     tie_flagged = None
     if not args.forward_only:
         pipe.check_converged(device)
         tie_flagged = pipe.tie_flagged      # images of the timed steps whose top-k cut fell inside a plateau of tied scores (reported only)
+    # --full: per-pair metric records, gathered over RCCL (the only collective of the path)
+    if args.full and not args.forward_only:
         # one more step, OUTSIDE the timed region, with the stages bracketed by timing events: t_forward / t_nms / t_match of the
         # record are this rank's batch times with nothing else in flight
         fence()
@@ -776,7 +785,8 @@ def main():
                         'gathered_records': int(metrics.shape[0]) if metrics is not None else None,
                         'record_fields': list(RECORD_FIELDS),
                         'rank0_cpu_affinity': ('%d CPUs: %d-%d' % (len(cpu_set), cpu_set[0], cpu_set[-1])) if cpu_set else None}
-    want_cpu, want_secondary = runs_extra_legs(world, use_dist, args.no_cpu_baseline, args.no_secondary, args.forward_only, args.host_input, c5)
+    want_cpu, want_secondary = runs_extra_legs(world, use_dist, args.no_cpu_baseline, args.no_secondary, args.forward_only, args.host_input,
+                                               c5) if args.full else (False, False)
     if want_cpu:
         if orig_affinity is not None:
             os.sched_setaffinity(0, orig_affinity)                # the CPU figure is the host's, not one NUMA node's

@@ -1,7 +1,7 @@
 """GPU (MI355X, ONE device): what of the multi-GPU path (reference analogue export_keypoints.py:52-53) can be
 tested without a second GPU.
 
-  * the rank program itself under torchrun with RCCL: `python -m torch.distributed.run --nproc-per-node 1 bench.py --gpus 1`
+  * the rank program itself under torchrun with RCCL: `python -m torch.distributed.run --nproc-per-node 1 bench.py --gpus 1 --full`
     -- init_process_group('nccl'), barrier, all_reduce(MAX) of the step time and the metric all_gather on device tensors;
   * world size 2 EMULATED sequentially on the one device: shard 0 and shard 1 of 8 pairs (dist.shard_pairs) run as two
     independent single-rank pipelines; their `pair_metric_records`, concatenated the way `gather_pair_metrics` orders them
@@ -25,7 +25,7 @@ def test_bench_rank_program_under_torchrun_rccl():
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
            '--master-port', '29533', os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
-           '--pairs-per-gpu', '4', '--no-cpu-baseline']
+           '--pairs-per-gpu', '4', '--full', '--no-cpu-baseline']
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith('{')][-1]
@@ -44,7 +44,8 @@ def test_bench_rank_program_under_torchrun_rccl():
 
 def test_value_under_torchrun_equals_the_plain_line():
     """N = 1 under torchrun (RCCL initialised, barrier + all-reduce around the timed loop) must report the same rate as the plain
-    N = 1 run within the run-to-run noise: the distributed plumbing costs the timed region nothing."""
+    N = 1 run within the run-to-run noise: the distributed plumbing costs the timed region nothing.  The plain run is also a plain
+    LINE (no --full): nothing after its timed region, only the torchrun one gathers the per-pair records."""
     env = dict(os.environ)
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     common = ['--gpus', '1', '--steps', '12', '--warmup', '4', '--pairs-per-gpu', '16', '--no-cpu-baseline']
@@ -52,11 +53,12 @@ def test_value_under_torchrun_equals_the_plain_line():
                            timeout=600, cwd=ROOT)
     assert plain.returncode == 0, plain.stderr[-2000:]
     tr = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr',
-                         '127.0.0.1', '--master-port', '29534', os.path.join(ROOT, 'bench.py')] + common, env=env,
+                         '127.0.0.1', '--master-port', '29534', os.path.join(ROOT, 'bench.py')] + common + ['--full'], env=env,
                         capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert tr.returncode == 0, tr.stderr[-2000:]
     a = json.loads([l for l in plain.stdout.splitlines() if l.startswith('{')][-1])
     b = json.loads([l for l in tr.stdout.splitlines() if l.startswith('{')][-1])
+    assert 'pair_metrics' not in a and a['cpu_baseline'] is None and 'parity' not in a and 'secondary' not in a
     assert 'ranks' not in a and b['ranks']['ranks_seen'] == 1 and b['ranks']['gathered_records'] == b['config']['pairs_per_gpu']
     assert b['ranks']['record_fields'] == ['pair_id', 'n_kp_a', 'n_kp_b', 'n_matches', 't_forward', 't_nms', 't_match', 'desc_err']
     assert b['pair_metrics']['t_forward_ms'] > 0 and b['pair_metrics']['t_nms_ms'] > 0 and b['pair_metrics']['t_match_ms'] > 0

@@ -11,12 +11,12 @@ mkdir -p "$R"
 bash tools/collect_profiles.sh "$R" > "$R.log" 2>&1
 # the PMC summary first: the bench lines below read roofline.traffic from profiles/${TAG}_pmc_hbm_traffic*.json
 python3 tools/summarize_profiles.py "$R" "$TAG" > "$R/summary.log" 2>&1
-python3 bench.py > "$R/bench_n1.json" 2> "$R/bench_n1.err"
-python3 bench.py --workload c5 > "$R/bench_c5.json" 2> "$R/bench_c5.err"
-python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --no-cpu-baseline > "$R/bench_rccl.json" 2> "$R/bench_rccl.err"
-MP_DEBUG=wino43_gen=2 python3 bench.py --no-cpu-baseline > "$R/bench_gen2.json" 2> "$R/bench_gen2.err"
-MP_DEBUG=no_winograd python3 bench.py --no-cpu-baseline --steps 10 > "$R/bench_direct.json" 2> "$R/bench_direct.err"
-MP_DEBUG=f16_no_res python3 bench.py --workload c5 --no-cpu-baseline > "$R/bench_c5_stream.json" 2> "$R/bench_c5_stream.err"
+python3 bench.py --full > "$R/bench_n1.json" 2> "$R/bench_n1.err"
+python3 bench.py --full --workload c5 > "$R/bench_c5.json" 2> "$R/bench_c5.err"
+python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --full --no-cpu-baseline > "$R/bench_rccl.json" 2> "$R/bench_rccl.err"
+MP_DEBUG=wino43_gen=2 python3 bench.py --full --no-cpu-baseline > "$R/bench_gen2.json" 2> "$R/bench_gen2.err"
+MP_DEBUG=no_winograd python3 bench.py --full --no-cpu-baseline --steps 10 > "$R/bench_direct.json" 2> "$R/bench_direct.err"
+MP_DEBUG=f16_no_res python3 bench.py --full --workload c5 --no-cpu-baseline > "$R/bench_c5_stream.json" 2> "$R/bench_c5_stream.err"
 { python3 tools/latency.py; MP_DEBUG=splitk_max=1 python3 tools/latency.py | sed -e 's/^/MP_DEBUG=splitk_max=1  /'; python3 tools/bench_layers.py 2 480 640; echo "== bench_layers 2 240 320"; python3 tools/bench_layers.py 2 240 320; } 2>&1 | grep -v amdgpu.ids > "$R/latency.txt"
 bash tools/pmc_f16.sh "$R/sq_c5" > "$R/sq_c5.txt" 2>&1
 bash tools/pmc_f16.sh "$R/sq_c3" 64 > "$R/sq_c3.txt" 2>&1
