@@ -42,9 +42,14 @@ def build_parser():
     parser.add_argument('-s', '--seed', default=0, type=int,
                         help='Seed of the random generators, reset before every checkpoint so that each sees the same '
                              'augmentation and label noise')
-    parser.add_argument('--no-photometric', action='store_true',
-                        help='Validate without the photometric augmentation the config asks for (the dataset refuses it: '
-                             'it is a training-time feature)')
+    photometric = parser.add_mutually_exclusive_group()
+    photometric.add_argument('--no-photometric', action='store_true',
+                             help='Validate without the photometric augmentation the config asks for')
+    photometric.add_argument('--photometric', choices=('host', 'device'), default=None,
+                             help="Validate with the config's photometric augmentation (on the GPU), its per-pixel noise "
+                                  "drawn as train.py draws it ('host': np.random fields, the reference's stream) or on "
+                                  "the GPU from one np.random key per field ('device'); sets "
+                                  'dataset.augmentation.photometric.noise')
     parser.add_argument('--batch-statistics', action='store_true',
                         help="Run the forward as train.py's validation loop does: BatchNorm with the statistics of each "
                              'batch (training mode, forward only) instead of the running statistics')
@@ -114,11 +119,15 @@ def main(argv=None):
             config['model'] = yaml.load(f, Loader=yaml.FullLoader)['model']
     photometric = config['dataset'].get('augmentation', {}).get('photometric', {})
     if photometric.get('enable', False):
-        if not args.no_photometric:
-            raise SystemExit('error: the config enables photometric augmentation (dataset.augmentation.photometric), which '
-                             'this implementation does not provide (a training-time feature the dataset refuses); rerun '
-                             'with --no-photometric to validate without it')
-        photometric['enable'] = False
+        if args.no_photometric:
+            photometric['enable'] = False
+        elif args.photometric is not None:
+            photometric['noise'] = args.photometric
+        elif photometric.get('noise') is None:
+            raise SystemExit('error: the config enables photometric augmentation (dataset.augmentation.photometric) but '
+                             "does not say where its per-pixel noise is drawn; rerun with --photometric host (train.py's "
+                             'np.random stream) or --photometric device (drawn on the GPU), or with --no-photometric to '
+                             'validate without it')
     if not torch.cuda.is_available():
         raise SystemExit('error: compute_validation_loss runs on an MI355X only (no CPU fallback)')
     device = torch.device('cuda:0')

@@ -344,6 +344,70 @@ int mp_descriptor_loss(mp_handle* h, const float* desc1, const float* desc2, int
                        int use_mask, void* workspace, long long workspace_bytes, double* out, float* warped,
                        void* stream);
 
+/* ---- photometric augmentation (multipoint/datasets/augmentation/augmentation.py:8-22 and
+ * photometric_augmentation.py:13-77) ----
+ * n images fp32 [n][H][W] (any H, W), one plan per image drawn on the host (multipoint_amd.datasets.augmentation.
+ * draw_photometric_plan: the reference's random / np.random draws in the reference's order).  A plan lists its primitives
+ * in the order they run; every op carries its own scalar draw.  Plans and ellipses are HOST memory, copied into the
+ * workspace on `stream` (the entry points synchronise `stream` once, after that copy, so the caller may free them on
+ * return); the per-pixel noise fields are device memory.
+ *   MP_PHOTO_GAUSSIAN_NOISE  additive_gaussian_noise (:13-17): x = clip(float(double(x) + n), 0, 1), n = normal[field] (host
+ *                            noise) or value * N(0, 1) from a counter-based hash of (key, pixel) (device noise)
+ *   MP_PHOTO_GAUSSIAN_ADD    the in-place `image += noise` of :15 alone, without the clip (an aliased pair's shared input)
+ *   MP_PHOTO_SPECKLE         additive_speckle_noise (:19-24): u = uniform[field] or hash(key, pixel); x = 0 where
+ *                            u < value, x = 1 where u > 1.0 - value (compared in double)
+ *   MP_PHOTO_BRIGHTNESS      random_brightness (:26-28): clip(x + float(value), 0, 1)
+ *   MP_PHOTO_CONTRAST        random_contrast (:30-34): m = image.mean() (numpy's float32 sum: pairwise sums of chunks of 8192
+ *                            pixels accumulated in order), clip((x - m) * float(value) + m, 0, 1)
+ *   MP_PHOTO_SHADE           additive_shade (:36-54): mask = cv2.ellipse fill (thickness -1) of ellipses
+ *                            [ellipse_offset, +ellipse_count) (x, y, ax, ay, angle in integer degrees), cv2.GaussianBlur(mask,
+ *                            (ksize, ksize), 0) with BORDER_REFLECT_101; clip(x * (1 - float(value) * mask), 0, 1)
+ *   MP_PHOTO_MOTION_BLUR     motion_blur (:56-77): cv2.filter2D with the ksize non-zero taps `taps` along the line of `mode`
+ *                            (0 'h', 1 'v', 2 'diag_down', 3 'diag_up') in row-major order, BORDER_REFLECT_101
+ * Every elementwise step is rounded separately (no fused multiply-add), as numpy computes it. */
+#define MP_PHOTO_MAX_OPS 16
+#define MP_PHOTO_MAX_TAPS 11
+#define MP_PHOTO_MAX_BLUR 801
+enum { MP_PHOTO_GAUSSIAN_NOISE = 0, MP_PHOTO_SPECKLE = 1, MP_PHOTO_BRIGHTNESS = 2, MP_PHOTO_CONTRAST = 3, MP_PHOTO_SHADE = 4,
+       MP_PHOTO_MOTION_BLUR = 5, MP_PHOTO_GAUSSIAN_ADD = 6 };
+
+typedef struct mp_photometric_op {
+    int kind;                       /* MP_PHOTO_* */
+    int ksize;                      /* shade: blur kernel size (odd, <= MP_PHOTO_MAX_BLUR); motion blur: taps (odd, <= 11) */
+    int mode;                       /* motion blur line */
+    int ellipse_offset, ellipse_count;   /* shade: rows of the ellipse table */
+    int field;                      /* host noise: plane of the normal / uniform field */
+    double value;                   /* stddev | prob | delta | strength | transparency */
+    unsigned long long key;         /* device noise: key of the counter-based generator */
+    float taps[MP_PHOTO_MAX_TAPS];  /* motion blur weights (float32, row-major order of the non-zero kernel entries) */
+    int pad;
+} mp_photometric_op;
+
+typedef struct mp_photometric_plan {
+    int n_ops;                      /* 0 .. MP_PHOTO_MAX_OPS */
+    int noise_device;               /* 0: normal / uniform fields given, 1: drawn on the device from op.key */
+    mp_photometric_op op[MP_PHOTO_MAX_OPS];
+} mp_photometric_plan;
+
+/* mp_photometric_workspace_bytes: bytes of the caller-owned device workspace of mp_photometric_augment /
+ * mp_photometric_shade_mask for n images of H x W with n_ellipses rows in the ellipse table. */
+int mp_photometric_workspace_bytes(int n, int H, int W, int n_ellipses, long long* bytes);
+
+/* replaces photometric_augmentation (augmentation.py:8-22) for a batch: out[i] = the plan's primitives applied to in[i] in
+ * order.  in == out is allowed.  plans host [n]; ellipses host int32 [n_ellipses][5]; normal / uniform device float64
+ * [n_normal][H][W] / [n_uniform][H][W], the reference's np.random.normal / np.random.uniform fields (NULL with 0 planes
+ * when every plan draws its noise on the device). */
+int mp_photometric_augment(mp_handle* h, const float* in, float* out, int n, int H, int W, const mp_photometric_plan* plans,
+                           const int* ellipses, int n_ellipses, const double* normal, int n_normal, const double* uniform,
+                           int n_uniform, void* workspace, long long workspace_bytes, void* stream);
+
+/* the shade mask of additive_shade (photometric_augmentation.py:39-51) of op `op_index` of every plan: the filled ellipses
+ * (blurred 0) or the mask after cv2.GaussianBlur (blurred 1); zeros for a plan whose op there is not a shade.
+ * out fp32 [n][H][W]. */
+int mp_photometric_shade_mask(mp_handle* h, int n, int H, int W, const mp_photometric_plan* plans, const int* ellipses,
+                              int n_ellipses, int op_index, int blurred, float* out, void* workspace,
+                              long long workspace_bytes, void* stream);
+
 /* per-launch timing of mp_forward with hipEvents on the caller's stream (bench.py roofline leg).
  * mp_profile_read synchronises; names[i] points to static strings. */
 int mp_profile_enable(mp_handle* h, int enable);

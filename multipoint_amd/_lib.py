@@ -40,6 +40,19 @@ class Tensor(ctypes.Structure):
     _fields_ = [('name', ctypes.c_char_p), ('data', c_void_p), ('numel', c_ll)]
 
 
+MP_PHOTO_MAX_OPS, MP_PHOTO_MAX_TAPS, MP_PHOTO_MAX_BLUR = 16, 11, 801
+
+
+class PhotometricOp(ctypes.Structure):
+    _fields_ = [('kind', c_int), ('ksize', c_int), ('mode', c_int), ('ellipse_offset', c_int), ('ellipse_count', c_int),
+                ('field', c_int), ('value', ctypes.c_double), ('key', ctypes.c_ulonglong),
+                ('taps', c_float * MP_PHOTO_MAX_TAPS), ('pad', c_int)]
+
+
+class PhotometricPlan(ctypes.Structure):
+    _fields_ = [('n_ops', c_int), ('noise_device', c_int), ('op', PhotometricOp * MP_PHOTO_MAX_OPS)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/multipoint_hip.h
 SIGNATURES = {
     'mp_create': (c_int, [ctypes.POINTER(c_void_p), c_int]),
@@ -95,6 +108,11 @@ SIGNATURES = {
     'mp_descriptor_loss': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_int, c_void_p, c_ll,
                                    c_void_p, c_void_p, c_void_p]),
+    'mp_photometric_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
+    'mp_photometric_augment': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(PhotometricPlan),
+                                       c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_ll, c_void_p]),
+    'mp_photometric_shade_mask': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(PhotometricPlan), c_void_p, c_int,
+                                          c_int, c_int, c_void_p, c_void_p, c_ll, c_void_p]),
     'mp_profile_enable': (c_int, [c_void_p, c_int]),
     'mp_profile_read': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_float),
                                 ctypes.POINTER(ctypes.c_double), c_int, ctypes.POINTER(c_int)]),

@@ -2034,4 +2034,95 @@ int mp_descriptor_loss(mp_handle* h, const float* desc1, const float* desc2, int
     return MP_OK;
 }
 
+int mp_photometric_workspace_bytes(int n, int H, int W, int n_ellipses, long long* bytes)
+{
+    if (!bytes || n <= 0 || n > 65535 || H <= 0 || W <= 0 || n_ellipses < 0 || (long long)n * H * W > (1LL << 34))
+        return MP_EINVAL;
+    *bytes = (long long)photometric_workspace_bytes(n, H, W, n_ellipses);
+    return MP_OK;
+}
+
+// the plans' ops, ellipse ranges, kernel sizes and noise planes against the buffers they index
+static int photometric_check(mp_handle* h, const char* fn, int n, int H, int W, const mp_photometric_plan* plans,
+                             const int* ellipses, int n_ellipses, int n_normal, int n_uniform, void* workspace,
+                             long long workspace_bytes)
+{
+    const std::string f(fn);
+    if (n <= 0 || n > 65535 || H <= 0 || W <= 0 || H > 8192 || (long long)n * H * W > (1LL << 34))
+        return fail(h, MP_EINVAL, f + ": need 0 < n <= 65535, 0 < H <= 8192, W > 0");
+    if (!plans) return fail(h, MP_EINVAL, f + ": NULL plans");
+    if (n_ellipses < 0 || (n_ellipses > 0 && !ellipses)) return fail(h, MP_EINVAL, f + ": bad ellipse table");
+    for (int i = 0; i < n; ++i) {
+        const mp_photometric_plan& p = plans[i];
+        if (p.n_ops < 0 || p.n_ops > MP_PHOTO_MAX_OPS) return fail(h, MP_EINVAL, f + ": n_ops outside 0.." + std::to_string(MP_PHOTO_MAX_OPS));
+        for (int s = 0; s < p.n_ops; ++s) {
+            const mp_photometric_op& o = p.op[s];
+            const std::string at = f + ": plan " + std::to_string(i) + " op " + std::to_string(s);
+            switch (o.kind) {
+            case MP_PHOTO_GAUSSIAN_NOISE:
+            case MP_PHOTO_GAUSSIAN_ADD:
+                if (!p.noise_device && (o.field < 0 || o.field >= n_normal)) return fail(h, MP_EINVAL, at + ": normal field out of range");
+                break;
+            case MP_PHOTO_SPECKLE:
+                if (!p.noise_device && (o.field < 0 || o.field >= n_uniform)) return fail(h, MP_EINVAL, at + ": uniform field out of range");
+                break;
+            case MP_PHOTO_BRIGHTNESS:
+            case MP_PHOTO_CONTRAST:
+                break;
+            case MP_PHOTO_SHADE:
+                if (o.ksize < 1 || o.ksize > MP_PHOTO_MAX_BLUR || (o.ksize & 1) == 0)
+                    return fail(h, MP_EINVAL, at + ": blur size must be odd and <= " + std::to_string(MP_PHOTO_MAX_BLUR));
+                if (o.ellipse_count < 0 || o.ellipse_offset < 0 || (long long)o.ellipse_offset + o.ellipse_count > n_ellipses)
+                    return fail(h, MP_EINVAL, at + ": ellipses outside the table");
+                break;
+            case MP_PHOTO_MOTION_BLUR:
+                if (o.ksize < 1 || o.ksize > MP_PHOTO_MAX_TAPS || (o.ksize & 1) == 0 || o.mode < 0 || o.mode > 3)
+                    return fail(h, MP_EINVAL, at + ": motion blur needs an odd size <= 11 and mode 0..3");
+                break;
+            default:
+                return fail(h, MP_EINVAL, at + ": unknown primitive " + std::to_string(o.kind));
+            }
+        }
+    }
+    if (photometric_lds_bytes(plans, n, H, W) > 65536) return fail(h, MP_EINVAL, f + ": frame too wide for the blur size");
+    if (!workspace || workspace_bytes < (long long)photometric_workspace_bytes(n, H, W, n_ellipses))
+        return fail(h, MP_EINVAL, f + ": workspace smaller than mp_photometric_workspace_bytes");
+    return MP_OK;
+}
+
+int mp_photometric_augment(mp_handle* h, const float* in, float* out, int n, int H, int W, const mp_photometric_plan* plans,
+                           const int* ellipses, int n_ellipses, const double* normal, int n_normal, const double* uniform,
+                           int n_uniform, void* workspace, long long workspace_bytes, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!in || !out) return fail(h, MP_EINVAL, "mp_photometric_augment: NULL tensor");
+    if (n_normal < 0 || n_uniform < 0 || (n_normal && !normal) || (n_uniform && !uniform))
+        return fail(h, MP_EINVAL, "mp_photometric_augment: bad noise fields");
+    const int rc = photometric_check(h, "mp_photometric_augment", n, H, W, plans, ellipses, n_ellipses, n_normal, n_uniform,
+                                     workspace, workspace_bytes);
+    if (rc != MP_OK) return rc;
+    MP_HIP(hipSetDevice(h->device));
+    launch_photometric(in, out, n, H, W, plans, ellipses, n_ellipses, normal, uniform, workspace,
+                       static_cast<hipStream_t>(stream));
+    MP_HIP(hipGetLastError());
+    return MP_OK;
+}
+
+int mp_photometric_shade_mask(mp_handle* h, int n, int H, int W, const mp_photometric_plan* plans, const int* ellipses,
+                              int n_ellipses, int op_index, int blurred, float* out, void* workspace,
+                              long long workspace_bytes, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!out) return fail(h, MP_EINVAL, "mp_photometric_shade_mask: NULL tensor");
+    if (op_index < 0 || op_index >= MP_PHOTO_MAX_OPS) return fail(h, MP_EINVAL, "mp_photometric_shade_mask: op_index out of range");
+    const int rc = photometric_check(h, "mp_photometric_shade_mask", n, H, W, plans, ellipses, n_ellipses, 1 << 30, 1 << 30,
+                                     workspace, workspace_bytes);
+    if (rc != MP_OK) return rc;
+    MP_HIP(hipSetDevice(h->device));
+    launch_photometric_shade_mask(n, H, W, plans, ellipses, n_ellipses, op_index, blurred, out, workspace,
+                                  static_cast<hipStream_t>(stream));
+    MP_HIP(hipGetLastError());
+    return MP_OK;
+}
+
 }  // extern "C"

@@ -367,3 +367,16 @@ void launch_bn_finalize(const double* part, long long npx, int C, const float* x
 // x [B][H][W][C] -> y [B][H or H/2][W or W/2][C], image b to out_list[b] (NULL: b); x == y allowed without pool and list
 void launch_bn_apply(const float* x, float* y, int B, int H, int W, int C, const float* scale, const float* shift, bool relu,
                      bool pool, const int* out_list, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
+// photometric augmentation (photometric.hip).  plans / ellipses are host arrays (copied into the workspace on the
+// stream); `workspace` holds photometric_workspace_bytes(n, H, W, n_ellipses) bytes.
+// ---------------------------------------------------------------------------------------------
+struct mp_photometric_plan;
+size_t photometric_workspace_bytes(int n, int H, int W, int n_ellipses);
+size_t photometric_lds_bytes(const mp_photometric_plan* plans, int n, int H, int W);
+void launch_photometric(const float* in, float* out, int n, int H, int W, const mp_photometric_plan* plans,
+                        const int* ellipses, int n_ellipses, const double* normal, const double* uniform, void* workspace,
+                        hipStream_t s);
+void launch_photometric_shade_mask(int n, int H, int W, const mp_photometric_plan* plans, const int* ellipses,
+                                   int n_ellipses, int op_index, int blurred, float* out, void* workspace, hipStream_t s);

@@ -2,7 +2,9 @@
 holds 'optical', 'thermal' (and 'thermal_raw') images, an optional second file holds the exported 'keypoints' labels
 per group; samples are emitted with the reference's dict schema, including the homographic augmentation that the
 prediction configs enable (ground-truth 'homography' + 'valid_mask', :209-227) -- its pixel work runs on the GPU
-(datasets/augmentation.py).  Photometric augmentation is training-only and rejected.
+(datasets/augmentation.py).  The photometric augmentation of the training / validation configs runs there too, in the
+reference's place (before the homographic warp, optical then thermal); it needs augmentation.photometric.noise set to
+'host' or 'device' (augmentation.photometric_noise_mode).
 
 h5py is imported lazily; a file name ending in '.npz' selects a flat numpy archive with the same layout
 ('<sample>/optical', '<sample>/thermal', '<sample>/keypoints'), which needs no h5py."""
@@ -60,9 +62,10 @@ def generate_keypoint_map(keypoints, image_shape):
 
 
 def check_augmentation_config(config, who):
-    if config['augmentation']['photometric']['enable']:
-        raise NotImplementedError(who + ': photometric augmentation is a training-time feature outside the accelerated '
-                                  'inference path; set augmentation.photometric.enable to false')
+    """An enabled photometric block must name its noise mode (NotImplementedError when absent, ValueError when unknown)."""
+    pcfg = config['augmentation']['photometric']
+    if pcfg['enable']:
+        augmentation.photometric_noise_mode(pcfg, who)
 
 
 def build_sample(optical, thermal, keypoints, config, name):
@@ -70,13 +73,17 @@ def build_sample(optical, thermal, keypoints, config, name):
     Draws from `random` / `np.random` in the reference's order."""
     h, w = thermal.shape[:2]
     hcfg = config['augmentation']['homographic']
+    pcfg = config['augmentation']['photometric']
     out = {}
 
     def entry(image, valid_mask, is_optical, kp):
-        if torch.is_tensor(image):                      # warped on the GPU
-            image, valid_mask = image.cpu()[None], valid_mask.cpu()[None]
+        if torch.is_tensor(image):                      # augmented / warped on the GPU
+            image = image.cpu()[None]
         else:
             image = torch.from_numpy(np.expand_dims(image, 0).astype(np.float32))
+        if torch.is_tensor(valid_mask):
+            valid_mask = valid_mask.cpu()[None]
+        else:
             valid_mask = torch.from_numpy(np.expand_dims(valid_mask, 0).astype(bool))
         e = {'image': image.to(torch.float32), 'valid_mask': valid_mask.to(torch.bool),
              'is_optical': torch.BoolTensor([is_optical])}
@@ -87,6 +94,8 @@ def build_sample(optical, thermal, keypoints, config, name):
     if config['single_image']:
         is_optical = bool(random.randint(0, 1))
         image = optical if is_optical else thermal
+        if pcfg['enable']:
+            image = augmentation.photometric_augmentation(_gpu_image(image), **pcfg)
         if hcfg['enable']:
             image, keypoints, valid_mask = augmentation.homographic_augmentation(_gpu_image(image), keypoints, **hcfg)
         else:
@@ -100,6 +109,16 @@ def build_sample(optical, thermal, keypoints, config, name):
                 optical, optical_is_optical = tmp_thermal, False
             if bool(random.randint(0, 1)):
                 thermal, thermal_is_optical = tmp_optical, True
+        if pcfg['enable']:
+            # :178-193; after a single flip optical and thermal are ONE array, and the optical call's in-place noise
+            # reaches the thermal call's input
+            plan_optical = augmentation.draw_photometric_plan(optical.shape, pcfg)
+            plan_thermal = augmentation.draw_photometric_plan(thermal.shape, pcfg)
+            if optical is thermal:
+                optical, thermal = augmentation.apply_photometric_plans(_gpu_image(optical), [plan_optical, plan_thermal])
+            else:
+                optical, thermal = augmentation.photometric_augmentation_batch(
+                    torch.stack([_gpu_image(optical), _gpu_image(thermal)])[:, None], [plan_optical, plan_thermal])[:, 0]
         hom_optical = hom_thermal = None
         if hcfg['enable']:
             # randomly pick one image to warp (:209-227)
@@ -126,6 +145,8 @@ def build_sample(optical, thermal, keypoints, config, name):
 
 
 def _gpu_image(image):
+    if torch.is_tensor(image):
+        return image
     return torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).cuda()
 
 

@@ -48,7 +48,8 @@ class SyntheticPairs(Dataset):
             raise IndexError(index)
         H, W = self.config['height'], self.config['width']
         optical, thermal = self.make_pair(self.config['seed'], index, H, W)
-        if self.config['augmentation']['homographic']['enable'] or self.config['random_pairs']:
+        aug = self.config['augmentation']
+        if aug['homographic']['enable'] or aug['photometric']['enable'] or self.config['random_pairs']:
             return build_sample(optical[0], thermal[0], None, self.config, self.get_name(index))
         ones = torch.ones((1, H, W), dtype=torch.bool)
         if self.config['single_image']:
