@@ -210,7 +210,7 @@ __global__ __launch_bounds__(256) void head_tail_f16_kernel(const HeadTailParams
             }
             float s = 0.f;
 #pragma unroll
-            for (int i = 0; i < 32; ++i) { v[i] = __expf(v[i] - m); s += v[i]; }
+            for (int i = 0; i < 32; ++i) { v[i] = __expf(v[i] - m); s += v[i]; }      // (error of __expf: head_tail.hip)
             s += __shfl_xor(s, 32);
             s += __expf(d - m);
             if (p.softmax_mode == 1) s += 0.00001f;
