@@ -1,7 +1,7 @@
 // BatchNorm2d with the statistics of the current batch (training-mode forward, forward only): the reference's train.py never
 // calls net.eval(), so its validation loop normalises every BatchNorm with the mean and biased variance of the batch
 // (torch.nn.functional.batch_norm(training=True), eps 1e-5) and blends the batch mean / unbiased variance into the running
-// statistics.  The convolutions run with an identity epilogue (api.hip: run_forward_batch_stats); these kernels do the rest.
+// statistics.  The convolutions run with an identity epilogue (forward.hip: run_forward_batch_stats); these kernels do the rest.
 //
 // bn_gather_kernel      the images routed to one encoder of a multispectral model, gathered into a contiguous batch (its
 //                       statistics cover those images only, MultiPoint.py:117-122)

@@ -94,7 +94,7 @@ __device__ __forceinline__ float max4_f(float a, float b, float c, float d)
 }
 
 // LINEAR: no activation at all (conv + bias only): the batch-statistics forward of bn_first models, whose BatchNorm needs the
-// pre-ReLU output (api.hip: run_forward_batch_stats); launched with the identity scale / shift
+// pre-ReLU output (forward.hip: run_forward_batch_stats); launched with the identity scale / shift
 template <int TAPS, int MBW, bool POOL, bool FUSE1, bool BNF, bool LINEAR = false>
 __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
 {

@@ -113,7 +113,7 @@ void launch_r(const ConvParams& q, hipStream_t s)
 
 }  // namespace
 
-// p: the layer's parameters as api.hip built them (REAL slices, ks_shift > 0); gen: 1 conv_wino43.hip, 2 conv_wino43b.hip.  The item
+// p: the layer's parameters as forward.hip built them (REAL slices, ks_shift > 0); gen: 1 conv_wino43.hip, 2 conv_wino43b.hip.  The item
 // shape is the one the convolution launchers pick (fewer items; 16 x 32 pixels on a tie)
 int launch_split_reduce(const ConvParams& p, int gen, bool pool, hipStream_t s)
 {

@@ -20,7 +20,7 @@
 //    apart), both double-buffered; raw 10 KiB (18 x 34 patch x 4 channels, one 16-byte granule per pixel = LDS-DMA order) in a
 //    ring of THREE; + a per-wave scratch for the input transform: 158 KiB.
 //  * Input layout: NHWC, or channel-quad-planar [B][C/4][H][W][4] when the producer is conv_first.hip or a pooled launch of
-//    this kernel (api.hip decides per tensor): a unit's patch rows are then contiguous, 9-11 cache lines per DMA instruction
+//    this kernel (forward.hip decides per tensor): a unit's patch rows are then contiguous, 9-11 cache lines per DMA instruction
 //    instead of 64.
 //  * DMA order: the memory pipe returns in order across the CU, so a weight DMA (L2 hit) queued behind a patch DMA (HBM miss)
 //    of ANY wave comes back at HBM latency.  The 5 weight DMAs of unit n+2 therefore go out right behind the barrier of unit
@@ -508,7 +508,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
             else pd_ = __builtin_amdgcn_mfma_f32_4x4x1f32(pw_[(k - 1) >> 2][(k - 1) & 3], x[k - 1], pd_, 0, 0, 0);
         } else {
             // ReLU only: the block's BatchNorm was folded at load time -- into p.w1 / p.b1 for conv -> BN -> ReLU models, into this
-            // layer's U and bias otherwise (api.hip build_encoder) -- which takes two packed multiply-adds and two LDS reads per
+            // layer's U and bias otherwise (model_load.hip build_encoder) -- which takes two packed multiply-adds and two LDS reads per
             // 64 pixels and unit out of the unit body
             const f32x4 v = {relu_q(pd_[0]), relu_q(pd_[1]), relu_q(pd_[2]), relu_q(pd_[3])};
             *reinterpret_cast<lds_f32x4_wptr>(raw_lds + wbuf + pg_w[j]) = v;
@@ -1119,7 +1119,7 @@ bool conv_wino43_supports(const ConvParams& p)
            p.in_cstride % 4 == 0 && p.in_coff % 4 == 0 && p.out_cstride % 4 == 0 && p.out_coff % 4 == 0;
 }
 
-// work items of a launch (the larger of the two item shapes' counts is never chosen): what api.hip sizes the split by
+// work items of a launch (the larger of the two item shapes' counts is never chosen): what forward.hip sizes the split by
 // floats of p.vglobal a pre-transformed launch of this layer needs: tile blocks x (cin / 4) units x 18 KiB
 long long conv_wino43_vglobal_floats(const ConvParams& p)
 {
@@ -1133,14 +1133,14 @@ long long conv_wino43_items(const ConvParams& p)
     return (long long)p.B * std::min(wide, tall) * p.nslices;
 }
 
-// p.wpack must point at the F(4x4,3x3) weights packed by pack_wino43_weights() (api.hip).  fuse_first: the input is the
+// p.wpack must point at the F(4x4,3x3) weights packed by pack_wino43_weights() (model_load.hip).  fuse_first: the input is the
 // first encoder block of p.img (p.w1 / b1 / s1 / t1, 64 channels), evaluated inside the kernel; the layer must be the pooled
 // 64 -> 64 one (enc.conv2).  p.ks_shift > 0 (small launches; (cin / 4) >> ks_shift even and >= 4): the input
 // channels run as 2^ks_shift items per (tile block, slice) that meet in p.split_scratch
 int launch_conv_wino43(const ConvParams& p, bool pool, hipStream_t s, bool fuse_first)
 {
     if (fuse_first) return pool && p.cin == 64 ? launch_q<true, 8, true>(p, s) : 2;          // 2: shape not covered
-    if (p.vglobal) {       // pre-transformed input (api.hip: un-pooled layers with >= 4 output slices; cin a multiple of 16, NHWC)
+    if (p.vglobal) {       // pre-transformed input (forward.hip: un-pooled layers with >= 4 output slices; cin a multiple of 16, NHWC)
         if (pool || p.ks_shift > 0 || p.cin % 16 != 0 || p.in_planar || p.cin > 256 || 256 % (p.cin / 2) != 0 || (p.cin / 2) < 8) return 2;
         const long long wide = (long long)((p.W + 31) / 32) * ((p.H + 15) / 16), tall = (long long)((p.W + 15) / 16) * ((p.H + 31) / 32);
         return tall < wide ? launch_vin<4>(p, s) : launch_vin<8>(p, s);

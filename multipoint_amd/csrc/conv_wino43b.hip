@@ -727,7 +727,7 @@ bool conv_wino43b_supports(const ConvParams& p)
 
 int launch_conv_wino43b(const ConvParams& p, bool pool, hipStream_t s)
 {
-    if (p.ks_shift > 0) {        // api.hip: single-pair launches with fewer items than CUs
+    if (p.ks_shift > 0) {        // forward.hip: single-pair launches with fewer items than CUs
         const int ncs = (p.cin / UC4) >> p.ks_shift;
         if (ncs < 2 || (ncs & 1) || (ncs << p.ks_shift) * UC4 != p.cin || !p.split_scratch) return 2;
         const int rc = p.pad_zero ? (pool ? launch_shape<true, true, true>(p, s) : launch_shape<false, true, true>(p, s))

@@ -19,7 +19,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 struct ConvParams {
     const float* in;      // [B][H][W][in_cstride], channels [in_coff, in_coff+cin) are read
     float* out;           // [B][Ho][Wo][out_cstride], channels [out_coff, out_coff+cout) written
-    const float* wpack;   // packed weights, see pack_conv_weights() in api.hip
+    const float* wpack;   // packed weights, see pack_mfma_weights() in model_load.hip
     const float* bias;    // [nslices*64] conv bias (zero padded)
     const float* scale;   // [nslices*64] BN scale  s = gamma / sqrt(var + eps)
     const float* shift;   // [nslices*64] BN shift  t = beta - mean * s
@@ -42,7 +42,7 @@ struct ConvParams {
     // conv_wino43.hip only: channel-quad-planar tensors [B][C/4][H][W][4] instead of NHWC (a unit of 4 input channels is then
     // contiguous row by row: its patch DMA touches ~10 cache lines per instruction instead of 64)
     int in_planar, out_planar;
-    // machine shape (api.hip: mp_create derives it from the device, run_conv copies it into every launch): compute units of
+    // machine shape (api.hip: mp_create derives it from the device, forward.hip: run_conv copies it into every launch): compute units of
     // the device = workgroups of a one-per-CU persistent grid, and log2 of its XCD count (workgroup b runs on XCD b mod nxcd;
     // each XCD has its own L2, so a persistent workgroup walks a contiguous share of ITS XCD's items)
     int ncu, xcd_shift;
@@ -110,7 +110,7 @@ void launch_conv_first_linear(const Conv1Params& p, hipStream_t s);
 // fraction (a^2 = 9/16, b^2 = 9/4, a^2 b^2 = 81/64, a^2 + b^2 = 45/16), keeps the even/odd structure (12 multiply-adds per
 // 1-D input transform, as before) and cuts the maximum error 3.4x and the rms error 2x (CPU emulation over a grid of dyadic
 // (a, b): the minimum is broad around a b ~ 1, b / a ~ 2; docs/HISTORY.md section 4).  Shared by the kernel and the host-side
-// weight transform U = G g G^T (api.hip).
+// weight transform U = G g G^T (model_load.hip).
 #ifndef MP_W43_A
 #define MP_W43_A 0.75
 #endif
@@ -203,9 +203,9 @@ void launch_conv_first_f16(const Conv1ParamsH& p, hipStream_t s);
 struct HeadTailParams {
     const float* x;             // [npx][xstride] output of the 3x3 head convolution: detector channels [0,K), descriptor [K,2K)
     int xstride, K;             // K = head channels (multiple of 32)
-    const float *wdet, *bdet, *sdet, *tdet;       // detector 1x1: pack_conv_weights(taps = 1) fragments, bias / BN scale / shift.
+    const float *wdet, *bdet, *sdet, *tdet;       // detector 1x1: pack_mfma_weights(taps = 1) fragments, bias / BN scale / shift.
                                                   // The kernel reads entries [0, 96) of bdet / sdet / tdet (three 32-channel blocks for the 65
-                                                  // detector channels) and [0, D) of the descriptor arrays: api.hip's build_conv pads every
+                                                  // detector channels) and [0, D) of the descriptor arrays: model_load.hip's build_conv pads every
                                                   // per-channel array to nslices * 64 >= 128 entries (zeros / identity BatchNorm)
     const float *wdesc, *bdesc, *sdesc, *tdesc;   // descriptor 1x1 (unused when desc == nullptr)
     int D;                      // descriptor size (64, 128 or 256)

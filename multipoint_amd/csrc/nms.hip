@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void nms_round_kernel(float* __restrict__ work
                                                        const float* __restrict__ prob, const uint8_t* __restrict__ mask,
                                                        float min_prob, int Ws, float tie_eps, int* __restrict__ tie_pairs)
 {
-    // Ws (INIT only): row stride = true width of prob / mask; the work map's W is Ws rounded up to a multiple of 4 (api.hip), the
+    // Ws (INIT only): row stride = true width of prob / mask; the work map's W is Ws rounded up to a multiple of 4 (post_api.hip), the
     // columns beyond Ws are never candidates.
     // tie_pairs (footprint tie guard, optional): per image, the candidates that die to a kept neighbour whose score is within
     // tie_eps of their own and to no kept neighbour with a clear margin -- decisions the convolution's rounding noise could flip

@@ -33,7 +33,7 @@ MACHINE = ['ncu=32,nxcd=1', 'ncu=200,nxcd=8']
 ROUTINGS = [('direct', DIRECT[0], e) for e in DIRECT[1] + MACHINE] + [('f16', F16[0], e) for e in F16[1] + MACHINE]
 
 # (B, H, W, config): B = 1 and B > 2, partial tiles, a 1x1 deepest frame (zero padding: reflection needs 2 pixels), and frames on
-# which pick_mbw (api.hip) chooses each tile width 32 / 16 / 8 at the full-resolution layers (test_shapes_cover_every_tile_width)
+# which pick_mbw (forward.hip) chooses each tile width 32 / 16 / 8 at the full-resolution layers (test_shapes_cover_every_tile_width)
 SHAPES = [(2, 16, 16, 'shipped'), (1, 8, 8, 'zero_pad'), (3, 72, 104, 'shipped'), (5, 40, 264, 'shipped'), (1, 240, 320, 'shipped'),
           (2, 480, 640, 'shipped'), (2, 24, 2048, 'shipped'), (2, 64, 72, 'shipped'), (3, 48, 80, 'bn_first')]
 
@@ -42,7 +42,7 @@ _STATS = {}
 
 
 def pick_mbw(H, W):
-    """api.hip pick_mbw: the tile width (tiles mbw x 256/mbw) with the least padded area, 32 on ties."""
+    """forward.hip pick_mbw: the tile width (tiles mbw x 256/mbw) with the least padded area, 32 on ties."""
     best, arg = None, 32
     for mbw in (32, 16, 8):
         th = 256 // mbw

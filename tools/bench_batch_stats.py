@@ -40,7 +40,7 @@ def timed(fn, reps, warmup=3):
 
 def bn_pass_bytes(cfg, B, H, W):
     """Bytes read + written by bn.stats and bn.apply over the forward's BatchNorm layers (the shipped layer walk of
-    api.hip: run_forward_batch_stats; channels padded to 32, the detector's 65 channels stored with a row of 80)."""
+    forward.hip: run_forward_batch_stats; channels padded to 32, the detector's 65 channels stored with a row of 80)."""
     stage = {0: [64, 64, 128, 128], 1: [32, 64, 96, 128], 2: [8, 16, 32, 64]}[cfg.get('channel_version', 0)]
     pad = [(c + 31) // 32 * 32 for c in stage]
     layers = []                     # (pixels, channels, pooled after)
