@@ -313,7 +313,7 @@ int mp_ha_finalize(mp_handle* h, const float* prob, const float* count, int B, i
 int mp_gaussian_filter(mp_handle* h, const float* in, int B, int H, int W, int ksize, const float* weights, float* out,
                        void* stream);
 
-/* ---- SuperPointLoss, forward-only evaluation (multipoint/utils/losses.py:8-272) ----
+/* ---- SuperPointLoss, evaluation and gradients (multipoint/utils/losses.py:8-272) ----
  * Shapes: logits fp32 [B][65][Hc][Wc] (mp_forward with force_return_logits); keypoint / valid maps uint8 [B][H][W],
  * nonzero = keypoint / valid pixel; desc1 / desc2 channels-last fp32 [B][Hc][Wc][D] like mp_forward's descriptors;
  * homographies fp32 [B][9] row-major, acting on (x, y, 1).  H == 8 Hc and W == 8 Wc are required (MP_EINVAL otherwise, as
@@ -343,6 +343,39 @@ int mp_descriptor_loss(mp_handle* h, const float* desc1, const float* desc2, int
                        int H, int W, float threshold, float positive_margin, float negative_margin, float lambda_d,
                        int use_mask, void* workspace, long long workspace_bytes, double* out, float* warped,
                        void* stream);
+
+/* Gradients of the loss (the backward of the above).  Both entry points are stateless: they take the
+ * forward's inputs again plus `forward_out`, the out array the matching forward call wrote, and recompute what they need
+ * (labels, cell validity, warped centres).  `coef` is device memory (double), the upstream coefficients, so that a
+ * backward never synchronises with the host.  With the upstream gradients g_T, g_det1, g_det2, g_desc, g_pos, g_neg of
+ * the batch means total, detector_loss1 / 2, descriptor_loss, positive_dist and negative_dist (lambda = the weight of the
+ * descriptor loss in total):  gamma_k = g_T + g_det_k,  alpha = lambda g_T + g_desc + g_pos,  beta = lambda g_T + g_desc
+ * + g_neg.  h(x) = 1 for x > 0, 1/2 for x == 0 (torch's maximum backward at a tie), 0 for x < 0; every tie is decided on
+ * the kernel's own fp32 value (the dot in the forward's k order).  An image whose count / normalisation is 0 gets NaN
+ * gradients (as the reference's division); other images are unaffected.  Results are bit-identical from run to run.
+ *
+ * mp_detector_loss_backward: coef[0] = gamma; grad_logits fp32 [B][65][Hc][Wc] =
+ *   gamma valid / (B count_b) (softmax(z) - onehot(label))                       (cross entropy; label as the forward's)
+ *   gamma valid / (B count_b) p (gp - sum_c p_c gp_c), gp_c = (p_c - y_c) / max(p_c (1 - p_c), 1e-12)   (BCE, p = softmax)
+ * with count_b = forward_out[b][1] (the forward's double [B][2]).  noise / noise_seed as given to the forward. */
+int mp_detector_loss_backward(mp_handle* h, const float* logits, int B, int Hc, int Wc, const unsigned char* keypoints,
+                              const unsigned char* valid_mask, int H, int W, int use_cross_entropy, const float* noise,
+                              unsigned long long noise_seed, const double* forward_out, const double* coef,
+                              void* workspace, long long workspace_bytes, float* grad_logits, void* stream);
+
+/* mp_descriptor_loss_backward: coef[0] = alpha, coef[1] = beta; norm_b = forward_out[b][3] (the forward's double [B][4]).
+ * With dot[i][j] = desc2[i] . desc1[j], w[i][j] = valid2[i] valid1[j] (1 without the mask), c = w corr(i, j):
+ *   G[i][j] = (-alpha lambda_d c h(positive_margin - dot) + beta (w - c) h(dot - negative_margin)) / (B norm_b)
+ *   grad1[j] = sum_i G[i][j] desc2[i],   grad2[i] = sum_j G[i][j] desc1[j]
+ * grad1 / grad2 channels-last fp32 [B][Hc][Wc][D] like the descriptors; each cell's gradient is written once (no
+ * atomics, nothing of size (Hc Wc)^2).  One of grad1 / grad2 may be NULL: that side is not computed (both NULL: MP_EINVAL).
+ * The workspace is mp_loss_workspace_bytes as for the forward. */
+int mp_descriptor_loss_backward(mp_handle* h, const float* desc1, const float* desc2, int B, int Hc, int Wc, int D,
+                                const float* hom1, const float* hom2, const unsigned char* valid1,
+                                const unsigned char* valid2, int H, int W, float threshold, float positive_margin,
+                                float negative_margin, float lambda_d, int use_mask, const double* forward_out,
+                                const double* coef, void* workspace, long long workspace_bytes, float* grad1,
+                                float* grad2, void* stream);
 
 /* ---- photometric augmentation (multipoint/datasets/augmentation/augmentation.py:8-22 and
  * photometric_augmentation.py:13-77) ----

@@ -108,6 +108,12 @@ SIGNATURES = {
     'mp_descriptor_loss': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_int, c_void_p, c_ll,
                                    c_void_p, c_void_p, c_void_p]),
+    'mp_detector_loss_backward': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                                          c_int, c_void_p, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p, c_ll, c_void_p,
+                                          c_void_p]),
+    'mp_descriptor_loss_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_int,
+                                            c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p]),
     'mp_photometric_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
     'mp_photometric_augment': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(PhotometricPlan),
                                        c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_ll, c_void_p]),

@@ -365,6 +365,227 @@ __global__ __launch_bounds__(RED) void descriptor_reduce_kernel(const float* __r
     }
 }
 
+// ---- backward (the gradient of the loss; every kernel recomputes what it needs from the forward's inputs) ----
+
+// One thread per cell: dlogits[c] = gamma * valid / (B * count_b) * d(loss)/d(logit_c).  CE: softmax - onehot(label), the
+// label as the forward picks it; BCE: torch's binary_cross_entropy backward gp_c = (p_c - y_c) / max(p_c (1 - p_c), 1e-12)
+// chained through the softmax, p (gp - sum_c p_c gp_c).  A zero count gives NaN (0 * inf), as the reference's autograd.
+__global__ __launch_bounds__(RED) void detector_loss_backward_kernel(const float* __restrict__ logits,
+                                                                    const unsigned char* __restrict__ kp,
+                                                                    const unsigned char* __restrict__ valid,
+                                                                    const float* __restrict__ noise,
+                                                                    unsigned long long seed, int B, int H, int W,
+                                                                    int use_ce, const double* __restrict__ fwd_out,
+                                                                    const double* __restrict__ coef,
+                                                                    float* __restrict__ grad)
+{
+    const int Hc = H >> 3, Wc = W >> 3, N = Hc * Wc;
+    const int b = blockIdx.y;
+    const int n = blockIdx.x * RED + threadIdx.x;
+    if (n >= N) return;
+    const int hc = n / Wc, wc = n - hc * Wc;
+    const long long pix0 = ((long long)b * H + hc * 8) * W + wc * 8;
+    bool vcell = true;
+    unsigned long long bits = 0;
+#pragma unroll
+    for (int dy = 0; dy < 8; ++dy) {
+        const unsigned long long kr = *reinterpret_cast<const unsigned long long*>(kp + pix0 + (long long)dy * W);
+        const unsigned long long vr = valid ? *reinterpret_cast<const unsigned long long*>(valid + pix0 + (long long)dy * W)
+                                            : ~0ull;
+#pragma unroll
+        for (int dx = 0; dx < 8; ++dx) {
+            bits |= (unsigned long long)(((kr >> (8 * dx)) & 0xff) != 0) << (8 * dy + dx);
+            vcell = vcell && (((vr >> (8 * dx)) & 0xff) != 0);
+        }
+    }
+    const float scale = (float)(coef[0] / ((double)B * fwd_out[2 * b + 1])) * (vcell ? 1.f : 0.f);
+    const float* lg = logits + (long long)b * 65 * N + n;
+    float* gd = grad + (long long)b * 65 * N + n;
+    float m = -__builtin_inff();
+    for (int c = 0; c < 65; ++c) m = fmaxf(m, lg[(long long)c * N]);
+    float se = 0.f;
+    for (int c = 0; c < 65; ++c) se += expf(lg[(long long)c * N] - m);
+    if (use_ce) {
+        int label = 64;
+        float best = 2.f;
+        for (unsigned long long rest = bits; rest; rest &= rest - 1) {
+            const int c = __builtin_ctzll(rest);
+            const float u = noise ? noise[(((long long)b * 64 + c) * Hc + hc) * Wc + wc] : hash_noise(seed, b, c, hc, wc, Hc, Wc);
+            const float v = __fadd_rn(3.f, u);
+            if (v > best) { best = v; label = c; }
+        }
+        for (int c = 0; c < 65; ++c) {
+            const float p = expf(lg[(long long)c * N] - m) / se;
+            gd[(long long)c * N] = scale * (c == label ? p - 1.f : p);
+        }
+    } else {
+        const int k = __builtin_popcountll(bits);
+        const float dust = k ? 0.f : 1.f;
+        const float S = (float)k + dust;
+        auto gp = [&](int c, float p) __attribute__((always_inline)) {
+            const float y = (c < 64 ? (float)((bits >> c) & 1) : dust) / S;
+            return (p - y) / fmaxf(p * (1.f - p), 1e-12f);
+        };
+        float dot = 0.f;
+        for (int c = 0; c < 65; ++c) {
+            const float p = expf(lg[(long long)c * N] - m) / se;
+            dot = fmaf(p, gp(c, p), dot);
+        }
+        for (int c = 0; c < 65; ++c) {
+            const float p = expf(lg[(long long)c * N] - m) / se;
+            gd[(long long)c * N] = scale * (p * (gp(c, p) - dot));
+        }
+    }
+}
+
+// torch's maximum(0, x) backward: 1 above, 1/2 at the tie, 0 below
+__device__ __forceinline__ float hinge_grad(float x) { return x > 0.f ? 1.f : (x == 0.f ? 0.5f : 0.f); }
+
+// dX_own[j] = sum_i G[i][j] X_other[i] for one side ("own"), G[i][j] = (-alpha lambda_d c h(m_p - dot) + beta (w - c)
+// h(dot - m_n)) / (B norm_b).  G is symmetric under swapping the sides with their cell data, so one template serves
+// both gradients.  A workgroup (4 waves) owns OWN = 128 own cells, 32 per wave, and walks the other side in tiles of TI
+// rows in a fixed order:
+//   dot   v_mfma_f32_32x32x2_f32 with the other side's rows as A and the wave's own cells (held in registers) as B: the
+//         accumulator's register r of lane l is other row 8 (r >> 2) + 4 (l >> 5) + (r & 3), own cell l & 31; the k
+//         mapping is the forward tile kernel's.  Every hinge and tie is decided on this kernel's own fp32 dot; in the
+//         launch with side 1 as own the operand roles are also the forward's, in the other launch A and B are exchanged
+//   G     formed in place in the dot registers
+//   dX    += G^T X_other, summed over the accumulator's row index: MFMA r takes dot register r as A, and the B operand of
+//         lane half h is the other side's row 8 (r >> 2) + 4h + (r & 3), channels d0 + (l & 31); no LDS transpose.
+//         Accumulator register r of block db is own cell 8 (r >> 2) + 4h + (r & 3), channel 32 db + (l & 31).
+// Each own cell's gradient is written once: no atomics, bit-identical from run to run.
+template <int D>
+struct GradShape {
+    static constexpr int TI = D <= 128 ? 64 : 32;          // other-side rows per tile (2 or 1 dot blocks of 32)
+};
+
+template <int D>
+__global__ __launch_bounds__(RED) void desc_loss_grad_kernel(const float* __restrict__ x_own,
+                                                            const float* __restrict__ x_other,
+                                                            const float4* __restrict__ cells_own,
+                                                            const float4* __restrict__ cells_other, int B, int N,
+                                                            float s_max, float pos_margin, float neg_margin,
+                                                            float lambda_d, int use_mask,
+                                                            const double* __restrict__ fwd_out,
+                                                            const double* __restrict__ coef,
+                                                            float* __restrict__ grad_own)
+{
+    constexpr int TI = GradShape<D>::TI, NT = TI / 32, RS = D + 4, NDB = D / 32;
+    __shared__ __attribute__((aligned(16))) float Xs[TI * RS];
+    __shared__ float4 oinfo[TI];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 31, half = lane >> 5;
+    const int b = blockIdx.y;
+    const int j = blockIdx.x * (4 * 32) + wave * 32 + li;            // this lane's own cell
+    const float* Xo = x_other + (long long)b * N * D;
+    const float4* co = cells_other + (long long)b * N;
+
+    // per-image coefficients (double on the device: no host synchronisation); a zero norm makes every G NaN
+    const double inv = 1.0 / ((double)B * fwd_out[4 * b + 3]);
+    const float ka = (float)(-coef[0] * (double)lambda_d * inv), kb = (float)(coef[1] * inv);
+
+    // the own cell's descriptor as the B operand of the dot: lane half h supplies k = 8g + 4h + e to MFMA (g, e)
+    f32x4 own[D / 8];
+    {
+        const float* xr = x_own + ((long long)b * N + min(j, N - 1)) * D + half * 4;
+#pragma unroll
+        for (int g = 0; g < D / 8; ++g) own[g] = *reinterpret_cast<const f32x4*>(xr + g * 8);
+    }
+    float4 cj = j < N ? cells_own[(long long)b * N + j] : make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!use_mask) cj.z = 1.f;
+
+    f32x16 dx[NDB];
+#pragma unroll
+    for (int db = 0; db < NDB; ++db)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dx[db][r] = 0.f;
+
+    // staging of a TI x D tile: granules of 16 bytes, GPT per thread; rows past N are zero (their G is 0 too)
+    constexpr int GPR = D / 4, GPT = TI * GPR / RED;
+    f32x4 st[GPT];
+    auto gload = [&](int i0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int q = 0; q < GPT; ++q) {
+            const int gran = tid + q * RED, row = gran / GPR, c4 = gran - row * GPR;
+            st[q] = i0 + row < N ? *reinterpret_cast<const f32x4*>(Xo + (long long)(i0 + row) * D + c4 * 4)
+                                 : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+    gload(0);
+    for (int i0 = 0; i0 < N; i0 += TI) {
+#pragma unroll
+        for (int q = 0; q < GPT; ++q) {
+            const int gran = tid + q * RED, row = gran / GPR, c4 = gran - row * GPR;
+            *reinterpret_cast<f32x4*>(&Xs[row * RS + c4 * 4]) = st[q];
+        }
+        if (tid < TI) {
+            float4 c = make_float4(0.f, 0.f, 0.f, 0.f);           // .w: the row is a cell of the image
+            if (i0 + tid < N) {
+                c = co[i0 + tid];
+                if (!use_mask) c.z = 1.f;
+                c.w = 1.f;
+            }
+            oinfo[tid] = c;
+        }
+        __syncthreads();
+        if (i0 + TI < N) gload(i0 + TI);                          // in flight across this tile's MFMAs
+
+        f32x16 acc[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+#pragma unroll
+        for (int g = 0; g < D / 8; ++g) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(&Xs[(t * 32 + li) * RS + g * 8 + half * 4]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], own[g][e], acc[t], 0, 0, 0);
+            }
+        }
+
+        // G in place, with the forward's fp32 correspondence test and hinge arguments
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float4 ci = oinfo[t * 32 + 8 * (r >> 2) + 4 * half + (r & 3)];
+                const float dy = __fsub_rn(cj.x, ci.x), dxx = __fsub_rn(cj.y, ci.y);
+                const float s = __fadd_rn(__fmul_rn(dy, dy), __fmul_rn(dxx, dxx));
+                const float w = ci.z * cj.z;
+                const float c = s <= s_max ? w : 0.f;
+                const float dot = acc[t][r];
+                const float gv = c * hinge_grad(pos_margin - dot) * ka + (w - c) * hinge_grad(dot - neg_margin) * kb;
+                acc[t][r] = ci.w != 0.f ? gv : 0.f;
+            }
+        }
+
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float* xr = &Xs[(t * 32 + 8 * (r >> 2) + 4 * half + (r & 3)) * RS + li];
+#pragma unroll
+                for (int db = 0; db < NDB; ++db)
+                    dx[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[t][r], xr[db * 32], dx[db], 0, 0, 0);
+            }
+        }
+        __syncthreads();                                          // before the next tile overwrites Xs / oinfo
+    }
+
+    const int jb = blockIdx.x * (4 * 32) + wave * 32;
+    float* go = grad_own + (long long)b * N * D;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int jj = jb + 8 * (r >> 2) + 4 * half + (r & 3);
+        if (jj < N) {
+#pragma unroll
+            for (int db = 0; db < NDB; ++db) go[(long long)jj * D + db * 32 + li] = dx[db][r];
+        }
+    }
+}
+
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct LossWorkspace {
@@ -431,4 +652,52 @@ void launch_descriptor_loss(const float* desc1, const float* desc2, const float*
                            neg_margin, use_mask, w.tile_part);
     hipLaunchKernelGGL(descriptor_reduce_kernel, dim3(B), dim3(RED), 0, s, w.tile_part, nt * nt, w.cnt_part, nblk, N, use_mask,
                        lambda_d, out);
+}
+
+void launch_detector_loss_backward(const float* logits, const unsigned char* kp, const unsigned char* valid,
+                                   const float* noise, unsigned long long seed, int B, int H, int W, int use_ce,
+                                   const double* fwd_out, const double* coef, float* grad, hipStream_t s)
+{
+    const int N = (H >> 3) * (W >> 3), nblk = (N + RED - 1) / RED;
+    hipLaunchKernelGGL(detector_loss_backward_kernel, dim3(nblk, B), dim3(RED), 0, s, logits, kp, valid, noise, seed, B, H, W,
+                       use_ce, fwd_out, coef, grad);
+}
+
+namespace {
+template <int D>
+void launch_desc_grad_sides(const float* desc1, const float* desc2, const float4* cells, int B, int N, float s_max,
+                            float pos_margin, float neg_margin, float lambda_d, int use_mask, const double* fwd_out,
+                            const double* coef, float* grad1, float* grad2, hipStream_t s)
+{
+    const dim3 grid((N + 127) / 128, B);
+    const float4* c1 = cells;
+    const float4* c2 = cells + (long long)B * N;
+    if (grad1)                                               // a NULL gradient: that side is not needed
+        hipLaunchKernelGGL(desc_loss_grad_kernel<D>, grid, dim3(RED), 0, s, desc1, desc2, c1, c2, B, N, s_max, pos_margin,
+                           neg_margin, lambda_d, use_mask, fwd_out, coef, grad1);
+    if (grad2)
+        hipLaunchKernelGGL(desc_loss_grad_kernel<D>, grid, dim3(RED), 0, s, desc2, desc1, c2, c1, B, N, s_max, pos_margin,
+                           neg_margin, lambda_d, use_mask, fwd_out, coef, grad2);
+}
+}  // namespace
+
+void launch_descriptor_loss_backward(const float* desc1, const float* desc2, const float* hom1, const float* hom2,
+                                     const unsigned char* valid1, const unsigned char* valid2, int B, int H, int W, int D,
+                                     float s_max, float pos_margin, float neg_margin, float lambda_d, int use_mask,
+                                     const double* fwd_out, const double* coef, void* workspace, float* grad1,
+                                     float* grad2, hipStream_t s)
+{
+    const LossWorkspace w = loss_workspace(workspace, B, H, W);
+    const int N = (H >> 3) * (W >> 3), nblk = (N + RED - 1) / RED;
+    hipLaunchKernelGGL(desc_prologue_kernel, dim3(nblk, B), dim3(RED), 0, s, hom1, hom2, valid1, valid2, B, H, W, w.cells,
+                       nullptr, w.cnt_part);
+    if (D == 64)
+        launch_desc_grad_sides<64>(desc1, desc2, w.cells, B, N, s_max, pos_margin, neg_margin, lambda_d, use_mask, fwd_out,
+                                   coef, grad1, grad2, s);
+    else if (D == 128)
+        launch_desc_grad_sides<128>(desc1, desc2, w.cells, B, N, s_max, pos_margin, neg_margin, lambda_d, use_mask, fwd_out,
+                                    coef, grad1, grad2, s);
+    else
+        launch_desc_grad_sides<256>(desc1, desc2, w.cells, B, N, s_max, pos_margin, neg_margin, lambda_d, use_mask, fwd_out,
+                                    coef, grad1, grad2, s);
 }

@@ -352,6 +352,18 @@ void launch_descriptor_loss(const float* desc1, const float* desc2, const float*
                             const unsigned char* valid1, const unsigned char* valid2, int B, int H, int W, int D,
                             float s_max, float pos_margin, float neg_margin, double lambda_d, int use_mask,
                             void* workspace, double* out, float* warped, hipStream_t s);
+// backward: fwd_out the forward's out array of the same call; coef device doubles, the upstream coefficients
+//   detector:   coef[0] = gamma; grad fp32 [B][65][Hc][Wc]
+//   descriptor: coef[0] = alpha (positive terms), coef[1] = beta (negative terms); grad1 / grad2 channels-last fp32
+//               [B][Hc*Wc][D], either may be NULL (that side is skipped); recomputes the prologue into the workspace
+void launch_detector_loss_backward(const float* logits, const unsigned char* kp, const unsigned char* valid,
+                                   const float* noise, unsigned long long seed, int B, int H, int W, int use_ce,
+                                   const double* fwd_out, const double* coef, float* grad, hipStream_t s);
+void launch_descriptor_loss_backward(const float* desc1, const float* desc2, const float* hom1, const float* hom2,
+                                     const unsigned char* valid1, const unsigned char* valid2, int B, int H, int W, int D,
+                                     float s_max, float pos_margin, float neg_margin, float lambda_d, int use_mask,
+                                     const double* fwd_out, const double* coef, void* workspace, float* grad1,
+                                     float* grad2, hipStream_t s);
 
 // BatchNorm2d with the statistics of the batch (batchnorm_stats.hip).  Activations NHWC fp32 [npx][cstride], C (a multiple of 4,
 // 8..1024) channels per pixel; part: double [bn_stats_parts(npx, C)][2][C] scratch (at most MP_BN_MAX_PARTS slots)

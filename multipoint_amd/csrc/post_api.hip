@@ -523,6 +523,42 @@ int mp_descriptor_loss(mp_handle* h, const float* desc1, const float* desc2, int
     return launch_status(h);
 }
 
+int mp_detector_loss_backward(mp_handle* h, const float* logits, int B, int Hc, int Wc, const unsigned char* keypoints,
+                              const unsigned char* valid_mask, int H, int W, int use_cross_entropy, const float* noise,
+                              unsigned long long noise_seed, const double* forward_out, const double* coef,
+                              void* workspace, long long workspace_bytes, float* grad_logits, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!logits || !keypoints || !forward_out || !coef || !grad_logits)
+        return fail(h, MP_EINVAL, "mp_detector_loss_backward: NULL tensor");
+    const int rc = loss_check(h, "mp_detector_loss_backward", B, Hc, Wc, H, W, workspace, workspace_bytes);
+    if (rc != MP_OK) return rc;
+    MP_HIP(hipSetDevice(h->device));
+    launch_detector_loss_backward(logits, keypoints, valid_mask, noise, noise_seed, B, H, W, use_cross_entropy != 0,
+                                  forward_out, coef, grad_logits, static_cast<hipStream_t>(stream));
+    return launch_status(h);
+}
+
+int mp_descriptor_loss_backward(mp_handle* h, const float* desc1, const float* desc2, int B, int Hc, int Wc, int D,
+                                const float* hom1, const float* hom2, const unsigned char* valid1,
+                                const unsigned char* valid2, int H, int W, float threshold, float positive_margin,
+                                float negative_margin, float lambda_d, int use_mask, const double* forward_out,
+                                const double* coef, void* workspace, long long workspace_bytes, float* grad1,
+                                float* grad2, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!desc1 || !desc2 || !forward_out || !coef || (!grad1 && !grad2))
+        return fail(h, MP_EINVAL, "mp_descriptor_loss_backward: NULL tensor");
+    if (D != 64 && D != 128 && D != 256) return fail(h, MP_EINVAL, "mp_descriptor_loss_backward: D must be 64, 128 or 256");
+    const int rc = loss_check(h, "mp_descriptor_loss_backward", B, Hc, Wc, H, W, workspace, workspace_bytes);
+    if (rc != MP_OK) return rc;
+    MP_HIP(hipSetDevice(h->device));
+    launch_descriptor_loss_backward(desc1, desc2, hom1, hom2, valid1, valid2, B, H, W, D, corr_bound(threshold),
+                                    positive_margin, negative_margin, lambda_d, use_mask != 0, forward_out, coef, workspace,
+                                    grad1, grad2, static_cast<hipStream_t>(stream));
+    return launch_status(h);
+}
+
 int mp_photometric_workspace_bytes(int n, int H, int W, int n_ellipses, long long* bytes)
 {
     if (!bytes || n <= 0 || n > 65535 || H <= 0 || W <= 0 || n_ellipses < 0 || (long long)n * H * W > (1LL << 34))
