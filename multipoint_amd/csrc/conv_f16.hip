@@ -9,6 +9,7 @@
 // Rounding points (all round-to-nearest-even, as autocast produces them):
 //   conv: fp32 accumulate (+ fp16 bias) -> fp16;  ReLU;  BN: fp32 affine on the fp16 value -> fp16;  max-pool.
 #include "mp_common.h"
+#include "mp_device.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -50,14 +51,6 @@ struct GeoH {
     static constexpr int NITER = (NV + 255) / 256;       // staging vectors per thread
     static constexpr int STEPS = TAPS * (CKH / 16);      // k16-steps per chunk
 };
-
-__device__ __forceinline__ int reflect_clamp_h(int v, int n)
-{
-    v = v < 0 ? -v : v;
-    v = v >= n ? 2 * (n - 1) - v : v;
-    v = v < 0 ? 0 : v;
-    return v >= n ? n - 1 : v;
-}
 
 __device__ __forceinline__ float round_h(float v) { return (float)(_Float16)v; }
 
@@ -193,7 +186,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvParamsH p)
                         zero = (gy < 0) | (gy >= p.H) | (gx < 0) | (gx >= p.W);
                         gy = min(max(gy, 0), p.H - 1); gx = min(max(gx, 0), p.W - 1);
                     } else {
-                        gy = reflect_clamp_h(gy, p.H); gx = reflect_clamp_h(gx, p.W);
+                        gy = reflect_clamp(gy, p.H); gx = reflect_clamp(gx, p.W);
                     }
                     if (!zero) off = (gy * p.W + gx) * p.in_cstride + c8 * 8;
                 } else {
@@ -607,7 +600,7 @@ __global__ __launch_bounds__(256) void conv_first_f16_kernel(const Conv1ParamsH 
             gy = min(max(gy, 0), p.H - 1); gx = min(max(gx, 0), p.W - 1);
             v = zero ? 0.f : in[gy * p.W + gx];
         } else {
-            v = in[reflect_clamp_h(gy, p.H) * p.W + reflect_clamp_h(gx, p.W)];
+            v = in[reflect_clamp(gy, p.H) * p.W + reflect_clamp(gx, p.W)];
         }
         tile[f] = round_h(v);
     }

@@ -14,6 +14,7 @@
 // operations of a CU execute in order, so a wave's tile writes are visible before its increment).  Group 1 starts half an
 // item late.
 #include "mp_common.h"
+#include "mp_device.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -58,14 +59,6 @@ struct GeoR {
     static constexpr int NITER = (NV + 255) / 256;       // staging vectors per thread of a group
     static constexpr int STEPS = 9 * (CKR / 16);         // k16-steps per chunk
 };
-
-__device__ __forceinline__ int reflect_clamp_r(int v, int n)
-{
-    v = v < 0 ? -v : v;
-    v = v >= n ? 2 * (n - 1) - v : v;
-    v = v < 0 ? 0 : v;
-    return v >= n ? n - 1 : v;
-}
 
 // conv result pair (fp32 accumulators) -> activation as autocast produces it; identical to conv_f16.hip's act_h2
 template <bool BNF>
@@ -219,7 +212,7 @@ __global__ __launch_bounds__(256 * NG, NG) void conv_f16_res_kernel(const ConvPa
                     zero = (gy < 0) | (gy >= p.H) | (gx < 0) | (gx >= p.W);
                     gy = min(max(gy, 0), p.H - 1); gx = min(max(gx, 0), p.W - 1);
                 } else {
-                    gy = reflect_clamp_r(gy, p.H); gx = reflect_clamp_r(gx, p.W);
+                    gy = reflect_clamp(gy, p.H); gx = reflect_clamp(gx, p.W);
                 }
                 if (!zero) off = (gy * p.W + gx) * p.in_cstride + c8 * 8;
             }
@@ -243,7 +236,7 @@ __global__ __launch_bounds__(256 * NG, NG) void conv_f16_res_kernel(const ConvPa
         for (int i = 0; i < NIPR; ++i) {
             const int f = min(gt + i * 256, NIP - 1);
             const int r = f / IW, c = f - r * IW;
-            ipx[i] = im[reflect_clamp_r(w.y0 - 2 + r, p.H) * p.W + reflect_clamp_r(w.x0 - 2 + c, p.W)];
+            ipx[i] = im[reflect_clamp(w.y0 - 2 + r, p.H) * p.W + reflect_clamp(w.x0 - 2 + c, p.W)];
         }
     };
     auto patch_write = [&](int par) __attribute__((always_inline)) {
@@ -267,8 +260,8 @@ __global__ __launch_bounds__(256 * NG, NG) void conv_f16_res_kernel(const ConvPa
             const int ly = pc / G::LW, lx = pc - ly * G::LW;
             int oy = ly, ox = lx;
             if (!interior) {
-                oy = reflect_clamp_r(w.y0 + ly - 1, p.H) - w.y0 + 1;
-                ox = reflect_clamp_r(w.x0 + lx - 1, p.W) - w.x0 + 1;
+                oy = reflect_clamp(w.y0 + ly - 1, p.H) - w.y0 + 1;
+                ox = reflect_clamp(w.x0 + lx - 1, p.W) - w.x0 + 1;
                 oy = min(max(oy, 0), IH - 3); ox = min(max(ox, 0), IW - 3);      // (only pixels of phantom outputs are clamped)
             }
             const int base = oy * IW + ox;

@@ -5,19 +5,12 @@
 // 4 consecutive output channels whose 36 weights + bias/scale/shift live in registers; a wave
 // writes 4 adjacent pixels = 1 KiB contiguous per store instruction.
 #include "mp_common.h"
+#include "mp_device.h"
 
 namespace {
 
 constexpr int TH = 8, TW = 32;              // output tile per workgroup
 constexpr int LW = TW + 2, LH = TH + 2;
-
-__device__ __forceinline__ int reflect_clamp1(int v, int n)
-{
-    v = v < 0 ? -v : v;
-    v = v >= n ? 2 * (n - 1) - v : v;
-    v = v < 0 ? 0 : v;
-    return v >= n ? n - 1 : v;
-}
 
 // C1 = output channels (64, or 32 for channel_version 1 / 2): C1/4 lanes share a pixel.  LINEAR: conv + bias only (the
 // batch-statistics forward of bn_first models: their BatchNorm needs the pre-ReLU output; scale / shift are not read)
@@ -44,7 +37,7 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const Conv1Params p)
             gy = min(max(gy, 0), p.H - 1); gx = min(max(gx, 0), p.W - 1);
             v = zero ? 0.f : in[gy * p.W + gx];
         } else {
-            v = in[reflect_clamp1(gy, p.H) * p.W + reflect_clamp1(gx, p.W)];
+            v = in[reflect_clamp(gy, p.H) * p.W + reflect_clamp(gx, p.W)];
         }
         tile[f] = v;
     }
@@ -126,7 +119,7 @@ __global__ __launch_bounds__(256) void conv_first_pool_kernel(const Conv1Params 
             gy = min(max(gy, 0), p.H - 1); gx = min(max(gx, 0), p.W - 1);
             v = zero ? 0.f : in[gy * p.W + gx];
         } else {
-            v = in[reflect_clamp1(gy, p.H) * p.W + reflect_clamp1(gx, p.W)];
+            v = in[reflect_clamp(gy, p.H) * p.W + reflect_clamp(gx, p.W)];
         }
         tile[f] = v;
     }
@@ -207,7 +200,7 @@ __global__ __launch_bounds__(256) void conv_first_planar_kernel(const Conv1Param
             gy = min(max(gy, 0), p.H - 1); gx = min(max(gx, 0), p.W - 1);
             v = zero ? 0.f : in[gy * p.W + gx];
         } else {
-            v = in[reflect_clamp1(gy, p.H) * p.W + reflect_clamp1(gx, p.W)];
+            v = in[reflect_clamp(gy, p.H) * p.W + reflect_clamp(gx, p.W)];
         }
         tile[f] = v;
     }

@@ -18,6 +18,7 @@
 // (tile+halo) x 32 ch = ~48 KiB, so three workgroups share a CU and their load/compute phases
 // overlap (the fp32 MFMA takes 64 cycles per issue, everything else hides behind it).
 #include "mp_common.h"
+#include "mp_device.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -70,22 +71,12 @@ struct Geo {
     static constexpr int STEPS = TAPS * (CK / 8);        // k8-steps per chunk
 };
 
-__device__ __forceinline__ int reflect_clamp(int v, int n)
-{
-    v = v < 0 ? -v : v;                     // ReflectionPad2d(1): -1 -> 1
-    v = v >= n ? 2 * (n - 1) - v : v;       //                      n -> n-2
-    v = v < 0 ? 0 : v;
-    return v >= n ? n - 1 : v;              // (only reachable for pixels outside the image tile)
-}
-
 // FUSE1: the input of this convolution is the first encoder block (ReflectionPad -> Conv2d(1,64,3) -> ReLU
 // -> BN, reference encoder modules 0-3) of the image: instead of reading a 64-channel tensor from HBM
 // (78.6 MB written + re-read per 480x640 image) the (tile+halo) x 32-channel chunk is COMPUTED from a
 // (tile + 2-pixel ring) image patch held in LDS, on the VALU, in the shadow of the MFMAs.
-// ReLU as an integer max (finite inputs): one v_max_i32, no NaN-canonicalising v_max_f32 in front of it.
-// Every VALU instruction outside the MFMA loop matters: fp32 MFMA and VALU share one pipe and a wave that
-// is not streaming MFMAs advances only one instruction per MFMA slot of its neighbour (tools/conv_timing.py).
-__device__ __forceinline__ float relu_f(float v) { return __int_as_float(max(__float_as_int(v), 0)); }
+// Every VALU instruction outside the MFMA loop matters (the ReLU is relu_bits, mp_device.h): fp32 MFMA and VALU share one pipe
+// and a wave that is not streaming MFMAs advances only one instruction per MFMA slot of its neighbour (tools/conv_timing.py).
 __device__ __forceinline__ float max4_f(float a, float b, float c, float d)
 {
     float r;
@@ -261,8 +252,8 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float v = a[e] + b4[e];
-            if (BNF) v = relu_f(v * s4[e] + t4[e]);
-            else v = relu_f(v) * s4[e] + t4[e];
+            if (BNF) v = relu_bits(v * s4[e] + t4[e]);
+            else v = relu_bits(v) * s4[e] + t4[e];
             a[e] = v;
         }
         return a;
@@ -385,9 +376,9 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
             v += bia[nb];
             if (BNF) {
                 v = v * scl[nb] + sft[nb];
-                if (RELU) v = relu_f(v);
+                if (RELU) v = relu_bits(v);
             } else {
-                if (RELU) v = relu_f(v);
+                if (RELU) v = relu_bits(v);
                 v = v * scl[nb] + sft[nb];
             }
             return v;
@@ -447,9 +438,9 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
             float x = a[rg * 4 + e] + b4[e];
             if (BNF) {
                 x = x * s4[e] + t4[e];
-                if (RELU) x = relu_f(x);
+                if (RELU) x = relu_bits(x);
             } else {
-                if (RELU) x = relu_f(x);
+                if (RELU) x = relu_bits(x);
                 x = x * s4[e] + t4[e];
             }
             v[e] = x;
@@ -758,9 +749,9 @@ __global__ __launch_bounds__(256, 1) void conv_mfma_persist_kernel(const ConvPar
                 v += bia[nb];
                 if (BNF) {
                     v = v * scl[nb] + sft[nb];
-                    if (RELU) v = relu_f(v);
+                    if (RELU) v = relu_bits(v);
                 } else {
-                    if (RELU) v = relu_f(v);
+                    if (RELU) v = relu_bits(v);
                     v = v * scl[nb] + sft[nb];
                 }
                 return v;
@@ -828,9 +819,9 @@ __global__ __launch_bounds__(256, 1) void conv_mfma_persist_kernel(const ConvPar
                                 float x = acc[mb][nb][rg * 4 + e] + b4[e];
                                 if (BNF) {
                                     x = x * s4[e] + t4[e];
-                                    if (RELU) x = relu_f(x);
+                                    if (RELU) x = relu_bits(x);
                                 } else {
-                                    if (RELU) x = relu_f(x);
+                                    if (RELU) x = relu_bits(x);
                                     x = x * s4[e] + t4[e];
                                 }
                                 v[e] = x;

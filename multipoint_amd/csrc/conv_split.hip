@@ -7,11 +7,11 @@
 // the last range to arrive, found through a device-scope counter, gathered the shares: 64 values x 8 ranges per thread are 8-16
 // dependent ~1.5 us trips behind a write-through / counter / barrier hand-off, which was most of what a small launch cost.)
 #include "mp_common.h"
+#include "mp_device.h"
 
 namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float relu_s(float v) { return __int_as_float(max(__float_as_int(v), 0)); }
 
 // GEN 1: conv_wino43.hip (512 threads per item, 32 values each: [h][a][b]); GEN 2: conv_wino43b.hip (256 threads, 64 values:
 // [m][h][a][b]).  The index arithmetic below is the epilogues' own (lane = tile, register quad = 4 consecutive output channels).
@@ -68,8 +68,8 @@ __global__ __launch_bounds__(256) void split_reduce_kernel(const ConvParams p)
         for (int k = 1; k < 8; ++k)
             if (k < KS) v += __builtin_bit_cast(f32x2, rawv[k][i]);         // range order: deterministic
         v = w43_add_bias(v, 2 * ap + (i >> 2), i & 3, bb);          // (the shares are the SCALED transform's values: at6s, mp_common.h)
-        if (BNF) { v = v * ss + tt; v = f32x2{relu_s(v[0]), relu_s(v[1])}; }
-        else { v = f32x2{relu_s(v[0]), relu_s(v[1])}; v = v * ss + tt; }
+        if (BNF) { v = v * ss + tt; v = f32x2{relu_bits(v[0]), relu_bits(v[1])}; }
+        else { v = f32x2{relu_bits(v[0]), relu_bits(v[1])}; v = v * ss + tt; }
         yv[i >> 2][i & 3] = v;
     }
     if (ch >= p.cout) return;

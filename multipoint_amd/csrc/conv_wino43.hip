@@ -1,14 +1,14 @@
 // 3x3 convolution by Winograd F(4x4, 3x3) on the fp32 matrix instruction: 36 element-wise GEMMs
 //   M[pos] (tiles x cout) += V[pos] (tiles x cin) * U[pos] (cin x cout),  pos = 0..35
-// per 4x4 output pixels -- 2.25 multiplications per output against 4 for F(2x2,3x3) (conv_wino.hip) and 9 for the direct
-// form: 1.78x fewer MFMAs than conv_wino.hip for the same ReflectionPad -> Conv2d -> ReLU -> BN [-> MaxPool] block
+// per 4x4 output pixels -- 2.25 multiplications per output against 4 for F(2x2,3x3) and 9 for the direct form (conv_mfma.hip)
+// for the same ReflectionPad -> Conv2d -> ReLU -> BN [-> MaxPool] block
 // (multipoint/models/MultiPoint.py:143-148).  fp32 throughout; U = G g G^T is computed once on the host (in double, rounded
 // once), V = B^T d B and Y = A^T M A are short fixed-order multiply-add chains whose coefficients are exact binary fractions.
 // Interpolation points {0, +-3/4, +-3/2, inf} instead of the textbook {0, +-1, +-2, inf}: same instruction count, 3.4x smaller
 // maximum error (mp_common.h; measured on trained-like statistics: docs/HISTORY.md section 4).
 //
-// Structure (the round-2 lessons of conv_wino.hip apply unchanged: every operand through LDS, filled by LDS-DMA; ONE counted
-// wait + barrier per unit; no control flow inside a unit; vector work clustered):
+// Structure (the round-2 lessons of the retired F(2x2,3x3) kernel apply unchanged: every operand through LDS, filled by
+// LDS-DMA; ONE counted wait + barrier per unit; no control flow inside a unit; vector work clustered):
 //  * Persistent workgroups, ONE per CU, 512 threads = 8 waves (two per SIMD).  Item = 32 tiles (4 rows x 8 columns of 4x4
 //    pixels = 16 x 32 output pixels, or -- TC4 = 4 -- 8 x 4 = 32 x 16 pixels where that covers the frame with fewer items)
 //    x 64 output channels.  Wave w multiplies tile block w&1 (16 tiles) by channel block w>>1
@@ -33,12 +33,13 @@
 //    one ROW each and write V with ds_write2_b32 of the registers as they are.  Reads, arithmetic and stores of the two passes
 //    are spread over groups 0-6 of the unit, the stores two per MFMA gap.
 #include "mp_common.h"
+#include "mp_device.h"
 
 #include <algorithm>
 #include <type_traits>
 
 #ifdef MP_TIMING
-// developer instrumentation (tools/conv_timing_wino.py with MP_TIMING_KERNEL=43): per-workgroup cycle sums per phase, wave 0
+// developer instrumentation (tools/conv_timing_wino43.py): per-workgroup cycle sums per phase, wave 0
 __device__ unsigned long long g_timing_q[256 * 8];
 __device__ int g_timing_q_sel = 480;
 extern "C" int mp_debug_select_height_wino43(int h) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_timing_q_sel), &h, sizeof(int)); }
@@ -70,95 +71,16 @@ constexpr int SW4 = 8 * 36 * 2;                    // floats of a wave's transfo
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ int reflect_clamp_q(int v, int n)
-{
-    v = v < 0 ? -v : v;
-    v = v >= n ? 2 * (n - 1) - v : v;
-    v = v < 0 ? 0 : v;
-    return v >= n ? n - 1 : v;
-}
-__device__ __forceinline__ float relu_q(float v) { return __int_as_float(max(__float_as_int(v), 0)); }
-// LDS-DMA, see conv_wino.hip (hazards in front of the statement are checked at build time: multipoint_amd/build.py)
+// LDS-DMA of 16 bytes per lane (mp_device.h), dropped by MPQX & 2.  LEAD = 1 behind a wave-uniform branch: the five wait states an
+// SGPR base needs behind a VALU write must lie INSIDE the branch's own block (multipoint_amd/build.py checks it), so the statement
+// opens with two more
+template <int LEAD = 0>
 __device__ __forceinline__ void dma16(const float* sbase, unsigned voff_bytes, unsigned lds_byte)
 {
     if (MPQX & 2) return;
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff_bytes), "s"(sbase), "s"(lds_byte) : "memory");
+    lds_dma<4, LEAD, 0>(sbase, voff_bytes, lds_byte);
 }
-// the same behind a wave-uniform branch: the five wait states an SGPR base needs behind a VALU write must lie INSIDE the branch's
-// own block (multipoint_amd/build.py checks it), so the statement opens with two more
-__device__ __forceinline__ void dma16b(const float* sbase, unsigned voff_bytes, unsigned lds_byte)
-{
-    if (MPQX & 2) return;
-    unsigned keep;
-    asm volatile("s_nop 1\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff_bytes), "s"(sbase), "s"(lds_byte) : "memory");
-}
-// 4 bytes per lane: 64 lanes x 4 bytes from (uniform base + per-lane byte offset) to LDS [lds_byte + 4 * lane, + 4)
-__device__ __forceinline__ void dma4(const float* sbase, unsigned voff_bytes, unsigned lds_byte)
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff_bytes), "s"(sbase), "s"(lds_byte) : "memory");
-}
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)p; }
-
-// Packed fp32 arithmetic as explicit instructions: hipcc scalarises a third of the transform's packed multiply-adds (4 v_fma_f32
-// for 2 v_pk_fma_f32 per pass), and next to an MFMA stream every vector instruction costs matrix-pipe time (docs/HISTORY.md A.3).
-// The transform coefficients come in scalar register pairs (VOP3P takes no literal on gfx950).
-// Two coefficients share one scalar register pair (low / high half, picked by op_sel: the selected half feeds both lanes), so the
-// six coefficients of the input transform occupy three pairs instead of six (SGPRs are what the fused-first-block instantiation
-// is shortest of).
-constexpr unsigned long long pk_const2(double lo, double hi)
-{
-    return (unsigned long long)__builtin_bit_cast(unsigned, (float)lo) | ((unsigned long long)__builtin_bit_cast(unsigned, (float)hi) << 32);
-}
-constexpr double W43A = MP_W43_A, W43B = MP_W43_B;                  // interpolation points {0, +-a, +-b, inf} (mp_common.h)
-constexpr unsigned long long K_AB = pk_const2(W43A, W43B), K_A2B2 = pk_const2(W43A * W43A, W43B * W43B),
-                             K_PS = pk_const2(W43A * W43A * W43B * W43B, W43A * W43A + W43B * W43B);
-static_assert((double)(float)(W43A * W43A * W43B * W43B) == W43A * W43A * W43B * W43B && (double)(float)(W43A * W43A + W43B * W43B) ==
-              W43A * W43A + W43B * W43B, "the transform coefficients must be exact in fp32");
-// HI = 0: the low half of k, 1: the high half
-template <int HI>
-__device__ __forceinline__ f32x2 pk_fma_k(f32x2 a, unsigned long long k, f32x2 c)      // a * k + c
-{
-    f32x2 d;
-    if (HI) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(d) : "v"(a), "s"(k), "v"(c));
-    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(d) : "v"(a), "s"(k), "v"(c));
-    return d;
-}
-template <int HI>
-__device__ __forceinline__ f32x2 pk_fnma_k(f32x2 a, unsigned long long k, f32x2 c)     // c - a * k
-{
-    f32x2 d;
-    if (HI) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(d) : "v"(a), "s"(k), "v"(c));
-    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(d) : "v"(a), "s"(k), "v"(c));
-    return d;
-}
-// 1-D input transform B^T d (6 -> 6), packed over two channels: 12 multiply-adds.  Row of point p = the coefficients of
-// x (x^2 - a^2)(x^2 - b^2) / (x - p), last row the polynomial itself:
-//   B^T = [a^2 b^2, 0, -(a^2+b^2), 0, 1, 0;  0, -+a b^2, -b^2, +-a, 1, 0 (p = +-a);  0, -+b a^2, -a^2, +-b, 1, 0 (p = +-b);
-//          0, a^2 b^2, 0, -(a^2+b^2), 0, 1]
-__device__ __forceinline__ void bt6(const f32x2 d[6], f32x2 r[6])
-{
-#if defined(MPQX) && (MPQX & 131072)
-    for (int i = 0; i < 6; ++i) r[i] = d[i];        // timing only: no arithmetic
-    return;
-#endif
-    const f32x2 t0 = pk_fnma_k<1>(d[2], K_A2B2, d[4]);      // d4 - b^2 d2      (even part of the +-a rows)
-    const f32x2 t1 = pk_fnma_k<1>(d[1], K_A2B2, d[3]);      // d3 - b^2 d1      (odd part / a)
-    const f32x2 t2 = pk_fnma_k<0>(d[2], K_A2B2, d[4]);      // d4 - a^2 d2      (+-b rows)
-    const f32x2 t3 = pk_fnma_k<0>(d[1], K_A2B2, d[3]);      // d3 - a^2 d1
-    r[0] = pk_fma_k<0>(d[0], K_PS, pk_fnma_k<1>(d[2], K_PS, d[4]));      // a^2 b^2 d0 + (d4 - (a^2+b^2) d2)
-    r[1] = pk_fma_k<0>(t1, K_AB, t0);                       // t0 + a t1
-    r[2] = pk_fnma_k<0>(t1, K_AB, t0);                      // t0 - a t1
-    r[3] = pk_fma_k<1>(t3, K_AB, t2);                       // t2 + b t3
-    r[4] = pk_fnma_k<1>(t3, K_AB, t2);                      // t2 - b t3
-    r[5] = pk_fma_k<0>(d[1], K_PS, pk_fnma_k<1>(d[3], K_PS, d[5]));      // a^2 b^2 d1 + (d5 - (a^2+b^2) d3)
-}
-// (1-D output transform: at6s(), mp_common.h)
+constexpr bool BT6_COPY = MPQX & 131072;           // (timing only: the input transform without arithmetic)
 
 // F1: the layer's input is the first encoder block (Cin = 1 -> 64, conv_first.hip's arithmetic) of p.img, computed by this
 // kernel itself, PER UNIT and straight into the raw LDS ring (round 3; round 2 evaluated it per item into a global scratch that
@@ -255,7 +177,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
             const int py = f / PX, px = f - py * PX;
             unsigned off = 0;
             if (f < NPIX) {
-                const int gy = reflect_clamp_q(w.y0 + py - 1, p.H), gx = reflect_clamp_q(w.x0 + px - 1, p.W);
+                const int gy = reflect_clamp(w.y0 + py - 1, p.H), gx = reflect_clamp(w.x0 + px - 1, p.W);
                 off = (unsigned)((gy * p.W + gx) * pix_stride) * 4u;
             }
             rvoff[j] = off;
@@ -314,7 +236,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
         for (int k = 3 * site; k < 3 * site + 3; ++k)
             if (k < u_cnt) {
                 const int b = u_first + k;
-                dma16b((MPQX & 256) ? p.wpack : ub + b * 256, (unsigned)lane * 16u, us_lds + (unsigned)(buf * UB4 + b * 256) * 4u);
+                dma16<1>((MPQX & 256) ? p.wpack : ub + b * 256, (unsigned)lane * 16u, us_lds + (unsigned)(buf * UB4 + b * 256) * 4u);
             }
     };
     auto u_ptr = [&](int slice) __attribute__((always_inline)) -> const float* {      // unit 0 of a slice
@@ -370,7 +292,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     };
     auto tf_pass1b = [&](unsigned next_byte) __attribute__((always_inline)) {   // next_byte: raw buffer of the next transform
         if (MPQX & 1) return;
-        bt6(td, tr);                                      // tr[i'] = (B^T d)[i'][column sub6]
+        bt6<BT6_COPY>(td, tr);                            // tr[i'] = (B^T d)[i'][column sub6]
         p1_a = p1_base + next_byte; p1_b = p1_base + 4u * PX * 16u + next_byte;
     };
     // the LDS write path takes two 8-byte stores per MFMA gap for free and saturates beyond (docs/HISTORY.md A.3): the transform's
@@ -405,7 +327,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     const unsigned p2_addr = lds_addr(Vs) + (unsigned)p2_write * 4u;
     auto tf_pass2b = [&]() __attribute__((always_inline)) {
         if (MPQX & 1) return;
-        bt6(td, tr);                                      // tr[j'] = V[row sub6][j']
+        bt6<BT6_COPY>(td, tr);                            // tr[j'] = V[row sub6][j']
     };
     auto tf_pass2w = [&](int buf, int k) __attribute__((always_inline)) {       // positions 2k, 2k+1 of both channels
         if (MPQX & 1) return;
@@ -459,7 +381,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
             if (!interior) {
                 // the raw pixel is the block's output at the frame position reflected by THIS layer's padding; its window starts
                 // one row / column before it, and staged row r holds image row reflect(y0 - 2 + r)
-                oy = reflect_clamp_q(w.y0 + py - 1, p.H) - w.y0 + 1; ox = reflect_clamp_q(w.x0 + px - 1, p.W) - w.x0 + 1;
+                oy = reflect_clamp(w.y0 + py - 1, p.H) - w.y0 + 1; ox = reflect_clamp(w.x0 + px - 1, p.W) - w.x0 + 1;
                 oy = min(max(oy, 0), IH1 - 3); ox = min(max(ox, 0), IW1 - 3);      // (only pixels of phantom outputs are clamped)
             }
             pg_x[j] = ip_lds + (unsigned)(pc_par * IPB + oy * IW1 + ox) * 4u;
@@ -475,8 +397,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
             if (wave * 64 + 512 * j >= IH1 * IW1) continue;       // (wave-uniform)
             const int q = min(tid + 512 * j, IH1 * IW1 - 1);
             const int r = q / IW1, c = q - r * IW1;
-            const unsigned off = (unsigned)(reflect_clamp_q(w.y0 - 2 + r, p.H) * p.W + reflect_clamp_q(w.x0 - 2 + c, p.W)) * 4u;
-            dma4(im, off, ip_lds + (unsigned)(par * IPB + wave * 64 + 512 * j) * 4u);
+            const unsigned off = (unsigned)(reflect_clamp(w.y0 - 2 + r, p.H) * p.W + reflect_clamp(w.x0 - 2 + c, p.W)) * 4u;
+            lds_dma<1, 0, 0>(im, off, ip_lds + (unsigned)(par * IPB + wave * 64 + 512 * j) * 4u);
         }
     };
     // the cursor: unit pc_unit of item pc_item is what the next produce() makes; LDS byte addresses of its weights / parameters
@@ -510,7 +432,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
             // ReLU only: the block's BatchNorm was folded at load time -- into p.w1 / p.b1 for conv -> BN -> ReLU models, into this
             // layer's U and bias otherwise (model_load.hip build_encoder) -- which takes two packed multiply-adds and two LDS reads per
             // 64 pixels and unit out of the unit body
-            const f32x4 v = {relu_q(pd_[0]), relu_q(pd_[1]), relu_q(pd_[2]), relu_q(pd_[3])};
+            const f32x4 v = {relu_bits(pd_[0]), relu_bits(pd_[1]), relu_bits(pd_[2]), relu_bits(pd_[3])};
             *reinterpret_cast<lds_f32x4_wptr>(raw_lds + wbuf + pg_w[j]) = v;
         }
     };
@@ -908,7 +830,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
                                 m[r] = fmaxf(fmaxf(xv[2 * a][2 * b][r], xv[2 * a][2 * b + 1][r]), fmaxf(xv[2 * a + 1][2 * b][r], xv[2 * a + 1][2 * b + 1][r]));
                             if (BNF) {
                                 m = __builtin_elementwise_fma(m, ss, tt);
-                                m = f32x2{relu_q(m[0]), relu_q(m[1])};
+                                m = f32x2{relu_bits(m[0]), relu_bits(m[1])};
                             } else {
 #pragma unroll
                                 for (int r = 0; r < 2; ++r)
@@ -926,8 +848,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
 #pragma unroll
                     for (int b = 0; b < 4; ++b) {
                         f32x2 v = w43_add_bias(y[b], a, b, bb);
-                        if (BNF) { v = v * ss + tt; v = f32x2{relu_q(v[0]), relu_q(v[1])}; }
-                        else { v = f32x2{relu_q(v[0]), relu_q(v[1])}; v = v * ss + tt; }
+                        if (BNF) { v = v * ss + tt; v = f32x2{relu_bits(v[0]), relu_bits(v[1])}; }
+                        else { v = f32x2{relu_bits(v[0]), relu_bits(v[1])}; v = v * ss + tt; }
                         yv[a][b] = v;
                     }
                 }
@@ -1020,15 +942,15 @@ __global__ __launch_bounds__(256) void wino43_vprod_kernel(const ConvParams p, l
     const float* const base = p.in + (long long)img * p.H * p.W * p.in_cstride + p.in_coff + 2 * cp;
     int gx[6];
 #pragma unroll
-    for (int j = 0; j < 6; ++j) gx[j] = reflect_clamp_q(wx + j, p.W);
+    for (int j = 0; j < 6; ++j) gx[j] = reflect_clamp(wx + j, p.W);
     f32x2 r[6][6];                                       // r[i'][j] = (B^T d)[i'][column j]
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
         f32x2 d[6], o[6];
 #pragma unroll
         for (int i = 0; i < 6; ++i)
-            d[i] = *reinterpret_cast<const f32x2*>(base + ((long long)reflect_clamp_q(wy + i, p.H) * p.W + gx[j]) * p.in_cstride);
-        bt6(d, o);
+            d[i] = *reinterpret_cast<const f32x2*>(base + ((long long)reflect_clamp(wy + i, p.H) * p.W + gx[j]) * p.in_cstride);
+        bt6<BT6_COPY>(d, o);
 #pragma unroll
         for (int i = 0; i < 6; ++i) r[i][j] = o[i];
     }
@@ -1037,8 +959,8 @@ __global__ __launch_bounds__(256) void wino43_vprod_kernel(const ConvParams p, l
 #pragma unroll
     for (int i = 0; i < 6; i += 2) {                     // two rows = 12 positions = three 16-byte stores per channel
         f32x2 a[6], b[6];
-        bt6(r[i], a);
-        bt6(r[i + 1], b);
+        bt6<BT6_COPY>(r[i], a);
+        bt6<BT6_COPY>(r[i + 1], b);
         *reinterpret_cast<f32x4*>(dst0 + 6 * i) = f32x4{a[0][0], a[1][0], a[2][0], a[3][0]};
         *reinterpret_cast<f32x4*>(dst0 + 6 * i + 4) = f32x4{a[4][0], a[5][0], b[0][0], b[1][0]};
         *reinterpret_cast<f32x4*>(dst0 + 6 * i + 8) = f32x4{b[2][0], b[3][0], b[4][0], b[5][0]};
@@ -1110,7 +1032,7 @@ int launch_shape(const ConvParams& p, hipStream_t s)
 
 }  // namespace
 
-// true when launch_conv_wino43 handles this layer shape: reflection padding (zero-padding models use conv_wino.hip), input
+// true when launch_conv_wino43 handles this layer shape: reflection padding (zero-padding models use conv_wino43b.hip), input
 // channels a multiple of 8 (units of 4, unrolled in pairs), spatial size a multiple of the 4x4 tile
 bool conv_wino43_supports(const ConvParams& p)
 {

@@ -28,6 +28,7 @@
 //  * DMA order as in the first generation (weights and patches apart in time, one counted wait + barrier per unit), but the 9
 //    weight DMAs of a wave are spread from behind the barrier of unit n to group 1 of unit n+1 (one per 3 MFMAs).
 #include "mp_common.h"
+#include "mp_device.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -47,84 +48,17 @@ constexpr int VB4 = 2 * VR4 + 2;                   // floats per V' buffer (16-b
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ int reflect_clamp_q(int v, int n)
-{
-    v = v < 0 ? -v : v;
-    v = v >= n ? 2 * (n - 1) - v : v;
-    v = v < 0 ? 0 : v;
-    return v >= n ? n - 1 : v;
-}
-__device__ __forceinline__ float relu_q(float v) { return __int_as_float(max(__float_as_int(v), 0)); }
-// LDS-DMA (hazards in front of the statement are checked at build time: multipoint_amd/build.py)
+// LDS-DMA of 16 bytes per lane (mp_device.h), dropped by MPQX & 2.  OFF: the instruction's immediate offset, which moves the source
+// AND the LDS destination (round-4 probe; docs/HISTORY.md 3.3) -- exactly what a block-for-block copy wants: one scalar source base,
+// one scalar destination base and one lane-offset register serve a wave's nine weight blocks (the unit bodies are short of scalar
+// registers, and a lane-offset register per block would be spilled: the epilogue needs every register, and a reload inside a unit
+// body waits with vmcnt(0) for ALL DMAs in flight).  M0ADD is added to the destination only.
+template <int OFF = LDS_DMA_NO_OFFSET, int M0ADD = 0>
 __device__ __forceinline__ void dma16(const float* sbase, unsigned voff_bytes, unsigned lds_byte)
 {
     if (MPQX & 2) return;
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 1\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff_bytes), "s"(sbase), "s"(lds_byte) : "memory");
+    lds_dma<4, 0, 1, OFF, M0ADD>(sbase, voff_bytes, lds_byte);
 }
-// ... with the instruction's immediate offset OFF: it moves the source AND the LDS destination (round-4 probe; docs/HISTORY.md 3.3), which
-// is exactly what a block-for-block copy wants -- one scalar source base, one scalar destination base and one lane-offset register
-// serve a wave's nine weight blocks (the unit bodies are short of scalar registers, and a lane-offset register per block would
-// be spilled: the epilogue needs every register, and a reload inside a unit body waits with vmcnt(0) for ALL DMAs in flight).
-// M0ADD is added to the destination only.
-template <int OFF, int M0ADD>
-__device__ __forceinline__ void dma16i(const float* sbase, unsigned voff_bytes, unsigned lds_base)
-{
-    if (MPQX & 2) return;
-    unsigned keep;
-    if (M0ADD == 0)
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 1\n\tglobal_load_lds_dwordx4 %1, %2 offset:%4\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff_bytes), "s"(sbase), "s"(lds_base), "n"(OFF) : "memory");
-    else
-        asm volatile("s_mov_b32 %0, m0\n\ts_add_u32 m0, %3, %5\n\ts_nop 1\n\tglobal_load_lds_dwordx4 %1, %2 offset:%4\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff_bytes), "s"(sbase), "s"(lds_base), "n"(OFF), "n"(M0ADD) : "memory", "scc");
-}
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)p; }
-
-// packed fp32 multiply-add with a coefficient from a scalar register pair (low / high half picked by op_sel)
-constexpr unsigned long long pk_const2(double lo, double hi)
-{
-    return (unsigned long long)__builtin_bit_cast(unsigned, (float)lo) | ((unsigned long long)__builtin_bit_cast(unsigned, (float)hi) << 32);
-}
-constexpr double W43A = MP_W43_A, W43B = MP_W43_B;                  // interpolation points {0, +-a, +-b, inf} (mp_common.h)
-constexpr unsigned long long K_AB = pk_const2(W43A, W43B), K_BA = pk_const2(W43B, W43A), K_A2B2 = pk_const2(W43A * W43A, W43B * W43B),
-                             K_B2A2 = pk_const2(W43B * W43B, W43A * W43A),
-                             K_PS = pk_const2(W43A * W43A * W43B * W43B, W43A * W43A + W43B * W43B);
-static_assert((double)(float)(W43A * W43A * W43B * W43B) == W43A * W43A * W43B * W43B && (double)(float)(W43A * W43A + W43B * W43B) ==
-              W43A * W43A + W43B * W43B, "the transform coefficients must be exact in fp32");
-template <int HI>
-__device__ __forceinline__ f32x2 pk_fma_k(f32x2 a, unsigned long long k, f32x2 c)      // a * k + c
-{
-    f32x2 d;
-    if (HI) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(d) : "v"(a), "s"(k), "v"(c));
-    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(d) : "v"(a), "s"(k), "v"(c));
-    return d;
-}
-template <int HI>
-__device__ __forceinline__ f32x2 pk_fnma_k(f32x2 a, unsigned long long k, f32x2 c)     // c - a * k
-{
-    f32x2 d;
-    if (HI) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(d) : "v"(a), "s"(k), "v"(c));
-    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(d) : "v"(a), "s"(k), "v"(c));
-    return d;
-}
-// 1-D input transform B^T d (6 -> 6), packed over two channels: 12 multiply-adds (conv_wino43.hip's bt6, same order)
-__device__ __forceinline__ void bt6(const f32x2 d[6], f32x2 r[6])
-{
-    const f32x2 t0 = pk_fnma_k<1>(d[2], K_A2B2, d[4]);      // d4 - b^2 d2
-    const f32x2 t1 = pk_fnma_k<1>(d[1], K_A2B2, d[3]);      // d3 - b^2 d1
-    const f32x2 t2 = pk_fnma_k<0>(d[2], K_A2B2, d[4]);      // d4 - a^2 d2
-    const f32x2 t3 = pk_fnma_k<0>(d[1], K_A2B2, d[3]);      // d3 - a^2 d1
-    r[0] = pk_fma_k<0>(d[0], K_PS, pk_fnma_k<1>(d[2], K_PS, d[4]));
-    r[1] = pk_fma_k<0>(t1, K_AB, t0);
-    r[2] = pk_fnma_k<0>(t1, K_AB, t0);
-    r[3] = pk_fma_k<1>(t3, K_AB, t2);
-    r[4] = pk_fnma_k<1>(t3, K_AB, t2);
-    r[5] = pk_fma_k<0>(d[1], K_PS, pk_fnma_k<1>(d[3], K_PS, d[5]));
-}
-// (1-D output transform: at6s(), mp_common.h)
 
 // accumulator s * 2 + m: the first 64 are the compiler's (MFMA builtin: hipcc keeps them in the 256 AGPRs), the last 8 are pinned to
 // VGPRs by asm statements (288 > 256: with builtins only, hipcc still wants every MFMA result in an AGPR and shuttles the overflow
@@ -252,7 +186,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
                     const int gy = w.y0 + py - 1, gx = w.x0 + px - 1;
                     off = (gy >= 0 && gy < p.H && gx >= 0 && gx < p.W) ? (unsigned)((gy * p.W + gx) * pix_stride) * 4u : 0xFFFFFFFFu;
                 } else {
-                    const int gy = reflect_clamp_q(w.y0 + py - 1, p.H), gx = reflect_clamp_q(w.x0 + px - 1, p.W);
+                    const int gy = reflect_clamp(w.y0 + py - 1, p.H), gx = reflect_clamp(w.x0 + px - 1, p.W);
                     off = (unsigned)((gy * p.W + gx) * pix_stride) * 4u;
                 }
             }
@@ -292,8 +226,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
     auto u_dma = [&](const float* ubw, auto buf_tag, auto i_tag) __attribute__((always_inline)) {        // ubw = ub + wave * 2304 + 1024 floats
         constexpr int buf = decltype(buf_tag)::value, i = decltype(i_tag)::value;
         if (MPQX & 32) return;                                            // (timing only)
-        if constexpr (i < 8) dma16i<(i - 4) * 1024, buf * UB4 * 4>(ubw, lane16, us_w);
-        else dma16i<3072, buf * UB4 * 4 + 1024>(ubw, lane16 + 1024u, us_w);
+        if constexpr (i < 8) dma16<(i - 4) * 1024, buf * UB4 * 4>(ubw, lane16, us_w);
+        else dma16<3072, buf * UB4 * 4 + 1024>(ubw, lane16 + 1024u, us_w);
     };
     auto u_ptr = [&](int slice) __attribute__((always_inline)) -> const float* { return p.wpack + (long long)slice * NC * UB4; };
     auto load_prm = [&](int vslice) __attribute__((always_inline)) {
@@ -605,8 +539,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
                 auto out_row = [&](const int a, f32x2 (&y)[4]) __attribute__((always_inline)) { at6s(tcol[a], y); };
                 auto act = [&](f32x2 v, const int r, const int c) __attribute__((always_inline)) -> f32x2 {
                     v = w43_add_bias(v, r, c, bb);
-                    if (BNF) { v = v * ss + tt; return f32x2{relu_q(v[0]), relu_q(v[1])}; }
-                    v = f32x2{relu_q(v[0]), relu_q(v[1])};
+                    if (BNF) { v = v * ss + tt; return f32x2{relu_bits(v[0]), relu_bits(v[1])}; }
+                    v = f32x2{relu_bits(v[0]), relu_bits(v[1])};
                     return v * ss + tt;
                 };
                 // a uniform per-image base + 32-bit byte offsets (an image's output is far below 4 GB).  NHWC: pixel stride

@@ -10,12 +10,13 @@
 // (r&3) + 8*(r>>2) + 4*(lane>>5)).  The softmax and the L2 norm are then in-register reductions plus one exchange with
 // lane ^ 32, every register quad is 4 consecutive channels (= 4 horizontally adjacent pixels of the shuffled heat map, or
 // 16 bytes of the descriptor row), and nothing goes through LDS except the 3 x (96 + D) bias / scale / shift values.
-// Operands reach the matrix pipe through LDS, filled by LDS-DMA (conv_wino.hip's lesson: a DMA is free next to MFMAs, a
+// Operands reach the matrix pipe through LDS, filled by LDS-DMA (the Winograd kernels' lesson: a DMA is free next to MFMAs, a
 // register load costs 10-45 cycles of matrix-pipe time): K is walked in chunks of 32 channels, double-buffered; per chunk
 // the workgroup's four waves share ONE copy of the weight fragments (4 x (3 + D/32) KiB, packed by pack_conv_weights with
 // taps = 1) and each wave DMAs the 8 KiB of its own 32 pixels (a lane fetches 16 bytes of its own pixel's row, so the LDS
 // image is already in fragment order); one s_waitcnt vmcnt(0) + barrier per chunk.
 #include "mp_common.h"
+#include "mp_device.h"
 
 #include <type_traits>
 
@@ -27,15 +28,6 @@ __device__ __forceinline__ float acc_rd(float a)
     asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(x) : "a"(a));
     return x;
 }
-// LDS-DMA, see conv_wino.hip: 64 lanes x 16 bytes from (uniform base + per-lane byte offset) to LDS [lds_byte + 16*lane, +16)
-__device__ __forceinline__ void dma16(const float* sbase, unsigned voff_bytes, unsigned lds_byte)
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff_bytes), "s"(sbase), "s"(lds_byte) : "memory");
-}
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
 // ND = D / 32 descriptor blocks (0: no descriptor head)
 template <int ND>
 __global__ __launch_bounds__(256) void head_tail_kernel(const HeadTailParams p)
@@ -84,12 +76,12 @@ __global__ __launch_bounds__(256) void head_tail_kernel(const HeadTailParams p)
             const float* w = j < 3 ? p.wdet : p.wdesc;
             // pack_conv_weights layout [slice64][chunk32][kgroup4][nblock2][lane][4]
             const float* src = w + (((((long long)(nb >> 1) * nchunks + c) * 4 + wave) * 2 + (nb & 1)) * 64) * 4;
-            dma16(src, (unsigned)lane * 16u, wl_lds + (unsigned)(buf * WCH + (wave * NT + j) * 256) * 4u);
+            lds_dma<4, 0, 0>(src, (unsigned)lane * 16u, wl_lds + (unsigned)(buf * WCH + (wave * NT + j) * 256) * 4u);
         } else {
             const int q = j - NT, part = q >> 2, g = q & 3;
             if (ND == 0 && part == 1) return;
-            dma16((next_tile ? xbase_next : xbase) + part * p.K + c * 32 + g * 8, next_tile ? xoff_next : xoff,
-                  xl_lds + (unsigned)(buf * 4 * XCH + (part * 4 + g) * 256) * 4u);
+            lds_dma<4, 0, 0>((next_tile ? xbase_next : xbase) + part * p.K + c * 32 + g * 8, next_tile ? xoff_next : xoff,
+                             xl_lds + (unsigned)(buf * 4 * XCH + (part * 4 + g) * 256) * 4u);
         }
     };
 

@@ -20,20 +20,13 @@
 // image is already in fragment order).  The kernel is a stream: 20 MFMAs of 32 cycles per chunk against 13 DMAs per wave, so
 // what bounds it is bytes in flight (one chunk ahead = 32 KiB per CU), not the matrix pipe.
 #include "mp_common.h"
+#include "mp_device.h"
 
 #include <type_traits>
 
 namespace {
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void dma16h(const _Float16* sbase, unsigned voff_bytes, unsigned lds_byte)
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff_bytes), "s"(sbase), "s"(lds_byte) : "memory");
-}
-__device__ __forceinline__ void dma_wait_h() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -100,12 +93,12 @@ __global__ __launch_bounds__(256) void head_tail_f16_kernel(const HeadTailParams
             const int nb = j < 3 ? j : j - 3;
             const _Float16* w = j < 3 ? p.wdet : p.wdesc;
             const _Float16* src = w + (((((long long)(nb >> 1) * nchunks + c) * 4 + wave) * 2 + (nb & 1)) * 64) * 8;
-            dma16h(src, (unsigned)lane * 16u, wl_lds + (unsigned)(buf * WCH + (wave * NT + j) * 512) * 2u);
+            lds_dma<4, 0, 0>(src, (unsigned)lane * 16u, wl_lds + (unsigned)(buf * WCH + (wave * NT + j) * 512) * 2u);
         } else {
             const int q = j - NT, part = q >> 2, g = q & 3;
             if (ND == 0 && part == 1) return;
-            dma16h((next_tile ? xbase_next : xbase) + part * p.K + c * 64 + g * 16, next_tile ? xoff_next : xoff,
-                   xl_lds + (unsigned)(buf * 4 * XCH + (part * 4 + g) * 512) * 2u);
+            lds_dma<4, 0, 0>((next_tile ? xbase_next : xbase) + part * p.K + c * 64 + g * 16, next_tile ? xoff_next : xoff,
+                             xl_lds + (unsigned)(buf * 4 * XCH + (part * 4 + g) * 512) * 2u);
         }
     };
 
@@ -119,7 +112,7 @@ __global__ __launch_bounds__(256) void head_tail_f16_kernel(const HeadTailParams
 #pragma unroll
         for (int j = 0; j < NT + 8; ++j) chunk_dma(d, d, j, false);
     }
-    if (PD == 2) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NDMA) : "memory"); else dma_wait_h();
+    if (PD == 2) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NDMA) : "memory"); else dma_wait();
     __syncthreads();                                              // chunk 0 and prm visible
 
     for (;;) {
@@ -166,7 +159,7 @@ __global__ __launch_bounds__(256) void head_tail_f16_kernel(const HeadTailParams
         // chunk c + 1 must have landed; with PD = 2 the NDMA operations this chunk issued may stay in flight (the vector memory
         // counter retires loads in order, so "at most NDMA outstanding" means everything older than them -- the previous chunk's
         // DMAs and the epilogue's stores, which count in vmcnt too -- has completed)
-        if (PD == 2 && prefetch) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NDMA) : "memory"); else dma_wait_h();
+        if (PD == 2 && prefetch) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NDMA) : "memory"); else dma_wait();
         __syncthreads();                                          // next chunk landed, this one consumed
         bufi = bufi + 1 == NBUF ? 0 : bufi + 1;
     }

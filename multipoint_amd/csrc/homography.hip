@@ -8,16 +8,9 @@
 //   best = most inliers (lowest hypothesis index on ties), final model = normalised DLT over the best inlier set.
 // One thread per hypothesis (the matches of the pair sit in LDS); the winner is picked with a 64-bit atomicMax.
 #include "mp_common.h"
+#include "mp_device.h"
 
 namespace {
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z)
-{
-    z += 0x9e3779b97f4a7c15ull;
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
 
 // 4 distinct indices in [0, n) for hypothesis t of pair p
 __device__ __forceinline__ void sample4(unsigned long long seed, int p, int t, int n, int idx[4])

@@ -19,6 +19,7 @@
 // *_reduce_kernel         one workgroup per image sums the partials in fp64 in a fixed order: the result is
 //                         bit-identical from run to run (no float atomics anywhere).
 #include "mp_common.h"
+#include "mp_device.h"
 
 namespace {
 
@@ -26,14 +27,6 @@ constexpr int LT = 128;         // descriptor tile edge (cells of each side)
 constexpr int KC = 32;          // k-chunk of the product staged in LDS
 constexpr int KRS = KC + 4;     // LDS row stride in floats (the padding spreads the 16-byte reads over the banks)
 constexpr int RED = 256;        // threads of every launch here
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z)
-{
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 // label_noise 'device': a uniform draw in [0, 1) with 24 random bits (as torch.rand's fp32) per (seed, b, c, h, w)
 __device__ __forceinline__ float hash_noise(unsigned long long seed, int b, int c, int hc, int wc, int Hc, int Wc)

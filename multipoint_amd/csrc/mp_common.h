@@ -117,13 +117,69 @@ void launch_conv_first_linear(const Conv1Params& p, hipStream_t s);
 #ifndef MP_W43_B
 #define MP_W43_B 1.5
 #endif
+typedef float mp_f32x2 __attribute__((ext_vector_type(2)));
+// Packed fp32 arithmetic as explicit instructions: hipcc scalarises a third of the input transform's packed multiply-adds (4
+// v_fma_f32 for 2 v_pk_fma_f32 per pass), and next to an MFMA stream every vector instruction costs matrix-pipe time
+// (docs/HISTORY.md A.3).  The transform coefficients come in scalar register pairs (VOP3P takes no literal on gfx950).
+// Two coefficients share one scalar register pair (low / high half, picked by op_sel: the selected half feeds both lanes), so the
+// six coefficients of the input transform occupy three pairs instead of six (SGPRs are what the fused-first-block instantiation
+// of conv_wino43.hip is shortest of).
+constexpr unsigned long long pk_const2(double lo, double hi)
+{
+    return (unsigned long long)__builtin_bit_cast(unsigned, (float)lo) | ((unsigned long long)__builtin_bit_cast(unsigned, (float)hi) << 32);
+}
+constexpr double W43A = MP_W43_A, W43B = MP_W43_B;                  // interpolation points {0, +-a, +-b, inf}
+constexpr unsigned long long K_AB = pk_const2(W43A, W43B), K_BA = pk_const2(W43B, W43A), K_A2B2 = pk_const2(W43A * W43A, W43B * W43B),
+                             K_B2A2 = pk_const2(W43B * W43B, W43A * W43A),
+                             K_PS = pk_const2(W43A * W43A * W43B * W43B, W43A * W43A + W43B * W43B);
+static_assert((double)(float)(W43A * W43A * W43B * W43B) == W43A * W43A * W43B * W43B && (double)(float)(W43A * W43A + W43B * W43B) ==
+              W43A * W43A + W43B * W43B, "the transform coefficients must be exact in fp32");
+// HI = 0: the low half of k, 1: the high half
+template <int HI>
+__device__ __forceinline__ mp_f32x2 pk_fma_k(mp_f32x2 a, unsigned long long k, mp_f32x2 c)      // a * k + c
+{
+    mp_f32x2 d;
+    if (HI) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(d) : "v"(a), "s"(k), "v"(c));
+    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(d) : "v"(a), "s"(k), "v"(c));
+    return d;
+}
+template <int HI>
+__device__ __forceinline__ mp_f32x2 pk_fnma_k(mp_f32x2 a, unsigned long long k, mp_f32x2 c)     // c - a * k
+{
+    mp_f32x2 d;
+    if (HI) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(d) : "v"(a), "s"(k), "v"(c));
+    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(d) : "v"(a), "s"(k), "v"(c));
+    return d;
+}
+// 1-D input transform B^T d (6 -> 6) of the F(4x4,3x3) kernels, packed over two channels: 12 multiply-adds.  Row of point p = the
+// coefficients of x (x^2 - a^2)(x^2 - b^2) / (x - p), last row the polynomial itself:
+//   B^T = [a^2 b^2, 0, -(a^2+b^2), 0, 1, 0;  0, -+a b^2, -b^2, +-a, 1, 0 (p = +-a);  0, -+b a^2, -a^2, +-b, 1, 0 (p = +-b);
+//          0, a^2 b^2, 0, -(a^2+b^2), 0, 1]
+// COPY (timing only, conv_wino43.hip's MPQX & 131072): r = d, no arithmetic
+template <bool COPY = false>
+__device__ __forceinline__ void bt6(const mp_f32x2 d[6], mp_f32x2 r[6])
+{
+    if constexpr (COPY) {
+        for (int i = 0; i < 6; ++i) r[i] = d[i];
+        return;
+    }
+    const mp_f32x2 t0 = pk_fnma_k<1>(d[2], K_A2B2, d[4]);      // d4 - b^2 d2      (even part of the +-a rows)
+    const mp_f32x2 t1 = pk_fnma_k<1>(d[1], K_A2B2, d[3]);      // d3 - b^2 d1      (odd part / a)
+    const mp_f32x2 t2 = pk_fnma_k<0>(d[2], K_A2B2, d[4]);      // d4 - a^2 d2      (+-b rows)
+    const mp_f32x2 t3 = pk_fnma_k<0>(d[1], K_A2B2, d[3]);      // d3 - a^2 d1
+    r[0] = pk_fma_k<0>(d[0], K_PS, pk_fnma_k<1>(d[2], K_PS, d[4]));      // a^2 b^2 d0 + (d4 - (a^2+b^2) d2)
+    r[1] = pk_fma_k<0>(t1, K_AB, t0);                          // t0 + a t1
+    r[2] = pk_fnma_k<0>(t1, K_AB, t0);                         // t0 - a t1
+    r[3] = pk_fma_k<1>(t3, K_AB, t2);                          // t2 + b t3
+    r[4] = pk_fnma_k<1>(t3, K_AB, t2);                         // t2 - b t3
+    r[5] = pk_fma_k<0>(d[1], K_PS, pk_fnma_k<1>(d[3], K_PS, d[5]));      // a^2 b^2 d1 + (d5 - (a^2+b^2) d3)
+}
 // 1-D output transform A^T m (6 -> 4) of the F(4x4,3x3) kernels, packed over two output channels, with the powers of `a` factored
 // out of rows 1 and 2: A^T[i][p] = p^i over the points (0, a, -a, b, -b, inf) and b = 2a give
 //   y0 = m0 + s1 + s2,  y1 = a (d1 + 2 d2),  y2 = a^2 (s1 + 4 s2),  y3 = a^3 (d1 + 8 d2) + m5     (s = sums, d = differences)
 // so z = (y0, y1 / a, y2 / a^2, y3) takes 10 packed instructions instead of 13 (every bracket is ONE multiply-add with an exact
 // coefficient), and the factor sigma_r sigma_c, sigma = (1, a, a^2, 1), of output (r, c) goes into the multiply-add that adds the
 // bias anyway (w43_out_scale; 1, a .. a^4 are exact binary fractions).  Two roundings fewer per y1 / y2 than the plain form.
-typedef float mp_f32x2 __attribute__((ext_vector_type(2)));
 static_assert(MP_W43_B == 2 * MP_W43_A, "at6s() needs b = 2a");
 __device__ __forceinline__ void at6s(const mp_f32x2 m[6], mp_f32x2 z[4])
 {

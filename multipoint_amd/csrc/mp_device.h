@@ -1,0 +1,59 @@
+// Device primitives shared by the kernel sources of libmultipoint_hip.so (gfx950).  Internal header.
+#pragma once
+#include <hip/hip_runtime.h>
+
+// ReflectionPad2d(1) index of row / column v of an n-pixel frame
+__device__ __forceinline__ int reflect_clamp(int v, int n)
+{
+    v = v < 0 ? -v : v;                     // ReflectionPad2d(1): -1 -> 1
+    v = v >= n ? 2 * (n - 1) - v : v;       //                      n -> n-2
+    v = v < 0 ? 0 : v;
+    return v >= n ? n - 1 : v;              // (only reachable for pixels outside the image tile)
+}
+
+// ReLU as an integer max (finite inputs): one v_max_i32, no NaN-canonicalising v_max_f32 in front of it
+__device__ __forceinline__ float relu_bits(float v) { return __int_as_float(max(__float_as_int(v), 0)); }
+
+// splitmix64 finaliser: the counter-based hash behind RANSAC sampling (homography.hip), label noise (losses.hip) and
+// photometric noise (photometric.hip)
+__device__ __forceinline__ unsigned long long mix64(unsigned long long z)
+{
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// LDS-DMA: 64 lanes x DWORDS dwords from (uniform base + per-lane byte offset [+ OFF]) to LDS [lds_byte [+ M0ADD] [+ OFF] +
+// 4 DWORDS lane, ...).  The immediate OFF moves the source AND the LDS destination, M0ADD the destination only.  M0 is
+// compiler-reserved and not preserved around an asm statement: the statement sets it and restores it.
+// hipcc pads no hazard inside an asm statement, and an SGPR base needs five wait states behind a VALU write: NOP is the s_nop
+// in front of the load, LEAD > 0 opens the statement with s_nop LEAD (behind a wave-uniform branch the wait states must lie
+// inside the branch's own block).  multipoint_amd/build.py checks the generated code of the sources that use this (DMA_SOURCES).
+constexpr int LDS_DMA_NO_OFFSET = 1 << 13;      // OFF: the instruction without an offset field (13-bit signed: never a real one)
+template <int DWORDS, int LEAD, int NOP, int OFF = LDS_DMA_NO_OFFSET, int M0ADD = 0, typename T>
+__device__ __forceinline__ void lds_dma(const T* sbase, unsigned voff_bytes, unsigned lds_byte)
+{
+    static_assert(DWORDS == 1 || DWORDS == 4, "global_load_lds_dword or global_load_lds_dwordx4");
+    unsigned keep;
+    // an asm template is a string literal: one statement per variant of its text, all with the same operands
+#define MP_LDS_DMA(LEAD_S, M0_S, LOAD_S, ...)                                                                                  \
+    asm volatile(LEAD_S "s_mov_b32 %0, m0\n\t" M0_S "\n\ts_nop %4\n\t" LOAD_S "\n\ts_mov_b32 m0, %0"                          \
+                 : "=&s"(keep) : "v"(voff_bytes), "s"(sbase), "s"(lds_byte), "n"(NOP), "n"(OFF), "n"(M0ADD), "n"(LEAD)       \
+                 : __VA_ARGS__)
+#define MP_LDS_DMA_M0(LEAD_S, LOAD_S)                                                                                          \
+    if constexpr (M0ADD == 0 && OFF == LDS_DMA_NO_OFFSET) MP_LDS_DMA(LEAD_S, "s_mov_b32 m0, %3", LOAD_S " %1, %2", "memory"); \
+    else if constexpr (M0ADD == 0) MP_LDS_DMA(LEAD_S, "s_mov_b32 m0, %3", LOAD_S " %1, %2 offset:%5", "memory");             \
+    else if constexpr (OFF == LDS_DMA_NO_OFFSET) MP_LDS_DMA(LEAD_S, "s_add_u32 m0, %3, %6", LOAD_S " %1, %2", "memory", "scc"); \
+    else MP_LDS_DMA(LEAD_S, "s_add_u32 m0, %3, %6", LOAD_S " %1, %2 offset:%5", "memory", "scc")
+    if constexpr (LEAD == 0 && DWORDS == 4) { MP_LDS_DMA_M0("", "global_load_lds_dwordx4"); }
+    else if constexpr (LEAD == 0) { MP_LDS_DMA_M0("", "global_load_lds_dword"); }
+    else if constexpr (DWORDS == 4) { MP_LDS_DMA_M0("s_nop %7\n\t", "global_load_lds_dwordx4"); }
+    else { MP_LDS_DMA_M0("s_nop %7\n\t", "global_load_lds_dword"); }
+#undef MP_LDS_DMA_M0
+#undef MP_LDS_DMA
+}
+// wait for every LDS-DMA (and every other vector-memory load) of the wave: hipcc counts none of the asm statements above
+__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// byte address of an LDS array (the M0 / ds_* operand)
+__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)p; }

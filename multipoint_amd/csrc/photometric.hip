@@ -20,6 +20,7 @@
 //
 // All pixel arithmetic follows numpy's float32 operation order with every step rounded (no contraction into FMA).
 #include "mp_common.h"
+#include "mp_device.h"
 #include "../../include/multipoint_hip.h"
 
 #pragma clang fp contract(off)
@@ -38,14 +39,6 @@ constexpr int FULL_LEAVES = 64;         // a chunk of 8192 halves evenly down to
 constexpr int MAX_VERTS = 80;           // ellipse2Poly with delta >= 5: at most 73 points
 constexpr int COL_TX = 16, COL_TY = 64; // column-filter tile (columns x output rows)
 constexpr int STACK = 64;               // pairwise-tree walk stacks (depth <= 7 for a chunk of 8192)
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z)
-{
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 // device noise: a double in [0, 1) with 53 random bits per (key, counter), counter-based (the same splitmix hash as
 // losses.hip's label noise); normals by Box-Muller from the counters 2p and 2p + 1

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Developer tool: build multipoint_amd/libmultipoint_hip_exp_<name>.so with extra hipcc flags for ONE source file
-# (default conv_wino.hip); every other object comes from the regular build.   tools/build_variant.sh <name> "<flags>" [src]
+# (default conv_wino43.hip); every other object comes from the regular build.   tools/build_variant.sh <name> "<flags>" [src]
 set -e
 cd "$(dirname "$0")/.."
 NAME=$1; FLAGS=$2; SRC=${3:-conv_wino43.hip}
