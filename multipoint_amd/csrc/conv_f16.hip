@@ -14,21 +14,9 @@
 #include <algorithm>
 #include <type_traits>
 
-#ifdef MP_TIMING
-// developer instrumentation: per-workgroup cycle sums per phase (wave 0), see tools/conv_timing_f16.py
-__device__ unsigned long long g_timing_h[512 * 8];
-__device__ int g_timing_h_sel = 1024;       // only launches whose input height matches are recorded
-extern "C" int mp_debug_select_height_f16(int h) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_timing_h_sel), &h, sizeof(int)); }
-extern "C" int mp_debug_read_timing_f16(unsigned long long* host, int n)
-{
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_timing_h), sizeof(unsigned long long) * n);
-}
-#define MPH_T(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#define MPH_ADD(slot, a, b) do { tsum[slot] += (b) - (a); } while (0)      // wave-uniform register accumulators
-#else
-#define MPH_T(var) do { } while (0)
-#define MPH_ADD(slot, a, b) do { } while (0)
-#endif
+// developer instrumentation: per-workgroup cycle sums per phase (wave 0), see tools/conv_timing.py f16
+MP_TIMING_TABLE(g_timing_h, 512 * 8, mp_debug_read_timing_f16)
+MP_TIMING_HEIGHT(g_timing_h_sel, 1024, mp_debug_select_height_f16)       // only launches whose input height matches are recorded
 
 namespace {
 
@@ -266,7 +254,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvParamsH p)
 #endif
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (;;) {
-        MPH_T(t_item);
+        MP_CLOCK(t_item);
         f32x16 acc[2][2];      // not zero-initialised: the first MFMAs of the item take a literal-zero C operand
         const int item_next = item + stride;
         const bool has_next = item_next < item_end;
@@ -298,8 +286,8 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvParamsH p)
             }
             const h8* wc = wp + (long long)c * (G::STEPS * 128);
             const h8* wt = last ? wnext : wc + G::STEPS * 128;   // where the prefetch continues after this chunk
-            MPH_T(t_steps0);
-            if (c == 0) MPH_ADD(0, t_item, t_steps0);          // item start -> first step (decode, offsets)
+            MP_CLOCK(t_steps0);
+            if (c == 0) MP_CLOCK_ADD(0, t_item, t_steps0);          // item start -> first step (decode, offsets)
 #pragma unroll
             for (int s = 0; s < RA - 1; ++s) {
                 af[s][0] = *reinterpret_cast<const h8*>(&lds[a_base + a_off(s)]);
@@ -336,20 +324,20 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvParamsH p)
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            MPH_T(t_steps1);
-            MPH_ADD(1, t_steps0, t_steps1);                    // the MFMA steps of a chunk
+            MP_CLOCK(t_steps1);
+            MP_CLOCK_ADD(1, t_steps0, t_steps1);                    // the MFMA steps of a chunk
             __syncthreads();                                   // this chunk's LDS image fully consumed
-            MPH_T(t_bar);
-            MPH_ADD(2, t_steps1, t_bar);                       // barrier skew
+            MP_CLOCK(t_bar);
+            MP_CLOCK_ADD(2, t_steps1, t_bar);                       // barrier skew
             if (last) cur_pad = nxt_pad;
             if (!last || has_next) lds_write();                // staged registers are free again before the epilogue
-            MPH_T(t_ldsw);
-            MPH_ADD(3, t_bar, t_ldsw);                         // staging data landed + LDS write
+            MP_CLOCK(t_ldsw);
+            MP_CLOCK_ADD(3, t_bar, t_ldsw);                         // staging data landed + LDS write
             if (!last) __syncthreads();
         };
         chunk_body(0, std::true_type{});
         for (int c = 1; c < nchunks; ++c) chunk_body(c, std::false_type{});
-        MPH_T(t_epi0);
+        MP_CLOCK(t_epi0);
 
         // ---------------- epilogue of item `cur` ----------------
         const int slice = cur.slice, img = cur.img, y0 = cur.y0, x0 = cur.x0;
@@ -533,8 +521,8 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvParamsH p)
                 store_all(std::false_type{});          // a partial channel slice (cout = 65: the 1x1 detector head as its own launch)
             }
         }
-        MPH_T(t_epi1);
-        MPH_ADD(4, t_epi0, t_epi1);                            // epilogue
+        MP_CLOCK(t_epi1);
+        MP_CLOCK_ADD(4, t_epi0, t_epi1);                            // epilogue
 #ifdef MP_TIMING
         tsum[7] += 1;
         if (!has_next && tid == 0 && t_on)
@@ -543,8 +531,8 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvParamsH p)
         if (!has_next) return;
         __syncthreads();                                       // next item's LDS image complete, every epilogue done
         if (nxt.slice != cur.slice) load_prm(nxt.slice);       // (rare) visible to the next epilogue via the post-steps barrier
-        MPH_T(t_bar2);
-        MPH_ADD(5, t_epi1, t_bar2);
+        MP_CLOCK(t_bar2);
+        MP_CLOCK_ADD(5, t_epi1, t_bar2);
         item = item_next;
         cur = nxt;
         wp = wnext;

@@ -26,29 +26,12 @@
 
 #ifdef MP_TIMING
 // developer instrumentation: per-wave s_memtime stamps of the first 8192 workgroups (slot 15: HW_ID | XCC_ID << 32)
-__device__ unsigned long long g_timing[8192 * 4 * 16];
-__device__ int g_timing_h = 480;          // only launches whose input height matches are stamped
+// (the persistent kernel writes its wave-uniform per-phase cycle sums to the same table, once per workgroup: g_timing[blockIdx*8 + i])
+MP_TIMING_TABLE(g_timing, 8192 * 4 * 16, mp_debug_read_timing)
+MP_TIMING_HEIGHT(g_timing_h, 480, mp_debug_select_height)          // only launches whose input height matches are stamped
 #define MP_STAMP(i) do { if ((tid & 63) == 0 && blockIdx.x < 8192 && p.H == g_timing_h) g_timing[(blockIdx.x * 4 + (tid >> 6)) * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-extern "C" int mp_debug_select_height(int h) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_timing_h), &h, sizeof(int)); }
-extern "C" int mp_debug_read_timing(unsigned long long* host, int n)
-{
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_timing), sizeof(unsigned long long) * n);
-}
 #else
 #define MP_STAMP(i) do { } while (0)
-#endif
-#ifdef MP_TIMING
-// persistent kernel: wave-uniform per-phase cycle sums, written once per workgroup to g_timing[blockIdx*8 + i]
-#define MPP_T(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#define MPP_ADD(slot, a, b) do { tsum[slot] += (b) - (a); } while (0)
-#else
-#define MPP_T(var) do { } while (0)
-#define MPP_ADD(slot, a, b) do { } while (0)
-#endif
-#if defined(MP_TIMING) && MP_TIMING == 2      // prologue-focused stamps (reuse slots 4..6 of the first chunk)
-#define MP_STAMP_P(i) MP_STAMP(i)
-#else
-#define MP_STAMP_P(i) do { } while (0)
 #endif
 
 namespace {
@@ -150,17 +133,6 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
     // ---- per-thread staging offsets (element offsets from in_base, -1 = store zeros) ----
     // interior tiles (every halo pixel inside the image: ~87 % of the tiles at 480x640) take a lean path:
     // no reflect / clamp / zero logic here and no zero-select at the LDS writes.
-    MP_STAMP_P(8);       // block decode done (kernel arguments loaded)
-#if defined(MP_TIMING) && MP_TIMING == 3
-    {   // calibration: 256 dependent VALU adds between stamps 8 and 9 (how fast does this wave issue?)
-        MP_STAMP(8);
-        int xx = tid;
-#pragma unroll
-        for (int i = 0; i < 256; ++i) asm volatile("v_add_u32 %0, %0, %1" : "+v"(xx) : "v"(tid));
-        MP_STAMP(9);
-        if (xx == 0x7fffffff) p.out[0] = 0.f;
-    }
-#endif
     bool interior = false;
     if constexpr (TAPS == 9)
         interior = (y0 >= 1) && (y0 + G::TH < p.H) && (x0 >= 1) && (x0 + G::TW < p.W);
@@ -208,7 +180,6 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
     }
 
     // ---- A-fragment LDS base of this lane (M-block 2*wave, tap (0,0), k-group 0) ----
-    MP_STAMP_P(9);       // staging offsets done
     const int a_base = (((2 * wave) * G::MBH + li / MBW) * G::LW + (li % MBW)) * PS + half * 4;
     constexpr int A_MB = G::MBH * G::LW * PS;     // second M-block of the wave
 
@@ -652,7 +623,7 @@ __global__ __launch_bounds__(256, 1) void conv_mfma_persist_kernel(const ConvPar
     const bool t_on = (p.H == g_timing_h);
 #endif
     for (;;) {
-        MPP_T(t_item);
+        MP_CLOCK(t_item);
         f32x16 acc[2][2];
         const int item_next = item + stride;
         const bool has_next = item_next < item_end;
@@ -681,8 +652,8 @@ __global__ __launch_bounds__(256, 1) void conv_mfma_persist_kernel(const ConvPar
             const bool stage_pad = last ? nxt_pad : cur_pad;           // padding flags of the image being staged
             const float* const rbuf = lds + bufsel * BUF;               // image of this chunk
             float* const wbuf = lds + (bufsel ^ 1) * BUF;               // image being built for the next chunk / item
-            MPP_T(t_s0);
-            if (c == 0) MPP_ADD(0, t_item, t_s0);
+            MP_CLOCK(t_s0);
+            if (c == 0) MP_CLOCK_ADD(0, t_item, t_s0);
             af2[0][0] = *reinterpret_cast<const f32x4*>(&rbuf[a_base]);
             af2[0][1] = *reinterpret_cast<const f32x4*>(&rbuf[a_base + A_MB]);
             af2[1][0] = *reinterpret_cast<const f32x4*>(&rbuf[a_base + 8]);          // step 1 = tap 0, channel group 1
@@ -724,18 +695,18 @@ __global__ __launch_bounds__(256, 1) void conv_mfma_persist_kernel(const ConvPar
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            MPP_T(t_s1);
-            MPP_ADD(1, t_s0, t_s1);
+            MP_CLOCK(t_s1);
+            MP_CLOCK_ADD(1, t_s0, t_s1);
             bufsel ^= 1;
             if (last) cur_pad = nxt_pad;
             __syncthreads();                                   // next image complete, this one fully consumed
-            MPP_T(t_b);
-            MPP_ADD(2, t_s1, t_b);
+            MP_CLOCK(t_b);
+            MP_CLOCK_ADD(2, t_s1, t_b);
         };
         chunk_body(0, std::true_type{});
         for (int c = 1; c < nchunks; ++c) chunk_body(c, std::false_type{});
 
-        MPP_T(t_e0);
+        MP_CLOCK(t_e0);
         // ---------------- epilogue of item `cur`: wave-uniform 64-bit base + one per-lane offset ----------------
         const int slice = cur.slice, img = cur.img, y0 = cur.y0, x0 = cur.x0;
         const long long px0 = cur.px0;
@@ -851,8 +822,8 @@ __global__ __launch_bounds__(256, 1) void conv_mfma_persist_kernel(const ConvPar
             };
             if (full) store_all(std::true_type{}); else store_all(std::false_type{});
         }
-        MPP_T(t_e1);
-        MPP_ADD(4, t_e0, t_e1);
+        MP_CLOCK(t_e1);
+        MP_CLOCK_ADD(4, t_e0, t_e1);
 #ifdef MP_TIMING
         tsum[7] += 1;
         if (!has_next && tid == 0 && t_on)

@@ -38,25 +38,10 @@
 #include <algorithm>
 #include <type_traits>
 
-#ifdef MP_TIMING
-// developer instrumentation (tools/conv_timing_wino43.py): per-workgroup cycle sums per phase, wave 0
-__device__ unsigned long long g_timing_q[256 * 8];
-__device__ int g_timing_q_sel = 480;
-extern "C" int mp_debug_select_height_wino43(int h) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_timing_q_sel), &h, sizeof(int)); }
-extern "C" int mp_debug_read_timing_wino43(unsigned long long* host, int n)
-{
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_timing_q), sizeof(unsigned long long) * n);
-}
-#define MPQ_T(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#define MPQ_ADD(slot, a, b) do { tsum[slot] += (b) - (a); } while (0)
-#else
-#define MPQ_T(var) do { } while (0)
-#define MPQ_ADD(slot, a, b) do { } while (0)
-#endif
+// developer instrumentation (tools/conv_timing.py wino43): per-workgroup cycle sums per phase, wave 0
+MP_TIMING_TABLE(g_timing_q, 256 * 8, mp_debug_read_timing_wino43)
+MP_TIMING_HEIGHT(g_timing_q_sel, 480, mp_debug_select_height_wino43)
 
-#ifndef MPQX
-#define MPQX 0     // developer elimination switches (timing only, results WRONG): 1 no input transform, 2 no DMA, 4 no fragment reads, 8 no epilogue
-#endif
 namespace {
 
 // an item's 32 tiles are 4 rows x 8 columns (16 x 32 output pixels, raw patch 18 x 34) or -- TC4 = 4 -- 8 rows x 4 columns (32 x 16
@@ -71,16 +56,14 @@ constexpr int SW4 = 8 * 36 * 2;                    // floats of a wave's transfo
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// LDS-DMA of 16 bytes per lane (mp_device.h), dropped by MPQX & 2.  LEAD = 1 behind a wave-uniform branch: the five wait states an
+// LDS-DMA of 16 bytes per lane (mp_device.h).  LEAD = 1 behind a wave-uniform branch: the five wait states an
 // SGPR base needs behind a VALU write must lie INSIDE the branch's own block (multipoint_amd/build.py checks it), so the statement
 // opens with two more
 template <int LEAD = 0>
 __device__ __forceinline__ void dma16(const float* sbase, unsigned voff_bytes, unsigned lds_byte)
 {
-    if (MPQX & 2) return;
     lds_dma<4, LEAD, 0>(sbase, voff_bytes, lds_byte);
 }
-constexpr bool BT6_COPY = MPQX & 131072;           // (timing only: the input transform without arithmetic)
 
 // F1: the layer's input is the first encoder block (Cin = 1 -> 64, conv_first.hip's arithmetic) of p.img, computed by this
 // kernel itself, PER UNIT and straight into the raw LDS ring (round 3; round 2 evaluated it per item into a global scratch that
@@ -193,9 +176,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     const unsigned raw_dummy = raw_lds + 3u * RB4 * 4u;
     auto raw_dma = [&](const float* src, unsigned boff_bytes, int j) __attribute__((always_inline)) {
         const unsigned dst = j == 0 ? raw_m0 + boff_bytes : (wave + 8 < NRB ? raw_m0 + 8192u + boff_bytes : raw_dummy);
-        if (MPQX & 16) return;
-        if (MPQX & 128) { dma16(p.in, (unsigned)lane * 16u, dst); return; }   // L1-hot source
-        dma16(src, (MPQX & 64) ? (unsigned)lane * 16u : rvoff[j], dst);
+        dma16(src, rvoff[j], dst);
     };
     // the unit's 36 weight blocks of 1 KiB over the waves: wave w issues blocks [u_first, u_first + u_cnt), up to three per site (two
     // sites per unit).  No dummy loads: the unit barrier's vmcnt(2) / vmcnt(3) leaves the NEWEST two / three loads in flight -- the raw /
@@ -204,14 +185,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     // blocks of 64 for 8 waves), so SIMDs 0, 1 (waves 0, 4 / 1, 5) issue 3 + 4 weight loads and SIMDs 2, 3 (waves 2, 6 / 3, 7) 6 + 5:
     // an LDS-DMA costs ~50 cycles of its SIMD's issue next to the MFMA stream, the extra raw block ~170.
     int u_first, u_cnt;
-    if constexpr (F1 && !(MPQX & 33554432)) {
-#if defined(MP_DMA_BAL) && MP_DMA_BAL == 0          // (developer A/B) no dummies, not balanced: 5 on waves 0-3, 4 on waves 4-7
-        constexpr int cnt_[8] = {5, 5, 5, 5, 4, 4, 4, 4}, first_[8] = {0, 5, 10, 15, 20, 24, 28, 32};
-#elif defined(MP_DMA_BAL) && MP_DMA_BAL == 3        // (developer A/B) SIMDs 0, 1: 8, SIMDs 2, 3: 10
-        constexpr int cnt_[8] = {4, 4, 5, 5, 4, 4, 5, 5}, first_[8] = {0, 4, 8, 13, 18, 22, 26, 31};
-#else
+    if constexpr (F1) {
         constexpr int cnt_[8] = {3, 3, 6, 6, 4, 4, 5, 5}, first_[8] = {0, 3, 14, 20, 6, 10, 26, 31};
-#endif
         u_cnt = 3; u_first = 0;
 #pragma unroll
         for (int w = 0; w < 8; ++w) { u_cnt = wave == w ? cnt_[w] : u_cnt; u_first = wave == w ? first_[w] : u_first; }
@@ -220,7 +195,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     }
     // site 0: blocks k = 0..2 of this wave, site 1: k = 3..5 (wave-uniform branches)
     auto u_dma_site = [&](const float* ub, int buf, int site) __attribute__((always_inline)) {
-        if (MPQX & 32) return;
         if constexpr (VIN) {
             // (the pre-transformed-input instantiation sits at 252 registers: the branch-free form with four dummy re-loads of block 35
             // per unit -- five loads on every wave, blocks wave + 8 i -- keeps it free of scratch)
@@ -228,7 +202,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
             for (int i = 3 * site; i < (site ? 5 : 3); ++i) {
                 int b = wave + 8 * i;
                 b = b < 36 ? b : 35;
-                dma16((MPQX & 256) ? p.wpack : ub + b * 256, (unsigned)lane * 16u, us_lds + (unsigned)(buf * UB4 + b * 256) * 4u);
+                dma16(ub + b * 256, (unsigned)lane * 16u, us_lds + (unsigned)(buf * UB4 + b * 256) * 4u);
             }
             return;
         }
@@ -236,7 +210,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
         for (int k = 3 * site; k < 3 * site + 3; ++k)
             if (k < u_cnt) {
                 const int b = u_first + k;
-                dma16<1>((MPQX & 256) ? p.wpack : ub + b * 256, (unsigned)lane * 16u, us_lds + (unsigned)(buf * UB4 + b * 256) * 4u);
+                dma16<1>(ub + b * 256, (unsigned)lane * 16u, us_lds + (unsigned)(buf * UB4 + b * 256) * 4u);
             }
     };
     auto u_ptr = [&](int slice) __attribute__((always_inline)) -> const float* {      // unit 0 of a slice
@@ -269,7 +243,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     // pass 2: row `sub6`: scratch pairs [sub6][0..5]; V[ch][tile][pos = 6*sub6 + j]
     const int p2_write = (2 * w_cp * 32 + w_tile) * 36 + 6 * sub6;
     f32x2 td[6], tr[6];
-    f32x2 tq[6], tq2[6];                                 // MPQX & 65536 only
     // the lane's read position in the raw buffer the NEXT transform reads (two registers: rows 0-3 and rows 4-5 are
     // within a ds_read2_b64's offset range of them); advanced inside the VALU cluster of pass 1b, where an add is cheap
     // (absolute LDS byte addresses, so that the reads take the registers as they are)
@@ -277,29 +250,18 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     const unsigned p1_base = lds_addr(raw) + (unsigned)p1_read * 4u;
     unsigned p1_a = p1_base, p1_b = p1_base + 4u * PX * 16u;
     auto tf_pass1 = [&]() __attribute__((always_inline)) {
-        if (MPQX & (1 | 16384)) return;
-        if (MPQX & 65536) {               // timing only: the reads are issued, nothing depends on them until the unit's end
-#pragma unroll
-            for (int i = 0; i < 4; ++i) tq[i] = reinterpret_cast<lds_pair_ptr>(p1_a)[i * PX * 2];
-#pragma unroll
-            for (int i = 4; i < 6; ++i) tq[i] = reinterpret_cast<lds_pair_ptr>(p1_b)[(i - 4) * PX * 2];
-            return;
-        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) td[i] = reinterpret_cast<lds_pair_ptr>(p1_a)[i * PX * 2];
 #pragma unroll
         for (int i = 4; i < 6; ++i) td[i] = reinterpret_cast<lds_pair_ptr>(p1_b)[(i - 4) * PX * 2];
     };
     auto tf_pass1b = [&](unsigned next_byte) __attribute__((always_inline)) {   // next_byte: raw buffer of the next transform
-        if (MPQX & 1) return;
-        bt6<BT6_COPY>(td, tr);                            // tr[i'] = (B^T d)[i'][column sub6]
+        bt6(td, tr);                            // tr[i'] = (B^T d)[i'][column sub6]
         p1_a = p1_base + next_byte; p1_b = p1_base + 4u * PX * 16u + next_byte;
     };
     // the LDS write path takes two 8-byte stores per MFMA gap for free and saturates beyond (docs/HISTORY.md A.3): the transform's
     // stores go out in pairs, one pair per gap
     auto tf_pass1w = [&](int k) __attribute__((always_inline)) {                // rows 2k, 2k+1 of the scratch
-        if (MPQX & 1) return;
-        if (MPQX & 32768) { asm volatile("" :: "v"(tr[2 * k]), "v"(tr[2 * k + 1])); return; }     // timing only: no store
         // lanes 6, 7 of a window sit out: three lanes storing to one address are a 3-way bank conflict on every store
         unsigned long long save;
         if (k == 0)
@@ -313,12 +275,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
                          : "=&s"(save) : "v"(scr_w), "v"(tr[4]), "v"(tr[5]), "s"(0x3F3F3F3F3F3F3F3Full) : "memory");
     };
     auto tf_pass2 = [&]() __attribute__((always_inline)) {
-        if (MPQX & (1 | 16384)) return;
-        if (MPQX & 65536) {
-#pragma unroll
-            for (int j = 0; j < 6; ++j) tq2[j] = *reinterpret_cast<const f32x2*>(&myscr[(sub6 * 6 + j) * 2]);
-            return;
-        }
 #pragma unroll
         for (int j = 0; j < 6; ++j) td[j] = *reinterpret_cast<const f32x2*>(&myscr[(sub6 * 6 + j) * 2]);
     };
@@ -326,12 +282,9 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     // packed results go out as they are (hipcc pairs them into ds_write_b64 through nine v_mov)
     const unsigned p2_addr = lds_addr(Vs) + (unsigned)p2_write * 4u;
     auto tf_pass2b = [&]() __attribute__((always_inline)) {
-        if (MPQX & 1) return;
-        bt6<BT6_COPY>(td, tr);                            // tr[j'] = V[row sub6][j']
+        bt6(td, tr);                            // tr[j'] = V[row sub6][j']
     };
     auto tf_pass2w = [&](int buf, int k) __attribute__((always_inline)) {       // positions 2k, 2k+1 of both channels
-        if (MPQX & 1) return;
-        if (MPQX & 262144) { asm volatile("" :: "v"(tr[2 * k]), "v"(tr[2 * k + 1])); return; }    // timing only: no store
         const unsigned a0 = p2_addr + (unsigned)buf * (VB4 * 4u), a1 = a0 + 32u * 36u * 4u;
         const int j = 2 * k;
         unsigned long long save;
@@ -417,7 +370,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     auto gather_x = [&](float (&x)[9], const int j) __attribute__((always_inline)) {
         const lds_f32_ptr xp = reinterpret_cast<lds_f32_ptr>(pg_x[j]);
 #pragma unroll
-        for (int t = 0; t < 9; ++t) x[t] = (MPQX & 16777216) ? 1.f : xp[(t / 3) * IW1 + (t % 3)];
+        for (int t = 0; t < 9; ++t) x[t] = xp[(t / 3) * IW1 + (t % 3)];
     };
     auto prod_step = [&](const int k, const unsigned wbuf, const int j, const float (&x)[9]) __attribute__((always_inline)) {
         const lds_f32x4_ptr wp = reinterpret_cast<lds_f32x4_ptr>(pc_wv);
@@ -426,8 +379,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
             pd_ = bp[0];
             pw_[0] = wp[0]; pw_[1] = wp[1]; pw_[2] = wp[2];
         } else if (k <= 9) {
-            if (MPQX & 8388608) asm volatile("" :: "v"(pw_[(k - 1) >> 2][(k - 1) & 3]), "v"(x[k - 1]));       // (timing only: no small MFMAs)
-            else pd_ = __builtin_amdgcn_mfma_f32_4x4x1f32(pw_[(k - 1) >> 2][(k - 1) & 3], x[k - 1], pd_, 0, 0, 0);
+            pd_ = __builtin_amdgcn_mfma_f32_4x4x1f32(pw_[(k - 1) >> 2][(k - 1) & 3], x[k - 1], pd_, 0, 0, 0);
         } else {
             // ReLU only: the block's BatchNorm was folded at load time -- into p.w1 / p.b1 for conv -> BN -> ReLU models, into this
             // layer's U and bias otherwise (model_load.hip build_encoder) -- which takes two packed multiply-adds and two LDS reads per
@@ -564,7 +516,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     const bool t_on = ((POOL ? p.H : -p.H) == g_timing_q_sel);
 #endif
     for (;;) {
-        MPQ_T(t_item);
+        MP_CLOCK(t_item);
         f32x4 acc[36];
         const int item_next = item + stride;
         const bool has_next = item_next < item_end;
@@ -573,9 +525,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
         const float* unext = u_ptr(next_slice);
         // schedule of the input transform inside a unit (group g, slot e behind the e-th MFMA of the group)
         auto tf_at = [&](const int g, const int e, const int vb) __attribute__((always_inline)) {
-#ifndef MP_TF_SCHED
-#define MP_TF_SCHED -1
-#endif
             // slots (group, MFMA of the group) of: raw reads | column pass + hand-over stores 0 | 1 | 2 | scratch reads | row pass + V stores 0 | 1 | 2.
             // Row 0: the schedule of rounds 3-5, kept for the fused launch (its production steps fill the neighbouring slots) and the
             // 32 x 16-pixel items.  Row 1 (round 6): the row pass one slot earlier and its stores one per group instead of back to back --
@@ -584,7 +533,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
             constexpr int S[2][8][2] = {
                 {{0, 2}, {2, 2}, {2, 3}, {3, 1}, {3, 2}, {5, 2}, {5, 3}, {6, 1}},
                 {{0, 2}, {2, 2}, {2, 3}, {3, 1}, {3, 2}, {4, 3}, {5, 1}, {6, 1}}};
-            constexpr int TFS = MP_TF_SCHED >= 0 ? MP_TF_SCHED : ((TC4 == 8 && !F1) ? 1 : 0);
+            constexpr int TFS = (TC4 == 8 && !F1) ? 1 : 0;
             auto at = [&](const int k) { return g == S[TFS][k][0] && e == S[TFS][k][1]; };
             if (at(0)) tf_pass1();
             if (at(1)) { tf_pass1b(F1 ? (unsigned)vb * (RB4 * 4u) : 3u * RB4 * 4u - rd_byte - rt_byte); tf_pass1w(0); }   // unit n+1 transforms raw(n+2): ring of 3 (F1: of 2, buffer n & 1)
@@ -603,8 +552,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
             // early: +-0 / +0.9 % -- profiles/r06_transform_schedules.txt)
             constexpr int slot_g[11] = {0, 0, 1, 1, 1, 2, 3, 4, 4, 4, 5};
             constexpr int slot_e[11] = {1, 3, 1, 2, 3, 1, 3, 1, 2, 3, 1};
-            if (MPQX & 4194304) return;                            // (timing only: no production at all)
-            if (g == 0 && e == 0 && !(MPQX & 2097152)) { if (wave + 8 < NRB) produce(wbuf, 1); }      // (2097152, timing only: not the second block)
+            if (g == 0 && e == 0) { if (wave + 8 < NRB) produce(wbuf, 1); }
 #pragma unroll
             for (int k = 0; k <= 10; ++k)
                 if (g == slot_g[k] && e == slot_e[k]) prod_step(k, wbuf, 0, px_);
@@ -620,7 +568,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
             const float* const urn = Us + (vb ^ 1) * UB4 + a_base;
             const float* const vrn = Vs + vsn * VB4 + b_base;
             const float* const un2 = c + 2 < NC ? up + (long long)(c + 2) * UB4 : unext + (long long)(c + 2 - NC) * UB4;
-            MPQ_T(t_u0);
+            MP_CLOCK(t_u0);
 #ifdef MP_TIMING
             unsigned long long t_b0 = 0, t_b1 = 0;
 #endif
@@ -634,7 +582,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
                     __builtin_amdgcn_sched_barrier(0);
                     if constexpr (!VIN) { if (e != 2) tf_at(g, e, vb); }
                     if constexpr (F1) prod_at(g, e, vb);
-                    if (e == 0 && !(MPQX & 4)) {
+                    if (e == 0) {
                         // fragments two groups ahead; groups 7, 8 fetch groups 0, 1 of the NEXT unit (behind the unit barrier)
                         af[(g + 2) % 3] = *reinterpret_cast<const f32x4*>(g + 2 < 9 ? &ur[4 * (g + 2)] : &urn[4 * (g - 7)]);
                         bf[(g + 2) % 3] = *reinterpret_cast<const f32x4*>(g + 2 < 9 ? &vr[4 * (g + 2)] : &vrn[4 * (g - 7)]);
@@ -667,10 +615,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
                             if constexpr (F1) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");     // (no raw DMA in flight: raw(n+2) was produced above)
                             else if constexpr (VIN) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");   // U(n+1), V(n+2) landed; V(n+3) stays in flight
                             else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-                            if (MPQX & 65536) {
-#pragma unroll
-                                for (int q = 0; q < 6; ++q) asm volatile("" :: "v"(tq[q]), "v"(tq2[q]));
-                            }
 #ifdef MP_TIMING
                             t_b1 = __builtin_amdgcn_s_memtime();
 #endif
@@ -683,9 +627,9 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            MPQ_T(t_u1);
-            MPQ_ADD(0, t_u0, t_u1);                                   // a unit incl. its barrier
-            MPQ_ADD(1, t_b0, t_b1);                                   // the DMA wait alone (slot 4: the barrier behind it)
+            MP_CLOCK(t_u1);
+            MP_CLOCK_ADD(0, t_u0, t_u1);                                   // a unit incl. its barrier
+            MP_CLOCK_ADD(1, t_b0, t_b1);                                   // the DMA wait alone (slot 4: the barrier behind it)
         };
         auto unit = [&](const int c, auto first_tag, auto vb_tag, auto vs_tag) __attribute__((always_inline)) {
             unit_body(c, first_tag, vb_tag, vs_tag);
@@ -723,62 +667,32 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
         unit(NC - 1, std::false_type{}, VB1{}, VB1{});
         }
 
-        MPQ_T(t_e0);
-        MPQ_ADD(3, t_item, t_e0);                                      // whole unit loop of the item
+        MP_CLOCK(t_e0);
+        MP_CLOCK_ADD(3, t_item, t_e0);                                      // whole unit loop of the item
         // F1: the image patch of item k+2 -> this item's patch buffer (last read while unit 13 was multiplied); in flight across the epilogue
         if constexpr (F1) { if (item_next + stride < item_end) patch_dma(decode(item_next + stride), cur_par); }
         // ---- output transform Y = A^T M A in registers, bias / ReLU / BN, [2x2 max-pool], store ----
         // lane = tile (lane & 15) of the wave's tile block, registers r = output channels 4 * (lane >> 4) + r of its channel block
-        if (MPQX & 8) {
-            float sink = 0.f;
-#pragma unroll
-            for (int s2 = 0; s2 < 36; ++s2) sink += acc[s2][0] + acc[s2][1] + acc[s2][2] + acc[s2][3];
-            if (sink == 123.456f) p.out[tid] = sink;
-        } else {
-            const int tl = tb * 16 + (lane & 15);                       // tile of the item: row tl / TC4, column tl % TC4
-            const int cl = cb * 16 + 4 * (lane >> 4);                   // first of this lane's 4 output channels in the slice
-            const f32x4 b4 = *reinterpret_cast<const f32x4*>(&prm[cl]);
-            const f32x4 s4 = *reinterpret_cast<const f32x4*>(&prm[64 + cl]);
-            const f32x4 t4 = *reinterpret_cast<const f32x4*>(&prm[128 + cl]);
-            const int oy = cur.y0 + 4 * (tl / TC4), ox = cur.x0 + 4 * (tl % TC4);
-            const int ch0 = (SPLIT ? cur.slice >> p.ks_shift : cur.slice) * 64 + cl;
-            const int cs = p.out_cstride;
-            // per channel pair h (registers 2h, 2h+1): transform, activation, [pool] -- the 72 accumulator registers of a
-            // finished pair are dead before the next one starts (register budget: 256 per lane); the first pair's results
-            // wait in registers so that every pixel is ONE 16-byte store of the lane's 4 channels
-            constexpr int NO = POOL ? 2 : 4;                            // output rows / columns per tile
-            f32x2 keep[NO][NO];
-            // SPLIT: this item's share of the sum over input channels leaves as pre-bias output tiles; split_reduce_kernel (conv_split.hip),
-            // the next launch on the stream, adds the ranges' shares up in range order (deterministic) and runs the rest of the epilogue
-            if constexpr (SPLIT) {
-                unsigned long long* const part = reinterpret_cast<unsigned long long*>(p.split_scratch) + (long long)item * (2 * 16 * 512) + tid;
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    f32x2 tcol[4][6];
-#pragma unroll
-                    for (int j = 0; j < 6; ++j) {
-                        f32x2 m[6], y[4];
-#pragma unroll
-                        for (int i = 0; i < 6; ++i) m[i] = f32x2{acc[6 * i + j][2 * h], acc[6 * i + j][2 * h + 1]};
-                        at6s(m, y);
-#pragma unroll
-                        for (int a = 0; a < 4; ++a) tcol[a][j] = y[a];
-                    }
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) {
-                        f32x2 y[4];
-                        at6s(tcol[a], y);
-#pragma unroll
-                        for (int b = 0; b < 4; ++b)
-                            part[(h * 16 + a * 4 + b) * 512] = __builtin_bit_cast(unsigned long long, y[b]);
-                    }
-                }
-            }
-            if constexpr (!SPLIT) {
+        const int tl = tb * 16 + (lane & 15);                       // tile of the item: row tl / TC4, column tl % TC4
+        const int cl = cb * 16 + 4 * (lane >> 4);                   // first of this lane's 4 output channels in the slice
+        const f32x4 b4 = *reinterpret_cast<const f32x4*>(&prm[cl]);
+        const f32x4 s4 = *reinterpret_cast<const f32x4*>(&prm[64 + cl]);
+        const f32x4 t4 = *reinterpret_cast<const f32x4*>(&prm[128 + cl]);
+        const int oy = cur.y0 + 4 * (tl / TC4), ox = cur.x0 + 4 * (tl % TC4);
+        const int ch0 = (SPLIT ? cur.slice >> p.ks_shift : cur.slice) * 64 + cl;
+        const int cs = p.out_cstride;
+        // per channel pair h (registers 2h, 2h+1): transform, activation, [pool] -- the 72 accumulator registers of a
+        // finished pair are dead before the next one starts (register budget: 256 per lane); the first pair's results
+        // wait in registers so that every pixel is ONE 16-byte store of the lane's 4 channels
+        constexpr int NO = POOL ? 2 : 4;                            // output rows / columns per tile
+        f32x2 keep[NO][NO];
+        // SPLIT: this item's share of the sum over input channels leaves as pre-bias output tiles; split_reduce_kernel (conv_split.hip),
+        // the next launch on the stream, adds the ranges' shares up in range order (deterministic) and runs the rest of the epilogue
+        if constexpr (SPLIT) {
+            unsigned long long* const part = reinterpret_cast<unsigned long long*>(p.split_scratch) + (long long)item * (2 * 16 * 512) + tid;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                f32x2 tcol[4][6];                                       // T[a][j] = sum_i A^T[a][i] M[i][j]
-                if constexpr (!SPLIT) {
+                f32x2 tcol[4][6];
 #pragma unroll
                 for (int j = 0; j < 6; ++j) {
                     f32x2 m[6], y[4];
@@ -788,112 +702,135 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
 #pragma unroll
                     for (int a = 0; a < 4; ++a) tcol[a][j] = y[a];
                 }
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    f32x2 y[4];
+                    at6s(tcol[a], y);
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+                        part[(h * 16 + a * 4 + b) * 512] = __builtin_bit_cast(unsigned long long, y[b]);
                 }
-                const f32x2 bb = {b4[2 * h], b4[2 * h + 1]}, ss = {s4[2 * h], s4[2 * h + 1]}, tt = {t4[2 * h], t4[2 * h + 1]};
-                f32x2 res[NO][NO];
-                if constexpr (POOL) {
-                    // Pool BEFORE the activation: one activation per pooled value instead of four (-17 % of the epilogue's vector
-                    // instructions, and next to the fp32 MFMA stream every vector instruction is matrix-pipe time).  Bit for bit the
-                    // same result: bias add, ReLU and the BatchNorm affine are monotonic per channel -- non-decreasing where the
-                    // scale is >= 0, non-increasing where it is negative -- so max(f(x_i)) = f(max x_i), or f(min x_i) for a negative
-                    // scale.  The sign g = +-1 of the channel's scale is folded into the multiply-add that scales and adds the bias
-                    // anyway (x' = g x exactly: an fma is odd in its product and addend), one max-pool serves both signs
-                    // (max g x = g * max / min x), and the activation of the sign-folded value needs no multiplication back:
-                    //   conv -> ReLU -> BN:  s relu(x) + t = |s| clamp(x') + t,  clamp = max(x', 0) for g = 1, min(x', 0) for g = -1
-                    //                        (one v_med3_i32 on the float bits, as the ReLU is one v_max_i32)
-                    //   conv -> BN -> ReLU:  relu(s x + t) = relu(|s| x' + t)
-                    // (tests/test_gpu_parity.py::test_pooled_epilogue_pools_before_the_activation compares against the direct kernels.)
-                    const f32x4 g4 = *reinterpret_cast<const f32x4*>(&prm[192 + cl]);
-                    const f32x4 lo4 = *reinterpret_cast<const f32x4*>(&prm[256 + cl]), hi4 = *reinterpret_cast<const f32x4*>(&prm[320 + cl]);
-                    const f32x2 gg = {g4[2 * h], g4[2 * h + 1]};
-                    const f32x2 gb = bb * gg;                                                  // g * bias (exact)
-                    constexpr float A1 = (float)MP_W43_A, A2 = A1 * A1, A3 = A2 * A1, A4 = A2 * A2;
-                    const f32x2 gk[5] = {gg, gg * f32x2{A1, A1}, gg * f32x2{A2, A2}, gg * f32x2{A3, A3}, gg * f32x2{A4, A4}};      // g * sigma_r sigma_c
-                    f32x2 xv[4][4];
+            }
+        }
+        if constexpr (!SPLIT) {
 #pragma unroll
-                    for (int a = 0; a < 4; ++a) {
-                        f32x2 y[4];
-                        at6s(tcol[a], y);
+        for (int h = 0; h < 2; ++h) {
+            f32x2 tcol[4][6];                                       // T[a][j] = sum_i A^T[a][i] M[i][j]
+            if constexpr (!SPLIT) {
 #pragma unroll
-                        for (int b = 0; b < 4; ++b) {
-                            const int e = (a == 1 ? 1 : a == 2 ? 2 : 0) + (b == 1 ? 1 : b == 2 ? 2 : 0);      // w43_out_scale(a, b) = A1^e
-                            xv[a][b] = __builtin_elementwise_fma(y[b], gk[e], gb);
-                        }
-                    }
+            for (int j = 0; j < 6; ++j) {
+                f32x2 m[6], y[4];
 #pragma unroll
-                    for (int a = 0; a < NO; ++a)
+                for (int i = 0; i < 6; ++i) m[i] = f32x2{acc[6 * i + j][2 * h], acc[6 * i + j][2 * h + 1]};
+                at6s(m, y);
 #pragma unroll
-                        for (int b = 0; b < NO; ++b) {
-                            f32x2 m;
-#pragma unroll
-                            for (int r = 0; r < 2; ++r)
-                                m[r] = fmaxf(fmaxf(xv[2 * a][2 * b][r], xv[2 * a][2 * b + 1][r]), fmaxf(xv[2 * a + 1][2 * b][r], xv[2 * a + 1][2 * b + 1][r]));
-                            if (BNF) {
-                                m = __builtin_elementwise_fma(m, ss, tt);
-                                m = f32x2{relu_bits(m[0]), relu_bits(m[1])};
-                            } else {
-#pragma unroll
-                                for (int r = 0; r < 2; ++r)
-                                    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(m[r]) : "v"(m[r]), "v"(lo4[2 * h + r]), "v"(hi4[2 * h + r]));
-                                m = __builtin_elementwise_fma(m, ss, tt);
-                            }
-                            res[a][b] = m;
-                        }
-                } else {
-                f32x2 yv[4][4];                                         // [row a][col b] -> this pair's 2 channels
+                for (int a = 0; a < 4; ++a) tcol[a][j] = y[a];
+            }
+            }
+            const f32x2 bb = {b4[2 * h], b4[2 * h + 1]}, ss = {s4[2 * h], s4[2 * h + 1]}, tt = {t4[2 * h], t4[2 * h + 1]};
+            f32x2 res[NO][NO];
+            if constexpr (POOL) {
+                // Pool BEFORE the activation: one activation per pooled value instead of four (-17 % of the epilogue's vector
+                // instructions, and next to the fp32 MFMA stream every vector instruction is matrix-pipe time).  Bit for bit the
+                // same result: bias add, ReLU and the BatchNorm affine are monotonic per channel -- non-decreasing where the
+                // scale is >= 0, non-increasing where it is negative -- so max(f(x_i)) = f(max x_i), or f(min x_i) for a negative
+                // scale.  The sign g = +-1 of the channel's scale is folded into the multiply-add that scales and adds the bias
+                // anyway (x' = g x exactly: an fma is odd in its product and addend), one max-pool serves both signs
+                // (max g x = g * max / min x), and the activation of the sign-folded value needs no multiplication back:
+                //   conv -> ReLU -> BN:  s relu(x) + t = |s| clamp(x') + t,  clamp = max(x', 0) for g = 1, min(x', 0) for g = -1
+                //                        (one v_med3_i32 on the float bits, as the ReLU is one v_max_i32)
+                //   conv -> BN -> ReLU:  relu(s x + t) = relu(|s| x' + t)
+                // (tests/test_gpu_parity.py::test_pooled_epilogue_pools_before_the_activation compares against the direct kernels.)
+                const f32x4 g4 = *reinterpret_cast<const f32x4*>(&prm[192 + cl]);
+                const f32x4 lo4 = *reinterpret_cast<const f32x4*>(&prm[256 + cl]), hi4 = *reinterpret_cast<const f32x4*>(&prm[320 + cl]);
+                const f32x2 gg = {g4[2 * h], g4[2 * h + 1]};
+                const f32x2 gb = bb * gg;                                                  // g * bias (exact)
+                constexpr float A1 = (float)MP_W43_A, A2 = A1 * A1, A3 = A2 * A1, A4 = A2 * A2;
+                const f32x2 gk[5] = {gg, gg * f32x2{A1, A1}, gg * f32x2{A2, A2}, gg * f32x2{A3, A3}, gg * f32x2{A4, A4}};      // g * sigma_r sigma_c
+                f32x2 xv[4][4];
 #pragma unroll
                 for (int a = 0; a < 4; ++a) {
                     f32x2 y[4];
                     at6s(tcol[a], y);
 #pragma unroll
                     for (int b = 0; b < 4; ++b) {
-                        f32x2 v = w43_add_bias(y[b], a, b, bb);
-                        if (BNF) { v = v * ss + tt; v = f32x2{relu_bits(v[0]), relu_bits(v[1])}; }
-                        else { v = f32x2{relu_bits(v[0]), relu_bits(v[1])}; v = v * ss + tt; }
-                        yv[a][b] = v;
+                        const int e = (a == 1 ? 1 : a == 2 ? 2 : 0) + (b == 1 ? 1 : b == 2 ? 2 : 0);      // w43_out_scale(a, b) = A1^e
+                        xv[a][b] = __builtin_elementwise_fma(y[b], gk[e], gb);
                     }
                 }
 #pragma unroll
                 for (int a = 0; a < NO; ++a)
 #pragma unroll
-                    for (int b = 0; b < NO; ++b) res[a][b] = yv[a][b];
+                    for (int b = 0; b < NO; ++b) {
+                        f32x2 m;
+#pragma unroll
+                        for (int r = 0; r < 2; ++r)
+                            m[r] = fmaxf(fmaxf(xv[2 * a][2 * b][r], xv[2 * a][2 * b + 1][r]), fmaxf(xv[2 * a + 1][2 * b][r], xv[2 * a + 1][2 * b + 1][r]));
+                        if (BNF) {
+                            m = __builtin_elementwise_fma(m, ss, tt);
+                            m = f32x2{relu_bits(m[0]), relu_bits(m[1])};
+                        } else {
+#pragma unroll
+                            for (int r = 0; r < 2; ++r)
+                                asm("v_med3_i32 %0, %1, %2, %3" : "=v"(m[r]) : "v"(m[r]), "v"(lo4[2 * h + r]), "v"(hi4[2 * h + r]));
+                            m = __builtin_elementwise_fma(m, ss, tt);
+                        }
+                        res[a][b] = m;
+                    }
+            } else {
+            f32x2 yv[4][4];                                         // [row a][col b] -> this pair's 2 channels
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                f32x2 y[4];
+                at6s(tcol[a], y);
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    f32x2 v = w43_add_bias(y[b], a, b, bb);
+                    if (BNF) { v = v * ss + tt; v = f32x2{relu_bits(v[0]), relu_bits(v[1])}; }
+                    else { v = f32x2{relu_bits(v[0]), relu_bits(v[1])}; v = v * ss + tt; }
+                    yv[a][b] = v;
                 }
-                if (h == 0) {
+            }
+#pragma unroll
+            for (int a = 0; a < NO; ++a)
+#pragma unroll
+                for (int b = 0; b < NO; ++b) res[a][b] = yv[a][b];
+            }
+            if (h == 0) {
+#pragma unroll
+                for (int a = 0; a < NO; ++a)
+#pragma unroll
+                    for (int b = 0; b < NO; ++b) keep[a][b] = res[a][b];
+            } else {
+                const int Ho = POOL ? p.H >> 1 : p.H, Wo = POOL ? p.W >> 1 : p.W;
+                const int py0 = POOL ? oy >> 1 : oy, px0 = POOL ? ox >> 1 : ox;
+                // a uniform per-image base + 32-bit byte offsets (an image's output is far below 4 GB).  NHWC: pixel stride
+                // cs floats; planar [B][cout/4][Ho][Wo][4]: this lane's quad is plane ch0 / 4, pixel stride 16 bytes
+                char* const img_base = reinterpret_cast<char*>(
+                    p.out_planar ? p.out + (long long)cur.img * (p.cout / 4) * Ho * Wo * 4
+                                 : p.out + (long long)cur.img * Ho * Wo * cs + p.out_coff);
+                const unsigned ps = p.out_planar ? 16u : (unsigned)cs * 4u;                       // bytes per pixel step
+                const unsigned rs = (unsigned)Wo * ps;                                            // bytes per row step
+                const unsigned o0 = p.out_planar ? (unsigned)(((ch0 >> 2) * Ho + py0) * Wo + px0) * 16u
+                                                 : (unsigned)((py0 * Wo + px0) * cs + ch0) * 4u;
+                // H and W are multiples of 4 (conv_wino43_supports) and tiles are 4-aligned: a tile is inside the image or
+                // outside as a whole, and cout is a multiple of 4 -- ONE test, then NO x NO unconditional 16-byte stores
+                if (oy < p.H && ox < p.W && ch0 < p.cout) {
 #pragma unroll
                     for (int a = 0; a < NO; ++a)
 #pragma unroll
-                        for (int b = 0; b < NO; ++b) keep[a][b] = res[a][b];
-                } else {
-                    const int Ho = POOL ? p.H >> 1 : p.H, Wo = POOL ? p.W >> 1 : p.W;
-                    const int py0 = POOL ? oy >> 1 : oy, px0 = POOL ? ox >> 1 : ox;
-                    // a uniform per-image base + 32-bit byte offsets (an image's output is far below 4 GB).  NHWC: pixel stride
-                    // cs floats; planar [B][cout/4][Ho][Wo][4]: this lane's quad is plane ch0 / 4, pixel stride 16 bytes
-                    char* const img_base = reinterpret_cast<char*>(
-                        p.out_planar ? p.out + (long long)cur.img * (p.cout / 4) * Ho * Wo * 4
-                                     : p.out + (long long)cur.img * Ho * Wo * cs + p.out_coff);
-                    const unsigned ps = p.out_planar ? 16u : (unsigned)cs * 4u;                       // bytes per pixel step
-                    const unsigned rs = (unsigned)Wo * ps;                                            // bytes per row step
-                    const unsigned o0 = p.out_planar ? (unsigned)(((ch0 >> 2) * Ho + py0) * Wo + px0) * 16u
-                                                     : (unsigned)((py0 * Wo + px0) * cs + ch0) * 4u;
-                    // H and W are multiples of 4 (conv_wino43_supports) and tiles are 4-aligned: a tile is inside the image or
-                    // outside as a whole, and cout is a multiple of 4 -- ONE test, then NO x NO unconditional 16-byte stores
-                    if (oy < p.H && ox < p.W && ch0 < p.cout) {
-#pragma unroll
-                        for (int a = 0; a < NO; ++a)
-#pragma unroll
-                            for (int b = 0; b < NO; ++b) {
-                                const f32x4 v = {keep[a][b][0], keep[a][b][1], res[a][b][0], res[a][b][1]};
-                                // (non-temporal stores, measured: un-pooled NHWC outputs +10 % -- the 64-byte pieces of a pixel's line written
-                                // by four waves no longer merge in L2 --, pooled planar ones -1 % for the launch and +1 % for its consumer)
-                                *reinterpret_cast<f32x4*>(img_base + (o0 + (unsigned)a * rs + (unsigned)b * ps)) = v;
-                            }
-                    }
+                        for (int b = 0; b < NO; ++b) {
+                            const f32x4 v = {keep[a][b][0], keep[a][b][1], res[a][b][0], res[a][b][1]};
+                            // (non-temporal stores, measured: un-pooled NHWC outputs +10 % -- the 64-byte pieces of a pixel's line written
+                            // by four waves no longer merge in L2 --, pooled planar ones -1 % for the launch and +1 % for its consumer)
+                            *reinterpret_cast<f32x4*>(img_base + (o0 + (unsigned)a * rs + (unsigned)b * ps)) = v;
+                        }
                 }
             }
-            }
         }
-        MPQ_T(t_e1);
-        MPQ_ADD(2, t_e0, t_e1);                                        // epilogue
+        }
+        MP_CLOCK(t_e1);
+        MP_CLOCK_ADD(2, t_e0, t_e1);                                        // epilogue
 #ifdef MP_TIMING
         tsum[7] += 1;
         if (!has_next && tid == 0 && t_on)
@@ -950,7 +887,7 @@ __global__ __launch_bounds__(256) void wino43_vprod_kernel(const ConvParams p, l
 #pragma unroll
         for (int i = 0; i < 6; ++i)
             d[i] = *reinterpret_cast<const f32x2*>(base + ((long long)reflect_clamp(wy + i, p.H) * p.W + gx[j]) * p.in_cstride);
-        bt6<BT6_COPY>(d, o);
+        bt6(d, o);
 #pragma unroll
         for (int i = 0; i < 6; ++i) r[i][j] = o[i];
     }
@@ -959,8 +896,8 @@ __global__ __launch_bounds__(256) void wino43_vprod_kernel(const ConvParams p, l
 #pragma unroll
     for (int i = 0; i < 6; i += 2) {                     // two rows = 12 positions = three 16-byte stores per channel
         f32x2 a[6], b[6];
-        bt6<BT6_COPY>(r[i], a);
-        bt6<BT6_COPY>(r[i + 1], b);
+        bt6(r[i], a);
+        bt6(r[i + 1], b);
         *reinterpret_cast<f32x4*>(dst0 + 6 * i) = f32x4{a[0][0], a[1][0], a[2][0], a[3][0]};
         *reinterpret_cast<f32x4*>(dst0 + 6 * i + 4) = f32x4{a[4][0], a[5][0], b[0][0], b[1][0]};
         *reinterpret_cast<f32x4*>(dst0 + 6 * i + 8) = f32x4{b[2][0], b[3][0], b[4][0], b[5][0]};

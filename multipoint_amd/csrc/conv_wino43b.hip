@@ -33,12 +33,6 @@
 #include <algorithm>
 #include <type_traits>
 
-#ifndef MPB_DMA_EARLY
-#define MPB_DMA_EARLY 0
-#endif
-#ifndef MPQX
-#define MPQX 0     // developer elimination switches (timing only, results WRONG): 1 no input transform, 2 no DMA, 8 no epilogue
-#endif
 namespace {
 
 constexpr int UC4 = 4;                             // input channels per unit
@@ -48,7 +42,7 @@ constexpr int VB4 = 2 * VR4 + 2;                   // floats per V' buffer (16-b
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// LDS-DMA of 16 bytes per lane (mp_device.h), dropped by MPQX & 2.  OFF: the instruction's immediate offset, which moves the source
+// LDS-DMA of 16 bytes per lane (mp_device.h).  OFF: the instruction's immediate offset, which moves the source
 // AND the LDS destination (round-4 probe; docs/HISTORY.md 3.3) -- exactly what a block-for-block copy wants: one scalar source base,
 // one scalar destination base and one lane-offset register serve a wave's nine weight blocks (the unit bodies are short of scalar
 // registers, and a lane-offset register per block would be spilled: the epilogue needs every register, and a reload inside a unit
@@ -56,7 +50,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <int OFF = LDS_DMA_NO_OFFSET, int M0ADD = 0>
 __device__ __forceinline__ void dma16(const float* sbase, unsigned voff_bytes, unsigned lds_byte)
 {
-    if (MPQX & 2) return;
     lds_dma<4, 0, 1, OFF, M0ADD>(sbase, voff_bytes, lds_byte);
 }
 
@@ -200,9 +193,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
     const f32x4 zero4v = {0.f, 0.f, 0.f, 0.f};
     auto raw_dma = [&](const float* src, unsigned boff_bytes, int j, unsigned voff) __attribute__((always_inline)) {
         const unsigned dst = (wave + 4 * j < NRB) ? raw_m0 + (unsigned)j * 4096u + boff_bytes : raw_dummy;
-        if (MPQX & 16) return;                                            // (timing only)
-        if (MPQX & 64) { dma16(src, (unsigned)lane * 16u, dst); return; } // (timing only: a linear 1 KiB instead of the patch gather)
-        if (MPQX & 128) { dma16(p.in, voff, dst); return; }               // (timing only: the gather pattern on cache-hot addresses)
         if constexpr (ZPAD) {
             // lanes whose pixel lies outside the frame (offset ~0) are masked out of the DMA and write a zero granule into their slot
             // instead: every slot of the buffer is written each unit, by one or the other -- no branch in the unit body
@@ -225,7 +215,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
     const unsigned us_w = us_lds + (unsigned)wave * 9216u + 4096u;
     auto u_dma = [&](const float* ubw, auto buf_tag, auto i_tag) __attribute__((always_inline)) {        // ubw = ub + wave * 2304 + 1024 floats
         constexpr int buf = decltype(buf_tag)::value, i = decltype(i_tag)::value;
-        if (MPQX & 32) return;                                            // (timing only)
         if constexpr (i < 8) dma16<(i - 4) * 1024, buf * UB4 * 4>(ubw, lane16, us_w);
         else dma16<3072, buf * UB4 * 4 + 1024>(ubw, lane16 + 1024u, us_w);
     };
@@ -250,7 +239,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
     f32x2 ho[6];
     unsigned tf_ra = 0, tf_re = 0;                  // ... of the raw buffer the column pass reads (set once per unit)
     auto tf_read = [&](const int c) __attribute__((always_inline)) {
-        if (MPQX & 1) return;
         auto ro = [](int k) { return (k * P + (k >> 2)) * 2; };      // row k of the window, in 8-byte pairs
         const int o = c * 2;
 #pragma unroll
@@ -259,7 +247,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
         for (int i = 0; i < 4; ++i) hd[3 + i] = reinterpret_cast<lds_pair_ptr>(tf_ra)[o + ro(1 + i)];
     };
     auto tf_col = [&](const int c) __attribute__((always_inline)) {          // three rows of X of column c: 6 packed multiply-adds
-        if (MPQX & 1) return;
         const f32x2* d = hd;
         hx[0][c] = pk_fma_k<0>(d[0], K_PS, pk_fnma_k<1>(d[1], K_PS, d[2]));      // a^2 b^2 e0 + (e4 - (a^2 + b^2) e2): row 0 / row 5
         const f32x2 t0 = pk_fnma_k<1>(d[4], k_sq, d[6]);                         // m4 - s m2
@@ -267,11 +254,10 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
         hx[1][c] = pk_fma_k<0>(t1, k_pt, t0);                                    // t0 + p t1: row 1 / row 3
         hx[2][c] = pk_fnma_k<0>(t1, k_pt, t0);                                   // t0 - p t1: row 2 / row 4
     };
-    auto tf_row = [&](const int k) __attribute__((always_inline)) { if (!(MPQX & 1)) bt6(hx[k], ho); };
+    auto tf_row = [&](const int k) __attribute__((always_inline)) { bt6(hx[k], ho); };
     // V'[buf][c][6 row + j][lane], j = 2 jj, 2 jj + 1, both channels: four lane-linear stores (address = M0 + offset + 4 lane)
     const unsigned tf_m0[3] = {vs_lds + tf_row0, vs_lds + tf_row1, vs_lds + tf_row2};
     auto tf_store = [&](const int k, const int jj, auto vbuf_tag) __attribute__((always_inline)) {
-        if (MPQX & 1) return;
         constexpr int VBB = decltype(vbuf_tag)::value * VB4 * 4;           // byte offset of the V' buffer
         unsigned keep;
 #define MPB_VST(J)                                                                                                              \
@@ -407,14 +393,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
                         // DMAs: U(n+2) -> U[vb] from behind this unit's barrier (every fragment of U[vb] has been fetched) to group 1 of
                         // the next unit, one per three MFMAs; raw(n+4) in groups 2, 3 -- apart from the weights in time (the memory
                         // pipe returns in order: a weight DMA queued behind a patch DMA comes back at HBM latency)
-#if MPB_DMA_EARLY
-                        // (variant: all nine weight blocks behind the barrier, the patch DMAs two groups earlier)
-                        if (g == 7) { if (q == 1) u_dma(un2, VB{}, MPB_I(0)); if (q == 2) u_dma(un2, VB{}, MPB_I(1)); if (q == 4) u_dma(un2, VB{}, MPB_I(2)); if (q == 5) u_dma(un2, VB{}, MPB_I(3)); if (q == 7) u_dma(un2, VB{}, MPB_I(4)); }
-                        else if (g == 8) { if (q == 1) u_dma(un2, VB{}, MPB_I(5)); if (q == 3) u_dma(un2, VB{}, MPB_I(6)); if (q == 5) u_dma(un2, VB{}, MPB_I(7)); if (q == 7) u_dma(un2, VB{}, MPB_I(8)); }
-                        else if (g == 0) { if (q == 2) raw_dma(rsrc, r_dm, 0, rv0); if (q == 5) raw_dma(rsrc, r_dm, 1, rv1); }
-                        else if (g == 1) { if (q == 1) raw_dma(rsrc, r_dm, 2, rv2); }
-                        if (g == 0 && q == 0) { rv0 = rvl[0]; rv1 = rvl[64]; rv2 = rvl[128]; }
-#else
                         if (g == 7) { if (q == 1) u_dma(un2, VB{}, MPB_I(0)); if (q == 4) u_dma(un2, VB{}, MPB_I(1)); if (q == 7) u_dma(un2, VB{}, MPB_I(2)); }
                         else if (g == 8) { if (q == 2) u_dma(un2, VB{}, MPB_I(3)); if (q == 5) u_dma(un2, VB{}, MPB_I(4)); }
                         else if (g == 0) { if (q == 1) u_dma(un1, VN{}, MPB_I(5)); if (q == 4) u_dma(un1, VN{}, MPB_I(6)); if (q == 7) u_dma(un1, VN{}, MPB_I(7)); }
@@ -422,7 +400,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
                         else if (g == 2) { if (q == 1) raw_dma(rsrc, r_dm, 0, rv0); if (q == 5) raw_dma(rsrc, r_dm, 1, rv1); }
                         else if (g == 3) { if (q == 1) raw_dma(rsrc, r_dm, 2, rv2); }
                         if (g == 1 && q == 5) { rv0 = rvl[0]; rv1 = rvl[64]; rv2 = rvl[128]; }      // the gather offsets of this unit's patch DMAs
-#endif
                         // ROLE 0: column pass of unit n+2 (column c2 read and evaluated in group c2).  ROLE 1: row pass of unit n+1 -> V'[vb ^ 1]
                         // (row k evaluated in group 2 k, stored four dwords per slot).  ROLE 2: nothing.  ROLE 3 (pair 1, last unit of an item):
                         // the column pass of unit n+2 AND, behind the barrier, its row pass -> V'[vb], which every wave has finished reading
@@ -478,130 +455,123 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
         // ---- output transform Y = A^T M A in registers, bias / ReLU / BN, [2x2 max-pool], store ----
         // lane = tile (lane & 15) of the wave's tile block, registers r = output channels 4 * (lane >> 4) + r of column block m
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");               // the last MFMAs' results (asm statements: no hazard tracking)
-        if (MPQX & 8) {
-            float sink = 0.f;
+        int eln = lane;
+        asm volatile("" : "+v"(eln));                            // (opaque: the epilogue's lane constants are not hoisted out of the item loop)
+        const int tl = tb * 16 + (eln & 15);                        // tile T of the item (numbering: lane_values())
+        const int t_ty = TC4 == 8 ? (tl >> 2) & 3 : tl >> 2, t_tx = TC4 == 8 ? 4 * (tl >> 4) + (tl & 3) : tl & 3;
+        const int oy = cur.y0 + 4 * t_ty, ox = cur.x0 + 4 * t_tx;
+        const int cs = p.out_cstride;
+        constexpr int NO = POOL ? 2 : 4;                            // output rows / columns per tile
+        const int Ho = POOL ? p.H >> 1 : p.H, Wo = POOL ? p.W >> 1 : p.W;
+        const int py0 = POOL ? oy >> 1 : oy, px0 = POOL ? ox >> 1 : ox;
+        // MODE 0: the ordinary epilogue; 1 (SPLIT): this range's pre-bias output tiles -> split_scratch
+        unsigned long long* const part = SPLIT ? reinterpret_cast<unsigned long long*>(p.split_scratch) + (long long)item * (64 * 256) + tid : nullptr;
+        auto epilogue = [&](auto mode_tag) __attribute__((always_inline)) {
+        constexpr int MODE = decltype(mode_tag)::value;
 #pragma unroll
-            for (int s2 = 0; s2 < 36; ++s2) sink += acc[s2][0][0] + acc[s2][1][3];
-            if (sink == 123.456f) p.out[tid] = sink;
-        } else {
-            int eln = lane;
-            asm volatile("" : "+v"(eln));                            // (opaque: the epilogue's lane constants are not hoisted out of the item loop)
-            const int tl = tb * 16 + (eln & 15);                        // tile T of the item (numbering: lane_values())
-            const int t_ty = TC4 == 8 ? (tl >> 2) & 3 : tl >> 2, t_tx = TC4 == 8 ? 4 * (tl >> 4) + (tl & 3) : tl & 3;
-            const int oy = cur.y0 + 4 * t_ty, ox = cur.x0 + 4 * t_tx;
-            const int cs = p.out_cstride;
-            constexpr int NO = POOL ? 2 : 4;                            // output rows / columns per tile
-            const int Ho = POOL ? p.H >> 1 : p.H, Wo = POOL ? p.W >> 1 : p.W;
-            const int py0 = POOL ? oy >> 1 : oy, px0 = POOL ? ox >> 1 : ox;
-            // MODE 0: the ordinary epilogue; 1 (SPLIT): this range's pre-bias output tiles -> split_scratch
-            unsigned long long* const part = SPLIT ? reinterpret_cast<unsigned long long*>(p.split_scratch) + (long long)item * (64 * 256) + tid : nullptr;
-            auto epilogue = [&](auto mode_tag) __attribute__((always_inline)) {
-            constexpr int MODE = decltype(mode_tag)::value;
+        for (int m = 0; m < 2; ++m) {
+        const int cl = cbb * 32 + m * 16 + 4 * (eln >> 4);          // first of this lane's 4 output channels in the slice
+        const f32x4 b4 = *reinterpret_cast<const f32x4*>(&prm[cl]);
+        const f32x4 s4 = *reinterpret_cast<const f32x4*>(&prm[64 + cl]);
+        const f32x4 t4 = *reinterpret_cast<const f32x4*>(&prm[128 + cl]);
+        const int ch0 = (SPLIT ? cur.slice >> p.ks_shift : cur.slice) * 64 + cl;
+        f32x2 keep[NO][NO];
 #pragma unroll
-            for (int m = 0; m < 2; ++m) {
-            const int cl = cbb * 32 + m * 16 + 4 * (eln >> 4);          // first of this lane's 4 output channels in the slice
-            const f32x4 b4 = *reinterpret_cast<const f32x4*>(&prm[cl]);
-            const f32x4 s4 = *reinterpret_cast<const f32x4*>(&prm[64 + cl]);
-            const f32x4 t4 = *reinterpret_cast<const f32x4*>(&prm[128 + cl]);
-            const int ch0 = (SPLIT ? cur.slice >> p.ks_shift : cur.slice) * 64 + cl;
-            f32x2 keep[NO][NO];
+        for (int h = 0; h < 2; ++h) {
+            f32x2 tcol[4][6];                                       // T[a][j] = sum_i A^T[a][i] M[i][j]
+            {
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                f32x2 tcol[4][6];                                       // T[a][j] = sum_i A^T[a][i] M[i][j]
-                {
+            for (int j = 0; j < 6; ++j) {
+                f32x2 mm[6], y[4];
 #pragma unroll
-                for (int j = 0; j < 6; ++j) {
-                    f32x2 mm[6], y[4];
-#pragma unroll
-                    for (int i = 0; i < 6; ++i) {
-                        float lo, hi;
-                        MPB_ACC_RD(lo, acc[6 * i + j][m], (6 * i + j) * 2 + m, 2 * h);
-                        MPB_ACC_RD(hi, acc[6 * i + j][m], (6 * i + j) * 2 + m, 2 * h + 1);
-                        mm[i] = f32x2{lo, hi};
-                    }
-                    at6s(mm, y);
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) tcol[a][j] = y[a];
-                    __builtin_amdgcn_sched_barrier(0);      // (register peak: the scheduler otherwise hoists every accumulator read)
+                for (int i = 0; i < 6; ++i) {
+                    float lo, hi;
+                    MPB_ACC_RD(lo, acc[6 * i + j][m], (6 * i + j) * 2 + m, 2 * h);
+                    MPB_ACC_RD(hi, acc[6 * i + j][m], (6 * i + j) * 2 + m, 2 * h + 1);
+                    mm[i] = f32x2{lo, hi};
                 }
+                at6s(mm, y);
+#pragma unroll
+                for (int a = 0; a < 4; ++a) tcol[a][j] = y[a];
+                __builtin_amdgcn_sched_barrier(0);      // (register peak: the scheduler otherwise hoists every accumulator read)
+            }
+            }
+            if constexpr (MODE == 1) {
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    f32x2 y[4];
+                    at6s(tcol[a], y);
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) part[((m * 2 + h) * 16 + a * 4 + b) * 256] = __builtin_bit_cast(unsigned long long, y[b]);
                 }
-                if constexpr (MODE == 1) {
+            } else {
+            const f32x2 bb = {b4[2 * h], b4[2 * h + 1]}, ss = {s4[2 * h], s4[2 * h + 1]}, tt = {t4[2 * h], t4[2 * h + 1]};
+            // row a of the 4x4 output tile, pre-bias
+            auto out_row = [&](const int a, f32x2 (&y)[4]) __attribute__((always_inline)) { at6s(tcol[a], y); };
+            auto act = [&](f32x2 v, const int r, const int c) __attribute__((always_inline)) -> f32x2 {
+                v = w43_add_bias(v, r, c, bb);
+                if (BNF) { v = v * ss + tt; return f32x2{relu_bits(v[0]), relu_bits(v[1])}; }
+                v = f32x2{relu_bits(v[0]), relu_bits(v[1])};
+                return v * ss + tt;
+            };
+            // a uniform per-image base + 32-bit byte offsets (an image's output is far below 4 GB).  NHWC: pixel stride
+            // cs floats; planar [B][cout/4][Ho][Wo][4]: this lane's quad is plane ch0 / 4, pixel stride 16 bytes
+            char* const img_base = reinterpret_cast<char*>(
+                p.out_planar ? p.out + (long long)cur.img * (p.cout / 4) * Ho * Wo * 4
+                             : p.out + (long long)cur.img * Ho * Wo * cs + p.out_coff);
+            const unsigned ps = p.out_planar ? 16u : (unsigned)cs * 4u;                       // bytes per pixel step
+            const unsigned rs = (unsigned)Wo * ps;                                            // bytes per row step
+            const unsigned o0 = p.out_planar ? (unsigned)(((ch0 >> 2) * Ho + py0) * Wo + px0) * 16u
+                                             : (unsigned)((py0 * Wo + px0) * cs + ch0) * 4u;
+            const bool inside = py0 + NO <= Ho && px0 + NO <= Wo;     // the whole tile lies inside the frame
+            // one output row (pooled: one row pair) at a time: the register peak is what decides whether loop-carried
+            // values survive the epilogue in registers (a reload inside a unit body stalls on every DMA in flight)
 #pragma unroll
-                    for (int a = 0; a < 4; ++a) {
-                        f32x2 y[4];
-                        at6s(tcol[a], y);
+            for (int a = 0; a < NO; ++a) {
+                __builtin_amdgcn_sched_barrier(0);
+                f32x2 res[NO];
+                if constexpr (POOL) {
+                    f32x2 y0[4], y1[4];
+                    out_row(2 * a, y0); out_row(2 * a + 1, y1);
 #pragma unroll
-                        for (int b = 0; b < 4; ++b) part[((m * 2 + h) * 16 + a * 4 + b) * 256] = __builtin_bit_cast(unsigned long long, y[b]);
-                    }
+                    for (int b = 0; b < 4; ++b) { y0[b] = act(y0[b], 2 * a, b); y1[b] = act(y1[b], 2 * a + 1, b); }
+#pragma unroll
+                    for (int b = 0; b < 2; ++b)
+#pragma unroll
+                        for (int r = 0; r < 2; ++r)
+                            res[b][r] = fmaxf(fmaxf(y0[2 * b][r], y0[2 * b + 1][r]), fmaxf(y1[2 * b][r], y1[2 * b + 1][r]));
                 } else {
-                const f32x2 bb = {b4[2 * h], b4[2 * h + 1]}, ss = {s4[2 * h], s4[2 * h + 1]}, tt = {t4[2 * h], t4[2 * h + 1]};
-                // row a of the 4x4 output tile, pre-bias
-                auto out_row = [&](const int a, f32x2 (&y)[4]) __attribute__((always_inline)) { at6s(tcol[a], y); };
-                auto act = [&](f32x2 v, const int r, const int c) __attribute__((always_inline)) -> f32x2 {
-                    v = w43_add_bias(v, r, c, bb);
-                    if (BNF) { v = v * ss + tt; return f32x2{relu_bits(v[0]), relu_bits(v[1])}; }
-                    v = f32x2{relu_bits(v[0]), relu_bits(v[1])};
-                    return v * ss + tt;
-                };
-                // a uniform per-image base + 32-bit byte offsets (an image's output is far below 4 GB).  NHWC: pixel stride
-                // cs floats; planar [B][cout/4][Ho][Wo][4]: this lane's quad is plane ch0 / 4, pixel stride 16 bytes
-                char* const img_base = reinterpret_cast<char*>(
-                    p.out_planar ? p.out + (long long)cur.img * (p.cout / 4) * Ho * Wo * 4
-                                 : p.out + (long long)cur.img * Ho * Wo * cs + p.out_coff);
-                const unsigned ps = p.out_planar ? 16u : (unsigned)cs * 4u;                       // bytes per pixel step
-                const unsigned rs = (unsigned)Wo * ps;                                            // bytes per row step
-                const unsigned o0 = p.out_planar ? (unsigned)(((ch0 >> 2) * Ho + py0) * Wo + px0) * 16u
-                                                 : (unsigned)((py0 * Wo + px0) * cs + ch0) * 4u;
-                const bool inside = py0 + NO <= Ho && px0 + NO <= Wo;     // the whole tile lies inside the frame
-                // one output row (pooled: one row pair) at a time: the register peak is what decides whether loop-carried
-                // values survive the epilogue in registers (a reload inside a unit body stalls on every DMA in flight)
+                    f32x2 y0[4];
+                    out_row(a, y0);
 #pragma unroll
-                for (int a = 0; a < NO; ++a) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    f32x2 res[NO];
-                    if constexpr (POOL) {
-                        f32x2 y0[4], y1[4];
-                        out_row(2 * a, y0); out_row(2 * a + 1, y1);
+                    for (int b = 0; b < 4; ++b) res[b] = act(y0[b], a, b);
+                }
+                if (h == 0) {
 #pragma unroll
-                        for (int b = 0; b < 4; ++b) { y0[b] = act(y0[b], 2 * a, b); y1[b] = act(y1[b], 2 * a + 1, b); }
+                    for (int b = 0; b < NO; ++b) keep[a][b] = res[b];
+                } else if (ch0 < p.cout) {
+                    if (inside) {                                     // unconditional 16-byte stores
 #pragma unroll
-                        for (int b = 0; b < 2; ++b)
+                        for (int b = 0; b < NO; ++b) {
+                            const f32x4 v = {keep[a][b][0], keep[a][b][1], res[b][0], res[b][1]};
+                            *reinterpret_cast<f32x4*>(img_base + (o0 + (unsigned)a * rs + (unsigned)b * ps)) = v;
+                        }
+                    } else {                                          // frame edge of a frame that is no multiple of the tile (or a phantom tile)
 #pragma unroll
-                            for (int r = 0; r < 2; ++r)
-                                res[b][r] = fmaxf(fmaxf(y0[2 * b][r], y0[2 * b + 1][r]), fmaxf(y1[2 * b][r], y1[2 * b + 1][r]));
-                    } else {
-                        f32x2 y0[4];
-                        out_row(a, y0);
-#pragma unroll
-                        for (int b = 0; b < 4; ++b) res[b] = act(y0[b], a, b);
-                    }
-                    if (h == 0) {
-#pragma unroll
-                        for (int b = 0; b < NO; ++b) keep[a][b] = res[b];
-                    } else if (ch0 < p.cout) {
-                        if (inside) {                                     // unconditional 16-byte stores
-#pragma unroll
-                            for (int b = 0; b < NO; ++b) {
+                        for (int b = 0; b < NO; ++b)
+                            if (py0 + a < Ho && px0 + b < Wo) {
                                 const f32x4 v = {keep[a][b][0], keep[a][b][1], res[b][0], res[b][1]};
                                 *reinterpret_cast<f32x4*>(img_base + (o0 + (unsigned)a * rs + (unsigned)b * ps)) = v;
                             }
-                        } else {                                          // frame edge of a frame that is no multiple of the tile (or a phantom tile)
-#pragma unroll
-                            for (int b = 0; b < NO; ++b)
-                                if (py0 + a < Ho && px0 + b < Wo) {
-                                    const f32x4 v = {keep[a][b][0], keep[a][b][1], res[b][0], res[b][1]};
-                                    *reinterpret_cast<f32x4*>(img_base + (o0 + (unsigned)a * rs + (unsigned)b * ps)) = v;
-                                }
-                        }
                     }
                 }
-                }
             }
             }
-            };
-            // (SPLIT: split_reduce_kernel, the next launch on the stream, sums the ranges' shares in range order and runs the rest)
-            epilogue(std::integral_constant<int, SPLIT ? 1 : 0>{});
         }
+        }
+        };
+        // (SPLIT: split_reduce_kernel, the next launch on the stream, sums the ranges' shares in range order and runs the rest)
+        epilogue(std::integral_constant<int, SPLIT ? 1 : 0>{});
         if (!has_next) { dma_wait(); return; }      // the prefetch DMAs still in flight write THIS workgroup's LDS: drain them
         if (next_slice != cur.slice) {
             __syncthreads();

@@ -155,14 +155,8 @@ __device__ __forceinline__ mp_f32x2 pk_fnma_k(mp_f32x2 a, unsigned long long k, 
 // coefficients of x (x^2 - a^2)(x^2 - b^2) / (x - p), last row the polynomial itself:
 //   B^T = [a^2 b^2, 0, -(a^2+b^2), 0, 1, 0;  0, -+a b^2, -b^2, +-a, 1, 0 (p = +-a);  0, -+b a^2, -a^2, +-b, 1, 0 (p = +-b);
 //          0, a^2 b^2, 0, -(a^2+b^2), 0, 1]
-// COPY (timing only, conv_wino43.hip's MPQX & 131072): r = d, no arithmetic
-template <bool COPY = false>
 __device__ __forceinline__ void bt6(const mp_f32x2 d[6], mp_f32x2 r[6])
 {
-    if constexpr (COPY) {
-        for (int i = 0; i < 6; ++i) r[i] = d[i];
-        return;
-    }
     const mp_f32x2 t0 = pk_fnma_k<1>(d[2], K_A2B2, d[4]);      // d4 - b^2 d2      (even part of the +-a rows)
     const mp_f32x2 t1 = pk_fnma_k<1>(d[1], K_A2B2, d[3]);      // d3 - b^2 d1      (odd part / a)
     const mp_f32x2 t2 = pk_fnma_k<0>(d[2], K_A2B2, d[4]);      // d4 - a^2 d2      (+-b rows)

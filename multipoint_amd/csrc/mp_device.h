@@ -57,3 +57,26 @@ __device__ __forceinline__ void lds_dma(const T* sbase, unsigned voff_bytes, uns
 __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 // byte address of an LDS array (the M0 / ds_* operand)
 __device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)p; }
+
+// Phase timers of the -DMP_TIMING developer build (tools/conv_timing.py): a kernel keeps wave-uniform cycle sums in a local
+// `unsigned long long tsum[]` and writes them to its table once per workgroup.  MP_CLOCK(var) reads the clock into a const,
+// MP_CLOCK_ADD(slot, a, b) adds b - a to tsum[slot]; MP_TIMING_TABLE declares a kernel's table and its extern "C" reader,
+// MP_TIMING_HEIGHT the input height whose launches are recorded and its setter.  All empty without MP_TIMING.
+#ifdef MP_TIMING
+#define MP_CLOCK(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
+#define MP_CLOCK_ADD(slot, a, b) do { tsum[slot] += (b) - (a); } while (0)
+#define MP_TIMING_TABLE(table, n, reader)                                                                                      \
+    __device__ unsigned long long table[n];                                                                                    \
+    extern "C" int reader(unsigned long long* host, int cnt)                                                                   \
+    {                                                                                                                          \
+        return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(table), sizeof(unsigned long long) * cnt);                            \
+    }
+#define MP_TIMING_HEIGHT(sel, init, setter)                                                                                    \
+    __device__ int sel = init;                                                                                                 \
+    extern "C" int setter(int h) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(sel), &h, sizeof(int)); }
+#else
+#define MP_CLOCK(var) do { } while (0)
+#define MP_CLOCK_ADD(slot, a, b) do { } while (0)
+#define MP_TIMING_TABLE(table, n, reader)
+#define MP_TIMING_HEIGHT(sel, init, setter)
+#endif

@@ -337,19 +337,11 @@ void launch_nms_round(float* work, int B, int H, int W, const NmsFootprint& fp, 
     int* flags = remaining + 64;
     const float* np = nullptr;
     const uint8_t* nm = nullptr;
-#ifndef MP_NMS_LOOP_FROM
-#define MP_NMS_LOOP_FROM 1
-#endif
-#ifndef MP_NMS_LOOP_GRID
-#define MP_NMS_LOOP_GRID 2048
-#endif
-#ifndef MP_NMS_NO_LOOP       // (developer A/B: tools/build_variant.sh nl "-DMP_NMS_NO_LOOP" nms.hip)
-    if (fp.R == 3 && round >= MP_NMS_LOOP_FROM)       // the usual footprint (size 4): later rounds on a small grid that walks the tiles
-        hipLaunchKernelGGL((nms_round_kernel<3, false, true>), dim3((unsigned)(ntiles < MP_NMS_LOOP_GRID ? ntiles : MP_NMS_LOOP_GRID)), dim3(256), 0, s, work, H, W,
+    constexpr int LOOP_FROM = 1, LOOP_GRID = 2048;
+    if (fp.R == 3 && round >= LOOP_FROM)       // the usual footprint (size 4): later rounds on a small grid that walks the tiles
+        hipLaunchKernelGGL((nms_round_kernel<3, false, true>), dim3((unsigned)(ntiles < LOOP_GRID ? ntiles : LOOP_GRID)), dim3(256), 0, s, work, H, W,
                            tiles_x, tiles_y, fp, flags, ntiles, round, np, nm, 0.f, W, tie_eps, tie_pairs);
-    else
-#endif
-    if (fp.R == 3)
+    else if (fp.R == 3)
         hipLaunchKernelGGL((nms_round_kernel<3, false>), dim3((unsigned)ntiles), dim3(256), 0, s, work, H, W, tiles_x,
                            tiles_y, fp, flags, ntiles, round, np, nm, 0.f, W, tie_eps, tie_pairs);
     else if (fp.R == 1)
