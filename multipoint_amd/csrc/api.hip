@@ -19,6 +19,8 @@ namespace {
 //   no_vin               the 3x3 head convolutions (>= 4 output slices) transform their input per slice inside the kernel instead of
 //                        taking it pre-transformed from a pass of its own (conv_wino43.hip VIN; bit-identical either way)
 //   no_planar            channel-quad-planar tensors never (default: behind conv1 and pooled producers; round 6 retired planar=2 = everywhere)
+//   no_xplanar           column-interleaved planar tensors never: the tensors between an un-pooled conv_wino43.hip launch and its
+//                        conv_wino43.hip consumer stay NHWC (bit-identical either way; no_planar implies it)
 //   no_persist, persist_min_items=N   direct kernels: per-tile launches / persistent from N items per CU
 //   splitk_max=1..8      most ranges the input channels of a small launch are cut into
 //   f16_no_res, f16_no_fuse1, f16_res_groups=2   fp16 path: streaming kernel everywhere / first block as its own launch / two groups
@@ -143,6 +145,7 @@ int mp_create(mp_handle** out, int device)
     d.head_fuse = !debug_switch("no_head_fuse");
     d.vin = !debug_switch("no_vin");
     d.planar = !debug_switch("no_planar");
+    d.xplanar = d.planar && !debug_switch("no_xplanar");
     if (debug_switch("persist_min_items", &v) && v > 0) d.persist = v;
     if (debug_switch("no_persist")) d.persist = 0;
     if (debug_switch("splitk_max", &v) && v >= 1 && v <= 8) d.splitk_max = v;

@@ -21,7 +21,9 @@
 //    ring of THREE; + a per-wave scratch for the input transform: 158 KiB.
 //  * Input layout: NHWC, or channel-quad-planar [B][C/4][H][W][4] when the producer is conv_first.hip or a pooled launch of
 //    this kernel (forward.hip decides per tensor): a unit's patch rows are then contiguous, 9-11 cache lines per DMA instruction
-//    instead of 64.
+//    instead of 64.  Behind an UN-POOLED launch of this kernel: column-interleaved planar [B][C/4][H][4 = x mod 4][W/4][4] -- the
+//    16 tiles a store instruction of the epilogue covers are then consecutive 16-byte pieces per tile row (whole cache lines
+//    instead of 16 half lines), and a patch row is four runs.
 //  * DMA order: the memory pipe returns in order across the CU, so a weight DMA (L2 hit) queued behind a patch DMA (HBM miss)
 //    of ANY wave comes back at HBM latency.  The 5 weight DMAs of unit n+2 therefore go out right behind the barrier of unit
 //    n, the 2 patch DMAs of unit n+3 six MFMA groups ahead of the next weights, and the barrier waits with vmcnt(2) --
@@ -135,23 +137,33 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     };
 
     // ---- raw patch staging by DMA: granule f = block * 64 + lane = patch pixel f; this wave issues blocks wave, wave + 8 ----
-    const int pix_stride = p.in_planar ? 4 : p.in_cstride;              // floats between horizontally adjacent pixels
+    const int pix_stride = p.in_planar ? 4 : p.in_cstride;              // floats between horizontally adjacent pixels (x-planar: pixels 4 apart)
     const long long unit_stride = p.in_planar ? (long long)p.H * p.W * 4 : UC4;     // floats between consecutive units
+    // column-interleaved planar input [B][cin/4][H][4 = x mod 4][W/4 = x div 4][4] (MP_LAYOUT_XPLANAR: the producer is an
+    // un-pooled launch of this kernel): pixel (y, x) of a plane is y * row_stride + (x & 3) * W + (x >> 2) * 4 floats; the other
+    // layouts are the same expression with x_shift = x_mask = 0
+    const int x_shift = p.in_planar == MP_LAYOUT_XPLANAR ? 2 : 0, x_mask = p.in_planar == MP_LAYOUT_XPLANAR ? 3 : 0;
+    const int row_stride = p.W * pix_stride;                            // floats between vertically adjacent pixels
+    auto pixel_off = [&](int y, int x) __attribute__((always_inline)) -> int {
+        return y * row_stride + (x >> x_shift) * pix_stride + (x & x_mask) * p.W;
+    };
     unsigned rvoff[2];            // byte offset of the granule's source pixel (channel 0 of the unit)
     bool roff_rel = false;        // rvoff holds the item-invariant offsets of interior items
     auto raw_offsets = [&](const Where& w) __attribute__((always_inline)) -> const float* {
         const bool interior = (w.y0 >= 1) && (w.y0 + OY < p.H) && (w.x0 >= 1) && (w.x0 + OX < p.W);
         if (interior) {
+            // the offsets are relative to the patch's first pixel (y0 - 1, x0 - 1); x-planar: to (y0 - 1, x0 - 4), the first pixel
+            // of that residue plane's run (x0 is a multiple of 16), so that no offset is negative
             if (!roff_rel) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int f = (wave + 8 * j) * 64 + lane;
                     const int py = f / PX, px = f - py * PX;
-                    rvoff[j] = (f < NPIX) ? (unsigned)((py * p.W + px) * pix_stride) * 4u : 0u;
+                    rvoff[j] = (f < NPIX) ? (unsigned)pixel_off(py, px + x_mask) * 4u : 0u;
                 }
                 roff_rel = true;
             }
-            return w.in_base + (long long)((w.y0 - 1) * p.W + (w.x0 - 1)) * pix_stride;
+            return w.in_base + pixel_off(w.y0 - 1, w.x0 - 1 - x_mask);
         }
         roff_rel = false;
 #pragma unroll
@@ -161,7 +173,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
             unsigned off = 0;
             if (f < NPIX) {
                 const int gy = reflect_clamp(w.y0 + py - 1, p.H), gx = reflect_clamp(w.x0 + px - 1, p.W);
-                off = (unsigned)((gy * p.W + gx) * pix_stride) * 4u;
+                off = (unsigned)pixel_off(gy, gx) * 4u;
             }
             rvoff[j] = off;
         }
@@ -805,13 +817,17 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
                 const int Ho = POOL ? p.H >> 1 : p.H, Wo = POOL ? p.W >> 1 : p.W;
                 const int py0 = POOL ? oy >> 1 : oy, px0 = POOL ? ox >> 1 : ox;
                 // a uniform per-image base + 32-bit byte offsets (an image's output is far below 4 GB).  NHWC: pixel stride
-                // cs floats; planar [B][cout/4][Ho][Wo][4]: this lane's quad is plane ch0 / 4, pixel stride 16 bytes
+                // cs floats; planar [B][cout/4][Ho][Wo][4]: this lane's quad is plane ch0 / 4, pixel stride 16 bytes;
+                // x-planar [B][cout/4][Ho][4][Wo/4][4] (un-pooled launches only: tiles start at multiples of 4): a step in x is the
+                // next residue plane, the tile column a 16-byte step -- the 8 (4) tile columns of an item are one 128 (64)-byte run
+                const bool xpl = !POOL && p.out_planar == MP_LAYOUT_XPLANAR;
                 char* const img_base = reinterpret_cast<char*>(
                     p.out_planar ? p.out + (long long)cur.img * (p.cout / 4) * Ho * Wo * 4
                                  : p.out + (long long)cur.img * Ho * Wo * cs + p.out_coff);
-                const unsigned ps = p.out_planar ? 16u : (unsigned)cs * 4u;                       // bytes per pixel step
-                const unsigned rs = (unsigned)Wo * ps;                                            // bytes per row step
-                const unsigned o0 = p.out_planar ? (unsigned)(((ch0 >> 2) * Ho + py0) * Wo + px0) * 16u
+                const unsigned ps = xpl ? (unsigned)Wo * 4u : p.out_planar ? 16u : (unsigned)cs * 4u;       // bytes per pixel step
+                const unsigned rs = p.out_planar ? (unsigned)Wo * 16u : (unsigned)Wo * ps;          // bytes per row step
+                const unsigned o0 = xpl ? (unsigned)(((ch0 >> 2) * Ho + py0) * Wo * 4 + px0) * 4u
+                                  : p.out_planar ? (unsigned)(((ch0 >> 2) * Ho + py0) * Wo + px0) * 16u
                                                  : (unsigned)((py0 * Wo + px0) * cs + ch0) * 4u;
                 // H and W are multiples of 4 (conv_wino43_supports) and tiles are 4-aligned: a tile is inside the image or
                 // outside as a whole, and cout is a multiple of 4 -- ONE test, then NO x NO unconditional 16-byte stores
@@ -998,6 +1014,9 @@ long long conv_wino43_items(const ConvParams& p)
 // channels run as 2^ks_shift items per (tile block, slice) that meet in p.split_scratch
 int launch_conv_wino43(const ConvParams& p, bool pool, hipStream_t s, bool fuse_first)
 {
+    // x-planar tensors: written by un-pooled launches only (a pooled tile's 2 columns are no whole 16-byte step), never split
+    if (p.out_planar == MP_LAYOUT_XPLANAR && pool) return 2;
+    if ((p.in_planar == MP_LAYOUT_XPLANAR || p.out_planar == MP_LAYOUT_XPLANAR) && p.ks_shift > 0) return 2;
     if (fuse_first) return pool && p.cin == 64 ? launch_q<true, 8, true>(p, s) : 2;          // 2: shape not covered
     if (p.vglobal) {       // pre-transformed input (forward.hip: un-pooled layers with >= 4 output slices; cin a multiple of 16, NHWC)
         if (pool || p.ks_shift > 0 || p.cin % 16 != 0 || p.in_planar || p.cin > 256 || 256 % (p.cin / 2) != 0 || (p.cin / 2) < 8) return 2;

@@ -631,6 +631,7 @@ bool conv_wino43b_supports(const ConvParams& p)
 
 int launch_conv_wino43b(const ConvParams& p, bool pool, hipStream_t s)
 {
+    if (p.in_planar == MP_LAYOUT_XPLANAR || p.out_planar == MP_LAYOUT_XPLANAR) return 2;      // conv_wino43.hip's layout only
     if (p.ks_shift > 0) {        // forward.hip: single-pair launches with fewer items than CUs
         const int ncs = (p.cin / UC4) >> p.ks_shift;
         if (ncs < 2 || (ncs & 1) || (ncs << p.ks_shift) * UC4 != p.cin || !p.split_scratch) return 2;

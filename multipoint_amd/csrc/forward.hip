@@ -58,7 +58,7 @@ enum class Kernel { direct, wino43, wino43b, f16, f16_res, f16_res_slices };
 struct ConvLaunch {
     Kernel kernel = Kernel::direct;
     bool fuse_first = false;                    // the encoder's first block is evaluated inside this launch (enc.conv2)
-    bool in_planar = false, out_planar = false; // channel-quad-planar input / output tensor (fp32 F(4x4,3x3) launches only)
+    int in_planar = MP_LAYOUT_NHWC, out_planar = MP_LAYOUT_NHWC;    // layout of the input / output tensor (fp32 F(4x4,3x3) launches only)
     int ks_shift = 0;                           // split-K: the input channels run as 2^ks_shift ranges (split_ws)
     bool vin = false;                           // the input is transformed once, by a pass of its own (vin_ws)
 };
@@ -150,9 +150,16 @@ EncoderPlan plan_encoder(const mp_handle* h, const Encoder& E, int nb, int fwd_b
         // costs the producer more than the consumer's patch DMAs gain: conv3 1.29 vs 1.17 ms.)  The encoder output stays NHWC
         // (a planar one was measured for the head convolution: slower).
         const bool producer = i == 0 ? !E.first_pool : P.conv[i - 1].kernel != Kernel::direct && E.conv[i - 1].pool;
-        c.in_planar = h->dbg.planar && c.kernel != Kernel::direct && producer;
-        if (i > 0) P.conv[i - 1].out_planar = c.in_planar;
+        c.in_planar = h->dbg.planar && c.kernel != Kernel::direct && producer ? MP_LAYOUT_PLANAR : MP_LAYOUT_NHWC;
         plan_split_vin(h, L, nb, hh, ww, fwd_batch, c);
+        // ... and column-interleaved planar behind an UN-POOLED layer, when both ends are plain conv_wino43.hip launches (the
+        // any-frame kernel, the split-K reduction and the pre-transformed-input pass read and write the other two layouts only): the
+        // tile columns of an item are then consecutive 16-byte pieces, so a store instruction of the producer writes whole cache
+        // lines instead of 16 half lines, and the consumer's patch rows are four runs instead of 34 pieces 256 bytes or more apart
+        if (i > 0 && h->dbg.xplanar && !E.conv[i - 1].pool && P.conv[i - 1].kernel == Kernel::wino43 && P.conv[i - 1].ks_shift == 0 &&
+            c.kernel == Kernel::wino43 && c.ks_shift == 0 && !c.vin)
+            c.in_planar = MP_LAYOUT_XPLANAR;
+        if (i > 0) P.conv[i - 1].out_planar = c.in_planar;
         if (L.pool) { hh /= 2; ww /= 2; }
     }
     return P;
@@ -331,7 +338,7 @@ int run_forward(mp_handle* h, const float* images, const ImageRoute& route, int 
         const Encoder& E = h->enc[e];
         const int* list = h->cfg.multispectral ? lists + 512 * e : nullptr;
         const EncoderPlan plan = plan_encoder(h, E, nb, B, H, W);
-        if (!plan.conv[0].fuse_first) run_first(h, E, plan.conv[0].in_planar, images, P, nb, H, W, list, s);
+        if (!plan.conv[0].fuse_first) run_first(h, E, plan.conv[0].in_planar == MP_LAYOUT_PLANAR, images, P, nb, H, W, list, s);
         int hh = E.first_pool ? H / 2 : H, ww = E.first_pool ? W / 2 : W;
         T* src = P;
         T* dst = Q;

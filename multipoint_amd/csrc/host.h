@@ -75,7 +75,7 @@ struct ProfEntry {
 // (debug_switch() in api.hip documents them).  A loaded model's own settings are its ConvPolicy.
 struct DebugSwitches {
     bool winograd = true, wino43 = true, fuse_first = true, fuse43 = true, head_fuse = true, vin = true, planar = true;
-    bool f16_res = true, f16_fuse1 = true;
+    bool xplanar = true, f16_res = true, f16_fuse1 = true;
     int wino43_gen = 0, persist = 8, splitk_max = 8, f16_res_groups = 3;
 };
 

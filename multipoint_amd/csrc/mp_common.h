@@ -9,6 +9,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define MP_WAVE 64
 
+// activation tensor layouts of the fp32 F(4x4,3x3) launches (ConvParams::in_planar / out_planar)
+enum { MP_LAYOUT_NHWC = 0, MP_LAYOUT_PLANAR = 1, MP_LAYOUT_XPLANAR = 2 };
+
 // ---------------------------------------------------------------------------------------------
 // conv (implicit GEMM on v_mfma_f32_32x32x2_f32)
 // ---------------------------------------------------------------------------------------------
@@ -40,7 +43,10 @@ struct ConvParams {
     int nitems;           // work items (tile, slice) of the launch (filled in by the launcher)
     int persist;          // 0: per-tile kernel only; n > 0: persistent workgroups for launches with >= n items per CU
     // conv_wino43.hip only: channel-quad-planar tensors [B][C/4][H][W][4] instead of NHWC (a unit of 4 input channels is then
-    // contiguous row by row: its patch DMA touches ~10 cache lines per instruction instead of 64)
+    // contiguous row by row: its patch DMA touches ~10 cache lines per instruction instead of 64), or -- MP_LAYOUT_XPLANAR, behind an
+    // un-pooled conv_wino43_kernel launch -- column-interleaved planar [B][C/4][H][4 = x mod 4][W/4 = x div 4][4]: the tile columns
+    // of an item are then consecutive 16-byte pieces, so an epilogue store instruction writes whole cache lines.  MP_LAYOUT_*
+    // values; conv_wino43b.hip, the split-K reduction and conv_first.hip know the first two only
     int in_planar, out_planar;
     // machine shape (api.hip: mp_create derives it from the device, forward.hip: run_conv copies it into every launch): compute units of
     // the device = workgroups of a one-per-CU persistent grid, and log2 of its XCD count (workgroup b runs on XCD b mod nxcd;
