@@ -17,8 +17,9 @@ LIB_PATH = os.path.join(HERE, 'libmultipoint_hip.so')
 SOURCES = ['conv_mfma.hip', 'conv_wino43.hip', 'conv_wino43b.hip', 'conv_split.hip', 'conv_f16.hip', 'conv_f16_res.hip', 'conv_first.hip', 'heads_post.hip', 'head_tail.hip', 'head_tail_f16.hip', 'nms.hip', 'keypoints.hip',
            'sample_match.hip', 'match_extra.hip', 'pair_metrics.hip', 'detector_metrics.hip', 'homography.hip', 'homog_adapt.hip', 'losses.hip', 'batchnorm_stats.hip', 'photometric.hip', 'api.hip',
            'model_load.hip', 'forward.hip', 'post_api.hip']
-HEADERS = [os.path.join(CSRC, 'mp_common.h'), os.path.join(CSRC, 'mp_device.h'), os.path.join(CSRC, 'host.h'),
-           os.path.join(HERE, '..', 'include', 'multipoint_hip.h')]
+HEADERS = [os.path.join(CSRC, h) for h in ('mp_common.h', 'mp_device.h', 'mp_tile.h', 'mp_f16.h', 'mp_f16_store_pooled.inc',
+                                            'mp_f16_store_lines.inc', 'host.h')] + [
+    os.path.join(HERE, '..', 'include', 'multipoint_hip.h')]
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function'] + \
     os.environ.get('MP_HIPCC_FLAGS', '').split()          # e.g. -DMP_TIMING (developer instrumentation)

@@ -10,6 +10,8 @@
 //   conv: fp32 accumulate (+ fp16 bias) -> fp16;  ReLU;  BN: fp32 affine on the fp16 value -> fp16;  max-pool.
 #include "mp_common.h"
 #include "mp_device.h"
+#include "mp_f16.h"
+#include "mp_tile.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -19,9 +21,6 @@ MP_TIMING_TABLE(g_timing_h, 512 * 8, mp_debug_read_timing_f16)
 MP_TIMING_HEIGHT(g_timing_h_sel, 1024, mp_debug_select_height_f16)       // only launches whose input height matches are recorded
 
 namespace {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
 constexpr int CKH = 64;        // input channels per LDS chunk
 constexpr int PSH = CKH + 8;   // LDS pixel stride in halfs (144 B)
@@ -42,40 +41,6 @@ struct GeoH {
 
 __device__ __forceinline__ float round_h(float v) { return (float)(_Float16)v; }
 
-// conv result (fp32 accumulator) -> activation value as autocast produces it (still held in fp32)
-template <bool RELU, bool BNF>
-__device__ __forceinline__ float act_h(float acc, float bias, float scale, float shift)
-{
-    float v = round_h(acc + bias);
-    if (BNF) {
-        v = round_h(v * scale + shift);
-        if (RELU) v = fmaxf(v, 0.f);
-    } else {
-        if (RELU) v = fmaxf(v, 0.f);
-        v = round_h(v * scale + shift);
-    }
-    return v;
-}
-
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// the same on a pair, written so that hipcc emits packed instructions (v_pk_add_f32, v_cvt_pk_f16_f32,
-// v_pk_max_f16, v_pk_fma_f32): ReLU commutes with the rounding, so it runs on the packed halves
-template <bool RELU, bool BNF>
-__device__ __forceinline__ h2 act_h2(float a0, float a1, f32x2 bias, f32x2 scale, f32x2 shift)
-{
-    const f32x2 x = f32x2{a0, a1} + bias;
-    h2 h = __builtin_convertvector(x, h2);
-    const h2 zero = {0, 0};
-    if (RELU && !BNF) h = __builtin_elementwise_max(h, zero);
-    f32x2 y = __builtin_convertvector(h, f32x2) * scale + shift;
-    asm volatile("" : "+v"(y));      // y exists as an fp32 pair (autocast: BatchNorm result in fp32, THEN fp16): no v_fma_mixlo_f16, which rounds once
-    h2 o = __builtin_convertvector(y, h2);
-    if (RELU && BNF) o = __builtin_elementwise_max(o, zero);
-    return o;
-}
-
 template <int TAPS, int MBW, bool POOL, bool BNF>
 __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvParamsH p)
 {
@@ -86,8 +51,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvParamsH p)
     // bias | BN scale | BN shift of the current 64-channel slice: fetched from global memory only when the slice
     // changes (a global load in every epilogue costs its L2 latency per item)
     __shared__ __attribute__((aligned(16))) float prm[3 * 64];
-    // un-pooled layers: a wave's output block (32 pixels x 64 channels, 4 KiB) passes through LDS so that a lane stores 16 bytes and eight
-    // lanes a pixel's whole 128-byte line (conv_f16_res.hip's epilogue); 16-byte granules XOR-swizzled by the pixel's low bits
+    // un-pooled layers: the waves' staging blocks of mp_f16_store_lines.inc, 4 KiB each
     __shared__ __attribute__((aligned(16))) _Float16 ostage[POOL ? 8 : 4 * 2048];
 
     const int tid = threadIdx.x;
@@ -103,26 +67,8 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvParamsH p)
     const int stride = xr.stride, item_end = xr.item_end;
     int item = xr.item;
 
-    auto udiv = [](unsigned n, unsigned magic, unsigned d) -> unsigned { return d == 1 ? n : __umulhi(n, magic); };
-    struct Where { int slice, img, y0, x0; long long px0; const _Float16* in_base; };
-    auto decode = [&](int it) __attribute__((always_inline)) -> Where {
-        Where w{};
-        const int tile = (int)udiv((unsigned)it, p.magic_slices, (unsigned)p.nslices);
-        w.slice = it - tile * p.nslices;
-        if constexpr (TAPS == 9) {
-            const int trow = (int)udiv((unsigned)tile, p.magic_tx, (unsigned)p.tiles_x);
-            const int tx = tile - trow * p.tiles_x;
-            const int bi = (int)udiv((unsigned)trow, p.magic_ty, (unsigned)p.tiles_y);
-            const int ty = trow - bi * p.tiles_y;
-            w.img = p.img_list ? p.img_list[bi] : bi;
-            w.y0 = ty * G::TH; w.x0 = tx * G::TW;
-            w.in_base = p.in + (long long)w.img * p.H * p.W * p.in_cstride + p.in_coff;
-        } else {
-            w.px0 = (long long)tile * 256;
-            w.in_base = p.in + w.px0 * p.in_cstride + p.in_coff;
-        }
-        return w;
-    };
+    using Where = TileWhere<_Float16>;
+    auto decode = [&](int it) __attribute__((always_inline)) -> Where { return tile_decode<_Float16, TAPS, G::TH, G::TW>(p, it); };
     // per-thread staging offsets in halfs.  Interior items (every halo pixel inside the image; all pixels valid in
     // flat mode): offsets relative to the item's first halo pixel, IDENTICAL for every such item, so they are
     // computed once and only the wave-uniform base pointer moves (no VALU per item: a wave that is not streaming
@@ -342,184 +288,16 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvParamsH p)
         // ---------------- epilogue of item `cur` ----------------
         const int slice = cur.slice, img = cur.img, y0 = cur.y0, x0 = cur.x0;
         const long long px0 = cur.px0;
-        // Addressing: wave-uniform 64-bit base (scalar unit) + one per-lane 32-bit offset computed once per item + uniform
-        // per-store increments.  `full` items (tile entirely inside the output) store unconditionally; partial tiles
-        // send masked lanes to a dummy line so that BOTH paths issue the same number of stores and hipcc's vmcnt
-        // counting stays exact (a guarded store would make the next item's first operand wait cover every store).
+        constexpr bool SLICED = true;
         if constexpr (POOL) {
-            // lane = channel (li), register r = pixel (r&3) + 8*(r>>2) + 4*half of the M-block; registers r, r+1
-            // are horizontally adjacent pixels -> one packed pair
-            // (the lane's item-invariant epilogue values -- parameter addresses, store offset -- are derived from an OPAQUE copy of the lane id,
-            // so that hipcc recomputes them here instead of carrying them through the MFMA loop: it spilled 7 of them to scratch)
             int lq = lane;
-            asm volatile("" : "+v"(lq));
+            asm volatile("" : "+v"(lq));      // (why: mp_f16_store_pooled.inc)
             const int li = lq & 31, half = lq >> 5;
-            f32x2 bia[2], scl[2], sft[2];
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb) {
-                const float b = prm[nb * 32 + li], sc = prm[64 + nb * 32 + li], sh = prm[128 + nb * 32 + li];
-                bia[nb] = f32x2{b, b}; scl[nb] = f32x2{sc, sc}; sft[nb] = f32x2{sh, sh};
-            }
-            const int Ho = p.H >> 1, Wo = p.W >> 1;
-            const int cs = p.out_cstride;
-            // Pool BEFORE the activation: bias add, fp16 rounding and ReLU are non-decreasing and the BatchNorm affine is monotonic in the direction of its
-            // scale's sign, so the maximum of a window's four activations IS the activation of the maximum (scale < 0: the minimum) of its
-            // four accumulators, bit for bit -- one activation per pooled value instead of four (channels li and 32 + li share a packed pair)
-            const f32x2 biap = {bia[0][0], bia[1][0]}, sclp = {scl[0][0], scl[1][0]}, sftp = {sft[0][0], sft[1][0]};
-            const bool neg0 = sclp[0] < 0.f, neg1 = sclp[1] < 0.f;
-            auto pooled_first = [&](const float (&q)[2][4]) __attribute__((always_inline)) -> h2 {
-                const float x0 = fmaxf(fmaxf(q[0][0], q[0][1]), fmaxf(q[0][2], q[0][3])), n0 = fminf(fminf(q[0][0], q[0][1]), fminf(q[0][2], q[0][3]));
-                const float x1 = fmaxf(fmaxf(q[1][0], q[1][1]), fmaxf(q[1][2], q[1][3])), n1 = fminf(fminf(q[1][0], q[1][1]), fminf(q[1][2], q[1][3]));
-                return act_h2<RELU, BNF>(neg0 ? n0 : x0, neg1 ? n1 : x1, biap, sclp, sftp);
-            };
-            const bool full = (y0 + G::TH <= p.H) && (x0 + G::TW <= p.W) && (slice * 64 + 64 <= p.cout);
-            const int lane_off = 2 * half * cs + li;
-            _Float16* const obase = p.out + ((long long)img * Ho * Wo) * cs + p.out_coff + slice * 64;
-            // MBW == 32: rows 2*wave (mb 0) and 2*wave+1 (mb 1) pool together; otherwise both rows of a window are
-            // registers r and r+RDOWN of one M-block
-            constexpr int RDOWN = (MBW == 32) ? 0 : (MBW == 16) ? 8 : 4;
-            constexpr int NMB = (MBW == 32) ? 1 : 2;
-            auto store_all = [&](auto full_tag) __attribute__((always_inline)) {
-                constexpr bool FULL = decltype(full_tag)::value;
-#pragma unroll
-                for (int mb = 0; mb < NMB; ++mb)
-#pragma unroll
-                    for (int r = 0; r < 16; r += 2) {
-                        if (RDOWN != 0 && (r & RDOWN) != 0) continue;
-                        const int iu = (r & 3) + 8 * (r >> 2);                       // lane-independent part of the pixel index
-                        const int oy = (MBW == 32) ? (y0 + 2 * wave) >> 1 : (y0 + (2 * wave + mb) * G::MBH + iu / MBW) >> 1;
-                        const int oxu = (x0 + iu % MBW) >> 1;                        // + 2*half per lane
-                        _Float16* const rowp = obase + ((long long)oy * Wo + oxu) * cs;
-                        h2 vp;
-                        {
-                            float q[2][4];
-#pragma unroll
-                            for (int nb = 0; nb < 2; ++nb) {
-                                if constexpr (MBW == 32) {
-                                    q[nb][0] = acc[0][nb][r]; q[nb][1] = acc[0][nb][r + 1]; q[nb][2] = acc[1][nb][r]; q[nb][3] = acc[1][nb][r + 1];
-                                } else {
-                                    q[nb][0] = acc[mb][nb][r]; q[nb][1] = acc[mb][nb][r + 1];
-                                    q[nb][2] = acc[mb][nb][r + RDOWN]; q[nb][3] = acc[mb][nb][r + RDOWN + 1];
-                                }
-                            }
-                            vp = pooled_first(q);
-                        }
-#pragma unroll
-                        for (int nb = 0; nb < 2; ++nb) {
-                            const _Float16 v = vp[nb];
-                            if constexpr (FULL) {
-                                rowp[nb * 32 + lane_off] = v;
-                            } else {
-                                const bool ok = (oy < Ho) & (oxu + 2 * half < Wo) & (slice * 64 + nb * 32 + li < p.cout);
-                                _Float16* dst = ok ? rowp + nb * 32 + lane_off : p.dummy + lq;
-                                *dst = v;
-                            }
-                        }
-                    }
-            };
-            if (full) store_all(std::true_type{}); else store_all(std::false_type{});
+#include "mp_f16_store_pooled.inc"
         } else {
-            // non-pooled: lane = pixel, register r = channel (r&3) + 8*(r>>2) + 4*half of the N-block -> 8-byte stores
-            const int cs = p.out_cstride;
-            int lane_off;
-            _Float16* obase;
-            bool full;
-            if constexpr (TAPS == 1) {
-                lane_off = li * cs + half * 4;
-                obase = p.out + px0 * cs + p.out_coff + slice * 64;
-                full = (px0 + 256 <= p.total_px) && (slice * 64 + 64 <= p.cout);
-            } else {
-                lane_off = ((li / MBW) * p.W + li % MBW) * cs + half * 4;
-                obase = p.out + (((long long)img * p.H + y0) * p.W + x0) * cs + p.out_coff + slice * 64;
-                full = (y0 + G::TH <= p.H) && (x0 + G::TW <= p.W) && (slice * 64 + 64 <= p.cout);
-            }
-            auto store_all = [&](auto full_tag) __attribute__((always_inline)) {
-                constexpr bool FULL = decltype(full_tag)::value;
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                    for (int rg = 0; rg < 4; ++rg) {
-                        const int cl = nb * 32 + rg * 8 + half * 4;
-                        const f32x4 b4 = *reinterpret_cast<const f32x4*>(&prm[cl]);
-                        const f32x4 s4 = *reinterpret_cast<const f32x4*>(&prm[64 + cl]);
-                        const f32x4 t4 = *reinterpret_cast<const f32x4*>(&prm[128 + cl]);
-#pragma unroll
-                        for (int mb = 0; mb < 2; ++mb) {
-                            const h2 lo = act_h2<RELU, BNF>(acc[mb][nb][rg * 4], acc[mb][nb][rg * 4 + 1], f32x2{b4[0], b4[1]},
-                                                            f32x2{s4[0], s4[1]}, f32x2{t4[0], t4[1]});
-                            const h2 hi = act_h2<RELU, BNF>(acc[mb][nb][rg * 4 + 2], acc[mb][nb][rg * 4 + 3], f32x2{b4[2], b4[3]},
-                                                            f32x2{s4[2], s4[3]}, f32x2{t4[2], t4[3]});
-                            const h4 v = h4{lo[0], lo[1], hi[0], hi[1]};
-                            // M-block (2*wave+mb): rows (2*wave+mb)*MBH.. of the tile, or 32 consecutive pixels in flat mode
-                            _Float16* const mp = (TAPS == 1) ? obase + (long long)((2 * wave + mb) * 32) * cs
-                                                             : obase + (long long)((2 * wave + mb) * G::MBH) * p.W * cs;
-                            _Float16* const dst = mp + nb * 32 + rg * 8 + lane_off;
-                            if constexpr (FULL) {
-                                *reinterpret_cast<h4*>(dst) = v;
-                            } else {
-                                bool okp;
-                                if constexpr (TAPS == 1) okp = px0 + (2 * wave + mb) * 32 + li < p.total_px;
-                                else okp = (y0 + (2 * wave + mb) * G::MBH + li / MBW < p.H) & (x0 + li % MBW < p.W);
-                                const int ch0 = slice * 64 + cl;
-                                if (ch0 + 3 < p.cout || !okp) {
-                                    *reinterpret_cast<h4*>(okp ? dst : p.dummy + lane * 4) = v;
-                                } else {                     // partial channel quad (cout = 65: the 1x1 detector head only)
-#pragma unroll
-                                    for (int e = 0; e < 4; ++e)
-                                        if (ch0 + e < p.cout) dst[e] = v[e];
-                                }
-                            }
-                        }
-                    }
-            };
-            if (TAPS == 9 || slice * 64 + 64 <= p.cout) {      // (3x3 layers: cout is a multiple of 64, launch_conv_f16 refuses anything else)
-                // Per M-block (32 pixels): every lane writes its eight 8-byte channel quads into the wave's staging block
-                // [pixel][granule ^ (pixel & 7)][8 halfs], then lane l reads granule l & 7 of pixels l >> 3, + 8, + 16, + 24 and stores 16 bytes:
-                // eight lanes = one pixel's 64 channels = one 128-byte line (8-byte pieces 128 bytes apart cost 32 partial lines per store
-                // instruction: measured 20 % of an un-pooled launch)
-                _Float16* const stg = ostage + wave * 2048;
-                int lq = lane;
-                asm volatile("" : "+v"(lq));              // the addresses below are item-invariant: keep hipcc from holding them in registers through the MFMA loop
-                const int wrow = (lq & 31) * 64 + (lq >> 5) * 4, wsw = lq & 7;
-                const int rg_l = lq & 7, rp0 = lq >> 3;
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                        for (int rg = 0; rg < 4; ++rg) {
-                            const int cl = nb * 32 + rg * 8 + half * 4;
-                            const f32x4 b4 = *reinterpret_cast<const f32x4*>(&prm[cl]);
-                            const f32x4 s4 = *reinterpret_cast<const f32x4*>(&prm[64 + cl]);
-                            const f32x4 t4 = *reinterpret_cast<const f32x4*>(&prm[128 + cl]);
-                            const h2 lo = act_h2<RELU, BNF>(acc[mb][nb][rg * 4], acc[mb][nb][rg * 4 + 1], f32x2{b4[0], b4[1]},
-                                                            f32x2{s4[0], s4[1]}, f32x2{t4[0], t4[1]});
-                            const h2 hi = act_h2<RELU, BNF>(acc[mb][nb][rg * 4 + 2], acc[mb][nb][rg * 4 + 3], f32x2{b4[2], b4[3]},
-                                                            f32x2{s4[2], s4[3]}, f32x2{t4[2], t4[3]});
-                            *reinterpret_cast<h4*>(stg + wrow + (((nb * 4 + rg) ^ wsw) << 3)) = h4{lo[0], lo[1], hi[0], hi[1]};
-                        }
-                    asm volatile("" ::: "memory");                                // (same wave: the LDS executes its operations in order)
-                    _Float16* const mp = (TAPS == 1) ? obase + (long long)((2 * wave + mb) * 32) * cs
-                                                     : obase + (long long)((2 * wave + mb) * G::MBH) * p.W * cs;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int px = rp0 + 8 * k;                          // (rp0 < 8: px / MBW and the k-part of px % MBW are uniform)
-                        const h8 v = *reinterpret_cast<const h8*>(stg + px * 64 + ((rg_l ^ rp0) << 3));
-                        _Float16* dst = (TAPS == 1) ? mp + (8 * k) * cs + (rp0 * cs + rg_l * 8)
-                                                    : mp + (((8 * k) / MBW) * p.W + (8 * k) % MBW) * cs + (rp0 * cs + rg_l * 8);
-                        if (!full) {
-                            bool okp;
-                            if constexpr (TAPS == 1) okp = px0 + (2 * wave + mb) * 32 + px < p.total_px;
-                            else okp = (y0 + (2 * wave + mb) * G::MBH + px / MBW < p.H) & (x0 + px % MBW < p.W);
-                            dst = okp ? dst : p.dummy + lane * 8;
-                        }
-                        *reinterpret_cast<h8*>(dst) = v;
-                    }
-                    asm volatile("" ::: "memory");
-                }
-            } else if constexpr (TAPS == 1) {
-                store_all(std::false_type{});          // a partial channel slice (cout = 65: the 1x1 detector head as its own launch)
-            }
+            constexpr int KS = 512;
+#define MP_F16_STAGE (ostage + wave * 2048)
+#include "mp_f16_store_lines.inc"
         }
         MP_CLOCK(t_epi1);
         MP_CLOCK_ADD(4, t_epi0, t_epi1);                            // epilogue
@@ -548,11 +326,7 @@ int launch_h(const ConvParamsH& p, hipStream_t s)
     const long long nitems = ntiles * p.nslices;
     if (nitems <= 0) return 0;
     ConvParamsH q = p;
-    auto magic = [](int d) -> unsigned { return d <= 1 ? 0u : (unsigned)((0x100000000ull / (unsigned)d) + 1ull); };
-    q.magic_slices = magic(p.nslices); q.magic_tx = magic(p.tiles_x); q.magic_ty = magic(p.tiles_y);
-    const long long dmax = std::max(std::max(p.nslices, p.tiles_x), p.tiles_y);
-    if (nitems * dmax >= 0x100000000ll) return 1;      // beyond the 32-bit tile decode: reported as MP_EINVAL
-    q.nitems = (int)nitems;
+    if (tile_items(q, nitems)) return 1;
     // persistent workgroups: two per CU, a multiple of the XCD count
     const long long nblk = persistent_grid(nitems, p.ncu, p.xcd_shift, 2);
     const ConvParamsH& pp = q;

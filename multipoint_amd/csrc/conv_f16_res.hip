@@ -15,6 +15,8 @@
 // item late.
 #include "mp_common.h"
 #include "mp_device.h"
+#include "mp_f16.h"
+#include "mp_tile.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -24,11 +26,6 @@
 MP_TIMING_TABLE(g_timing_r, 512 * 8, mp_debug_read_timing_f16_res)
 
 namespace {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int CKR = 32;        // input channels per LDS chunk
 constexpr int PSR = CKR + 8;   // LDS pixel stride in halfs: 80 B = 20 dwords -> 16 consecutive pixels start in 16 distinct 16-byte bank groups
@@ -46,21 +43,6 @@ struct GeoR {
     static constexpr int NITER = (NV + 255) / 256;       // staging vectors per thread of a group
     static constexpr int STEPS = 9 * (CKR / 16);         // k16-steps per chunk
 };
-
-// conv result pair (fp32 accumulators) -> activation as autocast produces it; identical to conv_f16.hip's act_h2
-template <bool BNF>
-__device__ __forceinline__ h2 act_r2(float a0, float a1, f32x2 bias, f32x2 scale, f32x2 shift)
-{
-    const f32x2 x = f32x2{a0, a1} + bias;
-    h2 h = __builtin_convertvector(x, h2);
-    const h2 zero = {0, 0};
-    if (!BNF) h = __builtin_elementwise_max(h, zero);
-    f32x2 y = __builtin_convertvector(h, f32x2) * scale + shift;
-    asm volatile("" : "+v"(y));      // y exists as an fp32 pair (autocast: BatchNorm result in fp32, THEN fp16): no v_fma_mixlo_f16, which rounds once
-    h2 o = __builtin_convertvector(y, h2);
-    if (BNF) o = __builtin_elementwise_max(o, zero);
-    return o;
-}
 
 // barrier of the four waves of a group: a counter in LDS.  The LDS executes the operations of a CU in the order they are
 // issued, and a wave issues its own in program order: whatever a wave read from or wrote to LDS before its increment has been
@@ -96,9 +78,7 @@ __global__ __launch_bounds__(256 * NG, NG) void conv_f16_res_kernel(const ConvPa
     __shared__ __attribute__((aligned(16))) _Float16 tiles[NG][G::NPIX * PSR];
     __shared__ __attribute__((aligned(16))) float prm[3 * 64];
     __shared__ unsigned gctr[NG];
-    // un-pooled layers: a wave's output block (32 pixels x 64 channels, 4 KiB) passes through LDS so that a lane stores 16 bytes and eight
-    // lanes a pixel's whole 128-byte line (lane = pixel in the accumulators: 8-byte pieces 128 bytes apart, 32 partial lines per store
-    // instruction -- measured 20 % of enc.conv3's launch); 16-byte granules XOR-swizzled by the pixel's low bits instead of a padded stride.
+    // un-pooled layers: a wave's output block passes through an LDS staging block on its way out (mp_f16_store_lines.inc).
     // The staging block lives in the group's own TILE: behind the last chunk's barrier nobody reads the tile any more, and the next item's
     // chunk 0 waits in the staging registers until the epilogue is through (lds_write() behind it).  A wave stages in the stripes of the
     // tile that its OWN threads write in lds_write() -- pixels 16 w + 64 j .. + 15 (1280 bytes each), eight 128-byte rows per stripe --
@@ -148,19 +128,8 @@ __global__ __launch_bounds__(256 * NG, NG) void conv_f16_res_kernel(const ConvPa
     // epilogue / tile hand-over
     for (int g = 0; g < grp; ++g) __builtin_amdgcn_s_sleep(NG == 2 ? 127 : 70);
 
-    auto udiv = [](unsigned n, unsigned magic, unsigned d) -> unsigned { return d == 1 ? n : __umulhi(n, magic); };
-    struct Where { int img, y0, x0; const _Float16* in_base; };
-    auto decode = [&](int tile) __attribute__((always_inline)) -> Where {
-        Where w{};
-        const int trow = (int)udiv((unsigned)tile, p.magic_tx, (unsigned)p.tiles_x);
-        const int tx = tile - trow * p.tiles_x;
-        const int bi = (int)udiv((unsigned)trow, p.magic_ty, (unsigned)p.tiles_y);
-        const int ty = trow - bi * p.tiles_y;
-        w.img = p.img_list ? p.img_list[bi] : bi;
-        w.y0 = ty * G::TH; w.x0 = tx * G::TW;
-        w.in_base = p.in + (long long)w.img * p.H * p.W * p.in_cstride + p.in_coff;
-        return w;
-    };
+    using Where = TileWhere<_Float16>;
+    auto decode = [&](int tile) __attribute__((always_inline)) -> Where { return tile_decode<_Float16, 9, G::TH, G::TW, false>(p, tile); };
     // per-thread staging offsets in halfs (channel granule c8 of patch pixel lp); interior items share one item-invariant set
     int goff[G::NITER];
     bool goff_rel = false;
@@ -260,6 +229,8 @@ __global__ __launch_bounds__(256 * NG, NG) void conv_f16_res_kernel(const ConvPa
     // the bias rides in the GEMM as tap 9 against a 1.0 in the patch tail), apply ReLU / BatchNorm, write chunk 0 into the tile
     // and keep chunk 1 packed in registers (8 per M-block) until chunk 0 has been multiplied (tile_chunk1).
     h4 keep1[NJ][4];
+    // act_h2<true, BNF> without the bias add and without its opaque fp32 pair: as a call of act_h2 with a zero bias the F1
+    // instantiations grow by 12 ds_ instructions, so the chain stays written out
     auto act_nb = [](float a0, float a1, f32x2 scale, f32x2 shift) __attribute__((always_inline)) -> h2 {
         h2 h = __builtin_convertvector(f32x2{a0, a1}, h2);        // conv output (bias included) -> fp16
         const h2 zero = {0, 0};
@@ -472,118 +443,20 @@ __global__ __launch_bounds__(256 * NG, NG) void conv_f16_res_kernel(const ConvPa
         chunk_body(std::integral_constant<int, 0>{});
         chunk_body(std::integral_constant<int, 1>{});
 
-        // ---------------- epilogue of item `cur` (conv_f16.hip's, one 64-channel slice) ----------------
+        // ---------------- epilogue of item `cur`: one 64-channel slice ----------------
         MP_CLOCK(t_e0);
         const int img = cur.img, y0 = cur.y0, x0 = cur.x0;
+        constexpr int TAPS = 9, slice = 0;
+        constexpr bool RELU = true, SLICED = false;
         if constexpr (POOL) {
-            // lane = channel (li), register r = pixel (r&3) + 8*(r>>2) + 4*half of the M-block; registers r, r+1 are
-            // horizontally adjacent pixels -> one packed pair
-            f32x2 bia[2], scl[2], sft[2];
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb) {
-                const float b = prm[nb * 32 + li], sc = prm[64 + nb * 32 + li], sh = prm[128 + nb * 32 + li];
-                bia[nb] = f32x2{b, b}; scl[nb] = f32x2{sc, sc}; sft[nb] = f32x2{sh, sh};
-            }
-            const int Ho = p.H >> 1, Wo = p.W >> 1;
-            const int cs = p.out_cstride;
-            // Pool BEFORE the activation: bias add, fp16 rounding and ReLU are non-decreasing and the BatchNorm affine is monotonic in the direction of its
-            // scale's sign, so the maximum of a window's four activations IS the activation of the maximum (scale < 0: the minimum) of its
-            // four accumulators, bit for bit -- one activation per pooled value instead of four (channels li and 32 + li share a packed pair)
-            const f32x2 biap = {bia[0][0], bia[1][0]}, sclp = {scl[0][0], scl[1][0]}, sftp = {sft[0][0], sft[1][0]};
-            const bool neg0 = sclp[0] < 0.f, neg1 = sclp[1] < 0.f;
-            auto pooled_first = [&](const float (&q)[2][4]) __attribute__((always_inline)) -> h2 {
-                const float x0 = fmaxf(fmaxf(q[0][0], q[0][1]), fmaxf(q[0][2], q[0][3])), n0 = fminf(fminf(q[0][0], q[0][1]), fminf(q[0][2], q[0][3]));
-                const float x1 = fmaxf(fmaxf(q[1][0], q[1][1]), fmaxf(q[1][2], q[1][3])), n1 = fminf(fminf(q[1][0], q[1][1]), fminf(q[1][2], q[1][3]));
-                return act_r2<BNF>(neg0 ? n0 : x0, neg1 ? n1 : x1, biap, sclp, sftp);
-            };
-            const bool full = (y0 + G::TH <= p.H) && (x0 + G::TW <= p.W);
-            const int lane_off = 2 * half * cs + li;
-            _Float16* const obase = p.out + ((long long)img * Ho * Wo) * cs + p.out_coff;
-            constexpr int RDOWN = (MBW == 32) ? 0 : (MBW == 16) ? 8 : 4;
-            constexpr int NMB = (MBW == 32) ? 1 : 2;
-            auto store_all = [&](auto full_tag) __attribute__((always_inline)) {
-                constexpr bool FULL = decltype(full_tag)::value;
-#pragma unroll
-                for (int mb = 0; mb < NMB; ++mb)
-#pragma unroll
-                    for (int r = 0; r < 16; r += 2) {
-                        if (RDOWN != 0 && (r & RDOWN) != 0) continue;
-                        const int iu = (r & 3) + 8 * (r >> 2);
-                        const int oy = (MBW == 32) ? (y0 + 2 * wave) >> 1 : (y0 + (2 * wave + mb) * G::MBH + iu / MBW) >> 1;
-                        const int oxu = (x0 + iu % MBW) >> 1;
-                        _Float16* const rowp = obase + ((long long)oy * Wo + oxu) * cs;
-                        h2 vp;
-                        {
-                            float q[2][4];
-#pragma unroll
-                            for (int nb = 0; nb < 2; ++nb) {
-                                if constexpr (MBW == 32) {
-                                    q[nb][0] = acc[0][nb][r]; q[nb][1] = acc[0][nb][r + 1]; q[nb][2] = acc[1][nb][r]; q[nb][3] = acc[1][nb][r + 1];
-                                } else {
-                                    q[nb][0] = acc[mb][nb][r]; q[nb][1] = acc[mb][nb][r + 1];
-                                    q[nb][2] = acc[mb][nb][r + RDOWN]; q[nb][3] = acc[mb][nb][r + RDOWN + 1];
-                                }
-                            }
-                            vp = pooled_first(q);
-                        }
-#pragma unroll
-                        for (int nb = 0; nb < 2; ++nb) {
-                            const _Float16 v = vp[nb];
-                            if constexpr (FULL) {
-                                rowp[nb * 32 + lane_off] = v;
-                            } else {
-                                const bool ok = (oy < Ho) & (oxu + 2 * half < Wo);
-                                _Float16* dst = ok ? rowp + nb * 32 + lane_off : p.dummy + lane;
-                                *dst = v;
-                            }
-                        }
-                    }
-            };
-            if (full) store_all(std::true_type{}); else store_all(std::false_type{});
+            const int lq = lane;
+#include "mp_f16_store_pooled.inc"
         } else {
-            // non-pooled: lane = pixel li, register r = channel (r&3) + 8*(r>>2) + 4*half of the N-block.  Per M-block (32 pixels): every lane
-            // writes its eight 8-byte channel quads into the wave's staging block [pixel][granule ^ (pixel & 7)][8 halfs], then lane l reads
-            // granule l & 7 of pixels l >> 3, + 8, + 16, + 24 and stores 16 bytes: eight lanes = one pixel's 64 channels = one 128-byte line
-            const int cs = p.out_cstride;
-            _Float16* const obase = p.out + (((long long)img * p.H + y0) * p.W + x0) * cs + p.out_coff;
-            const bool full = (y0 + G::TH <= p.H) && (x0 + G::TW <= p.W);
-            _Float16* const stg = lds + (16 * wave) * PSR;                          // + stripe (row >> 3) * 64 * PSR + (row & 7) * 64
-            int lq = lane;
-            asm volatile("" : "+v"(lq));                  // the addresses below are item-invariant: keep hipcc from holding them in registers through the MFMA loop
-            const int wrow = ((lq & 31) >> 3) * (64 * PSR) + (lq & 7) * 64 + (lq >> 5) * 4, wsw = lq & 7;   // halfs: this lane's pixel row, + the half's 8 bytes in a granule
-            const int rg_l = lq & 7, rp0 = lq >> 3;                                // read side: granule, first pixel
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                    for (int rg = 0; rg < 4; ++rg) {
-                        const int cl = nb * 32 + rg * 8 + half * 4;
-                        const f32x4 b4 = *reinterpret_cast<const f32x4*>(&prm[cl]);
-                        const f32x4 s4 = *reinterpret_cast<const f32x4*>(&prm[64 + cl]);
-                        const f32x4 t4 = *reinterpret_cast<const f32x4*>(&prm[128 + cl]);
-                        const h2 lo = act_r2<BNF>(acc[mb][nb][rg * 4], acc[mb][nb][rg * 4 + 1], f32x2{b4[0], b4[1]},
-                                                  f32x2{s4[0], s4[1]}, f32x2{t4[0], t4[1]});
-                        const h2 hi = act_r2<BNF>(acc[mb][nb][rg * 4 + 2], acc[mb][nb][rg * 4 + 3], f32x2{b4[2], b4[3]},
-                                                  f32x2{s4[2], s4[3]}, f32x2{t4[2], t4[3]});
-                        *reinterpret_cast<h4*>(stg + wrow + (((nb * 4 + rg) ^ wsw) << 3)) = h4{lo[0], lo[1], hi[0], hi[1]};
-                    }
-                asm volatile("" ::: "memory");                                    // (same wave: the LDS executes its operations in order)
-                _Float16* const mp = obase + (long long)((2 * wave + mb) * G::MBH) * p.W * cs;
-                const int gy0 = y0 + (2 * wave + mb) * G::MBH;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int px = rp0 + 8 * k;                                    // pixel of the M-block (rp0 < 8: px / MBW and the k-part of px % MBW are uniform)
-                    const h8 v = *reinterpret_cast<const h8*>(stg + k * (64 * PSR) + rp0 * 64 + ((rg_l ^ rp0) << 3));   // row px = rp0 + 8 k: stripe k
-                    _Float16* dst = mp + (((8 * k) / MBW) * p.W + (8 * k) % MBW) * cs + (rp0 * cs + rg_l * 8);
-                    if (!full) {
-                        const bool okp = (gy0 + px / MBW < p.H) & (x0 + px % MBW < p.W);
-                        dst = okp ? dst : p.dummy + lane * 8;
-                    }
-                    *reinterpret_cast<h8*>(dst) = v;
-                }
-                asm volatile("" ::: "memory");
-            }
+            // the staging block: four stripes of the group's own tile (see `tiles` above), + stripe (row >> 3) * 64 * PSR + (row & 7) * 64
+            constexpr int KS = 64 * PSR;
+            const long long px0 = 0;                                              // (flat mode only)
+#define MP_F16_STAGE (lds + (16 * wave) * PSR)
+#include "mp_f16_store_lines.inc"
         }
         if constexpr (!POOL) { if (has_next) lds_write(); }   // the next item's chunk 0 into the tile the epilogue staged in
         MP_CLOCK(t_e1);
@@ -609,11 +482,7 @@ int launch_res(const ConvParamsH& p, hipStream_t s)
     const long long nitems = (long long)p.B * p.tiles_x * p.tiles_y;
     if (nitems <= 0) return 0;
     ConvParamsH q = p;
-    auto magic = [](int d) -> unsigned { return d <= 1 ? 0u : (unsigned)((0x100000000ull / (unsigned)d) + 1ull); };
-    q.magic_tx = magic(p.tiles_x); q.magic_ty = magic(p.tiles_y);
-    const long long dmax = std::max(p.tiles_x, p.tiles_y);
-    if (nitems * dmax >= 0x100000000ll) return 1;      // beyond the 32-bit tile decode: reported as MP_EINVAL
-    q.nitems = (int)nitems;
+    if (tile_items(q, nitems)) return 1;
     // persistent workgroups, ONE per CU, each running NG groups (= virtual workgroups) over its XCD's share
     const unsigned grid = persistent_grid((nitems + NG - 1) / NG, p.ncu, p.xcd_shift);
     const ConvParamsH& pp = q;

@@ -19,6 +19,7 @@
 // overlap (the fp32 MFMA takes 64 cycles per issue, everything else hides behind it).
 #include "mp_common.h"
 #include "mp_device.h"
+#include "mp_tile.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -108,27 +109,12 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
         const int q = nblk >> p.xcd_shift, r = nblk & (nx - 1), xcd = bid & (nx - 1), pos = bid >> p.xcd_shift;
         logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
     }
-    // exact division by multiply-high with host-computed magic numbers: stays on the scalar unit (a
-    // runtime integer division costs ~20 VALU instructions, and VALU shares the pipe with fp32 MFMA)
-    auto udiv = [](unsigned n, unsigned magic, unsigned d) -> unsigned { return d == 1 ? n : __umulhi(n, magic); };
-    int tile = (int)udiv((unsigned)logical, p.magic_slices, (unsigned)p.nslices);
+    const int tile = (int)udiv((unsigned)logical, p.magic_slices, (unsigned)p.nslices);
     const int slice = logical - tile * p.nslices;
-
-    int img = 0, y0 = 0, x0 = 0;
-    long long px0 = 0;
-    const float* in_base;      // wave-uniform base: image (3x3) or first pixel of the tile (1x1)
-    if constexpr (TAPS == 9) {
-        const int trow = (int)udiv((unsigned)tile, p.magic_tx, (unsigned)p.tiles_x);
-        const int tx = tile - trow * p.tiles_x;
-        const int bi = (int)udiv((unsigned)trow, p.magic_ty, (unsigned)p.tiles_y);
-        const int ty = trow - bi * p.tiles_y;
-        img = p.img_list ? p.img_list[bi] : bi;
-        y0 = ty * G::TH; x0 = tx * G::TW;
-        in_base = p.in + (long long)img * p.H * p.W * p.in_cstride + p.in_coff;
-    } else {
-        px0 = (long long)tile * 256;
-        in_base = p.in + px0 * p.in_cstride + p.in_coff;
-    }
+    const TileWhere<float> w0 = tile_decode<float, TAPS, G::TH, G::TW, false>(p, tile);
+    const int img = w0.img, y0 = w0.y0, x0 = w0.x0;
+    const long long px0 = w0.px0;
+    const float* const in_base = w0.in_base;      // wave-uniform base: image (3x3) or first pixel of the tile (1x1)
 
     // ---- per-thread staging offsets (element offsets from in_base, -1 = store zeros) ----
     // interior tiles (every halo pixel inside the image: ~87 % of the tiles at 480x640) take a lean path:
@@ -491,26 +477,8 @@ __global__ __launch_bounds__(256, 1) void conv_mfma_persist_kernel(const ConvPar
     const int stride = xr.stride, item_end = xr.item_end;
     int item = xr.item;
 
-    auto udiv = [](unsigned n, unsigned magic, unsigned d) -> unsigned { return d == 1 ? n : __umulhi(n, magic); };
-    struct Where { int slice, img, y0, x0; long long px0; const float* in_base; };
-    auto decode = [&](int it) __attribute__((always_inline)) -> Where {
-        Where w{};
-        const int tile = (int)udiv((unsigned)it, p.magic_slices, (unsigned)p.nslices);
-        w.slice = it - tile * p.nslices;
-        if constexpr (TAPS == 9) {
-            const int trow = (int)udiv((unsigned)tile, p.magic_tx, (unsigned)p.tiles_x);
-            const int tx = tile - trow * p.tiles_x;
-            const int bi = (int)udiv((unsigned)trow, p.magic_ty, (unsigned)p.tiles_y);
-            const int ty = trow - bi * p.tiles_y;
-            w.img = p.img_list ? p.img_list[bi] : bi;
-            w.y0 = ty * G::TH; w.x0 = tx * G::TW;
-            w.in_base = p.in + (long long)w.img * p.H * p.W * p.in_cstride + p.in_coff;
-        } else {
-            w.px0 = (long long)tile * 256;
-            w.in_base = p.in + w.px0 * p.in_cstride + p.in_coff;
-        }
-        return w;
-    };
+    using Where = TileWhere<float>;
+    auto decode = [&](int it) __attribute__((always_inline)) -> Where { return tile_decode<float, TAPS, G::TH, G::TW>(p, it); };
     int goff[G::NITER];
     bool goff_rel = false;          // goff holds the item-invariant relative offsets of interior items
     bool cur_pad = false;           // the LDS image being written has padding slots
@@ -849,12 +817,7 @@ int launch_t(const ConvParams& p, hipStream_t s)
     const long long nblk = ntiles * p.nslices;
     if (nblk <= 0) return 0;
     ConvParams q = p;
-    // magic = floor(2^32 / d) + 1 gives floor(n / d) == umulhi(n, magic) for all n with n * d < 2^32
-    auto magic = [](int d) -> unsigned { return d <= 1 ? 0u : (unsigned)((0x100000000ull / (unsigned)d) + 1ull); };
-    q.magic_slices = magic(p.nslices); q.magic_tx = magic(p.tiles_x); q.magic_ty = magic(p.tiles_y);
-    const long long dmax = std::max(std::max(p.nslices, p.tiles_x), p.tiles_y);
-    if (nblk * dmax >= 0x100000000ll) return 1;        // beyond the 32-bit tile decode: reported as MP_EINVAL
-    q.nitems = (int)nblk;
+    if (tile_items(q, nblk)) return 1;
     const ConvParams& pp = q;
     if constexpr (!FUSE1) {
         if constexpr (TAPS == 9) {

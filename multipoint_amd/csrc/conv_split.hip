@@ -8,10 +8,9 @@
 // dependent ~1.5 us trips behind a write-through / counter / barrier hand-off, which was most of what a small launch cost.)
 #include "mp_common.h"
 #include "mp_device.h"
+#include "mp_tile.h"
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // GEN 1: conv_wino43.hip (512 threads per item, 32 values each: [h][a][b]); GEN 2: conv_wino43b.hip (256 threads, 64 values:
 // [m][h][a][b]).  The index arithmetic below is the epilogues' own (lane = tile, register quad = 4 consecutive output channels).
@@ -26,7 +25,6 @@ __global__ __launch_bounds__(256) void split_reduce_kernel(const ConvParams p)
     const int tid = (int)(gid % T), q = (int)((gid / T) % NQ);
     const int g = (int)(gid / (T * NQ));               // (tile block, slice)
     if (g >= p.nitems) return;
-    auto udiv = [](unsigned n, unsigned magic, unsigned d) -> unsigned { return d == 1 ? n : __umulhi(n, magic); };
     const int tile = (int)udiv((unsigned)g, p.magic_slices, (unsigned)p.nslices);
     const int slice = g - tile * p.nslices;
     const int trow = (int)udiv((unsigned)tile, p.magic_tx, (unsigned)p.tiles_x);
@@ -124,9 +122,7 @@ int launch_split_reduce(const ConvParams& p, int gen, bool pool, hipStream_t s)
     q.tiles_x = (p.W + OX - 1) / OX; q.tiles_y = (p.H + OY - 1) / OY;
     const long long nitems = (long long)p.B * q.tiles_x * q.tiles_y * p.nslices;
     if (nitems <= 0) return 0;
-    auto magic = [](int d) -> unsigned { return d <= 1 ? 0u : (unsigned)((0x100000000ull / (unsigned)d) + 1ull); };
-    q.magic_slices = magic(q.nslices); q.magic_tx = magic(q.tiles_x); q.magic_ty = magic(q.tiles_y);
-    q.nitems = (int)nitems;
+    if (tile_items(q, nitems)) return 1;
     if (gen == 1) {
         if (tc4 == 4) { if (pool) launch_r<1, true, 4>(q, s); else launch_r<1, false, 4>(q, s); }
         else { if (pool) launch_r<1, true, 8>(q, s); else launch_r<1, false, 8>(q, s); }

@@ -36,6 +36,7 @@
 //    are spread over groups 0-6 of the unit, the stores two per MFMA gap.
 #include "mp_common.h"
 #include "mp_device.h"
+#include "mp_tile.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -56,7 +57,6 @@ constexpr int NRB = (NPIX + 63) / 64;              // raw DMA blocks of 64 granu
 constexpr int RB4 = NRB * 64 * 4;                  // floats per raw buffer: 10 blocks (10 KiB); one dummy block behind the three
 constexpr int SW4 = 8 * 36 * 2;                    // floats of a wave's transform scratch: 8 windows x 36 x (2 channels)
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // LDS-DMA of 16 bytes per lane (mp_device.h).  LEAD = 1 behind a wave-uniform branch: the five wait states an
 // SGPR base needs behind a VALU write must lie INSIDE the branch's own block (multipoint_amd/build.py checks it), so the statement
@@ -115,7 +115,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     int item = xr.item;
     if (item >= item_end) return;
 
-    auto udiv = [](unsigned n, unsigned magic, unsigned d) -> unsigned { return d == 1 ? n : __umulhi(n, magic); };
     struct Where { int slice, img, y0, x0, tile; const float* in_base; };
     auto decode = [&](int it) __attribute__((always_inline)) -> Where {
         Where w{};
@@ -940,11 +939,7 @@ int launch_q(const ConvParams& p, hipStream_t s)
     q.tiles_x = (p.W + OX - 1) / OX; q.tiles_y = (p.H + OY - 1) / OY;
     const long long nitems = (long long)p.B * q.tiles_x * q.tiles_y * q.nslices;
     if (nitems <= 0) return 0;
-    auto magic = [](int d) -> unsigned { return d <= 1 ? 0u : (unsigned)((0x100000000ull / (unsigned)d) + 1ull); };
-    q.magic_slices = magic(q.nslices); q.magic_tx = magic(q.tiles_x); q.magic_ty = magic(q.tiles_y);
-    const long long dmax = std::max(std::max(q.nslices, q.tiles_x), q.tiles_y);
-    if (nitems * dmax >= 0x100000000ll) return 1;
-    q.nitems = (int)nitems;
+    if (tile_items(q, nitems)) return 1;
     const unsigned grid = persistent_grid(nitems, p.ncu, p.xcd_shift);
     const ConvParams& pp = q;
     if (p.bn_first) hipLaunchKernelGGL((conv_wino43_kernel<POOL, true, TC4, F1, SPLIT>), dim3(grid), dim3(512), 0, s, pp);
@@ -961,11 +956,7 @@ int launch_vin(const ConvParams& p, hipStream_t s)
     q.tiles_x = (p.W + OX - 1) / OX; q.tiles_y = (p.H + OY - 1) / OY;
     const long long ntb = (long long)p.B * q.tiles_x * q.tiles_y, nitems = ntb * q.nslices;
     if (nitems <= 0) return 0;
-    auto magic = [](int d) -> unsigned { return d <= 1 ? 0u : (unsigned)((0x100000000ull / (unsigned)d) + 1ull); };
-    q.magic_slices = magic(q.nslices); q.magic_tx = magic(q.tiles_x); q.magic_ty = magic(q.tiles_y);
-    const long long dmax = std::max(std::max(q.nslices, q.tiles_x), q.tiles_y);
-    if (nitems * dmax >= 0x100000000ll) return 1;
-    q.nitems = (int)nitems;
+    if (tile_items(q, nitems)) return 1;
     const ConvParams& pp = q;
     const int tl = 256 / (p.cin / 2);                    // tiles per producer block (launch_conv_wino43 checked the divisibility)
     hipLaunchKernelGGL((wino43_vprod_kernel<TC4>), dim3((unsigned)(ntb * (32 / tl))), dim3(256), 0, s, pp, ntb);

@@ -29,6 +29,7 @@
 //    weight DMAs of a wave are spread from behind the barrier of unit n to group 1 of unit n+1 (one per 3 MFMAs).
 #include "mp_common.h"
 #include "mp_device.h"
+#include "mp_tile.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -40,7 +41,6 @@ constexpr int UB4 = UC4 * 64 * 36;                 // floats per U buffer  [ch][
 constexpr int VR4 = 36 * 64 + 1;                   // floats per channel region of a V' buffer: [pos][lane], odd so that the two channels of a pair sit one bank apart
 constexpr int VB4 = 2 * VR4 + 2;                   // floats per V' buffer (16-byte multiple)
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // LDS-DMA of 16 bytes per lane (mp_device.h).  OFF: the instruction's immediate offset, which moves the source
 // AND the LDS destination (round-4 probe; docs/HISTORY.md 3.3) -- exactly what a block-for-block copy wants: one scalar source base,
@@ -123,7 +123,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
     int item = xr.item;
     if (item >= item_end) return;
 
-    auto udiv = [](unsigned n, unsigned magic, unsigned d) -> unsigned { return d == 1 ? n : __umulhi(n, magic); };
     struct Where { int slice, img, y0, x0; const float* in_base; };
     auto decode = [&](int it) __attribute__((always_inline)) -> Where {
         Where w{};
@@ -598,11 +597,7 @@ int launch_q(const ConvParams& p, hipStream_t s)
     q.tiles_x = (p.W + OX - 1) / OX; q.tiles_y = (p.H + OY - 1) / OY;
     const long long nitems = (long long)p.B * q.tiles_x * q.tiles_y * q.nslices;
     if (nitems <= 0) return 0;
-    auto magic = [](int d) -> unsigned { return d <= 1 ? 0u : (unsigned)((0x100000000ull / (unsigned)d) + 1ull); };
-    q.magic_slices = magic(q.nslices); q.magic_tx = magic(q.tiles_x); q.magic_ty = magic(q.tiles_y);
-    const long long dmax = std::max(std::max(q.nslices, q.tiles_x), q.tiles_y);
-    if (nitems * dmax >= 0x100000000ll) return 1;
-    q.nitems = (int)nitems;
+    if (tile_items(q, nitems)) return 1;
     const unsigned grid = persistent_grid(nitems, p.ncu, p.xcd_shift);
     const ConvParams& pp = q;
     if (p.bn_first) hipLaunchKernelGGL((conv_wino43b_kernel<POOL, true, TC4, ZPAD, SPLIT>), dim3(grid), dim3(256), 0, s, pp);

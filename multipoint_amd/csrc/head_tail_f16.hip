@@ -21,28 +21,18 @@
 // what bounds it is bytes in flight (one chunk ahead = 32 KiB per CU), not the matrix pipe.
 #include "mp_common.h"
 #include "mp_device.h"
+#include "mp_f16.h"
 
 #include <type_traits>
 
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-// conv output pair (fp32 accumulators) -> what autocast leaves: fp16(acc + bias), then the BatchNorm affine in fp32, rounded to
-// fp16.  Written on a PAIR exactly like conv_f16.hip's act_h2 (without the ReLU: the 1x1 head convolutions have none,
-// MultiPoint.py:66-72,82-86) so that hipcc emits v_pk_add_f32 / v_cvt_pk_f16_f32 / v_pk_fma_f32: the scalar form becomes
-// v_fma_mixlo_f16 -- ONE rounding from the exact product-sum to fp16 where autocast rounds to fp32 first and to fp16 second,
-// which flips output bits.
+// conv output pair (fp32 accumulators) -> what autocast leaves, as an fp32 pair: act_h2 without the ReLU (the 1x1 head
+// convolutions have none, MultiPoint.py:66-72,82-86).  The scalar form becomes v_fma_mixlo_f16 -- ONE rounding from the exact
+// product-sum to fp16 where autocast rounds to fp32 first and to fp16 second, which flips output bits.
 __device__ __forceinline__ f32x2 head_act2(float a0, float a1, f32x2 bias, f32x2 scale, f32x2 shift)
 {
-    const f32x2 x = f32x2{a0, a1} + bias;
-    const h2 h = __builtin_convertvector(x, h2);
-    f32x2 y = __builtin_convertvector(h, f32x2) * scale + shift;
-    asm volatile("" : "+v"(y));      // y exists as an fp32 pair: no fused multiply-add-and-round-to-fp16 even where one half is unused
-    const h2 o = __builtin_convertvector(y, h2);
-    return __builtin_convertvector(o, f32x2);
+    return __builtin_convertvector(act_h2<false, false>(a0, a1, bias, scale, shift), f32x2);
 }
 
 // ND = D / 32 descriptor blocks (0: no descriptor head)

@@ -6,6 +6,7 @@
 //   desc_l2  : torch.nn.functional.normalize(x, p=2, dim=1)  (MultiPoint.py:163-164), eps 1e-12
 // Both are wave-level kernels: reductions are DPP/shuffle trees inside 8- or 16-lane groups.
 #include "mp_common.h"
+#include "mp_f16.h"
 
 namespace {
 
@@ -86,7 +87,6 @@ __global__ __launch_bounds__(256) void desc_l2norm_kernel(const T* __restrict__ 
         if constexpr (sizeof(T) == 4) {
             v = *reinterpret_cast<const f32x4*>(raw + px * D + c);
         } else {
-            typedef _Float16 h4 __attribute__((ext_vector_type(4)));
             const h4 hv = *reinterpret_cast<const h4*>(raw + px * D + c);
             v = f32x4{(float)hv[0], (float)hv[1], (float)hv[2], (float)hv[3]};
         }

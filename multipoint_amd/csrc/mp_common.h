@@ -6,6 +6,7 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #define MP_WAVE 64
 
@@ -123,7 +124,6 @@ void launch_conv_first_linear(const Conv1Params& p, hipStream_t s);
 #ifndef MP_W43_B
 #define MP_W43_B 1.5
 #endif
-typedef float mp_f32x2 __attribute__((ext_vector_type(2)));
 // Packed fp32 arithmetic as explicit instructions: hipcc scalarises a third of the input transform's packed multiply-adds (4
 // v_fma_f32 for 2 v_pk_fma_f32 per pass), and next to an MFMA stream every vector instruction costs matrix-pipe time
 // (docs/HISTORY.md A.3).  The transform coefficients come in scalar register pairs (VOP3P takes no literal on gfx950).
@@ -142,17 +142,17 @@ static_assert((double)(float)(W43A * W43A * W43B * W43B) == W43A * W43A * W43B *
               W43A * W43A + W43B * W43B, "the transform coefficients must be exact in fp32");
 // HI = 0: the low half of k, 1: the high half
 template <int HI>
-__device__ __forceinline__ mp_f32x2 pk_fma_k(mp_f32x2 a, unsigned long long k, mp_f32x2 c)      // a * k + c
+__device__ __forceinline__ f32x2 pk_fma_k(f32x2 a, unsigned long long k, f32x2 c)      // a * k + c
 {
-    mp_f32x2 d;
+    f32x2 d;
     if (HI) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(d) : "v"(a), "s"(k), "v"(c));
     else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(d) : "v"(a), "s"(k), "v"(c));
     return d;
 }
 template <int HI>
-__device__ __forceinline__ mp_f32x2 pk_fnma_k(mp_f32x2 a, unsigned long long k, mp_f32x2 c)     // c - a * k
+__device__ __forceinline__ f32x2 pk_fnma_k(f32x2 a, unsigned long long k, f32x2 c)     // c - a * k
 {
-    mp_f32x2 d;
+    f32x2 d;
     if (HI) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(d) : "v"(a), "s"(k), "v"(c));
     else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(d) : "v"(a), "s"(k), "v"(c));
     return d;
@@ -161,12 +161,12 @@ __device__ __forceinline__ mp_f32x2 pk_fnma_k(mp_f32x2 a, unsigned long long k, 
 // coefficients of x (x^2 - a^2)(x^2 - b^2) / (x - p), last row the polynomial itself:
 //   B^T = [a^2 b^2, 0, -(a^2+b^2), 0, 1, 0;  0, -+a b^2, -b^2, +-a, 1, 0 (p = +-a);  0, -+b a^2, -a^2, +-b, 1, 0 (p = +-b);
 //          0, a^2 b^2, 0, -(a^2+b^2), 0, 1]
-__device__ __forceinline__ void bt6(const mp_f32x2 d[6], mp_f32x2 r[6])
+__device__ __forceinline__ void bt6(const f32x2 d[6], f32x2 r[6])
 {
-    const mp_f32x2 t0 = pk_fnma_k<1>(d[2], K_A2B2, d[4]);      // d4 - b^2 d2      (even part of the +-a rows)
-    const mp_f32x2 t1 = pk_fnma_k<1>(d[1], K_A2B2, d[3]);      // d3 - b^2 d1      (odd part / a)
-    const mp_f32x2 t2 = pk_fnma_k<0>(d[2], K_A2B2, d[4]);      // d4 - a^2 d2      (+-b rows)
-    const mp_f32x2 t3 = pk_fnma_k<0>(d[1], K_A2B2, d[3]);      // d3 - a^2 d1
+    const f32x2 t0 = pk_fnma_k<1>(d[2], K_A2B2, d[4]);      // d4 - b^2 d2      (even part of the +-a rows)
+    const f32x2 t1 = pk_fnma_k<1>(d[1], K_A2B2, d[3]);      // d3 - b^2 d1      (odd part / a)
+    const f32x2 t2 = pk_fnma_k<0>(d[2], K_A2B2, d[4]);      // d4 - a^2 d2      (+-b rows)
+    const f32x2 t3 = pk_fnma_k<0>(d[1], K_A2B2, d[3]);      // d3 - a^2 d1
     r[0] = pk_fma_k<0>(d[0], K_PS, pk_fnma_k<1>(d[2], K_PS, d[4]));      // a^2 b^2 d0 + (d4 - (a^2+b^2) d2)
     r[1] = pk_fma_k<0>(t1, K_AB, t0);                          // t0 + a t1
     r[2] = pk_fnma_k<0>(t1, K_AB, t0);                         // t0 - a t1
@@ -181,22 +181,22 @@ __device__ __forceinline__ void bt6(const mp_f32x2 d[6], mp_f32x2 r[6])
 // coefficient), and the factor sigma_r sigma_c, sigma = (1, a, a^2, 1), of output (r, c) goes into the multiply-add that adds the
 // bias anyway (w43_out_scale; 1, a .. a^4 are exact binary fractions).  Two roundings fewer per y1 / y2 than the plain form.
 static_assert(MP_W43_B == 2 * MP_W43_A, "at6s() needs b = 2a");
-__device__ __forceinline__ void at6s(const mp_f32x2 m[6], mp_f32x2 z[4])
+__device__ __forceinline__ void at6s(const f32x2 m[6], f32x2 z[4])
 {
     constexpr float a3 = (float)(MP_W43_A * MP_W43_A * MP_W43_A);
-    const mp_f32x2 s1 = m[1] + m[2], d1 = m[1] - m[2], s2 = m[3] + m[4], d2 = m[3] - m[4];
+    const f32x2 s1 = m[1] + m[2], d1 = m[1] - m[2], s2 = m[3] + m[4], d2 = m[3] - m[4];
     z[0] = (m[0] + s1) + s2;
-    z[1] = __builtin_elementwise_fma(d2, mp_f32x2{2.f, 2.f}, d1);
-    z[2] = __builtin_elementwise_fma(s2, mp_f32x2{4.f, 4.f}, s1);
-    z[3] = __builtin_elementwise_fma(__builtin_elementwise_fma(d2, mp_f32x2{8.f, 8.f}, d1), mp_f32x2{a3, a3}, m[5]);
+    z[1] = __builtin_elementwise_fma(d2, f32x2{2.f, 2.f}, d1);
+    z[2] = __builtin_elementwise_fma(s2, f32x2{4.f, 4.f}, s1);
+    z[3] = __builtin_elementwise_fma(__builtin_elementwise_fma(d2, f32x2{8.f, 8.f}, d1), f32x2{a3, a3}, m[5]);
 }
 constexpr float w43_sigma(int r) { return r == 1 ? (float)MP_W43_A : r == 2 ? (float)(MP_W43_A * MP_W43_A) : 1.f; }
 constexpr float w43_out_scale(int r, int c) { return w43_sigma(r) * w43_sigma(c); }
 // pre-bias output (r, c) of a tile from the scaled transform's value + the bias: ONE multiply-add (an add where the factor is 1)
-__device__ __forceinline__ mp_f32x2 w43_add_bias(mp_f32x2 z, int r, int c, mp_f32x2 bias)
+__device__ __forceinline__ f32x2 w43_add_bias(f32x2 z, int r, int c, f32x2 bias)
 {
     const float k = w43_out_scale(r, c);
-    return k == 1.f ? z + bias : __builtin_elementwise_fma(z, mp_f32x2{k, k}, bias);
+    return k == 1.f ? z + bias : __builtin_elementwise_fma(z, f32x2{k, k}, bias);
 }
 bool conv_wino43_supports(const ConvParams& p);
 long long conv_wino43_items(const ConvParams& p);      // work items the launch would have (B x tile blocks x slices)

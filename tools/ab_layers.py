@@ -34,6 +34,7 @@ for n, ms, fl in net.profile_read(): by.setdefault(n, []).append(ms)
 print('AB_RESULT ' + json.dumps({k: float(np.median(v)) for k, v in by.items()}))
 ''' % root
 res = {v: [] for v in variants}
+failed = None
 for r in range(rounds):
     for v in (variants if r % 2 == 0 else variants[::-1]):
         name, _, dbg = v.partition(':')
@@ -43,11 +44,23 @@ for r in range(rounds):
             env['MP_LIB'] = os.path.join(root, 'multipoint_amd', 'libmultipoint_hip_exp_%s.so' % name)
         if dbg:
             env['MP_DEBUG'] = dbg
-        out = subprocess.run([sys.executable, '-c', CHILD] + extra, env=env, capture_output=True, text=True).stdout
+        # a shared card: nothing more is started after a child that failed, hung or printed no result (the table of the
+        # rounds so far is still printed, and the exit status says so)
+        try:
+            done = subprocess.run([sys.executable, '-c', CHILD] + extra, env=env, capture_output=True, text=True, timeout=300)
+            rc, out, err = done.returncode, done.stdout, done.stderr
+        except subprocess.TimeoutExpired as e:
+            rc, out, err = 124, '', 'timed out after %d s' % e.timeout
         line = [l for l in out.split('\n') if l.startswith('AB_RESULT ')]
-        if line:
-            res[v].append(json.loads(line[0][10:]))
-layers = list(res[variants[0]][0].keys()) if res[variants[0]] else []
+        if rc != 0 or not line:
+            failed = 'round %d, variant %s: exit status %d%s\n%s' % (r, v, rc, '' if line else ', no AB_RESULT line', err[-2000:])
+            break
+        res[v].append(json.loads(line[0][10:]))
+    if failed:
+        break
+if failed and not all(res[v] for v in variants):
+    sys.exit('ab_layers: stopped at ' + failed)
+layers = list(res[variants[0]][0].keys())
 print('%-16s' % 'layer' + ''.join('%24s' % v for v in variants))
 for k in layers + ['total']:
     row = '%-16s' % k
@@ -56,3 +69,5 @@ for k in layers + ['total']:
         row += '   med %7.4f min %7.4f' % (float(np.median(xs)), min(xs))
     print(row)
 print('rounds per variant:', {v: len(res[v]) for v in variants})
+if failed:
+    sys.exit('ab_layers: stopped at ' + failed)
