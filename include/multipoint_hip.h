@@ -250,6 +250,25 @@ int mp_match_threshold(mp_handle* h, const float* descA, const int* countA, cons
                        long long pair_stride, int count_stride, int P, int K, int D, float threshold, int capacity,
                        int* list_ij, float* list_dist, int* list_count, void* stream);
 
+/* one-directional matching of P pairs at the speed of mp_match_mutual_nn (the same MFMA distance tiles, one direction,
+ * the two nearest per query); same descriptor / count addressing and the same [P][K] outputs as mp_match_mutual_nn, so
+ * mp_find_homography and the per-pair records take them unchanged.  Rows are taken as UNIT vectors (what
+ * mp_sample_descriptors always produces): the metric is sqrt(2 - 2 clip(a.b, -1, 1)), which for unit rows equals the
+ * L2 distance; for arbitrary rows use mp_match_knn2.  D must be 64, 128 or 256.
+ *   ratio <= 0  replaces cv2.BFMatcher(cv2.NORM_L2).match() without crossCheck (matching.py:7,31): every query row of
+ *               a pair with at least one train row is matched to its nearest (ties: the lower train index).
+ *   ratio > 0   replaces knnMatch(d1, d2, 2) plus Lowe's ratio test (matching.py:20-27): query i keeps its nearest iff
+ *               (double)d1 < ratio * (double)d2, compared in double as Python compares `m.distance < 0.9 * n.distance`
+ *               (pass 0.9, not 0.9f).  A pair with fewer than two train rows yields no matches (the reference's
+ *               `for m, n in all_matches` raises there).
+ *   match_idx [P][K]: train index of query i or -1; match_dist [P][K] (0 where unmatched); match_count [P]
+ *   second_idx / second_dist [P][K] or NULL: the second-nearest train row of every query row (-1 / 0 where the pair
+ *               has fewer than two train rows or i >= countA), whatever the ratio test decided */
+int mp_match_nearest(mp_handle* h, const float* descA, const int* countA, const float* descB, const int* countB,
+                     long long pair_stride, int count_stride, int P, int K, int D, double ratio,
+                     int* match_idx, float* match_dist, int* match_count,
+                     int* second_idx /* [P][K] or NULL */, float* second_dist /* [P][K] or NULL */, void* stream);
+
 /* ---- single-image detector metrics: multipoint/utils/evaluation.py:10-97 (predict_keypoints.py:88-104) ----
  * mp_detector_metrics replaces compute_tp_fp_dist (evaluation.py:56-97) for B heat maps at once:
  *   prob          fp32 [B][H][W]  detector map after valid mask / NMS (evaluation.py:19-25)

@@ -347,6 +347,12 @@ void launch_match_impl(const float* dA, const int* nA, const float* dB, const in
                        unsigned long long* rowbest, unsigned long long* colbest, int* match_idx,
                        float* match_dist, int* match_count, hipStream_t s);
 
+// one-directional matching of P pairs on the same MFMA tiles (match_nearest.hip): nearest train row per query (ratio <= 0) or
+// Lowe's ratio test on the two nearest (ratio > 0); best2: [MATCH_SHARES][P][K][2] packed scratch; second_* may be NULL
+void launch_match_nearest(const float* dA, const int* nA, const float* dB, const int* nB, long long pair_stride,
+                          int count_stride, int P, int K, int D, double ratio, unsigned long long* best2, int* match_idx,
+                          float* match_dist, int* match_count, int* second_idx, float* second_dist, hipStream_t s);
+
 // remaining get_matches modes (match_extra.hip): two nearest train rows per query (BFMatcher knnMatch / match without
 // crossCheck), idx/dist [P][K][2]; all pairs closer than thr (ThresholdMatcher), list_count [P] pre-set to 0
 void launch_match_knn2(const float* dA, const int* nA, const float* dB, const int* nB, long long pair_stride,

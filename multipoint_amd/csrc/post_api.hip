@@ -230,6 +230,27 @@ int mp_match_mutual_nn(mp_handle* h, const float* descA, const int* countA, cons
     return launch_status(h);
 }
 
+int mp_match_nearest(mp_handle* h, const float* descA, const int* countA, const float* descB, const int* countB,
+                     long long pair_stride, int count_stride, int P, int K, int D, double ratio, int* match_idx,
+                     float* match_dist, int* match_count, int* second_idx, float* second_dist, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!descA || !descB || !countA || !countB || !match_idx || !match_dist || !match_count)
+        return fail(h, MP_EINVAL, "mp_match_nearest: NULL tensor");
+    if (D != 64 && D != 128 && D != 256) return fail(h, MP_EINVAL, "mp_match_nearest: D must be 64, 128 or 256");
+    if (P <= 0 || P > 65535 || K <= 0) return fail(h, MP_EINVAL, "mp_match_nearest: need 0 < P <= 65535, K > 0");
+    if (ratio != ratio) return fail(h, MP_EINVAL, "mp_match_nearest: ratio is NaN");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MP_HIP(hipSetDevice(h->device));
+    const size_t need = (size_t)P * K * 8 * 2 * MATCH_SHARES;      // the two smallest packed keys per query row, one array per column share
+    int rc;
+    if ((rc = ensure(h, h->match_ws, need))) return rc;
+    launch_match_nearest(descA, countA, descB, countB, pair_stride, count_stride, P, K, D, ratio,
+                         static_cast<unsigned long long*>(h->match_ws.p), match_idx, match_dist, match_count, second_idx,
+                         second_dist, s);
+    return launch_status(h);
+}
+
 static int match_extra_check(mp_handle* h, const char* fn, const void* a, const void* b, const void* c, const void* d,
                              int P, int K, int D)
 {

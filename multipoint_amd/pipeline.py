@@ -15,10 +15,13 @@ from .utils import utils as U
 
 
 class PairResults:
-    def __init__(self, kp_yx, kp_score, kp_count, desc, match_idx, match_dist, match_count, H, W):
+    def __init__(self, kp_yx, kp_score, kp_count, desc, match_idx, match_dist, match_count, H, W, match_mode='mutual'):
         self.kp_yx, self.kp_score, self.kp_count = kp_yx, kp_score, kp_count
         self.desc = desc
         self.match_idx, self.match_dist, self.match_count = match_idx, match_dist, match_count
+        # which matcher filled match_idx: 'mutual' (mutual nearest neighbours: one-to-one), 'nearest' (every optical keypoint's
+        # nearest thermal one) or 'ratio' (the nearest, kept by Lowe's ratio test); the last two can name a thermal keypoint twice
+        self.match_mode = match_mode
         self.H, self.W = H, W
         self.done = None            # event recorded on the stream that produced these tensors
         self.inputs_consumed = None # event: the forward has read the input images (they may be overwritten after it)
@@ -84,22 +87,29 @@ class PairPipeline:
         self.nms_rounds = nms_rounds
         m = config.get('matching', {'method': 'bfmatcher', 'method_kwargs': {'crossCheck': True},
                                     'knn_matches': False})
-        # the batched pipeline keeps ONE match per optical keypoint (match_idx [P][K]): the mutual-NN matchers.  The other
-        # get_matches modes (ratio test, one-directional nearest, thresholdmatcher) run per pair through
-        # utils.get_matches (mp_match_knn2 / mp_match_threshold), as utils.compute_descriptor_metrics does.
-        if m.get('knn_matches', False):
-            raise NotImplementedError('PairPipeline batches the mutual-NN matchers only; use utils.get_matches for knn_matches')
+        # The batched pipeline keeps ONE match per optical keypoint (match_idx [P][K]).  That fits the mutual-NN matchers
+        # (mp_match_mutual_nn) and the one-directional modes of 'bfmatcher' (mp_match_nearest): the nearest thermal keypoint
+        # of every optical one, and the same behind Lowe's ratio test (`knn_matches: true`, ratio 0.9 as get_matches
+        # hard-codes it, matching.py:22).  'thresholdmatcher' is one-to-many -- every pair closer than the threshold -- and
+        # does not fit one match per query; it runs per pair through utils.get_matches (mp_match_threshold), as
+        # utils.compute_descriptor_metrics does.  Configurations get_matches rejects raise the same error here.
+        knn = bool(m.get('knn_matches', False))
+        self.match_mode, self.match_ratio = 'mutual', 0.0
         if m['method'] == 'bfmatcher':
-            if not m.get('method_kwargs', {}).get('crossCheck', False):
-                raise NotImplementedError('PairPipeline batches the mutual-NN matchers only; use utils.get_matches for '
-                                          'bfmatcher without crossCheck')
             self.match_threshold = -1.0
+            if m.get('method_kwargs', {}).get('crossCheck', False):
+                if knn:
+                    raise ValueError('BFMatcher: crossCheck=True supports knnMatch with k=1 only (as OpenCV)')
+            else:
+                self.match_mode, self.match_ratio = ('ratio', 0.9) if knn else ('nearest', 0.0)
         elif m['method'] == 'nnmatcher':
             self.match_threshold = float(m.get('method_kwargs', {}).get('threshold', 0.7))
             if self.match_threshold < 0:
                 raise ValueError('\'threshold\' should be non-negative')
+            if knn:
+                raise AttributeError("'NNMatcher' object has no attribute 'knnMatch'")      # matching.py:21
         elif m['method'] in ('thresholdmatcher', 'flann'):
-            raise NotImplementedError("PairPipeline batches the mutual-NN matchers only; use utils.get_matches for '%s'"
+            raise NotImplementedError("PairPipeline keeps one match per optical keypoint; use utils.get_matches for '%s'"
                                       % m['method'])
         else:
             raise ValueError('unknown matching method')
@@ -213,11 +223,17 @@ class PairPipeline:
         mcnt = torch.empty((P,), dtype=torch.int32, device=dev)
         h = _lib.get_handle(dev)
         with torch.cuda.device(dev):
-            h.check(h.lib.mp_match_mutual_nn(
-                h.ptr, _lib.ptr(desc), _lib.ptr(cnt), ctypes.c_void_p(desc.data_ptr() + K * D * 4),
-                ctypes.c_void_p(cnt.data_ptr() + 4), 2 * K * D, 2, P, K, D, float(self.match_threshold),
-                _lib.ptr(midx), _lib.ptr(mdist), _lib.ptr(mcnt), _lib.stream_ptr(dev)))
-        return PairResults(kp, sc, cnt, desc, midx, mdist, mcnt, H, W)
+            if self.match_mode == 'mutual':
+                h.check(h.lib.mp_match_mutual_nn(
+                    h.ptr, _lib.ptr(desc), _lib.ptr(cnt), ctypes.c_void_p(desc.data_ptr() + K * D * 4),
+                    ctypes.c_void_p(cnt.data_ptr() + 4), 2 * K * D, 2, P, K, D, float(self.match_threshold),
+                    _lib.ptr(midx), _lib.ptr(mdist), _lib.ptr(mcnt), _lib.stream_ptr(dev)))
+            else:
+                h.check(h.lib.mp_match_nearest(
+                    h.ptr, _lib.ptr(desc), _lib.ptr(cnt), ctypes.c_void_p(desc.data_ptr() + K * D * 4),
+                    ctypes.c_void_p(cnt.data_ptr() + 4), 2 * K * D, 2, P, K, D, self.match_ratio,
+                    _lib.ptr(midx), _lib.ptr(mdist), _lib.ptr(mcnt), None, None, _lib.stream_ptr(dev)))
+        return PairResults(kp, sc, cnt, desc, midx, mdist, mcnt, H, W, self.match_mode)
 
     def __call__(self, optical, thermal, mask_optical=None, mask_thermal=None):
         images = self.interleave(optical, thermal)

@@ -43,7 +43,11 @@ def ground_truth_homographies(h_optical, h_thermal):
 def pair_metrics(res, homography, threshold_keypoints):
     """GPU arithmetic of evaluation.py:287-328 for the pairs of a PairResults.
     homography: (2P,9) float64 from ground_truth_homographies().
-    Returns (metrics [P,8] int32 device tensor, tp [2P,K] uint8 device tensor); see include/multipoint_hip.h."""
+    Returns (metrics [P,8] int32 device tensor, tp [2P,K] uint8 device tensor); see include/multipoint_hip.h.
+    The results must hold MUTUAL matches: tp[2p+1] reads the same pair from the thermal side, which only a one-to-one
+    match list defines (the reference hard-codes the cross-check matcher for these metrics, evaluation.py:273-282)."""
+    if getattr(res, 'match_mode', 'mutual') != 'mutual':
+        raise ValueError("pair_metrics needs mutual matches; these results were matched in '%s' mode" % res.match_mode)
     res.wait()
     dev = res.kp_yx.device
     P = res.num_pairs
@@ -120,9 +124,9 @@ def _warp_yx(pts_yx, hmat):
 
 def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoints, threshold_warp=None):
     """Same signature and result keys as the reference function (evaluation.py:209)."""
-    from ..pipeline import PairPipeline
+    from ..pipeline import PairPipeline, PairResults
     from .utils import data_to_device
-    from .matching import get_matches
+    from .matching import get_matches, match_pairs, nearest_pairs
     # The metrics are ALWAYS computed on cv2.BFMatcher(crossCheck=True) matches, whatever the config says -- the
     # reference hard-codes that matcher for matches_optical / matches_thermal (evaluation.py:273-282) and uses
     # config['matching'] only for the matches the homography is estimated from (:332-336).
@@ -131,6 +135,11 @@ def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoi
     same_matcher = (mcfg.get('method', 'bfmatcher') == 'bfmatcher' and not mcfg.get('knn_matches', False)
                     and dict(mcfg.get('method_kwargs', {})) == {'crossCheck': True})
     pipe = PairPipeline(net, dict(config, matching=metric_matching))
+    # another ONE-match-per-keypoint matcher for the homography estimate (nnmatcher, bfmatcher without crossCheck, the ratio
+    # test) is batched like the default one; PairPipeline reads the configuration and raises what get_matches raises
+    sel = None
+    if not same_matcher and mcfg.get('method') in ('bfmatcher', 'nnmatcher'):
+        sel = PairPipeline(None, dict(config, matching=mcfg))
     tp_o, tp_t, dist_o, dist_t, ms_o, ms_t, pts_dist = [], [], [], [], [], [], []
     n_gt_o = n_gt_t = 0
     for data in dataloader:
@@ -144,11 +153,23 @@ def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoi
         gth = ground_truth_homographies(ho, ht)
         metrics, tp = pair_metrics(res, gth, threshold_keypoints)
         pipe.check_converged()
-        if same_matcher:
-            h_est, _, n_in = find_homography(res, config.get('reprojection_threshold', 3))
+        est = res if same_matcher else None
+        if sel is not None and res.kp_yx.shape[1] <= MAX_RANSAC_MATCHES:
+            # all pairs in one launch, on the result's own descriptor lists in place, then one batched RANSAC call
+            Kc, Dc = res.desc.shape[1:]
+            lay = dict(pair_stride=2 * Kc * Dc, count_stride=2)
+            if sel.match_mode == 'mutual':
+                mm = match_pairs(res.desc, res.kp_count, res.desc[1:], res.kp_count[1:], sel.match_threshold, **lay)
+            else:
+                mm = nearest_pairs(res.desc, res.kp_count, res.desc[1:], res.kp_count[1:], sel.match_ratio or None, **lay)
+            est = PairResults(res.kp_yx, res.kp_score, res.kp_count, res.desc, mm[0], mm[1], mm[2], res.H, res.W,
+                              sel.match_mode)
+        if est is not None:
+            h_est, _, n_in = find_homography(est, config.get('reprojection_threshold', 3))
             h_est = h_est.cpu().numpy(); n_in = n_in.cpu().numpy()
         else:
-            # another matcher for the homography estimate: per pair through get_matches (GPU), like the reference
+            # one-to-many matchers (thresholdmatcher) and lists longer than one RANSAC launch holds: per pair through
+            # get_matches (GPU), like the reference
             h_est = np.zeros((B, 3, 3)); n_in = np.zeros(B, dtype=np.int64)
             kp_all = res.kp_yx.cpu().numpy(); cnt_all = res.kp_count.cpu().numpy()
             Kc = kp_all.shape[1]

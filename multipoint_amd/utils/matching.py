@@ -1,6 +1,8 @@
 """Host-side mirror of multipoint/utils/matching.py: get_matches with the mutual-nearest-neighbour methods of the hot
 path ('bfmatcher' with crossCheck=True, 'nnmatcher') and the remaining modes ('bfmatcher' without crossCheck, the
-knn_matches ratio test, 'thresholdmatcher'); every distance matrix is evaluated on the GPU and never materialised."""
+knn_matches ratio test, 'thresholdmatcher'); every distance matrix is evaluated on the GPU and never materialised.
+match_pairs / nearest_pairs are the batched entries (all pairs of a batch in one launch, unit rows); get_matches is the
+per-pair function of the reference and accepts arbitrary rows."""
 import ctypes
 
 import numpy as np
@@ -8,7 +10,7 @@ import torch
 
 from .. import _lib
 
-__all__ = ['get_matches', 'NNMatcher', 'ThresholdMatcher', 'DMatch', 'match_pairs', 'knn2_pairs']
+__all__ = ['get_matches', 'NNMatcher', 'ThresholdMatcher', 'DMatch', 'match_pairs', 'knn2_pairs', 'nearest_pairs']
 
 
 class DMatch:
@@ -22,23 +24,65 @@ class DMatch:
         return 'DMatch(queryIdx=%d, trainIdx=%d, distance=%.6f)' % (self.queryIdx, self.trainIdx, self.distance)
 
 
-def match_pairs(descA, countA, descB, countB, threshold=-1.0):
+def _pair_layout(descA, countA, descB, countB, pair_stride, count_stride):
+    """Addressing of P pairs for the batched matchers.  Default: descA / descB [P,K,D] contiguous, countA / countB [P].
+    With `pair_stride` (floats between consecutive pairs) and `count_stride`, descA / descB / countA / countB are
+    contiguous views that BEGIN at the first pair's rows / counts and are read in place -- the interleaved lists of
+    PairResults: (desc, kp_count, desc[1:], kp_count[1:], pair_stride=2 * K * D, count_stride=2)."""
+    K, D = descA.shape[-2:]
+    if pair_stride is None:
+        P = descA.shape[0]
+        return (descA.contiguous(), countA.contiguous(), descB.contiguous(), countB.contiguous(), P, K, D, K * D,
+                int(count_stride))
+    count_stride = int(count_stride)
+    P = (countA.numel() + count_stride - 1) // count_stride
+    for d, c in ((descA, countA), (descB, countB)):
+        if not (d.is_contiguous() and c.is_contiguous()):
+            raise ValueError('strided matching reads contiguous views in place')
+        if P < 1 or d.numel() < (P - 1) * pair_stride + K * D or c.numel() < (P - 1) * count_stride + 1:
+            raise ValueError('descriptor / count views are shorter than %d pairs at these strides' % P)
+    return descA, countA, descB, countB, P, K, D, int(pair_stride), count_stride
+
+
+def match_pairs(descA, countA, descB, countB, threshold=-1.0, pair_stride=None, count_stride=1):
     """Mutual NN for P independent pairs on the GPU.
-    descA/descB [P,K,D] fp32 unit rows, countA/countB [P] int32.
+    descA/descB [P,K,D] fp32 unit rows, countA/countB [P] int32 (or strided views, see _pair_layout).
     Returns (match_idx [P,K] int32 (-1 = none), match_dist [P,K] f32, match_count [P] int32)."""
     dev = descA.device
-    P, K, D = descA.shape
-    descA = descA.contiguous(); descB = descB.contiguous()
+    descA, countA, descB, countB, P, K, D, pair_stride, count_stride = _pair_layout(descA, countA, descB, countB,
+                                                                                    pair_stride, count_stride)
     midx = torch.empty((P, K), dtype=torch.int32, device=dev)
     mdist = torch.empty((P, K), dtype=torch.float32, device=dev)
     mcnt = torch.empty((P,), dtype=torch.int32, device=dev)
     h = _lib.get_handle(dev)
     with torch.cuda.device(dev):
-        h.check(h.lib.mp_match_mutual_nn(h.ptr, _lib.ptr(descA), _lib.ptr(countA.contiguous()),
-                                         _lib.ptr(descB), _lib.ptr(countB.contiguous()),
-                                         K * D, 1, P, K, D, float(threshold), _lib.ptr(midx),
+        h.check(h.lib.mp_match_mutual_nn(h.ptr, _lib.ptr(descA), _lib.ptr(countA), _lib.ptr(descB), _lib.ptr(countB),
+                                         pair_stride, count_stride, P, K, D, float(threshold), _lib.ptr(midx),
                                          _lib.ptr(mdist), _lib.ptr(mcnt), _lib.stream_ptr(dev)))
     return midx, mdist, mcnt
+
+
+def nearest_pairs(descA, countA, descB, countB, ratio=None, return_second=False, pair_stride=None, count_stride=1):
+    """One-directional matching for P independent pairs on the GPU (mp_match_nearest; unit rows, D in {64, 128, 256}).
+    `ratio=None`: every query row is matched to its nearest train row (BFMatcher.match without crossCheck);
+    `ratio=r`: kept iff distance < r * second distance (knnMatch(.., 2) + Lowe's ratio test; get_matches uses 0.9).
+    Returns (match_idx [P,K] int32 (-1 = none), match_dist [P,K] f32, match_count [P] int32), with `return_second`
+    followed by (second_idx [P,K] int32, second_dist [P,K] f32): the second-nearest train row of every query."""
+    dev = descA.device
+    descA, countA, descB, countB, P, K, D, pair_stride, count_stride = _pair_layout(descA, countA, descB, countB,
+                                                                                    pair_stride, count_stride)
+    midx = torch.empty((P, K), dtype=torch.int32, device=dev)
+    mdist = torch.empty((P, K), dtype=torch.float32, device=dev)
+    mcnt = torch.empty((P,), dtype=torch.int32, device=dev)
+    sidx = torch.empty((P, K), dtype=torch.int32, device=dev) if return_second else None
+    sdist = torch.empty((P, K), dtype=torch.float32, device=dev) if return_second else None
+    h = _lib.get_handle(dev)
+    with torch.cuda.device(dev):
+        h.check(h.lib.mp_match_nearest(h.ptr, _lib.ptr(descA), _lib.ptr(countA), _lib.ptr(descB), _lib.ptr(countB),
+                                       pair_stride, count_stride, P, K, D, 0.0 if ratio is None else float(ratio),
+                                       _lib.ptr(midx), _lib.ptr(mdist), _lib.ptr(mcnt), _lib.ptr(sidx), _lib.ptr(sdist),
+                                       _lib.stream_ptr(dev)))
+    return (midx, mdist, mcnt, sidx, sdist) if return_second else (midx, mdist, mcnt)
 
 
 def _mutual_nn(desc_1, desc_2, threshold):

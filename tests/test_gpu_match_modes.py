@@ -1,0 +1,336 @@
+"""GPU (MI355X): the one-directional matcher modes -- mp_match_nearest (the nearest train row of every query, and Lowe's
+ratio test on the two nearest) from the kernel up to PairPipeline and utils.compute_descriptor_metrics.
+
+There is no reference-held vector for the matchers (OpenCV is absent), so the yardstick is a float64 numpy evaluation
+of the same definition on the float32 inputs: u = 2 - 2 clip(a.b, -1, 1) (the squared L2 distance of unit rows),
+neighbours sorted by (u, train index), ratio test u1 < ratio^2 u2 with ratio^2 evaluated in double.
+
+Tolerance.  tau = 2 (D + 2) 2^-24 is the worst-case error of an fp32 dot product of D terms of unit rows, carried into u.
+Two train rows whose float64 u differ by more than 2 tau are ordered the same way by any fp32 evaluation; a query is
+AMBIGUOUS when a non-zero gap between its sorted first, second and third u lies in (0, 2 tau] -- there either order is a
+correct answer.  Exact ties (gap 0: identical train rows) are not ambiguous: the lower train index comes first."""
+import random
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+K = 160
+PAIRS = [(160, 130), (37, 160), (129, 33), (5, 2), (3, 1), (0, 7), (7, 0)]
+# 129 rows cross the 128-row workgroup boundary; 130 and 33 columns the 32-column tile and the column-share boundary;
+# M = 2 and M = 1 are the top-2 edges; two pairs have an empty side
+RATIO = 0.9
+MAX_AMBIGUOUS = 0.02
+
+
+def tau(D):
+    return 2.0 * (D + 2) * 2.0 ** -24
+
+
+def _unit(x):
+    return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)
+
+
+def make_pair(D, case):
+    """A: unit Gaussian rows.  Two thirds of min(N, M) rows of B, at permuted positions, are noisy copies of permuted rows
+    of A (noise 0.9 U(0.2, 2) per row: distance ratios on both sides of Lowe's 0.9), the rest random unit rows; one planted
+    row of B is copied over another row, which makes exact distance ties.
+    Checked on the CPU for the seeds used (100 D + case): the ratio test keeps 15-62 % of the queries of the pairs with
+    more than 5 rows; no query is nearer than 1.2e-4 in u (15 tau at D = 64, where it occurs; >= 0.03 elsewhere) to the
+    ratio boundary; the only ambiguous queries are 2 of the 160 x 130 case at D = 256 (1.25 % <= 2 %)."""
+    N, M = PAIRS[case]
+    rng = np.random.default_rng(100 * D + case)
+    A = _unit(rng.standard_normal((N, D))) if N else np.zeros((0, D), np.float32)
+    B = _unit(rng.standard_normal((M, D))) if M else np.zeros((0, D), np.float32)
+    n_pl = (2 * min(N, M)) // 3
+    if n_pl:
+        pos = rng.permutation(M)[:n_pl]; src = rng.permutation(N)[:n_pl]
+        s = 0.9 * rng.uniform(0.2, 2.0, (n_pl, 1))
+        B[pos] = _unit(A[src].astype(np.float64) + s * rng.standard_normal((n_pl, D)) / np.sqrt(D))
+        if M >= 2:
+            other = (pos[0] + 1 + int(rng.integers(0, M - 1))) % M
+            B[other] = B[pos[0]]
+    return A, B
+
+
+def reference(A, B, D):
+    """float64 yardstick: (order [N, min(M, 3)] train indices by (u, index), u sorted alike, ambiguous [N] bool, u [N, M])."""
+    N, M = len(A), len(B)
+    u = 2.0 - 2.0 * np.clip(A.astype(np.float64) @ B.astype(np.float64).T, -1.0, 1.0)
+    order = np.argsort(u, axis=1, kind='stable')[:, :3]              # stable: equal u -> lower index first
+    us = np.take_along_axis(u, order, 1)
+    gaps = np.diff(us, axis=1)
+    amb = ((gaps > 0) & (gaps <= 2 * tau(D))).any(axis=1) if M >= 2 else np.zeros(N, bool)
+    return order, us, amb, u
+
+
+@pytest.fixture(scope='module')
+def cases():
+    """Inputs and their float64 reference, computed once per D and left unchanged."""
+    out = {}
+    for D in (64, 128, 256):
+        prs = [make_pair(D, c) for c in range(len(PAIRS))]
+        out[D] = (prs, [reference(a, b, D) for a, b in prs])
+    return out
+
+
+def _layouts(prs, D):
+    """The same pairs in the separate layout ([P,K,D] x 2) and in the interleaved one (slot 2p = A, 2p+1 = B)."""
+    P = len(prs)
+    inter = np.zeros((2 * P, K, D), np.float32); cnt = np.zeros(2 * P, np.int32)
+    for p, (a, b) in enumerate(prs):
+        inter[2 * p, :len(a)] = a; inter[2 * p + 1, :len(b)] = b
+        cnt[2 * p], cnt[2 * p + 1] = len(a), len(b)
+    t = torch.from_numpy(inter).to(DEV); c = torch.from_numpy(cnt).to(DEV)
+    sep = (t[0::2].contiguous(), c[0::2].contiguous(), t[1::2].contiguous(), c[1::2].contiguous(), {})
+    ilv = (t, c, t[1:], c[1:], dict(pair_stride=2 * K * D, count_stride=2))
+    return {'separate': sep, 'interleaved': ilv}
+
+
+def _run(layout, ratio):
+    from multipoint_amd.utils import nearest_pairs
+    a, ca, b, cb, kw = layout
+    out = nearest_pairs(a, ca, b, cb, ratio=ratio, return_second=True, **kw)
+    torch.cuda.synchronize()
+    return [o.cpu().numpy() for o in out]
+
+
+@pytest.mark.parametrize('layout', ['separate', 'interleaved'])
+@pytest.mark.parametrize('D', [64, 128, 256])
+def test_kernel_against_float64(cases, D, layout):
+    prs, refs = cases[D]
+    lay = _layouts(prs, D)[layout]
+    near = _run(lay, None)
+    rat = _run(lay, RATIO)
+    for again, first in ((_run(lay, None), near), (_run(lay, RATIO), rat)):          # two runs are bit-identical
+        for x, y in zip(again, first):
+            assert np.array_equal(x.view(np.int32), y.view(np.int32))
+    t2 = 2 * tau(D)
+    for p, ((A, B), (order, us, amb, u)) in enumerate(zip(prs, refs)):
+        N, M = len(A), len(B)
+        midx, mdist, mcnt, sidx, sdist = (x[p] if x.ndim > 1 else x for x in near)
+        ridx, rdist, rcnt, rsidx, rsdist = (x[p] if x.ndim > 1 else x for x in rat)
+        # rows at or beyond the count hold -1 / 0
+        for ix, ds in ((midx, mdist), (sidx, sdist), (ridx, rdist), (rsidx, rsdist)):
+            assert (ix[N:] == -1).all() and (ds[N:] == 0).all()
+        assert np.array_equal(sidx, rsidx) and np.array_equal(sdist, rsdist)          # the second neighbour ignores the mode
+        print('D %d %s pair %d (%d x %d): %d ambiguous' % (D, layout, p, N, M, int(amb.sum())))
+        assert amb.sum() <= MAX_AMBIGUOUS * max(N, 1)
+        if N == 0:
+            assert mcnt[p] == 0 and rcnt[p] == 0
+            continue
+        if M == 0:
+            assert (midx[:N] == -1).all() and (sidx[:N] == -1).all() and mcnt[p] == 0 and rcnt[p] == 0
+            assert (ridx[:N] == -1).all()
+            continue
+        ok = ~amb
+        # one-way mode: every query is matched to its nearest
+        assert mcnt[p] == N and (midx[:N] >= 0).all()
+        assert np.array_equal(midx[:N][ok], order[ok, 0])
+        rows = np.arange(N)
+        assert np.abs(mdist[:N].astype(np.float64) ** 2 - u[rows, midx[:N]]).max() <= t2         # |d^2 - u64| <= 2 tau
+        assert (u[rows, midx[:N]] - us[:, 0]).max() <= t2                 # (an ambiguous query still has a nearest within 2 tau)
+        if M == 1:
+            assert (sidx[:N] == -1).all() and (sdist[:N] == 0).all()
+            assert rcnt[p] == 0 and (ridx[:N] == -1).all()            # ratio mode needs two train rows: no matches
+            continue
+        assert np.array_equal(sidx[:N][ok], order[ok, 1])
+        assert (sidx[:N] >= 0).all() and (sidx[:N] != midx[:N]).all()
+        assert np.abs(sdist[:N].astype(np.float64) ** 2 - u[rows, sidx[:N]]).max() <= t2
+        assert (u[rows, sidx[:N]] - us[:, 1]).max() <= t2
+        # ratio mode: decision, count and matched set exact for ALL queries
+        keep = us[:, 0] < (RATIO * RATIO) * us[:, 1]
+        margin = np.abs(us[:, 0] - (RATIO * RATIO) * us[:, 1]).min()
+        print('    ratio test keeps %d of %d, nearest to the boundary %.3g' % (int(keep.sum()), N, margin))
+        # a condition on the inputs, not on the kernel: both sides of u1 < ratio^2 u2 carry an error of at most tau (and a
+        # few roundings of the square roots), so a boundary further away than 4 tau is decided alike by any fp32 evaluation
+        assert margin > 4 * tau(D)
+        assert np.array_equal(ridx[:N] >= 0, keep) and rcnt[p] == int(keep.sum())
+        assert np.array_equal(ridx[:N][keep], midx[:N][keep]) and np.array_equal(rdist[:N][keep], mdist[:N][keep])
+        assert (rdist[:N][~keep] == 0).all()
+
+
+@pytest.mark.parametrize('D', [64, 128, 256])
+def test_against_per_pair_get_matches(cases, D):
+    """The batched matcher against the existing per-pair route (utils.get_matches on mp_match_knn2, true L2 distances):
+    outside the ambiguous queries the matched (queryIdx, trainIdx) sets are identical."""
+    from multipoint_amd.utils import get_matches
+    prs, refs = cases[D]
+    lay = _layouts(prs, D)['separate']
+    near, rat = _run(lay, None), _run(lay, RATIO)
+    for p, ((A, B), (_, _, amb, _)) in enumerate(zip(prs, refs)):
+        N, M = len(A), len(B)
+        for knn, got in ((False, near), (True, rat)):
+            have = {(i, int(got[0][p, i])) for i in range(N) if got[0][p, i] >= 0 and not amb[i]}
+            if knn and N > 0 and M < 2:
+                # get_matches raises for knn_matches with fewer than two train rows (`for m, n in all_matches`); the
+                # batched matcher returns no matches there (a stated deviation)
+                with pytest.raises(ValueError):
+                    get_matches(A, B, 'bfmatcher', True)
+                assert not have
+                continue
+            want = {(m.queryIdx, m.trainIdx) for m in get_matches(A, B, 'bfmatcher', knn) if not amb[m.queryIdx]}
+            assert have == want, (D, p, knn)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# pipeline and metric driver
+# ----------------------------------------------------------------------------------------------------------------------
+MODES = {'ratio': {'method': 'bfmatcher', 'method_kwargs': {}, 'knn_matches': True},
+         'nearest': {'method': 'bfmatcher', 'method_kwargs': {}, 'knn_matches': False}}
+DEFAULT = {'method': 'bfmatcher', 'method_kwargs': {'crossCheck': True}, 'knn_matches': False}
+
+
+@pytest.fixture(scope='module')
+def net(oracle):
+    import multipoint_amd.models as models
+    cfg = dict(oracle.SHIPPED_MODEL_CONFIG)
+    n = models.MultiPoint(cfg); n.load_state_dict(oracle.make_weights(0, cfg)); n.to(DEV); n.eval()
+    return n
+
+
+def _pred(matching):
+    return {'nms': 4, 'detection_threshold': 0.015, 'topk': 300, 'cpu_nms': True, 'reprojection_threshold': 3,
+            'matching': matching}
+
+
+@pytest.mark.parametrize('mode', ['ratio', 'nearest'])
+def test_pipeline_modes(oracle, net, mode):
+    import multipoint_amd.utils as U
+    from multipoint_amd.pipeline import PairPipeline
+    opt = oracle.make_images(5, 2, 120, 160).to(DEV)
+    th = torch.roll(opt, shifts=(2, 3), dims=(2, 3)).contiguous()           # shifted content: correspondences exist
+    pipe = PairPipeline(net, _pred(MODES[mode]))
+    res = pipe.run_converged(PairPipeline.interleave(opt, th))
+    assert res.match_mode == mode
+    Kp, D = res.desc.shape[1:]
+    ratio = RATIO if mode == 'ratio' else None
+    midx, mdist, mcnt = U.nearest_pairs(res.desc, res.kp_count, res.desc[1:], res.kp_count[1:], ratio=ratio,
+                                        pair_stride=2 * Kp * D, count_stride=2)
+    assert torch.equal(midx, res.match_idx) and torch.equal(mcnt, res.match_count)
+    assert torch.equal(mdist.view(torch.int32), res.match_dist.view(torch.int32))
+    assert int(res.match_count.sum()) > 0
+    for p, rec in enumerate(res.to_host()):
+        _, _, amb, _ = reference(rec['desc_optical'], rec['desc_thermal'], D)
+        print('%s pair %d: %d of %d queries ambiguous' % (mode, p, int(amb.sum()), len(amb)))
+        want = {(m.queryIdx, m.trainIdx) for m in U.get_matches(rec['desc_optical'], rec['desc_thermal'], 'bfmatcher',
+                                                                mode == 'ratio') if not amb[m.queryIdx]}
+        have = {(int(q), int(t)) for q, t in zip(rec['match_query'], rec['match_train']) if not amb[q]}
+        assert have == want
+        assert len(rec['match_query']) == int(res.match_count[p])
+    with pytest.raises(ValueError, match='mutual'):
+        U.pair_metrics(res, U.ground_truth_homographies(torch.eye(3).repeat(2, 1, 1), torch.eye(3).repeat(2, 1, 1)), 4.0)
+
+
+def _loader(batch_size):
+    """The SamePair construction of tests/test_gpu_metrics.py::test_descriptor_metrics_matcher_config."""
+    from multipoint_amd.datasets import SyntheticPairs
+    from oracle import ha_oracle as HA
+    hc = dict(HA.PREDICTION_AUGMENTATION)
+    hc['params'] = dict(hc['params'], perspective_amplitude_x=0.02, perspective_amplitude_y=0.02, max_angle=0.05,
+                        scaling_amplitude=0.02)                        # mild warps: the matches support a homography
+    ds = SyntheticPairs({'num_samples': 4, 'height': 120, 'width': 160, 'augmentation': {'homographic': hc}})
+
+    class SamePair(torch.utils.data.Dataset):                     # thermal := optical content, so matches exist
+        def __len__(self): return len(ds)
+        def __getitem__(self, i):
+            random.seed(10 + i); np.random.seed(20 + i)
+            s = ds[i]
+            base = torch.from_numpy(SyntheticPairs.make_pair(0, i, 120, 160)[0])
+            if torch.equal(s['optical']['homography'], torch.eye(3)):
+                s['optical']['image'] = base
+            else:
+                s['thermal']['image'] = base
+            return s
+    return torch.utils.data.DataLoader(SamePair(), batch_size=batch_size, shuffle=False, num_workers=0)
+
+
+def _corner_dist(h_est, gt, H_o, W_o):
+    from multipoint_amd.utils.evaluation import _warp_yx
+    pts = np.array([[0, 0], [H_o, 0], [0, W_o], [H_o, H_o]])           # the reference's corner list (evaluation.py:351-356)
+    return np.linalg.norm(_warp_yx(pts, h_est) - _warp_yx(pts, gt), axis=1).sum() / 4
+
+
+def _per_pair_routes(net, batch_size):
+    """For every sample of the loader, the routes that exist without the batched matcher modes:
+    'default_batch'   find_homography on the batch's mutual matches,
+    'default_pair'    find_homography_points per pair over to_host(),
+    mode              get_matches + find_homography_points per pair (what the driver ran for these modes before),
+    plus, per mode, whether the batched match list equals the per-pair one.  Returns {name: [pts_dist per sample]}, equal."""
+    import multipoint_amd.utils as U
+    from multipoint_amd.pipeline import PairPipeline
+    from multipoint_amd.utils.evaluation import find_homography, find_homography_points, ground_truth_homographies
+    pipe = PairPipeline(net, _pred(DEFAULT))
+    out = {k: [] for k in ('default_batch', 'default_pair', 'ratio', 'nearest')}
+    equal = {'ratio': [], 'nearest': []}
+    for data in _loader(batch_size):
+        data = U.data_to_device(data, DEV)
+        opt, th = data['optical'], data['thermal']
+        res = pipe(opt['image'], th['image'], opt.get('valid_mask'), th.get('valid_mask'))
+        gth = ground_truth_homographies(opt['homography'], th['homography'])
+        H_o, W_o = opt['image'].shape[2:]
+        hb, _, nb = find_homography(res, 3)
+        hb = hb.cpu().numpy(); nb = nb.cpu().numpy()
+        recs = res.to_host()
+        Kp, D = res.desc.shape[1:]
+        batched = {m: U.nearest_pairs(res.desc, res.kp_count, res.desc[1:], res.kp_count[1:],
+                                      ratio=RATIO if m == 'ratio' else None, pair_stride=2 * Kp * D,
+                                      count_stride=2)[0].cpu().numpy() for m in MODES}
+        for p, rec in enumerate(recs):
+            gt = gth[2 * p].numpy().reshape(3, 3)
+            out['default_batch'].append(_corner_dist(hb[p], gt, H_o, W_o) if nb[p] >= 4 else 999.0)
+
+            def estimate(q, t):
+                if len(q) < 4:
+                    return 999.0
+                hp, mask = find_homography_points(rec['kp_optical'][q][:, ::-1], rec['kp_thermal'][t][:, ::-1], 3, device=DEV)
+                return _corner_dist(hp, gt, H_o, W_o) if hp is not None and mask.sum() >= 4 else 999.0
+            out['default_pair'].append(estimate(rec['match_query'], rec['match_train']))
+            for m, cfg in MODES.items():
+                ms = U.get_matches(rec['desc_optical'], rec['desc_thermal'], cfg['method'], cfg['knn_matches'])
+                q = np.array([mm.queryIdx for mm in ms], np.int64); t = np.array([mm.trainIdx for mm in ms], np.int64)
+                out[m].append(estimate(q, t))
+                bi = batched[m][p, :len(rec['kp_optical'])]
+                bq = np.nonzero(bi >= 0)[0]
+                equal[m].append(np.array_equal(bq, q) and np.array_equal(bi[bq], t))
+    return out, equal
+
+
+def test_driver_single_pair_batches_equal_per_pair_route(net):
+    """Batch size 1: the RANSAC sampler's pair index is 0 on both routes, the seed is the same and the matches are gathered
+    in query order, so wherever the batched match list equals the per-pair one the estimate is the same to float64
+    rounding."""
+    import multipoint_amd.utils as U
+    ref, equal = _per_pair_routes(net, 1)
+    for m, cfg in MODES.items():
+        got = U.compute_descriptor_metrics(net, _loader(1), DEV, _pred(cfg), 4, 3)['pts_dist']
+        print('%s: %d of %d batched match lists equal the per-pair list; pts_dist driver %s per pair %s'
+              % (m, sum(equal[m]), len(equal[m]), np.array2string(np.asarray(got), precision=6),
+                 np.array2string(np.asarray(ref[m]), precision=6)))
+        assert len(got) == 4
+        for i in range(4):
+            if equal[m][i]:
+                assert abs(got[i] - ref[m][i]) <= 1e-9 * max(1.0, abs(ref[m][i])), (m, i, got[i], ref[m][i])
+
+
+def test_driver_batches_of_two_agree_with_per_pair_route(net):
+    """Batch size 2: the second pair of a batch draws other RANSAC samples than a single-pair call does (the sampler depends
+    on the pair index).  The yardstick for that is measured in the same run between the two routes that exist for the
+    DEFAULT matcher -- find_homography on the batch against find_homography_points per pair over to_host() -- and the
+    new modes may differ from their per-pair route by twice that; the h_correctness decision (< 3 px) must agree."""
+    import multipoint_amd.utils as U
+    ref, _ = _per_pair_routes(net, 2)
+    base = np.abs(np.asarray(ref['default_batch']) - np.asarray(ref['default_pair'])).max()
+    print('default matcher, batch vs per pair: max |pts_dist difference| = %.6g px' % base)
+    for m, cfg in MODES.items():
+        out = U.compute_descriptor_metrics(net, _loader(2), DEV, _pred(cfg), 4, 3)
+        got = np.asarray(out['pts_dist']); want = np.asarray(ref[m])
+        diff = np.abs(got - want).max()
+        print('%s: pts_dist driver %s per pair %s, max difference %.6g px' % (m, got, want, diff))
+        assert np.array_equal(got < 3, want < 3)
+        assert out['h_correctness'] == (want < 3).sum() / len(want)
+        # measured on an MI355X: base 7.32 px (the estimates on these synthetic-weight pairs are unstable: 88-128 px from the
+        # ground truth); nearest 0.0077 px; ratio 0 (fewer than 4 matches survive the ratio test: 999 on both routes)
+        assert diff <= 2 * base
