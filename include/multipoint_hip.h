@@ -193,7 +193,8 @@ int mp_sample_descriptors(mp_handle* h, const float* desc, int B, int Hc, int Wc
  *   descA/descB: first pair's descriptors [K][D]; pair p at + p * pair_stride floats
  *   countA/countB: int32, pair p at [p * count_stride]
  *   threshold < 0 disables the distance test (plain mutual NN == crossCheck)
- *   match_idx [P][K]: train index of query i or -1; match_dist [P][K]; match_count [P] */
+ *   match_idx [P][K]: train index of query i or -1; match_dist [P][K]; match_count [P]
+ *   0 < P <= 65535 (all four matchers: a pair is a row of the launch grid), K > 0, D must be 64, 128 or 256 */
 int mp_match_mutual_nn(mp_handle* h, const float* descA, const int* countA, const float* descB,
                        const int* countB, long long pair_stride, int count_stride, int P, int K,
                        int D, float threshold, int* match_idx, float* match_dist, int* match_count,

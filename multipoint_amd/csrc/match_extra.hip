@@ -1,5 +1,5 @@
 // The remaining matcher modes of utils.get_matches (reference multipoint/utils/matching.py:4-33, :74-99), next to the
-// mutual-NN kernels of sample_match.hip:
+// mutual-NN kernels of match_mfma.hip:
 //
 //  * knn2_kernel       cv2.BFMatcher(cv2.NORM_L2).knnMatch(d1, d2, 2) and .match() without crossCheck: for every query
 //                      row the two nearest train rows under || a - b ||_2 (float32 sum of squared differences, then

@@ -340,14 +340,15 @@ void launch_extract_threshold(const float* map, const unsigned char* mask, int B
 void launch_sample_desc(const float* desc, int B, int Hc, int Wc, int D, int H, int W,
                         const int* kp_yx, const int* kp_count, int K, float* out, hipStream_t s);
 
-// mutual nearest neighbour matching of P pairs; rowbest/colbest: [P][K] packed scratch
-constexpr int MATCH_SHARES = 2;     // column shares of the matcher's arg-min passes (sample_match.hip); rowbest / colbest hold one array per share
+// MFMA matchers (match_mfma.hip, unit rows, D in {64, 128, 256}); their scratch holds one array of packed keys per column share
+constexpr int MATCH_SHARES = 2;     // column shares of the row passes (mp_match.h: column_share)
+// mutual nearest neighbour matching of P pairs; rowbest/colbest: [MATCH_SHARES][P][K] packed scratch each
 void launch_match_impl(const float* dA, const int* nA, const float* dB, const int* nB,
                        long long pair_stride, int count_stride, int P, int K, int D, float thr,
                        unsigned long long* rowbest, unsigned long long* colbest, int* match_idx,
                        float* match_dist, int* match_count, hipStream_t s);
 
-// one-directional matching of P pairs on the same MFMA tiles (match_nearest.hip): nearest train row per query (ratio <= 0) or
+// one-directional matching of P pairs on the same tile walk: nearest train row per query (ratio <= 0) or
 // Lowe's ratio test on the two nearest (ratio > 0); best2: [MATCH_SHARES][P][K][2] packed scratch; second_* may be NULL
 void launch_match_nearest(const float* dA, const int* nA, const float* dB, const int* nB, long long pair_stride,
                           int count_stride, int P, int K, int D, double ratio, unsigned long long* best2, int* match_idx,

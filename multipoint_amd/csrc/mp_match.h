@@ -1,0 +1,143 @@
+// The MFMA matchers' walk over the distance tiles (match_mfma.hip): packed keys, column shares, the two running states and
+// the tile loop that nn_rows_kernel and near2_rows_kernel share.  Internal header.
+//
+// X rows against Y rows, both unit: d = sqrt(u), u = 2 - 2 clip(x.y, -1, 1).  Each wave owns one 32-row block of X; the four
+// waves of a workgroup walk the same 32-column tiles of Y, which reach them through LDS: a tile is 32 x D contiguous floats,
+// staged with fully coalesced 16-byte loads (one 1 KiB run per wave instruction) one tile ahead, and read back as MFMA
+// fragments (padded rows: conflict free).  Fetching the fragments straight from global memory -- 16 bytes out of every
+// 128-byte line of 32 lines per load instruction, each wave for itself -- kept the kernel at twice its MFMA time (131 us for
+// 62 us of v_mfma_f32_32x32x2_f32).  The products are formed TRANSPOSED (Y fragment as the A operand): lane li owns X row
+// r0 + li, its 16 accumulator registers are 16 columns of the tile, and the columns reach a lane in ascending order.
+#pragma once
+#include "mp_common.h"
+
+constexpr unsigned long long NO_KEY = ~0ull;             // (distance bits 0xffffffff are a NaN: never a real key)
+
+// (distance bits << 32 | column): ordered by distance, equal distances by the lower column
+__device__ __forceinline__ unsigned long long match_key(float u, int col)
+{
+    return ((unsigned long long)__float_as_uint(sqrtf(u)) << 32) | (unsigned)col;
+}
+
+// the two smallest of the union of two ascending key pairs
+__device__ __forceinline__ void merge2(unsigned long long& k1, unsigned long long& k2, unsigned long long o1,
+                                       unsigned long long o2)
+{
+    const unsigned long long lo = k1 < o1 ? k1 : o1, hi = k1 < o1 ? o1 : k1, s = k2 < o2 ? k2 : o2;
+    k1 = lo;
+    k2 = hi < s ? hi : s;
+}
+
+// The Y columns are cut into `nsplit` contiguous shares of whole tiles, each share leaves its own array of keys (the epilogue
+// kernels merge them) -- twice the waves per SIMD for the same work: the epilogue of one wave has another wave's MFMAs to
+// hide behind.
+struct ColumnShare { int c_begin, c_end; };
+__device__ __forceinline__ ColumnShare column_share(int ny, int share, int nsplit)
+{
+    const int ntile = (ny + 31) >> 5, per = (ntile + nsplit - 1) / nsplit;
+    return {min(share * per, ntile) * 32, min(min((share + 1) * per, ntile) * 32, ny)};
+}
+
+// ONE running arg-min per lane, over columns that arrive in ascending order, so a later column replaces the best one only
+// with a strictly smaller distance.  d = sqrt(u) is monotone in u: "u < the smallest u seen" is a necessary condition that
+// costs one compare, and the correctly rounded sqrt (~20 instructions) + 64-bit key update run only for candidates that pass
+// it -- a lane has seen 16 (t - 1) columns before tile t, so few do.  Keys, hence ties (lowest index wins), are exactly those
+// of the per-element form.
+struct KeepNearest {
+    unsigned long long run = NO_KEY;
+    float ub = __builtin_inff();
+    __device__ __forceinline__ void offer(float u, int col, bool in_range)
+    {
+        if (in_range && u < ub) {
+            ub = u;
+            const unsigned long long key = match_key(u, col);
+            run = key < run ? key : run;
+        }
+    }
+};
+
+// Two running keys per lane, k1 < k2, and the u each of them came from.  A column whose u is not below ub2 has d >= the
+// second distance and a larger index: its key cannot enter.  "u < ub2" (strict) is the one compare every element pays; the
+// correctly rounded sqrt and the 64-bit updates run only behind it.  Keys are distinct (the index is part of the key), so
+// "the two smallest keys of a row" is a pure function of the inputs whatever the order in which lanes, half-waves and shares
+// are merged, and exact distance ties go to the lower index first.
+struct KeepTwoNearest {
+    float ub1 = __builtin_inff(), ub2 = __builtin_inff();
+    unsigned long long k1 = NO_KEY, k2 = NO_KEY;
+    __device__ __forceinline__ void offer(float u, int col, bool in_range)
+    {
+        if (in_range && u < ub2) {
+            const unsigned long long key = match_key(u, col);
+            if (key < k1) { k2 = k1; ub2 = ub1; k1 = key; ub1 = u; }
+            else if (key < k2) { k2 = key; ub2 = u; }                 // (equal d, larger index: neither)
+        }
+    }
+};
+
+// Offers every column of [c_begin, c_end) of Y (ny rows) to `keep` for X row r0 + li, li = lane & 31; the lane's half-wave,
+// half = lane >> 5, sees the columns with (col & 4) == 4 * half.  Called by all 256 threads of the workgroup: a wave without
+// rows (returns false) still stages tiles and meets the barriers.
+template <int D, class Keep>
+__device__ __forceinline__ bool walk_tiles(const float* __restrict__ X, const float* __restrict__ Y, int nx, int ny,
+                                           int c_begin, int c_end, int r0, int li, int half, Keep& keep)
+{
+    constexpr int RS = D + 4;                            // LDS row stride in floats
+    __shared__ __attribute__((aligned(16))) float ytile[2][32 * RS];
+    const int tid = threadIdx.x;
+    const bool active = r0 < nx;
+
+    constexpr int NG = D / 8;
+    f32x4 a[NG];
+    {
+        const int row = min(r0 + li, nx - 1);
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+            a[g] = *reinterpret_cast<const f32x4*>(X + (long long)row * D + g * 8 + half * 4);
+    }
+    // staging: the tile's 32 * D / 4 granules of 16 bytes, D / 32 per thread (rows beyond ny repeat row ny - 1; never selected)
+    constexpr int GPT = D / 32, GPR = D / 4;
+    f32x4 stage[GPT];
+    auto gload = [&](int c0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < GPT; ++k) {
+            const int gran = tid + k * 256;
+            const int row = gran / GPR, q = gran - row * GPR;
+            stage[k] = *reinterpret_cast<const f32x4*>(Y + (long long)min(c0 + row, ny - 1) * D + q * 4);
+        }
+    };
+    auto lstore = [&](int buf) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < GPT; ++k) {
+            const int gran = tid + k * 256;
+            const int row = gran / GPR, q = gran - row * GPR;
+            *reinterpret_cast<f32x4*>(&ytile[buf][row * RS + q * 4]) = stage[k];
+        }
+    };
+    if (c_begin < c_end) { gload(c_begin); lstore(0); }
+    __syncthreads();
+    for (int c0 = c_begin, buf = 0; c0 < c_end; c0 += 32, buf ^= 1) {
+        const bool more = c0 + 32 < c_end;
+        if (more) gload(c0 + 32);                        // in flight across this tile's MFMAs
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const f32x4 bv = *reinterpret_cast<const f32x4*>(&ytile[buf][li * RS + g * 8 + half * 4]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[e], a[g][e], acc, 0, 0, 0);      // acc[r]: column i(r) of the tile, row li
+        }
+        if (active) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int col = c0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const float t = fminf(fmaxf(acc[r], -1.f), 1.f);               // np.clip, matching.py:51
+                keep.offer(2.f - 2.f * t, col, col < ny);
+            }
+        }
+        if (more) lstore(buf ^ 1);                       // last read one barrier ago
+        __syncthreads();
+    }
+    return active;
+}

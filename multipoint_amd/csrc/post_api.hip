@@ -209,24 +209,39 @@ int mp_sample_descriptors(mp_handle* h, const float* desc, int B, int Hc, int Wc
     return launch_status(h);
 }
 
+// what the four matchers share: tensors, the grid's pair bound (gridDim.y = P) and the descriptor width -- the MFMA row kernels
+// exist for three widths, the scalar route of match_extra.hip takes any up to 256
+static int match_check(mp_handle* h, const char* fn, const void* a, const void* b, const void* c, const void* d,
+                       int P, int K, int D, bool mfma_rows)
+{
+    if (!a || !b || !c || !d) return fail(h, MP_EINVAL, std::string(fn) + ": NULL tensor");
+    if (P <= 0 || P > 65535 || K <= 0) return fail(h, MP_EINVAL, std::string(fn) + ": need 0 < P <= 65535, K > 0");
+    if (mfma_rows ? (D != 64 && D != 128 && D != 256) : (D <= 0 || D > 256))
+        return fail(h, MP_EINVAL, std::string(fn) + (mfma_rows ? ": D must be 64, 128 or 256" : ": D must be in [1, 256]"));
+    return MP_OK;
+}
+
+// the MFMA matchers' scratch: packed (distance bits, index) keys, two per row and column share (mutual: one per direction,
+// nearest: the two smallest)
+static int match_workspace(mp_handle* h, int P, int K)
+{
+    return ensure(h, h->match_ws, (size_t)P * K * 8 * 2 * MATCH_SHARES);
+}
+
 int mp_match_mutual_nn(mp_handle* h, const float* descA, const int* countA, const float* descB,
                        const int* countB, long long pair_stride, int count_stride, int P, int K, int D,
                        float threshold, int* match_idx, float* match_dist, int* match_count, void* stream)
 {
     if (!h) return MP_EINVAL;
-    if (!descA || !descB || !countA || !countB || !match_idx || !match_dist || !match_count)
-        return fail(h, MP_EINVAL, "mp_match_mutual_nn: NULL tensor");
-    if (D != 64 && D != 128 && D != 256) return fail(h, MP_EINVAL, "mp_match_mutual_nn: D must be 64, 128 or 256");
-    if (P <= 0 || K <= 0) return fail(h, MP_EINVAL, "mp_match_mutual_nn: P and K must be positive");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    MP_HIP(hipSetDevice(h->device));
-    const size_t need = (size_t)P * K * 8 * 2 * MATCH_SHARES;      // packed (distance bits, index) arg-min arrays, one per column share
     int rc;
-    if ((rc = ensure(h, h->match_ws, need))) return rc;
+    if ((rc = match_check(h, "mp_match_mutual_nn", descA, descB, countA, countB, P, K, D, true))) return rc;
+    if (!match_idx || !match_dist || !match_count) return fail(h, MP_EINVAL, "mp_match_mutual_nn: NULL tensor");
+    MP_HIP(hipSetDevice(h->device));
+    if ((rc = match_workspace(h, P, K))) return rc;
     unsigned long long* rowbest = static_cast<unsigned long long*>(h->match_ws.p);
     unsigned long long* colbest = rowbest + (size_t)P * K * MATCH_SHARES;
     launch_match_impl(descA, countA, descB, countB, pair_stride, count_stride, P, K, D, threshold, rowbest,
-                      colbest, match_idx, match_dist, match_count, s);
+                      colbest, match_idx, match_dist, match_count, static_cast<hipStream_t>(stream));
     return launch_status(h);
 }
 
@@ -235,29 +250,16 @@ int mp_match_nearest(mp_handle* h, const float* descA, const int* countA, const 
                      float* match_dist, int* match_count, int* second_idx, float* second_dist, void* stream)
 {
     if (!h) return MP_EINVAL;
-    if (!descA || !descB || !countA || !countB || !match_idx || !match_dist || !match_count)
-        return fail(h, MP_EINVAL, "mp_match_nearest: NULL tensor");
-    if (D != 64 && D != 128 && D != 256) return fail(h, MP_EINVAL, "mp_match_nearest: D must be 64, 128 or 256");
-    if (P <= 0 || P > 65535 || K <= 0) return fail(h, MP_EINVAL, "mp_match_nearest: need 0 < P <= 65535, K > 0");
-    if (ratio != ratio) return fail(h, MP_EINVAL, "mp_match_nearest: ratio is NaN");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    MP_HIP(hipSetDevice(h->device));
-    const size_t need = (size_t)P * K * 8 * 2 * MATCH_SHARES;      // the two smallest packed keys per query row, one array per column share
     int rc;
-    if ((rc = ensure(h, h->match_ws, need))) return rc;
+    if ((rc = match_check(h, "mp_match_nearest", descA, descB, countA, countB, P, K, D, true))) return rc;
+    if (!match_idx || !match_dist || !match_count) return fail(h, MP_EINVAL, "mp_match_nearest: NULL tensor");
+    if (ratio != ratio) return fail(h, MP_EINVAL, "mp_match_nearest: ratio is NaN");
+    MP_HIP(hipSetDevice(h->device));
+    if ((rc = match_workspace(h, P, K))) return rc;
     launch_match_nearest(descA, countA, descB, countB, pair_stride, count_stride, P, K, D, ratio,
                          static_cast<unsigned long long*>(h->match_ws.p), match_idx, match_dist, match_count, second_idx,
-                         second_dist, s);
+                         second_dist, static_cast<hipStream_t>(stream));
     return launch_status(h);
-}
-
-static int match_extra_check(mp_handle* h, const char* fn, const void* a, const void* b, const void* c, const void* d,
-                             int P, int K, int D)
-{
-    if (!a || !b || !c || !d) return fail(h, MP_EINVAL, std::string(fn) + ": NULL tensor");
-    if (P <= 0 || P > 65535 || K <= 0) return fail(h, MP_EINVAL, std::string(fn) + ": need 0 < P <= 65535, K > 0");
-    if (D <= 0 || D > 256) return fail(h, MP_EINVAL, std::string(fn) + ": D must be in [1, 256]");
-    return MP_OK;
 }
 
 int mp_match_knn2(mp_handle* h, const float* descA, const int* countA, const float* descB, const int* countB,
@@ -266,7 +268,7 @@ int mp_match_knn2(mp_handle* h, const float* descA, const int* countA, const flo
 {
     if (!h) return MP_EINVAL;
     int rc;
-    if ((rc = match_extra_check(h, "mp_match_knn2", descA, descB, countA, countB, P, K, D))) return rc;
+    if ((rc = match_check(h, "mp_match_knn2", descA, descB, countA, countB, P, K, D, false))) return rc;
     if (!nn_idx || !nn_dist) return fail(h, MP_EINVAL, "mp_match_knn2: NULL output");
     MP_HIP(hipSetDevice(h->device));
     launch_match_knn2(descA, countA, descB, countB, pair_stride, count_stride, P, K, D, nn_idx, nn_dist,
@@ -280,7 +282,7 @@ int mp_match_threshold(mp_handle* h, const float* descA, const int* countA, cons
 {
     if (!h) return MP_EINVAL;
     int rc;
-    if ((rc = match_extra_check(h, "mp_match_threshold", descA, descB, countA, countB, P, K, D))) return rc;
+    if ((rc = match_check(h, "mp_match_threshold", descA, descB, countA, countB, P, K, D, false))) return rc;
     if (!list_ij || !list_dist || !list_count) return fail(h, MP_EINVAL, "mp_match_threshold: NULL output");
     if (capacity <= 0) return fail(h, MP_EINVAL, "mp_match_threshold: capacity must be positive");
     if (!(threshold >= 0.f)) return fail(h, MP_EINVAL, "mp_match_threshold: threshold must be non-negative");

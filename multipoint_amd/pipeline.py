@@ -4,7 +4,6 @@ GPU.  The reference runs two forwards (optical, thermal), two box_nms calls and 
 samples with three cv2 matcher calls each; here both images of all pairs go through ONE forward as an
 interleaved batch (image 2p = optical, 2p+1 = thermal), keypoints stay on the device as fixed-capacity
 lists, and all pairs are matched by one launch.  Nothing synchronises until results are read."""
-import ctypes
 import os
 
 import numpy as np
@@ -12,6 +11,7 @@ import torch
 
 from . import _lib
 from .utils import utils as U
+from .utils.matching import match_pairs, nearest_pairs
 
 
 class PairResults:
@@ -216,23 +216,12 @@ class PairPipeline:
             mark()                  # keypoint lists done (stage timing)
         K = kp.shape[1]
         desc = U.interpolate_descriptors_batched(kp, cnt, out['desc'], H, W)        # [B,K,D]
-        D = desc.shape[2]
-        P = B // 2
-        midx = torch.empty((P, K), dtype=torch.int32, device=dev)
-        mdist = torch.empty((P, K), dtype=torch.float32, device=dev)
-        mcnt = torch.empty((P,), dtype=torch.int32, device=dev)
-        h = _lib.get_handle(dev)
-        with torch.cuda.device(dev):
-            if self.match_mode == 'mutual':
-                h.check(h.lib.mp_match_mutual_nn(
-                    h.ptr, _lib.ptr(desc), _lib.ptr(cnt), ctypes.c_void_p(desc.data_ptr() + K * D * 4),
-                    ctypes.c_void_p(cnt.data_ptr() + 4), 2 * K * D, 2, P, K, D, float(self.match_threshold),
-                    _lib.ptr(midx), _lib.ptr(mdist), _lib.ptr(mcnt), _lib.stream_ptr(dev)))
-            else:
-                h.check(h.lib.mp_match_nearest(
-                    h.ptr, _lib.ptr(desc), _lib.ptr(cnt), ctypes.c_void_p(desc.data_ptr() + K * D * 4),
-                    ctypes.c_void_p(cnt.data_ptr() + 4), 2 * K * D, 2, P, K, D, self.match_ratio,
-                    _lib.ptr(midx), _lib.ptr(mdist), _lib.ptr(mcnt), None, None, _lib.stream_ptr(dev)))
+        # the interleaved list read in place: slot 2p against slot 2p + 1
+        lay = dict(pair_stride=2 * K * desc.shape[2], count_stride=2)
+        if self.match_mode == 'mutual':
+            midx, mdist, mcnt = match_pairs(desc, cnt, desc[1:], cnt[1:], self.match_threshold, **lay)
+        else:
+            midx, mdist, mcnt = nearest_pairs(desc, cnt, desc[1:], cnt[1:], self.match_ratio, **lay)
         return PairResults(kp, sc, cnt, desc, midx, mdist, mcnt, H, W, self.match_mode)
 
     def __call__(self, optical, thermal, mask_optical=None, mask_thermal=None):

@@ -44,22 +44,32 @@ def _pair_layout(descA, countA, descB, countB, pair_stride, count_stride):
     return descA, countA, descB, countB, P, K, D, int(pair_stride), count_stride
 
 
+def _batched_match(entry, layout, mode, second=None):
+    """One call of a batched MFMA matcher on the current stream: `entry` (mp_match_mutual_nn / mp_match_nearest) on the
+    pairs `layout` (_pair_layout) addresses, with its mode argument (threshold / ratio).  `second`: None for the entry
+    without second-neighbour outputs, else whether to allocate them.
+    Returns [match_idx [P,K] int32, match_dist [P,K] f32, match_count [P] int32] (+ [second_idx, second_dist] or Nones)."""
+    descA, countA, descB, countB, P, K, D, pair_stride, count_stride = layout
+    dev = descA.device
+    out = [torch.empty((P, K), dtype=torch.int32, device=dev), torch.empty((P, K), dtype=torch.float32, device=dev),
+           torch.empty((P,), dtype=torch.int32, device=dev)]
+    if second is not None:
+        out += [torch.empty((P, K), dtype=torch.int32, device=dev) if second else None,
+                torch.empty((P, K), dtype=torch.float32, device=dev) if second else None]
+    h = _lib.get_handle(dev)
+    with torch.cuda.device(dev):
+        h.check(getattr(h.lib, entry)(h.ptr, _lib.ptr(descA), _lib.ptr(countA), _lib.ptr(descB), _lib.ptr(countB),
+                                      pair_stride, count_stride, P, K, D, mode, *[_lib.ptr(o) for o in out],
+                                      _lib.stream_ptr(dev)))
+    return out
+
+
 def match_pairs(descA, countA, descB, countB, threshold=-1.0, pair_stride=None, count_stride=1):
     """Mutual NN for P independent pairs on the GPU.
     descA/descB [P,K,D] fp32 unit rows, countA/countB [P] int32 (or strided views, see _pair_layout).
     Returns (match_idx [P,K] int32 (-1 = none), match_dist [P,K] f32, match_count [P] int32)."""
-    dev = descA.device
-    descA, countA, descB, countB, P, K, D, pair_stride, count_stride = _pair_layout(descA, countA, descB, countB,
-                                                                                    pair_stride, count_stride)
-    midx = torch.empty((P, K), dtype=torch.int32, device=dev)
-    mdist = torch.empty((P, K), dtype=torch.float32, device=dev)
-    mcnt = torch.empty((P,), dtype=torch.int32, device=dev)
-    h = _lib.get_handle(dev)
-    with torch.cuda.device(dev):
-        h.check(h.lib.mp_match_mutual_nn(h.ptr, _lib.ptr(descA), _lib.ptr(countA), _lib.ptr(descB), _lib.ptr(countB),
-                                         pair_stride, count_stride, P, K, D, float(threshold), _lib.ptr(midx),
-                                         _lib.ptr(mdist), _lib.ptr(mcnt), _lib.stream_ptr(dev)))
-    return midx, mdist, mcnt
+    layout = _pair_layout(descA, countA, descB, countB, pair_stride, count_stride)
+    return tuple(_batched_match('mp_match_mutual_nn', layout, float(threshold)))
 
 
 def nearest_pairs(descA, countA, descB, countB, ratio=None, return_second=False, pair_stride=None, count_stride=1):
@@ -68,35 +78,15 @@ def nearest_pairs(descA, countA, descB, countB, ratio=None, return_second=False,
     `ratio=r`: kept iff distance < r * second distance (knnMatch(.., 2) + Lowe's ratio test; get_matches uses 0.9).
     Returns (match_idx [P,K] int32 (-1 = none), match_dist [P,K] f32, match_count [P] int32), with `return_second`
     followed by (second_idx [P,K] int32, second_dist [P,K] f32): the second-nearest train row of every query."""
-    dev = descA.device
-    descA, countA, descB, countB, P, K, D, pair_stride, count_stride = _pair_layout(descA, countA, descB, countB,
-                                                                                    pair_stride, count_stride)
-    midx = torch.empty((P, K), dtype=torch.int32, device=dev)
-    mdist = torch.empty((P, K), dtype=torch.float32, device=dev)
-    mcnt = torch.empty((P,), dtype=torch.int32, device=dev)
-    sidx = torch.empty((P, K), dtype=torch.int32, device=dev) if return_second else None
-    sdist = torch.empty((P, K), dtype=torch.float32, device=dev) if return_second else None
-    h = _lib.get_handle(dev)
-    with torch.cuda.device(dev):
-        h.check(h.lib.mp_match_nearest(h.ptr, _lib.ptr(descA), _lib.ptr(countA), _lib.ptr(descB), _lib.ptr(countB),
-                                       pair_stride, count_stride, P, K, D, 0.0 if ratio is None else float(ratio),
-                                       _lib.ptr(midx), _lib.ptr(mdist), _lib.ptr(mcnt), _lib.ptr(sidx), _lib.ptr(sdist),
-                                       _lib.stream_ptr(dev)))
-    return (midx, mdist, mcnt, sidx, sdist) if return_second else (midx, mdist, mcnt)
+    layout = _pair_layout(descA, countA, descB, countB, pair_stride, count_stride)
+    out = _batched_match('mp_match_nearest', layout, 0.0 if ratio is None else float(ratio), bool(return_second))
+    return tuple(out if return_second else out[:3])
 
 
 def _mutual_nn(desc_1, desc_2, threshold):
-    d1 = torch.as_tensor(desc_1); d2 = torch.as_tensor(desc_2)
-    if d1.shape[0] == 0 or d2.shape[0] == 0:              # matching.py:46-47
+    if len(desc_1) == 0 or len(desc_2) == 0:              # matching.py:46-47
         return []
-    if d1.shape[1] != d2.shape[1]:
-        raise AssertionError('descriptor sizes differ')    # matching.py:45
-    dev = d1.device if d1.device.type == 'cuda' else _lib.require_cuda(None)
-    N, M, D = d1.shape[0], d2.shape[0], d1.shape[1]
-    K = max(N, M)
-    A = torch.zeros((1, K, D), dtype=torch.float32, device=dev); A[0, :N] = d1.to(dev, torch.float32)
-    Bm = torch.zeros((1, K, D), dtype=torch.float32, device=dev); Bm[0, :M] = d2.to(dev, torch.float32)
-    nA = torch.tensor([N], dtype=torch.int32, device=dev); nB = torch.tensor([M], dtype=torch.int32, device=dev)
+    A, nA, Bm, nB, N, M, K, D, dev = _pad_pair(desc_1, desc_2)         # (raises for differing sizes, matching.py:45)
     midx, mdist, _ = match_pairs(A, nA, Bm, nB, threshold)
     midx = midx[0, :N].cpu().numpy(); mdist = mdist[0, :N].cpu().numpy()
     q = np.nonzero(midx >= 0)[0]

@@ -175,6 +175,50 @@ def test_against_per_pair_get_matches(cases, D):
             assert have == want, (D, p, knn)
 
 
+@pytest.mark.parametrize('layout', ['separate', 'interleaved'])
+@pytest.mark.parametrize('D', [64, 128, 256])
+def test_mutual_is_two_nearest_passes(cases, D, layout):
+    """mp_match_mutual_nn against two one-way passes of mp_match_nearest: query i is matched to its nearest j iff i is the
+    nearest of j [and the distance is below the threshold].  All three calls walk the same tiles, form the same products in
+    the same order and build the same keys, so indices, distance bit patterns and counts are EQUAL: no tolerance, no
+    ambiguous queries."""
+    from multipoint_amd.utils import match_pairs, nearest_pairs
+    prs, _ = cases[D]
+    a, ca, b, cb, kw = _layouts(prs, D)[layout]
+    ab = [x.cpu().numpy() for x in nearest_pairs(a, ca, b, cb, ratio=None, **kw)]
+    ba = [x.cpu().numpy() for x in nearest_pairs(b, cb, a, ca, ratio=None, **kw)]     # (interleaved: the views the other way round)
+    for thr in (None, 0.9):
+        midx, mdist, mcnt = (x.cpu().numpy() for x in match_pairs(a, ca, b, cb, threshold=-1.0 if thr is None else thr, **kw))
+        for p, (A, B) in enumerate(prs):
+            N = len(A)
+            j = ab[0][p, :N]
+            back = np.full(N, -2, np.int64)
+            back[j >= 0] = ba[0][p, j[j >= 0]]
+            matched = (j >= 0) & (back == np.arange(N))
+            if thr:
+                matched &= ab[1][p, :N] < np.float32(thr)
+            want_idx = np.full(K, -1, np.int32); want_dist = np.zeros(K, np.int32)
+            want_idx[:N] = np.where(matched, j, -1)
+            want_dist[:N] = np.where(matched, ab[1][p, :N].view(np.int32), 0)
+            print('D %d %s thr %s pair %d (%d x %d): %d mutual' % (D, layout, thr, p, N, len(B), int(matched.sum())))
+            assert np.array_equal(midx[p], want_idx)
+            assert np.array_equal(mdist[p].view(np.int32), want_dist)
+            assert mcnt[p] == int(matched.sum())
+
+
+def test_mutual_rejects_too_many_pairs():
+    """A pair is a row of the launch grid (gridDim.y <= 65535): one pair more is refused by the entry's validation, with the
+    bound in the message, instead of failing at the launch."""
+    from multipoint_amd.utils import match_pairs
+    P = 65536
+    desc = torch.zeros((P, 1, 64), dtype=torch.float32, device=DEV)
+    cnt = torch.zeros((P,), dtype=torch.int32, device=DEV)
+    with pytest.raises(ValueError, match='P <= 65535'):              # (MP_EINVAL: raised before anything is launched)
+        match_pairs(desc, cnt, desc.clone(), cnt.clone())
+    torch.cuda.synchronize()                                         # no launch error is pending either
+    assert int(match_pairs(desc[:2], cnt[:2], desc[:2], cnt[:2])[2].sum()) == 0
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # pipeline and metric driver
 # ----------------------------------------------------------------------------------------------------------------------
