@@ -228,7 +228,8 @@ int mp_repeatability(mp_handle* h, const int* kp_yx, const int* kp_count, const 
  * (predict_align_image_pair.py:205-216, multipoint/utils/evaluation.py:330-349) for P pairs (slot 2p optical, 2p+1
  * thermal).  Not a bit-level restatement of OpenCV (absent third-party code with its own RNG): max_iters hypotheses
  * from 4 random matches each (counter-based RNG on `seed`: reproducible), forward reprojection error test, most
- * inliers wins, normalised-DLT refit over the winner's inliers.
+ * inliers wins, normalised-DLT refit over the winner's inliers.  OpenCV's closing Levenberg-Marquardt polish is a call of
+ * its own: mp_refine_homography.
  *   homography   device double [P][9], row-major, maps optical (x, y, 1) to thermal; all zeros when < 4 matches or
  *                no hypothesis found 4 inliers (the reference's `H_est is None`)
  *   inlier_mask  uint8 [P][K] per OPTICAL keypoint (1 = its match is an inlier); n_inliers int32 [P] */
@@ -269,6 +270,43 @@ int mp_match_nearest(mp_handle* h, const float* descA, const int* countA, const 
                      long long pair_stride, int count_stride, int P, int K, int D, double ratio,
                      int* match_idx, float* match_dist, int* match_count,
                      int* second_idx /* [P][K] or NULL */, float* second_dist /* [P][K] or NULL */, void* stream);
+
+/* guided matching: mutual nearest neighbours INSIDE a geometric gate, for re-matching under a first homography estimate
+ * (mp_find_homography).  Descriptors, counts, outputs and limits as for mp_match_mutual_nn (unit rows, the same fp32 MFMA
+ * distance tiles, D 64 / 128 / 256, 0 < P <= 65535); the list is again one-to-one, so mp_find_homography, mp_pair_metrics and
+ * the per-pair records take it unchanged.
+ *   kpA_yx / kpB_yx  int32 (y, x) of the optical / thermal rows, addressed like the descriptors: row r of pair p at
+ *                kp + (p * (pair_stride / D) + r) * 2 -- for the interleaved lists of a pair batch kp_yx and kp_yx + 2 K
+ *                (pair_stride must be a multiple of D)
+ *   homography   device double [P][9], row-major, optical (x, y, 1) -> thermal, as mp_find_homography writes it
+ *   wa_i       = H_p (x_i, y_i, 1) in double, divided by its third component and rounded once to fp32; optical row i has no
+ *                candidates if that component is 0 or the result is not finite -- so a pair whose H_p is all zeros
+ *                (mp_find_homography's "no estimate") gets no matches
+ *   gate(i, j) = (wa_i.x - x_j)^2 + (wa_i.y - y_j)^2 <= radius^2 in fp32 (radius finite and positive)
+ *   i is matched to j iff j minimises d(i, .) over {j : gate(i, j)} and i minimises d(., j) over {i : gate(i, j)} (the
+ *                lower index wins exact ties) and, with threshold >= 0, d < threshold
+ * Both directions decide the gate from the same fp32 bits, so the mutual test is exact; results are bit-identical from
+ * run to run. */
+int mp_match_guided(mp_handle* h, const float* descA, const int* countA, const float* descB, const int* countB,
+                    long long pair_stride, int count_stride, int P, int K, int D, const int* kpA_yx, const int* kpB_yx,
+                    const double* homography /* [P][9] */, float radius, float threshold, int* match_idx, float* match_dist,
+                    int* match_count, void* stream);
+
+/* the last step of cv2.findHomography(..., cv2.RANSAC, thr), which mp_find_homography leaves out: a Levenberg-Marquardt
+ * polish of the estimate over its inliers (OpenCV 4.2: HomographyRefineCallback + createLMSolver(cb, 10)).  fp64; 8
+ * parameters (h22 = 1), residuals (x' - u, y' - v), lambda_0 = 1e-3, at most `iters` iterations (OpenCV: 10) of at most 8
+ * trial steps (J^T J + lambda diag(J^T J))^-1 (-J^T r); a step is accepted iff the cost falls (then lambda <- max(0.1
+ * lambda, 1e-12), else lambda <- 10 lambda; a singular system is a rejected trial), an iteration without an accepted step
+ * ends the polish.  Lists as for mp_find_homography (slot 2p optical, 2p+1 thermal; 0 < K <= 3200); match_idx may come
+ * from any of the matchers.
+ *   homography   device double [P][9]: in the estimate, out the polished matrix divided by h22.  All zeros out when the
+ *                input is all zeros (or has h22 = 0) or fewer than 4 matches are inliers
+ *   inlier_mask  uint8 [P][K] per optical keypoint, n_inliers [P]: the matches whose forward reprojection error under the
+ *                INPUT estimate is <= reproj_threshold -- the set the polish runs on, recomputed here
+ *   cost         double [P][2] or NULL: sum of squared residuals over that set before / after (after <= before) */
+int mp_refine_homography(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K,
+                         double reproj_threshold, int iters, double* homography, unsigned char* inlier_mask, int* n_inliers,
+                         double* cost /* [P][2] or NULL */, void* stream);
 
 /* ---- single-image detector metrics: multipoint/utils/evaluation.py:10-97 (predict_keypoints.py:88-104) ----
  * mp_detector_metrics replaces compute_tp_fp_dist (evaluation.py:56-97) for B heat maps at once:

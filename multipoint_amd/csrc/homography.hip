@@ -7,6 +7,7 @@
 //   solve (8x8 Gaussian elimination, fp64), score = number of matches with forward reprojection error <= threshold,
 //   best = most inliers (lowest hypothesis index on ties), final model = normalised DLT over the best inlier set.
 // One thread per hypothesis (the matches of the pair sit in LDS); the winner is picked with a 64-bit atomicMax.
+// OpenCV's last step, the Levenberg-Marquardt polish of the refitted model, is a launch of its own (refine_kernel).
 #include "mp_common.h"
 #include "mp_device.h"
 
@@ -268,6 +269,156 @@ __global__ __launch_bounds__(256) void refit_kernel(const int* __restrict__ kp_y
     }
 }
 
+// ---- the Levenberg-Marquardt polish (mp_refine_homography) ----
+// What cv2.findHomography does after its refit (HomographyRefineCallback + createLMSolver(cb, 10)): minimise the forward
+// reprojection residuals (x' - u, y' - v) over the inliers in the 8 parameters h0..h7 (h8 = 1).  lambda starts at 1e-3; an
+// iteration tries up to 8 steps (J^T J + lambda diag(J^T J))^-1 (-J^T r), accepts the first one that lowers the cost
+// (lambda <- max(0.1 lambda, 1e-12)) and multiplies lambda by 10 after every other one; an iteration without an accepted
+// step ends the polish.  One workgroup per pair, fp64 throughout.
+
+constexpr int LM_SUMS = 45;       // J^T J upper triangle (36) | J^T r (8) | cost
+
+// solves the symmetric 8x8 system (A + lam diag(A)) x = -g, A given by its upper triangle in row order; false: singular
+__device__ bool lm_step(const double* sums, double lam, double* step)
+{
+    double a[8][9];
+    for (int r = 0, k = 0; r < 8; ++r)
+        for (int c = r; c < 8; ++c, ++k) { a[r][c] = sums[k]; a[c][r] = sums[k]; }
+    for (int r = 0; r < 8; ++r) { a[r][r] += lam * a[r][r]; a[r][8] = -sums[36 + r]; }
+    for (int c = 0; c < 8; ++c) {
+        int piv = c;
+        double best = fabs(a[c][c]);
+        for (int r = c + 1; r < 8; ++r)
+            if (fabs(a[r][c]) > best) { best = fabs(a[r][c]); piv = r; }
+        if (!(best > 0.0) || !isfinite(best)) return false;
+        if (piv != c)
+            for (int k = c; k < 9; ++k) { const double tmp = a[c][k]; a[c][k] = a[piv][k]; a[piv][k] = tmp; }
+        const double inv = 1.0 / a[c][c];
+        for (int r = c + 1; r < 8; ++r) {
+            const double f = a[r][c] * inv;
+            for (int k = c; k < 9; ++k) a[r][k] -= f * a[c][k];
+        }
+    }
+    for (int c = 7; c >= 0; --c) {
+        double s = a[c][8];
+        for (int k = c + 1; k < 8; ++k) s -= a[c][k] * step[k];
+        step[c] = s / a[c][c];
+    }
+    return true;
+}
+
+// out[0..44] = the sums of J^T J, J^T r and r.r at parameters h over the inliers among pts[0..n) (a NaN x marks an
+// outlier).  Fixed order: a thread adds its inliers i = tid, tid + 256, ..., the lanes of a wave are added by the xor
+// butterfly, the four waves' sums in wave order through LDS -- the same bits on every run.  All 256 threads call it.
+__device__ void lm_sums(const float* pts, int n, const double* h, double* wave_part /* [4][LM_SUMS] LDS */, double* out)
+{
+    const int tid = threadIdx.x;
+    double acc[LM_SUMS];
+#pragma unroll
+    for (int k = 0; k < LM_SUMS; ++k) acc[k] = 0.0;
+    for (int i = tid; i < n; i += 256) {
+        if (pts[i * 4] != pts[i * 4]) continue;
+        const double X = pts[i * 4], Y = pts[i * 4 + 1];
+        double ww = h[6] * X + h[7] * Y + 1.0;
+        ww = fabs(ww) > 2.220446049250313e-16 ? 1.0 / ww : 0.0;
+        const double xi = (h[0] * X + h[1] * Y + h[2]) * ww, yi = (h[3] * X + h[4] * Y + h[5]) * ww;
+        const double rx = xi - pts[i * 4 + 2], ry = yi - pts[i * 4 + 3];
+        const double jx[8] = {X * ww, Y * ww, ww, 0.0, 0.0, 0.0, -X * ww * xi, -Y * ww * xi};
+        const double jy[8] = {0.0, 0.0, 0.0, X * ww, Y * ww, ww, -X * ww * yi, -Y * ww * yi};
+#pragma unroll
+        for (int a = 0, k = 0; a < 8; ++a) {
+#pragma unroll
+            for (int c = a; c < 8; ++c, ++k) acc[k] += jx[a] * jx[c] + jy[a] * jy[c];
+        }
+#pragma unroll
+        for (int a = 0; a < 8; ++a) acc[36 + a] += jx[a] * rx + jy[a] * ry;
+        acc[44] += rx * rx + ry * ry;
+    }
+#pragma unroll
+    for (int k = 0; k < LM_SUMS; ++k) {
+        double v = acc[k];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if ((tid & 63) == 0) wave_part[(tid >> 6) * LM_SUMS + k] = v;
+    }
+    __syncthreads();
+    if (tid < LM_SUMS)
+        out[tid] = ((wave_part[tid] + wave_part[LM_SUMS + tid]) + wave_part[2 * LM_SUMS + tid]) + wave_part[3 * LM_SUMS + tid];
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void refine_kernel(const int* __restrict__ kp_yx, const int* __restrict__ kp_count,
+                                                     const int* __restrict__ match_idx, int K, double thr, int iters,
+                                                     double* __restrict__ H_io, unsigned char* __restrict__ mask,
+                                                     int* __restrict__ n_inliers, double* __restrict__ cost_out)
+{
+    extern __shared__ float pts[];            // [K][4] floats, then [K] ints (query index of each match)
+    int* qidx = reinterpret_cast<int*>(pts + (size_t)K * 4);
+    __shared__ double wave_part[4 * LM_SUMS];
+    __shared__ double cur[LM_SUMS], cand[LM_SUMS];     // the sums at the accepted parameters / at the step being tried
+    __shared__ double hcur[8], htry[8];
+    __shared__ int count_s[4], state;                  // state: 0 = the trial's system was singular, 1 = evaluate htry
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int n = gather(kp_yx, kp_count, match_idx, p, K, pts, qidx);
+    double h[9];
+    for (int k = 0; k < 9; ++k) h[k] = H_io[p * 9 + k];
+    // the inliers of the INPUT estimate (an all-zero matrix has none: inlier() refuses w = 0)
+    const double thr2 = thr * thr;
+    int mine = 0;
+    for (int i = tid; i < n; i += 256) {
+        const bool in = inlier(h, pts[i * 4], pts[i * 4 + 1], pts[i * 4 + 2], pts[i * 4 + 3], thr2);
+        mask[(size_t)p * K + qidx[i]] = in ? 1 : 0;
+        if (in) ++mine; else pts[i * 4] = __int_as_float(0x7fc00000);          // NaN marks an outlier for lm_sums
+    }
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
+    if ((tid & 63) == 0) count_s[tid >> 6] = mine;
+    __syncthreads();
+    const int m = count_s[0] + count_s[1] + count_s[2] + count_s[3];
+    if (m < 4 || !(fabs(h[8]) > 0.0) || !isfinite(h[8])) {
+        if (tid == 0) {
+            n_inliers[p] = m;
+            for (int k = 0; k < 9; ++k) H_io[p * 9 + k] = 0.0;
+            if (cost_out) { cost_out[p * 2] = 0.0; cost_out[p * 2 + 1] = 0.0; }
+        }
+        return;
+    }
+    if (tid < 8) hcur[tid] = h[tid] / h[8];
+    __syncthreads();
+    lm_sums(pts, n, hcur, wave_part, cur);
+    const double cost0 = cur[44];
+    double lam = 1e-3;                                  // (every thread follows thread 0's decisions through `state` and the sums)
+    for (int it = 0; it < iters; ++it) {
+        bool accepted = false;
+        for (int trial = 0; trial < 8 && !accepted; ++trial) {
+            if (tid == 0) {
+                double step[8];
+                const bool ok = lm_step(cur, lam, step);
+                for (int k = 0; k < 8; ++k) htry[k] = hcur[k] + step[k];
+                state = ok ? 1 : 0;
+            }
+            __syncthreads();
+            const bool ok = state != 0;
+            if (ok) lm_sums(pts, n, htry, wave_part, cand);
+            accepted = ok && cand[44] < cur[44];         // (a NaN cost is not an improvement)
+            __syncthreads();
+            if (accepted) {
+                if (tid < LM_SUMS) cur[tid] = cand[tid];
+                if (tid < 8) hcur[tid] = htry[tid];
+                lam = fmax(lam * 0.1, 1e-12);
+            } else {
+                lam *= 10.0;
+            }
+            __syncthreads();
+        }
+        if (!accepted) break;
+    }
+    if (tid == 0) {
+        n_inliers[p] = m;
+        for (int k = 0; k < 8; ++k) H_io[p * 9 + k] = hcur[k];
+        H_io[p * 9 + 8] = 1.0;
+        if (cost_out) { cost_out[p * 2] = cost0; cost_out[p * 2 + 1] = cur[44]; }
+    }
+}
+
 }  // namespace
 
 void launch_ransac_homography(const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K, int T, double thr,
@@ -278,4 +429,13 @@ void launch_ransac_homography(const int* kp_yx, const int* kp_count, const int* 
     hipLaunchKernelGGL(ransac_kernel, dim3((T + 255) / 256, P), dim3(256), lds1, s, kp_yx, kp_count, match_idx, K, T, thr, seed, best);
     hipLaunchKernelGGL(refit_kernel, dim3(P), dim3(256), lds2, s, kp_yx, kp_count, match_idx, K, thr, seed, best, H_out, mask,
                        n_inliers);
+}
+
+// mask must be zeroed by the caller (only the matched optical keypoints are written)
+void launch_refine_homography(const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K, double thr, int iters,
+                              double* H_io, unsigned char* mask, int* n_inliers, double* cost, hipStream_t s)
+{
+    const size_t lds = (size_t)K * 4 * sizeof(float) + (size_t)K * sizeof(int);
+    hipLaunchKernelGGL(refine_kernel, dim3(P), dim3(256), lds, s, kp_yx, kp_count, match_idx, K, thr, iters, H_io, mask,
+                       n_inliers, cost);
 }

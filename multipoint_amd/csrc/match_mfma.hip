@@ -16,8 +16,6 @@
 //     closer: exact distance ties go to the lower train index first).
 #include "mp_match.h"
 
-#include <type_traits>
-
 namespace {
 
 // best[x] = min over y of (dist(x,y) bits << 32 | y), X rows against the share's Y rows.
@@ -82,47 +80,6 @@ __global__ __launch_bounds__(256) void near2_rows_kernel(const float* __restrict
     }
 }
 
-// the N smallest keys (k2 is untouched for N = 1) of row `at` over the column shares' arrays, which lie [share][pair][K][N]
-template <int N>
-__device__ __forceinline__ void merge_shares(const unsigned long long* __restrict__ best, long long at, int K, int nsplit,
-                                             unsigned long long& k1, unsigned long long& k2)
-{
-    const long long share_stride = (long long)gridDim.y * K * N;
-    at *= N;
-    k1 = best[at];
-    if constexpr (N == 2) k2 = best[at + 1];
-    for (int sh = 1; sh < nsplit; ++sh) {
-        if constexpr (N == 1) { const unsigned long long o = best[at + sh * share_stride]; k1 = o < k1 ? o : k1; }
-        else merge2(k1, k2, best[at + sh * share_stride], best[at + sh * share_stride + 1]);
-    }
-}
-
-// One best-or-no match per query row.  j < 0: none; j2 / d2: the second-nearest train row, for the entry that reports it
-struct RowMatch { int j = -1, j2 = -1; float d = 0.f, d2 = 0.f; };
-
-// The epilogue kernels' frame, one thread per query row i of pair p: match(p, i) decides the row, which is written
-// (second_* may be NULL), and the workgroup adds its matches to the pair's count.
-template <class Match>
-__device__ __forceinline__ void write_matches(int K, int* __restrict__ match_idx, float* __restrict__ match_dist,
-                                              int* __restrict__ match_count, int* __restrict__ second_idx,
-                                              float* __restrict__ second_dist, Match match)
-{
-    const int p = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    int hit = 0;
-    if (i < K) {
-        const RowMatch m = match(p, i);
-        const long long o = (long long)p * K + i;
-        match_idx[o] = m.j;
-        match_dist[o] = m.j >= 0 ? m.d : 0.f;
-        if (second_idx) second_idx[o] = m.j2;
-        if (second_dist) second_dist[o] = m.j2 >= 0 ? m.d2 : 0.f;
-        hit = m.j >= 0;
-    }
-    const int c = __syncthreads_count(hit);
-    if (threadIdx.x == 0 && c) atomicAdd(&match_count[p], c);
-}
-
 __global__ __launch_bounds__(256) void mutual_kernel(const unsigned long long* __restrict__ bestA,
                                                     const unsigned long long* __restrict__ bestB,
                                                     const int* __restrict__ nA, const int* __restrict__ nB,
@@ -171,15 +128,6 @@ __global__ __launch_bounds__(256) void nearest_kernel(const unsigned long long* 
         }
         return m;
     });
-}
-
-// the row kernels exist for the descriptor widths the C entries admit: launch(integral_constant<int, D>)
-template <class Launch>
-void for_width(int D, Launch launch)
-{
-    if (D == 64) launch(std::integral_constant<int, 64>{});
-    else if (D == 128) launch(std::integral_constant<int, 128>{});
-    else launch(std::integral_constant<int, 256>{});
 }
 
 }  // namespace

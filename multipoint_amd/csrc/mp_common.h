@@ -354,6 +354,14 @@ void launch_match_nearest(const float* dA, const int* nA, const float* dB, const
                           int count_stride, int P, int K, int D, double ratio, unsigned long long* best2, int* match_idx,
                           float* match_dist, int* match_count, int* second_idx, float* second_dist, hipStream_t s);
 
+// mutual nearest neighbours inside a geometric gate (match_guided.hip): a candidate pair (i, j) needs hom[p] to map optical
+// keypoint i within `radius` of thermal keypoint j.  kp*_yx rows lie like the descriptor rows (pair p at + p * (pair_stride / D)
+// rows); pos: [2][P][K][2] float scratch; rowbest/colbest as for launch_match_impl
+void launch_match_guided(const float* dA, const int* nA, const float* dB, const int* nB, long long pair_stride,
+                         int count_stride, int P, int K, int D, const int* kpA_yx, const int* kpB_yx, const double* hom,
+                         float radius, float thr, float* pos, unsigned long long* rowbest, unsigned long long* colbest,
+                         int* match_idx, float* match_dist, int* match_count, hipStream_t s);
+
 // remaining get_matches modes (match_extra.hip): two nearest train rows per query (BFMatcher knnMatch / match without
 // crossCheck), idx/dist [P][K][2]; all pairs closer than thr (ThresholdMatcher), list_count [P] pre-set to 0
 void launch_match_knn2(const float* dA, const int* nA, const float* dB, const int* nB, long long pair_stride,
@@ -377,6 +385,11 @@ void launch_repeatability(const int* kp_yx, const int* kp_count, const double* h
 void launch_ransac_homography(const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K, int T, double thr,
                               unsigned long long seed, unsigned long long* best, double* H_out, unsigned char* mask,
                               int* n_inliers, hipStream_t s);
+
+// Levenberg-Marquardt polish of hom [P][9] (in: estimate, out: polished, h22 = 1) over the matches within thr of the estimate;
+// mask [P][K] zeroed by the caller, cost [P][2] (before / after) or NULL
+void launch_refine_homography(const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K, double thr, int iters,
+                              double* H_io, unsigned char* mask, int* n_inliers, double* cost, hipStream_t s);
 
 // single-image detector metrics (detector_metrics.hip; evaluation.py:56-97): best [B][H][W] scratch, rec_count / n_gt [B]
 // (all three pre-set to 0), records [B][H*W]

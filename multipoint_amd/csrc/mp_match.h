@@ -11,6 +11,8 @@
 #pragma once
 #include "mp_common.h"
 
+#include <type_traits>
+
 constexpr unsigned long long NO_KEY = ~0ull;             // (distance bits 0xffffffff are a NaN: never a real key)
 
 // (distance bits << 32 | column): ordered by distance, equal distances by the lower column
@@ -74,12 +76,23 @@ struct KeepTwoNearest {
     }
 };
 
-// Offers every column of [c_begin, c_end) of Y (ny rows) to `keep` for X row r0 + li, li = lane & 31; the lane's half-wave,
-// half = lane >> 5, sees the columns with (col & 4) == 4 * half.  Called by all 256 threads of the workgroup: a wave without
-// rows (returns false) still stages tiles and meets the barriers.
-template <int D, class Keep>
+// The walk's gate: one more predicate on every (row, column) element, with whatever it needs of the tile's 32 columns staged
+// next to the tile itself.  fetch(c0, ny) loads the part of tile c0 this thread stages into registers (it runs with the tile's
+// own global loads, one tile ahead), stash(buf) puts it into LDS buffer `buf` (with the tile's own LDS stores, in front of the
+// same barrier), pass(buf, slot) decides column c0 + slot of the tile in `buf` for the lane's row.  NoGate admits everything
+// and compiles to nothing: the matchers without a gate are the code they were.
+struct NoGate {
+    __device__ __forceinline__ void fetch(int, int) {}
+    __device__ __forceinline__ void stash(int) {}
+    __device__ __forceinline__ bool pass(int, int) const { return true; }
+};
+
+// Offers every column of [c_begin, c_end) of Y (ny rows) that `gate` admits to `keep` for X row r0 + li, li = lane & 31; the
+// lane's half-wave, half = lane >> 5, sees the columns with (col & 4) == 4 * half.  Called by all 256 threads of the
+// workgroup: a wave without rows (returns false) still stages tiles and meets the barriers.
+template <int D, class Keep, class Gate = NoGate>
 __device__ __forceinline__ bool walk_tiles(const float* __restrict__ X, const float* __restrict__ Y, int nx, int ny,
-                                           int c_begin, int c_end, int r0, int li, int half, Keep& keep)
+                                           int c_begin, int c_end, int r0, int li, int half, Keep& keep, Gate gate = Gate())
 {
     constexpr int RS = D + 4;                            // LDS row stride in floats
     __shared__ __attribute__((aligned(16))) float ytile[2][32 * RS];
@@ -113,11 +126,11 @@ __device__ __forceinline__ bool walk_tiles(const float* __restrict__ X, const fl
             *reinterpret_cast<f32x4*>(&ytile[buf][row * RS + q * 4]) = stage[k];
         }
     };
-    if (c_begin < c_end) { gload(c_begin); lstore(0); }
+    if (c_begin < c_end) { gload(c_begin); gate.fetch(c_begin, ny); lstore(0); gate.stash(0); }
     __syncthreads();
     for (int c0 = c_begin, buf = 0; c0 < c_end; c0 += 32, buf ^= 1) {
         const bool more = c0 + 32 < c_end;
-        if (more) gload(c0 + 32);                        // in flight across this tile's MFMAs
+        if (more) { gload(c0 + 32); gate.fetch(c0 + 32, ny); }     // in flight across this tile's MFMAs
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -131,13 +144,65 @@ __device__ __forceinline__ bool walk_tiles(const float* __restrict__ X, const fl
         if (active) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int col = c0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int slot = (r & 3) + 8 * (r >> 2) + 4 * half, col = c0 + slot;
                 const float t = fminf(fmaxf(acc[r], -1.f), 1.f);               // np.clip, matching.py:51
-                keep.offer(2.f - 2.f * t, col, col < ny);
+                keep.offer(2.f - 2.f * t, col, col < ny && gate.pass(buf, slot));
             }
         }
-        if (more) lstore(buf ^ 1);                       // last read one barrier ago
+        if (more) { lstore(buf ^ 1); gate.stash(buf ^ 1); }       // last read one barrier ago
         __syncthreads();
     }
     return active;
+}
+
+// ---- what the epilogue kernels and the launches of match_mfma.hip and match_guided.hip share ----
+
+// the N smallest keys (k2 is untouched for N = 1) of row `at` over the column shares' arrays, which lie [share][pair][K][N]
+template <int N>
+__device__ __forceinline__ void merge_shares(const unsigned long long* __restrict__ best, long long at, int K, int nsplit,
+                                             unsigned long long& k1, unsigned long long& k2)
+{
+    const long long share_stride = (long long)gridDim.y * K * N;
+    at *= N;
+    k1 = best[at];
+    if constexpr (N == 2) k2 = best[at + 1];
+    for (int sh = 1; sh < nsplit; ++sh) {
+        if constexpr (N == 1) { const unsigned long long o = best[at + sh * share_stride]; k1 = o < k1 ? o : k1; }
+        else merge2(k1, k2, best[at + sh * share_stride], best[at + sh * share_stride + 1]);
+    }
+}
+
+// One best-or-no match per query row.  j < 0: none; j2 / d2: the second-nearest train row, for the entry that reports it
+struct RowMatch { int j = -1, j2 = -1; float d = 0.f, d2 = 0.f; };
+
+// The epilogue kernels' frame, one thread per query row i of pair p: match(p, i) decides the row, which is written
+// (second_* may be NULL), and the workgroup adds its matches to the pair's count.
+template <class Match>
+__device__ __forceinline__ void write_matches(int K, int* __restrict__ match_idx, float* __restrict__ match_dist,
+                                              int* __restrict__ match_count, int* __restrict__ second_idx,
+                                              float* __restrict__ second_dist, Match match)
+{
+    const int p = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int hit = 0;
+    if (i < K) {
+        const RowMatch m = match(p, i);
+        const long long o = (long long)p * K + i;
+        match_idx[o] = m.j;
+        match_dist[o] = m.j >= 0 ? m.d : 0.f;
+        if (second_idx) second_idx[o] = m.j2;
+        if (second_dist) second_dist[o] = m.j2 >= 0 ? m.d2 : 0.f;
+        hit = m.j >= 0;
+    }
+    const int c = __syncthreads_count(hit);
+    if (threadIdx.x == 0 && c) atomicAdd(&match_count[p], c);
+}
+
+// the row kernels exist for the descriptor widths the C entries admit: launch(integral_constant<int, D>)
+template <class Launch>
+void for_width(int D, Launch launch)
+{
+    if (D == 64) launch(std::integral_constant<int, 64>{});
+    else if (D == 128) launch(std::integral_constant<int, 128>{});
+    else launch(std::integral_constant<int, 256>{});
 }

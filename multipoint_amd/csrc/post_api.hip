@@ -262,6 +262,31 @@ int mp_match_nearest(mp_handle* h, const float* descA, const int* countA, const 
     return launch_status(h);
 }
 
+int mp_match_guided(mp_handle* h, const float* descA, const int* countA, const float* descB, const int* countB,
+                    long long pair_stride, int count_stride, int P, int K, int D, const int* kpA_yx, const int* kpB_yx,
+                    const double* homography, float radius, float threshold, int* match_idx, float* match_dist,
+                    int* match_count, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    int rc;
+    if ((rc = match_check(h, "mp_match_guided", descA, descB, countA, countB, P, K, D, true))) return rc;
+    if (!kpA_yx || !kpB_yx || !homography || !match_idx || !match_dist || !match_count)
+        return fail(h, MP_EINVAL, "mp_match_guided: NULL tensor");
+    if (!(radius > 0.f) || !std::isfinite(radius)) return fail(h, MP_EINVAL, "mp_match_guided: radius must be finite and positive");
+    // (the keypoint rows are addressed in units of descriptor rows: pair p starts pair_stride / D rows behind the first)
+    if (pair_stride % D != 0) return fail(h, MP_EINVAL, "mp_match_guided: pair_stride must be a multiple of D");
+    MP_HIP(hipSetDevice(h->device));
+    // the matchers' key arrays, then the gate's positions [2][P][K][2] fp32
+    const size_t keys = (size_t)P * K * 8 * 2 * MATCH_SHARES;
+    if ((rc = ensure(h, h->match_ws, keys + (size_t)P * K * 4 * sizeof(float)))) return rc;
+    unsigned long long* rowbest = static_cast<unsigned long long*>(h->match_ws.p);
+    unsigned long long* colbest = rowbest + (size_t)P * K * MATCH_SHARES;
+    float* pos = reinterpret_cast<float*>(static_cast<char*>(h->match_ws.p) + keys);
+    launch_match_guided(descA, countA, descB, countB, pair_stride, count_stride, P, K, D, kpA_yx, kpB_yx, homography, radius,
+                        threshold, pos, rowbest, colbest, match_idx, match_dist, match_count, static_cast<hipStream_t>(stream));
+    return launch_status(h);
+}
+
 int mp_match_knn2(mp_handle* h, const float* descA, const int* countA, const float* descB, const int* countB,
                   long long pair_stride, int count_stride, int P, int K, int D, int* nn_idx, float* nn_dist,
                   void* stream)
@@ -354,6 +379,24 @@ int mp_find_homography(mp_handle* h, const int* kp_yx, const int* kp_count, cons
     MP_HIP(hipMemsetAsync(inlier_mask, 0, (size_t)P * K, s));
     launch_ransac_homography(kp_yx, kp_count, match_idx, P, K, max_iters, reproj_threshold, seed, best, homography,
                              inlier_mask, n_inliers, s);
+    return launch_status(h);
+}
+
+int mp_refine_homography(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K,
+                         double reproj_threshold, int iters, double* homography, unsigned char* inlier_mask, int* n_inliers,
+                         double* cost, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!kp_yx || !kp_count || !match_idx || !homography || !inlier_mask || !n_inliers)
+        return fail(h, MP_EINVAL, "mp_refine_homography: NULL tensor");
+    if (P <= 0 || K <= 0 || K > 3200) return fail(h, MP_EINVAL, "mp_refine_homography: need P > 0 and 0 < K <= 3200");
+    if (iters < 0 || iters > 1000) return fail(h, MP_EINVAL, "mp_refine_homography: iters must be in [0, 1000]");
+    if (!(reproj_threshold > 0.0)) return fail(h, MP_EINVAL, "mp_refine_homography: threshold must be positive");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MP_HIP(hipSetDevice(h->device));
+    MP_HIP(hipMemsetAsync(inlier_mask, 0, (size_t)P * K, s));
+    launch_refine_homography(kp_yx, kp_count, match_idx, P, K, reproj_threshold, iters, homography, inlier_mask, n_inliers, cost,
+                             s);
     return launch_status(h);
 }
 

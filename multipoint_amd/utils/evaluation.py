@@ -44,10 +44,11 @@ def pair_metrics(res, homography, threshold_keypoints):
     """GPU arithmetic of evaluation.py:287-328 for the pairs of a PairResults.
     homography: (2P,9) float64 from ground_truth_homographies().
     Returns (metrics [P,8] int32 device tensor, tp [2P,K] uint8 device tensor); see include/multipoint_hip.h.
-    The results must hold MUTUAL matches: tp[2p+1] reads the same pair from the thermal side, which only a one-to-one
+    The results must hold MUTUAL matches (match_mode 'mutual', or 'guided': mutual inside a gate): tp[2p+1] reads the same pair from the thermal side, which only a one-to-one
     match list defines (the reference hard-codes the cross-check matcher for these metrics, evaluation.py:273-282)."""
-    if getattr(res, 'match_mode', 'mutual') != 'mutual':
-        raise ValueError("pair_metrics needs mutual matches; these results were matched in '%s' mode" % res.match_mode)
+    if getattr(res, 'match_mode', 'mutual') not in ('mutual', 'guided'):
+        raise ValueError("pair_metrics needs mutual matches (match_mode 'mutual' or 'guided': one-to-one lists); these "
+                         "results were matched in '%s' mode" % res.match_mode)
     res.wait()
     dev = res.kp_yx.device
     P = res.num_pairs
@@ -68,7 +69,8 @@ def find_homography(res, reproj_threshold=3.0, max_iters=2000, seed=0):
     """Batched cv2.findHomography(optical_pts, thermal_pts, cv2.RANSAC, reproj_threshold) for the pairs of a PairResults
     (predict_align_image_pair.py:205-216).  NOT OpenCV's algorithm bit for bit: every pair evaluates `max_iters` 4-point
     hypotheses in parallel (no confidence-driven early stop) and refits the best consensus set by the normalised DLT
-    (OpenCV: adaptive iteration bound at confidence 0.995, refit, then a Levenberg-Marquardt polish).  Measured against an
+    (OpenCV: adaptive iteration bound at confidence 0.995, refit, then a Levenberg-Marquardt polish -- that polish exists
+    as a step of its own, refine_homography / refine_alignment, and is opt-in: this function stops at the refit).  Measured against an
     independent restatement of OpenCV 4.2's published algorithm (test infrastructure,
     tests/test_gpu_metrics.py::test_find_homography_against_opencv_semantics; planted homographies, 10-75 % outliers):
     mean corner distance differs by <= 0.11 px, the h_correctness decision (< 3 px) agrees on every pair, the inlier
@@ -87,6 +89,77 @@ def find_homography(res, reproj_threshold=3.0, max_iters=2000, seed=0):
                                          _lib.ptr(res.match_idx.contiguous()), P, K, float(reproj_threshold), int(max_iters),
                                          int(seed), _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin), _lib.stream_ptr(dev)))
     return Hm, mask, nin
+
+
+def refine_homography(res, H, reproj_threshold=3.0, iters=10):
+    """The Levenberg-Marquardt polish that closes cv2.findHomography(..., cv2.RANSAC, thr), batched (mp_refine_homography):
+    `H` ([P,3,3] or [P,9] float64, find_homography's estimate) is polished over the matches of `res` whose forward
+    reprojection error under H is <= reproj_threshold (recomputed, so `res` may hold any matcher's list).
+    Returns (H [P,3,3] float64 (h22 = 1; all zeros where the input is all zeros or fewer than 4 matches are inliers),
+    mask [P,K] uint8 and n_inliers [P] int32 of that inlier set, cost [P,2] float64: the sum of squared residuals over it
+    before / after)."""
+    iters = int(iters)
+    if not float(reproj_threshold) > 0.0:
+        raise ValueError('refine_homography: reproj_threshold must be positive')
+    if not 0 <= iters <= 1000:
+        raise ValueError('refine_homography: iters must be in [0, 1000]')
+    P, K = res.num_pairs, res.kp_yx.shape[1]
+    Hm = torch.as_tensor(H, dtype=torch.float64)
+    if Hm.numel() != P * 9:
+        raise ValueError('refine_homography: need one 3x3 matrix per pair (%d), got %d values' % (P, Hm.numel()))
+    res.wait()
+    dev = res.kp_yx.device
+    Hm = Hm.to(dev).reshape(P, 3, 3).clone().contiguous()                    # (polished in place: never the caller's tensor)
+    mask = torch.empty((P, K), dtype=torch.uint8, device=dev)
+    nin = torch.empty((P,), dtype=torch.int32, device=dev)
+    cost = torch.empty((P, 2), dtype=torch.float64, device=dev)
+    h = _lib.get_handle(dev)
+    with torch.cuda.device(dev):
+        h.check(h.lib.mp_refine_homography(h.ptr, _lib.ptr(res.kp_yx.contiguous()), _lib.ptr(res.kp_count.contiguous()),
+                                           _lib.ptr(res.match_idx.contiguous()), P, K, float(reproj_threshold), iters,
+                                           _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin), _lib.ptr(cost), _lib.stream_ptr(dev)))
+    return Hm, mask, nin, cost
+
+
+def refine_alignment(res, reproj_threshold=3.0, radius=None, rounds=1, polish=True, max_iters=2000, seed=0, threshold=-1.0):
+    """Guided re-matching and a polished homography for the pairs of a PairResults with mutual matches (an extension; the
+    reference stops at cv2.findHomography on the first match list):
+      1. find_homography on the matches of `res`;
+      2. `rounds` times: guided_pairs under the current estimate (partners within `radius` pixels of where the estimate
+         maps a keypoint; default 2 * reproj_threshold; `threshold` as for match_pairs), then find_homography on the new list;
+      3. with `polish`, refine_homography.
+    A pair without a first estimate keeps its original matches and a zero matrix.  `res` is not modified.
+    Returns (res2, H [P,3,3] float64, mask [P,K] uint8, n_inliers [P] int32); res2 is a new PairResults that shares the
+    keypoints and descriptors of `res`, holds the final match list and has match_mode 'guided'."""
+    from ..pipeline import PairResults
+    from .matching import guided_pairs
+    if getattr(res, 'match_mode', 'mutual') != 'mutual':
+        raise ValueError("refine_alignment starts from mutual matches; these results were matched in '%s' mode" % res.match_mode)
+    rounds = int(rounds)
+    if rounds < 0:
+        raise ValueError('refine_alignment: rounds must be >= 0')
+    radius = 2.0 * float(reproj_threshold) if radius is None else float(radius)
+    if not (radius > 0.0 and np.isfinite(radius)):
+        raise ValueError('refine_alignment: radius must be finite and positive, got %r' % radius)
+    H, mask, nin = find_homography(res, reproj_threshold, max_iters, seed)
+    cur = res
+    if rounds > 0:
+        K, D = res.desc.shape[1:]
+        none = (nin < 4)                                     # no first estimate (zero matrix): the original matches stay
+        for _ in range(rounds):
+            mi, md, mc = guided_pairs(res.desc, res.kp_count, res.desc[1:], res.kp_count[1:], res.kp_yx, res.kp_yx[1:], H,
+                                      radius, threshold, pair_stride=2 * K * D, count_stride=2)
+            mi = torch.where(none[:, None], res.match_idx, mi)
+            md = torch.where(none[:, None], res.match_dist, md)
+            mc = torch.where(none, res.match_count, mc)
+            cur = PairResults(res.kp_yx, res.kp_score, res.kp_count, res.desc, mi, md, mc, res.H, res.W, 'guided')
+            H, mask, nin = find_homography(cur, reproj_threshold, max_iters, seed)
+    if cur is res:
+        cur = PairResults(res.kp_yx, res.kp_score, res.kp_count, res.desc, res.match_idx, res.match_dist, res.match_count,
+                          res.H, res.W, 'guided')
+    if polish:
+        H, mask, nin, _ = refine_homography(cur, H, reproj_threshold)
+    return cur, H, mask, nin
 
 
 MAX_RANSAC_MATCHES = 3200        # mp_find_homography keeps a pair's correspondences in LDS
@@ -122,8 +195,24 @@ def _warp_yx(pts_yx, hmat):
     return (xy1[:, :2] / xy1[:, 2:3])[:, ::-1]
 
 
+def _refinement_config(config):
+    """refine_alignment's keyword arguments from prediction.alignment_refinement, or None when it is absent or disabled."""
+    cfg = config.get('alignment_refinement') or {}
+    unknown = set(cfg) - {'enable', 'radius', 'rounds', 'polish'}
+    if unknown:
+        raise ValueError('alignment_refinement: unknown key(s) %s' % sorted(unknown))
+    if not cfg.get('enable', False):
+        return None
+    return {'radius': cfg.get('radius'), 'rounds': int(cfg.get('rounds', 1)), 'polish': bool(cfg.get('polish', True))}
+
+
 def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoints, threshold_warp=None):
-    """Same signature and result keys as the reference function (evaluation.py:209)."""
+    """Same signature and result keys as the reference function (evaluation.py:209).
+    Extension: config['alignment_refinement'] = {enable: false, radius: null, rounds: 1, polish: true}.  With enable: true
+    every batch's mutual matches additionally go through refine_alignment (guided re-matching under the first estimate,
+    then the Levenberg-Marquardt polish) and the result gains pts_dist_refined / average_h_error_refined /
+    h_correctness_refined (as their unrefined namesakes, from the refined estimate) and n_matches_refined (matches per
+    pair after re-matching).  Every other key keeps its value; without enable there is no new key."""
     from ..pipeline import PairPipeline, PairResults
     from .utils import data_to_device
     from .matching import get_matches, match_pairs, nearest_pairs
@@ -140,6 +229,8 @@ def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoi
     sel = None
     if not same_matcher and mcfg.get('method') in ('bfmatcher', 'nnmatcher'):
         sel = PairPipeline(None, dict(config, matching=mcfg))
+    refine = _refinement_config(config)
+    pts_dist_ref, n_matches_ref = [], []
     tp_o, tp_t, dist_o, dist_t, ms_o, ms_t, pts_dist = [], [], [], [], [], [], []
     n_gt_o = n_gt_t = 0
     for data in dataloader:
@@ -188,6 +279,13 @@ def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoi
                 hp, mask = find_homography_points(opts, tpts, config.get('reprojection_threshold', 3), device=device)
                 if hp is not None:
                     h_est[p] = hp; n_in[p] = int(mask.sum())
+        if refine is not None:
+            if res.kp_yx.shape[1] > MAX_RANSAC_MATCHES:
+                raise ValueError('alignment_refinement: at most %d keypoints per image (the RANSAC launch keeps a pair\'s '
+                                 'matches in LDS)' % MAX_RANSAC_MATCHES)
+            res_r, h_ref, _, n_in_ref = refine_alignment(res, config.get('reprojection_threshold', 3), **refine)
+            h_ref = h_ref.cpu().numpy(); n_in_ref = n_in_ref.cpu().numpy()
+            n_matches_ref.extend(int(c) for c in res_r.match_count.cpu().numpy())
         H_o, W_o = opt['image'].shape[2:]
         m = metrics.cpu().numpy(); tp = tp.cpu().numpy()
         midx = res.match_idx.cpu().numpy(); mdist = res.match_dist.cpu().numpy()
@@ -210,6 +308,13 @@ def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoi
                 pts_dist.append(np.linalg.norm(_warp_yx(pts, h_est[p]) - _warp_yx(pts, gt), axis=1).sum() / 4)
             else:
                 pts_dist.append(999.0)
+            if refine is not None:
+                if n_in_ref[p] >= 4:
+                    pts = np.array([[0, 0], [H_o, 0], [0, W_o], [H_o, H_o]])
+                    gt = gth[2 * p].numpy().reshape(3, 3)
+                    pts_dist_ref.append(np.linalg.norm(_warp_yx(pts, h_ref[p]) - _warp_yx(pts, gt), axis=1).sum() / 4)
+                else:
+                    pts_dist_ref.append(999.0)
     out = summarize_descriptor_metrics(np.concatenate(tp_o) if tp_o else np.zeros(0, bool),
                                         np.concatenate(dist_o) if dist_o else np.zeros(0, np.float32),
                                         np.concatenate(tp_t) if tp_t else np.zeros(0, bool),
@@ -219,6 +324,13 @@ def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoi
     out['pts_dist'] = pts_dist
     out['average_h_error'] = pts_dist.mean() if len(pts_dist) else None
     out['h_correctness'] = (pts_dist < threshold_warp).sum() / len(pts_dist) if len(pts_dist) and threshold_warp is not None else None
+    if refine is not None:
+        pts_dist_ref = np.array(pts_dist_ref)
+        out['pts_dist_refined'] = pts_dist_ref
+        out['average_h_error_refined'] = pts_dist_ref.mean() if len(pts_dist_ref) else None
+        out['h_correctness_refined'] = ((pts_dist_ref < threshold_warp).sum() / len(pts_dist_ref)
+                                        if len(pts_dist_ref) and threshold_warp is not None else None)
+        out['n_matches_refined'] = np.array(n_matches_ref, dtype=np.int64)
     return out
 
 

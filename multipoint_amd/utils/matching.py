@@ -2,7 +2,8 @@
 path ('bfmatcher' with crossCheck=True, 'nnmatcher') and the remaining modes ('bfmatcher' without crossCheck, the
 knn_matches ratio test, 'thresholdmatcher'); every distance matrix is evaluated on the GPU and never materialised.
 match_pairs / nearest_pairs are the batched entries (all pairs of a batch in one launch, unit rows); get_matches is the
-per-pair function of the reference and accepts arbitrary rows."""
+per-pair function of the reference and accepts arbitrary rows.  guided_pairs is match_pairs inside a geometric gate (an
+extension: re-matching under a first homography estimate)."""
 import ctypes
 
 import numpy as np
@@ -10,7 +11,8 @@ import torch
 
 from .. import _lib
 
-__all__ = ['get_matches', 'NNMatcher', 'ThresholdMatcher', 'DMatch', 'match_pairs', 'knn2_pairs', 'nearest_pairs']
+__all__ = ['get_matches', 'NNMatcher', 'ThresholdMatcher', 'DMatch', 'match_pairs', 'knn2_pairs', 'nearest_pairs',
+           'guided_pairs']
 
 
 class DMatch:
@@ -81,6 +83,50 @@ def nearest_pairs(descA, countA, descB, countB, ratio=None, return_second=False,
     layout = _pair_layout(descA, countA, descB, countB, pair_stride, count_stride)
     out = _batched_match('mp_match_nearest', layout, 0.0 if ratio is None else float(ratio), bool(return_second))
     return tuple(out if return_second else out[:3])
+
+
+def guided_pairs(descA, countA, descB, countB, kpA, kpB, homography, radius, threshold=-1.0, pair_stride=None,
+                 count_stride=1):
+    """Mutual NN inside a geometric gate for P independent pairs on the GPU (mp_match_guided): optical row i and thermal
+    row j are candidates for each other only if `homography[p]` maps keypoint i within `radius` pixels of keypoint j.
+    descA / descB / countA / countB / pair_stride / count_stride as for match_pairs; kpA / kpB: int32 (y, x) keypoints
+    laid out like the descriptors ([P,K,2], or with pair_stride contiguous views that begin at the first pair's rows --
+    res.kp_yx and res.kp_yx[1:] for a PairResults); homography: [P,3,3] or [P,9] float64, optical (x, y, 1) -> thermal
+    (find_homography's; an all-zero matrix yields no matches for its pair).
+    Returns (match_idx [P,K] int32 (-1 = none), match_dist [P,K] f32, match_count [P] int32): a one-to-one list."""
+    radius = float(radius)
+    if not (radius > 0.0 and np.isfinite(radius)):
+        raise ValueError('guided_pairs: radius must be finite and positive, got %r' % radius)
+    descA, countA, descB, countB, P, K, D, stride, count_stride = _pair_layout(descA, countA, descB, countB, pair_stride,
+                                                                              count_stride)
+    if stride % D != 0:
+        raise ValueError('guided_pairs: pair_stride must be a multiple of D = %d (keypoint rows are addressed like '
+                         'descriptor rows)' % D)
+    rows = stride // D
+    for kp in (kpA, kpB):
+        if kp.dtype != torch.int32 or kp.device != descA.device:
+            raise ValueError('guided_pairs: keypoints must be int32 tensors on the descriptors\' device')
+    if pair_stride is None:
+        if tuple(kpA.shape) != (P, K, 2) or tuple(kpB.shape) != (P, K, 2):
+            raise ValueError('guided_pairs: keypoints must be [P, K, 2] = [%d, %d, 2]' % (P, K))
+        kpA, kpB = kpA.contiguous(), kpB.contiguous()
+    else:
+        for kp in (kpA, kpB):
+            if not kp.is_contiguous() or kp.numel() < ((P - 1) * rows + K) * 2:
+                raise ValueError('guided_pairs: keypoint views are shorter than %d pairs at this stride (or not contiguous)' % P)
+    dev = descA.device
+    hom = torch.as_tensor(homography, dtype=torch.float64)
+    if hom.numel() != P * 9:
+        raise ValueError('guided_pairs: need one 3x3 homography per pair (%d), got %d values' % (P, hom.numel()))
+    hom = hom.reshape(P, 9).to(dev).contiguous()
+    out = [torch.empty((P, K), dtype=torch.int32, device=dev), torch.empty((P, K), dtype=torch.float32, device=dev),
+           torch.empty((P,), dtype=torch.int32, device=dev)]
+    h = _lib.get_handle(dev)
+    with torch.cuda.device(dev):
+        h.check(h.lib.mp_match_guided(h.ptr, _lib.ptr(descA), _lib.ptr(countA), _lib.ptr(descB), _lib.ptr(countB), stride,
+                                      count_stride, P, K, D, _lib.ptr(kpA), _lib.ptr(kpB), _lib.ptr(hom), radius,
+                                      float(threshold), *[_lib.ptr(o) for o in out], _lib.stream_ptr(dev)))
+    return tuple(out)
 
 
 def _mutual_nn(desc_1, desc_2, threshold):

@@ -39,6 +39,8 @@ def build_parser():
     parser.add_argument('-th', dest='threshold_homography', default=1, type=int, help='Homography correctness threshold')
     parser.add_argument('-s', '--seed', default=0, type=int, help='Seed of the random generators')
     parser.add_argument('--save-npz', default=None, help='(extension) write keypoints/descriptors/matches of the sample here')
+    parser.add_argument('--refine', action='store_true', help='(extension) re-match under the first homography estimate and '
+                        'polish it (utils.refine_alignment); the aligned image uses the refined estimate')
     return parser
 
 
@@ -61,6 +63,46 @@ def select_device(config):
         raise RuntimeError('this implementation runs on an MI355X only: prediction.allow_gpu must be true and '
                            'a GPU must be visible (there is no CPU fallback; the reference runs on CPU)')
     return torch.device('cuda:0')
+
+
+def refine_estimate(kp_optical, kp_thermal, desc_optical, desc_thermal, matches, mask, H, W, pred, H_est):
+    """--refine: the sample's lists as a one-pair PairResults through utils.refine_alignment.  Prints inliers / matches
+    before and after and returns the refined estimate (the first one where there is nothing to refine)."""
+    from multipoint_amd.pipeline import PairResults
+    no, nt = kp_optical.shape[0], kp_thermal.shape[0]
+    D = desc_optical.shape[1] if no else desc_thermal.shape[1] if nt else 0
+    crosscheck = (pred['matching']['method'] == 'nnmatcher' or
+                  (pred['matching']['method'] == 'bfmatcher' and not pred['matching']['knn_matches']
+                   and pred['matching']['method_kwargs'].get('crossCheck', False)))
+    if not crosscheck:
+        raise ValueError('--refine starts from mutual matches: prediction.matching must be nnmatcher, or bfmatcher with crossCheck')
+    before = 'Refinement: {} inliers of {} matches'.format(int(np.sum(mask)), len(matches))
+    if no == 0 or nt == 0 or D not in (64, 128, 256) or max(no, nt) > utils.MAX_RANSAC_MATCHES:
+        print(before + ' -> unchanged (nothing to refine at these list sizes)')
+        return H_est
+    K = max(no, nt)
+    dev = desc_optical.device
+    kp = torch.zeros((2, K, 2), dtype=torch.int32, device=dev)
+    kp[0, :no] = kp_optical.to(torch.int32); kp[1, :nt] = kp_thermal.to(torch.int32)
+    desc = torch.zeros((2, K, D), dtype=torch.float32, device=dev)
+    desc[0, :no] = desc_optical; desc[1, :nt] = desc_thermal
+    midx = torch.full((1, K), -1, dtype=torch.int32)
+    mdist = torch.zeros((1, K), dtype=torch.float32)
+    for m in matches:
+        midx[0, m.queryIdx] = m.trainIdx; mdist[0, m.queryIdx] = m.distance
+    res = PairResults(kp, None, torch.tensor([no, nt], dtype=torch.int32, device=dev), desc, midx.to(dev), mdist.to(dev),
+                      torch.tensor([len(matches)], dtype=torch.int32, device=dev), H, W)
+    res2, H_ref, _, n_in = utils.refine_alignment(res, pred['reprojection_threshold'],
+                                                  threshold=pred['matching']['method_kwargs'].get('threshold', -1.0)
+                                                  if pred['matching']['method'] == 'nnmatcher' else -1.0)
+    if int(n_in[0]) < 4:
+        print(before + ' -> no refined estimate')
+        return H_est
+    print(before + ' -> {} inliers of {} matches'.format(int(n_in[0]), int(res2.match_count[0])))
+    H_ref = H_ref[0].cpu().numpy()
+    print('Refined Homography:')
+    print(H_ref)
+    return H_ref
 
 
 def main(argv=None):
@@ -135,7 +177,7 @@ def main(argv=None):
         print('Two forward passes took: {} s'.format(t_2 - t_1))
         print('Box nms: {} s'.format(t_3 - t_2))
 
-        if args.plot or args.save_npz:
+        if args.plot or args.save_npz or args.refine:
             H, W = data['optical']['image'].shape[2:]
             thr = pred['detection_threshold']
             pred_optical = torch.nonzero((out_optical['prob'][0].squeeze() > thr).float())
@@ -166,6 +208,9 @@ def main(argv=None):
             print('Estimated Homography:')
             print(H_est)
             print('RANSAC inliers: {} of {} matches'.format(int(np.sum(mask)), len(matches)))
+            if args.refine:
+                H_est = refine_estimate(pred_optical, pred_thermal, desc_optical, desc_thermal, matches, mask, H, W, pred,
+                                        H_est)
             print('Ground Truth Homography:')
             print(H_gt)
             print('--------------------------------------------------------')
