@@ -499,6 +499,77 @@ int mp_photometric_shade_mask(mp_handle* h, int n, int H, int W, const mp_photom
                               int n_ellipses, int op_index, int blurred, float* out, void* workspace,
                               long long workspace_bytes, void* stream);
 
+/* ---- mutual-information alignment (create_dataset/helper_functions/align.py:13-215) ----
+ * An EVALUATION is (pair p, bin count n, transform T [9] double, mapping thermal pixels to optical ones):
+ *   w   = cv2.warpPerspective(optical[p], inv(T), (W, H), borderValue=-1.0), INTER_LINEAR: the arithmetic of
+ *         mp_warp_perspective_cv with taps outside the Ho x Wo source reading -1 and the block width taken from the H x W
+ *         destination; the matrix applied to destination pixels is cv_invert3(cv_invert3(T)), the closed-form adjugate
+ *         inverse both times (the reference's first inverse is LAPACK's: a last-bits deviation)
+ *   jh  = np.histogram2d(w.ravel(), thermal[p].ravel(), bins=(n, 2n)) as numpy >= 2 bins float32 samples: per axis
+ *         a = min, b = max (a - 0.5, b + 0.5 when equal), float32 edges e[i] = fl(fl(i (b - a) / n) + a), e[n] = b,
+ *         bin = (edges <= v) - 1, v == b in the last bin.  Counts are u32 and exact (integer atomics only)
+ *   jh  = scipy.ndimage.gaussian_filter(jh, sigma, mode='constant') in double when sigma > 0 (sigma <= 16)
+ *   mi  = sum jh log jh - sum s1 log s1 - sum s2 log s2 of jh = (jh + 2^-52) / sum and its marginals, or normalised
+ *         (sum s1 log s1 + sum s2 log s2) / sum jh log jh - 1
+ *   value = -mi  (+ the Frobenius norm of T_init - T with a regulariser)
+ * The value of an evaluation has the same bits alone, inside any batch and from run to run.
+ * optical fp32 [n_pairs][Ho][Wo], thermal fp32 [n_pairs][H][W], transforms device double [n_evals][9]; eval_pair / eval_bins
+ * are HOST int arrays [n_evals], copied into the workspace on `stream`, which mp_mi_joint_histogram, mp_mi_objective and
+ * mp_mi_refine_begin synchronise once behind that copy.
+ * MP_EINVAL: a NULL tensor, sizes that are not positive (frames above 32767 x 32767 or 2^30 pixels), bins outside [1, 256], a
+ * pair index outside [0, n_pairs), more than 65535 evaluations or pairs, sigma outside [0, 16], a workspace smaller than
+ * mp_mi_workspace_bytes says for the call's evaluations.
+ *
+ * mp_mi_workspace_bytes: n_thermal_maps = distinct (pair, bins) among the evaluations, max_bins their largest bin count,
+ * smoothing != 0 when sigma > 0.  A refinement of P problems counts MP_MI_SLOTS evaluations per problem. */
+#define MP_MI_SLOTS 10
+int mp_mi_workspace_bytes(int n_evals, int n_pairs, int n_thermal_maps, int H, int W, int max_bins, int smoothing,
+                          long long* bytes);
+
+/* counts u32: the n x 2n histogram of evaluation e starts at sum over e' < e of 2 n_e'^2; minmax fp32 [n_evals][2]: min and
+ * max of the warped frame; warped fp32 [n_evals][H][W] or NULL.  strategy 0: an LDS copy of the histogram per workgroup
+ * for n <= 64, global atomics above; 1 / 2 force one of the two (1 needs n <= 64).  The counts do not depend on it. */
+int mp_mi_joint_histogram(mp_handle* h, const float* optical, int Ho, int Wo, const float* thermal, int H, int W, int n_pairs,
+                          const int* eval_pair, const int* eval_bins, const double* transforms, int n_evals, int strategy,
+                          unsigned int* counts, float* minmax, float* warped, void* workspace, long long workspace_bytes,
+                          void* stream);
+
+/* values double [n_evals]; init_transforms device double [n_evals][9] adds the regulariser, NULL: none */
+int mp_mi_objective(mp_handle* h, const float* optical, int Ho, int Wo, const float* thermal, int H, int W, int n_pairs,
+                    const int* eval_pair, const int* eval_bins, const double* transforms, int n_evals, double sigma,
+                    int normalized, const double* init_transforms, double* values, void* workspace, long long workspace_bytes,
+                    void* stream);
+
+/* Nelder-Mead over the 9 entries of T for a batch of problems, as scipy.optimize.minimize(method='Nelder-Mead', options=
+ * {'adaptive': False}) runs it: initial simplex x0 and per coordinate 1.05 x0[k] (0.00025 where x0[k] == 0), reflection,
+ * expansion, outside and inside contraction, shrink; iterations and function calls counted as scipy counts them (the
+ * reference's call leaves maxiter = maxfun = 1800, xatol = fatol = 1e-6); success = neither limit was reached.  Equal
+ * values keep their order when the simplex is sorted.
+ *   mp_mi_refine_begin   problems HOST [n_problems], init_transforms device double [n_problems][9]; the workspace (sized
+ *                        for MP_MI_SLOTS * n_problems evaluations) holds the whole state until the next begin on this handle
+ *   mp_mi_refine_step    enqueues n_iters rounds: one objective launch over the candidate points of every live problem
+ *                        (the simplex at first, then the four candidate points of a step, or the nine shrunk vertices),
+ *                        then the decision.  Finished problems cost nothing.  *live (device int) = problems still running
+ *                        after the last round.  No host synchronisation: the caller reads *live between calls.
+ *   mp_mi_refine_result  transforms double [n_problems][9], values double, iterations / function_calls / success int
+ *                        [n_problems]; a problem still running reports its best vertex so far and success 0.
+ * A handle runs ONE refinement at a time: its record (where the pieces lie in the workspace, and the caller's `optical`
+ * pointer) is kept in the handle, and the next mp_mi_refine_begin on the handle replaces it.  `optical` and the workspace
+ * must stay allocated and unchanged from begin to the last step / result; a workspace that was freed must not be handed to
+ * step / result again, even if a new allocation has its address.
+ * MP_ESTATE: step / result on a workspace other than the one of the handle's latest begin. */
+typedef struct mp_mi_problem {
+    int pair, bins;                 /* bins in [1, 256] */
+    int maxiter, maxfun;            /* scipy's limits (200 * 9 each by default) */
+    double xatol, fatol;
+} mp_mi_problem;
+int mp_mi_refine_begin(mp_handle* h, const float* optical, int Ho, int Wo, const float* thermal, int H, int W, int n_pairs,
+                       const mp_mi_problem* problems, const double* init_transforms, int n_problems, double sigma,
+                       int normalized, int regularize, void* workspace, long long workspace_bytes, void* stream);
+int mp_mi_refine_step(mp_handle* h, void* workspace, int n_iters, int* live, void* stream);
+int mp_mi_refine_result(mp_handle* h, void* workspace, double* transforms, double* values, int* iterations,
+                        int* function_calls, int* success, void* stream);
+
 /* per-launch timing of mp_forward with hipEvents on the caller's stream (bench.py roofline leg).
  * mp_profile_read synchronises; names[i] points to static strings. */
 int mp_profile_enable(mp_handle* h, int enable);

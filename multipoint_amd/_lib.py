@@ -53,6 +53,13 @@ class PhotometricPlan(ctypes.Structure):
     _fields_ = [('n_ops', c_int), ('noise_device', c_int), ('op', PhotometricOp * MP_PHOTO_MAX_OPS)]
 
 
+class MiProblem(ctypes.Structure):
+    _fields_ = [('pair', c_int), ('bins', c_int), ('maxiter', c_int), ('maxfun', c_int), ('xatol', ctypes.c_double),
+                ('fatol', ctypes.c_double)]
+
+
+MP_MI_SLOTS = 10
+
 # name -> (restype, argtypes); every symbol declared in include/multipoint_hip.h
 SIGNATURES = {
     'mp_create': (c_int, [ctypes.POINTER(c_void_p), c_int]),
@@ -125,6 +132,17 @@ SIGNATURES = {
                                        c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_ll, c_void_p]),
     'mp_photometric_shade_mask': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(PhotometricPlan), c_void_p, c_int,
                                           c_int, c_int, c_void_p, c_void_p, c_ll, c_void_p]),
+    'mp_mi_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
+    'mp_mi_joint_histogram': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_int),
+                                      ctypes.POINTER(c_int), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_ll, c_void_p]),
+    'mp_mi_objective': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_int),
+                                ctypes.POINTER(c_int), c_void_p, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p,
+                                c_ll, c_void_p]),
+    'mp_mi_refine_begin': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(MiProblem),
+                                   c_void_p, c_int, ctypes.c_double, c_int, c_int, c_void_p, c_ll, c_void_p]),
+    'mp_mi_refine_step': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'mp_mi_refine_result': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'mp_profile_enable': (c_int, [c_void_p, c_int]),
     'mp_profile_read': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_float),
                                 ctypes.POINTER(ctypes.c_double), c_int, ctypes.POINTER(c_int)]),

@@ -1,0 +1,261 @@
+// C ABI of the mutual-information alignment (mutual_info.hip): joint histograms, the objective, and the batched
+// Nelder-Mead refinement.  The caller owns every buffer; the host-side lists of an entry point (pair index and bin count
+// per evaluation, the problems of a refinement) are copied into the workspace on the stream, which is synchronised once
+// behind that copy so that the caller may free them on return.  mp_mi_refine_step never synchronises.
+#include "host.h"
+
+#include <map>
+#include <utility>
+
+using namespace mp_host;
+
+static_assert(MI_SLOTS == MP_MI_SLOTS, "the kernels' slots per problem and the public header's must agree");
+
+namespace {
+
+size_t up(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// where the pieces of a call lie in its workspace (byte offsets)
+struct MiLayout {
+    size_t ev, slots, nact, M, keys, tkeys, tmap, warped, counts, smooth_a, smooth_b, part, rowsum, colpart, values, cand, state,
+        opts, tinit, live, total;
+};
+
+MiLayout mi_layout(long long E, long long B, long long S, long long H, long long W, long long max_bins, bool smoothing)
+{
+    MiLayout l{};
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += up(bytes); return o; };
+    const size_t hist = (size_t)(2 * max_bins * max_bins), P = (size_t)((E + MI_SLOTS - 1) / MI_SLOTS);
+    l.ev = take((size_t)E * sizeof(MiEval));
+    l.slots = take((size_t)S * sizeof(int2));
+    l.nact = take(P * 4);
+    l.M = take((size_t)E * 72);
+    l.keys = take((size_t)E * 8);
+    l.tkeys = take((size_t)B * 8);
+    l.tmap = take((size_t)S * H * W * 2);
+    l.warped = take((size_t)E * H * W * 4);
+    l.counts = take((size_t)E * hist * 4);
+    l.smooth_a = take(smoothing ? (size_t)E * hist * 8 : 0);
+    l.smooth_b = take(smoothing ? (size_t)E * hist * 8 : 0);
+    l.part = take((size_t)E * MI_PARTS * 8);
+    l.rowsum = take((size_t)E * 256 * 8);
+    l.colpart = take((size_t)E * MI_PARTS * 512 * 8);
+    l.values = take((size_t)E * 8);
+    l.cand = take((size_t)E * 72);
+    l.state = take(P * sizeof(MiNmState));
+    l.opts = take(P * sizeof(MiNmOptions));
+    l.tinit = take(P * 72);
+    l.live = take(4);
+    l.total = at;
+    return l;
+}
+
+struct MiCall {
+    MiLayout lay{};
+    MiLaunch L{};
+    char* ws = nullptr;
+    long long stride = 0;          // counters per evaluation inside the workspace: 2 max_bins^2
+    template <typename T> T* at(size_t off) const { return reinterpret_cast<T*>(ws + off); }
+};
+
+// Checks the arguments the three entry points share, writes the evaluation list and the thermal bin maps into the workspace and
+// fills c.  `packed`: the counters of evaluation e follow those of e - 1 directly (the caller's array of mp_mi_joint_histogram);
+// otherwise they lie 2 max_bins^2 apart in the workspace.
+int mi_stage(mp_handle* h, const std::string& fn, const float* optical, int Ho, int Wo, const float* thermal, int H, int W, int B,
+             const int* pair, const int* bins, int E, int G, bool packed, bool smoothing, void* workspace, long long bytes,
+             hipStream_t s, MiCall& c)
+{
+    if (!optical || !thermal || !pair || !bins || !workspace) return fail(h, MP_EINVAL, fn + ": NULL tensor");
+    if (B > 65535) return fail(h, MP_EINVAL, fn + ": at most 65535 pairs per call");
+    if (B <= 0 || E <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return fail(h, MP_EINVAL, fn + ": sizes must be positive");
+    if (H > 32767 || W > 32767 || Ho > 32767 || Wo > 32767 || (long long)H * W > 0x3fffffffLL || (long long)Ho * Wo > 0x3fffffffLL)
+        return fail(h, MP_EINVAL, fn + ": frames of at most 32767 x 32767 and 2^30 pixels");
+    if (E > 65535) return fail(h, MP_EINVAL, fn + ": at most 65535 evaluations per call (" + std::to_string(MI_SLOTS) + " per problem)");
+    std::vector<MiEval> ev((size_t)E);
+    std::vector<int2> slots;
+    std::map<std::pair<int, int>, int> slot_of;
+    int maxb = 1, lds_bins = 0;
+    long long off = 0;
+    for (int e = 0; e < E; ++e) {
+        if (pair[e] < 0 || pair[e] >= B) return fail(h, MP_EINVAL, fn + ": pair index outside [0, n_pairs)");
+        if (bins[e] < 1 || bins[e] > 256) return fail(h, MP_EINVAL, fn + ": bins must be in [1, 256]");
+        if (bins[e] > maxb) maxb = bins[e];
+        if (bins[e] <= 64 && bins[e] > lds_bins) lds_bins = bins[e];
+        auto it = slot_of.find({pair[e], bins[e]});
+        if (it == slot_of.end()) {
+            it = slot_of.emplace(std::make_pair(pair[e], bins[e]), (int)slots.size()).first;
+            slots.push_back(int2{pair[e], bins[e]});
+        }
+        ev[e] = MiEval{pair[e], bins[e], it->second, 0, off};
+        off += 2LL * bins[e] * bins[e];
+    }
+    c.stride = 2LL * maxb * maxb;
+    if (!packed) for (int e = 0; e < E; ++e) ev[e].off = e * c.stride;
+    c.lay = mi_layout(E, B, (long long)slots.size(), H, W, maxb, smoothing);
+    if (bytes < (long long)c.lay.total)
+        return fail(h, MP_EINVAL, fn + ": workspace of " + std::to_string(bytes) + " B, needs " + std::to_string(c.lay.total) +
+                                      " B (mp_mi_workspace_bytes)");
+    c.ws = static_cast<char*>(workspace);
+    MP_HIP(hipSetDevice(h->device));
+    MP_HIP(hipMemcpyAsync(c.ws + c.lay.ev, ev.data(), ev.size() * sizeof(MiEval), hipMemcpyHostToDevice, s));
+    MP_HIP(hipMemcpyAsync(c.ws + c.lay.slots, slots.data(), slots.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+    launch_mi_thermal(thermal, B, H * W, c.at<int2>(c.lay.slots), (int)slots.size(), c.at<unsigned>(c.lay.tkeys),
+                      c.at<unsigned short>(c.lay.tmap), s);
+    MP_HIP(hipStreamSynchronize(s));
+    c.L = MiLaunch{optical, Ho, Wo, H, W, E, G, lds_bins, c.at<MiEval>(c.lay.ev), nullptr, nullptr, c.at<double>(c.lay.M),
+                   c.at<unsigned>(c.lay.keys), c.at<unsigned short>(c.lay.tmap), c.at<double>(c.lay.part),
+                   c.at<double>(c.lay.rowsum), c.at<double>(c.lay.colpart)};
+    return MP_OK;
+}
+
+int sigma_check(mp_handle* h, const std::string& fn, double sigma)
+{
+    if (!(sigma >= 0.0) || (int)(4.0 * sigma + 0.5) > MI_MAX_RADIUS)
+        return fail(h, MP_EINVAL, fn + ": smoothing sigma must be in [0, " + std::to_string(MI_MAX_RADIUS / 4) + "]");
+    return MP_OK;
+}
+
+// one objective launch of the running refinement followed by scipy's decision rules
+void refine_iteration(const MiRefine& r, int* live, hipStream_t s)
+{
+    launch_mi_histograms(r.L, r.counts, r.warped, nullptr, 0, s);
+    launch_mi_score(r.L, r.counts, r.sigma, r.normalized, r.reg_init, MI_SLOTS, r.smooth_stride, r.smooth_a, r.smooth_b, r.values, s);
+    launch_mi_nm_decide(r.state, r.P, r.cand, r.values, r.nact, live, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mp_mi_workspace_bytes(int n_evals, int n_pairs, int n_thermal_maps, int H, int W, int max_bins, int smoothing,
+                          long long* bytes)
+{
+    if (!bytes || n_evals <= 0 || n_evals > 65535 || n_pairs <= 0 || n_pairs > 65535 || n_thermal_maps <= 0 || H <= 0 || W <= 0 || H > 32767 ||
+        W > 32767 || (long long)H * W > 0x3fffffffLL || max_bins < 1 || max_bins > 256)
+        return MP_EINVAL;
+    *bytes = (long long)mi_layout(n_evals, n_pairs, n_thermal_maps, H, W, max_bins, smoothing != 0).total;
+    return MP_OK;
+}
+
+int mp_mi_joint_histogram(mp_handle* h, const float* optical, int Ho, int Wo, const float* thermal, int H, int W, int n_pairs,
+                          const int* eval_pair, const int* eval_bins, const double* transforms, int n_evals, int strategy,
+                          unsigned int* counts, float* minmax, float* warped, void* workspace, long long workspace_bytes,
+                          void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!transforms || !counts || !minmax) return fail(h, MP_EINVAL, "mp_mi_joint_histogram: NULL tensor");
+    if (strategy < 0 || strategy > 2)
+        return fail(h, MP_EINVAL, "mp_mi_joint_histogram: strategy must be 0 (by bin count), 1 (LDS copies) or 2 (global atomics)");
+    if (strategy == 1 && eval_bins)
+        for (int e = 0; e < n_evals; ++e)
+            if (eval_bins[e] > 64) return fail(h, MP_EINVAL, "mp_mi_joint_histogram: the LDS copies hold at most 64 bins");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MiCall c;
+    const int rc = mi_stage(h, "mp_mi_joint_histogram", optical, Ho, Wo, thermal, H, W, n_pairs, eval_pair, eval_bins, n_evals, 1,
+                            true, false, workspace, workspace_bytes, s, c);
+    if (rc != MP_OK) return rc;
+    c.L.T = transforms;
+    launch_mi_histograms(c.L, counts, warped ? warped : c.at<float>(c.lay.warped), minmax, strategy, s);
+    return launch_status(h);
+}
+
+int mp_mi_objective(mp_handle* h, const float* optical, int Ho, int Wo, const float* thermal, int H, int W, int n_pairs,
+                    const int* eval_pair, const int* eval_bins, const double* transforms, int n_evals, double sigma,
+                    int normalized, const double* init_transforms, double* values, void* workspace, long long workspace_bytes,
+                    void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!transforms || !values) return fail(h, MP_EINVAL, "mp_mi_objective: NULL tensor");
+    int rc = sigma_check(h, "mp_mi_objective", sigma);
+    if (rc != MP_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MiCall c;
+    rc = mi_stage(h, "mp_mi_objective", optical, Ho, Wo, thermal, H, W, n_pairs, eval_pair, eval_bins, n_evals, 1, false,
+                  sigma > 0.0, workspace, workspace_bytes, s, c);
+    if (rc != MP_OK) return rc;
+    c.L.T = transforms;
+    unsigned* counts = c.at<unsigned>(c.lay.counts);
+    launch_mi_histograms(c.L, counts, c.at<float>(c.lay.warped), nullptr, 0, s);
+    launch_mi_score(c.L, counts, sigma, normalized != 0, init_transforms, 1, c.stride, c.at<double>(c.lay.smooth_a),
+                    c.at<double>(c.lay.smooth_b), values, s);
+    return launch_status(h);
+}
+
+int mp_mi_refine_begin(mp_handle* h, const float* optical, int Ho, int Wo, const float* thermal, int H, int W, int n_pairs,
+                       const mp_mi_problem* problems, const double* init_transforms, int n_problems, double sigma,
+                       int normalized, int regularize, void* workspace, long long workspace_bytes, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    h->mi = MiRefine{};
+    if (!problems || !init_transforms) return fail(h, MP_EINVAL, "mp_mi_refine_begin: NULL tensor");
+    if (n_problems <= 0 || n_problems > 65535 / MI_SLOTS)
+        return fail(h, MP_EINVAL, "mp_mi_refine_begin: need 0 < n_problems <= " + std::to_string(65535 / MI_SLOTS));
+    int rc = sigma_check(h, "mp_mi_refine_begin", sigma);
+    if (rc != MP_OK) return rc;
+    const int P = n_problems, E = P * MI_SLOTS;
+    std::vector<int> pair((size_t)E), bins((size_t)E);
+    std::vector<MiNmOptions> opts((size_t)P);
+    for (int q = 0; q < P; ++q) {
+        const mp_mi_problem& pr = problems[q];
+        if (pr.maxiter < 1 || pr.maxfun < 1 || !(pr.xatol >= 0.0) || !(pr.fatol >= 0.0))
+            return fail(h, MP_EINVAL, "mp_mi_refine_begin: maxiter and maxfun must be positive, xatol and fatol non-negative");
+        for (int v = 0; v < MI_SLOTS; ++v) { pair[q * MI_SLOTS + v] = pr.pair; bins[q * MI_SLOTS + v] = pr.bins; }
+        opts[q] = MiNmOptions{pr.maxiter, pr.maxfun, pr.xatol, pr.fatol};
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MiCall c;
+    rc = mi_stage(h, "mp_mi_refine_begin", optical, Ho, Wo, thermal, H, W, n_pairs, pair.data(), bins.data(), E, MI_SLOTS, false,
+                  sigma > 0.0, workspace, workspace_bytes, s, c);
+    if (rc != MP_OK) return rc;
+    MiRefine r;
+    r.workspace = workspace;
+    r.L = c.L;
+    r.P = P; r.normalized = normalized != 0; r.sigma = sigma; r.smooth_stride = c.stride;
+    r.counts = c.at<unsigned>(c.lay.counts);
+    r.warped = c.at<float>(c.lay.warped);
+    r.smooth_a = c.at<double>(c.lay.smooth_a); r.smooth_b = c.at<double>(c.lay.smooth_b);
+    r.cand = c.at<double>(c.lay.cand); r.values = c.at<double>(c.lay.values);
+    r.state = c.at<MiNmState>(c.lay.state);
+    r.nact = c.at<int>(c.lay.nact);
+    r.L.T = r.cand;
+    r.L.nact = r.nact;
+    // the problems' initial transforms are kept in the workspace: the regulariser reads them at every evaluation
+    double* init = c.at<double>(c.lay.tinit);
+    MP_HIP(hipMemcpyAsync(init, init_transforms, (size_t)P * 72, hipMemcpyDeviceToDevice, s));
+    MP_HIP(hipMemcpyAsync(c.ws + c.lay.opts, opts.data(), opts.size() * sizeof(MiNmOptions), hipMemcpyHostToDevice, s));
+    launch_mi_nm_begin(r.state, c.at<MiNmOptions>(c.lay.opts), init, P, r.cand, r.nact, s);
+    MP_HIP(hipStreamSynchronize(s));
+    r.reg_init = regularize ? init : nullptr;
+    h->mi = r;
+    return launch_status(h);
+}
+
+int mp_mi_refine_step(mp_handle* h, void* workspace, int n_iters, int* live, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!workspace || !live) return fail(h, MP_EINVAL, "mp_mi_refine_step: NULL tensor");
+    if (!h->mi.workspace || h->mi.workspace != workspace)
+        return fail(h, MP_ESTATE, "mp_mi_refine_step: no refinement was begun in this workspace");
+    if (n_iters < 1 || n_iters > 100000) return fail(h, MP_EINVAL, "mp_mi_refine_step: n_iters must be in [1, 100000]");
+    MP_HIP(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    for (int i = 0; i < n_iters; ++i) refine_iteration(h->mi, live, s);
+    return launch_status(h);
+}
+
+int mp_mi_refine_result(mp_handle* h, void* workspace, double* transforms, double* values, int* iterations,
+                        int* function_calls, int* success, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!workspace || !transforms || !values || !iterations || !function_calls || !success)
+        return fail(h, MP_EINVAL, "mp_mi_refine_result: NULL tensor");
+    if (!h->mi.workspace || h->mi.workspace != workspace)
+        return fail(h, MP_ESTATE, "mp_mi_refine_result: no refinement was begun in this workspace");
+    MP_HIP(hipSetDevice(h->device));
+    launch_mi_nm_result(h->mi.state, h->mi.P, transforms, values, iterations, function_calls, success,
+                        static_cast<hipStream_t>(stream));
+    return launch_status(h);
+}
+
+}  // extern "C"

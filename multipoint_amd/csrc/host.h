@@ -1,5 +1,5 @@
 // Host-side state of libmultipoint_hip.so shared by the C ABI's translation units (api.hip, model_load.hip, forward.hip,
-// post_api.hip): the handle, its layers and device buffers, and the error helpers.  Internal: the public C ABI is
+// post_api.hip, align_api.hip): the handle, its layers and device buffers, and the error helpers.  Internal: the public C ABI is
 // include/multipoint_hip.h.
 #pragma once
 #include "../../include/multipoint_hip.h"
@@ -90,6 +90,21 @@ struct ConvPolicy {
     int splitk_max = 8;             // most ranges the input channels of a small launch are cut into (1: never)
 };
 
+// the refinement mp_mi_refine_begin started: where its pieces lie in the caller's workspace (align_api.hip)
+struct MiRefine {
+    void* workspace = nullptr;
+    MiLaunch L{};
+    int P = 0, normalized = 0;
+    double sigma = 0.0;
+    long long smooth_stride = 0;
+    unsigned* counts = nullptr;
+    float* warped = nullptr;
+    double *smooth_a = nullptr, *smooth_b = nullptr, *cand = nullptr, *values = nullptr;
+    const double* reg_init = nullptr;     // the problems' initial transforms when the objective is regularised
+    MiNmState* state = nullptr;
+    int* nact = nullptr;
+};
+
 }  // namespace mp_host
 
 struct mp_handle {
@@ -127,6 +142,7 @@ struct mp_handle {
     int head_channels = 256;        // width of each 3x3 head convolution (MultiPoint.py:38-53)
     mp_host::DevBuf f16_dummy;      // scratch line for masked-off store lanes of the fp16 kernels
     int* pinned = nullptr;          // small pinned host scratch (img lists, counters)
+    mp_host::MiRefine mi;           // the running mutual-information refinement (mp_mi_refine_*)
     bool prof = false;
     bool head_fallback_noted = false;
     std::vector<mp_host::ProfEntry> prof_entries;

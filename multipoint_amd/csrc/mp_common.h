@@ -468,3 +468,44 @@ void launch_photometric(const float* in, float* out, int n, int H, int W, const 
                         hipStream_t s);
 void launch_photometric_shade_mask(int n, int H, int W, const mp_photometric_plan* plans, const int* ellipses,
                                    int n_ellipses, int op_index, int blurred, float* out, void* workspace, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
+// mutual-information alignment (mutual_info.hip; reference create_dataset/helper_functions/align.py:13-215).
+// An evaluation is (pair, bins, transform); its n x 2n counters start at counts + off.  G consecutive evaluations form a
+// group of which the first nact[group] run (nact NULL: all of them): the candidate slots of one Nelder-Mead problem.
+// ---------------------------------------------------------------------------------------------
+#define MI_PARTS 16            // row blocks of the score's first pass
+#define MI_MAX_RADIUS 64       // of the smoothing kernel: int(4 sigma + 0.5)
+#define MI_SLOTS 10            // candidate slots of a Nelder-Mead problem: the 9 + 1 vertices of its simplex
+struct MiEval { int pair, bins, tslot, pad; long long off; };
+struct MiNmOptions { int maxiter, maxfun; double xatol, fatol; };
+struct MiNmState {
+    double sim[MI_SLOTS][9], fsim[MI_SLOTS];
+    MiNmOptions opt;
+    int iterations, fcalls, phase, done, status, pad;
+};
+struct MiLaunch {
+    const float* optical;      // [B][Ho][Wo]
+    int Ho, Wo, H, W, E, G;
+    int lds_bins;              // largest bin count <= 64 among the evaluations (0: none): sizes hist_kernel's LDS
+    const MiEval* ev;          // [E]
+    const int* nact;           // [E / G] or NULL
+    const double* T;           // [E][9]
+    double* M;                 // [E][9]: cv_invert3(cv_invert3(T))
+    unsigned* keys;            // [E][2]: ordered keys of the warped frame's min / max
+    const unsigned short* tmap;   // [S][H W]: thermal bins per distinct (pair, bins)
+    double *part, *rowsum, *colpart;   // [E][MI_PARTS], [E][256], [E][MI_PARTS][512]
+};
+// tkeys [B][2], tmap [S][H W] for the S slots (pair, bins)
+void launch_mi_thermal(const float* thermal, int B, int HW, const int2* slots, int S, unsigned* tkeys, unsigned short* tmap,
+                       hipStream_t s);
+// counts (zeroed here), warped [E][H][W]; minmax [E][2] or NULL; strategy 0 by bin count, 1 LDS copies, 2 global atomics
+void launch_mi_histograms(const MiLaunch& L, unsigned* counts, float* warped, float* minmax, int strategy, hipStream_t s);
+// values [E] = -MI (+ |Tinit[e / tg] - T[e]|_F when Tinit); smooth_a / smooth_b [E][smooth_stride] doubles when sigma > 0
+void launch_mi_score(const MiLaunch& L, const unsigned* counts, double sigma, int normalized, const double* Tinit, int tg,
+                     long long smooth_stride, double* smooth_a, double* smooth_b, double* values, hipStream_t s);
+void launch_mi_nm_begin(MiNmState* state, const MiNmOptions* opt, const double* Tinit, int P, double* cand, int* nact,
+                        hipStream_t s);
+void launch_mi_nm_decide(MiNmState* state, int P, double* cand, const double* values, int* nact, int* live, hipStream_t s);
+void launch_mi_nm_result(const MiNmState* state, int P, double* T, double* value, int* iterations, int* fcalls, int* success,
+                         hipStream_t s);

@@ -1,0 +1,367 @@
+"""Intensity-based alignment of an optical frame on a thermal one by (normalised) mutual information: the alignment core of
+the reference's dataset tooling (create_dataset/helper_functions/align.py) on the GPU (csrc/mutual_info.hip).
+
+The reference's names keep their argument order: warp_image, mutual_information_2d, calculate_negative_mutual_information,
+refine_alignment.  Images are fp32 CUDA tensors; a `transform` is a 3x3 float64 matrix (numpy array or tensor) that maps
+thermal (destination) pixel coordinates to optical (source) ones, exactly as in the reference, and transforms are returned
+as float64 numpy arrays.  negative_mutual_information_batch, refine_alignment_batch and the batched align_images have no
+counterpart in the reference.
+
+Import this module as multipoint_amd.utils.alignment: its refine_alignment is NOT the guided refine_alignment that
+multipoint_amd.utils exports.
+
+Not implemented (NotImplementedError): 2x3 affine transforms and `decompose_transformation` (cv2.warpAffine is another
+fixed-point path that has no restatement here), and the geometric part of check_perspective_transformation
+(cv2.decomposeHomographyMat).
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from .. import _lib
+
+__all__ = ['warp_image', 'mutual_information_2d', 'calculate_negative_mutual_information', 'refine_alignment',
+           'negative_mutual_information_batch', 'refine_alignment_batch', 'align_images', 'joint_histograms',
+           'rank_candidates', 'check_perspective_transformation', 'alignment_type_name']
+
+_AFFINE = ('2x3 affine transforms are not implemented: cv2.warpAffine is a different fixed-point path than '
+           'cv2.warpPerspective and has no restatement in this project')
+
+
+def _transforms(t):
+    """any array-like of 3x3 matrices (or flat 9-vectors) -> float64 numpy (n, 9); affine and decomposed forms are refused."""
+    if isinstance(t, torch.Tensor):
+        t = t.detach().cpu().numpy()
+    t = np.asarray(t, np.float64)
+    if t.shape[-2:] == (2, 3) or (t.ndim == 1 and t.size == 6):
+        raise NotImplementedError(_AFFINE)
+    if t.ndim == 1 and t.size == 4:
+        raise NotImplementedError('decomposed (angle, scale, dx, dy) transforms are affine: ' + _AFFINE)
+    if t.size % 9 != 0 or (t.ndim >= 2 and t.shape[-2:] != (3, 3) and t.shape[-1] != 9):
+        raise ValueError('Unknown transformation shape: %s' % (t.shape,))
+    return np.ascontiguousarray(t.reshape(-1, 9))
+
+
+def _frames(x, name):
+    """(H, W), (B, H, W) or (B, 1, H, W) fp32 CUDA tensor -> contiguous (B, H, W)."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError('%s must be a CUDA tensor (multipoint_amd computes on the GPU only)' % name)
+    if x.dim() == 2:
+        x = x[None]
+    elif x.dim() == 4:
+        if x.shape[1] != 1:
+            raise ValueError('%s must have one channel, got %s' % (name, tuple(x.shape)))
+        x = x[:, 0]
+    elif x.dim() != 3:
+        raise ValueError('%s must be (H, W), (B, H, W) or (B, 1, H, W), got %s' % (name, tuple(x.shape)))
+    return x.to(torch.float32).contiguous()
+
+
+def _ints(v):
+    v = [int(i) for i in v]
+    return (ctypes.c_int * len(v))(*v)
+
+
+class _Call:
+    """The arguments every entry point shares, and a workspace of the size the library asks for."""
+
+    def __init__(self, optical, thermal, pair_index, bins, n_evals=None, smoothing=False):
+        self.optical, self.thermal = _frames(optical, 'optical'), _frames(thermal, 'thermal')
+        if self.optical.shape[0] != self.thermal.shape[0]:
+            raise ValueError('optical and thermal must hold the same number of frames')
+        if self.optical.device != self.thermal.device:
+            raise ValueError('optical and thermal must be on the same device')
+        self.dev = self.optical.device
+        self.h = _lib.get_handle(self.dev)
+        self.B, self.Ho, self.Wo = self.optical.shape
+        self.H, self.W = self.thermal.shape[1:]
+        self.pair, self.bins = [int(p) for p in pair_index], [int(b) for b in bins]
+        n_evals = len(self.pair) if n_evals is None else n_evals
+        maps = len(set(zip(self.pair, self.bins)))
+        need = _lib.c_ll()
+        rc = self.h.lib.mp_mi_workspace_bytes(n_evals, self.B, max(maps, 1), self.H, self.W, min(max(self.bins + [1]), 256),
+                                              int(smoothing), ctypes.byref(need))
+        if rc != _lib.MP_OK:
+            raise ValueError('mutual information: unsupported sizes (%d evaluations of %d pairs at %dx%d)'
+                             % (n_evals, self.B, self.H, self.W))
+        self.workspace = torch.empty(need.value, dtype=torch.uint8, device=self.dev)
+        self.stream = _lib.stream_ptr(self.dev)
+
+    def head(self):
+        return (self.h.ptr, _lib.ptr(self.optical), self.Ho, self.Wo, _lib.ptr(self.thermal), self.H, self.W, self.B)
+
+    def tail(self):
+        return (_lib.ptr(self.workspace), self.workspace.numel(), self.stream)
+
+
+def joint_histograms(optical, thermal, pair_index, bins, transforms, strategy=0, return_warped=False):
+    """The joint histograms of the evaluations (pair_index[e], bins[e], transforms[e]): a list of (n, 2n) int64 CPU tensors,
+    the (E, 2) fp32 min / max of the warped frames and, if asked for, the warped frames (E, H, W).  strategy 0 chooses the
+    histogram kernel by bin count, 1 / 2 force the LDS-privatised / the global-atomics one."""
+    T = _transforms(transforms)
+    c = _Call(optical, thermal, pair_index, bins)
+    E = len(c.pair)
+    if T.shape[0] != E or len(c.bins) != E:
+        raise ValueError('one pair index, bin count and transform per evaluation')
+    Td = torch.from_numpy(T).to(c.dev)
+    total = sum(2 * n * n for n in c.bins if 1 <= n <= 256)
+    counts = torch.empty(max(total, 1), dtype=torch.int32, device=c.dev)
+    minmax = torch.empty((E, 2), dtype=torch.float32, device=c.dev)
+    warped = torch.empty((E, c.H, c.W), dtype=torch.float32, device=c.dev) if return_warped else None
+    c.h.check(c.h.lib.mp_mi_joint_histogram(*c.head(), _ints(c.pair), _ints(c.bins), _lib.ptr(Td), E, int(strategy),
+                                            _lib.ptr(counts), _lib.ptr(minmax), _lib.ptr(warped), *c.tail()))
+    flat = counts.cpu().to(torch.int64) & 0xffffffff
+    out, at = [], 0
+    for n in c.bins:
+        out.append(flat[at:at + 2 * n * n].reshape(n, 2 * n))
+        at += 2 * n * n
+    return out, minmax, warped
+
+
+def _objective(optical, thermal, pair_index, bins, transforms, init_transforms, normalized_mi, smoothing_sigma):
+    """values (E,) float64 CUDA tensor of the evaluations (pair_index[e], bins[e], transforms[e])."""
+    T = _transforms(transforms)
+    c = _Call(optical, thermal, pair_index, bins, smoothing=smoothing_sigma > 0)
+    E = len(c.pair)
+    if T.shape[0] != E or len(c.bins) != E:
+        raise ValueError('one pair index, bin count and transform per evaluation')
+    Td = torch.from_numpy(T).to(c.dev)
+    Ti = None
+    if init_transforms is not None:
+        Ti = _transforms(init_transforms)
+        if Ti.shape[0] != E:
+            raise ValueError('one initial transform per evaluation')
+        Ti = torch.from_numpy(Ti).to(c.dev)
+    values = torch.empty(E, dtype=torch.float64, device=c.dev)
+    c.h.check(c.h.lib.mp_mi_objective(*c.head(), _ints(c.pair), _ints(c.bins), _lib.ptr(Td), E, float(smoothing_sigma),
+                                      int(bool(normalized_mi)), _lib.ptr(Ti), _lib.ptr(values), *c.tail()))
+    return values
+
+
+def negative_mutual_information_batch(optical, thermal, transforms, bins, init_transforms=None, regularize=False,
+                                      normalized_mi=False, smoothing_sigma=0):
+    """The objective for E transforms of each of B pairs in one launch: optical (B, 1, Ho, Wo), thermal (B, 1, H, W),
+    transforms (B, E, 3, 3); bins an int or one int per transform (E); init_transforms (B, 3, 3) or (B, E, 3, 3) for the
+    regulariser.  Returns a (B, E) float64 CUDA tensor."""
+    t = transforms.detach().cpu().numpy() if isinstance(transforms, torch.Tensor) else np.asarray(transforms, np.float64)
+    if t.ndim != 4 or t.shape[2:] != (3, 3):
+        if t.ndim == 4 and t.shape[2:] == (2, 3):
+            raise NotImplementedError(_AFFINE)
+        raise ValueError('transforms must be (B, E, 3, 3), got %s' % (t.shape,))
+    B, E = t.shape[:2]
+    bins = [int(bins)] * E if np.ndim(bins) == 0 else [int(b) for b in bins]
+    if len(bins) != E:
+        raise ValueError('bins must be one int or one per transform')
+    init = None
+    if regularize:
+        if init_transforms is None:
+            raise ValueError('the regulariser needs init_transforms')
+        init = _transforms(init_transforms).reshape(B, -1, 9)
+        init = np.broadcast_to(init, (B, E, 9)).reshape(-1, 9)
+    pair = np.repeat(np.arange(B), E)
+    v = _objective(optical, thermal, pair, bins * B, t.reshape(-1, 9), init, normalized_mi, smoothing_sigma)
+    return v.reshape(B, E)
+
+
+def warp_image(image, transform, height, width):
+    """cv2.warpPerspective(image, inv(transform), (width, height), borderValue=-1.0) (align.py:13-50) for one frame (H, W) or a
+    batch (B, 1, H, W) with one transform for all frames or one per frame.  Returns a tensor of the input's rank."""
+    T = _transforms(transform)
+    img = _frames(image, 'image')
+    B = img.shape[0]
+    if T.shape[0] not in (1, B):
+        raise ValueError('one transform, or one per frame')
+    T = np.broadcast_to(T, (B, 9)).copy()
+    dummy = torch.zeros((B, int(height), int(width)), dtype=torch.float32, device=img.device)
+    _, _, warped = joint_histograms(img, dummy, range(B), [1] * B, T, return_warped=True)
+    if image.dim() == 2:
+        return warped[0]
+    return warped[:, None] if image.dim() == 4 else warped
+
+
+def _sample_grid(n):
+    """rows x cols = n with both sides within the warp's 32767 limit (the samples are laid out as a frame)."""
+    if n <= 32767:
+        return 1, n
+    for cols in range(32767, 0, -1):
+        if n % cols == 0 and n // cols <= 32767:
+            return n // cols, cols
+    raise ValueError('cannot lay %d samples out as a frame of at most 32767 x 32767' % n)
+
+
+def mutual_information_2d(x, y, sigma=5, bins=100, normalized=False):
+    """(Normalised) mutual information of two equally long sample vectors from their n x 2n joint histogram (align.py:52-100).
+    x, y: fp32 CUDA tensors of any shape with the same number of elements.  Returns a float.
+    The samples are laid out as a frame of at most 32767 x 32767 for the identity warp: a 2-D input keeps its shape, up to
+    32767 samples form one row, more need a factorisation within those limits (ValueError otherwise, e.g. a large prime)."""
+    if x.numel() != y.numel():
+        raise ValueError('x and y must have the same number of samples')
+    rows, cols = (x.shape if x.dim() == 2 and max(x.shape) <= 32767 else _sample_grid(x.numel()))
+    # the identity warp copies x bit for bit (every coordinate lands on a pixel centre with weight 1)
+    v = _objective(x.reshape(rows, cols), y.reshape(rows, cols), [0], [bins], np.eye(3), None, normalized, sigma)
+    return -float(v.item())
+
+
+def calculate_negative_mutual_information(transform, optical, thermal, init_transform, bins, regularize=False,
+                                          normalized_mi=False, smoothing_sigma=0):
+    """Negative mutual information between the warped optical and the thermal frame (align.py:102-155), plus the Frobenius
+    norm of init_transform - transform with `regularize`.  Returns a float."""
+    _transforms(init_transform)
+    v = _objective(optical, thermal, [0], [bins], transform, init_transform if regularize else None, normalized_mi,
+                   smoothing_sigma)
+    return float(v.item())
+
+
+def refine_alignment_batch(optical, thermal, pair_index, bins, init_transforms, regularize=False, normalized_mi=False,
+                           smoothing_sigma=0, xatol=1e-6, fatol=1e-6, maxiter=None, maxfun=None, chunk=32):
+    """Nelder-Mead maximisation of the mutual information for a batch of problems (pair_index[q], bins[q],
+    init_transforms[q]) as scipy runs it for the reference (align.py:202-207).  xatol, fatol, maxiter, maxfun: scalars or one
+    value per problem (None: scipy's 200 * 9).  The iterations are enqueued `chunk` at a time; between chunks one integer, the
+    number of problems still running, is read back.  Returns dict(transform (P, 3, 3), value (P,), nit, nfev, success) of
+    numpy arrays, plus 'rounds', the number of objective launches that were enqueued (a multiple of `chunk`)."""
+    T = _transforms(init_transforms)
+    P = T.shape[0]
+    pair, bins = [int(p) for p in pair_index], [int(b) for b in bins]
+    if len(pair) != P or len(bins) != P:
+        raise ValueError('one pair index, bin count and initial transform per problem')
+
+    def per(v, default):
+        v = default if v is None else v
+        return [v] * P if np.ndim(v) == 0 else list(v)
+    if maxiter is None and maxfun is None:
+        maxiter = maxfun = 200 * 9
+    big = 2 ** 31 - 1
+    it, fn, xa, fa = per(maxiter, big), per(maxfun, big), per(xatol, 1e-6), per(fatol, 1e-6)
+    S = _lib.MP_MI_SLOTS
+    c = _Call(optical, thermal, pair, bins, n_evals=S * P, smoothing=smoothing_sigma > 0)
+    problems = (_lib.MiProblem * P)(*[_lib.MiProblem(pair[q], bins[q], int(min(it[q], big)), int(min(fn[q], big)),
+                                                     float(xa[q]), float(fa[q])) for q in range(P)])
+    Td = torch.from_numpy(T).to(c.dev)
+    lib = c.h.lib
+    c.h.check(lib.mp_mi_refine_begin(*c.head(), problems, _lib.ptr(Td), P, float(smoothing_sigma), int(bool(normalized_mi)),
+                                     int(bool(regularize)), *c.tail()))
+    live = torch.zeros(1, dtype=torch.int32, device=c.dev)
+    rounds = 0
+    while True:
+        c.h.check(lib.mp_mi_refine_step(c.h.ptr, _lib.ptr(c.workspace), int(chunk), _lib.ptr(live), c.stream))
+        rounds += int(chunk)
+        if int(live.item()) == 0:
+            break
+    out_T = torch.empty((P, 9), dtype=torch.float64, device=c.dev)
+    value = torch.empty(P, dtype=torch.float64, device=c.dev)
+    nit, nfev, ok = (torch.empty(P, dtype=torch.int32, device=c.dev) for _ in range(3))
+    c.h.check(lib.mp_mi_refine_result(c.h.ptr, _lib.ptr(c.workspace), _lib.ptr(out_T), _lib.ptr(value), _lib.ptr(nit),
+                                      _lib.ptr(nfev), _lib.ptr(ok), c.stream))
+    return {'transform': out_T.cpu().numpy().reshape(P, 3, 3), 'value': value.cpu().numpy(), 'nit': nit.cpu().numpy(),
+            'nfev': nfev.cpu().numpy(), 'success': ok.cpu().numpy().astype(bool), 'rounds': rounds}
+
+
+def refine_alignment(optical, thermal, init_transform, decompose_transformation, regularize, bins=256, normalized_mi=False,
+                     smoothing_sigma=0):
+    """Refine the alignment by maximising the mutual information between the optical and the thermal frame
+    (align.py:157-215).  Returns (transform (3, 3) float64 numpy array, success)."""
+    # (decompose_transformation: the reference only decomposes 2x3 transforms and ignores the flag for a 3x3 one; so does
+    # this -- a 2x3 transform, decomposed or not, is refused by _transforms)
+    T = _transforms(init_transform)
+    r = refine_alignment_batch(optical, thermal, [0], [bins], T, regularize, normalized_mi, smoothing_sigma)
+    return r['transform'][0], bool(r['success'][0])
+
+
+def check_perspective_transformation(*args, **kwargs):
+    raise NotImplementedError('the geometric checks of check_perspective_transformation (rotation and translation limits) '
+                              'decompose the homography with cv2.decomposeHomographyMat, which has no restatement in this '
+                              'project; align_images applies the mutual-information check only')
+
+
+def alignment_type_name(bins, normalized_mi, smoothing_sigma):
+    """wrapper_refine_alignement's name of a perspective alignment (align.py:249-259)."""
+    return 'bin' + str(bins) + ('_normalized' if normalized_mi else '') + '_s' + str(smoothing_sigma)
+
+
+def rank_candidates(scores, method):
+    """Index of the best candidate from scores[candidate][bin size] (negative mutual information: smaller is better),
+    align.py:568-594 as written: 'sum' adds a candidate's scores; 'order' adds, per bin size, the argsort() of the
+    candidates' scores -- the indices that would sort them, not the candidates' ranks -- and takes the smallest total."""
+    s = np.asarray(scores, np.float64)
+    if s.ndim != 2 or s.shape[0] < 1:
+        raise ValueError('scores must be (candidates, bin sizes)')
+    if method == 'sum':
+        total = np.zeros(s.shape[0])
+        for k in range(s.shape[1]):
+            total = total + s[:, k]
+        return int(np.argmin(total))
+    if method == 'order':
+        ranking = np.zeros(s.shape[0])
+        for k in range(s.shape[1]):
+            ranking += s[:, k].argsort(kind='stable')
+        return int(np.argmin(ranking))
+    raise ValueError('Unknown ranking_method')
+
+
+def align_images(optical, thermal, init_transform, params, geometric_checks=False):
+    """The reference's align_images (align.py:446-613) for B pairs at once: every bin size of every pair is one Nelder-Mead
+    problem of one batch; a result is a candidate when the solver succeeded and the mutual information at 100 bins moved
+    by less than alignment/check/both/max_diff_mi (and, with alignment/check/invalid_pixels, no border pixel entered the
+    frame); the initial transform is a candidate with alignment/accept_init; every candidate is scored under every bin size in
+    one objective call and ranked by alignment/ranking_method.
+
+    optical (Ho, Wo) or (B, 1, Ho, Wo), thermal (H, W) or (B, 1, H, W), init_transform (3, 3) or (B, 3, 3).
+    geometric_checks=True asks for the rotation / translation limits of check_perspective_transformation as well, which are
+    not implemented: it raises NotImplementedError (the default applies the mutual-information check only).
+    Returns (transform, type, candidates) for one pair, lists of them for a batch; transform and type are None where no
+    candidate is valid.  A candidate is dict(type, transform, mi={bins: score}, value, init_value, nit, nfev)."""
+    if geometric_checks:
+        check_perspective_transformation()
+    if params.get('alignment/decomposed_transformation', False):
+        raise NotImplementedError('alignment/decomposed_transformation: ' + _AFFINE)
+    single = optical.dim() == 2
+    opt, th = _frames(optical, 'optical'), _frames(thermal, 'thermal')
+    B = opt.shape[0]
+    T0 = np.broadcast_to(_transforms(init_transform), (B, 9)) if _transforms(init_transform).shape[0] == 1 \
+        else _transforms(init_transform)
+    if T0.shape[0] != B:
+        raise ValueError('one initial transform, or one per pair')
+    sizes = [int(b) for b in params['alignment/bin_sizes']]
+    normalized = bool(params.get('alignment/normalized_mi', False))
+    sigma = params.get('alignment/smoothing_sigma', 0)
+    cands = [[] for _ in range(B)]
+    if params.get('alignment/accept_init', False):
+        for b in range(B):
+            cands[b].append({'type': 'init', 'transform': T0[b].reshape(3, 3).copy()})
+    if params.get('alignment/run_optimization', True) and sizes:
+        pair = [b for b in range(B) for _ in sizes]
+        r = refine_alignment_batch(opt, th, pair, sizes * B, T0[pair], False, normalized, sigma)
+        # the check of check_perspective_transformation that needs no decomposition: |MI(init) - MI(new)| at 100 bins
+        P = len(pair)
+        both = np.concatenate([T0[pair], r['transform'].reshape(P, 9)])
+        mi100 = _objective(opt, th, pair * 2, [100] * (2 * P), both, None, normalized, sigma).cpu().numpy()
+        own = _objective(opt, th, pair, sizes * B, T0[pair], None, normalized, sigma).cpu().numpy()
+        inside = np.ones(P, bool)
+        if params.get('alignment/check/invalid_pixels', False):
+            _, mm, _ = joint_histograms(opt, th, pair, [1] * P, r['transform'])
+            inside = mm[:, 0].cpu().numpy() != -1.0
+        for q in range(P):
+            valid = abs(mi100[q] - mi100[P + q]) < params['alignment/check/both/max_diff_mi'] and inside[q]
+            if valid and r['success'][q]:
+                cands[pair[q]].append({'type': alignment_type_name(sizes[q % len(sizes)], normalized, sigma),
+                                       'transform': r['transform'][q].copy(), 'value': float(r['value'][q]),
+                                       'init_value': float(own[q]), 'nit': int(r['nit'][q]), 'nfev': int(r['nfev'][q])})
+    # the ranking scores are the plain negative mutual information, as align.py:531-535 and :551-555 call it
+    flat = [(b, c) for b in range(B) for c in cands[b]]
+    if flat and sizes:
+        pair = [b for b, _ in flat for _ in sizes]
+        Ts = np.stack([c['transform'].reshape(9) for _, c in flat for _ in sizes])
+        sc = _objective(opt, th, pair, sizes * len(flat), Ts, None, False, 0).cpu().numpy().reshape(len(flat), len(sizes))
+        for (_, c), row in zip(flat, sc):
+            c['mi'] = {n: float(v) for n, v in zip(sizes, row)}
+    best_T, best_type = [], []
+    for b in range(B):
+        if not cands[b]:
+            best_T.append(None); best_type.append(None)
+            continue
+        i = rank_candidates([[c['mi'][n] for n in sizes] for c in cands[b]], params.get('alignment/ranking_method', 'sum'))
+        best_T.append(cands[b][i]['transform']); best_type.append(cands[b][i]['type'])
+    if single:
+        return best_T[0], best_type[0], cands[0]
+    return best_T, best_type, cands

@@ -41,6 +41,10 @@ def build_parser():
     parser.add_argument('--save-npz', default=None, help='(extension) write keypoints/descriptors/matches of the sample here')
     parser.add_argument('--refine', action='store_true', help='(extension) re-match under the first homography estimate and '
                         'polish it (utils.refine_alignment); the aligned image uses the refined estimate')
+    parser.add_argument('--mi', action='store_true', help='(extension) print the negative normalised mutual information at 100 bins of '
+                        'the pair under the identity, the estimated and (with --refine) the refined homography')
+    parser.add_argument('--mi-refine', action='store_true', help='(extension) maximise the mutual information from the estimated '
+                        'homography (utils.alignment.align_images; yaml block prediction.mi_alignment) and print the result')
     return parser
 
 
@@ -103,6 +107,48 @@ def refine_estimate(kp_optical, kp_thermal, desc_optical, desc_thermal, matches,
     print('Refined Homography:')
     print(H_ref)
     return H_ref
+
+
+MI_ALIGNMENT_DEFAULTS = {'alignment/bin_sizes': [16, 32, 64, 100, 256], 'alignment/normalized_mi': True,
+                         'alignment/smoothing_sigma': 0, 'alignment/check/both/max_diff_mi': 0.5, 'alignment/accept_init': True,
+                         'alignment/ranking_method': 'order'}
+# (the values of the reference's config_align_images.yaml, except alignment/check/invalid_pixels, which is left off on purpose:
+# an estimated homography usually brings border pixels into the frame, and that check would reject every refinement of it)
+
+
+def estimate_to_transform(H_est):
+    """The homography estimated here maps optical pixels to thermal ones (cv2.warpPerspective(optical, H_est) inverts it);
+    the `transform` of utils.alignment maps thermal (destination) pixels to optical (source) ones, as the reference's align.py
+    does: its inverse.  A singular estimate becomes the identity."""
+    H_est = np.asarray(H_est, np.float64)
+    if abs(np.linalg.det(H_est)) < 1e-12:
+        return np.eye(3)
+    return np.linalg.inv(H_est)
+
+
+def mi_report(optical, thermal, named):
+    """--mi: the negative normalised mutual information at 100 bins under each (name, optical -> thermal homography)."""
+    from multipoint_amd.utils import alignment
+    T = np.stack([estimate_to_transform(H) for _, H in named])
+    v = alignment.negative_mutual_information_batch(optical, thermal, T[None], 100, normalized_mi=True)[0].cpu().numpy()
+    print('Negative normalised MI (100 bins): ' + ', '.join('{} {:.6f}'.format(n, x) for (n, _), x in zip(named, v)))
+
+
+def mi_refine(optical, thermal, H_est, pred):
+    """--mi-refine: utils.alignment.align_images from the estimate.  Prints the winning candidate's type, its negative
+    normalised mutual information at 100 bins and its matrix in the direction of the estimate (optical -> thermal)."""
+    from multipoint_amd.utils import alignment
+    params = dict(MI_ALIGNMENT_DEFAULTS, **(pred.get('mi_alignment') or {}))
+    T, kind, _ = alignment.align_images(optical[0, 0], thermal[0, 0], estimate_to_transform(H_est), params)
+    if T is None:
+        print('MI alignment: none (no valid candidate)')
+        return None
+    v = alignment.calculate_negative_mutual_information(T, optical[0, 0], thermal[0, 0], T, 100, normalized_mi=True)
+    print('MI alignment: {} negative normalised MI (100 bins) {:.6f}'.format(kind, v))
+    H_mi = estimate_to_transform(T)
+    print('MI-aligned Homography:')
+    print(H_mi)
+    return H_mi
 
 
 def main(argv=None):
@@ -177,7 +223,7 @@ def main(argv=None):
         print('Two forward passes took: {} s'.format(t_2 - t_1))
         print('Box nms: {} s'.format(t_3 - t_2))
 
-        if args.plot or args.save_npz or args.refine:
+        if args.plot or args.save_npz or args.refine or args.mi or args.mi_refine:
             H, W = data['optical']['image'].shape[2:]
             thr = pred['detection_threshold']
             pred_optical = torch.nonzero((out_optical['prob'][0].squeeze() > thr).float())
@@ -208,9 +254,15 @@ def main(argv=None):
             print('Estimated Homography:')
             print(H_est)
             print('RANSAC inliers: {} of {} matches'.format(int(np.sum(mask)), len(matches)))
+            H_first = H_est
             if args.refine:
                 H_est = refine_estimate(pred_optical, pred_thermal, desc_optical, desc_thermal, matches, mask, H, W, pred,
                                         H_est)
+            if args.mi:
+                mi_report(data['optical']['image'][:1], data['thermal']['image'][:1],
+                          [('identity', np.eye(3)), ('estimated', H_first)] + ([('refined', H_est)] if args.refine else []))
+            if args.mi_refine:
+                mi_refine(data['optical']['image'][:1], data['thermal']['image'][:1], H_est, pred)
             print('Ground Truth Homography:')
             print(H_gt)
             print('--------------------------------------------------------')
