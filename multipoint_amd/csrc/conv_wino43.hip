@@ -74,7 +74,8 @@ __device__ __forceinline__ void dma16(const float* sbase, unsigned voff_bytes, u
 // unit n + 2 are produced for the item's 18 x 34 patch by v_mfma_f32_4x4x1_16b_f32: 16 blocks of D[4 channels][4 pixels] +=
 // W[4][1] X[1][4] per instruction, nine taps = nine instructions per 64 pixels, the bias as the accumulator's initial value.  A
 // lane supplies ITS pixel's tap value (gathered from a 20 x 36 fp32 image patch in LDS whose rows and columns are staged
-// already reflected) and the weight of channel lane & 3, and receives the 4 channels of its own pixel -- exactly one raw
+// already reflected); the weights come from ONE register of all nine taps (lane 4 t + c: tap t, channel c), whose block t the MFMA
+// of tap t broadcasts as the A operand of every block (cbsz:4 abid:t); the lane receives the 4 channels of its own pixel -- exactly one raw
 // granule, written after ReLU / BatchNorm with one ds_write_b128.  Nothing of the block ever leaves the CU; the image patch of
 // item k + 2 arrives by 4-byte LDS-DMA during the epilogue of item k.
 // VIN (round 5: layers with MANY output slices -- the 3x3 head convolutions, 512 couts = 8 slices): the input arrives already
@@ -191,19 +192,12 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     };
     // the unit's 36 weight blocks of 1 KiB over the waves: wave w issues blocks [u_first, u_first + u_cnt), up to three per site (two
     // sites per unit).  No dummy loads: the unit barrier's vmcnt(2) / vmcnt(3) leaves the NEWEST two / three loads in flight -- the raw /
-    // V loads every wave issues in equal number behind its weight loads -- however many weight loads precede them.  Plain launches:
-    // 5 blocks on waves 0-3, 4 on waves 4-7.  F1: waves 0, 1 also produce the second raw block of every unit (612 patch pixels are 10
-    // blocks of 64 for 8 waves), so SIMDs 0, 1 (waves 0, 4 / 1, 5) issue 3 + 4 weight loads and SIMDs 2, 3 (waves 2, 6 / 3, 7) 6 + 5:
-    // an LDS-DMA costs ~50 cycles of its SIMD's issue next to the MFMA stream, the extra raw block ~170.
-    int u_first, u_cnt;
-    if constexpr (F1) {
-        constexpr int cnt_[8] = {3, 3, 6, 6, 4, 4, 5, 5}, first_[8] = {0, 3, 14, 20, 6, 10, 26, 31};
-        u_cnt = 3; u_first = 0;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) { u_cnt = wave == w ? cnt_[w] : u_cnt; u_first = wave == w ? first_[w] : u_first; }
-    } else {
-        u_cnt = wave < 4 ? 5 : 4; u_first = wave < 4 ? 5 * wave : 20 + 4 * (wave - 4);
-    }
+    // V loads every wave issues in equal number behind its weight loads -- however many weight loads precede them.
+    // 5 blocks on waves 0-3, 4 on waves 4-7.  F1 as well: waves 0, 1 also produce the second raw block of every unit (612 patch pixels
+    // are 10 blocks of 64 for 8 waves), but with the unit's weights and bias shared between the blocks and its taps resident that block
+    // is nine small MFMAs and a store -- no longer worth a skewed split (until round 8 it cost ~170 cycles against ~50 per LDS-DMA, and
+    // the shares were 3, 3, 6, 6, 4, 4, 5, 5; five splits measured in profiles/r08_first_block_lds.txt).
+    const int u_cnt = wave < 4 ? 5 : 4, u_first = wave < 4 ? 5 * wave : 20 + 4 * (wave - 4);
     // site 0: blocks k = 0..2 of this wave, site 1: k = 3..5 (wave-uniform branches)
     auto u_dma_site = [&](const float* ub, int buf, int site) __attribute__((always_inline)) {
         if constexpr (VIN) {
@@ -230,14 +224,17 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     auto load_prm = [&](int vslice) __attribute__((always_inline)) {
         const int slice = SPLIT ? vslice >> p.ks_shift : vslice;
         if (tid < 64) {
-            const float sc = p.scale[slice * 64 + tid];
-            prm[tid] = p.bias[slice * 64 + tid]; prm[128 + tid] = p.shift[slice * 64 + tid];
+            int t = tid;
+            // (F1: the LDS address of prm[tid] is not worth a register across the unit loop, which has none to spare)
+            if constexpr (F1) asm volatile("" : "+v"(t));
+            const float sc = p.scale[slice * 64 + t];
+            prm[t] = p.bias[slice * 64 + t]; prm[128 + t] = p.shift[slice * 64 + t];
             if constexpr (POOL && !SPLIT) {
                 const bool neg = sc < 0.f;
-                prm[64 + tid] = fabsf(sc); prm[192 + tid] = neg ? -1.f : 1.f;
-                prm[256 + tid] = __int_as_float(neg ? (int)0x80000000 : 0); prm[320 + tid] = __int_as_float(neg ? 0 : 0x7fffffff);
+                prm[64 + t] = fabsf(sc); prm[192 + t] = neg ? -1.f : 1.f;
+                prm[256 + t] = __int_as_float(neg ? (int)0x80000000 : 0); prm[320 + t] = __int_as_float(neg ? 0 : 0x7fffffff);
             } else {
-                prm[64 + tid] = sc;
+                prm[64 + t] = sc;
             }
         }
     };
@@ -318,13 +315,13 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     // ---- F1: the first encoder block, produced per unit into the raw ring ----
     // LDS: the raw ring needs only TWO buffers here (nothing is in flight from memory); the third buffer's 10 KiB hold two image
     // patches (item k's and item k+1's: 20 x 36 fp32, rows / columns already reflected) and the block's bias per unit (its BatchNorm is folded away at load time);
-    // w1s holds the weights as [unit][tap][channel of the unit].
+    // w1u holds the weights as [unit][lane of the broadcast register: 4 * tap + channel of the unit].
     constexpr int IW1 = PX + 2, IH1 = PY + 2;                 // image patch: the receptive field of the 18 x 34 raw patch
     constexpr int IPB = 768;                                  // floats per patch buffer (IH1 * IW1 = 720, rounded up to whole 64-lane DMA blocks)
-    static_assert(!F1 || (IH1 * IW1 <= IPB && 2 * IPB + 16 * 4 + 16 * 4 * 12 <= RB4), "F1: patches + parameters + weights must fit the third raw buffer");
+    static_assert(!F1 || (IH1 * IW1 <= IPB && 2 * IPB + 16 * 4 + 16 * 48 <= RB4), "F1: patches + parameters + weights must fit the third raw buffer");
     const unsigned ip_lds = raw_lds + 2u * RB4 * 4u;          // ipatch[2][IPB]
     const unsigned bst_lds = ip_lds + 2u * IPB * 4u;          // bst[16][bias4] (the block's BatchNorm is folded away at load time)
-    const unsigned w1_lds = bst_lds + 16u * 4u * 4u;         // w1u[16 units][4 channels][12: taps 0..8, 3 unused]
+    const unsigned w1_lds = bst_lds + 16u * 4u * 4u;         // w1u[16 units][48: lane 4 * tap + channel, taps 0..8; 12 unused (zero)]
     typedef const __attribute__((address_space(3))) float* lds_f32_ptr;
     typedef const __attribute__((address_space(3))) f32x4* lds_f32x4_ptr;
     typedef __attribute__((address_space(3))) f32x4* lds_f32x4_wptr;
@@ -359,7 +356,11 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             if (wave * 64 + 512 * j >= IH1 * IW1) continue;       // (wave-uniform)
-            const int q = min(tid + 512 * j, IH1 * IW1 - 1);
+            int q = tid + 512 * j;
+            // (recomputed per item: hoisted out of the item loop, row and column of both blocks are four registers held across the
+            // unit loop, which has none to spare)
+            asm volatile("" : "+v"(q));
+            q = min(q, IH1 * IW1 - 1);
             const int r = q / IW1, c = q - r * IW1;
             const unsigned off = (unsigned)(reflect_clamp(w.y0 - 2 + r, p.H) * p.W + reflect_clamp(w.x0 - 2 + c, p.W)) * 4u;
             lds_dma<1, 0, 0>(im, off, ip_lds + (unsigned)(par * IPB + wave * 64 + 512 * j) * 4u);
@@ -367,54 +368,74 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     };
     // the cursor: unit pc_unit of item pc_item is what the next produce() makes; LDS byte addresses of its weights / parameters
     int pc_unit = 0, pc_next_item = item + stride;
-    unsigned pc_wv = w1_lds + (unsigned)(lane & 3) * 48u;     // w1u[unit][lane & 3][0..11]
+    unsigned pc_wv = w1_lds + (unsigned)min(lane, 47) * 4u;   // w1u[unit][lane] (lanes 36.. read the zero padding; nothing selects them)
     unsigned pc_bv = bst_lds;                                 // bst[unit * 4]
     // 64 pixels x 4 channels of the cursor's unit -> raw buffer at byte wbuf: nine rank-1 MFMAs on the lane's own pixel.  In steps, so
     // that the unit body can thread them through the gaps of its own MFMA stream (the nine small MFMAs depend on each other):
-    //   step 0: issue the reads (9 taps of the pixel, 9 weights, the bias as the accumulator's initial value)
-    //   steps 1..9: one v_mfma_f32_4x4x1_16b_f32 each; step 8 also fetches the BatchNorm terms
-    //   step 10: ReLU / BatchNorm and the 16-byte store
-    // The nine tap values of a pixel are the same for all 16 units of an item: block 0's (every wave) stay in registers (px_, loaded
-    // when the cursor enters an item); the second block of waves 0, 1 gathers them per unit.
-    float px_[9];
-    f32x4 pw_[3], pd_;
+    //   step 0: issue the reads (the unit's weights, the bias as the accumulator's initial value)
+    //   steps 1..9: one v_mfma_f32_4x4x1_16b_f32 each
+    //   step 10: ReLU and the 16-byte store
+    // The weights do not depend on the pixel: ONE register holds all nine taps of the unit's four channels (lane 4 t + c: tap t, channel
+    // c -- the A operand of the instruction's block t), and tap t's MFMA broadcasts block t's A operand to all 16 blocks (cbsz:4
+    // abid:t).  One ds_read_b32 of consecutive dwords per unit instead of three ds_read_b128 of a 12-register row per channel.
+    // The nine tap values of a pixel are the same for all 16 units of an item: they stay in registers, loaded when the cursor enters
+    // an item (px_: block 0, every wave; qx_: the second block of waves 0, 1, which shares the unit's weight register and bias).
+    float px_[9], qx_[9];
+    float pw_;
+    f32x4 pd_;
     auto gather_x = [&](float (&x)[9], const int j) __attribute__((always_inline)) {
         const lds_f32_ptr xp = reinterpret_cast<lds_f32_ptr>(pg_x[j]);
 #pragma unroll
         for (int t = 0; t < 9; ++t) x[t] = xp[(t / 3) * IW1 + (t % 3)];
     };
-    auto prod_step = [&](const int k, const unsigned wbuf, const int j, const float (&x)[9]) __attribute__((always_inline)) {
-        const lds_f32x4_ptr wp = reinterpret_cast<lds_f32x4_ptr>(pc_wv);
-        const lds_f32x4_ptr bp = reinterpret_cast<lds_f32x4_ptr>(pc_bv);
+    // tap t of a block: D[channel][pixel] = C + W[channel] X[pixel] with block t's W for every block (the broadcast selector is an
+    // immediate of the instruction)
+    auto tap_mfma = [&](const int t, const float x, const f32x4 c) __attribute__((always_inline)) -> f32x4 {
+        switch (t) {
+        case 0: return __builtin_amdgcn_mfma_f32_4x4x1f32(pw_, x, c, 4, 0, 0);
+        case 1: return __builtin_amdgcn_mfma_f32_4x4x1f32(pw_, x, c, 4, 1, 0);
+        case 2: return __builtin_amdgcn_mfma_f32_4x4x1f32(pw_, x, c, 4, 2, 0);
+        case 3: return __builtin_amdgcn_mfma_f32_4x4x1f32(pw_, x, c, 4, 3, 0);
+        case 4: return __builtin_amdgcn_mfma_f32_4x4x1f32(pw_, x, c, 4, 4, 0);
+        case 5: return __builtin_amdgcn_mfma_f32_4x4x1f32(pw_, x, c, 4, 5, 0);
+        case 6: return __builtin_amdgcn_mfma_f32_4x4x1f32(pw_, x, c, 4, 6, 0);
+        case 7: return __builtin_amdgcn_mfma_f32_4x4x1f32(pw_, x, c, 4, 7, 0);
+        default: return __builtin_amdgcn_mfma_f32_4x4x1f32(pw_, x, c, 4, 8, 0);
+        }
+    };
+    auto prod_step = [&](const int k, const unsigned wbuf) __attribute__((always_inline)) {
         if (k == 0) {
-            pd_ = bp[0];
-            pw_[0] = wp[0]; pw_[1] = wp[1]; pw_[2] = wp[2];
+            pd_ = reinterpret_cast<lds_f32x4_ptr>(pc_bv)[0];
+            pw_ = reinterpret_cast<lds_f32_ptr>(pc_wv)[0];
         } else if (k <= 9) {
-            pd_ = __builtin_amdgcn_mfma_f32_4x4x1f32(pw_[(k - 1) >> 2][(k - 1) & 3], x[k - 1], pd_, 0, 0, 0);
+            pd_ = tap_mfma(k - 1, px_[k - 1], pd_);
         } else {
             // ReLU only: the block's BatchNorm was folded at load time -- into p.w1 / p.b1 for conv -> BN -> ReLU models, into this
             // layer's U and bias otherwise (model_load.hip build_encoder) -- which takes two packed multiply-adds and two LDS reads per
             // 64 pixels and unit out of the unit body
             const f32x4 v = {relu_bits(pd_[0]), relu_bits(pd_[1]), relu_bits(pd_[2]), relu_bits(pd_[3])};
-            *reinterpret_cast<lds_f32x4_wptr>(raw_lds + wbuf + pg_w[j]) = v;
+            *reinterpret_cast<lds_f32x4_wptr>(raw_lds + wbuf + pg_w[0]) = v;
         }
     };
-    auto produce = [&](const unsigned wbuf, const int j) __attribute__((always_inline)) {       // all steps at once
-        if (j == 0) {
+    // the second block of waves 0, 1 as one piece, between step 0 and step 1 of block 0: pw_ holds the unit's weights, pd_ still the bias
+    auto produce2 = [&](const unsigned wbuf) __attribute__((always_inline)) {
+        f32x4 d = tap_mfma(0, qx_[0], pd_);
 #pragma unroll
-            for (int k = 0; k <= 10; ++k) prod_step(k, wbuf, 0, px_);
-        } else {
-            float qx[9];
-            gather_x(qx, 1);
+        for (int t = 1; t < 9; ++t) d = tap_mfma(t, qx_[t], d);
+        const f32x4 v = {relu_bits(d[0]), relu_bits(d[1]), relu_bits(d[2]), relu_bits(d[3])};
+        *reinterpret_cast<lds_f32x4_wptr>(raw_lds + wbuf + pg_w[1]) = v;
+    };
+    auto produce = [&](const unsigned wbuf) __attribute__((always_inline)) {       // a whole unit at once (prologue)
+        prod_step(0, wbuf);
+        if (wave + 8 < NRB) produce2(wbuf);
 #pragma unroll
-            for (int k = 0; k <= 10; ++k) prod_step(k, wbuf, 1, qx);
-        }
+        for (int k = 1; k <= 10; ++k) prod_step(k, wbuf);
     };
     auto prod_advance = [&]() __attribute__((always_inline)) {
-        pc_wv += 4u * 12u * 4u; pc_bv += 4u * 4u;
+        pc_wv += 48u * 4u; pc_bv += 4u * 4u;
         if (++pc_unit == NC) {
             pc_unit = 0;
-            pc_wv -= (unsigned)NC * 4u * 12u * 4u; pc_bv -= (unsigned)NC * 4u * 4u;
+            pc_wv -= (unsigned)NC * 48u * 4u; pc_bv -= (unsigned)NC * 4u * 4u;
             if (pc_next_item < item_end) {
                 const Where w = decode(pc_next_item);
                 pc_par ^= 1;
@@ -424,6 +445,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
                     pg_x[0] += flip; pg_x[1] += flip;
                 }
                 gather_x(px_, 0);                                 // (the patch landed and was fenced by a unit barrier long ago)
+                if (wave + 8 < NRB) gather_x(qx_, 1);
                 pc_next_item += stride;
             }
         }
@@ -456,9 +478,9 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     // ---- prologue ----
     Where cur = decode(item);
     if constexpr (F1) {
-        for (int f = tid; f < 16 * 4 * 12; f += 512) {            // w1u[unit][channel of the unit][tap] <- p.w1 [tap][64]
-            const int ch = f / 12, t = f - ch * 12;
-            (raw + 2 * RB4 + 2 * IPB + 16 * 4)[f] = t < 9 ? p.w1[t * 64 + ch] : 0.f;
+        for (int f = tid; f < 16 * 48; f += 512) {                // w1u[unit][4 * tap + channel of the unit] <- p.w1 [tap][64]
+            const int u = f / 48, l = f - u * 48;
+            (raw + 2 * RB4 + 2 * IPB + 16 * 4)[f] = l < 36 ? p.w1[(l >> 2) * 64 + 4 * u + (l & 3)] : 0.f;
         }
         if (tid < 64) (raw + 2 * RB4 + 2 * IPB)[tid] = p.b1[tid];       // bst[unit][4]: the bias = the accumulators' initial value
         patch_dma(cur, 0);
@@ -467,9 +489,10 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
         dma_wait();
         __syncthreads();                                          // patches, weights and parameters visible
         gather_x(px_, 0);
-        produce(0u, 0); if (wave + 8 < NRB) produce(0u, 1);       // raw(0) -> buffer 0
+        if (wave + 8 < NRB) gather_x(qx_, 1);
+        produce(0u);                                              // raw(0) -> buffer 0
         prod_advance();
-        produce(RB4 * 4u, 0); if (wave + 8 < NRB) produce(RB4 * 4u, 1);       // raw(1) -> buffer 1
+        produce(RB4 * 4u);                                        // raw(1) -> buffer 1
         prod_advance();
     }
     const float* rbase = (F1 || VIN) ? p.in : raw_offsets(cur);
@@ -556,17 +579,17 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
             if (at(7)) tf_pass2w(vb ^ 1, 2);
         };
         // F1: the production of raw(n+2) (prod_step) in the slots the transform leaves free, one small MFMA per slot; the second
-        // block of waves 0, 1 (granules 512..611) as one piece in front of them
+        // block of waves 0, 1 (granules 512..611) as one piece behind step 0, whose weight register and bias it shares
         auto prod_at = [&](const int g, const int e, const int vb) __attribute__((always_inline)) {
             const unsigned wbuf = (unsigned)vb * (RB4 * 4u);
             // (round 6: the second block at group 1 / 3 / 5 instead of 0: +-0 / +1.7 % / +1.6 %; one production step per group or all of them
             // early: +-0 / +0.9 % -- profiles/r06_transform_schedules.txt)
             constexpr int slot_g[11] = {0, 0, 1, 1, 1, 2, 3, 4, 4, 4, 5};
-            constexpr int slot_e[11] = {1, 3, 1, 2, 3, 1, 3, 1, 2, 3, 1};
-            if (g == 0 && e == 0) { if (wave + 8 < NRB) produce(wbuf, 1); }
+            constexpr int slot_e[11] = {0, 3, 1, 2, 3, 1, 3, 1, 2, 3, 1};
 #pragma unroll
             for (int k = 0; k <= 10; ++k)
-                if (g == slot_g[k] && e == slot_e[k]) prod_step(k, wbuf, 0, px_);
+                if (g == slot_g[k] && e == slot_e[k]) prod_step(k, wbuf);
+            if (g == 0 && e == 0) { if (wave + 8 < NRB) produce2(wbuf); }
         };
         // the 36 MFMAs of a unit and everything that rides in their shadow: one basic block
         auto unit_body = [&](const int c, auto first_tag, auto vb_tag, auto vs_tag) __attribute__((always_inline)) {
