@@ -184,7 +184,8 @@ int mp_extract_keypoints(mp_handle* h, const float* map, const unsigned char* va
                          int K, int* kp_yx, float* kp_score, int* kp_count, void* stream);
 
 /* replaces utils.interpolate_descriptors (multipoint/utils/utils.py:159-167).
- *   desc [B][Hc][Wc][D] channels-last, out [B][K][D]; rows k >= kp_count[b] are written as zeros. */
+ *   desc [B][Hc][Wc][D] channels-last, D a multiple of 64 up to 384, out [B][K][D]; rows k >= kp_count[b] are written as
+ *   zeros. */
 int mp_sample_descriptors(mp_handle* h, const float* desc, int B, int Hc, int Wc, int D, int H, int W,
                           const int* kp_yx, const int* kp_count, int K, float* out, void* stream);
 
@@ -194,7 +195,7 @@ int mp_sample_descriptors(mp_handle* h, const float* desc, int B, int Hc, int Wc
  *   countA/countB: int32, pair p at [p * count_stride]
  *   threshold < 0 disables the distance test (plain mutual NN == crossCheck)
  *   match_idx [P][K]: train index of query i or -1; match_dist [P][K]; match_count [P]
- *   0 < P <= 65535 (all four matchers: a pair is a row of the launch grid), K > 0, D must be 64, 128 or 256 */
+ *   0 < P <= 65535 (all four matchers: a pair is a row of the launch grid), K > 0, D must be 64, 128, 256 or 384 (LGHD) */
 int mp_match_mutual_nn(mp_handle* h, const float* descA, const int* countA, const float* descB,
                        const int* countB, long long pair_stride, int count_stride, int P, int K,
                        int D, float threshold, int* match_idx, float* match_dist, int* match_count,
@@ -238,7 +239,7 @@ int mp_find_homography(mp_handle* h, const int* kp_yx, const int* kp_count, cons
                        unsigned char* inlier_mask, int* n_inliers, void* stream);
 
 /* the other modes of utils.get_matches (multipoint/utils/matching.py:4-33); same descriptor / count addressing as
- * mp_match_mutual_nn, 1 <= D <= 256.
+ * mp_match_mutual_nn, 1 <= D <= 384.
  * mp_match_knn2 replaces cv2.BFMatcher(cv2.NORM_L2).knnMatch(d1, d2, 2) (:21, followed by Lowe's ratio test :23-27)
  * and .match() without crossCheck (:7,31): nn_idx / nn_dist [P][K][2] = the two nearest train rows of every query
  * row under ||a - b||_2 (ties: lower train index first), idx -1 where the pair has fewer than 1 / 2 train rows.
@@ -256,7 +257,7 @@ int mp_match_threshold(mp_handle* h, const float* descA, const int* countA, cons
  * the two nearest per query); same descriptor / count addressing and the same [P][K] outputs as mp_match_mutual_nn, so
  * mp_find_homography and the per-pair records take them unchanged.  Rows are taken as UNIT vectors (what
  * mp_sample_descriptors always produces): the metric is sqrt(2 - 2 clip(a.b, -1, 1)), which for unit rows equals the
- * L2 distance; for arbitrary rows use mp_match_knn2.  D must be 64, 128 or 256.
+ * L2 distance; for arbitrary rows use mp_match_knn2.  D must be 64, 128, 256 or 384.
  *   ratio <= 0  replaces cv2.BFMatcher(cv2.NORM_L2).match() without crossCheck (matching.py:7,31): every query row of
  *               a pair with at least one train row is matched to its nearest (ties: the lower train index).
  *   ratio > 0   replaces knnMatch(d1, d2, 2) plus Lowe's ratio test (matching.py:20-27): query i keeps its nearest iff
@@ -569,6 +570,43 @@ int mp_mi_refine_begin(mp_handle* h, const float* optical, int Ho, int Wo, const
 int mp_mi_refine_step(mp_handle* h, void* workspace, int n_iters, int* live, void* stream);
 int mp_mi_refine_result(mp_handle* h, void* workspace, double* transforms, double* values, int* iterations,
                         int* function_calls, int* success, void* stream);
+
+/* ---- 2-D FFT and the LGHD baseline (multipoint/models/ClassicDetectors.py, class LGHD) ----
+ * Line lengths are 2^a 3^b 5^c in [8, 4096] (mp_fft_supported); complex arrays are interleaved fp32 (re, im).
+ *
+ * mp_fft2d: unnormalised DFT of `planes` frames of H x W complex values along the rows (axes 1, length W), the columns
+ * (axes 2, length H) or both (3); inverse != 0 conjugates the kernel (no 1 / N).  in == out is allowed.
+ * MP_EINVAL: a transformed length outside the supported set, planes outside [1, 65535]. */
+int mp_fft_supported(int n);
+int mp_fft2d(mp_handle* h, const float* in, float* out, int planes, int H, int W, int inverse, int axes, void* stream);
+
+/* u8[i] = (uint8)(image[i] * 255.0f): the reference's (image * 255.0).astype(np.uint8), one fp32 multiply then truncation */
+int mp_lghd_quantize(mp_handle* h, const float* image, unsigned char* u8, long long n, void* stream);
+
+/* FAST-9/16, threshold 10, with non-maximum suppression.  Circle (dx, dy): (0,3) (1,3) (2,2) (3,1) (3,0) (3,-1) (2,-2) (1,-3)
+ * (0,-3) (-1,-3) (-2,-2) (-3,-1) (-3,0) (-3,1) (-2,2) (-1,3); only 3 <= y <= H-4, 3 <= x <= W-4 are tested.
+ *   score    u8 [B][H][W]: the largest t for which 9 contiguous circle pixels (wrapping) are all > p + t or all < p - t,
+ *            0 where that is below 10
+ *   corners  u8 [B][H][W]: 1 where score > 0 and strictly above the scores of all 8 neighbours
+ *   prob     fp32 [B][H][W] or NULL: 1.0 at corners with 20 <= y <= H-20 and 20 <= x <= W-20 (the descriptor's patch lies
+ *            inside the frame), 0 elsewhere */
+int mp_lghd_detect(mp_handle* h, const unsigned char* u8, int B, int H, int W, unsigned char* score, unsigned char* corners,
+                   float* prob, void* stream);
+
+/* orientation u8 [B][4][H][W]: for scale sc the first o in [0, 6) that maximises |ifft2(fft2(u8) * bank[sc * 6 + o])|.
+ * bank fp32 [24][H][W] (real, in FFT order).  The workspace holds the spectrum and the 24 half-transformed planes of as many
+ * images as fit (at least one): mp_lghd_workspace_bytes sizes it for min(B, 4).
+ * MP_EINVAL: H or W outside the FFT's lengths, B outside [1, 65535], a workspace smaller than one image needs. */
+int mp_lghd_workspace_bytes(int B, int H, int W, long long* bytes);
+int mp_lghd_orientation(mp_handle* h, const unsigned char* u8, const float* bank, int B, int H, int W,
+                        unsigned char* orientation, void* workspace, long long workspace_bytes, void* stream);
+
+/* The 384 patch-histogram counts of every keypoint: rows [y-20, y+20) x columns [x-20, x+20) of the four orientation planes in
+ * 4 x 4 cells of 10 x 10 pixels, laid out [scale][cell row][cell col][orientation].  kp_yx int32 [B][K][2], kp_count int32 [B];
+ * raw fp32 [B][K][384] exact counts, unit the same rows L2-normalised; either may be NULL.  Rows beyond kp_count, and keypoints
+ * whose patch leaves the frame, are zero. */
+int mp_lghd_describe(mp_handle* h, const unsigned char* orientation, int B, int H, int W, const int* kp_yx, const int* kp_count,
+                     int K, float* raw, float* unit, void* stream);
 
 /* per-launch timing of mp_forward with hipEvents on the caller's stream (bench.py roofline leg).
  * mp_profile_read synchronises; names[i] points to static strings. */

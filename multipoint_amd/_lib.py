@@ -143,6 +143,14 @@ SIGNATURES = {
                                    c_void_p, c_int, ctypes.c_double, c_int, c_int, c_void_p, c_ll, c_void_p]),
     'mp_mi_refine_step': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'mp_mi_refine_result': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'mp_fft_supported': (c_int, [c_int]),
+    'mp_fft2d': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'mp_lghd_quantize': (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
+    'mp_lghd_detect': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'mp_lghd_workspace_bytes': (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
+    'mp_lghd_orientation': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_ll, c_void_p]),
+    'mp_lghd_describe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                 c_void_p]),
     'mp_profile_enable': (c_int, [c_void_p, c_int]),
     'mp_profile_read': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_float),
                                 ctypes.POINTER(ctypes.c_double), c_int, ctypes.POINTER(c_int)]),

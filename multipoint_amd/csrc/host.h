@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -143,6 +144,7 @@ struct mp_handle {
     mp_host::DevBuf f16_dummy;      // scratch line for masked-off store lanes of the fp16 kernels
     int* pinned = nullptr;          // small pinned host scratch (img lists, counters)
     mp_host::MiRefine mi;           // the running mutual-information refinement (mp_mi_refine_*)
+    std::map<int, mp_host::DevBuf> fft_tw;     // FFT twiddle tables by line length (lghd_api.hip)
     bool prof = false;
     bool head_fallback_noted = false;
     std::vector<mp_host::ProfEntry> prof_entries;

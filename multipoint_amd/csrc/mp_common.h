@@ -509,3 +509,22 @@ void launch_mi_nm_begin(MiNmState* state, const MiNmOptions* opt, const double* 
 void launch_mi_nm_decide(MiNmState* state, int P, double* cand, const double* values, int* nact, int* live, hipStream_t s);
 void launch_mi_nm_result(const MiNmState* state, int P, double* T, double* value, int* iterations, int* fcalls, int* success,
                          hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
+// 2-D FFT (fft.hip) and the LGHD baseline (lghd.hip; reference multipoint/models/ClassicDetectors.py, class LGHD).
+// Complex arrays are interleaved fp32 (re, im).  tw_rows / tw_cols: the tables fft_twiddles() fills for W and H, on the device.
+// ---------------------------------------------------------------------------------------------
+void fft_twiddles(int n, float* table);       // host: table [n][2] = exp(-2 pi i t / n), computed in double and rounded once
+// axes: 1 rows (length W), 2 columns (length H), 3 both; in == out allowed
+void launch_fft2d(const float* in, float* out, int planes, int H, int W, int inverse, int axes, const float* tw_rows,
+                  const float* tw_cols, hipStream_t s);
+// orientation u8 [nb][4][H][W]; spectrum: nb complex frames, tmp: nb * 24 complex frames
+void launch_lghd_orientation(const unsigned char* u8, const float* bank, int nb, int H, int W, float* spectrum, float* tmp,
+                             unsigned char* orientation, const float* tw_rows, const float* tw_cols, hipStream_t s);
+void launch_lghd_quantize(const float* image, unsigned char* u8, long long n, hipStream_t s);
+// score / corners u8 [B][H][W], prob fp32 [B][H][W] or NULL
+void launch_lghd_detect(const unsigned char* u8, int B, int H, int W, unsigned char* score, unsigned char* corners, float* prob,
+                        hipStream_t s);
+// raw / unit fp32 [B][K][384], either may be NULL
+void launch_lghd_describe(const unsigned char* ori, int B, int H, int W, const int* kp_yx, const int* kp_count, int K, float* raw,
+                          float* unit, hipStream_t s);

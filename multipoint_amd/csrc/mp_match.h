@@ -91,8 +91,8 @@ struct NoGate {
 // lane's half-wave, half = lane >> 5, sees the columns with (col & 4) == 4 * half.  Called by all 256 threads of the
 // workgroup: a wave without rows (returns false) still stages tiles and meets the barriers.
 template <int D, class Keep, class Gate = NoGate>
-__device__ __forceinline__ bool walk_tiles(const float* __restrict__ X, const float* __restrict__ Y, int nx, int ny,
-                                           int c_begin, int c_end, int r0, int li, int half, Keep& keep, Gate gate = Gate())
+__device__ __forceinline__ bool walk_tiles_whole(const float* __restrict__ X, const float* __restrict__ Y, int nx, int ny,
+                                                 int c_begin, int c_end, int r0, int li, int half, Keep& keep, Gate gate = Gate())
 {
     constexpr int RS = D + 4;                            // LDS row stride in floats
     __shared__ __attribute__((aligned(16))) float ytile[2][32 * RS];
@@ -155,6 +155,89 @@ __device__ __forceinline__ bool walk_tiles(const float* __restrict__ X, const fl
     return active;
 }
 
+// The same walk for rows wider than 256 floats, where neither a double-buffered tile of whole rows (2 x 32 x (D + 4) floats) fits
+// the 64 KiB of static LDS nor the X row (D / 2 registers per lane) the register file next to the staging registers: D is walked
+// in slices of 128 floats.  A step is (tile, slice); the steps are staged one ahead through the two LDS buffers exactly as the
+// tiles are above, the lane re-reads its X row's slice at every step (L1 / L2 hits), and the 16 accumulators simply continue
+// across the slices of a tile -- the products are added in ascending k, as for the other widths.  The gate's data belongs to a
+// TILE: it is fetched with slice 0 of the tile and lies in the gate's buffer tile & 1.
+template <int D, class Keep, class Gate = NoGate>
+__device__ __forceinline__ bool walk_tiles_sliced(const float* __restrict__ X, const float* __restrict__ Y, int nx, int ny,
+                                                  int c_begin, int c_end, int r0, int li, int half, Keep& keep, Gate gate = Gate())
+{
+    constexpr int SL = 128, NS = D / SL, RS = SL + 4;
+    static_assert(D % SL == 0, "sliced walk: D must be a multiple of 128");
+    __shared__ __attribute__((aligned(16))) float yslice[2][32 * RS];
+    const int tid = threadIdx.x;
+    const bool active = r0 < nx;
+    const float* xrow = X + (long long)min(r0 + li, nx - 1) * D + half * 4;
+    constexpr int NG = SL / 8, GPT = SL / 32, GPR = SL / 4;
+    f32x4 stage[GPT];
+    auto gload = [&](int c0, int sl) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < GPT; ++k) {
+            const int gran = tid + k * 256;
+            const int row = gran / GPR, q = gran - row * GPR;
+            stage[k] = *reinterpret_cast<const f32x4*>(Y + (long long)min(c0 + row, ny - 1) * D + sl * SL + q * 4);
+        }
+    };
+    auto lstore = [&](int buf) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < GPT; ++k) {
+            const int gran = tid + k * 256;
+            const int row = gran / GPR, q = gran - row * GPR;
+            *reinterpret_cast<f32x4*>(&yslice[buf][row * RS + q * 4]) = stage[k];
+        }
+    };
+    if (c_begin < c_end) { gload(c_begin, 0); gate.fetch(c_begin, ny); lstore(0); gate.stash(0); }
+    __syncthreads();
+    int buf = 0;
+    for (int c0 = c_begin, tb = 0; c0 < c_end; c0 += 32, tb ^= 1) {
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int sl = 0; sl < NS; ++sl, buf ^= 1) {
+            const bool last = sl == NS - 1;
+            const bool more = !last || c0 + 32 < c_end;
+            if (more) {                                             // the next step, in flight across this one's MFMAs
+                if (last) { gload(c0 + 32, 0); gate.fetch(c0 + 32, ny); }
+                else gload(c0, sl + 1);
+            }
+            f32x4 a[NG];
+#pragma unroll
+            for (int g = 0; g < NG; ++g) a[g] = *reinterpret_cast<const f32x4*>(xrow + sl * SL + g * 8);
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                const f32x4 bv = *reinterpret_cast<const f32x4*>(&yslice[buf][li * RS + g * 8 + half * 4]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[e], a[g][e], acc, 0, 0, 0);
+            }
+            if (last && active) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int slot = (r & 3) + 8 * (r >> 2) + 4 * half, col = c0 + slot;
+                    const float t = fminf(fmaxf(acc[r], -1.f), 1.f);
+                    keep.offer(2.f - 2.f * t, col, col < ny && gate.pass(tb, slot));
+                }
+            }
+            if (more) { lstore(buf ^ 1); if (last) gate.stash(tb ^ 1); }      // last read one barrier ago
+            __syncthreads();
+        }
+    }
+    return active;
+}
+
+// walk_tiles<D>: whole rows up to 256 floats, slices above
+template <int D, class Keep, class Gate = NoGate>
+__device__ __forceinline__ bool walk_tiles(const float* __restrict__ X, const float* __restrict__ Y, int nx, int ny,
+                                           int c_begin, int c_end, int r0, int li, int half, Keep& keep, Gate gate = Gate())
+{
+    if constexpr (D > 256) return walk_tiles_sliced<D>(X, Y, nx, ny, c_begin, c_end, r0, li, half, keep, gate);
+    else return walk_tiles_whole<D>(X, Y, nx, ny, c_begin, c_end, r0, li, half, keep, gate);
+}
+
 // ---- what the epilogue kernels and the launches of match_mfma.hip and match_guided.hip share ----
 
 // the N smallest keys (k2 is untouched for N = 1) of row `at` over the column shares' arrays, which lie [share][pair][K][N]
@@ -204,5 +287,6 @@ void for_width(int D, Launch launch)
 {
     if (D == 64) launch(std::integral_constant<int, 64>{});
     else if (D == 128) launch(std::integral_constant<int, 128>{});
-    else launch(std::integral_constant<int, 256>{});
+    else if (D == 256) launch(std::integral_constant<int, 256>{});
+    else launch(std::integral_constant<int, 384>{});
 }

@@ -202,22 +202,22 @@ int mp_sample_descriptors(mp_handle* h, const float* desc, int B, int Hc, int Wc
 {
     if (!h) return MP_EINVAL;
     if (!desc || !kp_yx || !kp_count || !out) return fail(h, MP_EINVAL, "mp_sample_descriptors: NULL tensor");
-    if (D % 64 != 0 || D > 256 || D <= 0)
-        return fail(h, MP_EINVAL, "mp_sample_descriptors: D must be 64, 128, 192 or 256");
+    if (D % 64 != 0 || D > 384 || D <= 0)
+        return fail(h, MP_EINVAL, "mp_sample_descriptors: D must be a multiple of 64 up to 384");
     MP_HIP(hipSetDevice(h->device));
     launch_sample_desc(desc, B, Hc, Wc, D, H, W, kp_yx, kp_count, K, out, static_cast<hipStream_t>(stream));
     return launch_status(h);
 }
 
 // what the four matchers share: tensors, the grid's pair bound (gridDim.y = P) and the descriptor width -- the MFMA row kernels
-// exist for three widths, the scalar route of match_extra.hip takes any up to 256
+// exist for four widths, the scalar route of match_extra.hip takes any up to 384
 static int match_check(mp_handle* h, const char* fn, const void* a, const void* b, const void* c, const void* d,
                        int P, int K, int D, bool mfma_rows)
 {
     if (!a || !b || !c || !d) return fail(h, MP_EINVAL, std::string(fn) + ": NULL tensor");
     if (P <= 0 || P > 65535 || K <= 0) return fail(h, MP_EINVAL, std::string(fn) + ": need 0 < P <= 65535, K > 0");
-    if (mfma_rows ? (D != 64 && D != 128 && D != 256) : (D <= 0 || D > 256))
-        return fail(h, MP_EINVAL, std::string(fn) + (mfma_rows ? ": D must be 64, 128 or 256" : ": D must be in [1, 256]"));
+    if (mfma_rows ? (D != 64 && D != 128 && D != 256 && D != 384) : (D <= 0 || D > 384))
+        return fail(h, MP_EINVAL, std::string(fn) + (mfma_rows ? ": D must be 64, 128, 256 or 384" : ": D must be in [1, 384]"));
     return MP_OK;
 }
 

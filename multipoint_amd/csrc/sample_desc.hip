@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void sample_desc_kernel(const float* __restric
     const bool vx0 = x0 >= 0 && x0 < Wc, vx1 = x1 >= 0 && x1 < Wc;
     const float* base = desc + (long long)b * Hc * Wc * D;
     float ss = 0.f;
-    float vals[4];                      // D <= 256
+    float vals[6];                      // D <= 384
     const int nrep = D >> 6;
     for (int r = 0; r < nrep; ++r) {
         const int c = r * 64 + lane;

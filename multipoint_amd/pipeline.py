@@ -175,7 +175,7 @@ class PairPipeline:
                 if t is not None:
                     t.record_stream(fwd)
             post.wait_stream(fwd)      # (a forward the caller enqueues next on ITS stream is ordered behind this one by the model itself)
-            for t in (out['prob'], out['desc'], valid_mask):
+            for t in (out['prob'], out.get('desc'), out.get('orientation'), valid_mask):
                 if t is not None:
                     t.record_stream(post)
         else:
@@ -215,7 +215,12 @@ class PairPipeline:
         if mark is not None:
             mark()                  # keypoint lists done (stage timing)
         K = kp.shape[1]
-        desc = U.interpolate_descriptors_batched(kp, cnt, out['desc'], H, W)        # [B,K,D]
+        if 'orientation' in out:
+            # ClassicDetectors: the patch histograms of the keypoints straight from the orientation maps -- what sampling the
+            # reference's dense map yields, without the map
+            desc = self.net.describe(out, kp, cnt)                                  # [B,K,384]
+        else:
+            desc = U.interpolate_descriptors_batched(kp, cnt, out['desc'], H, W)        # [B,K,D]
         # the interleaved list read in place: slot 2p against slot 2p + 1
         lay = dict(pair_stride=2 * K * desc.shape[2], count_stride=2)
         if self.match_mode == 'mutual':
@@ -251,7 +256,7 @@ class PairPipeline:
         out = self.net(data)
         res = self._settle(self._post(out, valid_mask, dev, B, H, W), out, valid_mask, dev, B, H, W)
         self.tie_redone = 0
-        if self.tie_robust and self.nms > 0:
+        if self.tie_robust and self.nms > 0 and 'orientation' not in out:      # (ClassicDetectors: no convolution algorithm to switch)
             # tie guards (include/multipoint_hip.h), evaluated on the CONVERGED pass -- the flags of the latest detect call, i.e. of
             # the lists `res` holds: images whose top-k cut fell inside a plateau of scores tied within the default convolution
             # algorithm's rounding noise (or whose NMS decided many such near-ties, whatever `topk`) are re-evaluated ONCE with the
@@ -266,7 +271,7 @@ class PairPipeline:
                 U.topk_ambiguous(dev, B)                         # (the redone lists flag the same plateaus again: read and drop)
         self._last = res
         if self.keep_maps:
-            res.prob, res.desc_map = out['prob'], out['desc']
+            res.prob, res.desc_map = out['prob'], out.get('desc')
         return res
 
     def _settle(self, res, out, valid_mask, dev, B, H, W):

@@ -75,7 +75,7 @@ def match_pairs(descA, countA, descB, countB, threshold=-1.0, pair_stride=None, 
 
 
 def nearest_pairs(descA, countA, descB, countB, ratio=None, return_second=False, pair_stride=None, count_stride=1):
-    """One-directional matching for P independent pairs on the GPU (mp_match_nearest; unit rows, D in {64, 128, 256}).
+    """One-directional matching for P independent pairs on the GPU (mp_match_nearest; unit rows, D in {64, 128, 256, 384}).
     `ratio=None`: every query row is matched to its nearest train row (BFMatcher.match without crossCheck);
     `ratio=r`: kept iff distance < r * second distance (knnMatch(.., 2) + Lowe's ratio test; get_matches uses 0.9).
     Returns (match_idx [P,K] int32 (-1 = none), match_dist [P,K] f32, match_count [P] int32), with `return_second`

@@ -81,7 +81,7 @@ def refine_estimate(kp_optical, kp_thermal, desc_optical, desc_thermal, matches,
     if not crosscheck:
         raise ValueError('--refine starts from mutual matches: prediction.matching must be nnmatcher, or bfmatcher with crossCheck')
     before = 'Refinement: {} inliers of {} matches'.format(int(np.sum(mask)), len(matches))
-    if no == 0 or nt == 0 or D not in (64, 128, 256) or max(no, nt) > utils.MAX_RANSAC_MATCHES:
+    if no == 0 or nt == 0 or D not in (64, 128, 256, 384) or max(no, nt) > utils.MAX_RANSAC_MATCHES:
         print(before + ' -> unchanged (nothing to refine at these list sizes)')
         return H_est
     K = max(no, nt)
