@@ -571,6 +571,33 @@ int mp_mi_refine_step(mp_handle* h, void* workspace, int n_iters, int* live, voi
 int mp_mi_refine_result(mp_handle* h, void* workspace, double* transforms, double* values, int* iterations,
                         int* function_calls, int* success, void* stream);
 
+/* ---- image pyramid of the staged alignment (create_dataset/align_images.py:163-171, helper_functions/align.py:485-489;
+ * DESIGN.md 3.8.3) ----
+ * mp_gaussian_blur: cv2.GaussianBlur(frame, (ksize, ksize), 0) of n fp32 frames in [n][H][W], the float path of sepFilter2D:
+ *   weights  getGaussianKernel(ksize, 0, CV_32F): for ksize 1, 3, 5, 7 the fixed tables [1], [.25 .5 .25],
+ *            [.0625 .25 .375 .25 .0625], [.03125 .109375 .21875 .28125 .21875 .109375 .03125]; above that
+ *            sigma = 0.3 ((ksize - 1) / 2 - 1) + 0.8, exp in double, stored as float, normalised by the double sum
+ *   rows     sum over the taps from left to right, w[0] x[-r] first
+ *   columns  w[r] S[0], then w[r + j] (S[+j] + S[-j]) for j = 1 .. r
+ *   border   BORDER_REFLECT_101; every product and sum is rounded to fp32 (no FMA)
+ * decimate 0: out [n][H][W].  decimate != 0: out [n][(H + 1) / 2][(W + 1) / 2], the even rows and columns of that result bit
+ * for bit (the reference's [::2, ::2]); only those pixels are computed.  No workspace; in and out must not overlap.
+ * MP_EINVAL: a NULL tensor, in == out, an even ksize or one outside [1, 31], ksize / 2 >= min(H, W), n outside [1, 65535],
+ * H or W outside [1, 32767].
+ * mp_gaussian_weights writes the ksize weights (host memory; needs no device); MP_EINVAL for a ksize as above or NULL. */
+int mp_gaussian_weights(int ksize, float* weights);
+int mp_gaussian_blur(mp_handle* h, const float* in, int n, int H, int W, int ksize, int decimate, float* out, void* stream);
+
+/* 8- and 16-bit frames as the reference turns them into fp32 (align.py:485, align_images.py:161): out fp32 [n][H][W] from
+ *   MP_FRAMES_U8    uint8 [n][H][W]:      v / 255.0f
+ *   MP_FRAMES_BGR8  uint8 [n][H][W][3]:   each channel / 255.0f, then COLOR_BGR2GRAY (0.114f B + 0.587f G) + 0.299f R
+ *   MP_FRAMES_U16   uint16 [n][H][W]:     v / 65535.0f
+ * MP_EINVAL: a NULL tensor, another mode, n outside [1, 65535], H or W outside [1, 32767]. */
+#define MP_FRAMES_U8 0
+#define MP_FRAMES_BGR8 1
+#define MP_FRAMES_U16 2
+int mp_frames_to_float(mp_handle* h, const void* in, int mode, int n, int H, int W, float* out, void* stream);
+
 /* ---- 2-D FFT and the LGHD baseline (multipoint/models/ClassicDetectors.py, class LGHD) ----
  * Line lengths are 2^a 3^b 5^c in [8, 4096] (mp_fft_supported); complex arrays are interleaved fp32 (re, im).
  *

@@ -59,6 +59,7 @@ class MiProblem(ctypes.Structure):
 
 
 MP_MI_SLOTS = 10
+MP_FRAMES_U8, MP_FRAMES_BGR8, MP_FRAMES_U16 = 0, 1, 2
 
 # name -> (restype, argtypes); every symbol declared in include/multipoint_hip.h
 SIGNATURES = {
@@ -143,6 +144,9 @@ SIGNATURES = {
                                    c_void_p, c_int, ctypes.c_double, c_int, c_int, c_void_p, c_ll, c_void_p]),
     'mp_mi_refine_step': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'mp_mi_refine_result': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'mp_gaussian_weights': (c_int, [c_int, ctypes.POINTER(c_float)]),
+    'mp_gaussian_blur': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'mp_frames_to_float': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'mp_fft_supported': (c_int, [c_int]),
     'mp_fft2d': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'mp_lghd_quantize': (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),

@@ -7,6 +7,12 @@ thermal (destination) pixel coordinates to optical (source) ones, exactly as in 
 as float64 numpy arrays.  negative_mutual_information_batch, refine_alignment_batch and the batched align_images have no
 counterpart in the reference.
 
+The staged procedure of the reference's create_dataset/align_images.py (ImageAligner.align_images_mutual_information, lines
+151-248) is align_images_mutual_information: an image pyramid from gaussian_blur (csrc/pyramid.hip), an optional stage on
+blurred frames and the full-resolution stage, for one pair or a batch that moves through the stages in lockstep.  The
+reference pyramids the uint8 BGR optical image (OpenCV's fixed-point 8-bit blur) and converts every level to grey; here the
+fp32 grey frame is pyramided.  Both are linear: only the 8-bit rounding of each level differs.
+
 Import this module as multipoint_amd.utils.alignment: its refine_alignment is NOT the guided refine_alignment that
 multipoint_amd.utils exports.
 
@@ -23,7 +29,9 @@ from .. import _lib
 
 __all__ = ['warp_image', 'mutual_information_2d', 'calculate_negative_mutual_information', 'refine_alignment',
            'negative_mutual_information_batch', 'refine_alignment_batch', 'align_images', 'joint_histograms',
-           'rank_candidates', 'check_perspective_transformation', 'alignment_type_name']
+           'rank_candidates', 'check_perspective_transformation', 'alignment_type_name', 'gaussian_blur', 'frames_to_float',
+           'gaussian_weights', 'pyramid_levels', 'scale_transform', 'run_alignment_stages',
+           'align_images_mutual_information']
 
 _AFFINE = ('2x3 affine transforms are not implemented: cv2.warpAffine is a different fixed-point path than '
            'cv2.warpPerspective and has no restatement in this project')
@@ -299,7 +307,66 @@ def rank_candidates(scores, method):
     raise ValueError('Unknown ranking_method')
 
 
-def align_images(optical, thermal, init_transform, params, geometric_checks=False):
+def gaussian_weights(ksize):
+    """getGaussianKernel(ksize, 0, CV_32F) as the library's blur uses it: float32 numpy (ksize,).  Needs no GPU."""
+    w = (ctypes.c_float * 31)()
+    if _lib.load_library().mp_gaussian_weights(int(ksize), w) != _lib.MP_OK:
+        raise ValueError('ksize must be odd and in [1, 31], got %s' % (ksize,))
+    return np.array(w[:int(ksize)], np.float32)
+
+
+def gaussian_blur(frames, ksize, decimate=False):
+    """cv2.GaussianBlur(frame, (ksize, ksize), 0) of fp32 CUDA frames (H, W), (B, H, W) or (B, 1, H, W): the float path of
+    sepFilter2D with BORDER_REFLECT_101, bit for bit (include/multipoint_hip.h states the arithmetic).  decimate=True returns
+    the blurred frames' [::2, ::2] -- (H + 1) // 2 x (W + 1) // 2 -- and computes only those pixels.  Returns a new tensor of
+    the input's rank.  ValueError: an even ksize or one outside [1, 31], ksize // 2 >= min(H, W)."""
+    x = _frames(frames, 'frames')
+    B, H, W = x.shape
+    shape = (B, (H + 1) // 2, (W + 1) // 2) if decimate else (B, H, W)
+    out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    h = _lib.get_handle(x.device)
+    h.check(h.lib.mp_gaussian_blur(h.ptr, _lib.ptr(x), B, H, W, int(ksize), int(bool(decimate)), _lib.ptr(out),
+                                   _lib.stream_ptr(x.device)))
+    if frames.dim() == 2:
+        return out[0]
+    return out[:, None] if frames.dim() == 4 else out
+
+
+def frames_to_float(frames, device=None, single_bgr=False):
+    """8- and 16-bit frames as the reference turns them into fp32: uint8 (B, H, W) -> / 255 (align.py:485 for a grey frame),
+    uint8 BGR (B, H, W, 3) -> / 255, then cv2.COLOR_BGR2GRAY, uint16 (B, H, W) -> / 65535 (align_images.py:161).  frames: a
+    numpy array or a CUDA tensor; one grey frame may come as (H, W); a 3-D uint8 array is a batch of grey frames unless
+    single_bgr says it is ONE (H, W, 3) BGR frame.  Returns a (B, H, W) fp32 CUDA tensor, (H, W) for one frame."""
+    if isinstance(frames, np.ndarray):
+        a = np.ascontiguousarray(frames)
+        if a.dtype == np.uint16:
+            x = torch.from_numpy(a.view(np.int16)).to(_lib.require_cuda(device)).view(torch.uint16)
+        elif a.dtype == np.uint8:
+            x = torch.from_numpy(a).to(_lib.require_cuda(device))
+        else:
+            raise ValueError('frames must be uint8 or uint16, got %s' % a.dtype)
+    else:
+        x = frames
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise RuntimeError('frames must be a numpy array or a CUDA tensor (multipoint_amd computes on the GPU only)')
+        if x.dtype not in (torch.uint8, torch.uint16):
+            raise ValueError('frames must be uint8 or uint16, got %s' % x.dtype)
+        x = x.contiguous()
+    bgr = x.dtype == torch.uint8 and x.dim() >= 3 and x.shape[-1] == 3 and (x.dim() == 4 or single_bgr)
+    single = x.dim() == (3 if bgr else 2)
+    if single:
+        x = x[None]
+    if x.dim() != (4 if bgr else 3):
+        raise ValueError('frames must be (B, H, W), (B, H, W, 3) BGR or one frame of either, got %s' % (tuple(x.shape),))
+    mode = _lib.MP_FRAMES_U16 if x.dtype == torch.uint16 else _lib.MP_FRAMES_BGR8 if bgr else _lib.MP_FRAMES_U8
+    B, H, W = x.shape[:3]
+    out = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
+    h = _lib.get_handle(x.device)
+    h.check(h.lib.mp_frames_to_float(h.ptr, _lib.ptr(x), mode, B, H, W, _lib.ptr(out), _lib.stream_ptr(x.device)))
+    return out[0] if single else out
+
+
+def align_images(optical, thermal, init_transform, params, geometric_checks=False, filter_images=False, stats=None):
     """The reference's align_images (align.py:446-613) for B pairs at once: every bin size of every pair is one Nelder-Mead
     problem of one batch; a result is a candidate when the solver succeeded and the mutual information at 100 bins moved
     by less than alignment/check/both/max_diff_mi (and, with alignment/check/invalid_pixels, no border pixel entered the
@@ -309,14 +376,18 @@ def align_images(optical, thermal, init_transform, params, geometric_checks=Fals
     optical (Ho, Wo) or (B, 1, Ho, Wo), thermal (H, W) or (B, 1, H, W), init_transform (3, 3) or (B, 3, 3).
     geometric_checks=True asks for the rotation / translation limits of check_perspective_transformation as well, which are
     not implemented: it raises NotImplementedError (the default applies the mutual-information check only).
+    filter_images=True blurs both frames with gaussian_blur(., alignment/filter_size) first (align.py:487-489).
     Returns (transform, type, candidates) for one pair, lists of them for a batch; transform and type are None where no
-    candidate is valid.  A candidate is dict(type, transform, mi={bins: score}, value, init_value, nit, nfev)."""
+    candidate is valid.  A candidate is dict(type, transform, mi={bins: score}, value, init_value, nit, nfev).  stats: a dict
+    whose 'rounds' grows by the objective launches the optimisation enqueued (refine_alignment_batch)."""
     if geometric_checks:
         check_perspective_transformation()
     if params.get('alignment/decomposed_transformation', False):
         raise NotImplementedError('alignment/decomposed_transformation: ' + _AFFINE)
     single = optical.dim() == 2
     opt, th = _frames(optical, 'optical'), _frames(thermal, 'thermal')
+    if filter_images:
+        opt, th = gaussian_blur(opt, params['alignment/filter_size']), gaussian_blur(th, params['alignment/filter_size'])
     B = opt.shape[0]
     T0 = np.broadcast_to(_transforms(init_transform), (B, 9)) if _transforms(init_transform).shape[0] == 1 \
         else _transforms(init_transform)
@@ -332,6 +403,8 @@ def align_images(optical, thermal, init_transform, params, geometric_checks=Fals
     if params.get('alignment/run_optimization', True) and sizes:
         pair = [b for b in range(B) for _ in sizes]
         r = refine_alignment_batch(opt, th, pair, sizes * B, T0[pair], False, normalized, sigma)
+        if stats is not None:
+            stats['rounds'] = stats.get('rounds', 0) + r['rounds']
         # the check of check_perspective_transformation that needs no decomposition: |MI(init) - MI(new)| at 100 bins
         P = len(pair)
         both = np.concatenate([T0[pair], r['transform'].reshape(P, 9)])
@@ -365,3 +438,139 @@ def align_images(optical, thermal, init_transform, params, geometric_checks=Fals
     if single:
         return best_T[0], best_type[0], cands[0]
     return best_T, best_type, cands
+
+
+# ---- the staged procedure of create_dataset/align_images.py:151-248 ----
+def pyramid_levels(H, W, filter_size, n_levels):
+    """The pyramid align_images.py:163-171 builds from an H x W frame, in the order it is built (finest first): a list of
+    (height, width, ksize), level i (1-based) being the [::2, ::2] of level i - 1 blurred with ksize =
+    ceil(filter_size * 0.5 ** i), plus 1 if that is even.  The stages run the list backwards (coarsest first)."""
+    out, ratio = [], 1.0
+    for _ in range(int(n_levels)):
+        ratio *= 0.5
+        k = int(np.ceil(filter_size * ratio))
+        if k % 2 == 0:
+            k += 1
+        H, W = (H + 1) // 2, (W + 1) // 2
+        out.append((H, W, k))
+    return out
+
+
+def scale_transform(T, level_shape, full_shape, down):
+    """A full-size transform at a pyramid level's size (down=True) or back (down=False): the eight in-place multiplications
+    of align_images.py:178-186 / :199-205 as written, in their order -- ratio_x from the ROW counts, ratio_y from the column
+    counts.  For frames with even sides this is S T S^-1 with S = diag(r, r, 1).  Returns a new (3, 3) float64 array."""
+    T = np.array(T, np.float64).reshape(3, 3)
+    ratio_x = float(level_shape[0]) / float(full_shape[0])
+    ratio_y = float(level_shape[1]) / float(full_shape[1])
+    if down:
+        T[0, 1:] *= ratio_x
+        T[1:, 0] /= ratio_x
+        T[1, 0] *= ratio_y
+        T[1, 2] *= ratio_y
+        T[0, 1] /= ratio_y
+        T[2, 1] /= ratio_y
+    else:
+        T[0, 1:] /= ratio_x
+        T[1:, 0] *= ratio_x
+        T[1, 0] /= ratio_y
+        T[1, 2] /= ratio_y
+        T[0, 1] *= ratio_y
+        T[2, 1] *= ratio_y
+    return T
+
+
+def run_alignment_stages(optical, thermal, t_init, params, align, blur):
+    """The stage sequence of ImageAligner.align_images_mutual_information (align_images.py:151-248) for B pairs in lockstep,
+    over an injected aligner and blur (align_images and gaussian_blur on the GPU; the tests drive it with stand-ins):
+
+      align(optical, thermal, transforms (n, 3, 3), params, filter_images) -> (transforms, types, candidates), lists of n,
+          a transform None where the pair has no valid candidate
+      blur(frames, ksize, decimate) -> frames
+
+    optical, thermal: arrays or tensors (B, H, W) that a list of indices can select from; t_init (B, 3, 3).
+      pyramid    (use_image_pyramid) both frames blurred and decimated alignment/n_pyramid_levels times; coarsest level first,
+                 the full size excluded: the transform is scaled down from full size, aligned there and scaled back up; a pair
+                 that fails a level goes back to its t_init
+      smoothing  (use_smoothing_stage) one full-size call with filter_images=True; failure: back to t_init
+      final      the full-size call; a pair that fails it and did not start from its t_init is tried again from there -- one
+                 call over those pairs only
+    Every stage is ONE call of `align` with a start per pair.  Returns per pair (success, transform, type, candidates, stages);
+    stages lists dict(name, shape (of the optical frame), start, type, success) for each stage the pair went through: name
+    'pyramid<i>' (level i of pyramid_levels, 1 = half size), 'smoothing', 'final', 'retry'."""
+    if not params.get('perspective', True):
+        raise NotImplementedError('perspective: false -- ' + _AFFINE)
+    if params.get('alignment/decomposed_transformation', False):
+        raise NotImplementedError('alignment/decomposed_transformation: ' + _AFFINE)
+    T0 = np.array(t_init, np.float64).reshape(-1, 3, 3)
+    B = T0.shape[0]
+    if optical.shape[0] != B or thermal.shape[0] != B:
+        raise ValueError('one optical frame, thermal frame and initial transform per pair')
+    T = T0.copy()
+    success = np.ones(B, bool)
+    stages = [[] for _ in range(B)]
+    last = [(None, None, [])] * B
+    full = tuple(optical.shape[-2:])
+
+    def stage(name, opt, th, index, start, filter_images):
+        Ts, kinds, cands = align(opt, th, start, params, filter_images)
+        for j, b in enumerate(index):
+            stages[b].append({'name': name, 'shape': tuple(opt.shape[-2:]), 'start': start[j].copy(), 'type': kinds[j],
+                              'success': Ts[j] is not None})
+            last[b] = (Ts[j], kinds[j], cands[j])
+        return Ts
+
+    everyone = list(range(B))
+    if params.get('use_image_pyramid', False):
+        plan = pyramid_levels(full[0], full[1], params.get('alignment/filter_size', 5), params.get('alignment/n_pyramid_levels', 2))
+        levels = []
+        o, t = optical, thermal
+        for i, (_, _, k) in enumerate(plan):
+            o, t = blur(o, k, True), blur(t, k, True)
+            levels.insert(0, (i + 1, o, t))
+        for i, o, t in levels:
+            shape = tuple(o.shape[-2:])
+            start = np.stack([scale_transform(T[b], shape, full, True) for b in everyone])
+            Ts = stage('pyramid%d' % i, o, t, everyone, start, False)
+            for b in everyone:
+                success[b] = Ts[b] is not None
+                T[b] = scale_transform(Ts[b], shape, full, False) if success[b] else T0[b]
+    if params.get('use_smoothing_stage', False):
+        Ts = stage('smoothing', optical, thermal, everyone, T.copy(), True)
+        for b in everyone:
+            success[b] = Ts[b] is not None
+            if success[b]:
+                T[b] = Ts[b]
+    for b in everyone:
+        if not success[b]:
+            T[b] = T0[b]
+    from_init = [bool((T[b] == T0[b]).all()) for b in everyone]
+    Ts = stage('final', optical, thermal, everyone, T.copy(), False)
+    again = [b for b in everyone if Ts[b] is None and not from_init[b]]
+    if again:
+        stage('retry', optical[again], thermal[again], again, T0[again].copy(), False)
+    return [(last[b][0] is not None, last[b][0], last[b][1], last[b][2], stages[b]) for b in everyone]
+
+
+def align_images_mutual_information(optical, thermal, t_init, params, stats=None):
+    """ImageAligner.align_images_mutual_information (create_dataset/align_images.py:151-248) on fp32 grey frames, for one pair
+    -- optical (Ho, Wo), thermal (H, W), t_init (3, 3) -- or B pairs -- (B, 1, Ho, Wo) or (B, Ho, Wo), (B, 1, H, W) or (B, H, W),
+    t_init (3, 3) or (B, 3, 3): run_alignment_stages over align_images and gaussian_blur.  params: the reference's yaml keys --
+    use_image_pyramid, use_smoothing_stage (both default off), alignment/n_pyramid_levels (2), alignment/filter_size (5) and
+    what align_images reads; `perspective: false` and alignment/decomposed_transformation raise NotImplementedError;
+    alignment/use_multiprocess, alignment/optimization_timeout, show_results and verbose are accepted and ignored.
+    Returns (success, transform, type, candidates, stages) for one pair, a list of them for a batch; transform and type
+    are None without success.  stats: see align_images."""
+    single = optical.dim() == 2
+    opt, th = _frames(optical, 'optical'), _frames(thermal, 'thermal')
+    B = opt.shape[0]
+    T0 = _transforms(t_init)
+    if T0.shape[0] == 1:
+        T0 = np.broadcast_to(T0, (B, 9))
+    if T0.shape[0] != B or th.shape[0] != B:
+        raise ValueError('one initial transform, or one per pair')
+
+    def align(o, t, T, p, filter_images):
+        return align_images(o, t, T, p, filter_images=filter_images, stats=stats)
+    out = run_alignment_stages(opt, th, T0.reshape(B, 3, 3), params, align, gaussian_blur)
+    return out[0] if single else out

@@ -111,7 +111,8 @@ def refine_estimate(kp_optical, kp_thermal, desc_optical, desc_thermal, matches,
 
 MI_ALIGNMENT_DEFAULTS = {'alignment/bin_sizes': [16, 32, 64, 100, 256], 'alignment/normalized_mi': True,
                          'alignment/smoothing_sigma': 0, 'alignment/check/both/max_diff_mi': 0.5, 'alignment/accept_init': True,
-                         'alignment/ranking_method': 'order'}
+                         'alignment/ranking_method': 'order', 'use_image_pyramid': False, 'use_smoothing_stage': False,
+                         'alignment/n_pyramid_levels': 2, 'alignment/filter_size': 5}
 # (the values of the reference's config_align_images.yaml, except alignment/check/invalid_pixels, which is left off on purpose:
 # an estimated homography usually brings border pixels into the frame, and that check would reject every refinement of it)
 
@@ -135,11 +136,19 @@ def mi_report(optical, thermal, named):
 
 
 def mi_refine(optical, thermal, H_est, pred):
-    """--mi-refine: utils.alignment.align_images from the estimate.  Prints the winning candidate's type, its negative
-    normalised mutual information at 100 bins and its matrix in the direction of the estimate (optical -> thermal)."""
+    """--mi-refine: utils.alignment.align_images from the estimate -- with use_image_pyramid or use_smoothing_stage in the
+    yaml block the staged align_images_mutual_information, which prints one line per stage.  Prints the winning candidate's
+    type, its negative normalised mutual information at 100 bins and its matrix in the direction of the estimate (optical ->
+    thermal)."""
     from multipoint_amd.utils import alignment
     params = dict(MI_ALIGNMENT_DEFAULTS, **(pred.get('mi_alignment') or {}))
-    T, kind, _ = alignment.align_images(optical[0, 0], thermal[0, 0], estimate_to_transform(H_est), params)
+    if params['use_image_pyramid'] or params['use_smoothing_stage']:
+        _, T, kind, _, stages = alignment.align_images_mutual_information(optical[0, 0], thermal[0, 0],
+                                                                          estimate_to_transform(H_est), params)
+        for s in stages:
+            print('MI stage {} {}x{}: {}'.format(s['name'], s['shape'][0], s['shape'][1], s['type'] or 'failed'))
+    else:
+        T, kind, _ = alignment.align_images(optical[0, 0], thermal[0, 0], estimate_to_transform(H_est), params)
     if T is None:
         print('MI alignment: none (no valid candidate)')
         return None
