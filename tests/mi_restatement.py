@@ -27,15 +27,17 @@ def cv_invert3(M):
     return np.array(t, np.float64).reshape(3, 3)
 
 
-def warp_linear(src, Mi, height, width, border_value=-1.0):
-    """OpenCV's WarpPerspectiveInvoker + remapBilinear<float> for the already inverted matrix Mi (destination -> source):
-    coordinates in 1/32 px computed block-wise in float64 (block width from the DESTINATION size), four float32 taps weighted
-    left to right, taps outside the source read `border_value`."""
-    src = np.ascontiguousarray(src, dtype=np.float32)
-    Hs, Ws = src.shape
+def block_width(height, width):
+    """The width of WarpPerspectiveInvoker's blocks for a destination of height x width."""
+    return min(1024 // min(16, int(height)), int(width))
+
+
+def fixed_point(Mi, height, width, split=True):
+    """The source coordinates of every destination pixel in 1/32 px, (X, Y) as int64 (H, W), as WarpPerspectiveInvoker
+    computes them: the sum over the block start xb and the offset x - xb in float64.  split=False puts xb = 0 everywhere
+    (one block as wide as the frame), which is NOT OpenCV's arithmetic once the frame is wider than a block."""
     H, W = int(height), int(width)
-    bh0 = min(16, H)
-    bw0 = min(1024 // bh0, W)
+    bw0 = block_width(H, W) if split else W
     ys, xs = np.mgrid[0:H, 0:W]
     xb = ((xs // bw0) * bw0).astype(np.float64)
     x1 = xs.astype(np.float64) - xb
@@ -48,7 +50,16 @@ def warp_linear(src, Mi, height, width, border_value=-1.0):
         w = np.where(den != 0, 32.0 / den, 0.0)
         fX = np.clip((X0 + Mi[0, 0] * x1) * w, -2147483648.0, 2147483647.0)
         fY = np.clip((Y0 + Mi[1, 0] * x1) * w, -2147483648.0, 2147483647.0)
-    X, Y = np.rint(fX).astype(np.int64), np.rint(fY).astype(np.int64)
+    return np.rint(fX).astype(np.int64), np.rint(fY).astype(np.int64)
+
+
+def warp_linear(src, Mi, height, width, border_value=-1.0, split=True):
+    """OpenCV's WarpPerspectiveInvoker + remapBilinear<float> for the already inverted matrix Mi (destination -> source):
+    coordinates in 1/32 px computed block-wise in float64 (block width from the DESTINATION size), four float32 taps weighted
+    left to right, taps outside the source read `border_value`."""
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    Hs, Ws = src.shape
+    X, Y = fixed_point(Mi, height, width, split)
     sx, sy = np.clip(X >> 5, -32768, 32767), np.clip(Y >> 5, -32768, 32767)
     fx = ((X & 31).astype(np.float32) * np.float32(1.0 / 32)).astype(np.float32)
     fy = ((Y & 31).astype(np.float32) * np.float32(1.0 / 32)).astype(np.float32)
@@ -66,9 +77,9 @@ def warp_linear(src, Mi, height, width, border_value=-1.0):
     return out
 
 
-def warp_image(image, transform, height, width):
+def warp_image(image, transform, height, width, split=True):
     """align.py:13-50 for a 3x3 transform.  Both inverses are the closed-form one (the reference's first is np.linalg.inv)."""
-    return warp_linear(image, cv_invert3(cv_invert3(transform)), height, width, -1.0)
+    return warp_linear(image, cv_invert3(cv_invert3(transform)), height, width, -1.0, split)
 
 
 def bin_edges(v, n):
