@@ -71,7 +71,10 @@ def list_versions(model_dir):
 
 
 def validation_config(config):
-    """train.py:44-50: the dataset config with the validation file and labels."""
+    """train.py:44-50: the dataset config with the validation file and labels.  An on-the-fly SyntheticShapes block reads no
+    file (its samples and labels are generated): it passes through as it is."""
+    if config['dataset'].get('type') == 'SyntheticShapes' and config['dataset'].get('on-the-fly', True):
+        return copy.deepcopy(config['dataset'])
     validation = config.get('training', {}).get('validation', {})
     if validation.get('filename') is None:
         raise SystemExit('error: the config names no validation set: set training.validation.filename (and '

@@ -500,6 +500,60 @@ int mp_photometric_shade_mask(mp_handle* h, int n, int H, int W, const mp_photom
                               int n_ellipses, int op_index, int blurred, float* out, void* workspace,
                               long long workspace_bytes, void* stream);
 
+/* ---- synthetic shapes (multipoint/utils/draw_primitives.py, multipoint/datasets/SyntheticShapes.py) ----
+ * The host draws every random number of an image into a list of draw commands (multipoint_amd/utils/draw_primitives.py);
+ * mp_shapes_render replays the lists of n images on their fp32 canvases [n][H][W], command s of every image in the same
+ * launches, with OpenCV's integer drawing rules (LINE_8, 16.16 fixed point, spans clipped to the frame):
+ *   MP_SHAPES_THRESHOLD  canvas = u > t ? 1 : 0, u = fields[a[0]] (double, host noise) or hash(key, pixel) when a[0] < 0
+ *   MP_SHAPES_MEAN       mean[img] = the canvas mean, summed in double; stays on the device (colours resolve against it)
+ *   MP_SHAPES_BLOBS      circles a[0] .. a[0] + a[1] - 1 of the circle table, cv2.circle(..., -1) each: a pixel takes the
+ *                        colour of the highest-index circle that covers it; a[2] != 0: uncovered pixels take the command's
+ *                        colour (the fill below the blobs).  Circle i's colour is circle_colors[i] = (a, b).
+ *   MP_SHAPES_BOX_BLUR   cv2.blur(img, (a[0], a[0])): anchor a[0] / 2, BORDER_REFLECT_101 repeated, sums in double
+ *   MP_SHAPES_LINE       cv2.line((a[0], a[1]), (a[2], a[3]), thickness a[4])
+ *   MP_SHAPES_CONVEX     cv2.fillConvexPoly of vertices a[0] .. a[0] + a[1] - 1 of the vertex table
+ *   MP_SHAPES_POLY       cv2.fillPoly of one contour (same fields); a[2] != 0: the covered pixels are copied from the
+ *                        image's second canvas instead of taking a colour
+ *   MP_SHAPES_ELLIPSE    cv2.ellipse(centre (a[0], a[1]), axes (a[2], a[3]), angle a[4] degrees, 0, 360, colour, -1)
+ *   MP_SHAPES_RANDU      canvas = hash(key, pixel), uniform in [0, 1)
+ * target 0 is the image's canvas, 1 its second canvas (in the workspace; blobs / box blur only).
+ * A colour (a, b) with resolve != 0 is b when |u - mean[img]| < min_contrast and a otherwise; resolve == 0: a. */
+enum { MP_SHAPES_THRESHOLD = 0, MP_SHAPES_MEAN = 1, MP_SHAPES_BLOBS = 2, MP_SHAPES_BOX_BLUR = 3, MP_SHAPES_LINE = 4,
+       MP_SHAPES_CONVEX = 5, MP_SHAPES_POLY = 6, MP_SHAPES_ELLIPSE = 7, MP_SHAPES_RANDU = 8 };
+#define MP_SHAPES_MAX_VERTS 64      /* vertices of one polygon */
+#define MP_SHAPES_MAX_RADIUS 255    /* circle radius, line thickness */
+#define MP_SHAPES_MAX_BLOBS 15000   /* circles of one MP_SHAPES_BLOBS command (a tile's list holds them all) */
+#define MP_SHAPES_MAX_COORD 1048576 /* |coordinate| of a vertex, centre or end point */
+
+typedef struct mp_shapes_cmd {
+    int kind;                       /* MP_SHAPES_* */
+    int target;                     /* 0: canvas, 1: second canvas */
+    int a[6];                       /* per kind, see above */
+    int resolve;                    /* colour: 0 literal a, 1 resolved against the device mean */
+    int pad;
+    double u, col_a, col_b, min_contrast;
+    double t;                       /* threshold */
+    unsigned long long key;         /* device noise key (threshold with a[0] < 0, randu) */
+} mp_shapes_cmd;
+
+/* bytes of the caller-owned device workspace of mp_shapes_render / mp_shapes_finish for n images of H x W */
+int mp_shapes_workspace_bytes(int n, int H, int W, int n_cmds, int n_verts, int n_circles, long long* bytes);
+
+/* canvas device fp32 [n][H][W], read and written (a render may continue the canvases of an earlier one); mean device
+ * float64 [n], read and written likewise.  cmds host [cmd_offset[n]], image i owning cmds[cmd_offset[i] ..
+ * cmd_offset[i + 1]); verts host int32 [n_verts][2] (x, y); circles host int32 [n_circles][3] (x, y, radius);
+ * circle_colors host float64 [n_circles][2]; fields device float64 [n_fields][H][W]. */
+int mp_shapes_render(mp_handle* h, float* canvas, double* mean, int n, int H, int W, const mp_shapes_cmd* cmds,
+                     const int* cmd_offset, const int* verts, int n_verts, const int* circles, const double* circle_colors,
+                     int n_circles, const double* fields, int n_fields, void* workspace, long long workspace_bytes,
+                     void* stream);
+
+/* SyntheticShapes.py:131-144: cv2.GaussianBlur(canvas, (blur1[i], blur1[i]), 0), then with blur2[i] when it is not 0 (host
+ * int arrays [n], odd sizes <= MP_PHOTO_MAX_BLUR; the sepFilter2D restatement of the photometric shade, fp32), in place, then
+ * cv2.resize(..., (w, h), INTER_LINEAR) into out fp32 [n][h][w] (a plain copy when h x w is H x W). */
+int mp_shapes_finish(mp_handle* h, float* canvas, int n, int H, int W, const int* blur1, const int* blur2, float* out, int oh,
+                     int ow, void* workspace, long long workspace_bytes, void* stream);
+
 /* ---- mutual-information alignment (create_dataset/helper_functions/align.py:13-215) ----
  * An EVALUATION is (pair p, bin count n, transform T [9] double, mapping thermal pixels to optical ones):
  *   w   = cv2.warpPerspective(optical[p], inv(T), (W, H), borderValue=-1.0), INTER_LINEAR: the arithmetic of

@@ -53,6 +53,17 @@ class PhotometricPlan(ctypes.Structure):
     _fields_ = [('n_ops', c_int), ('noise_device', c_int), ('op', PhotometricOp * MP_PHOTO_MAX_OPS)]
 
 
+(MP_SHAPES_THRESHOLD, MP_SHAPES_MEAN, MP_SHAPES_BLOBS, MP_SHAPES_BOX_BLUR, MP_SHAPES_LINE, MP_SHAPES_CONVEX, MP_SHAPES_POLY,
+ MP_SHAPES_ELLIPSE, MP_SHAPES_RANDU) = range(9)
+MP_SHAPES_MAX_VERTS, MP_SHAPES_MAX_RADIUS, MP_SHAPES_MAX_BLOBS = 64, 255, 15000
+
+
+class ShapesCmd(ctypes.Structure):
+    _fields_ = [('kind', c_int), ('target', c_int), ('a', c_int * 6), ('resolve', c_int), ('pad', c_int),
+                ('u', ctypes.c_double), ('col_a', ctypes.c_double), ('col_b', ctypes.c_double),
+                ('min_contrast', ctypes.c_double), ('t', ctypes.c_double), ('key', ctypes.c_ulonglong)]
+
+
 class MiProblem(ctypes.Structure):
     _fields_ = [('pair', c_int), ('bins', c_int), ('maxiter', c_int), ('maxfun', c_int), ('xatol', ctypes.c_double),
                 ('fatol', ctypes.c_double)]
@@ -133,6 +144,11 @@ SIGNATURES = {
                                        c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_ll, c_void_p]),
     'mp_photometric_shade_mask': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(PhotometricPlan), c_void_p, c_int,
                                           c_int, c_int, c_void_p, c_void_p, c_ll, c_void_p]),
+    'mp_shapes_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
+    'mp_shapes_render': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(ShapesCmd), c_void_p,
+                                 c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_ll, c_void_p]),
+    'mp_shapes_finish': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                 c_void_p, c_ll, c_void_p]),
     'mp_mi_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
     'mp_mi_joint_histogram': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_int),
                                       ctypes.POINTER(c_int), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -466,6 +466,12 @@ size_t photometric_lds_bytes(const mp_photometric_plan* plans, int n, int H, int
 void launch_photometric(const float* in, float* out, int n, int H, int W, const mp_photometric_plan* plans,
                         const int* ellipses, int n_ellipses, const double* normal, const double* uniform, void* workspace,
                         hipStream_t s);
+// cv2.GaussianBlur(frame, (k, k), 0) of n fp32 frames in place with ksizes[img] (device array; 0: frame left alone), the
+// sepFilter2D restatement of the shade masks: weights [n][MP_PHOTO_MAX_BLUR] and tmp [n][H][W] are device scratch, kmax the
+// largest size (host); the caller checks gaussian_blur_lds_bytes(kmax, W) against the device limit
+size_t gaussian_blur_lds_bytes(int k, int W);
+void launch_gaussian_blur_frames(float* img, float* tmp, float* weights, const int* ksizes, int kmax, int n, int H, int W,
+                                 hipStream_t s);
 void launch_photometric_shade_mask(int n, int H, int W, const mp_photometric_plan* plans, const int* ellipses,
                                    int n_ellipses, int op_index, int blurred, float* out, void* workspace, hipStream_t s);
 

@@ -24,6 +24,12 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long z)
     return z ^ (z >> 31);
 }
 
+// a double in [0, 1) with 53 random bits per (key, counter), counter-based (photometric.hip, shapes.hip)
+__device__ __forceinline__ double hash_uniform(unsigned long long key, unsigned long long ctr)
+{
+    return (double)(mix64(key ^ mix64(ctr)) >> 11) * 0x1p-53;
+}
+
 // LDS-DMA: 64 lanes x DWORDS dwords from (uniform base + per-lane byte offset [+ OFF]) to LDS [lds_byte [+ M0ADD] [+ OFF] +
 // 4 DWORDS lane, ...).  The immediate OFF moves the source AND the LDS destination, M0ADD the destination only.  M0 is
 // compiler-reserved and not preserved around an asm statement: the statement sets it and restores it.

@@ -21,6 +21,7 @@
 // All pixel arithmetic follows numpy's float32 operation order with every step rounded (no contraction into FMA).
 #include "mp_common.h"
 #include "mp_device.h"
+#include "mp_raster.h"
 #include "../../include/multipoint_hip.h"
 
 #pragma clang fp contract(off)
@@ -30,23 +31,15 @@ static_assert(sizeof(mp_photometric_op) == 88 && sizeof(mp_photometric_plan) == 
 
 namespace {
 
-constexpr int XY_SHIFT = 16;
-constexpr long long XY_ONE = 1LL << XY_SHIFT;
+using namespace mp_raster;             // the 16.16 drawing rules shared with shapes.hip
 constexpr int MEAN_CHUNK = 8192;        // numpy's iterator buffer (np.getbufsize())
 constexpr int MEAN_LEAVES = 160;        // pairwise leaves of a chunk of <= 8192 (leaves hold >= 57 elements: 8192 -> 128)
 constexpr int MEAN_GROUP = 16;          // chunks whose leaves are summed in one parallel pass
 constexpr int FULL_LEAVES = 64;         // a chunk of 8192 halves evenly down to 64 leaves of 128: a balanced tree
-constexpr int MAX_VERTS = 80;           // ellipse2Poly with delta >= 5: at most 73 points
 constexpr int COL_TX = 16, COL_TY = 64; // column-filter tile (columns x output rows)
 constexpr int STACK = 64;               // pairwise-tree walk stacks (depth <= 7 for a chunk of 8192)
 
-// device noise: a double in [0, 1) with 53 random bits per (key, counter), counter-based (the same splitmix hash as
-// losses.hip's label noise); normals by Box-Muller from the counters 2p and 2p + 1
-__device__ __forceinline__ double hash_uniform(unsigned long long key, unsigned long long ctr)
-{
-    return (double)(mix64(key ^ mix64(ctr)) >> 11) * 0x1p-53;
-}
-
+// device noise: normals by Box-Muller from the counters 2p and 2p + 1 of hash_uniform (mp_device.h)
 __device__ __forceinline__ double hash_normal(unsigned long long key, unsigned long long p)
 {
     const double u1 = ((double)(mix64(key ^ mix64(2 * p)) >> 11) + 0.5) * 0x1p-53;     // (0, 1)
@@ -191,89 +184,6 @@ __global__ __launch_bounds__(256) void photo_mean_kernel(const float* const* cur
 // ---------------------------------------------------------------------------------------------
 // additive_shade: cv::ellipse fill + GaussianBlur
 // ---------------------------------------------------------------------------------------------
-// OpenCV's SinTable[d]: sin of d degrees with 7 decimals, as float
-__device__ __forceinline__ float sin_table(int d)
-{
-    return (float)(rint(sin((double)d * (3.141592653589793 / 180.0)) * 1e7) / 1e7);
-}
-
-__device__ __forceinline__ long long cv_round(double v) { return (long long)rint(v); }
-
-__device__ __forceinline__ void put_point(float* img, int H, int W, long long x, long long y)
-{
-    if (0 <= x && x < W && 0 <= y && y < H) img[y * (long long)W + x] = 1.f;
-}
-
-// clipLine(Size2l(W << 16, H << 16), p1, p2)
-__device__ bool clip_line(int W, int H, long long& x1, long long& y1, long long& x2, long long& y2)
-{
-    const long long right = ((long long)W << XY_SHIFT) - 1, bottom = ((long long)H << XY_SHIFT) - 1;
-    int c1 = (x1 < 0) + (x1 > right) * 2 + (y1 < 0) * 4 + (y1 > bottom) * 8;
-    int c2 = (x2 < 0) + (x2 > right) * 2 + (y2 < 0) * 4 + (y2 > bottom) * 8;
-    if ((c1 & c2) == 0 && (c1 | c2) != 0) {
-        long long a;
-        if (c1 & 12) {
-            a = c1 < 8 ? 0 : bottom;
-            x1 += (long long)((double)(a - y1) * (double)(x2 - x1) / (double)(y2 - y1));
-            y1 = a;
-            c1 = (x1 < 0) + (x1 > right) * 2;
-        }
-        if (c2 & 12) {
-            a = c2 < 8 ? 0 : bottom;
-            x2 += (long long)((double)(a - y2) * (double)(x2 - x1) / (double)(y2 - y1));
-            y2 = a;
-            c2 = (x2 < 0) + (x2 > right) * 2;
-        }
-        if ((c1 & c2) == 0 && (c1 | c2) != 0) {
-            if (c1) {
-                a = c1 == 1 ? 0 : right;
-                y1 += (long long)((double)(a - x1) * (double)(y2 - y1) / (double)(x2 - x1));
-                x1 = a;
-                c1 = 0;
-            }
-            if (c2) {
-                a = c2 == 1 ? 0 : right;
-                y2 += (long long)((double)(a - x2) * (double)(y2 - y1) / (double)(x2 - x1));
-                x2 = a;
-                c2 = 0;
-            }
-        }
-    }
-    return (c1 | c2) == 0;
-}
-
-// Line2: the LINE_8 segment between two 16.16 points
-__device__ void line2(float* img, int H, int W, long long x1, long long y1, long long x2, long long y2)
-{
-    if (!clip_line(W, H, x1, y1, x2, y2)) return;
-    long long dx = x2 - x1, dy = y2 - y1;
-    const long long j = dx < 0 ? -1 : 0, ax = (dx ^ j) - j;
-    const long long i = dy < 0 ? -1 : 0, ay = (dy ^ i) - i;
-    long long x_step = 0, y_step = 0;
-    long long ecount;
-    if (ax > ay) {
-        if (j) { long long t = x1; x1 = x2; x2 = t; t = y1; y1 = y2; y2 = t; }
-        dy = (dy ^ j) - j;
-        y_step = (dy * XY_ONE) / (ax | 1);
-        ecount = (x2 - x1) >> XY_SHIFT;
-    } else {
-        if (i) { long long t = x1; x1 = x2; x2 = t; t = y1; y1 = y2; y2 = t; }
-        dx = (dx ^ i) - i;
-        x_step = (dx * XY_ONE) / (ay | 1);
-        ecount = (y2 - y1) >> XY_SHIFT;
-    }
-    x1 += XY_ONE >> 1;
-    y1 += XY_ONE >> 1;
-    put_point(img, H, W, (x2 + (XY_ONE >> 1)) >> XY_SHIFT, (y2 + (XY_ONE >> 1)) >> XY_SHIFT);
-    if (ax > ay) {
-        x1 >>= XY_SHIFT;
-        for (; ecount >= 0; --ecount, ++x1, y1 += y_step) put_point(img, H, W, x1, y1 >> XY_SHIFT);
-    } else {
-        y1 >>= XY_SHIFT;
-        for (; ecount >= 0; --ecount, ++y1, x1 += x_step) put_point(img, H, W, x1 >> XY_SHIFT, y1);
-    }
-}
-
 // one workgroup (one wave) per (ellipse, image); dynamic LDS: 2 ints per row of the frame (the spans)
 __global__ __launch_bounds__(64) void shade_ellipse_kernel(const mp_photometric_plan* plans, const int* ellipses, int step,
                                                            int H, int W, float* mask)
@@ -287,102 +197,24 @@ __global__ __launch_bounds__(64) void shade_ellipse_kernel(const mp_photometric_
     __shared__ long long vx[MAX_VERTS], vy[MAX_VERTS], rx[MAX_VERTS], ry[MAX_VERTS];
     __shared__ int npts_s, ylo_s, yhi_s;
     extern __shared__ int spans[];             // [H][2]: xx1, xx2 of row y (xx1 > xx2: empty row)
-    // EllipseEx + ellipse2Poly (drawing.cpp), arc 0 .. 360: one lane per polygon point, then the consecutive duplicates
-    // dropped in order
-    const long long cxl = (long long)el[0] << XY_SHIFT, cyl = (long long)el[1] << XY_SHIFT;
-    const long long aw = (long long)abs(el[2]) << XY_SHIFT, ah = (long long)abs(el[3]) << XY_SHIFT;
-    int delta = (int)((max(aw, ah) + (XY_ONE >> 1)) >> XY_SHIFT);
-    delta = delta < 3 ? 90 : delta < 10 ? 30 : delta < 15 ? 18 : 5;
-    int angle = el[4];
-    while (angle < 0) angle += 360;
-    while (angle > 360) angle -= 360;
-    const int npoly = (360 + delta - 1) / delta + 1;      // i = 0, delta, ... < 360 + delta
-    {
-        const float alpha = sin_table(450 - angle), beta = sin_table(angle);
-        const double cx = (double)cxl, cy = (double)cyl;
-        for (int k = threadIdx.x; k < npoly; k += blockDim.x) {
-            const int t = min(k * delta, 360);
-            const double x = (double)aw * (double)sin_table(450 - t), y = (double)ah * (double)sin_table(t);
-            const double fx = cx + x * (double)alpha - y * (double)beta;
-            const double fy = cy + x * (double)beta + y * (double)alpha;
-            long long qx = cv_round(fx / (double)XY_ONE) << XY_SHIFT, qy = cv_round(fy / (double)XY_ONE) << XY_SHIFT;
-            qx += cv_round(fx - (double)qx);
-            qy += cv_round(fy - (double)qy);
-            rx[k] = qx;
-            ry[k] = qy;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int n = 0;
-        for (int k = 0; k < npoly; ++k)
-            if (n == 0 || rx[k] != vx[n - 1] || ry[k] != vy[n - 1]) { vx[n] = rx[k]; vy[n] = ry[k]; ++n; }
-        if (npoly == 1 || n == 1) { vx[0] = vx[1] = cxl; vy[0] = vy[1] = cyl; n = 2; }
-        npts_s = n;
-    }
-    __syncthreads();
+    ellipse_poly(el, vx, vy, rx, ry, &npts_s);
     const int npts = npts_s;
+    const auto put = [&](long long x, long long y) {
+        if (0 <= x && x < W && 0 <= y && y < H) m[y * (long long)W + x] = 1.f;
+    };
     // the outline: edge t runs from vertex t-1 (npts-1 for t = 0) to vertex t
     for (int t = threadIdx.x; t < npts; t += blockDim.x) {
         const int t0 = t == 0 ? npts - 1 : t - 1;
-        line2(m, H, W, vx[t0], vy[t0], vx[t], vy[t]);
+        line2(H, W, vx[t0], vy[t0], vx[t], vy[t], put);
     }
     if (threadIdx.x == 0) {
-        // FillConvexPoly (LINE_8, shift 16): the edge walk, one span per row
-        const long long delta = XY_ONE >> 1;
-        long long xmin = vx[0], xmax = vx[0], ymin = vy[0], ymax = vy[0];
-        int imin = 0;
-        for (int k = 0; k < npts; ++k) {
-            if (vy[k] < ymin) { ymin = vy[k]; imin = k; }
-            ymax = max(ymax, vy[k]); xmax = max(xmax, vx[k]); xmin = min(xmin, vx[k]);
-        }
-        xmin = (xmin + delta) >> XY_SHIFT; xmax = (xmax + delta) >> XY_SHIFT;
-        ymin = (ymin + delta) >> XY_SHIFT; ymax = (ymax + delta) >> XY_SHIFT;
         int ylo = 0, yhi = -1;                              // rows [ylo, yhi] have spans
-        if (!(npts < 3 || (int)xmax < 0 || (int)ymax < 0 || (int)xmin >= W || (int)ymin >= H)) {
-            ymax = min(ymax, (long long)H - 1);
-            int e_idx[2] = {imin, imin}, e_di[2] = {1, npts - 1};
-            long long e_x[2] = {-XY_ONE, -XY_ONE}, e_dx[2] = {0, 0};
-            int e_ye[2] = {(int)ymin, (int)ymin};
-            int y = (int)ymin, edges = npts;
-            ylo = max(y, 0);
-            do {
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    if (y >= e_ye[s]) {
-                        int idx0 = e_idx[s], di = e_di[s];
-                        int idx = idx0 + di;
-                        if (idx >= npts) idx -= npts;
-                        for (; edges-- > 0;) {
-                            const int ty = (int)((vy[idx] + delta) >> XY_SHIFT);
-                            if (ty > y) {
-                                const long long xs = vx[idx0], xe = vx[idx];
-                                e_ye[s] = ty;
-                                e_dx[s] = ((xe - xs) * 2 + (ty - y)) / (2LL * (ty - y));
-                                e_x[s] = xs;
-                                e_idx[s] = idx;
-                                break;
-                            }
-                            idx0 = idx;
-                            idx += di;
-                            if (idx >= npts) idx -= npts;
-                        }
-                    }
-                }
-                if (edges < 0) break;
-                if (y >= 0) {
-                    const int l = e_x[0] > e_x[1] ? 1 : 0;
-                    const int xx1 = (int)((e_x[l] + delta) >> XY_SHIFT), xx2 = (int)((e_x[1 - l] + delta) >> XY_SHIFT);
-                    int a = 1, b = 0;                           // empty
-                    if (xx2 >= 0 && xx1 < W) { a = max(xx1, 0); b = min(xx2, W - 1); }
-                    spans[2 * y] = a;
-                    spans[2 * y + 1] = b;
-                    yhi = y;
-                }
-                e_x[0] += e_dx[0];
-                e_x[1] += e_dx[1];
-            } while (++y <= (int)ymax);
-        }
+        convex_spans(vx, vy, npts, H, W, [&](int y, int a, int b) {
+            if (yhi < 0) ylo = y;
+            spans[2 * y] = a;
+            spans[2 * y + 1] = b;
+            yhi = y;
+        });
         ylo_s = ylo;
         yhi_s = yhi;
     }
@@ -393,12 +225,20 @@ __global__ __launch_bounds__(64) void shade_ellipse_kernel(const mp_photometric_
     }
 }
 
+// the blur size of image `img`: its shade op at `step`, or ksizes[img] when the caller blurs plain frames (0: no blur)
+__device__ __forceinline__ int blur_ksize(const mp_photometric_plan* plans, int step, const int* ksizes, int img)
+{
+    if (ksizes) return ksizes[img];
+    return step < plans[img].n_ops && plans[img].op[step].kind == MP_PHOTO_SHADE ? plans[img].op[step].ksize : 0;
+}
+
 // getGaussianKernel(k, 0, CV_32F): weights [n][MP_PHOTO_MAX_BLUR]
-__global__ __launch_bounds__(64) void blur_weights_kernel(const mp_photometric_plan* plans, int step, float* weights)
+__global__ __launch_bounds__(64) void blur_weights_kernel(const mp_photometric_plan* plans, int step, const int* ksizes,
+                                                          float* weights)
 {
     const int img = blockIdx.x;
-    if (step >= plans[img].n_ops || plans[img].op[step].kind != MP_PHOTO_SHADE) return;
-    const int k = plans[img].op[step].ksize;
+    const int k = blur_ksize(plans, step, ksizes, img);
+    if (k == 0) return;
     float* w = weights + (long long)img * MP_PHOTO_MAX_BLUR;
     const double sigma = ((k - 1) * 0.5 - 1) * 0.3 + 0.8;
     const double scale2x = -0.5 / (sigma * sigma);
@@ -418,12 +258,12 @@ __global__ __launch_bounds__(64) void blur_weights_kernel(const mp_photometric_p
 }
 
 // row filter: one workgroup per (row, image); dynamic LDS: the reflected row (W + 2r) and the k weights
-__global__ __launch_bounds__(256) void blur_rows_kernel(const mp_photometric_plan* plans, int step, const float* weights,
-                                                        const float* mask, int H, int W, float* tmp)
+__global__ __launch_bounds__(256) void blur_rows_kernel(const mp_photometric_plan* plans, int step, const int* ksizes,
+                                                        const float* weights, const float* mask, int H, int W, float* tmp)
 {
     const int img = blockIdx.y, y = blockIdx.x;
-    if (step >= plans[img].n_ops || plans[img].op[step].kind != MP_PHOTO_SHADE) return;
-    const int k = plans[img].op[step].ksize, r = k / 2;
+    const int k = blur_ksize(plans, step, ksizes, img), r = k / 2;
+    if (k == 0) return;
     extern __shared__ float lds[];
     float* w = lds;
     float* ext = lds + k;
@@ -441,12 +281,12 @@ __global__ __launch_bounds__(256) void blur_rows_kernel(const mp_photometric_pla
 
 // symmetric column filter: one workgroup per (COL_TX columns, COL_TY rows, image); 256 threads = COL_TX columns x 8
 // row groups; dynamic LDS: the k weights and the reflected input rows [COL_TY + 2r][COL_TX]
-__global__ __launch_bounds__(256) void blur_cols_kernel(const mp_photometric_plan* plans, int step, const float* weights,
-                                                        const float* tmp, int H, int W, float* mask)
+__global__ __launch_bounds__(256) void blur_cols_kernel(const mp_photometric_plan* plans, int step, const int* ksizes,
+                                                        const float* weights, const float* tmp, int H, int W, float* mask)
 {
     const int img = blockIdx.z;
-    if (step >= plans[img].n_ops || plans[img].op[step].kind != MP_PHOTO_SHADE) return;
-    const int k = plans[img].op[step].ksize, r = k / 2;
+    const int k = blur_ksize(plans, step, ksizes, img), r = k / 2;
+    if (k == 0) return;
     const int x0 = blockIdx.x * COL_TX, y0 = blockIdx.y * COL_TY;
     extern __shared__ float lds[];
     float* w = lds;
@@ -606,6 +446,18 @@ int max_blur(const mp_photometric_plan* plans, int n, int step)
     return m;
 }
 
+// GaussianBlur of n frames in place (through tmp): the shade masks of `step`, or plain frames with ksizes[img] (device)
+void launch_blur(const mp_photometric_plan* plans, int step, const int* ksizes, int k, float* weights, float* img, float* tmp,
+                 int n, int H, int W, hipStream_t s)
+{
+    const int r = k / 2;
+    hipLaunchKernelGGL(blur_weights_kernel, dim3(n), dim3(64), 0, s, plans, step, ksizes, weights);
+    hipLaunchKernelGGL(blur_rows_kernel, dim3(H, n), dim3(256), sizeof(float) * (size_t)(k + W + 2 * r), s, plans, step, ksizes,
+                       weights, img, H, W, tmp);
+    hipLaunchKernelGGL(blur_cols_kernel, dim3((W + COL_TX - 1) / COL_TX, (H + COL_TY - 1) / COL_TY, n), dim3(256),
+                       sizeof(float) * (size_t)(k + (COL_TY + 2 * r) * COL_TX), s, plans, step, ksizes, weights, tmp, H, W, img);
+}
+
 // the (blurred) shade masks of step `step` into w.mask
 void run_shade(const PhotoWorkspace& w, const mp_photometric_plan* host_plans, int n, int H, int W, int step, bool blurred,
                hipStream_t s)
@@ -616,13 +468,7 @@ void run_shade(const PhotoWorkspace& w, const mp_photometric_plan* host_plans, i
         hipLaunchKernelGGL(shade_ellipse_kernel, dim3(ne, n), dim3(64), sizeof(int) * 2 * (size_t)H, s, w.plans, w.ellipses,
                            step, H, W, w.mask);
     if (!blurred) return;
-    const int k = max_blur(host_plans, n, step), r = k / 2;
-    hipLaunchKernelGGL(blur_weights_kernel, dim3(n), dim3(64), 0, s, w.plans, step, w.weights);
-    hipLaunchKernelGGL(blur_rows_kernel, dim3(H, n), dim3(256), sizeof(float) * (size_t)(k + W + 2 * r), s, w.plans, step,
-                       w.weights, w.mask, H, W, w.tmp);
-    hipLaunchKernelGGL(blur_cols_kernel, dim3((W + COL_TX - 1) / COL_TX, (H + COL_TY - 1) / COL_TY, n), dim3(256),
-                       sizeof(float) * (size_t)(k + (COL_TY + 2 * r) * COL_TX), s, w.plans, step, w.weights, w.tmp, H, W,
-                       w.mask);
+    launch_blur(w.plans, step, nullptr, max_blur(host_plans, n, step), w.weights, w.mask, w.tmp, n, H, W, s);
 }
 
 void upload(const PhotoWorkspace& w, const mp_photometric_plan* plans, int n, const int* ellipses, int n_ellipses,
@@ -636,6 +482,18 @@ void upload(const PhotoWorkspace& w, const mp_photometric_plan* plans, int n, co
 }
 
 }  // namespace
+
+size_t gaussian_blur_lds_bytes(int k, int W)
+{
+    const int r = k / 2;
+    return max(sizeof(float) * (size_t)(k + W + 2 * r), sizeof(float) * (size_t)(k + (COL_TY + 2 * r) * COL_TX));
+}
+
+void launch_gaussian_blur_frames(float* img, float* tmp, float* weights, const int* ksizes, int kmax, int n, int H, int W,
+                                 hipStream_t s)
+{
+    launch_blur(nullptr, 0, ksizes, kmax, weights, img, tmp, n, H, W, s);
+}
 
 size_t photometric_workspace_bytes(int n, int H, int W, int n_ellipses)
 {

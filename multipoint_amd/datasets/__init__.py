@@ -1,6 +1,7 @@
 # mirrors multipoint/datasets/__init__.py for the prediction path
 from .synthetic_pairs import SyntheticPairs  # noqa: F401
 from .image_pair_dataset import ImagePairDataset  # noqa: F401
+from .synthetic_shapes import SyntheticShapes  # noqa: F401
 from . import augmentation  # noqa: F401,E402
 
 
@@ -11,6 +12,8 @@ def loader_num_workers(dataset, requested):
     cfg = getattr(dataset, 'config', {}) or {}
     aug = cfg.get('augmentation', {})
     gpu_work = any(bool(aug.get(k, {}).get('enable', False)) for k in ('homographic', 'photometric'))
+    if isinstance(dataset, SyntheticShapes) and cfg.get('on-the-fly', True):
+        gpu_work = True                                    # the images themselves are rendered on the GPU
     if gpu_work and requested:
         print('INFO: homographic / photometric augmentation runs on the GPU inside the dataset; using num_workers=0 '
               'instead of {}'.format(requested))
