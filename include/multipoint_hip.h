@@ -652,6 +652,44 @@ int mp_gaussian_blur(mp_handle* h, const float* in, int n, int H, int W, int ksi
 #define MP_FRAMES_U16 2
 int mp_frames_to_float(mp_handle* h, const void* in, int mode, int n, int H, int W, float* out, void* stream);
 
+/* ---- frame preparation (create_dataset/extract_images.py:167-242, preprocess_images; DESIGN.md 3.13 is the specification) ----
+ * Batches of n frames on the caller's stream; K, D and K_new are HOST arrays (K, K_new: 3 x 3 row-major, of which fx, fy, cx, cy
+ * are read; D: k1, k2, p1, p2[, k3]).
+ *
+ * mp_undistort: cv2.undistort(src, K, D, None, K_new) of uint8 [n][H][W][3] (MP_FRAMES_BGR8) or uint16 [n][H][W] (MP_FRAMES_U16).
+ * Per destination pixel (u, v), float64, + - * / only, nothing contracted: x = (u - cx') / fx', y = (v - cy') / fy',
+ * r2 = x x + y y, kr = 1 + ((k3 r2 + k2) r2 + k1) r2, xd = x kr + p1 (2 x y) + p2 (r2 + 2 x x),
+ * yd = y kr + p1 (r2 + 2 y y) + p2 (2 x y), us = fx xd + cx, vs = fy yd + cy; iu = rint(32 us), iv = rint(32 vs) (half to even,
+ * saturated to int32), first tap (iv >> 5, iu >> 5), fractions ax = iu & 31, ay = iv & 31.  Taps (sy, sx), (sy, sx + 1),
+ * (sy + 1, sx), (sy + 1, sx + 1) with weights (32 - ax)(32 - ay), ax (32 - ay), (32 - ax) ay, ax ay over 1024; a tap outside
+ * the frame reads 0.  8 bit: weights x 32, (sum + 16384) >> 15 per channel.  16 bit: float weights w / 1024, products summed in
+ * that order in fp32 (no FMA), rint half to even, saturated to [0, 65535].  rotate180 != 0 writes the result rotated by 180
+ * degrees ([..., ::-1, ::-1]).
+ * MP_EINVAL: a NULL argument, src == dst, another dtype, n_coeffs other than 4 or 5, a non-finite parameter, a zero focal
+ * length in K_new, n outside [1, 65535], H or W outside [1, 32767], more than 2^38 pixels, dst not 4-byte aligned. */
+int mp_undistort(mp_handle* h, const void* src, int dtype, int n, int H, int W, const double* K, const double* D, int n_coeffs,
+                 const double* K_new, int rotate180, void* dst, void* stream);
+
+/* cv2.resize(src, (ow, oh)), INTER_LINEAR, of uint8 [n][H][W][3] into [n][oh][ow][3]: OpenCV's 11-bit fixed-point path.  Per
+ * axis: f = (float)((d + 0.5) (in / out) - 0.5) with the product in float64, i = floor(f), f -= i; i < 0: i = 0, f = 0;
+ * i >= in - 1: i = in - 1, f = 0; a1 = rint(2048 f), a0 = rint(2048 (1 - f)), both saturated to int16.  S = v[i] a0 + v[i + 1] a1
+ * along the row, then (((b0 (S0 >> 4)) >> 16) + ((b1 (S1 >> 4)) >> 16) + 2) >> 2 saturated to uint8.
+ * MP_EINVAL: a NULL tensor, src == dst, a size outside the ranges above, dst not 4-byte aligned. */
+int mp_resize_bgr8(mp_handle* h, const unsigned char* src, int n, int H, int W, int oh, int ow, unsigned char* dst, void* stream);
+
+/* The thermal frame's rescale, per image of uint16 [n][H][W]:
+ *   bounds    lower = np.percentile(x, 1), upper = np.percentile(x, 99) (linear method, float64) from the exact order statistics;
+ *             outlier_rejection == 0: no bounds, nothing is clipped
+ *   clipped   (may be `in`, may be NULL) x < lower -> trunc(lower), then x > upper -> trunc(upper)
+ *   rescaled  fp32: cv2.normalize(clipped, 0, 1, NORM_MINMAX, CV_32F): scale = 1 / (max - min) in float64 (0 when max - min <=
+ *             DBL_EPSILON), shift = -min scale, out = (float)v (float)scale + (float)shift, a separate multiply and add
+ *   saved     (may be NULL) uint16: (rescaled * 65535).astype(uint16): fp32 product, truncated, the low 16 bits
+ * The workspace (mp_thermal_rescale_workspace_bytes, 16-byte aligned) is scratch; it is zeroed on the stream by the call.
+ * MP_EINVAL: a NULL in / rescaled / workspace, saved aliasing in or clipped, sizes as above, a small or misaligned workspace. */
+int mp_thermal_rescale_workspace_bytes(int n, long long* bytes);
+int mp_thermal_rescale(mp_handle* h, const unsigned short* in, int n, int H, int W, int outlier_rejection, unsigned short* clipped,
+                       float* rescaled, unsigned short* saved, void* workspace, long long workspace_bytes, void* stream);
+
 /* ---- 2-D FFT and the LGHD baseline (multipoint/models/ClassicDetectors.py, class LGHD) ----
  * Line lengths are 2^a 3^b 5^c in [8, 4096] (mp_fft_supported); complex arrays are interleaved fp32 (re, im).
  *

@@ -163,6 +163,12 @@ SIGNATURES = {
     'mp_gaussian_weights': (c_int, [c_int, ctypes.POINTER(c_float)]),
     'mp_gaussian_blur': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'mp_frames_to_float': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'mp_undistort': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double),
+                             ctypes.POINTER(ctypes.c_double), c_int, ctypes.POINTER(ctypes.c_double), c_int, c_void_p, c_void_p]),
+    'mp_resize_bgr8': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'mp_thermal_rescale_workspace_bytes': (c_int, [c_int, ctypes.POINTER(c_ll)]),
+    'mp_thermal_rescale': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_ll,
+                                   c_void_p]),
     'mp_fft_supported': (c_int, [c_int]),
     'mp_fft2d': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'mp_lghd_quantize': (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),

@@ -534,3 +534,24 @@ void launch_lghd_detect(const unsigned char* u8, int B, int H, int W, unsigned c
 // raw / unit fp32 [B][K][384], either may be NULL
 void launch_lghd_describe(const unsigned char* ori, int B, int H, int W, const int* kp_yx, const int* kp_count, int K, float* raw,
                           float* unit, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
+// Frame preparation (frames.hip; reference create_dataset/extract_images.py:167-242).
+// ---------------------------------------------------------------------------------------------
+struct FramesCamera {
+    double fx, fy, cx, cy;          // K of the source frame
+    double k1, k2, p1, p2, k3;      // radial-tangential distortion
+    double nfx, nfy, ncx, ncy;      // K_new of the destination frame
+};
+// np.percentile's linear method on H W values: the ranks the 1 % and the 99 % bound interpolate between and their weights
+struct FramesRanks {
+    long long rank[4];              // lower previous / next, upper previous / next
+    double gamma[2];
+};
+// src / dst: uint8 [n][H][W][3] (u16 = 0) or uint16 [n][H][W] (u16 = 1); dst 4-byte aligned, not src
+void launch_undistort(const void* src, int u16, int n, int H, int W, const FramesCamera& cam, int rotate180, void* dst, hipStream_t s);
+void launch_resize_bgr8(const unsigned char* src, int n, int H, int W, int oh, int ow, unsigned char* dst, hipStream_t s);
+size_t thermal_rescale_workspace_bytes(int n);
+// workspace: thermal_rescale_workspace_bytes(n) zeroed bytes on s; clipped (may be `in`) and saved may be NULL
+void launch_thermal_rescale(const unsigned short* in, int n, int H, int W, const FramesRanks& rk, unsigned short* clipped,
+                            float* rescaled, unsigned short* saved, void* workspace, hipStream_t s);

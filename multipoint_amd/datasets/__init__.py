@@ -2,6 +2,7 @@
 from .synthetic_pairs import SyntheticPairs  # noqa: F401
 from .image_pair_dataset import ImagePairDataset  # noqa: F401
 from .synthetic_shapes import SyntheticShapes  # noqa: F401
+from .image_file_pairs import ImageFilePairs  # noqa: F401
 from . import augmentation  # noqa: F401,E402
 
 
@@ -14,6 +15,8 @@ def loader_num_workers(dataset, requested):
     gpu_work = any(bool(aug.get(k, {}).get('enable', False)) for k in ('homographic', 'photometric'))
     if isinstance(dataset, SyntheticShapes) and cfg.get('on-the-fly', True):
         gpu_work = True                                    # the images themselves are rendered on the GPU
+    if isinstance(dataset, ImageFilePairs):
+        gpu_work = True                                    # the 8- / 16-bit files are converted to fp32 on the GPU
     if gpu_work and requested:
         print('INFO: homographic / photometric augmentation runs on the GPU inside the dataset; using num_workers=0 '
               'instead of {}'.format(requested))
