@@ -13,6 +13,8 @@ initial_transform.yaml with the key `perspective` (3x3, thermal pixel -> optical
                                       with the fp32 warp of utils.alignment.warp_image, rounded to 8 bit; pixels that take part of
                                       the border are 0
   aligned/best/<index>_thermal.png    (save_aligned_images) the thermal file, copied
+  aligned/all/<index>_optical_<i>.png (--save-candidates) the optical image under every valid candidate of the last stage, in
+                                      candidate order: the alternatives check_alignment.py offers when the best one is rejected
 
 and the method counters are printed in the reference's format (every stage that finds an alignment counts, as there).
 
@@ -38,6 +40,8 @@ def build_parser():
     parser.add_argument('-i', '--input-dir', default='/tmp/data', help='Input directory')
     parser.add_argument('-o', '--output-dir', default='/tmp/data/processed', help='Output directory')
     parser.add_argument('--batch', default=8, type=int, help='(extension) pairs aligned together in one batch')
+    parser.add_argument('--save-candidates', action='store_true', help='(extension) also write aligned/all/<index>_optical_<i>.png, '
+                        'the optical image under every valid candidate, for check_alignment.py')
     return parser
 
 
@@ -110,8 +114,11 @@ def main(argv=None):
     with open(os.path.join(args.input_dir, 'initial_transform.yaml'), 'rt') as fh:
         t_init = np.array(yaml.safe_load(fh)['perspective'], np.float64).reshape(3, 3)
     best_dir = os.path.join(args.output_dir, 'aligned', 'best')
+    all_dir = os.path.join(args.output_dir, 'aligned', 'all')
     if params.get('save_aligned_images', False):
         os.makedirs(best_dir, exist_ok=True)
+    if args.save_candidates:
+        os.makedirs(all_dir, exist_ok=True)
     counter, transforms, failed = {'total': 0}, {}, []
     for at in range(0, len(names), max(args.batch, 1)):
         pairs = [read_pair(args.input_dir, n) + (n,) for n in names[at:at + max(args.batch, 1)]]
@@ -127,7 +134,7 @@ def main(argv=None):
         optical = torch.stack([alignment.frames_to_float(p[1], single_bgr=p[1].ndim == 3) for p in live])
         thermal = alignment.frames_to_float(np.stack([p[2] for p in live]))
         results = alignment.align_images_mutual_information(optical, thermal, t_init, params)
-        for (index, opt, th, thermal_path, name), (ok, T, kind, _, stages) in zip(live, results):
+        for (index, opt, th, thermal_path, name), (ok, T, kind, candidates, stages) in zip(live, results):
             for s in stages:
                 if s['success']:
                     count(counter, s['type'])
@@ -141,6 +148,10 @@ def main(argv=None):
             if params.get('save_aligned_images', False):
                 save_aligned(alignment, os.path.join(best_dir, index + '_optical.png'), opt, T, th.shape[0], th.shape[1])
                 shutil.copyfile(thermal_path, os.path.join(best_dir, index + '_thermal.png'))
+            if args.save_candidates:                        # align_images.py:137-139
+                for i, c in enumerate(candidates):
+                    save_aligned(alignment, os.path.join(all_dir, '%s_optical_%d.png' % (index, i)), opt, c['transform'],
+                                 th.shape[0], th.shape[1])
     with open(os.path.join(args.output_dir, 'failed.log'), 'wt') as fh:
         fh.write(''.join(n + '\n' for n in failed))
     with open(os.path.join(args.output_dir, 'transforms.json'), 'wt') as fh:

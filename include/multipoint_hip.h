@@ -690,6 +690,72 @@ int mp_thermal_rescale_workspace_bytes(int n, long long* bytes);
 int mp_thermal_rescale(mp_handle* h, const unsigned short* in, int n, int H, int W, int outlier_rejection, unsigned short* clipped,
                        float* rescaled, unsigned short* saved, void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- result views as pictures (show_keypoints.py, show_image_pair_sample.py, the drawing of predict_keypoints.py:159-280 and
+ * predict_align_image_pair.py:197-254, create_dataset/check_alignment.py; DESIGN.md 3.14 is the specification) ----
+ * Canvases are uint8 [B][Hc][Wc][3], RGB, contiguous, owned by the caller.  Every entry queues its launches on `stream` and
+ * returns; list lengths are read on the device.  Every pixel write is checked against the canvas: what falls outside is
+ * clipped, what nothing covers keeps its value.  Centre + offset is added in 64 bits.  A result does not depend on the launch
+ * shape or on the order in which workgroups run.
+ * MP_EINVAL for all four: a NULL tensor (the optional ones excepted), B / P outside [1, 65535], a frame or canvas side outside
+ * [1, 32767], K outside [1, 2^20], and what each entry lists.
+ *
+ * The 8-bit value of a fp32 one, u8(g): NaN -> 0, clamped to [0, 1], (uint8)(c * 255.0f) with one fp32 product, truncated --
+ * numpy's (np.clip(g, 0, 1) * 255.0).astype(np.uint8).
+ *
+ * mp_draw_gray_to_rgb: B fp32 frames [B][H][W] as grey pixels at canvas offset (y0, x0): v = x, or the fp32 product x * m with
+ * `mask` (fp32 [B][H][W], may be NULL); g = the fp32 product v * gain; all three channels = u8(g).  Canvas pixels outside the
+ * frame are not written. */
+int mp_draw_gray_to_rgb(mp_handle* h, const float* images, const float* mask, int B, int H, int W, float gain,
+                        unsigned char* canvas, int Hc, int Wc, int y0, int x0, void* stream);
+
+/* mp_draw_marks: one layer of marks.  kp_yx int32 [B][K][2] (y, x), kp_count int32 [B] (a count above K means K, a negative
+ * one 0; only that many entries are read).  With half_r[k] the half widths of OpenCV's Circle() walk of radius r (the widest
+ * span it draws on the rows cy -+ k):
+ *   disc(c, r)     {(x, y): |y - cy| <= r, |x - cx| <= half_r[|y - cy|]}; r = 0 is the centre pixel
+ *   MP_DRAW_RING   disc(c, radius + thickness / 2) without disc(c, radius - (thickness + 1) / 2) (empty for a negative radius)
+ *   MP_DRAW_DISC   disc(c, radius)
+ *   MP_DRAW_CROSS  the centre row and the centre column within +-radius
+ * (integer divisions; disc and cross do not read the thickness).  Mark i has its centre at keypoint i + (y0, x0); a pixel takes
+ * palette[i mod n_colors] (uint8 [n_colors][3]) of the HIGHEST i covering it.
+ * MP_EINVAL: another kind, radius < 0, thickness < 1, outer radius (radius + thickness / 2 for a ring) above
+ * MP_DRAW_MAX_RADIUS, n_colors < 1. */
+#define MP_DRAW_MAX_RADIUS 64
+#define MP_DRAW_RING 0
+#define MP_DRAW_DISC 1
+#define MP_DRAW_CROSS 2
+int mp_draw_marks(mp_handle* h, const int* kp_yx, const int* kp_count, int B, int K, int kind, int radius, int thickness,
+                  const unsigned char* palette, int n_colors, unsigned char* canvas, int Hc, int Wc, int y0, int x0, void* stream);
+
+/* mp_draw_matches: one layer of matches per pair on a canvas that shows both images.  kp_a, kp_b int32 [P][K][2] (y, x) with
+ * count_a, count_b int32 [P]; match_idx int32 [P][K]: the index into kp_b that kp_a's entry q is matched to, or -1; draw_mask
+ * uint8 [P][K] or NULL.  Primitive q exists when q < min(count_a, K), 0 <= match_idx[q] < min(count_b, K) and draw_mask is NULL
+ * or non-zero at q; nothing else is read.  With A = kp_a[q] + (ya, xa) and B = kp_b[match_idx[q]] + (yb, xb) it covers the rings
+ * (MP_DRAW_RING at radius / thickness) around A and B and the LINE_8 segment A -> B: cv2.line at thickness 1, i.e. clipLine to
+ * the canvas and then the LineIterator from the left end, the rule of MP_SHAPES_LINE.  A pixel takes palette[q mod n_colors] of
+ * the HIGHEST q covering it.  The order is kept in an owner map (uint32 per canvas pixel, atomicMax(q + 1)) in the handle's
+ * grow-only workspace, cleared on `stream` at the start of the call; a buffer it outgrows stays allocated until mp_destroy.
+ * One call at a time per handle.
+ * MP_EINVAL: radius < 0, thickness < 1, outer radius above MP_DRAW_MAX_RADIUS, n_colors < 1.  MP_ENOMEM: the owner map. */
+int mp_draw_matches(mp_handle* h, const int* kp_a, const int* kp_b, const int* count_a, const int* count_b, const int* match_idx,
+                    const unsigned char* draw_mask, int P, int K, int ya, int xa, int yb, int xb, int radius, int thickness,
+                    const unsigned char* palette, int n_colors, unsigned char* canvas, int Hc, int Wc, void* stream);
+
+/* mp_draw_compose: alignment views of a warped optical frame and a thermal frame, both fp32 [B][H][W], at canvas offset
+ * (y0, x0).  T = u8(thermal); a pixel with warped < 0 (the -1 border of mp_mi_joint_histogram's warp) is outside: A = 0 there,
+ * A = u8(warped) elsewhere.
+ *   MP_DRAW_BLEND       (A alpha + T (256 - alpha) + 128) >> 8 on all channels
+ *   MP_DRAW_CHECKER     A where x / cell + y / cell is even, else T (frame coordinates, integer divisions)
+ *   MP_DRAW_ANAGLYPH    (R, G, B) = (A, T, T)
+ *   MP_DRAW_DIFFERENCE  |A - T| on all channels
+ * In blend, checker and difference an outside pixel shows (T, T, T).
+ * MP_EINVAL: another mode, alpha outside [0, 256], cell < 1. */
+#define MP_DRAW_BLEND 0
+#define MP_DRAW_CHECKER 1
+#define MP_DRAW_ANAGLYPH 2
+#define MP_DRAW_DIFFERENCE 3
+int mp_draw_compose(mp_handle* h, const float* warped, const float* thermal, int B, int H, int W, int mode, int alpha, int cell,
+                    unsigned char* canvas, int Hc, int Wc, int y0, int x0, void* stream);
+
 /* ---- 2-D FFT and the LGHD baseline (multipoint/models/ClassicDetectors.py, class LGHD) ----
  * Line lengths are 2^a 3^b 5^c in [8, 4096] (mp_fft_supported); complex arrays are interleaved fp32 (re, im).
  *

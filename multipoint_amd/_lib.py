@@ -71,6 +71,9 @@ class MiProblem(ctypes.Structure):
 
 MP_MI_SLOTS = 10
 MP_FRAMES_U8, MP_FRAMES_BGR8, MP_FRAMES_U16 = 0, 1, 2
+MP_DRAW_MAX_RADIUS = 64
+MP_DRAW_KINDS = {'ring': 0, 'disc': 1, 'cross': 2}
+MP_DRAW_MODES = {'blend': 0, 'checker': 1, 'anaglyph': 2, 'difference': 3}
 
 # name -> (restype, argtypes); every symbol declared in include/multipoint_hip.h
 SIGNATURES = {
@@ -169,6 +172,14 @@ SIGNATURES = {
     'mp_thermal_rescale_workspace_bytes': (c_int, [c_int, ctypes.POINTER(c_ll)]),
     'mp_thermal_rescale': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_ll,
                                    c_void_p]),
+    'mp_draw_gray_to_rgb': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int, c_int, c_int, c_int,
+                                    c_void_p]),
+    'mp_draw_marks': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                              c_int, c_int, c_int, c_void_p]),
+    'mp_draw_matches': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    'mp_draw_compose': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int,
+                                c_int, c_int, c_void_p]),
     'mp_fft_supported': (c_int, [c_int]),
     'mp_fft2d': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'mp_lghd_quantize': (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),

@@ -145,6 +145,9 @@ struct mp_handle {
     int* pinned = nullptr;          // small pinned host scratch (img lists, counters)
     mp_host::MiRefine mi;           // the running mutual-information refinement (mp_mi_refine_*)
     std::map<int, mp_host::DevBuf> fft_tw;     // FFT twiddle tables by line length (lghd_api.hip)
+    mp_host::DevBuf draw_ws;        // owner map of mp_draw_matches: one uint32 per canvas pixel, grow-only (draw.hip)
+    std::vector<mp_host::DevBuf> draw_retired;   // ... the buffers it outgrew: a launch on another stream may still use one, so
+                                                 // they live as long as the handle (each at most half its successor's size)
     bool prof = false;
     bool head_fallback_noted = false;
     std::vector<mp_host::ProfEntry> prof_entries;

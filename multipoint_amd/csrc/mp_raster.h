@@ -1,5 +1,6 @@
-// OpenCV's LINE_8 drawing rules in 16.16 fixed point, shared by the shade ellipses of photometric.hip and the synthetic
-// shapes of shapes.hip: clipLine, Line2, ellipse2Poly and the FillConvexPoly edge walk (drawing.cpp).  Internal header.
+// OpenCV's LINE_8 drawing rules, shared by the shade ellipses of photometric.hip, the synthetic shapes of shapes.hip and the
+// result views of draw.hip: clipLine, Line2, ellipse2Poly and the FillConvexPoly edge walk in 16.16 fixed point, Line (the
+// LineIterator) and the half widths of Circle's midpoint walk in whole pixels (drawing.cpp).  Internal header.
 // The callers supply where a pixel or a row span goes: put(x, y) is called for any integer pixel (the callee clips),
 // span(y, a, b) for every row y >= 0 the walk visits with the span already clipped to [0, W - 1] (a > b: empty row).
 #pragma once
@@ -92,6 +93,48 @@ __device__ __forceinline__ void line2(int H, int W, long long x1, long long y1, 
     } else {
         y1 >>= XY_SHIFT;
         for (; ecount >= 0; --ecount, ++y1, x1 += x_step) put(x1 >> XY_SHIFT, y1);
+    }
+}
+
+// Line(): LineIterator(img, p1, p2, 8, leftToRight) -- clipped to the frame, then Bresenham from the left end
+template <typename Paint>
+__device__ __forceinline__ void thin_line(int H, int W, long long x1, long long y1, long long x2, long long y2, Paint paint)
+{
+    if (x1 < 0 || x1 >= W || x2 < 0 || x2 >= W || y1 < 0 || y1 >= H || y2 < 0 || y2 >= H)
+        if (!clip_line_to(W - 1, H - 1, x1, y1, x2, y2)) return;
+    if (x2 < x1) { long long t = x1; x1 = x2; x2 = t; t = y1; y1 = y2; y2 = t; }
+    int dx = (int)(x2 - x1), dy = (int)(y2 - y1);
+    const int sy = dy < 0 ? -1 : 1;
+    dy = abs(dy);
+    const bool steep = dy > dx;
+    if (steep) { const int t = dx; dx = dy; dy = t; }
+    int err = dx - (dy + dy);
+    const int plus = dx + dx, minus = -(dy + dy);
+    int x = (int)x1, y = (int)y1;
+    for (int i = 0; i <= dx; ++i) {
+        paint(x, y);
+        const bool minor = err < 0;
+        err += minus + (minor ? plus : 0);
+        if (steep) { y += sy; x += minor ? 1 : 0; }
+        else { x += 1; y += minor ? sy : 0; }
+    }
+}
+
+// Circle(): half[k] = the half width of the widest span the midpoint walk of radius r draws on the rows cy -+ k, k = 0 .. r
+__device__ __forceinline__ void circle_halfwidths(int r, short* h)
+{
+    for (int k = 0; k <= r; ++k) h[k] = -1;
+    int err = 0, dx = r, dy = 0, plus = 1, minus = (r << 1) - 1;
+    while (dx >= dy) {
+        h[dy] = max((int)h[dy], dx);
+        h[dx] = max((int)h[dx], dy);
+        ++dy;
+        err += plus;
+        plus += 2;
+        const int mask = (err <= 0) - 1;
+        err -= minus & mask;
+        dx += mask;
+        minus -= mask & 2;
     }
 }
 

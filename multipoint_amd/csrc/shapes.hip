@@ -59,20 +59,7 @@ __global__ __launch_bounds__(256) void shapes_halfwidth_kernel(short* half)
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r > MP_SHAPES_MAX_RADIUS) return;
-    short* h = half + r * HALF_STRIDE;
-    for (int k = 0; k <= r; ++k) h[k] = -1;
-    int err = 0, dx = r, dy = 0, plus = 1, minus = (r << 1) - 1;
-    while (dx >= dy) {
-        h[dy] = max((int)h[dy], dx);
-        h[dx] = max((int)h[dx], dy);
-        ++dy;
-        err += plus;
-        plus += 2;
-        const int mask = (err <= 0) - 1;
-        err -= minus & mask;
-        dx += mask;
-        minus -= mask & 2;
-    }
+    circle_halfwidths(r, half + r * HALF_STRIDE);
 }
 
 __global__ __launch_bounds__(256) void shapes_pixel_kernel(const mp_shapes_cmd* cmds, const int* offset, int step,
@@ -205,30 +192,6 @@ __global__ __launch_bounds__(256) void shapes_box_cols_kernel(const mp_shapes_cm
     for (int y = y0; y < y1; ++y) {
         dst[(long long)y * W] = (float)(s * scale);
         s += src[(long long)reflect101(y + 1 - a + k - 1, H) * W] - src[(long long)reflect101(y - a, H) * W];
-    }
-}
-
-// Line(): LineIterator(img, p1, p2, 8, leftToRight) -- clipped to the frame, then Bresenham from the left end
-template <typename Paint>
-__device__ __forceinline__ void thin_line(int H, int W, long long x1, long long y1, long long x2, long long y2, Paint paint)
-{
-    if (x1 < 0 || x1 >= W || x2 < 0 || x2 >= W || y1 < 0 || y1 >= H || y2 < 0 || y2 >= H)
-        if (!clip_line_to(W - 1, H - 1, x1, y1, x2, y2)) return;
-    if (x2 < x1) { long long t = x1; x1 = x2; x2 = t; t = y1; y1 = y2; y2 = t; }
-    int dx = (int)(x2 - x1), dy = (int)(y2 - y1);
-    const int sy = dy < 0 ? -1 : 1;
-    dy = abs(dy);
-    const bool steep = dy > dx;
-    if (steep) { const int t = dx; dx = dy; dy = t; }
-    int err = dx - (dy + dy);
-    const int plus = dx + dx, minus = -(dy + dy);
-    int x = (int)x1, y = (int)y1;
-    for (int i = 0; i <= dx; ++i) {
-        paint(x, y);
-        const bool minor = err < 0;
-        err += minus + (minor ? plus : 0);
-        if (steep) { y += sy; x += minor ? 1 : 0; }
-        else { x += 1; y += minor ? sy : 0; }
     }
 }
 

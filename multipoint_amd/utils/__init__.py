@@ -4,3 +4,4 @@ from .utils import *  # noqa: F401,F403
 from .evaluation import *  # noqa: F401,F403  (compute_descriptor_metrics, pair_metrics, ...)
 from .homographies import *  # noqa: F401,F403  (homographic adaptation: export_keypoints.py)
 from .frames import *  # noqa: F401,F403  (frame preparation: prepare_images.py)
+from .drawing import *  # noqa: F401,F403  (results as pictures: keypoint, match and alignment views)

@@ -5,7 +5,8 @@ format, same three timing prints (reference predict_align_image_pair.py:141-143)
 MI355X through libmultipoint_hip.so.  -e computes NN-mAP, M-score and homography correctness like the
 reference (utils.compute_descriptor_metrics; per-sample arithmetic and a batched RANSAC on the GPU -- the
 RANSAC is the product's own, not OpenCV's RNG).  The matplotlib/cv2 visualisation of -p is replaced by a
-text summary of keypoints/matches, the estimated and the ground-truth homography (and --save-npz)."""
+text summary of keypoints/matches, the estimated and the ground-truth homography (and --save-npz), and with
+--plot-dir by PNG files drawn on the GPU (multipoint_amd.utils.drawing)."""
 import argparse
 import os
 import random
@@ -45,7 +46,32 @@ def build_parser():
                         'the pair under the identity, the estimated and (with --refine) the refined homography')
     parser.add_argument('--mi-refine', action='store_true', help='(extension) maximise the mutual information from the estimated '
                         'homography (utils.alignment.align_images; yaml block prediction.mi_alignment) and print the result')
+    parser.add_argument('--plot-dir', default=None, help='(extension) with -p: write matches.png, matches_inliers.png, '
+                        'warped_optical.png, overlay_checker.png and overlay_anaglyph.png into this directory')
     return parser
+
+
+def write_plots(plot_dir, optical, thermal, kp_optical, kp_thermal, matches, inlier_mask, H_final, radius):
+    """The pictures of reference predict_align_image_pair.py:197-254 as files: the match picture with all matches and with
+    RANSAC's inliers alone (its matchesMask picture), one colour per match in match order; the optical image warped onto the
+    thermal frame by the final estimate and two overlays of it with the thermal image.  Returns the file names."""
+    from multipoint_amd.datasets.augmentation import warp_perspective_cv
+    from multipoint_amd.utils import drawing
+    os.makedirs(plot_dir, exist_ok=True)
+    query = np.array([m.queryIdx for m in matches], np.int64)
+    train = np.array([m.trainIdx for m in matches], np.int64)
+    kp_a, kp_b = kp_optical[query].reshape(-1, 2), kp_thermal[train].reshape(-1, 2)       # one keypoint pair per match
+    inliers = np.zeros(len(matches), bool)
+    inliers[:len(inlier_mask)] = np.asarray(inlier_mask).reshape(-1)[:len(matches)] != 0
+    pictures = {'matches.png': drawing.draw_matches(optical, thermal, kp_a, kp_b, np.arange(len(matches)), radius=radius),
+                'matches_inliers.png': drawing.draw_matches(optical, thermal, kp_a, kp_b, np.arange(len(matches)), mask=inliers,
+                                                            radius=radius),
+                'warped_optical.png': drawing.gray_to_rgb(warp_perspective_cv(optical, H_final[None], border_reflect=False))}
+    views = drawing.alignment_views(optical, thermal, estimate_to_transform(H_final), modes=('checker', 'anaglyph'))
+    pictures['overlay_checker.png'], pictures['overlay_anaglyph.png'] = views['checker'], views['anaglyph']
+    for name, picture in pictures.items():
+        drawing.save_png(os.path.join(plot_dir, name), picture)
+    return list(pictures)
 
 
 def load_network(config, model_dir, version, device, seed=0):
@@ -270,8 +296,9 @@ def main(argv=None):
             if args.mi:
                 mi_report(data['optical']['image'][:1], data['thermal']['image'][:1],
                           [('identity', np.eye(3)), ('estimated', H_first)] + ([('refined', H_est)] if args.refine else []))
+            H_mi = None
             if args.mi_refine:
-                mi_refine(data['optical']['image'][:1], data['thermal']['image'][:1], H_est, pred)
+                H_mi = mi_refine(data['optical']['image'][:1], data['thermal']['image'][:1], H_est, pred)
             print('Ground Truth Homography:')
             print(H_gt)
             print('--------------------------------------------------------')
@@ -292,6 +319,11 @@ def main(argv=None):
                                     match_distance=np.array([m.distance for m in matches], dtype=np.float32),
                                     homography_estimated=H_est, homography_ground_truth=H_gt,
                                     warped_optical=warped_image[0, 0].cpu().numpy())
+            if args.plot and args.plot_dir:
+                # under the final estimate: the refined one with --refine, the MI-aligned one with --mi-refine
+                names = write_plots(args.plot_dir, data['optical']['image'][:1], data['thermal']['image'][:1], kpo, kpt, matches,
+                                    mask, H_est if H_mi is None else H_mi, args.radius)
+                print('Wrote {} to {}'.format(', '.join(names), args.plot_dir))
 
 
 if __name__ == "__main__":

@@ -4,7 +4,8 @@
 for a single sample or a batch (-b).  -e computes the keypoint repeatability of an image-pair dataset like the
 reference (utils.compute_repeatability_multispectral) and, for a single-image dataset with 'keypoints' labels, the
 detector precision / recall / mAP (utils.compute_detector_metrics) -- per-sample arithmetic on the GPU in both
-cases.  Drawing (-p) is replaced by a text summary."""
+cases.  The windows of -p are replaced by a text summary and, with --plot-dir, by PNG files drawn on the GPU
+(multipoint_amd.utils.drawing)."""
 import argparse
 import os
 import time
@@ -31,7 +32,41 @@ def build_parser():
     parser.add_argument('-t', dest='threshold', default=3, type=int, help='Distance threshold for two keypoints to be considered a match')
     parser.add_argument('-mask', dest='mask', action='store_true', help='If set invalid image pixels will be set to 0')
     parser.add_argument('-s', '--seed', default=0, type=int, help='Seed of the random generators')
+    parser.add_argument('--plot-dir', default=None, help='(extension) with -p: write the pictures the reference shows in windows '
+                        'into this directory as <i>_image[_optical|_thermal].png, <i>_prob*.png and <i>_prob_masked*.png')
     return parser
+
+
+def write_plots(plot_dir, data, outs, detection_threshold, radius, use_mask):
+    """The pictures of reference predict_keypoints.py:159-280, one set per sample i of the batch and per spectrum: the image
+    (times the valid mask with -mask) with the predictions -- (prob > threshold) * valid_mask -- as green rings of `radius` and
+    the label keypoints, where the dataset has them, as red rings of radius + 2; prob and prob * valid_mask at the reference's
+    display gain 0.9 / threshold.  Returns the file names."""
+    from multipoint_amd.utils import drawing
+    os.makedirs(plot_dir, exist_ok=True)
+    gain = 0.9 / detection_threshold
+    written = []
+    for side, out in outs.items():
+        d = data if side == 'image' else data[side]
+        suffix = '' if side == 'image' else '_' + side
+        B, _, H, W = d['image'].shape
+        mask = d['valid_mask'].reshape(B, H, W).to(torch.float32)
+        prob = out['prob'].reshape(B, H, W).to(torch.float32)
+        views = {'image': drawing.gray_to_rgb(d['image'], mask if use_mask else None),
+                 'prob': drawing.gray_to_rgb(prob, gain=gain), 'prob_masked': drawing.gray_to_rgb(prob, mask, gain=gain)}
+        labels = d.get('keypoints')
+        for i in range(B):
+            predicted = torch.nonzero((prob[i] > detection_threshold).float() * mask[i])
+            drawing.draw_keypoints(views['image'][i], predicted, radius=radius, color=(0, 255, 0))
+            if labels is not None:
+                kp = labels[i].squeeze()
+                if kp.shape == (H, W):
+                    kp = torch.nonzero(kp)
+                drawing.draw_keypoints(views['image'][i], kp, radius=radius + 2, color=(255, 0, 0))
+            for name, view in views.items():
+                written.append('%d_%s%s.png' % (i, name, suffix))
+                drawing.save_png(os.path.join(plot_dir, written[-1]), view[i])
+    return written
 
 
 def main(argv=None):
@@ -102,6 +137,9 @@ def main(argv=None):
         for side, out in outs.items():
             n = (out['prob'] > pred['detection_threshold']).flatten(1).sum(1).cpu().numpy()
             print('{} keypoints per image: {}'.format(side, n.tolist()))
+        if args.plot and args.plot_dir:
+            names = write_plots(args.plot_dir, data, outs, pred['detection_threshold'], args.radius, args.mask)
+            print('Wrote {} pictures to {}'.format(len(names), args.plot_dir))
 
 
 if __name__ == "__main__":
