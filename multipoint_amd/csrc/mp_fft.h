@@ -10,9 +10,11 @@
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
 #define MP_FFT_HD __host__ __device__ __forceinline__
+#define MP_FFT_UNROLL _Pragma("unroll")
 #else
 struct float2 { float x, y; };
 #define MP_FFT_HD inline
+#define MP_FFT_UNROLL               // (a plain C++ compiler does not know the pragma)
 #endif
 
 #define MP_FFT_MAX_PASSES 12
@@ -87,11 +89,11 @@ MP_FFT_HD void fft_pass(const float2* in, float2* out, int N, int cshift, int r,
         const int j = w >> cshift, c = w & cmask;
         const int k = pow2 ? (j & (Ns - 1)) : j % Ns;
         float2 v[5];
-#pragma unroll
+        MP_FFT_UNROLL
         for (int q = 0; q < 5; ++q)
             if (q < r) v[q] = in[((j + q * M) << cshift) + c];
         if (Ns > 1) {
-#pragma unroll
+            MP_FFT_UNROLL
             for (int q = 1; q < 5; ++q)
                 if (q < r) {
                     float2 t = tw[q * k * tstep];
@@ -101,7 +103,7 @@ MP_FFT_HD void fft_pass(const float2* in, float2* out, int N, int cshift, int r,
         }
         fft_butterfly(v, r, sg);
         const int o = (j - k) * r + k;
-#pragma unroll
+        MP_FFT_UNROLL
         for (int q = 0; q < 5; ++q)
             if (q < r) out[((o + q * Ns) << cshift) + c] = v[q];
     }

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import lghd_restatement as R
+from lghd_shape_cases import check_orientation
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -144,16 +145,9 @@ def test_fft_refuses_other_lengths(C):
 # ---- 3. orientation maps ----
 
 def _check_orientation(got, name):
-    """Every pixel whose float64 top-two magnitude gap is at least tau = 16 err32 carries the float64 arg-max; at most 1 % of a
-    scale's pixels lie below tau (a condition on the input, tests/test_lghd_host.py asserts it without a GPU)."""
+    """the rule of tests/lghd_shape_cases.py::check_orientation on a committed test image"""
     _, _, _, m64, err32, want = _reference(name)
-    gap = R.top_two_gap(m64)
-    decided = gap >= 16 * err32
-    assert np.all((~decided).reshape(4, -1).mean(1) <= 0.01)
-    wrong = got != want
-    print(name, 'pixels that differ from float64: %d, all with a gap below %.3g err32' % (wrong.sum(), (gap[wrong] / err32).max(initial=0)))
-    assert got.max() <= 5
-    assert not np.any(wrong & decided)
+    check_orientation(got, name, m64, err32, want)
 
 
 @pytest.mark.parametrize('name', ['noise_64x64', 'smooth_64x64', 'noise_96x120', 'smooth_96x120'])
