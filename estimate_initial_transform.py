@@ -1,0 +1,177 @@
+#!/usr/bin/env python3
+"""Estimate the initial transform align_images.py starts from, instead of measuring it by hand: ONE optical -> thermal
+homography for a whole recording, from the pooled matches of many of its pairs (multipoint_amd.utils.estimate_shared_homography
+on an MI355X).  A rig has one transform for all its frames; a single cross-spectral pair gives few matches and many wrong
+ones, a few hundred pairs together give thousands.
+
+    prepare_images.py  ->  estimate_initial_transform.py  ->  align_images.py  ->  check_alignment.py
+
+The flags -y -m -v -s and the `prediction:` keys of the yaml (nms, detection_threshold, topk, matching,
+reprojection_threshold, allow_gpu) are predict_align_image_pair.py's; -i is the directory of `<index>_optical.png` /
+`<index>_thermal.png` pairs (prepare_images.py's `preprocessed/`: the optical frames of one size, the thermal frames of
+another).  It works with a MultiPoint checkpoint and with the weight-free LGHD baseline (-m tests/golden/lghd -v none).
+
+Written next to the pairs (or to -o and its directory):
+  initial_transform.yaml          perspective: 3x3, thermal pixel -> optical pixel with h22 = 1 -- the inverse, taken in float64,
+                                  of the estimated optical -> thermal homography; the key and direction align_images.py reads
+  initial_transform_report.json   pairs read / used, matches pooled, inliers, cost before / after the polish, the inliers of every
+                                  pair and the number of pairs with at least 4 of them
+
+An existing yaml is not overwritten without --force: it may be a hand measurement.  When fewer than 4 inliers support the
+model, nothing is written and the exit status is 1.
+
+Not known: how well this works on real thermal / optical recordings -- no such data and no trained weights are in this
+repository; everything is verified on synthetic and planted data.  Look at the report (and at check_alignment.py's pictures)
+before trusting the file."""
+import argparse
+import json
+import os
+import random
+import sys
+
+import numpy as np
+import yaml
+
+YAML_NAME = 'initial_transform.yaml'
+REPORT_NAME = 'initial_transform_report.json'
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description='Estimate initial_transform.yaml of a directory of image pairs from their pooled matches')
+    parser.add_argument('-y', '--yaml-config', default='configs/config_image_pair_dataset_prediction.yaml', help='YAML config file')
+    parser.add_argument('-m', '--model-dir', default='model_weights/multipoint', help='Directory of the model')
+    parser.add_argument('-v', '--version', default='latest', help='Model version (name of the param file), none for no weights')
+    parser.add_argument('-i', '--input-dir', required=True, help='Directory of the <index>_optical.png / <index>_thermal.png pairs')
+    parser.add_argument('-o', '--output', default=None, help='The yaml file to write (default: <input-dir>/initial_transform.yaml)')
+    parser.add_argument('-s', '--seed', default=0, type=int, help='Seed of the random generators and of the RANSAC sampling')
+    parser.add_argument('--max-pairs', default=0, type=int, help='Use this many evenly spaced pairs (0: all)')
+    parser.add_argument('--batch', default=8, type=int, help='Pairs per forward')
+    parser.add_argument('--max-iters', default=2000, type=int, help='RANSAC hypotheses')
+    parser.add_argument('--force', action='store_true', help='Overwrite an existing yaml file (it may be hand-measured)')
+    return parser
+
+
+def select_pairs(names, max_pairs):
+    """`max_pairs` evenly spaced entries of `names`, the first and the last among them (all of them when max_pairs <= 0 or
+    not below their number)."""
+    names = list(names)
+    if max_pairs <= 0 or max_pairs >= len(names):
+        return names
+    if max_pairs == 1:
+        return names[:1]
+    return [names[(i * (len(names) - 1)) // (max_pairs - 1)] for i in range(max_pairs)]
+
+
+def perspective_from_estimate(H):
+    """The matrix align_images.py reads (thermal pixel -> optical pixel, h22 = 1) from the estimated optical -> thermal
+    homography: its inverse in float64, divided by its last entry."""
+    H = np.asarray(H, np.float64).reshape(3, 3)
+    if not np.isfinite(H).all() or abs(np.linalg.det(H)) < 1e-12:
+        raise ValueError('the estimated homography is singular')
+    T = np.linalg.inv(H)
+    if abs(T[2, 2]) < 1e-12:
+        raise ValueError('the inverse of the estimated homography has h22 = 0')
+    return T / T[2, 2]
+
+
+def build_report(names_read, names_used, pair_offsets, mask, n_inliers, cost):
+    """The report's fields from the estimator's result: mask [N] per pooled match, pair_offsets [P+1] the rows of every used pair."""
+    mask = np.asarray(mask).reshape(-1) != 0
+    po = np.asarray(pair_offsets).reshape(-1)
+    if len(po) != len(names_used) + 1 or int(po[-1]) != len(mask):
+        raise ValueError('build_report: %d pairs, %d offsets, %d matches' % (len(names_used), len(po), len(mask)))
+    per_pair = {n: int(mask[int(po[p]):int(po[p + 1])].sum()) for p, n in enumerate(names_used)}
+    return {
+        'pairs_read': len(names_read),
+        'pairs_used': len(names_used),
+        'matches_pooled': int(len(mask)),
+        'inliers': int(n_inliers),
+        'cost_before_polish': None if cost is None else float(cost[0]),
+        'cost_after_polish': None if cost is None else float(cost[1]),
+        'inliers_per_pair': per_pair,
+        'pairs_with_4_inliers': int(sum(v >= 4 for v in per_pair.values())),
+    }
+
+
+def estimate_on_gpu(args, config, names):
+    """Forward, keypoints, descriptors and matches of the pairs `names` in batches, pooled into one group; then the pooled
+    RANSAC and its polish.  Returns (H 3x3 float64 optical -> thermal, mask [N] uint8, pair_offsets [P+1], n_inliers,
+    (cost before, cost after))."""
+    import torch
+
+    import multipoint_amd.utils as utils
+    from multipoint_amd.datasets.image_file_pairs import read_png_pair
+    from multipoint_amd.pipeline import PairPipeline
+    from multipoint_amd.utils import alignment
+    from predict_align_image_pair import load_network, select_device
+    device = select_device(config)
+    print('Estimating on device: {}'.format(device))
+    pred = config['prediction']
+    net = load_network(config, args.model_dir, args.version, device, args.seed)
+    pipe = PairPipeline(net, pred)
+    pts, counts = [], []
+    with torch.no_grad():
+        for at in range(0, len(names), max(args.batch, 1)):
+            pairs = [read_png_pair(args.input_dir, n) for n in names[at:at + max(args.batch, 1)]]
+            if len({p[0].shape[:2] for p in pairs}) != 1 or len({p[1].shape for p in pairs}) != 1:
+                raise ValueError('all optical frames of a directory must have one size, and all thermal frames one size')
+            optical = torch.stack([alignment.frames_to_float(p[0], device, single_bgr=p[0].ndim == 3) for p in pairs])[:, None]
+            thermal = alignment.frames_to_float(np.stack([p[1] for p in pairs]), device).reshape(len(pairs), 1, *pairs[0][1].shape)
+            pooled = utils.pool_matches(pipe.run_two_sized(optical.contiguous(), thermal.contiguous()))
+            pts.append(pooled.pts)
+            po = pooled.pair_offsets.cpu().numpy()
+            counts.extend(int(c) for c in po[1:] - po[:-1])
+    pair_offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    n = int(pair_offsets[-1])
+    if n < 4:
+        return np.zeros((3, 3)), np.zeros(n, np.uint8), pair_offsets, 0, None
+    allp = utils.PooledMatches(torch.cat(pts).contiguous(), None, None, torch.tensor([0, n], dtype=torch.int32, device=device))
+    thr = float(pred.get('reprojection_threshold', 3))
+    H0, _, _ = utils.find_homography_pooled(allp, thr, max_iters=args.max_iters, seed=args.seed)
+    H, mask, nin, cost = utils.refine_homography_pooled(allp, H0, thr)
+    cost = cost[0].cpu().numpy()
+    return H[0].cpu().numpy(), mask.cpu().numpy(), pair_offsets, int(nin[0]), (float(cost[0]), float(cost[1]))
+
+
+def main(argv=None, estimator=estimate_on_gpu):
+    args = build_parser().parse_args(argv)
+    random.seed(args.seed)
+    np.random.seed(args.seed)
+    out_yaml = args.output or os.path.join(args.input_dir, YAML_NAME)
+    out_report = os.path.join(os.path.dirname(out_yaml) or '.', REPORT_NAME)
+    if os.path.exists(out_yaml) and not args.force:
+        print('%s exists (it may be hand-measured): pass --force to overwrite it' % out_yaml, file=sys.stderr)
+        return 2
+    with open(args.yaml_config, 'r') as f:
+        config = yaml.load(f, Loader=yaml.FullLoader)
+    with open(os.path.join(args.model_dir, 'params.yaml'), 'r') as f:
+        config['model'] = yaml.load(f, Loader=yaml.FullLoader)['model']      # overwrite the model params
+    from multipoint_amd.datasets.image_file_pairs import ImageFilePairs
+    names_read = ImageFilePairs({'directory': args.input_dir}).memberslist
+    names = select_pairs(names_read, args.max_pairs)
+    if not names:
+        print('no <index>_optical.png / <index>_thermal.png pairs in %s' % args.input_dir, file=sys.stderr)
+        return 1
+    print('Using {} of {} pairs'.format(len(names), len(names_read)))
+    H, mask, pair_offsets, n_inliers, cost = estimator(args, config, names)
+    report = build_report(names_read, names, pair_offsets, mask, n_inliers, cost)
+    print('Matches pooled: {}  inliers: {}  pairs with at least 4 inliers: {} of {}'.format(
+        report['matches_pooled'], report['inliers'], report['pairs_with_4_inliers'], report['pairs_used']))
+    if n_inliers < 4:
+        print('fewer than 4 inliers support a model: nothing written', file=sys.stderr)
+        return 1
+    T = perspective_from_estimate(H)
+    print('Estimated Homography (optical -> thermal):')
+    print(np.asarray(H))
+    print('perspective (thermal -> optical):')
+    print(T)
+    with open(out_yaml, 'wt') as fh:
+        yaml.safe_dump({'perspective': [[float(v) for v in row] for row in T]}, fh)
+    with open(out_report, 'wt') as fh:
+        json.dump(report, fh, indent=1, sort_keys=True)
+    print('Wrote {} and {}'.format(out_yaml, out_report))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -309,6 +309,44 @@ int mp_refine_homography(mp_handle* h, const int* kp_yx, const int* kp_count, co
                          double reproj_threshold, int iters, double* homography, unsigned char* inlier_mask, int* n_inliers,
                          double* cost /* [P][2] or NULL */, void* stream);
 
+/* ---- pooled homography: ONE model per group of pairs, from the matches of all of them (an extension; the reference leaves the
+ * initial transform of a recording to a hand measurement).  A rig has one optical -> thermal transform for a whole recording; a
+ * single cross-spectral pair has few matches and many wrong ones, many pairs together have thousands.  The algorithm is
+ * mp_find_homography's and mp_refine_homography's with the group index in the place of the pair index (sampling is
+ * sample4(seed, g, t, n_g)), so a group that holds one pair gets that pair's model; the correspondences live in global memory
+ * instead of LDS, so there is no 3200 limit.  Results are bit-identical from run to run (integer atomics only).
+ *
+ * mp_pool_matches compacts the match lists of P pairs (lists as for mp_find_homography: slot 2p optical, 2p+1 thermal; any K):
+ *   groups        device int32 [P], the group id of every pair, NON-DECREASING, in [0, G) -- or NULL: one group (G must be 1).
+ *                 Unchecked (device data); ids that decrease give group ranges that are wrong but never out of bounds
+ *   pts           device fp32 [capacity][4], 16-byte aligned: (x, y) optical, (u, v) thermal of every match with
+ *                 0 <= match_idx < thermal count, pair-major, query order inside a pair
+ *   query_index   device int32 [capacity]: the optical keypoint (row of match_idx) each row of pts came from
+ *   capacity      rows of pts / query_index; rows beyond it are dropped, so it must reach pair_offsets[P] (P * K always does)
+ *   pair_offsets  device int32 [P + 1]: pair p owns rows pair_offsets[p] .. pair_offsets[p + 1]; pair_offsets[P] = N
+ *   group_offsets device int32 [G + 1]: group g owns rows group_offsets[g] .. group_offsets[g + 1] (empty groups allowed)
+ *   workspace     device scratch of mp_pooled_workspace_bytes(P, G, max_iters) bytes (any max_iters >= 1 for this call)
+ * mp_find_homography_pooled estimates one model per group of a pts list (from mp_pool_matches or the caller's own fp32 points):
+ *   N             rows of pts, 0 <= N < 2^24; 0 < G <= 65535; 0 < max_iters <= 2^20
+ *   homography    device double [G][9], optical (x, y, 1) -> thermal; all zeros for a group with fewer than 4 rows or without a
+ *                 hypothesis of 4 inliers
+ *   inlier_mask   device uint8 [N], one per row of pts (all zeros in a group without a model); n_inliers int32 [G]
+ * mp_refine_homography_pooled is mp_refine_homography on the groups: homography [G][9] in / out, inlier_mask [N] / n_inliers [G]
+ * of the INPUT estimate, cost [G][2] or NULL.
+ * mp_pooled_chunk reports the points per staged chunk of the scoring kernel and the most workgroups that share one group's
+ * points (the sizes at which the kernel changes path; for tests). */
+int mp_pooled_chunk(int* chunk_points, int* max_splits);
+int mp_pooled_workspace_bytes(int P, int G, int max_iters, long long* bytes);
+int mp_pool_matches(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, const int* groups /* [P] or NULL */,
+                    int P, int K, int G, float* pts, int* query_index, long long capacity, int* pair_offsets, int* group_offsets,
+                    void* workspace, long long workspace_bytes, void* stream);
+int mp_find_homography_pooled(mp_handle* h, const float* pts, const int* group_offsets, long long N, int G,
+                              double reproj_threshold, int max_iters, unsigned long long seed, double* homography,
+                              unsigned char* inlier_mask, int* n_inliers, void* workspace, long long workspace_bytes, void* stream);
+int mp_refine_homography_pooled(mp_handle* h, const float* pts, const int* group_offsets, long long N, int G,
+                                double reproj_threshold, int iters, double* homography, unsigned char* inlier_mask, int* n_inliers,
+                                double* cost /* [G][2] or NULL */, void* stream);
+
 /* ---- single-image detector metrics: multipoint/utils/evaluation.py:10-97 (predict_keypoints.py:88-104) ----
  * mp_detector_metrics replaces compute_tp_fp_dist (evaluation.py:56-97) for B heat maps at once:
  *   prob          fp32 [B][H][W]  detector map after valid mask / NMS (evaluation.py:19-25)

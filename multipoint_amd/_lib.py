@@ -119,6 +119,14 @@ SIGNATURES = {
                                    ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p]),
     'mp_refine_homography': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_int,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'mp_pooled_chunk': (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    'mp_pooled_workspace_bytes': (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
+    'mp_pool_matches': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_ll,
+                                c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
+    'mp_find_homography_pooled': (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_int, ctypes.c_double, c_int, ctypes.c_ulonglong,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
+    'mp_refine_homography_pooled': (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_int, ctypes.c_double, c_int, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p]),
     'mp_detector_metrics': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'mp_warp_perspective': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,

@@ -391,6 +391,22 @@ void launch_ransac_homography(const int* kp_yx, const int* kp_count, const int* 
 void launch_refine_homography(const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K, double thr, int iters,
                               double* H_io, unsigned char* mask, int* n_inliers, double* cost, hipStream_t s);
 
+// pooled RANSAC homography (homography_pooled.hip): one model per group of pairs from their compacted matches
+constexpr int MP_POOLED_CHUNK = 1024;        // points per staged LDS chunk of the scoring kernel
+constexpr int MP_POOLED_MAX_SPLITS = 64;     // most workgroups that share the points of one (hypothesis block, group)
+// pts [capacity][4] fp32 (16-byte aligned) / query_index [capacity]: the usable matches of all pairs, pair-major in query order;
+// pair_offsets [P + 1], group_offsets [G + 1] (groups: device [P] non-decreasing ids or NULL = one group); pair_cnt [P] scratch
+void launch_pool_matches(const int* kp_yx, const int* kp_count, const int* match_idx, const int* groups, int P, int K, int G,
+                         float* pts, int* query_index, long long capacity, int* pair_offsets, int* group_offsets, int* pair_cnt,
+                         hipStream_t s);
+// counts [G][T] and mask [N] pre-set to 0; best [G] scratch; H_out [G][9], n_inliers [G]
+void launch_find_homography_pooled(const float* pts, const int* group_offsets, int N, int G, int T, double thr,
+                                   unsigned long long seed, unsigned int* counts, unsigned long long* best, double* H_out,
+                                   unsigned char* mask, int* n_inliers, hipStream_t s);
+// mask [N] pre-set to 0; cost [G][2] or NULL
+void launch_refine_homography_pooled(const float* pts, const int* group_offsets, int N, int G, double thr, int iters, double* H_io,
+                                     unsigned char* mask, int* n_inliers, double* cost, hipStream_t s);
+
 // single-image detector metrics (detector_metrics.hip; evaluation.py:56-97): best [B][H][W] scratch, rec_count / n_gt [B]
 // (all three pre-set to 0), records [B][H*W]
 void launch_detector_metrics(const float* prob, const unsigned char* gt, int B, int H, int W, float zero_thr,

@@ -241,6 +241,53 @@ class PairPipeline:
         # results on the side stream and reports non-convergence through check_converged())
         return self.run_converged(images, mask)
 
+    def run_two_sized(self, optical, thermal, mask_optical=None, mask_thermal=None):
+        """Pairs whose cameras deliver frames of two sizes ((P,1,Ho,Wo) and (P,1,Ht,Wt): prepare_images.py scales the optical
+        frame to the thermal frame's height and leaves the widths apart).  Frames of different shapes cannot be interleaved
+        into one batch, so each camera gets a forward and a keypoint list of its own (the exact, synchronising NMS; lists that
+        overflow are rebuilt at the size they need); the lists are then interleaved (slot 2p optical, 2p+1 thermal), described
+        with the descriptor sampler or `net.describe`, and matched like every other batch.  The PairResults' H / W are the
+        THERMAL frame's; `pair_metrics` is not meaningful on it (it tests both lists against one frame), and the tie-guard
+        redo of run_converged is not applied.  With equal shapes this is `self(optical, thermal, ...)`."""
+        if optical.shape[2:] == thermal.shape[2:]:
+            return self(optical, thermal, mask_optical, mask_thermal)
+        P = optical.shape[0]
+        if thermal.shape[0] != P or optical.dim() != 4 or thermal.dim() != 4:
+            raise ValueError('run_two_sized: need (P,1,H,W) optical and thermal batches of the same P, got %s and %s'
+                             % (tuple(optical.shape), tuple(thermal.shape)))
+        sides = []
+        for image, mask, flag in ((optical, mask_optical, True), (thermal, mask_thermal, False)):
+            out = self.net({'image': image, 'is_optical': torch.full((P, 1), flag, dtype=torch.bool)})
+            sides.append((out, mask, image.shape[2], image.shape[3]))
+        K = self.capacity or (self.topk if self.topk > 0 else 4096)
+        for attempt in range(6):
+            if attempt == 5:
+                raise RuntimeError('run_two_sized: keypoint lists did not settle after 5 passes (capacity %d)' % K)
+            lists = []
+            for out, mask, h, w in sides:
+                if self.nms > 0:
+                    lists.append(U.detect_keypoints(out['prob'], self.nms, self.thr, keep_top_k=self.topk, capacity=K, valid_mask=mask))
+                else:
+                    lists.append(U.extract_keypoints(out['prob'], self.thr, capacity=K, valid_mask=mask))
+            need = 0 if self._capacity_is_exact(K) else max(int(l[2].max()) for l in lists)
+            if need <= K:
+                break
+            K = ((need + 255) // 256) * 256
+        descs = []
+        for (out, mask, h, w), (kp, sc, cnt) in zip(sides, lists):
+            descs.append(self.net.describe(out, kp, cnt) if 'orientation' in out
+                         else U.interpolate_descriptors_batched(kp, cnt, out['desc'], h, w))
+        kp, sc, cnt, desc = (torch.stack((a, b), dim=1).reshape(2 * P, *a.shape[1:]).contiguous()
+                             for a, b in zip(lists[0] + (descs[0],), lists[1] + (descs[1],)))
+        lay = dict(pair_stride=2 * K * desc.shape[2], count_stride=2)
+        if self.match_mode == 'mutual':
+            midx, mdist, mcnt = match_pairs(desc, cnt, desc[1:], cnt[1:], self.match_threshold, **lay)
+        else:
+            midx, mdist, mcnt = nearest_pairs(desc, cnt, desc[1:], cnt[1:], self.match_ratio, **lay)
+        res = PairResults(kp, sc, cnt, desc, midx, mdist, mcnt, thermal.shape[2], thermal.shape[3], self.match_mode)
+        self._last = res
+        return res
+
     def run_converged(self, images, valid_mask=None, is_optical=None):
         """One batch with a guaranteed-exact NMS, for the dataset drivers (evaluation loops): the fixed number of
         asynchronous rounds first; if that left candidates undecided (chains of dependent decisions longer than

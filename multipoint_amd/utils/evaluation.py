@@ -8,6 +8,7 @@ in the reference (:360-419).
 The RANSAC homography estimate (:330-349, cv2.findHomography) runs on the GPU as well (mp_find_homography: same
 algorithm family, not OpenCV's RNG, so estimates agree with OpenCV's only to the reprojection tolerance); the
 4-corner error derived from it (:351-356) is four points of numpy per pair."""
+import collections
 import ctypes
 
 import numpy as np
@@ -185,6 +186,184 @@ def find_homography_points(optical_pts, thermal_pts, reproj_threshold=3.0, max_i
     if int(nin[0]) < 4:
         return None, np.zeros(n, np.uint8)
     return Hm[0].cpu().numpy(), mask[0].cpu().numpy()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# pooled homography: one model per GROUP of pairs (mp_pool_matches, mp_find_homography_pooled, mp_refine_homography_pooled)
+# ----------------------------------------------------------------------------------------------------------------------
+PooledMatches = collections.namedtuple('PooledMatches', 'pts query_index pair_offsets group_offsets')
+PooledMatches.__doc__ = """The usable matches of P pairs as one compact device list (pool_matches):
+pts [N,4] float32 (x, y optical, u, v thermal), pair-major and in query order inside a pair; query_index [N] int32, the optical
+keypoint of each row; pair_offsets [P+1] int32 and group_offsets [G+1] int32, the rows a pair / a group owns."""
+SharedHomography = collections.namedtuple('SharedHomography', 'H mask n_inliers cost pooled')
+
+MAX_POOLED_MATCHES = (1 << 24) - 1    # rows of one pooled call
+MAX_POOLED_GROUPS = 65535
+MAX_POOLED_ITERS = 1 << 20
+
+
+def pooled_chunk():
+    """(points per staged LDS chunk of the pooled scoring kernel, most point splits of a launch): the group sizes at which the
+    kernel changes path."""
+    c, s = ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load_library().mp_pooled_chunk(ctypes.byref(c), ctypes.byref(s)))
+    return c.value, s.value
+
+
+def _pooled_workspace(h, P, G, T, dev):
+    n = ctypes.c_longlong()
+    h.check(h.lib.mp_pooled_workspace_bytes(int(P), int(G), int(T), ctypes.byref(n)))
+    return torch.empty((max(n.value, 16),), dtype=torch.uint8, device=dev)
+
+
+def _group_ids(groups, P):
+    """The group id of every pair as a host int32 array and the number of groups; None, 1 for one group."""
+    if groups is None:
+        return None, 1
+    g = groups.detach().cpu().numpy() if isinstance(groups, torch.Tensor) else np.asarray(groups)
+    if g.shape != (P,) or g.dtype.kind not in 'iu':
+        raise ValueError('pool_matches: groups must be %d integers, one per pair; got shape %s, dtype %s' % (P, g.shape, g.dtype))
+    if P and int(g.min()) < 0:
+        raise ValueError('pool_matches: group ids must be non-negative')
+    if (np.diff(g.astype(np.int64)) < 0).any():
+        raise ValueError('pool_matches: group ids must be non-decreasing (a group is a contiguous run of pairs)')
+    G = int(g.max()) + 1 if P else 1
+    if G > MAX_POOLED_GROUPS:
+        raise ValueError('pool_matches: at most %d groups, got %d' % (MAX_POOLED_GROUPS, G))
+    return np.ascontiguousarray(g, dtype=np.int32), G
+
+
+def pool_matches(res, groups=None):
+    """The matches of the pairs of a PairResults as one compact list (mp_pool_matches), for estimating ONE homography per group
+    of pairs.  `groups`: the group id of every pair, non-decreasing (a group is a contiguous run of pairs; ids without a pair
+    are empty groups), default: all pairs in one group.  A match is dropped as the per-pair estimate drops it (no partner, or
+    a partner index beyond the thermal list).  Returns a PooledMatches; synchronises once to learn the number of matches."""
+    P, K = res.num_pairs, res.kp_yx.shape[1]
+    gid, G = _group_ids(groups, P)
+    if P <= 0 or K <= 0 or P * K > 0x7fffffff:
+        raise ValueError('pool_matches: need P > 0, K > 0 and P * K < 2^31; got P = %d, K = %d' % (P, K))
+    res.wait()
+    dev = res.kp_yx.device
+    pts = torch.empty((P * K, 4), dtype=torch.float32, device=dev)
+    qidx = torch.empty((P * K,), dtype=torch.int32, device=dev)
+    po = torch.empty((P + 1,), dtype=torch.int32, device=dev)
+    go = torch.empty((G + 1,), dtype=torch.int32, device=dev)
+    gdev = torch.from_numpy(gid).to(dev) if gid is not None else None
+    h = _lib.get_handle(dev)
+    with torch.cuda.device(dev):
+        ws = _pooled_workspace(h, P, G, 1, dev)
+        h.check(h.lib.mp_pool_matches(h.ptr, _lib.ptr(res.kp_yx.contiguous()), _lib.ptr(res.kp_count.contiguous()),
+                                      _lib.ptr(res.match_idx.contiguous()), _lib.ptr(gdev), P, K, G, _lib.ptr(pts), _lib.ptr(qidx),
+                                      P * K, _lib.ptr(po), _lib.ptr(go), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+    n = int(po[P])
+    return PooledMatches(pts[:n], qidx[:n], po, go)
+
+
+def _check_pooled(fn, pooled, reproj_threshold):
+    if not float(reproj_threshold) > 0.0:
+        raise ValueError('%s: reproj_threshold must be positive' % fn)
+    pts, go = pooled.pts, pooled.group_offsets
+    if pts.dim() != 2 or pts.shape[1] != 4 or pts.dtype != torch.float32:
+        raise ValueError('%s: pts must be [N,4] float32, got %s %s' % (fn, tuple(pts.shape), pts.dtype))
+    if pts.shape[0] > MAX_POOLED_MATCHES:
+        raise ValueError('%s: at most %d correspondences per call, got %d' % (fn, MAX_POOLED_MATCHES, pts.shape[0]))
+    if go.dim() != 1 or go.dtype != torch.int32 or not 2 <= go.numel() <= MAX_POOLED_GROUPS + 1:
+        raise ValueError('%s: group_offsets must be [G+1] int32 with 1 <= G <= %d' % (fn, MAX_POOLED_GROUPS))
+    return pts.shape[0], go.numel() - 1
+
+
+def find_homography_pooled(pooled, reproj_threshold=3.0, max_iters=2000, seed=0):
+    """One RANSAC homography per group of a PooledMatches (mp_find_homography_pooled): find_homography's algorithm with the
+    group in the place of the pair -- `max_iters` hypotheses per group from 4 of its correspondences, the most inliers win, the
+    winner's inliers are refitted by the normalised DLT -- on lists of any length.  Returns (H [G,3,3] float64 optical (x,y,1)
+    -> thermal, all zeros for a group with fewer than 4 correspondences or without a model; mask [N] uint8, one per row of
+    pooled.pts; n_inliers [G] int32).  The same input gives the same bits on every run."""
+    max_iters = int(max_iters)
+    N, G = _check_pooled('find_homography_pooled', pooled, reproj_threshold)
+    if not 0 < max_iters <= MAX_POOLED_ITERS:
+        raise ValueError('find_homography_pooled: max_iters must be in [1, %d]' % MAX_POOLED_ITERS)
+    dev = pooled.pts.device
+    pts = pooled.pts.contiguous()
+    Hm = torch.empty((G, 3, 3), dtype=torch.float64, device=dev)
+    mask = torch.empty((N,), dtype=torch.uint8, device=dev)
+    nin = torch.empty((G,), dtype=torch.int32, device=dev)
+    h = _lib.get_handle(dev)
+    with torch.cuda.device(dev):
+        ws = _pooled_workspace(h, 0, G, max_iters, dev)
+        h.check(h.lib.mp_find_homography_pooled(h.ptr, _lib.ptr(pts), _lib.ptr(pooled.group_offsets.contiguous()), N, G,
+                                                float(reproj_threshold), max_iters, int(seed), _lib.ptr(Hm), _lib.ptr(mask),
+                                                _lib.ptr(nin), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+    return Hm, mask, nin
+
+
+def refine_homography_pooled(pooled, H, reproj_threshold=3.0, iters=10):
+    """refine_homography on the groups of a PooledMatches (mp_refine_homography_pooled): `H` ([G,3,3] or [G,9] float64) is
+    polished over the group's correspondences within reproj_threshold of it.  Returns (H [G,3,3] float64 with h22 = 1, all zeros
+    where the input is all zeros or has fewer than 4 inliers; mask [N] uint8 and n_inliers [G] int32 of the INPUT estimate's
+    inlier set; cost [G,2] float64: the sum of squared residuals over it before / after)."""
+    iters = int(iters)
+    N, G = _check_pooled('refine_homography_pooled', pooled, reproj_threshold)
+    if not 0 <= iters <= 1000:
+        raise ValueError('refine_homography_pooled: iters must be in [0, 1000]')
+    Hm = torch.as_tensor(H, dtype=torch.float64)
+    if Hm.numel() != G * 9:
+        raise ValueError('refine_homography_pooled: need one 3x3 matrix per group (%d), got %d values' % (G, Hm.numel()))
+    dev = pooled.pts.device
+    pts = pooled.pts.contiguous()
+    Hm = Hm.to(dev).reshape(G, 3, 3).clone().contiguous()                    # (polished in place: never the caller's tensor)
+    mask = torch.empty((N,), dtype=torch.uint8, device=dev)
+    nin = torch.empty((G,), dtype=torch.int32, device=dev)
+    cost = torch.empty((G, 2), dtype=torch.float64, device=dev)
+    h = _lib.get_handle(dev)
+    with torch.cuda.device(dev):
+        h.check(h.lib.mp_refine_homography_pooled(h.ptr, _lib.ptr(pts), _lib.ptr(pooled.group_offsets.contiguous()), N, G,
+                                                  float(reproj_threshold), iters, _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin),
+                                                  _lib.ptr(cost), _lib.stream_ptr(dev)))
+    return Hm, mask, nin, cost
+
+
+def estimate_shared_homography(res, groups=None, reproj_threshold=3.0, max_iters=2000, seed=0, polish=True, iters=10):
+    """One homography per group of pairs that share a transform (a fixed rig: one group for the whole recording): pool_matches,
+    find_homography_pooled and, with `polish`, refine_homography_pooled.  Returns a SharedHomography: H [G,3,3] float64, mask [N]
+    uint8 per pooled match, n_inliers [G] int32, cost [G,2] float64 before / after the polish (None without it) and the
+    PooledMatches (its pair_offsets / query_index lead from a mask byte back to the pair and the optical keypoint)."""
+    if not float(reproj_threshold) > 0.0:
+        raise ValueError('estimate_shared_homography: reproj_threshold must be positive')
+    if not 0 < int(max_iters) <= MAX_POOLED_ITERS:
+        raise ValueError('estimate_shared_homography: max_iters must be in [1, %d]' % MAX_POOLED_ITERS)
+    if not 0 <= int(iters) <= 1000:
+        raise ValueError('estimate_shared_homography: iters must be in [0, 1000]')
+    pooled = pool_matches(res, groups)
+    H, mask, nin = find_homography_pooled(pooled, reproj_threshold, max_iters, seed)
+    cost = None
+    if polish:
+        H, mask, nin, cost = refine_homography_pooled(pooled, H, reproj_threshold, iters)
+    return SharedHomography(H, mask, nin, cost, pooled)
+
+
+def find_homography_pooled_points(optical_xy, thermal_xy, reproj_threshold=3.0, max_iters=2000, seed=0, device=None):
+    """find_homography_pooled for ONE set of corresponding (x, y) points of any length, taken as float32 (sub-pixel positions
+    are kept; find_homography_points, with its 3200 limit and integer positions, stays what the per-pair drivers use).
+    Returns (H 3x3 float64 numpy or None, mask (N,) uint8)."""
+    a = np.asarray(optical_xy, dtype=np.float32).reshape(-1, 2); b = np.asarray(thermal_xy, dtype=np.float32).reshape(-1, 2)
+    n = len(a)
+    if len(b) != n:
+        raise ValueError('find_homography_pooled_points: %d optical and %d thermal points' % (n, len(b)))
+    if n > MAX_POOLED_MATCHES:
+        raise ValueError('find_homography_pooled_points: at most %d correspondences per call, got %d' % (MAX_POOLED_MATCHES, n))
+    if not float(reproj_threshold) > 0.0:
+        raise ValueError('find_homography_pooled_points: reproj_threshold must be positive')
+    if not 0 < int(max_iters) <= MAX_POOLED_ITERS:
+        raise ValueError('find_homography_pooled_points: max_iters must be in [1, %d]' % MAX_POOLED_ITERS)
+    if n < 4:
+        return None, np.zeros(n, np.uint8)
+    dev = _lib.require_cuda(device)
+    pts = torch.from_numpy(np.ascontiguousarray(np.concatenate([a, b], 1))).to(dev)
+    pooled = PooledMatches(pts, None, None, torch.tensor([0, n], dtype=torch.int32, device=dev))
+    Hm, mask, nin = find_homography_pooled(pooled, reproj_threshold, max_iters, seed)
+    if int(nin[0]) < 4:
+        return None, np.zeros(n, np.uint8)
+    return Hm[0].cpu().numpy(), mask.cpu().numpy()
 
 
 def _warp_yx(pts_yx, hmat):
