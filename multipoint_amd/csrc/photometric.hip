@@ -38,6 +38,8 @@ constexpr int MEAN_GROUP = 16;          // chunks whose leaves are summed in one
 constexpr int FULL_LEAVES = 64;         // a chunk of 8192 halves evenly down to 64 leaves of 128: a balanced tree
 constexpr int COL_TX = 16, COL_TY = 64; // column-filter tile (columns x output rows)
 constexpr int STACK = 64;               // pairwise-tree walk stacks (depth <= 7 for a chunk of 8192)
+// static LDS of shade_ellipse_kernel (vx, vy, rx, ry and three ints) in front of its dynamic spans, rounded up to 16 bytes
+constexpr size_t SHADE_STATIC_LDS = (4 * MAX_VERTS * sizeof(long long) + 3 * sizeof(int) + 15) & ~(size_t)15;
 
 // device noise: normals by Box-Muller from the counters 2p and 2p + 1 of hash_uniform (mp_device.h)
 __device__ __forceinline__ double hash_normal(unsigned long long key, unsigned long long p)
@@ -500,12 +502,14 @@ size_t photometric_workspace_bytes(int n, int H, int W, int n_ellipses)
     return photo_workspace(nullptr, n, H, W, n_ellipses).bytes;
 }
 
-// the largest dynamic LDS request of a launch of these plans (the caller checks it against the device limit)
+// the largest LDS request of a launch of these plans (the caller checks it against the device limit): the dynamic part of
+// the blur kernels, dynamic plus static of shade_ellipse_kernel (its four vertex arrays and three ints)
 size_t photometric_lds_bytes(const mp_photometric_plan* plans, int n, int H, int W)
 {
-    size_t b = sizeof(int) * 2 * (size_t)H;
+    size_t b = 0;
     for (int s = 0; s < MP_PHOTO_MAX_OPS; ++s) {
         if (!any_kind(plans, n, s, MP_PHOTO_SHADE)) continue;
+        if (max_ellipses(plans, n, s) > 0) b = max(b, sizeof(int) * 2 * (size_t)H + SHADE_STATIC_LDS);
         const int k = max_blur(plans, n, s), r = k / 2;
         b = max(b, sizeof(float) * (size_t)(k + W + 2 * r));
         b = max(b, sizeof(float) * (size_t)(k + (COL_TY + 2 * r) * COL_TX));

@@ -778,7 +778,7 @@ static int photometric_check(mp_handle* h, const char* fn, int n, int H, int W, 
             }
         }
     }
-    if (photometric_lds_bytes(plans, n, H, W) > 65536) return fail(h, MP_EINVAL, f + ": frame too wide for the blur size");
+    if (photometric_lds_bytes(plans, n, H, W) > 65536) return fail(h, MP_EINVAL, f + ": frame too wide for the blur size, or too high for the ellipse spans, to fit the LDS");
     if (!workspace || workspace_bytes < (long long)photometric_workspace_bytes(n, H, W, n_ellipses))
         return fail(h, MP_EINVAL, f + ": workspace smaller than mp_photometric_workspace_bytes");
     return MP_OK;
