@@ -1,7 +1,12 @@
-// Device functions shared by the per-pair RANSAC (homography.hip: a pair's correspondences in LDS) and the pooled one
-// (homography_pooled.hip: a group's correspondences in global memory): counter-based sampling, the exact 4-point solve, the
-// forward reprojection test, the 9x9 eigen-solver of the normalised-DLT refit and the pieces of the Levenberg-Marquardt
-// polish.  Both files go through the same code, so the same correspondences give the same model in either.
+// The homography estimators' device code, written once (homography.hip: one model per pair; homography_pooled.hip: one model
+// per group of pairs): the ordered compaction of a pair's usable matches, counter-based sampling, the exact 4-point solve, the
+// forward reprojection test, the normalised-DLT refit and the Levenberg-Marquardt polish.
+// One body, two views.  refit_kernel, refine_kernel, lm_sums and hypothesis are templates on where the correspondences live
+// and how an outlier is marked: PairView (a pair's list in LDS) or PooledView (a group's rows in global memory).  A kernel gets
+// its view from a Source, the struct of launch arguments that locates the points of pair / group `index` (PairSource in
+// homography.hip gathers them into LDS, PooledSource in homography_pooled.hip looks up the group's range).  Every
+// floating-point operation, reduction and barrier is in the shared body, so the same correspondences give the same bits on
+// either route.
 #pragma once
 #include "mp_common.h"
 #include "mp_device.h"
@@ -65,6 +70,93 @@ __device__ __forceinline__ bool inlier(const double* h, double x, double y, doub
     return du * du + dv * dv <= thr2;
 }
 
+// ---- a pair's usable matches ----
+// the partner j = match_idx[p][i] of query i if the match is usable (i < no, 0 <= j < nt), else -1
+__device__ __forceinline__ int usable_match(const int* match_idx, int p, int K, int i, int no, int nt)
+{
+    if (i >= no) return -1;
+    const int j = match_idx[(size_t)p * K + i];
+    return (j >= 0 && j < nt) ? j : -1;
+}
+
+// the correspondence (x, y) -> (u, v) of query i and partner j of pair p (kp_yx: [2P][K] (y, x), slot 2p optical, 2p + 1 thermal)
+__device__ __forceinline__ float4 match_point(const int* kp_yx, int p, int K, int i, int j)
+{
+    const int* o = kp_yx + ((size_t)(2 * p) * K + i) * 2;
+    const int* t = kp_yx + ((size_t)(2 * p + 1) * K + j) * 2;
+    return make_float4((float)o[1], (float)o[0], (float)t[1], (float)t[0]);
+}
+
+// Ordered compaction of pair p's usable matches by a workgroup of 256 threads (all of them call it): the queries are walked in
+// steps of 256, a survivor's position comes from the wave's ballot and the prefix of the four waves' counts -- query order, as
+// the reference's list comprehension keeps it, and no atomics.  put(pos, i, j) is called once per usable match; returns their
+// number.
+template <class Put>
+__device__ int compact_matches(const int* kp_count, const int* match_idx, int p, int K, Put put)
+{
+    __shared__ int run_s;
+    __shared__ int wave_base[4];
+    const int tid = threadIdx.x, wv = tid >> 6, ln = tid & 63;
+    if (tid == 0) run_s = 0;
+    __syncthreads();
+    const int no = min(kp_count[2 * p], K), nt = min(kp_count[2 * p + 1], K);
+    for (int i0 = 0; i0 < no; i0 += 256) {
+        const int i = i0 + tid;
+        const int j = usable_match(match_idx, p, K, i, no, nt);
+        const unsigned long long bal = __ballot(j >= 0);
+        if (ln == 0) wave_base[wv] = __popcll(bal);
+        __syncthreads();
+        if (tid == 0) {
+            int run = run_s;
+            for (int w = 0; w < 4; ++w) { const int c = wave_base[w]; wave_base[w] = run; run += c; }
+            run_s = run;
+        }
+        __syncthreads();
+        if (j >= 0) put(wave_base[wv] + __popcll(bal & ((1ull << ln) - 1ull)), i, j);
+        __syncthreads();
+    }
+    return run_s;
+}
+
+// ---- the two point views ----
+// a pair's list in LDS: pts [n][4] floats (x, y, u, v), qidx [n] the query index of each match, mask_row the pair's row of the
+// mask (one byte per optical keypoint).  An outlier is marked by a NaN x.
+struct PairView {
+    float* pts;
+    const int* qidx;
+    unsigned char* mask_row;
+    int n;
+    __device__ float4 get(int i) const { return make_float4(pts[i * 4], pts[i * 4 + 1], pts[i * 4 + 2], pts[i * 4 + 3]); }
+    __device__ bool is_inlier(int i) const { return pts[i * 4] == pts[i * 4]; }
+    __device__ void set_inlier(int i, bool in) const
+    {
+        mask_row[qidx[i]] = in ? 1 : 0;
+        if (!in) pts[i * 4] = __int_as_float(0x7fc00000);
+    }
+};
+
+// a group's rows in global memory, pts and mask advanced by the group's start.  An outlier is known by its mask byte; a thread
+// reads only bytes it wrote itself (the bodies walk i = tid, tid + 256, ... in every pass).
+struct PooledView {
+    const float4* pts;
+    unsigned char* mask;
+    int n;
+    __device__ float4 get(int i) const { return pts[i]; }
+    __device__ bool is_inlier(int i) const { return mask[i] != 0; }
+    __device__ void set_inlier(int i, bool in) const { mask[i] = in ? 1 : 0; }
+};
+
+// hypothesis t of pair / group `index` from 4 sampled points of the view; false if the 4-point system is singular
+template <class View>
+__device__ __forceinline__ bool hypothesis(View pv, unsigned long long seed, int index, int t, double* h)
+{
+    int idx[4];
+    sample4(seed, index, t, pv.n, idx);
+    double x[4], y[4], u[4], v[4];
+    for (int k = 0; k < 4; ++k) { const float4 q = pv.get(idx[k]); x[k] = q.x; y[k] = q.y; u[k] = q.z; v[k] = q.w; }
+    return solve4(x, y, u, v, h);
+}
+
 // symmetric 9x9 eigen-decomposition by cyclic Jacobi; returns the eigenvector of the smallest eigenvalue
 __device__ void smallest_eigvec9(double a[9][9], double* out)
 {
@@ -122,6 +214,96 @@ __device__ void dlt_finish(const double* ata, double cx, double cy, double cu, d
     }
     const double nrm = fabs(out[2][2]) > 1e-300 ? 1.0 / out[2][2] : 1.0;
     for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) H_out[r * 3 + c] = out[r][c] * nrm;
+}
+
+// the sum of v over the 256 threads of the workgroup (a tree in LDS: the same bits on every run).  All 256 threads call it.
+__device__ __forceinline__ double block_sum(double v, double* red /* [256] LDS */)
+{
+    const int tid = threadIdx.x;
+    red[tid] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// One workgroup of 256 threads per pair / group: re-derive the winning hypothesis best[index], mark its inliers in the view,
+// refit by normalised DLT over them.  H_out[index] and n_inliers[index] are zero if there is no model.
+// (The body is the kernel itself and not a function that two kernels call: how the compiler contracts a sum of two products
+// into a multiply-add, as in smallest_eigvec9's rotations, depends on how deep the code sits in the inlining order.)
+template <class Source>
+__global__ __launch_bounds__(256) void refit_kernel(Source src, double thr, unsigned long long seed,
+                                                    const unsigned long long* __restrict__ best, double* __restrict__ H_out,
+                                                    int* __restrict__ n_inliers)
+{
+    __shared__ double red[256];
+    __shared__ double hsh[9];
+    __shared__ double ata[81];
+    const int index = blockIdx.x, tid = threadIdx.x;
+    const auto pv = src.view(index);
+    const int n = pv.n;
+    const unsigned long long b = best[index];
+    const int cnt = (int)(b >> 32);
+    if (n < 4 || cnt < 4) {
+        if (tid == 0) { n_inliers[index] = 0; for (int k = 0; k < 9; ++k) H_out[index * 9 + k] = 0.0; }
+        return;
+    }
+    if (tid == 0) {
+        double h[9];
+        hypothesis(pv, seed, index, 0x7fffffff - (int)(b & 0xffffffffull), h);
+        for (int k = 0; k < 9; ++k) hsh[k] = h[k];
+    }
+    __syncthreads();
+    // inlier flags of the best hypothesis + normalisation statistics (centroid, mean distance) of both point sets
+    const double thr2 = thr * thr;
+    double h[9];
+    for (int k = 0; k < 9; ++k) h[k] = hsh[k];
+    double sx = 0, sy = 0, su = 0, sv = 0, sc = 0;
+    for (int i = tid; i < n; i += 256) {
+        const float4 q = pv.get(i);
+        const bool in = inlier(h, q.x, q.y, q.z, q.w, thr2);
+        pv.set_inlier(i, in);
+        if (in) { sx += q.x; sy += q.y; su += q.z; sv += q.w; sc += 1.0; }
+    }
+    const double m = block_sum(sc, red);
+    const double cx = block_sum(sx, red) / m, cy = block_sum(sy, red) / m, cu = block_sum(su, red) / m, cv = block_sum(sv, red) / m;
+    double d1 = 0, d2 = 0;
+    for (int i = tid; i < n; i += 256) {
+        if (!pv.is_inlier(i)) continue;
+        const float4 q = pv.get(i);
+        d1 += sqrt((q.x - cx) * (q.x - cx) + (q.y - cy) * (q.y - cy));
+        d2 += sqrt((q.z - cu) * (q.z - cu) + (q.w - cv) * (q.w - cv));
+    }
+    const double md1 = block_sum(d1, red) / m, md2 = block_sum(d2, red) / m;
+    const double s1 = md1 > 1e-12 ? 1.4142135623730951 / md1 : 1.0, s2 = md2 > 1e-12 ? 1.4142135623730951 / md2 : 1.0;
+    // A^T A of the 2m x 9 DLT matrix on the normalised points: every thread sums its points' share of the 45 entries of the
+    // upper triangle, thread 0 collects the block sums
+    double acc9[45];
+    for (int k = 0; k < 45; ++k) acc9[k] = 0.0;
+    for (int i = tid; i < n; i += 256) {
+        if (!pv.is_inlier(i)) continue;
+        const float4 q = pv.get(i);
+        const double x = (q.x - cx) * s1, y = (q.y - cy) * s1;
+        const double u = (q.z - cu) * s2, v = (q.w - cv) * s2;
+        const double r0[9] = {x, y, 1.0, 0.0, 0.0, 0.0, -u * x, -u * y, -u};
+        const double r1[9] = {0.0, 0.0, 0.0, x, y, 1.0, -v * x, -v * y, -v};
+        int k = 0;
+        for (int a = 0; a < 9; ++a) for (int c = a; c < 9; ++c, ++k) acc9[k] += r0[a] * r0[c] + r1[a] * r1[c];
+    }
+    {
+        int k = 0;
+        for (int a = 0; a < 9; ++a)
+            for (int c = a; c < 9; ++c, ++k) {
+                const double s = block_sum(acc9[k], red);
+                if (tid == 0) { ata[a * 9 + c] = s; ata[c * 9 + a] = s; }
+            }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        dlt_finish(ata, cx, cy, cu, cv, s1, s2, H_out + index * 9);
+        n_inliers[index] = (int)m;
+    }
 }
 
 // ---- the Levenberg-Marquardt polish ----
@@ -197,6 +379,96 @@ __device__ __forceinline__ void lm_reduce(const double* acc, double* wave_part /
     if (tid < LM_SUMS)
         out[tid] = ((wave_part[tid] + wave_part[LM_SUMS + tid]) + wave_part[2 * LM_SUMS + tid]) + wave_part[3 * LM_SUMS + tid];
     __syncthreads();
+}
+
+// out[0..44] = the sums of J^T J, J^T r and r.r at parameters h over the view's inliers.  Fixed order: a thread adds its inliers
+// i = tid, tid + 256, ..., then lm_reduce.  All 256 threads call it.
+template <class View>
+__device__ void lm_sums(View pv, const double* h, double* wave_part /* [4][LM_SUMS] LDS */, double* out)
+{
+    double acc[LM_SUMS];
+#pragma unroll
+    for (int k = 0; k < LM_SUMS; ++k) acc[k] = 0.0;
+    for (int i = threadIdx.x; i < pv.n; i += 256) {
+        if (!pv.is_inlier(i)) continue;
+        const float4 q = pv.get(i);
+        lm_add_point(acc, h, q.x, q.y, q.z, q.w);
+    }
+    lm_reduce(acc, wave_part, out);
+}
+
+// One workgroup of 256 threads per pair / group: mark the inliers of the input estimate H_io[index] in the view and polish it
+// over them.  cost_out (may be NULL): [index][2] = the cost before and after.
+template <class Source>
+__global__ __launch_bounds__(256) void refine_kernel(Source src, double thr, int iters, double* __restrict__ H_io,
+                                                     int* __restrict__ n_inliers, double* __restrict__ cost_out)
+{
+    __shared__ double wave_part[4 * LM_SUMS];
+    __shared__ double cur[LM_SUMS], cand[LM_SUMS];     // the sums at the accepted parameters / at the step being tried
+    __shared__ double hcur[8], htry[8];
+    __shared__ int count_s[4], state;                  // state: 0 = the trial's system was singular, 1 = evaluate htry
+    const int index = blockIdx.x, tid = threadIdx.x;
+    const auto pv = src.view(index);
+    const int n = pv.n;
+    double h[9];
+    for (int k = 0; k < 9; ++k) h[k] = H_io[index * 9 + k];
+    // the inliers of the INPUT estimate (an all-zero matrix has none: inlier() refuses w = 0)
+    const double thr2 = thr * thr;
+    int mine = 0;
+    for (int i = tid; i < n; i += 256) {
+        const float4 q = pv.get(i);
+        const bool in = inlier(h, q.x, q.y, q.z, q.w, thr2);
+        pv.set_inlier(i, in);
+        if (in) ++mine;
+    }
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
+    if ((tid & 63) == 0) count_s[tid >> 6] = mine;
+    __syncthreads();
+    const int m = count_s[0] + count_s[1] + count_s[2] + count_s[3];
+    if (m < 4 || !(fabs(h[8]) > 0.0) || !isfinite(h[8])) {
+        if (tid == 0) {
+            n_inliers[index] = m;
+            for (int k = 0; k < 9; ++k) H_io[index * 9 + k] = 0.0;
+            if (cost_out) { cost_out[index * 2] = 0.0; cost_out[index * 2 + 1] = 0.0; }
+        }
+        return;
+    }
+    if (tid < 8) hcur[tid] = h[tid] / h[8];
+    __syncthreads();
+    lm_sums(pv, hcur, wave_part, cur);
+    const double cost0 = cur[44];
+    double lam = 1e-3;                                  // (every thread follows thread 0's decisions through `state` and the sums)
+    for (int it = 0; it < iters; ++it) {
+        bool accepted = false;
+        for (int trial = 0; trial < 8 && !accepted; ++trial) {
+            if (tid == 0) {
+                double step[8];
+                const bool ok = lm_step(cur, lam, step);
+                for (int k = 0; k < 8; ++k) htry[k] = hcur[k] + step[k];
+                state = ok ? 1 : 0;
+            }
+            __syncthreads();
+            const bool ok = state != 0;
+            if (ok) lm_sums(pv, htry, wave_part, cand);
+            accepted = ok && cand[44] < cur[44];         // (a NaN cost is not an improvement)
+            __syncthreads();
+            if (accepted) {
+                if (tid < LM_SUMS) cur[tid] = cand[tid];
+                if (tid < 8) hcur[tid] = htry[tid];
+                lam = fmax(lam * 0.1, 1e-12);
+            } else {
+                lam *= 10.0;
+            }
+            __syncthreads();
+        }
+        if (!accepted) break;
+    }
+    if (tid == 0) {
+        n_inliers[index] = m;
+        for (int k = 0; k < 8; ++k) H_io[index * 9 + k] = hcur[k];
+        H_io[index * 9 + 8] = 1.0;
+        if (cost_out) { cost_out[index * 2] = cost0; cost_out[index * 2 + 1] = cur[44]; }
+    }
 }
 
 }  // namespace

@@ -1,4 +1,5 @@
-"""Developer tool (GPU box): what the guided matcher costs over the plain mutual one, and the time of the homography polish.
+"""Developer tool (GPU box): what the guided matcher costs over the plain mutual one, and the times of the per-pair homography
+estimate and its polish.
 
     python tools/bench_guided.py [--calls 200] [--repeats 3] [--out FILE.json]
 
@@ -9,7 +10,8 @@ device events around `--calls` back-to-back calls each, alternating, `--repeats`
     mutual      mp_match_mutual_nn
     guided_r6   mp_match_guided, radius 6   (a row has about 0.4 / 1.5 gated candidates at 1000 / 4096 rows)
     guided_r48  mp_match_guided, radius 48  (about 24 / 97)
-    polish      mp_refine_homography on the radius-6 list and mp_find_homography's estimate (lists of at most 3200 rows)
+    find        mp_find_homography on the radius-6 list, threshold 3 px, the default hypothesis count (lists of at most 3200 rows)
+    polish      mp_refine_homography on the same list and find's estimate
 Prints one JSON line per size: microseconds per call as [min, median, max] over the repeats and the ratio of the guided
 medians to the mutual median of the same run."""
 import argparse
@@ -72,6 +74,7 @@ def main():
             mi, md, mc = guided(6.0)
             res = PairResults(kp, None, cnt, desc, mi, md, mc, *FRAME, 'guided')
             est = find_homography(res, 3.0)[0]
+            cand['find'] = lambda: find_homography(res, 3.0)
             cand['polish'] = lambda: refine_homography(res, est, 3.0)
             counts['polish_inliers'] = int(cand['polish']()[2].sum())
         for f in cand.values():                        # warm-up: code objects, workspace, allocator
