@@ -91,6 +91,15 @@ def test_gaussian_filter():
     for k in (1, 3, 5, 9):
         got = U.gaussian_filter(p.to(DEV), k).cpu()
         assert (got - HA.smooth(p, k)).abs().max().item() <= 1e-6
+        # a non-symmetric table: a filter that reads wgt[dx*k + dy] passes the Gaussian, not this one
+        w = torch.rand(k, k) - 0.3
+        r = (k - 1) // 2
+        want = torch.nn.functional.conv2d(torch.nn.functional.pad(p, (r, r, r, r), mode='reflect'), w[None, None])
+        got = U.gaussian_filter(p.to(DEV), k, w.to(DEV)).cpu()
+        assert (got - want).abs().max().item() <= 1e-6 * max(1.0, w.abs().sum().item())
+        if k > 1:
+            wrong = torch.nn.functional.conv2d(torch.nn.functional.pad(p, (r, r, r, r), mode='reflect'), w.t()[None, None])
+            assert (wrong - want).abs().max().item() > 1e-2
     with pytest.raises(ValueError):
         U.gaussian_filter(p.to(DEV), 4)
 
