@@ -18,7 +18,7 @@ SOURCES = ['conv_mfma.hip', 'conv_wino43.hip', 'conv_wino43b.hip', 'conv_split.h
            'sample_desc.hip', 'match_mfma.hip', 'match_guided.hip', 'match_extra.hip', 'pair_metrics.hip', 'detector_metrics.hip', 'homography.hip', 'homography_pooled.hip', 'homog_adapt.hip', 'losses.hip', 'batchnorm_stats.hip', 'photometric.hip', 'shapes.hip', 'api.hip',
            'model_load.hip', 'forward.hip', 'post_api.hip', 'mutual_info.hip', 'align_api.hip', 'pyramid.hip', 'fft.hip', 'lghd.hip', 'lghd_api.hip', 'frames.hip',
            'frames_api.hip', 'draw.hip']
-HEADERS = [os.path.join(CSRC, h) for h in ('mp_common.h', 'mp_device.h', 'mp_tile.h', 'mp_f16.h', 'mp_match.h', 'mp_fft.h', 'mp_raster.h', 'mp_homography.h', 'mp_f16_store_pooled.inc',
+HEADERS = [os.path.join(CSRC, h) for h in ('mp_common.h', 'mp_device.h', 'mp_tile.h', 'mp_head.h', 'mp_f16.h', 'mp_match.h', 'mp_fft.h', 'mp_raster.h', 'mp_homography.h', 'mp_f16_store_pooled.inc',
                                             'mp_f16_store_lines.inc', 'host.h')] + [
     os.path.join(HERE, '..', 'include', 'multipoint_hip.h')]
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')

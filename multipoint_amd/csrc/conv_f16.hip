@@ -69,67 +69,12 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvParamsH p)
 
     using Where = TileWhere<_Float16>;
     auto decode = [&](int it) __attribute__((always_inline)) -> Where { return tile_decode<_Float16, TAPS, G::TH, G::TW>(p, it); };
-    // per-thread staging offsets in halfs.  Interior items (every halo pixel inside the image; all pixels valid in
-    // flat mode): offsets relative to the item's first halo pixel, IDENTICAL for every such item, so they are
-    // computed once and only the wave-uniform base pointer moves (no VALU per item: a wave that is not streaming
-    // MFMAs issues its vector instructions very slowly next to one that is).  Boundary items: absolute offsets from
-    // in_base with -1 marking padding slots that are zero-filled at the LDS write.
+    // per-thread staging offsets in halfs and the base pointer the staging loads of item w add them to (mp_tile.h)
     int goff[G::NITER];
     bool goff_rel = false;          // goff currently holds the item-invariant relative offsets
     bool cur_pad = false;           // the LDS image being written has padding slots
-    auto is_interior = [&](const Where& w) __attribute__((always_inline)) -> bool {
-        if constexpr (TAPS == 9) return (w.y0 >= 1) && (w.y0 + G::TH < p.H) && (w.x0 >= 1) && (w.x0 + G::TW < p.W);
-        else return w.px0 + 256 <= p.total_px;
-    };
-    // returns the base pointer the staging loads of item w add goff to
     auto offsets = [&](const Where& w) __attribute__((always_inline)) -> const _Float16* {
-        if (is_interior(w)) {
-            if (!goff_rel) {
-#pragma unroll
-                for (int j = 0; j < G::NITER; ++j) {
-                    const int f = tid + j * 256;
-                    const int lp = f >> 3;
-                    int off = 0;
-                    if (f < G::NV) {
-                        if constexpr (TAPS == 9) {
-                            const int ly = lp / G::LW, lx = lp - ly * G::LW;
-                            off = (ly * p.W + lx) * p.in_cstride + (f & 7) * 8;
-                        } else {
-                            off = lp * p.in_cstride + (f & 7) * 8;
-                        }
-                    }
-                    goff[j] = off;
-                }
-                goff_rel = true;
-            }
-            if constexpr (TAPS == 9) return w.in_base + (long long)((w.y0 - 1) * p.W + (w.x0 - 1)) * p.in_cstride;
-            else return w.in_base;
-        }
-        goff_rel = false;
-#pragma unroll
-        for (int j = 0; j < G::NITER; ++j) {
-            const int f = tid + j * 256;
-            const int lp = f >> 3, c8 = f & 7;
-            int off = -1;
-            if (f < G::NV) {
-                if constexpr (TAPS == 9) {
-                    const int ly = lp / G::LW, lx = lp - ly * G::LW;
-                    int gy = w.y0 + ly - 1, gx = w.x0 + lx - 1;
-                    bool zero = false;
-                    if (p.pad_zero) {
-                        zero = (gy < 0) | (gy >= p.H) | (gx < 0) | (gx >= p.W);
-                        gy = min(max(gy, 0), p.H - 1); gx = min(max(gx, 0), p.W - 1);
-                    } else {
-                        gy = reflect_clamp(gy, p.H); gx = reflect_clamp(gx, p.W);
-                    }
-                    if (!zero) off = (gy * p.W + gx) * p.in_cstride + c8 * 8;
-                } else {
-                    if (w.px0 + lp < p.total_px) off = lp * p.in_cstride + c8 * 8;
-                }
-            }
-            goff[j] = off;
-        }
-        return w.in_base;
+        return stage_offsets<TAPS, G::TH, G::TW, 8, 8>(p, w, tid, goff, goff_rel);
     };
 
     const int a_base = (((2 * wave) * G::MBH + li / MBW) * G::LW + (li % MBW)) * PSH + half * 8;
@@ -345,27 +290,9 @@ __global__ __launch_bounds__(256) void conv_first_f16_kernel(const Conv1ParamsH 
 {
     __shared__ float tile[FLH * FLW];
     const int tid = threadIdx.x;
-    const int tiles_x = (p.W + FTW - 1) / FTW, tiles_y = (p.H + FTH - 1) / FTH;
-    int t = blockIdx.x;
-    const int tx = t % tiles_x; t /= tiles_x;
-    const int ty = t % tiles_y;
-    const int bi = t / tiles_y;
-    const int img = p.img_list ? p.img_list[bi] : bi;
-    const int y0 = ty * FTH, x0 = tx * FTW;
-    const float* in = p.in + (long long)img * p.H * p.W;
-    for (int f = tid; f < FLH * FLW; f += 256) {
-        const int ly = f / FLW, lx = f - ly * FLW;
-        int gy = y0 + ly - 1, gx = x0 + lx - 1;
-        float v;
-        if (p.pad_zero) {
-            const bool zero = (gy < 0) | (gy >= p.H) | (gx < 0) | (gx >= p.W);
-            gy = min(max(gy, 0), p.H - 1); gx = min(max(gx, 0), p.W - 1);
-            v = zero ? 0.f : in[gy * p.W + gx];
-        } else {
-            v = in[reflect_clamp(gy, p.H) * p.W + reflect_clamp(gx, p.W)];
-        }
-        tile[f] = round_h(v);
-    }
+    const FirstTile t = first_tile_decode<FTH, FTW>(p, blockIdx.x);
+    const int img = t.img, y0 = t.y0, x0 = t.x0;
+    patch_load<FTH, FTW, 1>(tile, p.in + (long long)img * p.H * p.W, y0, x0, p.H, p.W, p.pad_zero, tid, round_h);
     // channel pairs in f32x2 registers: the 72 multiply-adds and the activation of a pixel's 8 channels are packed
     // instructions (v_pk_fma_f32 with the pixel value broadcast, act_h2) -- the kernel is otherwise VALU-bound
     // (~180 scalar VALU instructions per 16-byte store against ~116 clocks of HBM time per KiB and CU)

@@ -130,50 +130,12 @@ __global__ __launch_bounds__(256 * NG, NG) void conv_f16_res_kernel(const ConvPa
 
     using Where = TileWhere<_Float16>;
     auto decode = [&](int tile) __attribute__((always_inline)) -> Where { return tile_decode<_Float16, 9, G::TH, G::TW, false>(p, tile); };
-    // per-thread staging offsets in halfs (channel granule c8 of patch pixel lp); interior items share one item-invariant set
+    // per-thread staging offsets in halfs (channel granule c8 of patch pixel lp: four lanes per pixel), mp_tile.h
     int goff[G::NITER];
     bool goff_rel = false;
     bool cur_pad = false;
     auto offsets = [&](const Where& w) __attribute__((always_inline)) -> const _Float16* {
-        const bool interior = (w.y0 >= 1) && (w.y0 + G::TH < p.H) && (w.x0 >= 1) && (w.x0 + G::TW < p.W);
-        if (interior) {
-            if (!goff_rel) {
-#pragma unroll
-                for (int j = 0; j < G::NITER; ++j) {
-                    const int f = gt + j * 256;
-                    const int lp = f >> 2;
-                    int off = 0;
-                    if (f < G::NV) {
-                        const int ly = lp / G::LW, lx = lp - ly * G::LW;
-                        off = (ly * p.W + lx) * p.in_cstride + (f & 3) * 8;
-                    }
-                    goff[j] = off;
-                }
-                goff_rel = true;
-            }
-            return w.in_base + (long long)((w.y0 - 1) * p.W + (w.x0 - 1)) * p.in_cstride;
-        }
-        goff_rel = false;
-#pragma unroll
-        for (int j = 0; j < G::NITER; ++j) {
-            const int f = gt + j * 256;
-            const int lp = f >> 2, c8 = f & 3;
-            int off = -1;
-            if (f < G::NV) {
-                const int ly = lp / G::LW, lx = lp - ly * G::LW;
-                int gy = w.y0 + ly - 1, gx = w.x0 + lx - 1;
-                bool zero = false;
-                if (p.pad_zero) {
-                    zero = (gy < 0) | (gy >= p.H) | (gx < 0) | (gx >= p.W);
-                    gy = min(max(gy, 0), p.H - 1); gx = min(max(gx, 0), p.W - 1);
-                } else {
-                    gy = reflect_clamp(gy, p.H); gx = reflect_clamp(gx, p.W);
-                }
-                if (!zero) off = (gy * p.W + gx) * p.in_cstride + c8 * 8;
-            }
-            goff[j] = off;
-        }
-        return w.in_base;
+        return stage_offsets<9, G::TH, G::TW, 8, 4>(p, w, gt, goff, goff_rel);
     };
 
 

@@ -17,6 +17,9 @@
 // (64 accumulator VGPRs).  K is walked in chunks of 32 input channels: per chunk the LDS tile is
 // (tile+halo) x 32 ch = ~48 KiB, so three workgroups share a CU and their load/compute phases
 // overlap (the fp32 MFMA takes 64 cycles per issue, everything else hides behind it).
+// Shared with the fp16 kernels (mp_tile.h): the item decode, the staging offsets of an item (stage_offsets) and the first block's
+// patch load; the padding rule is pad_source (mp_device.h).  Here once for both kernels: the activation order (conv_act) and the
+// guarded 16-byte store (store4).  The per-tile kernel keeps its own store addresses: see DESIGN.md section 9.
 #include "mp_common.h"
 #include "mp_device.h"
 #include "mp_tile.h"
@@ -68,6 +71,126 @@ __device__ __forceinline__ float max4_f(float a, float b, float c, float d)
     return r;
 }
 
+// bias -> (ReLU, BatchNorm) | BNF: (BatchNorm, ReLU): the activation order of every epilogue here and of the fused first block
+template <bool BNF, bool RELU>
+__device__ __forceinline__ float conv_act(float v, float bias, float scale, float shift)
+{
+    v += bias;
+    if (BNF) {
+        v = v * scale + shift;
+        if (RELU) v = relu_bits(v);
+    } else {
+        if (RELU) v = relu_bits(v);
+        v = v * scale + shift;
+    }
+    return v;
+}
+template <bool BNF, bool RELU>
+__device__ __forceinline__ f32x4 conv_act4(const f32x4& a, const f32x4& b4, const f32x4& s4, const f32x4& t4)
+{
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = conv_act<BNF, RELU>(a[e], b4[e], s4[e], t4[e]);
+    return v;
+}
+
+// 4 consecutive channels ch0 .. ch0 + 3 of one pixel to dst: one 16-byte store, or the channels below cout one by one
+__device__ __forceinline__ void store4(float* dst, int ch0, int cout, const f32x4& v)
+{
+    if (ch0 + 3 < cout) {
+        *reinterpret_cast<f32x4*>(dst) = v;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (ch0 + e < cout) dst[e] = v[e];
+    }
+}
+
+// Epilogue of one item of the persistent kernel: bias -> activation -> [2x2 max] -> store, addressed by a wave-uniform 64-bit base
+// plus ONE per-lane offset; an item whose tile and slice lie wholly inside the output stores unguarded (FULL).  prm: bias | scale |
+// shift of the item's slice, 64 each, in LDS.
+//   POOL:  lane = channel (li), register r = pixel (r&3) + 8*(r>>2) + 4*half of the M-block: the 2x2 window is in-lane
+//   else:  lane = pixel (li) of the M-block, register r = channel (r&3) + 8*(r>>2) + 4*half of the N-block: every register
+//          quad is 4 consecutive channels of one pixel -> one 16-byte store
+template <int MBW, bool POOL, bool BNF, bool RELU>
+__device__ __forceinline__ void persist_epilogue(const ConvParams& p, const TileWhere<float>& w, const f32x16 (&acc)[2][2], const float* prm,
+                                                 const int wave, const int half, const int li)
+{
+    using G = Geo<9, MBW>;
+    const int slice = w.slice;
+    const float *const bia = prm, *const scl = prm + 64, *const sft = prm + 128;
+    const int y0 = w.y0, x0 = w.x0;
+    const int cs = p.out_cstride;
+    if constexpr (POOL) {
+        float b[2], s[2], t[2];
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) { b[nb] = bia[nb * 32 + li]; s[nb] = scl[nb * 32 + li]; t[nb] = sft[nb * 32 + li]; }
+        auto act = [&](float v, int nb) __attribute__((always_inline)) -> float { return conv_act<BNF, RELU>(v, b[nb], s[nb], t[nb]); };
+        const int Ho = p.H >> 1, Wo = p.W >> 1;
+        const bool full = (y0 + G::TH <= p.H) && (x0 + G::TW <= p.W) && (slice * 64 + 64 <= p.cout);
+        const int lane_off = 2 * half * cs + li;
+        float* const obase = p.out + ((long long)w.img * Ho * Wo) * cs + p.out_coff + slice * 64;
+        // partner registers of the 2x2 window: +1 column = r+1; +1 row depends on the M-block shape
+        constexpr int RDOWN = (MBW == 32) ? 0 : (MBW == 16) ? 8 : 4;
+        constexpr int NMB = (MBW == 32) ? 1 : 2;
+        auto store_all = [&](auto full_tag) __attribute__((always_inline)) {
+            constexpr bool FULL = decltype(full_tag)::value;
+#pragma unroll
+            for (int mb = 0; mb < NMB; ++mb)
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    if (RDOWN != 0 && (r & RDOWN) != 0) continue;      // only top rows of each 2-row pair
+                    const int iu = (r & 3) + 8 * (r >> 2);
+                    const int oy = (MBW == 32) ? (y0 + 2 * wave) >> 1 : (y0 + (2 * wave + mb) * G::MBH + iu / MBW) >> 1;
+                    const int oxu = (x0 + iu % MBW) >> 1;
+                    float* const rowp = obase + ((long long)oy * Wo + oxu) * cs;
+#pragma unroll
+                    for (int nb = 0; nb < 2; ++nb) {
+                        const float v = (MBW == 32)
+                            ? max4_f(act(acc[0][nb][r], nb), act(acc[0][nb][r + 1], nb), act(acc[1][nb][r], nb), act(acc[1][nb][r + 1], nb))
+                            : max4_f(act(acc[mb][nb][r], nb), act(acc[mb][nb][r + 1], nb), act(acc[mb][nb][r + RDOWN], nb),
+                                     act(acc[mb][nb][r + RDOWN + 1], nb));
+                        if constexpr (FULL) {
+                            rowp[nb * 32 + lane_off] = v;
+                        } else {
+                            if ((oy < Ho) & (oxu + 2 * half < Wo) & (slice * 64 + nb * 32 + li < p.cout)) rowp[nb * 32 + lane_off] = v;
+                        }
+                    }
+                }
+        };
+        if (full) store_all(std::true_type{}); else store_all(std::false_type{});
+    } else {
+        const int lane_off = ((li / MBW) * p.W + li % MBW) * cs + half * 4;
+        float* const obase = p.out + (((long long)w.img * p.H + y0) * p.W + x0) * cs + p.out_coff + slice * 64;
+        const bool full = (y0 + G::TH <= p.H) && (x0 + G::TW <= p.W) && (slice * 64 + 64 <= p.cout);
+        auto store_all = [&](auto full_tag) __attribute__((always_inline)) {
+            constexpr bool FULL = decltype(full_tag)::value;
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+                for (int rg = 0; rg < 4; ++rg) {
+                    const int cl = nb * 32 + rg * 8 + half * 4;
+                    const f32x4 b4 = *reinterpret_cast<const f32x4*>(&bia[cl]);
+                    const f32x4 s4 = *reinterpret_cast<const f32x4*>(&scl[cl]);
+                    const f32x4 t4 = *reinterpret_cast<const f32x4*>(&sft[cl]);
+#pragma unroll
+                    for (int mb = 0; mb < 2; ++mb) {
+                        const f32x16& a = acc[mb][nb];
+                        const f32x4 v = conv_act4<BNF, RELU>(f32x4{a[rg * 4], a[rg * 4 + 1], a[rg * 4 + 2], a[rg * 4 + 3]}, b4, s4, t4);
+                        float* const dst = obase + (long long)((2 * wave + mb) * G::MBH) * p.W * cs + nb * 32 + rg * 8 + lane_off;
+                        if constexpr (FULL) {
+                            *reinterpret_cast<f32x4*>(dst) = v;
+                        } else {
+                            if ((y0 + (2 * wave + mb) * G::MBH + li / MBW < p.H) & (x0 + li % MBW < p.W))
+                                store4(dst, slice * 64 + cl, p.cout, v);
+                        }
+                    }
+                }
+        };
+        if (full) store_all(std::true_type{}); else store_all(std::false_type{});
+    }
+}
+
 // LINEAR: no activation at all (conv + bias only): the batch-statistics forward of bn_first models, whose BatchNorm needs the
 // pre-ReLU output (forward.hip: run_forward_batch_stats); launched with the identity scale / shift
 template <int TAPS, int MBW, bool POOL, bool FUSE1, bool BNF, bool LINEAR = false>
@@ -114,55 +237,36 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
     const TileWhere<float> w0 = tile_decode<float, TAPS, G::TH, G::TW, false>(p, tile);
     const int img = w0.img, y0 = w0.y0, x0 = w0.x0;
     const long long px0 = w0.px0;
-    const float* const in_base = w0.in_base;      // wave-uniform base: image (3x3) or first pixel of the tile (1x1)
 
     // ---- per-thread staging offsets (element offsets from in_base, -1 = store zeros) ----
     // interior tiles (every halo pixel inside the image: ~87 % of the tiles at 480x640) take a lean path:
     // no reflect / clamp / zero logic here and no zero-select at the LDS writes.
-    bool interior = false;
-    if constexpr (TAPS == 9)
-        interior = (y0 >= 1) && (y0 + G::TH < p.H) && (x0 >= 1) && (x0 + G::TW < p.W);
     int goff[G::NITER];
-    if (interior) {
-        const int base = ((y0 - 1) * p.W + (x0 - 1)) * p.in_cstride + (tid & 7) * 4;
+    bool interior = false;
+    const float* in_base = w0.in_base;            // wave-uniform base the staging loads add goff to (stage_offsets, mp_tile.h)
+    if constexpr (!FUSE1) {
+        in_base = stage_offsets<TAPS, G::TH, G::TW, 4, 8>(p, w0, tid, goff, interior);
+    } else {
+        // the fused first layer stages no tensor: goff is the centre of the first-layer window inside the image patch
+        // (patch origin = tile - 2)
+        interior = is_interior<TAPS, G::TH, G::TW>(p, w0);
 #pragma unroll
         for (int j = 0; j < G::NITER; ++j) {
-            const int lp = (tid + j * 256) >> 3;
+            const int f = tid + j * 256;
+            const int lp = f >> 3;
             const int ly = lp / G::LW, lx = lp - ly * G::LW;
-            goff[j] = (tid + j * 256 < G::NF4) ? base + (ly * p.W + lx) * (FUSE1 ? 0 : p.in_cstride) : 0;
-            if constexpr (FUSE1) goff[j] = (ly + 1) * (G::TW + 4) + (lx + 1);       // window centre in the image patch
-        }
-    } else {
-#pragma unroll
-    for (int j = 0; j < G::NITER; ++j) {
-        const int f = tid + j * 256;
-        const int lp = f >> 3, c4 = f & 7;
-        int off = -1;
-        if (f < G::NF4) {
-            if constexpr (TAPS == 9) {
-                const int ly = lp / G::LW, lx = lp - ly * G::LW;
-                int gy = y0 + ly - 1, gx = x0 + lx - 1;
-                bool zero = false;
-                if (p.pad_zero) {
-                    zero = (gy < 0) | (gy >= p.H) | (gx < 0) | (gx >= p.W);
-                    gy = min(max(gy, 0), p.H - 1); gx = min(max(gx, 0), p.W - 1);
-                } else {
-                    gy = reflect_clamp(gy, p.H); gx = reflect_clamp(gx, p.W);
-                }
-                if constexpr (FUSE1) {
-                    // centre of the first-layer window inside the image patch (patch origin = tile - 2);
+            int off = (ly + 1) * ITW + (lx + 1);
+            if (!interior) {
+                off = -1;
+                if (f < G::NF4) {
+                    const PadSource s = pad_source(y0 + ly - 1, x0 + lx - 1, p.H, p.W, p.pad_zero);
                     // pixels of partial tiles far outside the image are clamped (their outputs are not stored)
-                    const int qy = min(max(gy, y0 - 1), y0 + G::TH), qx = min(max(gx, x0 - 1), x0 + G::TW);
-                    if (!zero) off = (qy - y0 + 2) * ITW + (qx - x0 + 2);
-                } else {
-                    if (!zero) off = (gy * p.W + gx) * p.in_cstride + c4 * 4;
+                    const int qy = min(max(s.y, y0 - 1), y0 + G::TH), qx = min(max(s.x, x0 - 1), x0 + G::TW);
+                    if (!s.zero) off = (qy - y0 + 2) * ITW + (qx - x0 + 2);
                 }
-            } else {
-                if (px0 + lp < p.total_px) off = lp * p.in_cstride + c4 * 4;
             }
+            goff[j] = off;
         }
-        goff[j] = off;
-    }
     }
 
     // ---- A-fragment LDS base of this lane (M-block 2*wave, tap (0,0), k-group 0) ----
@@ -206,31 +310,12 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
         const f32x4 b4 = *reinterpret_cast<const f32x4*>(&p1s[ch]);
         const f32x4 s4 = *reinterpret_cast<const f32x4*>(&p1s[64 + ch]);
         const f32x4 t4 = *reinterpret_cast<const f32x4*>(&p1s[128 + ch]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float v = a[e] + b4[e];
-            if (BNF) v = relu_bits(v * s4[e] + t4[e]);
-            else v = relu_bits(v) * s4[e] + t4[e];
-            a[e] = v;
-        }
-        return a;
+        return conv_act4<BNF, true>(a, b4, s4, t4);
     };
 
     if constexpr (FUSE1) {
-        const float* image = p.img + (long long)img * p.H * p.W;
-        for (int f = tid; f < ITH * ITW; f += 256) {
-            const int r = f / ITW, c = f - r * ITW;
-            int gy = y0 - 2 + r, gx = x0 - 2 + c;
-            float v;
-            if (p.pad_zero) {
-                const bool zero = (gy < 0) | (gy >= p.H) | (gx < 0) | (gx >= p.W);
-                gy = min(max(gy, 0), p.H - 1); gx = min(max(gx, 0), p.W - 1);
-                v = zero ? 0.f : image[gy * p.W + gx];
-            } else {
-                v = image[reflect_clamp(gy, p.H) * p.W + reflect_clamp(gx, p.W)];
-            }
-            its[f] = v;
-        }
+        patch_load<G::TH, G::TW, 2>(its, p.img + (long long)img * p.H * p.W, y0, x0, p.H, p.W, p.pad_zero, tid,
+                                    [](float v) { return v; });
         for (int f = tid; f < 9 * 64; f += 256) w1s[f] = p.w1[f];
         if (tid < 64) { p1s[tid] = p.b1[tid]; p1s[64 + tid] = p.s1[tid]; p1s[128 + tid] = p.t1[tid]; }
         __syncthreads();
@@ -329,17 +414,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
             ch[nb] = slice * 64 + nb * 32 + li;
             bia[nb] = p.bias[ch[nb]]; scl[nb] = p.scale[ch[nb]]; sft[nb] = p.shift[ch[nb]];
         }
-        auto act = [&](float v, int nb) -> float {
-            v += bia[nb];
-            if (BNF) {
-                v = v * scl[nb] + sft[nb];
-                if (RELU) v = relu_bits(v);
-            } else {
-                if (RELU) v = relu_bits(v);
-                v = v * scl[nb] + sft[nb];
-            }
-            return v;
-        };
+        auto act = [&](float v, int nb) -> float { return conv_act<BNF, RELU>(v, bia[nb], scl[nb], sft[nb]); };
 
         {
             const int Ho = p.H >> 1, Wo = p.W >> 1;
@@ -389,29 +464,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
     // channel (r&3) + 8*(r>>2) + 4*half of the N-block: every register quad is 4 consecutive channels
     // of one pixel -> one 16-byte store.
     auto act4 = [&](const f32x16& a, int rg, const f32x4& b4, const f32x4& s4, const f32x4& t4) -> f32x4 {
-        f32x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float x = a[rg * 4 + e] + b4[e];
-            if (BNF) {
-                x = x * s4[e] + t4[e];
-                if (RELU) x = relu_bits(x);
-            } else {
-                if (RELU) x = relu_bits(x);
-                x = x * s4[e] + t4[e];
-            }
-            v[e] = x;
-        }
-        return v;
-    };
-    auto store4 = [&](float* dst, int ch0, const f32x4& v) {
-        if (ch0 + 3 < p.cout) {
-            *reinterpret_cast<f32x4*>(dst + ch0) = v;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (ch0 + e < p.cout) dst[ch0 + e] = v[e];
-        }
+        return conv_act4<BNF, RELU>(f32x4{a[rg * 4], a[rg * 4 + 1], a[rg * 4 + 2], a[rg * 4 + 3]}, b4, s4, t4);
     };
 
 #pragma unroll
@@ -427,7 +480,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
                 for (int mb = 0; mb < 2; ++mb) {
                     const long long gp = px0 + (2 * wave + mb) * 32 + li;
                     if (gp < p.total_px)
-                        store4(p.out + gp * p.out_cstride + p.out_coff, ch0, act4(acc[mb][nb], rg, b4, s4, t4));
+                        store4(p.out + gp * p.out_cstride + p.out_coff + ch0, ch0, p.cout, act4(acc[mb][nb], rg, b4, s4, t4));
                 }
             } else if constexpr (!POOL) {
 #pragma unroll
@@ -435,7 +488,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
                     const int oy = y0 + (2 * wave + mb) * G::MBH + li / MBW;
                     const int ox = x0 + li % MBW;
                     if (oy < p.H && ox < p.W)
-                        store4(p.out + (((long long)img * p.H + oy) * p.W + ox) * p.out_cstride + p.out_coff, ch0,
+                        store4(p.out + (((long long)img * p.H + oy) * p.W + ox) * p.out_cstride + p.out_coff + ch0, ch0, p.cout,
                                act4(acc[mb][nb], rg, b4, s4, t4));
                 }
             }
@@ -482,58 +535,8 @@ __global__ __launch_bounds__(256, 1) void conv_mfma_persist_kernel(const ConvPar
     int goff[G::NITER];
     bool goff_rel = false;          // goff holds the item-invariant relative offsets of interior items
     bool cur_pad = false;           // the LDS image being written has padding slots
-    auto is_interior = [&](const Where& w) __attribute__((always_inline)) -> bool {
-        if constexpr (TAPS == 9) return (w.y0 >= 1) && (w.y0 + G::TH < p.H) && (w.x0 >= 1) && (w.x0 + G::TW < p.W);
-        else return w.px0 + 256 <= p.total_px;
-    };
     auto offsets = [&](const Where& w) __attribute__((always_inline)) -> const float* {
-        if (is_interior(w)) {
-            if (!goff_rel) {
-#pragma unroll
-                for (int j = 0; j < G::NITER; ++j) {
-                    const int f = tid + j * 256;
-                    const int lp = f >> 3;
-                    int off = 0;
-                    if (f < G::NF4) {
-                        if constexpr (TAPS == 9) {
-                            const int ly = lp / G::LW, lx = lp - ly * G::LW;
-                            off = (ly * p.W + lx) * p.in_cstride + (f & 7) * 4;
-                        } else {
-                            off = lp * p.in_cstride + (f & 7) * 4;
-                        }
-                    }
-                    goff[j] = off;
-                }
-                goff_rel = true;
-            }
-            if constexpr (TAPS == 9) return w.in_base + (long long)((w.y0 - 1) * p.W + (w.x0 - 1)) * p.in_cstride;
-            else return w.in_base;
-        }
-        goff_rel = false;
-#pragma unroll
-        for (int j = 0; j < G::NITER; ++j) {
-            const int f = tid + j * 256;
-            const int lp = f >> 3, c4 = f & 7;
-            int off = -1;
-            if (f < G::NF4) {
-                if constexpr (TAPS == 9) {
-                    const int ly = lp / G::LW, lx = lp - ly * G::LW;
-                    int gy = w.y0 + ly - 1, gx = w.x0 + lx - 1;
-                    bool zero = false;
-                    if (p.pad_zero) {
-                        zero = (gy < 0) | (gy >= p.H) | (gx < 0) | (gx >= p.W);
-                        gy = min(max(gy, 0), p.H - 1); gx = min(max(gx, 0), p.W - 1);
-                    } else {
-                        gy = reflect_clamp(gy, p.H); gx = reflect_clamp(gx, p.W);
-                    }
-                    if (!zero) off = (gy * p.W + gx) * p.in_cstride + c4 * 4;
-                } else {
-                    if (w.px0 + lp < p.total_px) off = lp * p.in_cstride + c4 * 4;
-                }
-            }
-            goff[j] = off;
-        }
-        return w.in_base;
+        return stage_offsets<TAPS, G::TH, G::TW, 4, 8>(p, w, tid, goff, goff_rel);
     };
 
     const int a_base = (((2 * wave) * G::MBH + li / MBW) * G::LW + (li % MBW)) * PS + half * 4;
@@ -675,121 +678,8 @@ __global__ __launch_bounds__(256, 1) void conv_mfma_persist_kernel(const ConvPar
         for (int c = 1; c < nchunks; ++c) chunk_body(c, std::false_type{});
 
         MP_CLOCK(t_e0);
-        // ---------------- epilogue of item `cur`: wave-uniform 64-bit base + one per-lane offset ----------------
-        const int slice = cur.slice, img = cur.img, y0 = cur.y0, x0 = cur.x0;
-        const long long px0 = cur.px0;
-        const int cs = p.out_cstride;
-        if constexpr (POOL) {
-            // lane = channel (li), register r = pixel (r&3) + 8*(r>>2) + 4*half of the M-block
-            float bia[2], scl[2], sft[2];
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb) { bia[nb] = prm[nb * 32 + li]; scl[nb] = prm[64 + nb * 32 + li]; sft[nb] = prm[128 + nb * 32 + li]; }
-            auto act = [&](float v, int nb) __attribute__((always_inline)) -> float {
-                v += bia[nb];
-                if (BNF) {
-                    v = v * scl[nb] + sft[nb];
-                    if (RELU) v = relu_bits(v);
-                } else {
-                    if (RELU) v = relu_bits(v);
-                    v = v * scl[nb] + sft[nb];
-                }
-                return v;
-            };
-            const int Ho = p.H >> 1, Wo = p.W >> 1;
-            const bool full = (y0 + G::TH <= p.H) && (x0 + G::TW <= p.W) && (slice * 64 + 64 <= p.cout);
-            const int lane_off = 2 * half * cs + li;
-            float* const obase = p.out + ((long long)img * Ho * Wo) * cs + p.out_coff + slice * 64;
-            constexpr int RDOWN = (MBW == 32) ? 0 : (MBW == 16) ? 8 : 4;
-            constexpr int NMB = (MBW == 32) ? 1 : 2;
-            auto store_all = [&](auto full_tag) __attribute__((always_inline)) {
-                constexpr bool FULL = decltype(full_tag)::value;
-#pragma unroll
-                for (int mb = 0; mb < NMB; ++mb)
-#pragma unroll
-                    for (int r = 0; r < 16; r += 2) {
-                        if (RDOWN != 0 && (r & RDOWN) != 0) continue;
-                        const int iu = (r & 3) + 8 * (r >> 2);
-                        const int oy = (MBW == 32) ? (y0 + 2 * wave) >> 1 : (y0 + (2 * wave + mb) * G::MBH + iu / MBW) >> 1;
-                        const int oxu = (x0 + iu % MBW) >> 1;
-                        float* const rowp = obase + ((long long)oy * Wo + oxu) * cs;
-#pragma unroll
-                        for (int nb = 0; nb < 2; ++nb) {
-                            const float v = (MBW == 32)
-                                ? max4_f(act(acc[0][nb][r], nb), act(acc[0][nb][r + 1], nb), act(acc[1][nb][r], nb), act(acc[1][nb][r + 1], nb))
-                                : max4_f(act(acc[mb][nb][r], nb), act(acc[mb][nb][r + 1], nb), act(acc[mb][nb][r + RDOWN], nb),
-                                         act(acc[mb][nb][r + RDOWN + 1], nb));
-                            if constexpr (FULL) {
-                                rowp[nb * 32 + lane_off] = v;
-                            } else {
-                                if ((oy < Ho) & (oxu + 2 * half < Wo) & (slice * 64 + nb * 32 + li < p.cout)) rowp[nb * 32 + lane_off] = v;
-                            }
-                        }
-                    }
-            };
-            if (full) store_all(std::true_type{}); else store_all(std::false_type{});
-        } else {
-            int lane_off;
-            float* obase;
-            bool full;
-            if constexpr (TAPS == 1) {
-                lane_off = li * cs + half * 4;
-                obase = p.out + px0 * cs + p.out_coff + slice * 64;
-                full = (px0 + 256 <= p.total_px) && (slice * 64 + 64 <= p.cout);
-            } else {
-                lane_off = ((li / MBW) * p.W + li % MBW) * cs + half * 4;
-                obase = p.out + (((long long)img * p.H + y0) * p.W + x0) * cs + p.out_coff + slice * 64;
-                full = (y0 + G::TH <= p.H) && (x0 + G::TW <= p.W) && (slice * 64 + 64 <= p.cout);
-            }
-            auto store_all = [&](auto full_tag) __attribute__((always_inline)) {
-                constexpr bool FULL = decltype(full_tag)::value;
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                    for (int rg = 0; rg < 4; ++rg) {
-                        const int cl = nb * 32 + rg * 8 + half * 4;
-                        const f32x4 b4 = *reinterpret_cast<const f32x4*>(&prm[cl]);
-                        const f32x4 s4 = *reinterpret_cast<const f32x4*>(&prm[64 + cl]);
-                        const f32x4 t4 = *reinterpret_cast<const f32x4*>(&prm[128 + cl]);
-#pragma unroll
-                        for (int mb = 0; mb < 2; ++mb) {
-                            f32x4 v;
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                float x = acc[mb][nb][rg * 4 + e] + b4[e];
-                                if (BNF) {
-                                    x = x * s4[e] + t4[e];
-                                    if (RELU) x = relu_bits(x);
-                                } else {
-                                    if (RELU) x = relu_bits(x);
-                                    x = x * s4[e] + t4[e];
-                                }
-                                v[e] = x;
-                            }
-                            float* const mp = (TAPS == 1) ? obase + (long long)((2 * wave + mb) * 32) * cs
-                                                          : obase + (long long)((2 * wave + mb) * G::MBH) * p.W * cs;
-                            float* const dst = mp + nb * 32 + rg * 8 + lane_off;
-                            if constexpr (FULL) {
-                                *reinterpret_cast<f32x4*>(dst) = v;
-                            } else {
-                                bool okp;
-                                if constexpr (TAPS == 1) okp = px0 + (2 * wave + mb) * 32 + li < p.total_px;
-                                else okp = (y0 + (2 * wave + mb) * G::MBH + li / MBW < p.H) & (x0 + li % MBW < p.W);
-                                const int ch0 = slice * 64 + cl;
-                                if (okp) {
-                                    if (ch0 + 3 < p.cout) {
-                                        *reinterpret_cast<f32x4*>(dst) = v;
-                                    } else {
-#pragma unroll
-                                        for (int e = 0; e < 4; ++e)
-                                            if (ch0 + e < p.cout) dst[e] = v[e];
-                                    }
-                                }
-                            }
-                        }
-                    }
-            };
-            if (full) store_all(std::true_type{}); else store_all(std::false_type{});
-        }
+        // ---------------- epilogue of item `cur` ----------------
+        persist_epilogue<MBW, POOL, BNF, RELU>(p, cur, acc, prm, wave, half, li);
         MP_CLOCK(t_e1);
         MP_CLOCK_ADD(4, t_e0, t_e1);
 #ifdef MP_TIMING

@@ -15,8 +15,11 @@
 // the workgroup's four waves share ONE copy of the weight fragments (4 x (3 + D/32) KiB, packed by pack_conv_weights with
 // taps = 1) and each wave DMAs the 8 KiB of its own 32 pixels (a lane fetches 16 bytes of its own pixel's row, so the LDS
 // image is already in fragment order); one s_waitcnt vmcnt(0) + barrier per chunk.
+// Parameter staging, tile placement, both tails behind the BatchNorm and the launcher are mp_head.h's, shared with
+// head_tail_f16.hip; this file keeps the main loop and the step from an accumulator to a value (acc_rd + affine).
 #include "mp_common.h"
 #include "mp_device.h"
+#include "mp_head.h"
 
 #include <type_traits>
 
@@ -42,13 +45,7 @@ __global__ __launch_bounds__(256) void head_tail_kernel(const HeadTailParams p)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pl = lane & 31, hf = lane >> 5;
-    for (int i = tid; i < NP; i += 256) {
-        const bool det = i < 96;
-        const int c = det ? i : i - 96;
-        prm[i] = det ? p.bdet[c] : p.bdesc[c];
-        prm[NP + i] = det ? p.sdet[c] : p.sdesc[c];
-        prm[2 * NP + i] = det ? p.tdet[c] : p.tdesc[c];
-    }
+    head_stage_params<NP>(p, prm, tid);
 
     // Persistent workgroups: a workgroup walks tiles of 128 consecutive pixels, gridDim.x apart; the first chunk of the next
     // tile is DMA'd during the last chunk of the current one, so no tile pays its HBM latency in the open.  Waves (and
@@ -59,12 +56,7 @@ __global__ __launch_bounds__(256) void head_tail_kernel(const HeadTailParams p)
     bool valid = false;
     unsigned xoff = 0, xoff_next = 0;
     const float *xbase = p.x, *xbase_next = p.x;
-    auto place = [&](long long t, unsigned& off, const float*& base) __attribute__((always_inline)) {
-        const long long q = (t * 4 + wave) * 32 + pl;
-        off = (unsigned)(((q < p.npx ? q : p.npx - 1) - t * 128) * p.xstride + hf * 4) * 4u;      // bytes from the tile's first pixel
-        base = p.x + t * 128 * p.xstride;
-    };
-    place(tile, xoff, xbase);
+    head_place(p, tile, wave, pl, hf, xoff, xbase);
     const int nchunks = p.K >> 5;
     const unsigned wl_lds = (unsigned)(size_t)wl, xl_lds = (unsigned)(size_t)xl + (unsigned)wave * (XCH * 4u);
 
@@ -92,7 +84,7 @@ __global__ __launch_bounds__(256) void head_tail_kernel(const HeadTailParams p)
 
     for (;;) {
     const bool has_next = tile + gridDim.x < ntiles;
-    if (has_next) place(tile + gridDim.x, xoff_next, xbase_next);
+    if (has_next) head_place(p, tile + gridDim.x, wave, pl, hf, xoff_next, xbase_next);
     px = (tile * 4 + wave) * 32 + pl;
     valid = px < p.npx;
     f32x16 acc[NT];
@@ -143,10 +135,8 @@ __global__ __launch_bounds__(256) void head_tail_kernel(const HeadTailParams p)
     }
 
     // ---- detector: bias -> BN -> softmax over 65 channels -> shuffle ----
-    const int cell = (int)(px % ((long long)p.Hc * p.Wc));
-    const int b = (int)(px / ((long long)p.Hc * p.Wc));
-    const int hc = cell / p.Wc, wc = cell - hc * p.Wc;
     {
+        const HeadCell at = head_cell(p, px);
         float v[32];
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -157,50 +147,7 @@ __global__ __launch_bounds__(256) void head_tail_kernel(const HeadTailParams p)
             }
         // the dustbin (channel 64) is row 0 of block 2: register 0 of the lower half-wave; both halves need it
         float d = (acc_rd(acc[2][0]) + prm[64]) * prm[NP + 64] + prm[2 * NP + 64];
-        d = __shfl(d, pl);                                            // from lane pl (hf = 0)
-        if (p.logits_nchw && valid) {
-            const long long plane = (long long)p.Hc * p.Wc;
-            float* o = p.logits_nchw + (long long)b * 65 * plane + cell;
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[(long long)(32 * t + (r & 3) + 8 * (r >> 2) + 4 * hf) * plane] = v[16 * t + r];
-            if (hf == 0) o[64 * plane] = d;
-        }
-        if (p.prob) {
-            // mode 0: nn.Softmax2d (max-subtracted); mode 1: SuperPointMagicLeap.generate_heatmap: exp(x) / (sum + 1e-5)
-            float m = 0.f;
-            if (p.softmax_mode == 0) {
-                m = d;
-#pragma unroll
-                for (int i = 0; i < 32; ++i) m = fmaxf(m, v[i]);
-                m = fmaxf(m, __shfl_xor(m, 32));
-            }
-            float s = 0.f;
-#pragma unroll
-            // __expf(x) = v_exp_f32(x * log2(e)): the rounded product costs a relative ln(2) * ulp(|x| * log2(e)) / 2, about 6.6e-7
-            // (~6 ulp) at x = ln(1e-6); prob is measured within 1.3e-6 relative of float64 where it is >= 1e-6 (tests/test_gpu_exact.py)
-            for (int i = 0; i < 32; ++i) { v[i] = __expf(v[i] - m); s += v[i]; }
-            s += __shfl_xor(s, 32);
-            s += __expf(d - m);
-            if (p.softmax_mode == 1) s += 0.00001f;
-            // one IEEE division per pixel instead of 32 (a division is a ten-instruction sequence): v * (1/s) is within
-            // one ulp of v / s
-            const float rs = 1.0f / s;
-            if (valid) {
-                const int H = p.Hc * 8, W = p.Wc * 8;
-                float* o = p.prob + ((long long)b * H + hc * 8) * W + wc * 8 + 4 * hf;
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        // channels 32t + 8q + 4hf + (0..3) = row dy = 4t + q of the 8x8 block, columns 4hf .. 4hf+3
-                        const f32x4 o4 = {v[16 * t + 4 * q] * rs, v[16 * t + 4 * q + 1] * rs, v[16 * t + 4 * q + 2] * rs,
-                                          v[16 * t + 4 * q + 3] * rs};
-                        *reinterpret_cast<f32x4*>(o + (long long)(4 * t + q) * W) = o4;
-                    }
-            }
-        }
+        head_detector_tail(p, at, v, d, valid, pl, hf);
     }
     // ---- descriptor: bias -> BN -> L2 normalisation ----
     if constexpr (ND > 0) {
@@ -218,19 +165,7 @@ __global__ __launch_bounds__(256) void head_tail_kernel(const HeadTailParams p)
                         dv[4 * t + q][e] = x;
                         ss += x * x;
                     }
-            if (p.normalize) {
-                ss += __shfl_xor(ss, 32);
-                const float rd = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
-#pragma unroll
-                for (int i = 0; i < ND * 4; ++i) dv[i] = dv[i] * rd;
-            }
-            if (valid) {
-                float* o = p.desc + px * (32 * ND) + 4 * hf;
-#pragma unroll
-                for (int t = 0; t < ND; ++t)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) *reinterpret_cast<f32x4*>(o + 32 * t + 8 * q) = dv[4 * t + q];
-            }
+            head_descriptor_tail<ND>(p, dv, ss, px, valid, hf);
         }
     }
     if (!has_next) return;
@@ -246,14 +181,5 @@ __global__ __launch_bounds__(256) void head_tail_kernel(const HeadTailParams p)
 int launch_head_tail(const HeadTailParams& p, hipStream_t s)
 {
     if (p.K % 64 != 0 || p.npx <= 0) return 1;
-    const int D = p.desc ? p.D : 0;
-    const long long tiles = (p.npx + 127) / 128;                  // one workgroup per CU walks them
-    const dim3 grid((unsigned)(tiles < p.ncu ? tiles : p.ncu)), block(256);
-    switch (D) {
-    case 0: hipLaunchKernelGGL(head_tail_kernel<0>, grid, block, 0, s, p); return 0;
-    case 64: hipLaunchKernelGGL(head_tail_kernel<2>, grid, block, 0, s, p); return 0;
-    case 128: hipLaunchKernelGGL(head_tail_kernel<4>, grid, block, 0, s, p); return 0;
-    case 256: hipLaunchKernelGGL(head_tail_kernel<8>, grid, block, 0, s, p); return 0;
-    default: return 1;
-    }
+    return head_tail_launch(p, s, head_tail_kernel<0>, head_tail_kernel<2>, head_tail_kernel<4>, head_tail_kernel<8>);
 }

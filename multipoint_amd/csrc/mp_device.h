@@ -11,6 +11,26 @@ __device__ __forceinline__ int reflect_clamp(int v, int n)
     return v >= n ? n - 1 : v;              // (only reachable for pixels outside the image tile)
 }
 
+// The padding rule of the 3x3 convolutions: the frame pixel that feeds position (gy, gx) of a halo, and whether that
+// position is a zero instead (ZeroPad2d(1); the coordinates are then clamped into the frame, so a dummy load stays legal).
+struct PadSource { int y, x; bool zero; };
+__device__ __forceinline__ PadSource pad_source(int gy, int gx, int H, int W, int pad_zero)
+{
+    if (pad_zero) return {min(max(gy, 0), H - 1), min(max(gx, 0), W - 1), (bool)((gy < 0) | (gy >= H) | (gx < 0) | (gx >= W))};
+    return {reflect_clamp(gy, H), reflect_clamp(gx, W), false};
+}
+
+// borderInterpolate(p, n, BORDER_REFLECT_101) with the reflection repeated while p stays outside (period 2n - 2): the modulo
+// also keeps the rows and columns that a partial tile loads but never uses inside the frame
+__device__ __forceinline__ int reflect101(int p, int n)
+{
+    if (n == 1) return 0;
+    const int period = 2 * n - 2;
+    int q = p % period;
+    if (q < 0) q += period;
+    return q < n ? q : period - q;
+}
+
 // ReLU as an integer max (finite inputs): one v_max_i32, no NaN-canonicalising v_max_f32 in front of it
 __device__ __forceinline__ float relu_bits(float v) { return __int_as_float(max(__float_as_int(v), 0)); }
 

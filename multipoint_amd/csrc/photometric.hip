@@ -51,16 +51,6 @@ __device__ __forceinline__ double hash_normal(unsigned long long key, unsigned l
 
 __device__ __forceinline__ float clip01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
 
-// borderInterpolate(p, n, BORDER_REFLECT_101) with the reflection repeated while p stays outside: period 2n - 2
-__device__ __forceinline__ int reflect101(int p, int n)
-{
-    if (n == 1) return 0;
-    const int period = 2 * n - 2;
-    int q = p % period;
-    if (q < 0) q += period;
-    return q < n ? q : period - q;
-}
-
 // ---------------------------------------------------------------------------------------------
 // image.mean()
 // ---------------------------------------------------------------------------------------------

@@ -17,6 +17,7 @@
 // double, stored as float and normalised.  All pixel arithmetic is fp32 with every step rounded (no contraction into FMA), so
 // that a numpy float32 restatement matches bit for bit.
 #include "host.h"
+#include "mp_device.h"
 
 #pragma clang fp contract(off)
 
@@ -31,16 +32,7 @@ struct BlurWeights {
     float w[MAX_K];
 };
 
-// borderInterpolate(p, n, BORDER_REFLECT_101); k/2 < n keeps every pixel an output needs within one reflection, the modulo
-// keeps the rows and columns a partial tile loads but never uses inside the frame as well
-__device__ __forceinline__ int reflect101(int p, int n)
-{
-    if (n == 1) return 0;
-    const int period = 2 * n - 2;
-    int q = p % period;
-    if (q < 0) q += period;
-    return q < n ? q : period - q;
-}
+// (the border is reflect101 of mp_device.h; k/2 < n keeps every pixel an output needs within one reflection)
 
 // dynamic LDS: 32 floats of weights | the input rows [nrows][PW] | the row-filtered rows [nrows][OW]
 template <int DEC, int KT>

@@ -44,16 +44,6 @@ __device__ __forceinline__ float resolve_color(const mp_shapes_cmd& c, double me
     return (float)(c.resolve && fabs(c.u - mean) < c.min_contrast ? c.col_b : c.col_a);
 }
 
-// borderInterpolate(p, n, BORDER_REFLECT_101) with the reflection repeated while p stays outside: period 2n - 2
-__device__ __forceinline__ int reflect101(int p, int n)
-{
-    if (n == 1) return 0;
-    const int period = 2 * n - 2;
-    int q = p % period;
-    if (q < 0) q += period;
-    return q < n ? q : period - q;
-}
-
 // Circle(): half[r][k] = the half width of the widest span the midpoint walk of radius r draws on the rows cy -+ k
 __global__ __launch_bounds__(256) void shapes_halfwidth_kernel(short* half)
 {
