@@ -47,6 +47,8 @@ def build_parser():
     parser.add_argument('--max-pairs', default=0, type=int, help='Use this many evenly spaced pairs (0: all)')
     parser.add_argument('--batch', default=8, type=int, help='Pairs per forward')
     parser.add_argument('--max-iters', default=2000, type=int, help='RANSAC hypotheses')
+    parser.add_argument('--subpixel', action='store_true', help='Refine the keypoints to sub-pixel positions on the detector map '
+                        '(prediction.subpixel.enable): the pooled matches then hold float positions')
     parser.add_argument('--force', action='store_true', help='Overwrite an existing yaml file (it may be hand-measured)')
     return parser
 
@@ -107,6 +109,8 @@ def estimate_on_gpu(args, config, names):
     device = select_device(config)
     print('Estimating on device: {}'.format(device))
     pred = config['prediction']
+    if getattr(args, 'subpixel', False):
+        pred = dict(pred, subpixel=dict(pred.get('subpixel') or {}, enable=True))
     net = load_network(config, args.model_dir, args.version, device, args.seed)
     pipe = PairPipeline(net, pred)
     pts, counts = [], []

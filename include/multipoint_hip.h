@@ -189,6 +189,24 @@ int mp_extract_keypoints(mp_handle* h, const float* map, const unsigned char* va
 int mp_sample_descriptors(mp_handle* h, const float* desc, int B, int Hc, int Wc, int D, int H, int W,
                           const int* kp_yx, const int* kp_count, int K, float* out, void* stream);
 
+/* ---- sub-pixel keypoints (an extension: the reference keeps torch.nonzero's integer pixels; its interpolate_descriptors and
+ * cv2.findHomography take float positions) ----
+ * mp_refine_keypoints: a separable log-parabola fit on the detector map around every entry of a keypoint list, one thread per
+ * entry.  Any H x W.
+ *   prob       fp32 [B][H][W]: the FORWARD's map -- not the NMS output, whose suppressed neighbours are zero
+ *   kp_yx, kp_count, K   a list as mp_detect_keypoints / mp_extract_keypoints write it (a count above K is clamped)
+ *   kp_sub_yx  fp32 [B][K][2] (y, x); rows k >= min(kp_count[b], K) are written as zeros
+ * Per axis, with p0 = prob[y][x], p-, p+ its two neighbours on that axis, l = logf(p) and den = l- - 2 l0 + l+: the axis is
+ * refined iff both neighbours lie inside the frame, p-, p0, p+ are all finite and > 0, p0 >= p-, p0 >= p+ and den < 0; then
+ * delta = 0.5 (l- - l+) / den (so |delta| <= 0.5), else delta = 0 and the output is exactly (float)y / (float)x.
+ * mp_sample_descriptors_f: mp_sample_descriptors at float positions kp_yx_f [B][K][2] (the reference's keypoints.float(),
+ * utils.py:159-167): the same kernel body from the normalisation on, zero padding of out-of-range taps as grid_sample's; whole
+ * numbers give the bits of mp_sample_descriptors. */
+int mp_refine_keypoints(mp_handle* h, const float* prob, int B, int H, int W, const int* kp_yx, const int* kp_count, int K,
+                        float* kp_sub_yx, void* stream);
+int mp_sample_descriptors_f(mp_handle* h, const float* desc, int B, int Hc, int Wc, int D, int H, int W,
+                            const float* kp_yx_f, const int* kp_count, int K, float* out, void* stream);
+
 /* replaces utils.get_matches(..., 'nnmatcher' | 'bfmatcher' crossCheck=True)
  * (multipoint/utils/matching.py:4-33, NNMatcher.match :41-72) for P independent pairs.
  *   descA/descB: first pair's descriptors [K][D]; pair p at + p * pair_stride floats
@@ -237,6 +255,11 @@ int mp_repeatability(mp_handle* h, const int* kp_yx, const int* kp_count, const 
 int mp_find_homography(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K,
                        double reproj_threshold, int max_iters, unsigned long long seed, double* homography,
                        unsigned char* inlier_mask, int* n_inliers, void* stream);
+/* the same on sub-pixel keypoints: kp_sub_yx fp32 [2P][K][2] (y, x) (mp_refine_keypoints) in the place of kp_yx; one kernel
+ * template behind both, so a float list of whole numbers gives the bits of mp_find_homography */
+int mp_find_homography_f(mp_handle* h, const float* kp_sub_yx, const int* kp_count, const int* match_idx, int P, int K,
+                         double reproj_threshold, int max_iters, unsigned long long seed, double* homography,
+                         unsigned char* inlier_mask, int* n_inliers, void* stream);
 
 /* the other modes of utils.get_matches (multipoint/utils/matching.py:4-33); same descriptor / count addressing as
  * mp_match_mutual_nn, 1 <= D <= 384.
@@ -308,6 +331,10 @@ int mp_match_guided(mp_handle* h, const float* descA, const int* countA, const f
 int mp_refine_homography(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K,
                          double reproj_threshold, int iters, double* homography, unsigned char* inlier_mask, int* n_inliers,
                          double* cost /* [P][2] or NULL */, void* stream);
+/* the same on sub-pixel keypoints (kp_sub_yx fp32 [2P][K][2]); whole numbers give the bits of mp_refine_homography */
+int mp_refine_homography_f(mp_handle* h, const float* kp_sub_yx, const int* kp_count, const int* match_idx, int P, int K,
+                           double reproj_threshold, int iters, double* homography, unsigned char* inlier_mask, int* n_inliers,
+                           double* cost /* [P][2] or NULL */, void* stream);
 
 /* ---- pooled homography: ONE model per group of pairs, from the matches of all of them (an extension; the reference leaves the
  * initial transform of a recording to a hand measurement).  A rig has one optical -> thermal transform for a whole recording; a
@@ -340,6 +367,11 @@ int mp_pooled_workspace_bytes(int P, int G, int max_iters, long long* bytes);
 int mp_pool_matches(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, const int* groups /* [P] or NULL */,
                     int P, int K, int G, float* pts, int* query_index, long long capacity, int* pair_offsets, int* group_offsets,
                     void* workspace, long long workspace_bytes, void* stream);
+/* mp_pool_matches on sub-pixel keypoints (kp_sub_yx fp32 [2P][K][2]): pts holds the float positions as they are; the pooled
+ * estimators take pts and need no second entry */
+int mp_pool_matches_f(mp_handle* h, const float* kp_sub_yx, const int* kp_count, const int* match_idx,
+                      const int* groups /* [P] or NULL */, int P, int K, int G, float* pts, int* query_index, long long capacity,
+                      int* pair_offsets, int* group_offsets, void* workspace, long long workspace_bytes, void* stream);
 int mp_find_homography_pooled(mp_handle* h, const float* pts, const int* group_offsets, long long N, int G,
                               double reproj_threshold, int max_iters, unsigned long long seed, double* homography,
                               unsigned char* inlier_mask, int* n_inliers, void* workspace, long long workspace_bytes, void* stream);

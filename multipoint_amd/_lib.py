@@ -101,6 +101,9 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_void_p]),
     'mp_sample_descriptors': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'mp_refine_keypoints': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'mp_sample_descriptors_f': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'mp_match_mutual_nn': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int,
                                    c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     'mp_match_nearest': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int, c_int, c_int,
@@ -119,10 +122,16 @@ SIGNATURES = {
                                    ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p]),
     'mp_refine_homography': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_int,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'mp_find_homography_f': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_int,
+                                     ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'mp_refine_homography_f': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_int,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'mp_pooled_chunk': (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     'mp_pooled_workspace_bytes': (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
     'mp_pool_matches': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_ll,
                                 c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
+    'mp_pool_matches_f': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_ll,
+                                  c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
     'mp_find_homography_pooled': (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_int, ctypes.c_double, c_int, ctypes.c_ulonglong,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
     'mp_refine_homography_pooled': (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_int, ctypes.c_double, c_int, c_void_p, c_void_p,

@@ -10,15 +10,25 @@
 // OpenCV's last step, the Levenberg-Marquardt polish of the refitted model, is a launch of its own (refine_kernel).
 // This file locates a pair's matches (gather: ordered compaction into LDS) and hands them out as a PairView; the refit and the
 // polish are the kernel templates of mp_homography.h, which homography_pooled.hip runs on a group's rows in global memory.
+// The kernels and launchers are templates on the keypoint type KP -- int pixels, or float sub-pixel positions
+// (mp_refine_keypoints) -- which only decides what gather reads.  A translation unit instantiates them for ONE type,
+// MP_HOMOGRAPHY_KP: int here, float in homography_f.hip, which includes this file.  Two instantiations side by side change what
+// the compiler inlines (a helper with a single caller is inlined, with two it stays a call) and with that the fp64 contractions
+// of the refit: the int entries' bits, and their equality with the pooled route's, must not depend on the float entries.
 #include "mp_common.h"
 #include "mp_device.h"
 #include "mp_homography.h"
+
+#ifndef MP_HOMOGRAPHY_KP
+#define MP_HOMOGRAPHY_KP int
+#endif
 
 namespace {
 
 // gather the matched (x,y)->(u,v) pairs of pair p into LDS in query order; returns their number
 // pts: [n][4] floats in LDS order x, y, u, v; qidx (may be NULL): [n] the query index of each match
-__device__ int gather(const int* kp_yx, const int* kp_count, const int* match_idx, int p, int K, float* pts, int* qidx)
+template <class KP>
+__device__ int gather(const KP* kp_yx, const int* kp_count, const int* match_idx, int p, int K, float* pts, int* qidx)
 {
     return compact_matches(kp_count, match_idx, p, K, [&](int pos, int i, int j) {
         const float4 q = match_point(kp_yx, p, K, i, j);
@@ -27,7 +37,8 @@ __device__ int gather(const int* kp_yx, const int* kp_count, const int* match_id
     });
 }
 
-__global__ __launch_bounds__(256) void ransac_kernel(const int* __restrict__ kp_yx, const int* __restrict__ kp_count,
+template <class KP>
+__global__ __launch_bounds__(256) void ransac_kernel(const KP* __restrict__ kp_yx, const int* __restrict__ kp_count,
                                                      const int* __restrict__ match_idx, int K, int T, double thr,
                                                      unsigned long long seed, unsigned long long* __restrict__ best)
 {
@@ -47,9 +58,11 @@ __global__ __launch_bounds__(256) void ransac_kernel(const int* __restrict__ kp_
 }
 
 // what refit_kernel / refine_kernel (mp_homography.h) are launched with: the view of pair p is its gathered list in LDS
-// (dynamic LDS: [K][4] floats, then [K] ints) and its row of the mask
+// (dynamic LDS: [K][4] floats, then [K] ints) and its row of the mask.  KP: the keypoint type (int pixels or float sub-pixel
+// positions); it only decides what gather reads
+template <class KP>
 struct PairSource {
-    const int* kp_yx;
+    const KP* kp_yx;
     const int* kp_count;
     const int* match_idx;
     int K;
@@ -65,21 +78,30 @@ struct PairSource {
 
 }  // namespace
 
-void launch_ransac_homography(const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K, int T, double thr,
+template <class KP>
+void launch_ransac_homography(const KP* kp_yx, const int* kp_count, const int* match_idx, int P, int K, int T, double thr,
                               unsigned long long seed, unsigned long long* best, double* H_out, unsigned char* mask,
                               int* n_inliers, hipStream_t s)
 {
     const size_t lds1 = (size_t)K * 4 * sizeof(float), lds2 = lds1 + (size_t)K * sizeof(int);
-    hipLaunchKernelGGL(ransac_kernel, dim3((T + 255) / 256, P), dim3(256), lds1, s, kp_yx, kp_count, match_idx, K, T, thr, seed, best);
-    hipLaunchKernelGGL(refit_kernel<PairSource>, dim3(P), dim3(256), lds2, s, PairSource{kp_yx, kp_count, match_idx, K, mask}, thr,
+    hipLaunchKernelGGL(ransac_kernel<KP>, dim3((T + 255) / 256, P), dim3(256), lds1, s, kp_yx, kp_count, match_idx, K, T, thr, seed, best);
+    hipLaunchKernelGGL(refit_kernel<PairSource<KP>>, dim3(P), dim3(256), lds2, s, PairSource<KP>{kp_yx, kp_count, match_idx, K, mask}, thr,
                        seed, best, H_out, n_inliers);
 }
 
+template void launch_ransac_homography<MP_HOMOGRAPHY_KP>(const MP_HOMOGRAPHY_KP*, const int*, const int*, int, int, int, double,
+                                                         unsigned long long, unsigned long long*, double*, unsigned char*, int*,
+                                                         hipStream_t);
+
 // mask must be zeroed by the caller (only the matched optical keypoints are written)
-void launch_refine_homography(const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K, double thr, int iters,
+template <class KP>
+void launch_refine_homography(const KP* kp_yx, const int* kp_count, const int* match_idx, int P, int K, double thr, int iters,
                               double* H_io, unsigned char* mask, int* n_inliers, double* cost, hipStream_t s)
 {
     const size_t lds = (size_t)K * 4 * sizeof(float) + (size_t)K * sizeof(int);
-    hipLaunchKernelGGL(refine_kernel<PairSource>, dim3(P), dim3(256), lds, s, PairSource{kp_yx, kp_count, match_idx, K, mask}, thr,
+    hipLaunchKernelGGL(refine_kernel<PairSource<KP>>, dim3(P), dim3(256), lds, s, PairSource<KP>{kp_yx, kp_count, match_idx, K, mask}, thr,
                        iters, H_io, n_inliers, cost);
 }
+
+template void launch_refine_homography<MP_HOMOGRAPHY_KP>(const MP_HOMOGRAPHY_KP*, const int*, const int*, int, int, double, int,
+                                                         double*, unsigned char*, int*, double*, hipStream_t);

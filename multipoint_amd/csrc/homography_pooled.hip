@@ -83,7 +83,8 @@ __global__ __launch_bounds__(256) void pool_scan_kernel(const int* __restrict__ 
 
 // one workgroup per pair: its usable matches in query order to pts / query_index from row pair_offsets[p] on.  Rows at or
 // beyond `capacity` are not written.
-__global__ __launch_bounds__(256) void pool_write_kernel(const int* __restrict__ kp_yx, const int* __restrict__ kp_count,
+template <class KP>
+__global__ __launch_bounds__(256) void pool_write_kernel(const KP* __restrict__ kp_yx, const int* __restrict__ kp_count,
                                                          const int* __restrict__ match_idx, int K,
                                                          const int* __restrict__ pair_offsets, long long capacity,
                                                          float4* __restrict__ pts, int* __restrict__ query_index)
@@ -178,15 +179,21 @@ struct PooledSource {
 
 }  // namespace
 
-void launch_pool_matches(const int* kp_yx, const int* kp_count, const int* match_idx, const int* groups, int P, int K, int G,
+template <class KP>
+void launch_pool_matches(const KP* kp_yx, const int* kp_count, const int* match_idx, const int* groups, int P, int K, int G,
                          float* pts, int* query_index, long long capacity, int* pair_offsets, int* group_offsets, int* pair_cnt,
                          hipStream_t s)
 {
     hipLaunchKernelGGL(pool_count_kernel, dim3(P), dim3(256), 0, s, kp_count, match_idx, K, pair_cnt);
     hipLaunchKernelGGL(pool_scan_kernel, dim3(1), dim3(256), 0, s, pair_cnt, groups, P, G, pair_offsets, group_offsets);
-    hipLaunchKernelGGL(pool_write_kernel, dim3(P), dim3(256), 0, s, kp_yx, kp_count, match_idx, K, pair_offsets, capacity,
+    hipLaunchKernelGGL(pool_write_kernel<KP>, dim3(P), dim3(256), 0, s, kp_yx, kp_count, match_idx, K, pair_offsets, capacity,
                        reinterpret_cast<float4*>(pts), query_index);
 }
+
+template void launch_pool_matches<int>(const int*, const int*, const int*, const int*, int, int, int, float*, int*, long long, int*, int*,
+                                       int*, hipStream_t);
+template void launch_pool_matches<float>(const float*, const int*, const int*, const int*, int, int, int, float*, int*, long long, int*,
+                                         int*, int*, hipStream_t);
 
 void launch_find_homography_pooled(const float* pts, const int* group_offsets, int N, int G, int T, double thr,
                                    unsigned long long seed, unsigned int* counts, unsigned long long* best, double* H_out,

@@ -335,10 +335,16 @@ size_t keypoint_scratch_ints(int B, int H, int W);
 void launch_extract_threshold(const float* map, const unsigned char* mask, int B, int H, int W, float thr, int K, int* kp_yx,
                               float* kp_score, int* kp_count, int* seg_scratch, hipStream_t s);
 
+// sub-pixel keypoints (keypoints_subpixel.hip): a separable log-parabola fit on the detector map around every list entry;
+// kp_sub_yx [B][K][2] fp32 (y, x), rows beyond min(kp_count[b], K) zero
+void launch_refine_keypoints(const float* prob, int B, int H, int W, const int* kp_yx, const int* kp_count, int K,
+                             float* kp_sub_yx, hipStream_t s);
+
 // bilinear sampling (grid_sample align_corners=True, zeros) + L2 normalise.
-// desc [B][Hc][Wc][D] channels-last; kp_yx [B][K][2]; out [B][K][D]
+// desc [B][Hc][Wc][D] channels-last; kp_yx [B][K][2] int pixels or float sub-pixel positions; out [B][K][D]
+template <class KP>
 void launch_sample_desc(const float* desc, int B, int Hc, int Wc, int D, int H, int W,
-                        const int* kp_yx, const int* kp_count, int K, float* out, hipStream_t s);
+                        const KP* kp_yx, const int* kp_count, int K, float* out, hipStream_t s);
 
 // MFMA matchers (match_mfma.hip, unit rows, D in {64, 128, 256}); their scratch holds one array of packed keys per column share
 constexpr int MATCH_SHARES = 2;     // column shares of the row passes (mp_match.h: column_share)
@@ -382,13 +388,16 @@ void launch_repeatability(const int* kp_yx, const int* kp_count, const double* h
                           long long* warped, int* out, hipStream_t s);
 // batched RANSAC homography (predict_align_image_pair.py:205-216): best [P] scratch (pre-set to 0), H_out [P][9] double
 // (x,y) optical -> (x,y) thermal, mask [P][K] uint8 per optical keypoint (pre-set to 0), n_inliers [P]
-void launch_ransac_homography(const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K, int T, double thr,
+// KP (here and in the two launchers below): int for pixel keypoints, float for sub-pixel ones
+template <class KP>
+void launch_ransac_homography(const KP* kp_yx, const int* kp_count, const int* match_idx, int P, int K, int T, double thr,
                               unsigned long long seed, unsigned long long* best, double* H_out, unsigned char* mask,
                               int* n_inliers, hipStream_t s);
 
 // Levenberg-Marquardt polish of hom [P][9] (in: estimate, out: polished, h22 = 1) over the matches within thr of the estimate;
 // mask [P][K] zeroed by the caller, cost [P][2] (before / after) or NULL
-void launch_refine_homography(const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K, double thr, int iters,
+template <class KP>
+void launch_refine_homography(const KP* kp_yx, const int* kp_count, const int* match_idx, int P, int K, double thr, int iters,
                               double* H_io, unsigned char* mask, int* n_inliers, double* cost, hipStream_t s);
 
 // pooled RANSAC homography (homography_pooled.hip): one model per group of pairs from their compacted matches
@@ -396,7 +405,8 @@ constexpr int MP_POOLED_CHUNK = 1024;        // points per staged LDS chunk of t
 constexpr int MP_POOLED_MAX_SPLITS = 64;     // most workgroups that share the points of one (hypothesis block, group)
 // pts [capacity][4] fp32 (16-byte aligned) / query_index [capacity]: the usable matches of all pairs, pair-major in query order;
 // pair_offsets [P + 1], group_offsets [G + 1] (groups: device [P] non-decreasing ids or NULL = one group); pair_cnt [P] scratch
-void launch_pool_matches(const int* kp_yx, const int* kp_count, const int* match_idx, const int* groups, int P, int K, int G,
+template <class KP>
+void launch_pool_matches(const KP* kp_yx, const int* kp_count, const int* match_idx, const int* groups, int P, int K, int G,
                          float* pts, int* query_index, long long capacity, int* pair_offsets, int* group_offsets, int* pair_cnt,
                          hipStream_t s);
 // counts [G][T] and mask [N] pre-set to 0; best [G] scratch; H_out [G][9], n_inliers [G]

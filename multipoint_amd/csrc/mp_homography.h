@@ -80,10 +80,12 @@ __device__ __forceinline__ int usable_match(const int* match_idx, int p, int K, 
 }
 
 // the correspondence (x, y) -> (u, v) of query i and partner j of pair p (kp_yx: [2P][K] (y, x), slot 2p optical, 2p + 1 thermal)
-__device__ __forceinline__ float4 match_point(const int* kp_yx, int p, int K, int i, int j)
+// KP: int (pixel keypoints) or float (sub-pixel ones, mp_refine_keypoints): everything behind this cast is one body
+template <class KP>
+__device__ __forceinline__ float4 match_point(const KP* kp_yx, int p, int K, int i, int j)
 {
-    const int* o = kp_yx + ((size_t)(2 * p) * K + i) * 2;
-    const int* t = kp_yx + ((size_t)(2 * p + 1) * K + j) * 2;
+    const KP* o = kp_yx + ((size_t)(2 * p) * K + i) * 2;
+    const KP* t = kp_yx + ((size_t)(2 * p + 1) * K + j) * 2;
     return make_float4((float)o[1], (float)o[0], (float)t[1], (float)t[0]);
 }
 

@@ -199,15 +199,42 @@ int mp_extract_keypoints(mp_handle* h, const float* map, const unsigned char* va
     return launch_status(h);
 }
 
+// mp_sample_descriptors / mp_sample_descriptors_f: the same checks and launch on int or float keypoints
+extern "C++" {          // (a template cannot have C linkage)
+template <class KP>
+static int sample_descriptors(mp_handle* h, const std::string& fn, const float* desc, int B, int Hc, int Wc, int D, int H, int W,
+                              const KP* kp_yx, const int* kp_count, int K, float* out, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!desc || !kp_yx || !kp_count || !out) return fail(h, MP_EINVAL, fn + ": NULL tensor");
+    if (D % 64 != 0 || D > 384 || D <= 0)
+        return fail(h, MP_EINVAL, fn + ": D must be a multiple of 64 up to 384");
+    MP_HIP(hipSetDevice(h->device));
+    launch_sample_desc(desc, B, Hc, Wc, D, H, W, kp_yx, kp_count, K, out, static_cast<hipStream_t>(stream));
+    return launch_status(h);
+}
+}
+
 int mp_sample_descriptors(mp_handle* h, const float* desc, int B, int Hc, int Wc, int D, int H, int W,
                           const int* kp_yx, const int* kp_count, int K, float* out, void* stream)
 {
+    return sample_descriptors(h, "mp_sample_descriptors", desc, B, Hc, Wc, D, H, W, kp_yx, kp_count, K, out, stream);
+}
+
+int mp_sample_descriptors_f(mp_handle* h, const float* desc, int B, int Hc, int Wc, int D, int H, int W,
+                            const float* kp_yx_f, const int* kp_count, int K, float* out, void* stream)
+{
+    return sample_descriptors(h, "mp_sample_descriptors_f", desc, B, Hc, Wc, D, H, W, kp_yx_f, kp_count, K, out, stream);
+}
+
+int mp_refine_keypoints(mp_handle* h, const float* prob, int B, int H, int W, const int* kp_yx, const int* kp_count, int K,
+                        float* kp_sub_yx, void* stream)
+{
     if (!h) return MP_EINVAL;
-    if (!desc || !kp_yx || !kp_count || !out) return fail(h, MP_EINVAL, "mp_sample_descriptors: NULL tensor");
-    if (D % 64 != 0 || D > 384 || D <= 0)
-        return fail(h, MP_EINVAL, "mp_sample_descriptors: D must be a multiple of 64 up to 384");
+    if (!prob || !kp_yx || !kp_count || !kp_sub_yx) return fail(h, MP_EINVAL, "mp_refine_keypoints: NULL tensor");
+    if (B <= 0 || H <= 0 || W <= 0 || K <= 0) return fail(h, MP_EINVAL, "mp_refine_keypoints: B, H, W, K must be positive");
     MP_HIP(hipSetDevice(h->device));
-    launch_sample_desc(desc, B, Hc, Wc, D, H, W, kp_yx, kp_count, K, out, static_cast<hipStream_t>(stream));
+    launch_refine_keypoints(prob, B, H, W, kp_yx, kp_count, K, kp_sub_yx, static_cast<hipStream_t>(stream));
     return launch_status(h);
 }
 
@@ -362,16 +389,19 @@ int mp_repeatability(mp_handle* h, const int* kp_yx, const int* kp_count, const 
     return launch_status(h);
 }
 
-int mp_find_homography(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K,
-                       double reproj_threshold, int max_iters, unsigned long long seed, double* homography,
-                       unsigned char* inlier_mask, int* n_inliers, void* stream)
+// mp_find_homography / mp_find_homography_f: the same checks and launches on int or float keypoints
+extern "C++" {          // (a template cannot have C linkage)
+template <class KP>
+static int find_homography(mp_handle* h, const std::string& fn, const KP* kp_yx, const int* kp_count, const int* match_idx, int P,
+                           int K, double reproj_threshold, int max_iters, unsigned long long seed, double* homography,
+                           unsigned char* inlier_mask, int* n_inliers, void* stream)
 {
     if (!h) return MP_EINVAL;
     if (!kp_yx || !kp_count || !match_idx || !homography || !inlier_mask || !n_inliers)
-        return fail(h, MP_EINVAL, "mp_find_homography: NULL tensor");
-    if (P <= 0 || K <= 0 || K > 3200) return fail(h, MP_EINVAL, "mp_find_homography: need P > 0 and 0 < K <= 3200");
-    if (max_iters <= 0 || max_iters > (1 << 20)) return fail(h, MP_EINVAL, "mp_find_homography: max_iters out of range");
-    if (!(reproj_threshold > 0.0)) return fail(h, MP_EINVAL, "mp_find_homography: threshold must be positive");
+        return fail(h, MP_EINVAL, fn + ": NULL tensor");
+    if (P <= 0 || K <= 0 || K > 3200) return fail(h, MP_EINVAL, fn + ": need P > 0 and 0 < K <= 3200");
+    if (max_iters <= 0 || max_iters > (1 << 20)) return fail(h, MP_EINVAL, fn + ": max_iters out of range");
+    if (!(reproj_threshold > 0.0)) return fail(h, MP_EINVAL, fn + ": threshold must be positive");
     hipStream_t s = static_cast<hipStream_t>(stream);
     MP_HIP(hipSetDevice(h->device));
     int rc;
@@ -383,23 +413,60 @@ int mp_find_homography(mp_handle* h, const int* kp_yx, const int* kp_count, cons
                              inlier_mask, n_inliers, s);
     return launch_status(h);
 }
+}
 
-int mp_refine_homography(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K,
-                         double reproj_threshold, int iters, double* homography, unsigned char* inlier_mask, int* n_inliers,
-                         double* cost, void* stream)
+int mp_find_homography(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K,
+                       double reproj_threshold, int max_iters, unsigned long long seed, double* homography,
+                       unsigned char* inlier_mask, int* n_inliers, void* stream)
+{
+    return find_homography(h, "mp_find_homography", kp_yx, kp_count, match_idx, P, K, reproj_threshold, max_iters, seed, homography,
+                           inlier_mask, n_inliers, stream);
+}
+
+int mp_find_homography_f(mp_handle* h, const float* kp_sub_yx, const int* kp_count, const int* match_idx, int P, int K,
+                         double reproj_threshold, int max_iters, unsigned long long seed, double* homography,
+                         unsigned char* inlier_mask, int* n_inliers, void* stream)
+{
+    return find_homography(h, "mp_find_homography_f", kp_sub_yx, kp_count, match_idx, P, K, reproj_threshold, max_iters, seed,
+                           homography, inlier_mask, n_inliers, stream);
+}
+
+// mp_refine_homography / mp_refine_homography_f
+extern "C++" {          // (a template cannot have C linkage)
+template <class KP>
+static int refine_homography(mp_handle* h, const std::string& fn, const KP* kp_yx, const int* kp_count, const int* match_idx, int P,
+                             int K, double reproj_threshold, int iters, double* homography, unsigned char* inlier_mask,
+                             int* n_inliers, double* cost, void* stream)
 {
     if (!h) return MP_EINVAL;
     if (!kp_yx || !kp_count || !match_idx || !homography || !inlier_mask || !n_inliers)
-        return fail(h, MP_EINVAL, "mp_refine_homography: NULL tensor");
-    if (P <= 0 || K <= 0 || K > 3200) return fail(h, MP_EINVAL, "mp_refine_homography: need P > 0 and 0 < K <= 3200");
-    if (iters < 0 || iters > 1000) return fail(h, MP_EINVAL, "mp_refine_homography: iters must be in [0, 1000]");
-    if (!(reproj_threshold > 0.0)) return fail(h, MP_EINVAL, "mp_refine_homography: threshold must be positive");
+        return fail(h, MP_EINVAL, fn + ": NULL tensor");
+    if (P <= 0 || K <= 0 || K > 3200) return fail(h, MP_EINVAL, fn + ": need P > 0 and 0 < K <= 3200");
+    if (iters < 0 || iters > 1000) return fail(h, MP_EINVAL, fn + ": iters must be in [0, 1000]");
+    if (!(reproj_threshold > 0.0)) return fail(h, MP_EINVAL, fn + ": threshold must be positive");
     hipStream_t s = static_cast<hipStream_t>(stream);
     MP_HIP(hipSetDevice(h->device));
     MP_HIP(hipMemsetAsync(inlier_mask, 0, (size_t)P * K, s));
     launch_refine_homography(kp_yx, kp_count, match_idx, P, K, reproj_threshold, iters, homography, inlier_mask, n_inliers, cost,
                              s);
     return launch_status(h);
+}
+}
+
+int mp_refine_homography(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K,
+                         double reproj_threshold, int iters, double* homography, unsigned char* inlier_mask, int* n_inliers,
+                         double* cost, void* stream)
+{
+    return refine_homography(h, "mp_refine_homography", kp_yx, kp_count, match_idx, P, K, reproj_threshold, iters, homography,
+                             inlier_mask, n_inliers, cost, stream);
+}
+
+int mp_refine_homography_f(mp_handle* h, const float* kp_sub_yx, const int* kp_count, const int* match_idx, int P, int K,
+                           double reproj_threshold, int iters, double* homography, unsigned char* inlier_mask, int* n_inliers,
+                           double* cost, void* stream)
+{
+    return refine_homography(h, "mp_refine_homography_f", kp_sub_yx, kp_count, match_idx, P, K, reproj_threshold, iters, homography,
+                             inlier_mask, n_inliers, cost, stream);
 }
 
 // ---- pooled homography: one model per group of pairs (homography_pooled.hip) ----
@@ -443,25 +510,45 @@ int mp_pooled_workspace_bytes(int P, int G, int max_iters, long long* bytes)
     return MP_OK;
 }
 
-int mp_pool_matches(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, const int* groups, int P, int K,
-                    int G, float* pts, int* query_index, long long capacity, int* pair_offsets, int* group_offsets,
-                    void* workspace, long long workspace_bytes, void* stream)
+// mp_pool_matches / mp_pool_matches_f
+extern "C++" {          // (a template cannot have C linkage)
+template <class KP>
+static int pool_matches(mp_handle* h, const std::string& fn, const KP* kp_yx, const int* kp_count, const int* match_idx,
+                        const int* groups, int P, int K, int G, float* pts, int* query_index, long long capacity, int* pair_offsets,
+                        int* group_offsets, void* workspace, long long workspace_bytes, void* stream)
 {
     if (!h) return MP_EINVAL;
     if (!kp_yx || !kp_count || !match_idx || !pair_offsets || !group_offsets)
-        return fail(h, MP_EINVAL, "mp_pool_matches: NULL tensor");
-    if (P <= 0 || K <= 0 || (long long)P * K > 0x7fffffffLL) return fail(h, MP_EINVAL, "mp_pool_matches: need P > 0, K > 0 and P * K < 2^31");
-    if (G <= 0 || G > 65535) return fail(h, MP_EINVAL, "mp_pool_matches: need 0 < G <= 65535 groups");
-    if (!groups && G != 1) return fail(h, MP_EINVAL, "mp_pool_matches: without group ids there is one group (G = 1)");
-    if (capacity < 0 || (capacity > 0 && (!pts || !query_index))) return fail(h, MP_EINVAL, "mp_pool_matches: NULL tensor");
-    if ((reinterpret_cast<uintptr_t>(pts) & 15) != 0) return fail(h, MP_EINVAL, "mp_pool_matches: pts must be 16-byte aligned");
+        return fail(h, MP_EINVAL, fn + ": NULL tensor");
+    if (P <= 0 || K <= 0 || (long long)P * K > 0x7fffffffLL) return fail(h, MP_EINVAL, fn + ": need P > 0, K > 0 and P * K < 2^31");
+    if (G <= 0 || G > 65535) return fail(h, MP_EINVAL, fn + ": need 0 < G <= 65535 groups");
+    if (!groups && G != 1) return fail(h, MP_EINVAL, fn + ": without group ids there is one group (G = 1)");
+    if (capacity < 0 || (capacity > 0 && (!pts || !query_index))) return fail(h, MP_EINVAL, fn + ": NULL tensor");
+    if ((reinterpret_cast<uintptr_t>(pts) & 15) != 0) return fail(h, MP_EINVAL, fn + ": pts must be 16-byte aligned");
     if (!workspace || workspace_bytes < (long long)pooled_pool_bytes(P))
-        return fail(h, MP_EINVAL, "mp_pool_matches: workspace smaller than mp_pooled_workspace_bytes");
+        return fail(h, MP_EINVAL, fn + ": workspace smaller than mp_pooled_workspace_bytes");
     hipStream_t s = static_cast<hipStream_t>(stream);
     MP_HIP(hipSetDevice(h->device));
     launch_pool_matches(kp_yx, kp_count, match_idx, groups, P, K, G, pts, query_index, capacity, pair_offsets, group_offsets,
                         static_cast<int*>(workspace), s);
     return launch_status(h);
+}
+}
+
+int mp_pool_matches(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, const int* groups, int P, int K,
+                    int G, float* pts, int* query_index, long long capacity, int* pair_offsets, int* group_offsets,
+                    void* workspace, long long workspace_bytes, void* stream)
+{
+    return pool_matches(h, "mp_pool_matches", kp_yx, kp_count, match_idx, groups, P, K, G, pts, query_index, capacity, pair_offsets,
+                        group_offsets, workspace, workspace_bytes, stream);
+}
+
+int mp_pool_matches_f(mp_handle* h, const float* kp_sub_yx, const int* kp_count, const int* match_idx, const int* groups, int P, int K,
+                      int G, float* pts, int* query_index, long long capacity, int* pair_offsets, int* group_offsets,
+                      void* workspace, long long workspace_bytes, void* stream)
+{
+    return pool_matches(h, "mp_pool_matches_f", kp_sub_yx, kp_count, match_idx, groups, P, K, G, pts, query_index, capacity,
+                        pair_offsets, group_offsets, workspace, workspace_bytes, stream);
 }
 
 int mp_find_homography_pooled(mp_handle* h, const float* pts, const int* group_offsets, long long N, int G,

@@ -6,9 +6,11 @@
 
 namespace {
 
+// KP: int (pixel keypoints) or float (sub-pixel positions, what the reference's keypoints.float() admits); one body from the cast on
+template <class KP>
 __global__ __launch_bounds__(256) void sample_desc_kernel(const float* __restrict__ desc, int B, int Hc,
                                                          int Wc, int D, int H, int W,
-                                                         const int* __restrict__ kp_yx,
+                                                         const KP* __restrict__ kp_yx,
                                                          const int* __restrict__ kp_count, int K,
                                                          float* __restrict__ out)
 {
@@ -21,7 +23,7 @@ __global__ __launch_bounds__(256) void sample_desc_kernel(const float* __restric
         for (int r = 0; r < (D >> 6); ++r) out[wid * D + r * 64 + lane] = 0.f;
         return;
     }
-    const int y = kp_yx[wid * 2], x = kp_yx[wid * 2 + 1];
+    const KP y = kp_yx[wid * 2], x = kp_yx[wid * 2 + 1];
     // utils.py:162-163 (fp32) then ATen grid_sampler unnormalize, align_corners=True
     const float gy = (float)y / ((float)H * 0.5f) - 1.0f;
     const float gx = (float)x / ((float)W * 0.5f) - 1.0f;
@@ -56,11 +58,15 @@ __global__ __launch_bounds__(256) void sample_desc_kernel(const float* __restric
 
 }  // namespace
 
+template <class KP>
 void launch_sample_desc(const float* desc, int B, int Hc, int Wc, int D, int H, int W,
-                        const int* kp_yx, const int* kp_count, int K, float* out, hipStream_t s)
+                        const KP* kp_yx, const int* kp_count, int K, float* out, hipStream_t s)
 {
     const long long waves = (long long)B * K;
     if (waves <= 0) return;
-    hipLaunchKernelGGL(sample_desc_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, desc, B,
+    hipLaunchKernelGGL(sample_desc_kernel<KP>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, desc, B,
                        Hc, Wc, D, H, W, kp_yx, kp_count, K, out);
 }
+
+template void launch_sample_desc<int>(const float*, int, int, int, int, int, int, const int*, const int*, int, float*, hipStream_t);
+template void launch_sample_desc<float>(const float*, int, int, int, int, int, int, const float*, const int*, int, float*, hipStream_t);

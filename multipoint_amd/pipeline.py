@@ -15,8 +15,12 @@ from .utils.matching import match_pairs, nearest_pairs
 
 
 class PairResults:
-    def __init__(self, kp_yx, kp_score, kp_count, desc, match_idx, match_dist, match_count, H, W, match_mode='mutual'):
+    def __init__(self, kp_yx, kp_score, kp_count, desc, match_idx, match_dist, match_count, H, W, match_mode='mutual', *,
+                 kp_sub=None):
         self.kp_yx, self.kp_score, self.kp_count = kp_yx, kp_score, kp_count
+        # sub-pixel positions of kp_yx, float32 [2P,K,2] (y, x) (prediction.subpixel; utils.refine_keypoints), or None: what the
+        # homography estimators read when it is set.  The metrics, the guided gate and the drawings stay on kp_yx.
+        self.kp_sub = kp_sub
         self.desc = desc
         self.match_idx, self.match_dist, self.match_count = match_idx, match_dist, match_count
         # which matcher filled match_idx: 'mutual' (mutual nearest neighbours: one-to-one), 'nearest' (every optical keypoint's
@@ -54,6 +58,7 @@ class PairResults:
         K = kp.shape[1]
         mi = self.match_idx.cpu().numpy(); md = self.match_dist.cpu().numpy()
         desc = self.desc.cpu().numpy()
+        sub = self.kp_sub.cpu().numpy() if self.kp_sub is not None else None
         out = []
         for p in range(self.num_pairs):
             no, nt = min(int(cnt[2 * p]), K), min(int(cnt[2 * p + 1]), K)
@@ -62,6 +67,8 @@ class PairResults:
                             desc_optical=desc[2 * p, :no], desc_thermal=desc[2 * p + 1, :nt],
                             match_query=q.astype(np.int64), match_train=mi[p, q].astype(np.int64),
                             match_dist=md[p, q]))
+            if sub is not None:
+                out[-1].update(kp_optical_sub=sub[2 * p, :no], kp_thermal_sub=sub[2 * p + 1, :nt])
         return out
 
 
@@ -85,6 +92,16 @@ class PairPipeline:
         self.topk = config.get('topk', 0)
         self.capacity = capacity
         self.nms_rounds = nms_rounds
+        # prediction.subpixel: {enable: false} (an extension): the keypoint lists are refined on the forward's map
+        # (utils.refine_keypoints), the descriptors are sampled at the refined positions, and the results carry kp_sub
+        sub = config.get('subpixel') or {}
+        unknown = set(sub) - {'enable'}
+        if unknown:
+            raise ValueError('subpixel: unknown key(s) %s' % sorted(unknown))
+        self.subpixel = bool(sub.get('enable', False))
+        if self.subpixel and hasattr(net, 'describe'):
+            raise ValueError('subpixel: ClassicDetectors models have no sub-pixel keypoints (LGHD descriptors are patch '
+                             'histograms at integer centres)')
         m = config.get('matching', {'method': 'bfmatcher', 'method_kwargs': {'crossCheck': True},
                                     'knn_matches': False})
         # The batched pipeline keeps ONE match per optical keypoint (match_idx [P][K]).  That fits the mutual-NN matchers
@@ -215,19 +232,21 @@ class PairPipeline:
         if mark is not None:
             mark()                  # keypoint lists done (stage timing)
         K = kp.shape[1]
+        # (on this stream right behind the lists; from the map they were made from -- a map the tie guard redid included)
+        kp_sub = U.refine_keypoints(prob, kp, cnt) if self.subpixel else None
         if 'orientation' in out:
             # ClassicDetectors: the patch histograms of the keypoints straight from the orientation maps -- what sampling the
             # reference's dense map yields, without the map
             desc = self.net.describe(out, kp, cnt)                                  # [B,K,384]
         else:
-            desc = U.interpolate_descriptors_batched(kp, cnt, out['desc'], H, W)        # [B,K,D]
+            desc = U.interpolate_descriptors_batched(kp if kp_sub is None else kp_sub, cnt, out['desc'], H, W)        # [B,K,D]
         # the interleaved list read in place: slot 2p against slot 2p + 1
         lay = dict(pair_stride=2 * K * desc.shape[2], count_stride=2)
         if self.match_mode == 'mutual':
             midx, mdist, mcnt = match_pairs(desc, cnt, desc[1:], cnt[1:], self.match_threshold, **lay)
         else:
             midx, mdist, mcnt = nearest_pairs(desc, cnt, desc[1:], cnt[1:], self.match_ratio, **lay)
-        return PairResults(kp, sc, cnt, desc, midx, mdist, mcnt, H, W, self.match_mode)
+        return PairResults(kp, sc, cnt, desc, midx, mdist, mcnt, H, W, self.match_mode, kp_sub=kp_sub)
 
     def __call__(self, optical, thermal, mask_optical=None, mask_thermal=None):
         images = self.interleave(optical, thermal)
@@ -273,10 +292,12 @@ class PairPipeline:
             if need <= K:
                 break
             K = ((need + 255) // 256) * 256
-        descs = []
+        descs, subs = [], []
         for (out, mask, h, w), (kp, sc, cnt) in zip(sides, lists):
+            subs.append(U.refine_keypoints(out['prob'], kp, cnt) if self.subpixel else None)
             descs.append(self.net.describe(out, kp, cnt) if 'orientation' in out
-                         else U.interpolate_descriptors_batched(kp, cnt, out['desc'], h, w))
+                         else U.interpolate_descriptors_batched(kp if subs[-1] is None else subs[-1], cnt, out['desc'], h, w))
+        kp_sub = torch.stack(subs, dim=1).reshape(2 * P, K, 2).contiguous() if self.subpixel else None
         kp, sc, cnt, desc = (torch.stack((a, b), dim=1).reshape(2 * P, *a.shape[1:]).contiguous()
                              for a, b in zip(lists[0] + (descs[0],), lists[1] + (descs[1],)))
         lay = dict(pair_stride=2 * K * desc.shape[2], count_stride=2)
@@ -284,7 +305,7 @@ class PairPipeline:
             midx, mdist, mcnt = match_pairs(desc, cnt, desc[1:], cnt[1:], self.match_threshold, **lay)
         else:
             midx, mdist, mcnt = nearest_pairs(desc, cnt, desc[1:], cnt[1:], self.match_ratio, **lay)
-        res = PairResults(kp, sc, cnt, desc, midx, mdist, mcnt, thermal.shape[2], thermal.shape[3], self.match_mode)
+        res = PairResults(kp, sc, cnt, desc, midx, mdist, mcnt, thermal.shape[2], thermal.shape[3], self.match_mode, kp_sub=kp_sub)
         self._last = res
         return res
 

@@ -66,6 +66,18 @@ def pair_metrics(res, homography, threshold_keypoints):
     return metrics, tp
 
 
+def _keypoints_for_estimate(res, h, entry):
+    """The keypoint list a homography estimator reads and the C entry that takes it: the sub-pixel positions res.kp_sub
+    through `entry`_f when the results carry them (prediction.subpixel), else the integer list through `entry`."""
+    sub = getattr(res, 'kp_sub', None)
+    if sub is not None:
+        if sub.dtype != torch.float32 or tuple(sub.shape) != tuple(res.kp_yx.shape):
+            raise ValueError('%s: kp_sub must be float32 of the shape of kp_yx %s; got %s %s'
+                             % (entry, tuple(res.kp_yx.shape), sub.dtype, tuple(sub.shape)))
+        return getattr(h.lib, entry + '_f'), sub.contiguous()
+    return getattr(h.lib, entry), res.kp_yx.contiguous()
+
+
 def find_homography(res, reproj_threshold=3.0, max_iters=2000, seed=0):
     """Batched cv2.findHomography(optical_pts, thermal_pts, cv2.RANSAC, reproj_threshold) for the pairs of a PairResults
     (predict_align_image_pair.py:205-216).  NOT OpenCV's algorithm bit for bit: every pair evaluates `max_iters` 4-point
@@ -77,7 +89,9 @@ def find_homography(res, reproj_threshold=3.0, max_iters=2000, seed=0):
     mean corner distance differs by <= 0.11 px, the h_correctness decision (< 3 px) agrees on every pair, the inlier
     masks overlap by IoU >= 0.99 up to 50 % outliers (0.84 at 75 %: OpenCV's mask is the consensus set of its best
     4-point sample).  Returns (H [P,3,3] float64 mapping optical (x,y,1) to thermal -- all zeros
-    where the reference would get None --, inlier mask [P,K] uint8 per optical keypoint, n_inliers [P] int32)."""
+    where the reference would get None --, inlier mask [P,K] uint8 per optical keypoint, n_inliers [P] int32).
+    Results that carry sub-pixel keypoints (res.kp_sub, prediction.subpixel) are estimated from those (mp_find_homography_f);
+    so are refine_homography, refine_alignment's estimates and polish, pool_matches and estimate_shared_homography."""
     res.wait()
     dev = res.kp_yx.device
     P, K = res.num_pairs, res.kp_yx.shape[1]
@@ -85,10 +99,11 @@ def find_homography(res, reproj_threshold=3.0, max_iters=2000, seed=0):
     mask = torch.empty((P, K), dtype=torch.uint8, device=dev)
     nin = torch.empty((P,), dtype=torch.int32, device=dev)
     h = _lib.get_handle(dev)
+    entry, kp = _keypoints_for_estimate(res, h, 'mp_find_homography')
     with torch.cuda.device(dev):
-        h.check(h.lib.mp_find_homography(h.ptr, _lib.ptr(res.kp_yx.contiguous()), _lib.ptr(res.kp_count.contiguous()),
-                                         _lib.ptr(res.match_idx.contiguous()), P, K, float(reproj_threshold), int(max_iters),
-                                         int(seed), _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin), _lib.stream_ptr(dev)))
+        h.check(entry(h.ptr, _lib.ptr(kp), _lib.ptr(res.kp_count.contiguous()),
+                      _lib.ptr(res.match_idx.contiguous()), P, K, float(reproj_threshold), int(max_iters),
+                      int(seed), _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin), _lib.stream_ptr(dev)))
     return Hm, mask, nin
 
 
@@ -115,10 +130,11 @@ def refine_homography(res, H, reproj_threshold=3.0, iters=10):
     nin = torch.empty((P,), dtype=torch.int32, device=dev)
     cost = torch.empty((P, 2), dtype=torch.float64, device=dev)
     h = _lib.get_handle(dev)
+    entry, kp = _keypoints_for_estimate(res, h, 'mp_refine_homography')
     with torch.cuda.device(dev):
-        h.check(h.lib.mp_refine_homography(h.ptr, _lib.ptr(res.kp_yx.contiguous()), _lib.ptr(res.kp_count.contiguous()),
-                                           _lib.ptr(res.match_idx.contiguous()), P, K, float(reproj_threshold), iters,
-                                           _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin), _lib.ptr(cost), _lib.stream_ptr(dev)))
+        h.check(entry(h.ptr, _lib.ptr(kp), _lib.ptr(res.kp_count.contiguous()),
+                      _lib.ptr(res.match_idx.contiguous()), P, K, float(reproj_threshold), iters,
+                      _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin), _lib.ptr(cost), _lib.stream_ptr(dev)))
     return Hm, mask, nin, cost
 
 
@@ -129,7 +145,9 @@ def refine_alignment(res, reproj_threshold=3.0, radius=None, rounds=1, polish=Tr
       2. `rounds` times: guided_pairs under the current estimate (partners within `radius` pixels of where the estimate
          maps a keypoint; default 2 * reproj_threshold; `threshold` as for match_pairs), then find_homography on the new list;
       3. with `polish`, refine_homography.
-    A pair without a first estimate keeps its original matches and a zero matrix.  `res` is not modified.
+    A pair without a first estimate keeps its original matches and a zero matrix.  `res` is not modified.  With sub-pixel
+    keypoints on `res` (kp_sub) the estimates and the polish read them; the gate of the re-matching stays on the integer pixels
+    (it is several pixels wide).
     Returns (res2, H [P,3,3] float64, mask [P,K] uint8, n_inliers [P] int32); res2 is a new PairResults that shares the
     keypoints and descriptors of `res`, holds the final match list and has match_mode 'guided'."""
     from ..pipeline import PairResults
@@ -153,11 +171,12 @@ def refine_alignment(res, reproj_threshold=3.0, radius=None, rounds=1, polish=Tr
             mi = torch.where(none[:, None], res.match_idx, mi)
             md = torch.where(none[:, None], res.match_dist, md)
             mc = torch.where(none, res.match_count, mc)
-            cur = PairResults(res.kp_yx, res.kp_score, res.kp_count, res.desc, mi, md, mc, res.H, res.W, 'guided')
+            cur = PairResults(res.kp_yx, res.kp_score, res.kp_count, res.desc, mi, md, mc, res.H, res.W, 'guided',
+                              kp_sub=getattr(res, 'kp_sub', None))
             H, mask, nin = find_homography(cur, reproj_threshold, max_iters, seed)
     if cur is res:
         cur = PairResults(res.kp_yx, res.kp_score, res.kp_count, res.desc, res.match_idx, res.match_dist, res.match_count,
-                          res.H, res.W, 'guided')
+                          res.H, res.W, 'guided', kp_sub=getattr(res, 'kp_sub', None))
     if polish:
         H, mask, nin, _ = refine_homography(cur, H, reproj_threshold)
     return cur, H, mask, nin
@@ -168,7 +187,9 @@ MAX_RANSAC_MATCHES = 3200        # mp_find_homography keeps a pair's corresponde
 
 def find_homography_points(optical_pts, thermal_pts, reproj_threshold=3.0, max_iters=2000, seed=0, device=None):
     """cv2.findHomography(optical_pts, thermal_pts, cv2.RANSAC, reproj_threshold) for ONE set of corresponding (x, y)
-    points (integer pixel positions, as keypoints are).  Returns (H 3x3 float64 numpy or None, mask (N,) uint8)."""
+    points.  Integer input (pixel positions, as torch.nonzero's keypoints are) goes through mp_find_homography; floating
+    input (sub-pixel positions) is kept as float32 and goes through mp_find_homography_f, as cv2.findHomography takes float
+    points.  Returns (H 3x3 float64 numpy or None, mask (N,) uint8)."""
     from ..pipeline import PairResults
     a = np.asarray(optical_pts).reshape(-1, 2); b = np.asarray(thermal_pts).reshape(-1, 2)
     n = len(a)
@@ -180,8 +201,11 @@ def find_homography_points(optical_pts, thermal_pts, reproj_threshold=3.0, max_i
     dev = _lib.require_cuda(device)
     kp = torch.zeros((2, n, 2), dtype=torch.int32)
     kp[0] = torch.from_numpy(np.ascontiguousarray(a[:, ::-1]).astype(np.int32)); kp[1] = torch.from_numpy(np.ascontiguousarray(b[:, ::-1]).astype(np.int32))
+    sub = None
+    if a.dtype.kind == 'f' or b.dtype.kind == 'f':
+        sub = torch.from_numpy(np.stack([a[:, ::-1], b[:, ::-1]]).astype(np.float32)).to(dev)
     res = PairResults(kp.to(dev), None, torch.tensor([n, n], dtype=torch.int32, device=dev), None,
-                      torch.arange(n, dtype=torch.int32, device=dev).reshape(1, n), None, None, 0, 0)
+                      torch.arange(n, dtype=torch.int32, device=dev).reshape(1, n), None, None, 0, 0, kp_sub=sub)
     Hm, mask, nin = find_homography(res, reproj_threshold, max_iters, seed)
     if int(nin[0]) < 4:
         return None, np.zeros(n, np.uint8)
@@ -250,11 +274,12 @@ def pool_matches(res, groups=None):
     go = torch.empty((G + 1,), dtype=torch.int32, device=dev)
     gdev = torch.from_numpy(gid).to(dev) if gid is not None else None
     h = _lib.get_handle(dev)
+    entry, kp = _keypoints_for_estimate(res, h, 'mp_pool_matches')
     with torch.cuda.device(dev):
         ws = _pooled_workspace(h, P, G, 1, dev)
-        h.check(h.lib.mp_pool_matches(h.ptr, _lib.ptr(res.kp_yx.contiguous()), _lib.ptr(res.kp_count.contiguous()),
-                                      _lib.ptr(res.match_idx.contiguous()), _lib.ptr(gdev), P, K, G, _lib.ptr(pts), _lib.ptr(qidx),
-                                      P * K, _lib.ptr(po), _lib.ptr(go), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        h.check(entry(h.ptr, _lib.ptr(kp), _lib.ptr(res.kp_count.contiguous()),
+                      _lib.ptr(res.match_idx.contiguous()), _lib.ptr(gdev), P, K, G, _lib.ptr(pts), _lib.ptr(qidx),
+                      P * K, _lib.ptr(po), _lib.ptr(go), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
     n = int(po[P])
     return PooledMatches(pts[:n], qidx[:n], po, go)
 
@@ -391,7 +416,10 @@ def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoi
     every batch's mutual matches additionally go through refine_alignment (guided re-matching under the first estimate,
     then the Levenberg-Marquardt polish) and the result gains pts_dist_refined / average_h_error_refined /
     h_correctness_refined (as their unrefined namesakes, from the refined estimate) and n_matches_refined (matches per
-    pair after re-matching).  Every other key keeps its value; without enable there is no new key."""
+    pair after re-matching).  Every other key keeps its value; without enable there is no new key.
+    Extension: config['subpixel'] = {enable: false}.  With enable: true the pipeline refines its keypoint lists and samples the
+    descriptors at the refined positions, and every homography estimate here reads the sub-pixel positions; the keypoint
+    metrics (mp_pair_metrics) stay on the integer pixels, the reference's definitions."""
     from ..pipeline import PairPipeline, PairResults
     from .utils import data_to_device
     from .matching import get_matches, match_pairs, nearest_pairs
@@ -433,7 +461,7 @@ def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoi
             else:
                 mm = nearest_pairs(res.desc, res.kp_count, res.desc[1:], res.kp_count[1:], sel.match_ratio or None, **lay)
             est = PairResults(res.kp_yx, res.kp_score, res.kp_count, res.desc, mm[0], mm[1], mm[2], res.H, res.W,
-                              sel.match_mode)
+                              sel.match_mode, kp_sub=res.kp_sub)
         if est is not None:
             h_est, _, n_in = find_homography(est, config.get('reprojection_threshold', 3))
             h_est = h_est.cpu().numpy(); n_in = n_in.cpu().numpy()
@@ -441,7 +469,7 @@ def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoi
             # one-to-many matchers (thresholdmatcher) and lists longer than one RANSAC launch holds: per pair through
             # get_matches (GPU), like the reference
             h_est = np.zeros((B, 3, 3)); n_in = np.zeros(B, dtype=np.int64)
-            kp_all = res.kp_yx.cpu().numpy(); cnt_all = res.kp_count.cpu().numpy()
+            kp_all = (res.kp_yx if res.kp_sub is None else res.kp_sub).cpu().numpy(); cnt_all = res.kp_count.cpu().numpy()
             Kc = kp_all.shape[1]
             for p in range(B):
                 no, nt = min(int(cnt_all[2 * p]), Kc), min(int(cnt_all[2 * p + 1]), Kc)

@@ -9,7 +9,7 @@ import torch
 from .. import _lib
 
 __all__ = ['dict_update', 'data_to_device', 'data_unsqueeze', 'fix_model_weigth_keys', 'depth_to_space',
-           'space_to_depth', 'box_nms', 'detect_keypoints', 'extract_keypoints', 'nms_unresolved',
+           'space_to_depth', 'box_nms', 'detect_keypoints', 'extract_keypoints', 'refine_keypoints', 'nms_unresolved',
            'interpolate_descriptors', 'interpolate_descriptors_batched', 'topk_ambiguous', 'topk_tie_guard', 'nms_tie_guard',
            'tie_robust_redo', 'box_nms_tie_robust']
 
@@ -211,6 +211,30 @@ def extract_keypoints(prob, thr, capacity=None, valid_mask=None):
     return kp, sc, cnt
 
 
+def refine_keypoints(prob, kp_yx, kp_count):
+    """Sub-pixel positions of the entries of a keypoint list (mp_refine_keypoints; an extension): per axis the vertex of the
+    parabola through the logarithms of the detector map at the keypoint and its two neighbours, where that is a maximum
+    (include/multipoint_hip.h states the rule); an axis that is not refined keeps its integer exactly.
+    prob (H,W) or (B,1,H,W): the FORWARD's map, not the NMS output (its suppressed neighbours are zero); kp_yx [B,K,2] int32 and
+    kp_count [B] int32 as detect_keypoints / extract_keypoints return them.  Returns float32 [B,K,2] (y, x) on the GPU, rows
+    beyond kp_count[b] zero."""
+    p, _, dev, B, H, W = _prep_prob(prob, None)
+    kp = kp_yx.to(dev, torch.int32).contiguous()
+    cnt = kp_count.to(dev, torch.int32).contiguous()
+    if kp.dim() != 3 or kp.shape[0] != B or kp.shape[2] != 2 or cnt.shape != (B,):
+        raise ValueError('refine_keypoints: need kp_yx [B,K,2] and kp_count [B] for the %d map(s); got %s and %s'
+                         % (B, tuple(kp_yx.shape), tuple(kp_count.shape)))
+    K = kp.shape[1]
+    out = torch.empty((B, K, 2), dtype=torch.float32, device=dev)
+    if K == 0:
+        return out
+    h = _lib.get_handle(dev)
+    with torch.cuda.device(dev):
+        h.check(h.lib.mp_refine_keypoints(h.ptr, _lib.ptr(p), B, H, W, _lib.ptr(kp), _lib.ptr(cnt), K, _lib.ptr(out),
+                                          _lib.stream_ptr(dev)))
+    return out
+
+
 def _channels_last_desc(desc):
     """(B,D,Hc,Wc) logical -> contiguous (B,Hc,Wc,D) storage without a copy when the tensor already
     is the channels-last view produced by MultiPoint.forward."""
@@ -220,31 +244,35 @@ def _channels_last_desc(desc):
 
 def interpolate_descriptors_batched(kp_yx, kp_count, desc, H, W):
     """kp_yx [B,K,2] int32, kp_count [B] int32, desc (B,D,Hc,Wc) -> [B,K,D] unit rows (rows beyond
-    kp_count[b] are zero)."""
+    kp_count[b] are zero).  A floating-dtype kp_yx (sub-pixel positions, refine_keypoints) is sampled at its fractions
+    (mp_sample_descriptors_f), as the reference's keypoints.float() is; whole numbers give the bits of the int32 path."""
     dev = kp_yx.device
     d = _channels_last_desc(desc.to(dev, torch.float32))
     B, Hc, Wc, D = d.shape
     K = kp_yx.shape[1]
     out = torch.empty((B, K, D), dtype=torch.float32, device=dev)        # (the kernel writes the zero rows too)
     h = _lib.get_handle(dev)
+    if kp_yx.dtype.is_floating_point:
+        entry, kp = h.lib.mp_sample_descriptors_f, kp_yx.to(torch.float32).contiguous()
+    else:
+        entry, kp = h.lib.mp_sample_descriptors, kp_yx.contiguous()
     with torch.cuda.device(dev):
-        h.check(h.lib.mp_sample_descriptors(h.ptr, _lib.ptr(d), B, Hc, Wc, D, int(H), int(W),
-                                            _lib.ptr(kp_yx.contiguous()), _lib.ptr(kp_count.contiguous()),
-                                            K, _lib.ptr(out), _lib.stream_ptr(dev)))
+        h.check(entry(h.ptr, _lib.ptr(d), B, Hc, Wc, D, int(H), int(W), _lib.ptr(kp), _lib.ptr(kp_count.contiguous()),
+                      K, _lib.ptr(out), _lib.stream_ptr(dev)))
     return out
 
 
 def interpolate_descriptors(keypoints, descriptors_lowres, H, W):
     """multipoint/utils/utils.py:159-167: bilinear sampling (grid_sample, align_corners=True) of the
     coarse descriptor map at the keypoints followed by L2 normalisation.
-    keypoints (N,2) (y,x) integer tensor; descriptors_lowres (D,Hc,Wc); returns (N,D).
-    The input keypoints are not modified."""
+    keypoints (N,2) (y,x), an integer tensor or -- as the reference's keypoints.float() admits -- a floating one, which is
+    sampled at its fractions; descriptors_lowres (D,Hc,Wc); returns (N,D).  The input keypoints are not modified."""
     dev = descriptors_lowres.device if descriptors_lowres.device.type == 'cuda' else _lib.require_cuda(None)
     N = keypoints.shape[0]
     D = descriptors_lowres.shape[0]
     if N == 0:
         return torch.zeros((0, D), dtype=torch.float32, device=descriptors_lowres.device)
-    kp = keypoints.to(dev, torch.int32).reshape(1, N, 2).contiguous()
+    kp = keypoints.to(dev, torch.float32 if keypoints.dtype.is_floating_point else torch.int32).reshape(1, N, 2).contiguous()
     cnt = torch.full((1,), N, dtype=torch.int32, device=dev)
     out = interpolate_descriptors_batched(kp, cnt, descriptors_lowres.unsqueeze(0), H, W)
     return out[0].to(descriptors_lowres.device)

@@ -42,6 +42,9 @@ def build_parser():
     parser.add_argument('--save-npz', default=None, help='(extension) write keypoints/descriptors/matches of the sample here')
     parser.add_argument('--refine', action='store_true', help='(extension) re-match under the first homography estimate and '
                         'polish it (utils.refine_alignment); the aligned image uses the refined estimate')
+    parser.add_argument('--subpixel', action='store_true', help='(extension) refine the keypoints to sub-pixel positions on the '
+                        'detector map (utils.refine_keypoints): descriptors are sampled and the homography is estimated at them; '
+                        'with -e the same as prediction.subpixel.enable')
     parser.add_argument('--mi', action='store_true', help='(extension) print the negative normalised mutual information at 100 bins of '
                         'the pair under the identity, the estimated and (with --refine) the refined homography')
     parser.add_argument('--mi-refine', action='store_true', help='(extension) maximise the mutual information from the estimated '
@@ -95,9 +98,11 @@ def select_device(config):
     return torch.device('cuda:0')
 
 
-def refine_estimate(kp_optical, kp_thermal, desc_optical, desc_thermal, matches, mask, H, W, pred, H_est):
+def refine_estimate(kp_optical, kp_thermal, desc_optical, desc_thermal, matches, mask, H, W, pred, H_est, sub_optical=None,
+                    sub_thermal=None):
     """--refine: the sample's lists as a one-pair PairResults through utils.refine_alignment.  Prints inliers / matches
-    before and after and returns the refined estimate (the first one where there is nothing to refine)."""
+    before and after and returns the refined estimate (the first one where there is nothing to refine).  sub_*: the
+    sub-pixel positions of --subpixel, which the estimates and the polish then read."""
     from multipoint_amd.pipeline import PairResults
     no, nt = kp_optical.shape[0], kp_thermal.shape[0]
     D = desc_optical.shape[1] if no else desc_thermal.shape[1] if nt else 0
@@ -120,8 +125,12 @@ def refine_estimate(kp_optical, kp_thermal, desc_optical, desc_thermal, matches,
     mdist = torch.zeros((1, K), dtype=torch.float32)
     for m in matches:
         midx[0, m.queryIdx] = m.trainIdx; mdist[0, m.queryIdx] = m.distance
+    kp_sub = None
+    if sub_optical is not None and sub_thermal is not None:
+        kp_sub = torch.zeros((2, K, 2), dtype=torch.float32, device=dev)
+        kp_sub[0, :no] = sub_optical; kp_sub[1, :nt] = sub_thermal
     res = PairResults(kp, None, torch.tensor([no, nt], dtype=torch.int32, device=dev), desc, midx.to(dev), mdist.to(dev),
-                      torch.tensor([len(matches)], dtype=torch.int32, device=dev), H, W)
+                      torch.tensor([len(matches)], dtype=torch.int32, device=dev), H, W, kp_sub=kp_sub)
     res2, H_ref, _, n_in = utils.refine_alignment(res, pred['reprojection_threshold'],
                                                   threshold=pred['matching']['method_kwargs'].get('threshold', -1.0)
                                                   if pred['matching']['method'] == 'nnmatcher' else -1.0)
@@ -205,6 +214,12 @@ def main(argv=None):
                                                  shuffle=False, num_workers=datasets.loader_num_workers(dataset, config['prediction']['num_worker']))
     net = load_network(config, args.model_dir, args.version, device, args.seed)
     pred = config['prediction']
+    if args.subpixel:
+        pred['subpixel'] = dict(pred.get('subpixel') or {}, enable=True)
+    subpixel = bool((pred.get('subpixel') or {}).get('enable', False))
+    if subpixel and hasattr(net, 'describe'):
+        raise ValueError('subpixel: ClassicDetectors models have no sub-pixel keypoints (LGHD descriptors are patch histograms '
+                         'at integer centres)')
 
     with torch.no_grad():
         if args.evaluation:
@@ -240,6 +255,9 @@ def main(argv=None):
         synchronize()
         t_2 = time.time()
 
+        # the forward's maps: what the sub-pixel fit reads (the NMS output has zeros around every keypoint); an image the tie
+        # guard redoes is redone in place, so these are the maps the keypoints come from
+        prob_optical, prob_thermal = out_optical['prob'], out_thermal['prob']
         if pred['nms'] > 0:
             # (box_nms with the top-k tie guard: an image whose top-k cut falls inside a plateau of tied scores is re-evaluated
             # with the tie-exact convolution algorithm, so the kept indices follow the reference's exact score order)
@@ -263,8 +281,16 @@ def main(argv=None):
             thr = pred['detection_threshold']
             pred_optical = torch.nonzero((out_optical['prob'][0].squeeze() > thr).float())
             pred_thermal = torch.nonzero((out_thermal['prob'][0].squeeze() > thr).float())
-            desc_optical = utils.interpolate_descriptors(pred_optical, out_optical['desc'][0], H, W)
-            desc_thermal = utils.interpolate_descriptors(pred_thermal, out_thermal['desc'][0], H, W)
+            sub_optical = sub_thermal = None
+            if subpixel:
+                def refine(prob, kp):
+                    cnt = torch.tensor([kp.shape[0]], dtype=torch.int32, device=kp.device)
+                    return utils.refine_keypoints(prob[:1], kp.to(torch.int32).reshape(1, -1, 2), cnt)[0]
+                sub_optical, sub_thermal = refine(prob_optical, pred_optical), refine(prob_thermal, pred_thermal)
+            desc_optical = utils.interpolate_descriptors(pred_optical if sub_optical is None else sub_optical,
+                                                         out_optical['desc'][0], H, W)
+            desc_thermal = utils.interpolate_descriptors(pred_thermal if sub_thermal is None else sub_thermal,
+                                                         out_thermal['desc'][0], H, W)
             matches = utils.get_matches(desc_optical.cpu().numpy(), desc_thermal.cpu().numpy(),
                                         pred['matching']['method'], pred['matching']['knn_matches'],
                                         **pred['matching']['method_kwargs'])
@@ -278,8 +304,11 @@ def main(argv=None):
             print('--------------------------------------------------------')
             # align the images: homography from the matches (reference :209-216) next to the ground truth (:252-257)
             kpo = pred_optical.cpu().numpy(); kpt = pred_thermal.cpu().numpy()
-            optical_pts = np.array([kpo[m.queryIdx][::-1] for m in matches]).reshape(-1, 2)
-            thermal_pts = np.array([kpt[m.trainIdx][::-1] for m in matches]).reshape(-1, 2)
+            # (with --subpixel the estimate reads the refined positions: float points, as cv2.findHomography takes them)
+            kpo_est = kpo if sub_optical is None else sub_optical.cpu().numpy()
+            kpt_est = kpt if sub_thermal is None else sub_thermal.cpu().numpy()
+            optical_pts = np.array([kpo_est[m.queryIdx][::-1] for m in matches]).reshape(-1, 2)
+            thermal_pts = np.array([kpt_est[m.trainIdx][::-1] for m in matches]).reshape(-1, 2)
             H_est, mask = utils.find_homography_points(optical_pts, thermal_pts, pred['reprojection_threshold'], device=device)
             if H_est is None:
                 H_est = np.eye(3, 3)
@@ -292,7 +321,7 @@ def main(argv=None):
             H_first = H_est
             if args.refine:
                 H_est = refine_estimate(pred_optical, pred_thermal, desc_optical, desc_thermal, matches, mask, H, W, pred,
-                                        H_est)
+                                        H_est, sub_optical, sub_thermal)
             if args.mi:
                 mi_report(data['optical']['image'][:1], data['thermal']['image'][:1],
                           [('identity', np.eye(3)), ('estimated', H_first)] + ([('refined', H_est)] if args.refine else []))
@@ -318,7 +347,9 @@ def main(argv=None):
                                     match_train=np.array([m.trainIdx for m in matches]),
                                     match_distance=np.array([m.distance for m in matches], dtype=np.float32),
                                     homography_estimated=H_est, homography_ground_truth=H_gt,
-                                    warped_optical=warped_image[0, 0].cpu().numpy())
+                                    warped_optical=warped_image[0, 0].cpu().numpy(),
+                                    **({'kp_optical_sub': kpo_est.astype(np.float32), 'kp_thermal_sub': kpt_est.astype(np.float32)}
+                                       if subpixel else {}))
             if args.plot and args.plot_dir:
                 # under the final estimate: the refined one with --refine, the MI-aligned one with --mi-refine
                 names = write_plots(args.plot_dir, data['optical']['image'][:1], data['thermal']['image'][:1], kpo, kpt, matches,
