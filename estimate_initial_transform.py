@@ -20,6 +20,11 @@ Written next to the pairs (or to -o and its directory):
 An existing yaml is not overwritten without --force: it may be a hand measurement.  When fewer than 4 inliers support the
 model, nothing is written and the exit status is 1.
 
+--transform similarity | affine estimates that model instead (multipoint_amd.utils.find_transform_pooled and
+refine_transform_pooled; fewest inliers 3 | 4).  The yaml stays a 3x3 `perspective` that align_images.py reads as it is (its
+last row is then (0, 0, 1)); the report gains `transform` and, for a similarity, `similarity`: the angle, scale, dx and dy of
+the optical -> thermal estimate in the convention of multipoint_amd.utils.decompose_similarity.
+
 Not known: how well this works on real thermal / optical recordings -- no such data and no trained weights are in this
 repository; everything is verified on synthetic and planted data.  Look at the report (and at check_alignment.py's pictures)
 before trusting the file."""
@@ -49,6 +54,9 @@ def build_parser():
     parser.add_argument('--max-iters', default=2000, type=int, help='RANSAC hypotheses')
     parser.add_argument('--subpixel', action='store_true', help='Refine the keypoints to sub-pixel positions on the detector map '
                         '(prediction.subpixel.enable): the pooled matches then hold float positions')
+    parser.add_argument('--transform', default='homography', choices=['homography', 'similarity', 'affine'],
+                        help='Motion model of the estimate: the 8-parameter homography, a similarity (rotation, scale, two translations: '
+                        'what a rigid rig is close to, and what few inliers still determine) or an affine transform')
     parser.add_argument('--force', action='store_true', help='Overwrite an existing yaml file (it may be hand-measured)')
     return parser
 
@@ -76,14 +84,15 @@ def perspective_from_estimate(H):
     return T / T[2, 2]
 
 
-def build_report(names_read, names_used, pair_offsets, mask, n_inliers, cost):
-    """The report's fields from the estimator's result: mask [N] per pooled match, pair_offsets [P+1] the rows of every used pair."""
+def build_report(names_read, names_used, pair_offsets, mask, n_inliers, cost, transform='homography', H=None):
+    """The report's fields from the estimator's result: mask [N] per pooled match, pair_offsets [P+1] the rows of every used pair.
+    With another `transform` than the homography the report names it, and for a similarity holds the decomposed estimate H."""
     mask = np.asarray(mask).reshape(-1) != 0
     po = np.asarray(pair_offsets).reshape(-1)
     if len(po) != len(names_used) + 1 or int(po[-1]) != len(mask):
         raise ValueError('build_report: %d pairs, %d offsets, %d matches' % (len(names_used), len(po), len(mask)))
     per_pair = {n: int(mask[int(po[p]):int(po[p + 1])].sum()) for p, n in enumerate(names_used)}
-    return {
+    report = {
         'pairs_read': len(names_read),
         'pairs_used': len(names_used),
         'matches_pooled': int(len(mask)),
@@ -93,6 +102,12 @@ def build_report(names_read, names_used, pair_offsets, mask, n_inliers, cost):
         'inliers_per_pair': per_pair,
         'pairs_with_4_inliers': int(sum(v >= 4 for v in per_pair.values())),
     }
+    if transform != 'homography':
+        report['transform'] = transform
+        if transform == 'similarity' and H is not None and np.asarray(H).any():
+            from multipoint_amd.utils import decompose_similarity
+            report['similarity'] = dict(zip(('angle', 'scale', 'dx', 'dy'), decompose_similarity(H)))
+    return report
 
 
 def estimate_on_gpu(args, config, names):
@@ -127,12 +142,17 @@ def estimate_on_gpu(args, config, names):
             counts.extend(int(c) for c in po[1:] - po[:-1])
     pair_offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
     n = int(pair_offsets[-1])
-    if n < 4:
+    model = getattr(args, 'transform', 'homography')
+    if n < utils.TRANSFORM_MIN_POINTS[model]:
         return np.zeros((3, 3)), np.zeros(n, np.uint8), pair_offsets, 0, None
     allp = utils.PooledMatches(torch.cat(pts).contiguous(), None, None, torch.tensor([0, n], dtype=torch.int32, device=device))
     thr = float(pred.get('reprojection_threshold', 3))
-    H0, _, _ = utils.find_homography_pooled(allp, thr, max_iters=args.max_iters, seed=args.seed)
-    H, mask, nin, cost = utils.refine_homography_pooled(allp, H0, thr)
+    if model == 'homography':
+        H0, _, _ = utils.find_homography_pooled(allp, thr, max_iters=args.max_iters, seed=args.seed)
+        H, mask, nin, cost = utils.refine_homography_pooled(allp, H0, thr)
+    else:
+        H0, _, _ = utils.find_transform_pooled(allp, model, thr, max_iters=args.max_iters, seed=args.seed)
+        H, mask, nin, cost = utils.refine_transform_pooled(allp, H0, model, thr)
     cost = cost[0].cpu().numpy()
     return H[0].cpu().numpy(), mask.cpu().numpy(), pair_offsets, int(nin[0]), (float(cost[0]), float(cost[1]))
 
@@ -158,14 +178,19 @@ def main(argv=None, estimator=estimate_on_gpu):
         return 1
     print('Using {} of {} pairs'.format(len(names), len(names_read)))
     H, mask, pair_offsets, n_inliers, cost = estimator(args, config, names)
-    report = build_report(names_read, names, pair_offsets, mask, n_inliers, cost)
+    from multipoint_amd.utils import transform_min_inliers
+    min_inliers = transform_min_inliers(args.transform)
+    report = build_report(names_read, names, pair_offsets, mask, n_inliers, cost, args.transform, H)
     print('Matches pooled: {}  inliers: {}  pairs with at least 4 inliers: {} of {}'.format(
         report['matches_pooled'], report['inliers'], report['pairs_with_4_inliers'], report['pairs_used']))
-    if n_inliers < 4:
-        print('fewer than 4 inliers support a model: nothing written', file=sys.stderr)
+    if n_inliers < min_inliers:
+        print('fewer than %d inliers support a model: nothing written' % min_inliers, file=sys.stderr)
         return 1
     T = perspective_from_estimate(H)
-    print('Estimated Homography (optical -> thermal):')
+    if 'similarity' in report:
+        print('Similarity: angle {angle:.6f} rad  scale {scale:.6f}  dx {dx:.3f}  dy {dy:.3f}'.format(**report['similarity']))
+    print('Estimated Homography (optical -> thermal):' if args.transform == 'homography' else
+          'Estimated %s transform (optical -> thermal):' % args.transform)
     print(np.asarray(H))
     print('perspective (thermal -> optical):')
     print(T)

@@ -379,6 +379,50 @@ int mp_refine_homography_pooled(mp_handle* h, const float* pts, const int* group
                                 double reproj_threshold, int iters, double* homography, unsigned char* inlier_mask, int* n_inliers,
                                 double* cost /* [G][2] or NULL */, void* stream);
 
+/* ---- similarity and affine models on the same three routes (an extension; the reference's manual alignment estimates its
+ * initial transform both ways, cv2.estimateRigidTransform(ir, opt, False) next to cv2.findHomography,
+ * create_dataset/helper_functions/align.py).  A rig's optical -> thermal transform is close to a similarity, and a pair with
+ * 6-10 correct matches among dozens of wrong ones determines 4 or 6 parameters where it does not determine 8.  Not OpenCV's
+ * estimateAffinePartial2D / estimateAffine2D bit for bit; no adaptive iteration bound.
+ *   MP_MODEL_HOMOGRAPHY  the entry forwards to its *_homography* counterpart (`rounds` as `iters`): the same bits
+ *   MP_MODEL_SIMILARITY  [[a, -b, tx], [b, a, ty], [0, 0, 1]]; a hypothesis from 2 distinct matches in closed form (refused
+ *                        when they lie closer than 1e-5 px: |d|^2 < 1e-10)
+ *   MP_MODEL_AFFINE      [[a, b, tx], [c, d, ty], [0, 0, 1]]; a hypothesis from 3 matches by 3x3 elimination with partial
+ *                        pivoting (refused when a pivot is below 1e-10: collinear points)
+ * Arguments, lists, limits, sampling (sample4's counter scheme on S = 2 / 3 indices), tie-break and determinism are those of the
+ * counterparts; the test is forward error^2 <= reproj_threshold^2 (no division).  The refit over the winner's consensus set
+ * is the exact least-squares minimiser of the summed squared forward error (closed form on centred points / 3x3 normal
+ * equations on centred source points); a winner with fewer than S + 1 inliers -- a model that explains only its own sample --
+ * gives a zero matrix, zero count and zero mask.
+ * mp_refine_transform* is local optimisation in the place of the Levenberg-Marquardt polish, which the exact refit makes
+ * unnecessary: at most `rounds` (0..1000) times { mark the inliers of the current model, refit over them }, ended early by a
+ * marking that changes nothing.  In: the estimate (top two rows divided by h22; the last row is taken as (0, 0, h22)).  Out: the
+ * last model, inlier_mask / n_inliers of the last set marked (the set that model was fitted to; the input's own for rounds =
+ * 0), cost [.][2] or NULL: the summed squared error over that set under the model before / after the last refit
+ * (after <= before).  All outputs are zero for an estimate that is all zeros, not finite or has h22 = 0, and when a marked
+ * set has fewer than S + 1 members. */
+#define MP_MODEL_HOMOGRAPHY 0
+#define MP_MODEL_SIMILARITY 1
+#define MP_MODEL_AFFINE 2
+int mp_find_transform(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K, int model,
+                      double reproj_threshold, int max_iters, unsigned long long seed, double* transform,
+                      unsigned char* inlier_mask, int* n_inliers, void* stream);
+int mp_find_transform_f(mp_handle* h, const float* kp_sub_yx, const int* kp_count, const int* match_idx, int P, int K, int model,
+                        double reproj_threshold, int max_iters, unsigned long long seed, double* transform,
+                        unsigned char* inlier_mask, int* n_inliers, void* stream);
+int mp_refine_transform(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K, int model,
+                        double reproj_threshold, int rounds, double* transform, unsigned char* inlier_mask, int* n_inliers,
+                        double* cost /* [P][2] or NULL */, void* stream);
+int mp_refine_transform_f(mp_handle* h, const float* kp_sub_yx, const int* kp_count, const int* match_idx, int P, int K, int model,
+                          double reproj_threshold, int rounds, double* transform, unsigned char* inlier_mask, int* n_inliers,
+                          double* cost /* [P][2] or NULL */, void* stream);
+int mp_find_transform_pooled(mp_handle* h, const float* pts, const int* group_offsets, long long N, int G, int model,
+                             double reproj_threshold, int max_iters, unsigned long long seed, double* transform,
+                             unsigned char* inlier_mask, int* n_inliers, void* workspace, long long workspace_bytes, void* stream);
+int mp_refine_transform_pooled(mp_handle* h, const float* pts, const int* group_offsets, long long N, int G, int model,
+                               double reproj_threshold, int rounds, double* transform, unsigned char* inlier_mask, int* n_inliers,
+                               double* cost /* [G][2] or NULL */, void* stream);
+
 /* ---- single-image detector metrics: multipoint/utils/evaluation.py:10-97 (predict_keypoints.py:88-104) ----
  * mp_detector_metrics replaces compute_tp_fp_dist (evaluation.py:56-97) for B heat maps at once:
  *   prob          fp32 [B][H][W]  detector map after valid mask / NMS (evaluation.py:19-25)

@@ -136,6 +136,18 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
     'mp_refine_homography_pooled': (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_int, ctypes.c_double, c_int, c_void_p, c_void_p,
                                             c_void_p, c_void_p, c_void_p]),
+    'mp_find_transform': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_int,
+                                  ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'mp_find_transform_f': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_int,
+                                    ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'mp_refine_transform': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'mp_refine_transform_f': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'mp_find_transform_pooled': (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int, ctypes.c_double, c_int,
+                                         ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
+    'mp_refine_transform_pooled': (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int, ctypes.c_double, c_int, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p]),
     'mp_detector_metrics': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'mp_warp_perspective': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,

@@ -8,8 +8,8 @@
 //   best = most inliers (lowest hypothesis index on ties), final model = normalised DLT over the best inlier set.
 // One thread per hypothesis (the matches of the pair sit in LDS); the winner is picked with a 64-bit atomicMax.
 // OpenCV's last step, the Levenberg-Marquardt polish of the refitted model, is a launch of its own (refine_kernel).
-// This file locates a pair's matches (gather: ordered compaction into LDS) and hands them out as a PairView; the refit and the
-// polish are the kernel templates of mp_homography.h, which homography_pooled.hip runs on a group's rows in global memory.
+// A pair's matches are located by gather (ordered compaction into LDS) and handed out as a PairView by PairSource; these, the
+// refit and the polish are the templates of mp_homography.h, which homography_pooled.hip runs on a group's rows in global memory.
 // The kernels and launchers are templates on the keypoint type KP -- int pixels, or float sub-pixel positions
 // (mp_refine_keypoints) -- which only decides what gather reads.  A translation unit instantiates them for ONE type,
 // MP_HOMOGRAPHY_KP: int here, float in homography_f.hip, which includes this file.  Two instantiations side by side change what
@@ -24,18 +24,6 @@
 #endif
 
 namespace {
-
-// gather the matched (x,y)->(u,v) pairs of pair p into LDS in query order; returns their number
-// pts: [n][4] floats in LDS order x, y, u, v; qidx (may be NULL): [n] the query index of each match
-template <class KP>
-__device__ int gather(const KP* kp_yx, const int* kp_count, const int* match_idx, int p, int K, float* pts, int* qidx)
-{
-    return compact_matches(kp_count, match_idx, p, K, [&](int pos, int i, int j) {
-        const float4 q = match_point(kp_yx, p, K, i, j);
-        pts[pos * 4 + 0] = q.x; pts[pos * 4 + 1] = q.y; pts[pos * 4 + 2] = q.z; pts[pos * 4 + 3] = q.w;
-        if (qidx) qidx[pos] = i;
-    });
-}
 
 template <class KP>
 __global__ __launch_bounds__(256) void ransac_kernel(const KP* __restrict__ kp_yx, const int* __restrict__ kp_count,
@@ -56,25 +44,6 @@ __global__ __launch_bounds__(256) void ransac_kernel(const KP* __restrict__ kp_y
     // most inliers, then the LOWEST hypothesis index
     atomicMax(&best[p], ((unsigned long long)cnt << 32) | (unsigned long long)(0x7fffffff - t));
 }
-
-// what refit_kernel / refine_kernel (mp_homography.h) are launched with: the view of pair p is its gathered list in LDS
-// (dynamic LDS: [K][4] floats, then [K] ints) and its row of the mask.  KP: the keypoint type (int pixels or float sub-pixel
-// positions); it only decides what gather reads
-template <class KP>
-struct PairSource {
-    const KP* kp_yx;
-    const int* kp_count;
-    const int* match_idx;
-    int K;
-    unsigned char* mask;
-    __device__ PairView view(int p) const
-    {
-        extern __shared__ float pts[];
-        int* qidx = reinterpret_cast<int*>(pts + (size_t)K * 4);
-        const int n = gather(kp_yx, kp_count, match_idx, p, K, pts, qidx);
-        return PairView{pts, qidx, mask + (size_t)p * K, n};
-    }
-};
 
 }  // namespace
 

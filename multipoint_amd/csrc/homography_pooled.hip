@@ -100,14 +100,6 @@ __global__ __launch_bounds__(256) void pool_write_kernel(const KP* __restrict__ 
     });
 }
 
-// the rows [start, start + n) of group g, clamped to [0, N] (the offsets are device data: nothing they hold may lead outside pts)
-__device__ __forceinline__ int group_range(const int* group_offsets, int g, int N, int& start)
-{
-    const int a = min(max(group_offsets[g], 0), N), b = min(max(group_offsets[g + 1], 0), N);
-    start = a;
-    return max(b - a, 0);
-}
-
 // grid (hypothesis blocks, point splits, groups).  Block (bx, s, g) scores hypotheses bx * 256 .. + 255 of group g on the
 // chunks s, s + splits, ... of its points and adds the counts to counts[g][t].  A thread without a hypothesis (t >= T, or a
 // singular sample) still takes part in every staging barrier: the only early exits are the same for the whole workgroup.
@@ -163,20 +155,6 @@ __global__ __launch_bounds__(256) void pooled_select_kernel(const unsigned int* 
     }
 }
 
-// what refit_kernel / refine_kernel (mp_homography.h) are launched with: the view of group g is its range of pts and mask
-struct PooledSource {
-    const float4* pts;
-    const int* group_offsets;
-    int N;
-    unsigned char* mask;
-    __device__ PooledView view(int g) const
-    {
-        int start;
-        const int n = group_range(group_offsets, g, N, start);
-        return PooledView{pts + start, mask + start, n};
-    }
-};
-
 }  // namespace
 
 template <class KP>
@@ -206,6 +184,12 @@ void launch_find_homography_pooled(const float* pts, const int* group_offsets, i
     hipLaunchKernelGGL(pooled_select_kernel, dim3(G), dim3(256), 0, s, counts, T, best);
     hipLaunchKernelGGL(refit_kernel<PooledSource>, dim3(G), dim3(256), 0, s, PooledSource{p4, group_offsets, N, mask}, thr, seed, best,
                        H_out, n_inliers);
+}
+
+// the winner selection on its own, for the other motion models' pooled route (transform_pooled.hip): counts is model-free
+void launch_pooled_select(const unsigned int* counts, int T, int G, unsigned long long* best, hipStream_t s)
+{
+    hipLaunchKernelGGL(pooled_select_kernel, dim3(G), dim3(256), 0, s, counts, T, best);
 }
 
 void launch_refine_homography_pooled(const float* pts, const int* group_offsets, int N, int G, double thr, int iters, double* H_io,

@@ -417,6 +417,25 @@ void launch_find_homography_pooled(const float* pts, const int* group_offsets, i
 void launch_refine_homography_pooled(const float* pts, const int* group_offsets, int N, int G, double thr, int iters, double* H_io,
                                      unsigned char* mask, int* n_inliers, double* cost, hipStream_t s);
 
+// best [G] = the winning (count << 32) | (0x7fffffff - t) of counts [G][T] (the selection step of the pooled estimators)
+void launch_pooled_select(const unsigned int* counts, int T, int G, unsigned long long* best, hipStream_t s);
+
+// similarity / affine estimation (transform.hip, transform_f.hip, transform_pooled.hip): the homography launchers' arguments
+// and buffers plus `model`, MP_MODEL_SIMILARITY or MP_MODEL_AFFINE (the C entries forward MP_MODEL_HOMOGRAPHY to the
+// launchers above); `rounds` of local optimisation in the place of the polish's `iters`
+template <class KP>
+void launch_find_transform(int model, const KP* kp_yx, const int* kp_count, const int* match_idx, int P, int K, int T, double thr,
+                           unsigned long long seed, unsigned long long* best, double* H_out, unsigned char* mask, int* n_inliers,
+                           hipStream_t s);
+template <class KP>
+void launch_refine_transform(int model, const KP* kp_yx, const int* kp_count, const int* match_idx, int P, int K, double thr,
+                             int rounds, double* H_io, unsigned char* mask, int* n_inliers, double* cost, hipStream_t s);
+void launch_find_transform_pooled(int model, const float* pts, const int* group_offsets, int N, int G, int T, double thr,
+                                  unsigned long long seed, unsigned int* counts, unsigned long long* best, double* H_out,
+                                  unsigned char* mask, int* n_inliers, hipStream_t s);
+void launch_refine_transform_pooled(int model, const float* pts, const int* group_offsets, int N, int G, double thr, int rounds,
+                                    double* H_io, unsigned char* mask, int* n_inliers, double* cost, hipStream_t s);
+
 // single-image detector metrics (detector_metrics.hip; evaluation.py:56-97): best [B][H][W] scratch, rec_count / n_gt [B]
 // (all three pre-set to 0), records [B][H*W]
 void launch_detector_metrics(const float* prob, const unsigned char* gt, int B, int H, int W, float zero_thr,

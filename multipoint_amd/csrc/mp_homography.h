@@ -3,10 +3,11 @@
 // forward reprojection test, the normalised-DLT refit and the Levenberg-Marquardt polish.
 // One body, two views.  refit_kernel, refine_kernel, lm_sums and hypothesis are templates on where the correspondences live
 // and how an outlier is marked: PairView (a pair's list in LDS) or PooledView (a group's rows in global memory).  A kernel gets
-// its view from a Source, the struct of launch arguments that locates the points of pair / group `index` (PairSource in
-// homography.hip gathers them into LDS, PooledSource in homography_pooled.hip looks up the group's range).  Every
-// floating-point operation, reduction and barrier is in the shared body, so the same correspondences give the same bits on
-// either route.
+// its view from a Source, the struct of launch arguments that locates the points of pair / group `index` (PairSource gathers
+// them into LDS, PooledSource looks up the group's range).  Every floating-point operation, reduction and barrier is in the
+// shared body, so the same correspondences give the same bits on either route.
+// The model-free pieces -- compaction, match_point, the views and sources, block_sum -- also serve the similarity / affine
+// estimators (mp_transform.h), by inclusion: the bodies below have no caller and no template parameter from there.
 #pragma once
 #include "mp_common.h"
 #include "mp_device.h"
@@ -146,6 +147,60 @@ struct PooledView {
     __device__ float4 get(int i) const { return pts[i]; }
     __device__ bool is_inlier(int i) const { return mask[i] != 0; }
     __device__ void set_inlier(int i, bool in) const { mask[i] = in ? 1 : 0; }
+};
+
+// ---- the two sources: what locates the view of pair / group `index` ----
+// gather the matched (x,y)->(u,v) pairs of pair p into LDS in query order; returns their number
+// pts: [n][4] floats in LDS order x, y, u, v; qidx (may be NULL): [n] the query index of each match
+template <class KP>
+__device__ int gather(const KP* kp_yx, const int* kp_count, const int* match_idx, int p, int K, float* pts, int* qidx)
+{
+    return compact_matches(kp_count, match_idx, p, K, [&](int pos, int i, int j) {
+        const float4 q = match_point(kp_yx, p, K, i, j);
+        pts[pos * 4 + 0] = q.x; pts[pos * 4 + 1] = q.y; pts[pos * 4 + 2] = q.z; pts[pos * 4 + 3] = q.w;
+        if (qidx) qidx[pos] = i;
+    });
+}
+
+// what refit_kernel / refine_kernel are launched with: the view of pair p is its gathered list in LDS
+// (dynamic LDS: [K][4] floats, then [K] ints) and its row of the mask.  KP: the keypoint type (int pixels or float sub-pixel
+// positions); it only decides what gather reads
+template <class KP>
+struct PairSource {
+    const KP* kp_yx;
+    const int* kp_count;
+    const int* match_idx;
+    int K;
+    unsigned char* mask;
+    __device__ PairView view(int p) const
+    {
+        extern __shared__ float pts[];
+        int* qidx = reinterpret_cast<int*>(pts + (size_t)K * 4);
+        const int n = gather(kp_yx, kp_count, match_idx, p, K, pts, qidx);
+        return PairView{pts, qidx, mask + (size_t)p * K, n};
+    }
+};
+
+// the rows [start, start + n) of group g, clamped to [0, N] (the offsets are device data: nothing they hold may lead outside pts)
+__device__ __forceinline__ int group_range(const int* group_offsets, int g, int N, int& start)
+{
+    const int a = min(max(group_offsets[g], 0), N), b = min(max(group_offsets[g + 1], 0), N);
+    start = a;
+    return max(b - a, 0);
+}
+
+// what refit_kernel / refine_kernel are launched with: the view of group g is its range of pts and mask
+struct PooledSource {
+    const float4* pts;
+    const int* group_offsets;
+    int N;
+    unsigned char* mask;
+    __device__ PooledView view(int g) const
+    {
+        int start;
+        const int n = group_range(group_offsets, g, N, start);
+        return PooledView{pts + start, mask + start, n};
+    }
 };
 
 // hypothesis t of pair / group `index` from 4 sampled points of the view; false if the 4-point system is singular

@@ -590,6 +590,145 @@ int mp_refine_homography_pooled(mp_handle* h, const float* pts, const int* group
     return launch_status(h);
 }
 
+// ---- similarity / affine models on the three routes (transform.hip, transform_f.hip, transform_pooled.hip) ----
+// mp_find_transform / mp_find_transform_f: MP_MODEL_HOMOGRAPHY is the existing entry itself; the other models get the same
+// checks, buffers and memsets in front of their own launch
+extern "C++" {          // (a template cannot have C linkage)
+static bool transform_model_known(int model)
+{
+    return model == MP_MODEL_HOMOGRAPHY || model == MP_MODEL_SIMILARITY || model == MP_MODEL_AFFINE;
+}
+
+template <class KP>
+static int find_transform(mp_handle* h, const std::string& fn, const KP* kp_yx, const int* kp_count, const int* match_idx, int P,
+                          int K, int model, double reproj_threshold, int max_iters, unsigned long long seed, double* transform,
+                          unsigned char* inlier_mask, int* n_inliers, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!transform_model_known(model)) return fail(h, MP_EINVAL, fn + ": unknown model " + std::to_string(model));
+    if (model == MP_MODEL_HOMOGRAPHY)
+        return find_homography(h, fn, kp_yx, kp_count, match_idx, P, K, reproj_threshold, max_iters, seed, transform, inlier_mask,
+                               n_inliers, stream);
+    if (!kp_yx || !kp_count || !match_idx || !transform || !inlier_mask || !n_inliers)
+        return fail(h, MP_EINVAL, fn + ": NULL tensor");
+    if (P <= 0 || K <= 0 || K > 3200) return fail(h, MP_EINVAL, fn + ": need P > 0 and 0 < K <= 3200");
+    if (max_iters <= 0 || max_iters > (1 << 20)) return fail(h, MP_EINVAL, fn + ": max_iters out of range");
+    if (!(reproj_threshold > 0.0)) return fail(h, MP_EINVAL, fn + ": threshold must be positive");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MP_HIP(hipSetDevice(h->device));
+    int rc;
+    if ((rc = ensure(h, h->metrics_ws, (size_t)P * sizeof(unsigned long long)))) return rc;
+    unsigned long long* best = static_cast<unsigned long long*>(h->metrics_ws.p);
+    MP_HIP(hipMemsetAsync(best, 0, (size_t)P * sizeof(unsigned long long), s));
+    MP_HIP(hipMemsetAsync(inlier_mask, 0, (size_t)P * K, s));
+    launch_find_transform(model, kp_yx, kp_count, match_idx, P, K, max_iters, reproj_threshold, seed, best, transform, inlier_mask,
+                          n_inliers, s);
+    return launch_status(h);
+}
+
+template <class KP>
+static int refine_transform(mp_handle* h, const std::string& fn, const KP* kp_yx, const int* kp_count, const int* match_idx, int P,
+                            int K, int model, double reproj_threshold, int rounds, double* transform, unsigned char* inlier_mask,
+                            int* n_inliers, double* cost, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!transform_model_known(model)) return fail(h, MP_EINVAL, fn + ": unknown model " + std::to_string(model));
+    if (model == MP_MODEL_HOMOGRAPHY)
+        return refine_homography(h, fn, kp_yx, kp_count, match_idx, P, K, reproj_threshold, rounds, transform, inlier_mask, n_inliers,
+                                 cost, stream);
+    if (!kp_yx || !kp_count || !match_idx || !transform || !inlier_mask || !n_inliers)
+        return fail(h, MP_EINVAL, fn + ": NULL tensor");
+    if (P <= 0 || K <= 0 || K > 3200) return fail(h, MP_EINVAL, fn + ": need P > 0 and 0 < K <= 3200");
+    if (rounds < 0 || rounds > 1000) return fail(h, MP_EINVAL, fn + ": rounds must be in [0, 1000]");
+    if (!(reproj_threshold > 0.0)) return fail(h, MP_EINVAL, fn + ": threshold must be positive");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MP_HIP(hipSetDevice(h->device));
+    MP_HIP(hipMemsetAsync(inlier_mask, 0, (size_t)P * K, s));
+    launch_refine_transform(model, kp_yx, kp_count, match_idx, P, K, reproj_threshold, rounds, transform, inlier_mask, n_inliers, cost,
+                            s);
+    return launch_status(h);
+}
+}
+
+int mp_find_transform(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K, int model,
+                      double reproj_threshold, int max_iters, unsigned long long seed, double* transform,
+                      unsigned char* inlier_mask, int* n_inliers, void* stream)
+{
+    return find_transform(h, "mp_find_transform", kp_yx, kp_count, match_idx, P, K, model, reproj_threshold, max_iters, seed, transform,
+                          inlier_mask, n_inliers, stream);
+}
+
+int mp_find_transform_f(mp_handle* h, const float* kp_sub_yx, const int* kp_count, const int* match_idx, int P, int K, int model,
+                        double reproj_threshold, int max_iters, unsigned long long seed, double* transform,
+                        unsigned char* inlier_mask, int* n_inliers, void* stream)
+{
+    return find_transform(h, "mp_find_transform_f", kp_sub_yx, kp_count, match_idx, P, K, model, reproj_threshold, max_iters, seed,
+                          transform, inlier_mask, n_inliers, stream);
+}
+
+int mp_refine_transform(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K, int model,
+                        double reproj_threshold, int rounds, double* transform, unsigned char* inlier_mask, int* n_inliers,
+                        double* cost, void* stream)
+{
+    return refine_transform(h, "mp_refine_transform", kp_yx, kp_count, match_idx, P, K, model, reproj_threshold, rounds, transform,
+                            inlier_mask, n_inliers, cost, stream);
+}
+
+int mp_refine_transform_f(mp_handle* h, const float* kp_sub_yx, const int* kp_count, const int* match_idx, int P, int K, int model,
+                          double reproj_threshold, int rounds, double* transform, unsigned char* inlier_mask, int* n_inliers,
+                          double* cost, void* stream)
+{
+    return refine_transform(h, "mp_refine_transform_f", kp_sub_yx, kp_count, match_idx, P, K, model, reproj_threshold, rounds,
+                            transform, inlier_mask, n_inliers, cost, stream);
+}
+
+int mp_find_transform_pooled(mp_handle* h, const float* pts, const int* group_offsets, long long N, int G, int model,
+                             double reproj_threshold, int max_iters, unsigned long long seed, double* transform,
+                             unsigned char* inlier_mask, int* n_inliers, void* workspace, long long workspace_bytes, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!transform_model_known(model)) return fail(h, MP_EINVAL, "mp_find_transform_pooled: unknown model " + std::to_string(model));
+    if (model == MP_MODEL_HOMOGRAPHY)
+        return mp_find_homography_pooled(h, pts, group_offsets, N, G, reproj_threshold, max_iters, seed, transform, inlier_mask,
+                                         n_inliers, workspace, workspace_bytes, stream);
+    const int rc = pooled_check(h, "mp_find_transform_pooled", pts, group_offsets, N, G, reproj_threshold, transform, inlier_mask,
+                                n_inliers);
+    if (rc) return rc;
+    if (max_iters <= 0 || max_iters > (1 << 20)) return fail(h, MP_EINVAL, "mp_find_transform_pooled: max_iters must be in [1, 2^20]");
+    if (!workspace || workspace_bytes < (long long)pooled_find_bytes(G, max_iters))
+        return fail(h, MP_EINVAL, "mp_find_transform_pooled: workspace smaller than mp_pooled_workspace_bytes");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MP_HIP(hipSetDevice(h->device));
+    unsigned int* counts = static_cast<unsigned int*>(workspace);
+    unsigned long long* best = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + pooled_best_offset(G, max_iters));
+    MP_HIP(hipMemsetAsync(counts, 0, (size_t)G * max_iters * sizeof(unsigned int), s));
+    if (N > 0) MP_HIP(hipMemsetAsync(inlier_mask, 0, (size_t)N, s));
+    launch_find_transform_pooled(model, pts, group_offsets, (int)N, G, max_iters, reproj_threshold, seed, counts, best, transform,
+                                 inlier_mask, n_inliers, s);
+    return launch_status(h);
+}
+
+int mp_refine_transform_pooled(mp_handle* h, const float* pts, const int* group_offsets, long long N, int G, int model,
+                               double reproj_threshold, int rounds, double* transform, unsigned char* inlier_mask, int* n_inliers,
+                               double* cost, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!transform_model_known(model)) return fail(h, MP_EINVAL, "mp_refine_transform_pooled: unknown model " + std::to_string(model));
+    if (model == MP_MODEL_HOMOGRAPHY)
+        return mp_refine_homography_pooled(h, pts, group_offsets, N, G, reproj_threshold, rounds, transform, inlier_mask, n_inliers,
+                                           cost, stream);
+    const int rc = pooled_check(h, "mp_refine_transform_pooled", pts, group_offsets, N, G, reproj_threshold, transform, inlier_mask,
+                                n_inliers);
+    if (rc) return rc;
+    if (rounds < 0 || rounds > 1000) return fail(h, MP_EINVAL, "mp_refine_transform_pooled: rounds must be in [0, 1000]");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MP_HIP(hipSetDevice(h->device));
+    if (N > 0) MP_HIP(hipMemsetAsync(inlier_mask, 0, (size_t)N, s));
+    launch_refine_transform_pooled(model, pts, group_offsets, (int)N, G, reproj_threshold, rounds, transform, inlier_mask, n_inliers,
+                                   cost, s);
+    return launch_status(h);
+}
+
 int mp_detector_metrics(mp_handle* h, const float* prob, const unsigned char* keypoint_map, int B, int H, int W,
                         float zero_threshold, float distance_thresh, unsigned long long* work, int* rec_index,
                         float* rec_prob, unsigned int* rec_bits, int* rec_count, int* n_gt, void* stream)

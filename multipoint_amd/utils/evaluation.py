@@ -138,7 +138,8 @@ def refine_homography(res, H, reproj_threshold=3.0, iters=10):
     return Hm, mask, nin, cost
 
 
-def refine_alignment(res, reproj_threshold=3.0, radius=None, rounds=1, polish=True, max_iters=2000, seed=0, threshold=-1.0):
+def refine_alignment(res, reproj_threshold=3.0, radius=None, rounds=1, polish=True, max_iters=2000, seed=0, threshold=-1.0,
+                     model='homography'):
     """Guided re-matching and a polished homography for the pairs of a PairResults with mutual matches (an extension; the
     reference stops at cv2.findHomography on the first match list):
       1. find_homography on the matches of `res`;
@@ -147,7 +148,8 @@ def refine_alignment(res, reproj_threshold=3.0, radius=None, rounds=1, polish=Tr
       3. with `polish`, refine_homography.
     A pair without a first estimate keeps its original matches and a zero matrix.  `res` is not modified.  With sub-pixel
     keypoints on `res` (kp_sub) the estimates and the polish read them; the gate of the re-matching stays on the integer pixels
-    (it is several pixels wide).
+    (it is several pixels wide).  `model` 'similarity' or 'affine': steps 1 to 3 use find_transform and refine_transform (local
+    optimisation in the place of the polish) with that model; the default is unchanged, bit for bit.
     Returns (res2, H [P,3,3] float64, mask [P,K] uint8, n_inliers [P] int32); res2 is a new PairResults that shares the
     keypoints and descriptors of `res`, holds the final match list and has match_mode 'guided'."""
     from ..pipeline import PairResults
@@ -160,11 +162,19 @@ def refine_alignment(res, reproj_threshold=3.0, radius=None, rounds=1, polish=Tr
     radius = 2.0 * float(reproj_threshold) if radius is None else float(radius)
     if not (radius > 0.0 and np.isfinite(radius)):
         raise ValueError('refine_alignment: radius must be finite and positive, got %r' % radius)
-    H, mask, nin = find_homography(res, reproj_threshold, max_iters, seed)
+    if model == 'homography':
+        def find(r):
+            return find_homography(r, reproj_threshold, max_iters, seed)
+    else:
+        transform_model(model)
+
+        def find(r):
+            return find_transform(r, model, reproj_threshold, max_iters, seed)
+    H, mask, nin = find(res)
     cur = res
     if rounds > 0:
         K, D = res.desc.shape[1:]
-        none = (nin < 4)                                     # no first estimate (zero matrix): the original matches stay
+        none = (nin < transform_min_inliers(model))          # no first estimate (zero matrix): the original matches stay
         for _ in range(rounds):
             mi, md, mc = guided_pairs(res.desc, res.kp_count, res.desc[1:], res.kp_count[1:], res.kp_yx, res.kp_yx[1:], H,
                                       radius, threshold, pair_stride=2 * K * D, count_stride=2)
@@ -173,12 +183,15 @@ def refine_alignment(res, reproj_threshold=3.0, radius=None, rounds=1, polish=Tr
             mc = torch.where(none, res.match_count, mc)
             cur = PairResults(res.kp_yx, res.kp_score, res.kp_count, res.desc, mi, md, mc, res.H, res.W, 'guided',
                               kp_sub=getattr(res, 'kp_sub', None))
-            H, mask, nin = find_homography(cur, reproj_threshold, max_iters, seed)
+            H, mask, nin = find(cur)
     if cur is res:
         cur = PairResults(res.kp_yx, res.kp_score, res.kp_count, res.desc, res.match_idx, res.match_dist, res.match_count,
                           res.H, res.W, 'guided', kp_sub=getattr(res, 'kp_sub', None))
     if polish:
-        H, mask, nin, _ = refine_homography(cur, H, reproj_threshold)
+        if model == 'homography':
+            H, mask, nin, _ = refine_homography(cur, H, reproj_threshold)
+        else:
+            H, mask, nin, _ = refine_transform(cur, H, model, reproj_threshold)
     return cur, H, mask, nin
 
 
@@ -391,6 +404,200 @@ def find_homography_pooled_points(optical_xy, thermal_xy, reproj_threshold=3.0, 
     return Hm[0].cpu().numpy(), mask.cpu().numpy()
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# similarity and affine models on the same routes (mp_find_transform*, mp_refine_transform*)
+# ----------------------------------------------------------------------------------------------------------------------
+TRANSFORM_MODELS = {'homography': 0, 'similarity': 1, 'affine': 2}       # MP_MODEL_*
+TRANSFORM_MIN_POINTS = {'homography': 4, 'similarity': 2, 'affine': 3}   # the minimal sample S of a model
+
+
+def transform_model(model):
+    """The MP_MODEL_* number of a model name ('homography', 'similarity', 'affine')."""
+    if model not in TRANSFORM_MODELS:
+        raise ValueError('unknown transform model %r: expected one of %s' % (model, sorted(TRANSFORM_MODELS)))
+    return TRANSFORM_MODELS[model]
+
+
+def transform_min_inliers(model):
+    """The fewest inliers a model of this kind is reported with: 4 for a homography, S + 1 for the others (a model that explains
+    only its own minimal sample is no model)."""
+    transform_model(model)
+    return 4 if model == 'homography' else TRANSFORM_MIN_POINTS[model] + 1
+
+
+def find_transform(res, model, reproj_threshold=3.0, max_iters=2000, seed=0):
+    """find_homography with a choice of motion model (mp_find_transform): 'homography' (find_homography itself, the same bits),
+    'similarity' [[a, -b, tx], [b, a, ty], [0, 0, 1]] (rotation, scale, two translations: what the reference's manual
+    alignment gets from cv2.estimateRigidTransform(ir, opt, False)) or 'affine' [[a, b, tx], [c, d, ty], [0, 0, 1]].  The two
+    new models draw `max_iters` hypotheses from 2 / 3 matches each, keep the one with the most inliers and refit it by exact
+    least squares over them; a rig's few correct cross-spectral matches determine 4 or 6 parameters where they do not
+    determine 8.  NOT cv2.estimateAffinePartial2D / estimateAffine2D bit for bit, and without their adaptive iteration bound.
+    Returns what find_homography returns: (H [P,3,3] float64 optical (x,y,1) -> thermal, all zeros where there is no model
+    (fewer than transform_min_inliers(model) inliers); mask [P,K] uint8 per optical keypoint; n_inliers [P] int32).  Sub-pixel
+    keypoints on `res` (kp_sub) are read as find_homography reads them."""
+    m = transform_model(model)
+    res.wait()
+    dev = res.kp_yx.device
+    P, K = res.num_pairs, res.kp_yx.shape[1]
+    Hm = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
+    mask = torch.empty((P, K), dtype=torch.uint8, device=dev)
+    nin = torch.empty((P,), dtype=torch.int32, device=dev)
+    h = _lib.get_handle(dev)
+    entry, kp = _keypoints_for_estimate(res, h, 'mp_find_transform')
+    with torch.cuda.device(dev):
+        h.check(entry(h.ptr, _lib.ptr(kp), _lib.ptr(res.kp_count.contiguous()), _lib.ptr(res.match_idx.contiguous()), P, K, m,
+                      float(reproj_threshold), int(max_iters), int(seed), _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin),
+                      _lib.stream_ptr(dev)))
+    return Hm, mask, nin
+
+
+def refine_transform(res, H, model, reproj_threshold=3.0, rounds=10):
+    """refine_homography with a choice of motion model (mp_refine_transform).  'homography': the Levenberg-Marquardt polish,
+    `rounds` as its iterations (the same bits).  'similarity' / 'affine': local optimisation -- at most `rounds` times, mark the
+    matches within reproj_threshold of the current model and refit it by exact least squares over them; a marking that changes
+    nothing ends it.  Returns (H [P,3,3] float64, mask [P,K] uint8 and n_inliers [P] int32 of the last set marked -- the one
+    the returned model was fitted to, the input's own with rounds = 0 --, cost [P,2] float64: the summed squared error over
+    that set before / after the last refit).  All zeros where the input is all zeros or a set has fewer than
+    transform_min_inliers(model) members."""
+    m = transform_model(model)
+    rounds = int(rounds)
+    if not float(reproj_threshold) > 0.0:
+        raise ValueError('refine_transform: reproj_threshold must be positive')
+    if not 0 <= rounds <= 1000:
+        raise ValueError('refine_transform: rounds must be in [0, 1000]')
+    P, K = res.num_pairs, res.kp_yx.shape[1]
+    Hm = torch.as_tensor(H, dtype=torch.float64)
+    if Hm.numel() != P * 9:
+        raise ValueError('refine_transform: need one 3x3 matrix per pair (%d), got %d values' % (P, Hm.numel()))
+    res.wait()
+    dev = res.kp_yx.device
+    Hm = Hm.to(dev).reshape(P, 3, 3).clone().contiguous()                    # (refined in place: never the caller's tensor)
+    mask = torch.empty((P, K), dtype=torch.uint8, device=dev)
+    nin = torch.empty((P,), dtype=torch.int32, device=dev)
+    cost = torch.empty((P, 2), dtype=torch.float64, device=dev)
+    h = _lib.get_handle(dev)
+    entry, kp = _keypoints_for_estimate(res, h, 'mp_refine_transform')
+    with torch.cuda.device(dev):
+        h.check(entry(h.ptr, _lib.ptr(kp), _lib.ptr(res.kp_count.contiguous()), _lib.ptr(res.match_idx.contiguous()), P, K, m,
+                      float(reproj_threshold), rounds, _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin), _lib.ptr(cost),
+                      _lib.stream_ptr(dev)))
+    return Hm, mask, nin, cost
+
+
+def find_transform_points(optical_pts, thermal_pts, model, reproj_threshold=3.0, max_iters=2000, seed=0, device=None):
+    """find_homography_points with a choice of motion model: ONE set of corresponding (x, y) points, integer input through
+    mp_find_transform and floating input, kept as float32, through mp_find_transform_f.  Returns (H 3x3 float64 numpy or None,
+    mask (N,) uint8); None with fewer points than the model's minimal sample or without a model."""
+    from ..pipeline import PairResults
+    transform_model(model)
+    a = np.asarray(optical_pts).reshape(-1, 2); b = np.asarray(thermal_pts).reshape(-1, 2)
+    n = len(a)
+    if len(b) != n:
+        raise ValueError('find_transform_points: %d optical and %d thermal points' % (n, len(b)))
+    if n < TRANSFORM_MIN_POINTS[model]:
+        return None, np.zeros(n, np.uint8)
+    if n > MAX_RANSAC_MATCHES:
+        raise ValueError('find_transform_points: at most %d correspondences per call (the pair\'s matches live in LDS); '
+                         'got %d -- keep the closest ones' % (MAX_RANSAC_MATCHES, n))
+    dev = _lib.require_cuda(device)
+    kp = torch.zeros((2, n, 2), dtype=torch.int32)
+    kp[0] = torch.from_numpy(np.ascontiguousarray(a[:, ::-1]).astype(np.int32)); kp[1] = torch.from_numpy(np.ascontiguousarray(b[:, ::-1]).astype(np.int32))
+    sub = None
+    if a.dtype.kind == 'f' or b.dtype.kind == 'f':
+        sub = torch.from_numpy(np.stack([a[:, ::-1], b[:, ::-1]]).astype(np.float32)).to(dev)
+    res = PairResults(kp.to(dev), None, torch.tensor([n, n], dtype=torch.int32, device=dev), None,
+                      torch.arange(n, dtype=torch.int32, device=dev).reshape(1, n), None, None, 0, 0, kp_sub=sub)
+    Hm, mask, nin = find_transform(res, model, reproj_threshold, max_iters, seed)
+    if int(nin[0]) < transform_min_inliers(model):
+        return None, np.zeros(n, np.uint8)
+    return Hm[0].cpu().numpy(), mask[0].cpu().numpy()
+
+
+def find_transform_pooled(pooled, model, reproj_threshold=3.0, max_iters=2000, seed=0):
+    """find_homography_pooled with a choice of motion model (mp_find_transform_pooled): one model per group of a PooledMatches.
+    Returns (H [G,3,3] float64, mask [N] uint8 per row of pooled.pts, n_inliers [G] int32)."""
+    m = transform_model(model)
+    max_iters = int(max_iters)
+    N, G = _check_pooled('find_transform_pooled', pooled, reproj_threshold)
+    if not 0 < max_iters <= MAX_POOLED_ITERS:
+        raise ValueError('find_transform_pooled: max_iters must be in [1, %d]' % MAX_POOLED_ITERS)
+    dev = pooled.pts.device
+    pts = pooled.pts.contiguous()
+    Hm = torch.empty((G, 3, 3), dtype=torch.float64, device=dev)
+    mask = torch.empty((N,), dtype=torch.uint8, device=dev)
+    nin = torch.empty((G,), dtype=torch.int32, device=dev)
+    h = _lib.get_handle(dev)
+    with torch.cuda.device(dev):
+        ws = _pooled_workspace(h, 0, G, max_iters, dev)
+        h.check(h.lib.mp_find_transform_pooled(h.ptr, _lib.ptr(pts), _lib.ptr(pooled.group_offsets.contiguous()), N, G, m,
+                                               float(reproj_threshold), max_iters, int(seed), _lib.ptr(Hm), _lib.ptr(mask),
+                                               _lib.ptr(nin), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+    return Hm, mask, nin
+
+
+def refine_transform_pooled(pooled, H, model, reproj_threshold=3.0, rounds=10):
+    """refine_transform on the groups of a PooledMatches (mp_refine_transform_pooled).  Returns (H [G,3,3] float64, mask [N]
+    uint8, n_inliers [G] int32, cost [G,2] float64), as refine_transform describes them."""
+    m = transform_model(model)
+    rounds = int(rounds)
+    N, G = _check_pooled('refine_transform_pooled', pooled, reproj_threshold)
+    if not 0 <= rounds <= 1000:
+        raise ValueError('refine_transform_pooled: rounds must be in [0, 1000]')
+    Hm = torch.as_tensor(H, dtype=torch.float64)
+    if Hm.numel() != G * 9:
+        raise ValueError('refine_transform_pooled: need one 3x3 matrix per group (%d), got %d values' % (G, Hm.numel()))
+    dev = pooled.pts.device
+    pts = pooled.pts.contiguous()
+    Hm = Hm.to(dev).reshape(G, 3, 3).clone().contiguous()                    # (refined in place: never the caller's tensor)
+    mask = torch.empty((N,), dtype=torch.uint8, device=dev)
+    nin = torch.empty((G,), dtype=torch.int32, device=dev)
+    cost = torch.empty((G, 2), dtype=torch.float64, device=dev)
+    h = _lib.get_handle(dev)
+    with torch.cuda.device(dev):
+        h.check(h.lib.mp_refine_transform_pooled(h.ptr, _lib.ptr(pts), _lib.ptr(pooled.group_offsets.contiguous()), N, G, m,
+                                                 float(reproj_threshold), rounds, _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin),
+                                                 _lib.ptr(cost), _lib.stream_ptr(dev)))
+    return Hm, mask, nin, cost
+
+
+def estimate_shared_transform(res, groups=None, model='similarity', reproj_threshold=3.0, max_iters=2000, seed=0, polish=True,
+                              rounds=10):
+    """estimate_shared_homography with a choice of motion model: pool_matches, find_transform_pooled and, with `polish`,
+    refine_transform_pooled (`rounds` of local optimisation; the polish's iterations for 'homography').  Returns a
+    SharedHomography, as estimate_shared_homography does."""
+    transform_model(model)
+    if not float(reproj_threshold) > 0.0:
+        raise ValueError('estimate_shared_transform: reproj_threshold must be positive')
+    if not 0 < int(max_iters) <= MAX_POOLED_ITERS:
+        raise ValueError('estimate_shared_transform: max_iters must be in [1, %d]' % MAX_POOLED_ITERS)
+    if not 0 <= int(rounds) <= 1000:
+        raise ValueError('estimate_shared_transform: rounds must be in [0, 1000]')
+    pooled = pool_matches(res, groups)
+    H, mask, nin = find_transform_pooled(pooled, model, reproj_threshold, max_iters, seed)
+    cost = None
+    if polish:
+        H, mask, nin, cost = refine_transform_pooled(pooled, H, model, reproj_threshold, rounds)
+    return SharedHomography(H, mask, nin, cost, pooled)
+
+
+def decompose_similarity(H):
+    """(angle, scale, dx, dy) of a similarity [[a, -b, tx], [b, a, ty], [0, 0, 1]] in the convention of the reference's
+    optimiser (create_dataset/helper_functions/align.py:196-200, :210-211): angle = arctan2(H[0,1], H[0,0]), scale =
+    H[0,0] / cos(angle) -- computed as hypot(H[0,0], H[0,1]), the same number without the division by a cosine near zero --,
+    dx = H[0,2], dy = H[1,2]; the matrix is [[s cos, s sin, dx], [-s sin, s cos, dy]] again.  H is divided by H[2,2] first."""
+    m = np.asarray(H.detach().cpu() if isinstance(H, torch.Tensor) else H, dtype=np.float64).reshape(3, 3)
+    if not (np.isfinite(m).all() and m[2, 2] != 0.0):
+        raise ValueError('decompose_similarity: need a finite 3x3 matrix with H[2,2] != 0')
+    m = m / m[2, 2]
+    return float(np.arctan2(m[0, 1], m[0, 0])), float(np.hypot(m[0, 0], m[0, 1])), float(m[0, 2]), float(m[1, 2])
+
+
+def compose_similarity(angle, scale, dx, dy):
+    """The 3x3 matrix decompose_similarity takes apart."""
+    c, s = scale * np.cos(angle), scale * np.sin(angle)
+    return np.array([[c, s, dx], [-s, c, dy], [0.0, 0.0, 1.0]])
+
+
 def _warp_yx(pts_yx, hmat):
     """warp_keypoints(..., np.float) for a handful of points (homographies.py:331-346)."""
     p = np.asarray(pts_yx, dtype=np.float64)
@@ -419,7 +626,9 @@ def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoi
     pair after re-matching).  Every other key keeps its value; without enable there is no new key.
     Extension: config['subpixel'] = {enable: false}.  With enable: true the pipeline refines its keypoint lists and samples the
     descriptors at the refined positions, and every homography estimate here reads the sub-pixel positions; the keypoint
-    metrics (mp_pair_metrics) stay on the integer pixels, the reference's definitions."""
+    metrics (mp_pair_metrics) stay on the integer pixels, the reference's definitions.
+    Extension: config['transform_model'] = 'homography' | 'similarity' | 'affine' (default, and when absent: 'homography',
+    nothing changes).  With another model every estimate here, the refinement's included, is find_transform's."""
     from ..pipeline import PairPipeline, PairResults
     from .utils import data_to_device
     from .matching import get_matches, match_pairs, nearest_pairs
@@ -437,6 +646,10 @@ def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoi
     if not same_matcher and mcfg.get('method') in ('bfmatcher', 'nnmatcher'):
         sel = PairPipeline(None, dict(config, matching=mcfg))
     refine = _refinement_config(config)
+    model = config.get('transform_model', 'homography')
+    min_in, min_pts = transform_min_inliers(model), TRANSFORM_MIN_POINTS[model]
+    if refine is not None and model != 'homography':
+        refine = dict(refine, model=model)
     pts_dist_ref, n_matches_ref = [], []
     tp_o, tp_t, dist_o, dist_t, ms_o, ms_t, pts_dist = [], [], [], [], [], [], []
     n_gt_o = n_gt_t = 0
@@ -463,7 +676,10 @@ def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoi
             est = PairResults(res.kp_yx, res.kp_score, res.kp_count, res.desc, mm[0], mm[1], mm[2], res.H, res.W,
                               sel.match_mode, kp_sub=res.kp_sub)
         if est is not None:
-            h_est, _, n_in = find_homography(est, config.get('reprojection_threshold', 3))
+            if model == 'homography':
+                h_est, _, n_in = find_homography(est, config.get('reprojection_threshold', 3))
+            else:
+                h_est, _, n_in = find_transform(est, model, config.get('reprojection_threshold', 3))
             h_est = h_est.cpu().numpy(); n_in = n_in.cpu().numpy()
         else:
             # one-to-many matchers (thresholdmatcher) and lists longer than one RANSAC launch holds: per pair through
@@ -477,13 +693,16 @@ def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoi
                     continue
                 matches = get_matches(res.desc[2 * p, :no], res.desc[2 * p + 1, :nt], mcfg['method'],
                                       mcfg.get('knn_matches', False), **mcfg.get('method_kwargs', {}))
-                if len(matches) < 4:
+                if len(matches) < min_pts:
                     continue
                 if len(matches) > MAX_RANSAC_MATCHES:           # one-to-many matchers (thresholdmatcher): closest first
                     matches = sorted(matches, key=lambda mm: mm.distance)[:MAX_RANSAC_MATCHES]
                 opts = np.array([kp_all[2 * p, mm.queryIdx][::-1] for mm in matches])
                 tpts = np.array([kp_all[2 * p + 1, mm.trainIdx][::-1] for mm in matches])
-                hp, mask = find_homography_points(opts, tpts, config.get('reprojection_threshold', 3), device=device)
+                if model == 'homography':
+                    hp, mask = find_homography_points(opts, tpts, config.get('reprojection_threshold', 3), device=device)
+                else:
+                    hp, mask = find_transform_points(opts, tpts, model, config.get('reprojection_threshold', 3), device=device)
                 if hp is not None:
                     h_est[p] = hp; n_in[p] = int(mask.sum())
         if refine is not None:
@@ -509,14 +728,14 @@ def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoi
             ms_o.append(float(m[p, 2]) / m[p, 4] if m[p, 4] > 0 else 0.0)
             ms_t.append(float(m[p, 3]) / m[p, 5] if m[p, 5] > 0 else 0.0)
             # homography correctness (:351-356; the reference's corner list, including its (H_o, H_o) last point)
-            if n_in[p] >= 4:
+            if n_in[p] >= min_in:
                 pts = np.array([[0, 0], [H_o, 0], [0, W_o], [H_o, H_o]])
                 gt = gth[2 * p].numpy().reshape(3, 3)
                 pts_dist.append(np.linalg.norm(_warp_yx(pts, h_est[p]) - _warp_yx(pts, gt), axis=1).sum() / 4)
             else:
                 pts_dist.append(999.0)
             if refine is not None:
-                if n_in_ref[p] >= 4:
+                if n_in_ref[p] >= min_in:
                     pts = np.array([[0, 0], [H_o, 0], [0, W_o], [H_o, H_o]])
                     gt = gth[2 * p].numpy().reshape(3, 3)
                     pts_dist_ref.append(np.linalg.norm(_warp_yx(pts, h_ref[p]) - _warp_yx(pts, gt), axis=1).sum() / 4)

@@ -49,6 +49,10 @@ def build_parser():
                         'the pair under the identity, the estimated and (with --refine) the refined homography')
     parser.add_argument('--mi-refine', action='store_true', help='(extension) maximise the mutual information from the estimated '
                         'homography (utils.alignment.align_images; yaml block prediction.mi_alignment) and print the result')
+    parser.add_argument('--transform', default=None, choices=['homography', 'similarity', 'affine'],
+                        help='(extension) motion model of the estimate (default: prediction.transform_model, else homography): a '
+                        'similarity (rotation, scale, two translations) or an affine transform are determined by fewer inliers '
+                        'than the 8-parameter homography')
     parser.add_argument('--plot-dir', default=None, help='(extension) with -p: write matches.png, matches_inliers.png, '
                         'warped_optical.png, overlay_checker.png and overlay_anaglyph.png into this directory')
     return parser
@@ -99,10 +103,10 @@ def select_device(config):
 
 
 def refine_estimate(kp_optical, kp_thermal, desc_optical, desc_thermal, matches, mask, H, W, pred, H_est, sub_optical=None,
-                    sub_thermal=None):
+                    sub_thermal=None, model='homography'):
     """--refine: the sample's lists as a one-pair PairResults through utils.refine_alignment.  Prints inliers / matches
     before and after and returns the refined estimate (the first one where there is nothing to refine).  sub_*: the
-    sub-pixel positions of --subpixel, which the estimates and the polish then read."""
+    sub-pixel positions of --subpixel, which the estimates and the polish then read.  model: the motion model of --transform."""
     from multipoint_amd.pipeline import PairResults
     no, nt = kp_optical.shape[0], kp_thermal.shape[0]
     D = desc_optical.shape[1] if no else desc_thermal.shape[1] if nt else 0
@@ -133,13 +137,14 @@ def refine_estimate(kp_optical, kp_thermal, desc_optical, desc_thermal, matches,
                       torch.tensor([len(matches)], dtype=torch.int32, device=dev), H, W, kp_sub=kp_sub)
     res2, H_ref, _, n_in = utils.refine_alignment(res, pred['reprojection_threshold'],
                                                   threshold=pred['matching']['method_kwargs'].get('threshold', -1.0)
-                                                  if pred['matching']['method'] == 'nnmatcher' else -1.0)
-    if int(n_in[0]) < 4:
+                                                  if pred['matching']['method'] == 'nnmatcher' else -1.0,
+                                                  **({} if model == 'homography' else {'model': model}))
+    if int(n_in[0]) < utils.transform_min_inliers(model):
         print(before + ' -> no refined estimate')
         return H_est
     print(before + ' -> {} inliers of {} matches'.format(int(n_in[0]), int(res2.match_count[0])))
     H_ref = H_ref[0].cpu().numpy()
-    print('Refined Homography:')
+    print('Refined Homography:' if model == 'homography' else 'Refined %s transform:' % model)
     print(H_ref)
     return H_ref
 
@@ -216,6 +221,10 @@ def main(argv=None):
     pred = config['prediction']
     if args.subpixel:
         pred['subpixel'] = dict(pred.get('subpixel') or {}, enable=True)
+    if args.transform is not None:
+        pred['transform_model'] = args.transform
+    model = pred.get('transform_model', 'homography')
+    utils.transform_model(model)                        # (refuses an unknown name before any work)
     subpixel = bool((pred.get('subpixel') or {}).get('enable', False))
     if subpixel and hasattr(net, 'describe'):
         raise ValueError('subpixel: ClassicDetectors models have no sub-pixel keypoints (LGHD descriptors are patch histograms '
@@ -309,19 +318,25 @@ def main(argv=None):
             kpt_est = kpt if sub_thermal is None else sub_thermal.cpu().numpy()
             optical_pts = np.array([kpo_est[m.queryIdx][::-1] for m in matches]).reshape(-1, 2)
             thermal_pts = np.array([kpt_est[m.trainIdx][::-1] for m in matches]).reshape(-1, 2)
-            H_est, mask = utils.find_homography_points(optical_pts, thermal_pts, pred['reprojection_threshold'], device=device)
+            if model == 'homography':
+                H_est, mask = utils.find_homography_points(optical_pts, thermal_pts, pred['reprojection_threshold'], device=device)
+            else:
+                H_est, mask = utils.find_transform_points(optical_pts, thermal_pts, model, pred['reprojection_threshold'],
+                                                          device=device)
             if H_est is None:
                 H_est = np.eye(3, 3)
             eye = torch.eye(3)
             H_gt = np.matmul(data['thermal'].get('homography', eye[None])[0].cpu().numpy(),
                              np.linalg.inv(data['optical'].get('homography', eye[None])[0].cpu().numpy()))
-            print('Estimated Homography:')
+            print('Estimated Homography:' if model == 'homography' else 'Estimated %s transform:' % model)
             print(H_est)
+            if model == 'similarity':
+                print('Similarity: angle {:.6f} rad  scale {:.6f}  dx {:.3f}  dy {:.3f}'.format(*utils.decompose_similarity(H_est)))
             print('RANSAC inliers: {} of {} matches'.format(int(np.sum(mask)), len(matches)))
             H_first = H_est
             if args.refine:
                 H_est = refine_estimate(pred_optical, pred_thermal, desc_optical, desc_thermal, matches, mask, H, W, pred,
-                                        H_est, sub_optical, sub_thermal)
+                                        H_est, sub_optical, sub_thermal, model)
             if args.mi:
                 mi_report(data['optical']['image'][:1], data['thermal']['image'][:1],
                           [('identity', np.eye(3)), ('estimated', H_first)] + ([('refined', H_est)] if args.refine else []))
