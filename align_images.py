@@ -8,7 +8,8 @@ initial_transform.yaml with the key `perspective` (3x3, thermal pixel -> optical
 (--batch); all frames of a run have the same size.  Written to the output directory:
 
   failed.log                          the optical file name of every pair without a valid alignment
-  transforms.json                     {index: {"transform": 3x3, "type": winning candidate}} of the aligned pairs
+  transforms.json                     {index: {"transform": 3x3, "type": winning candidate}} of the aligned pairs; with a
+                                      motion model other than the homography (--transform, alignment/model) also "model"
   aligned/best/<index>_optical.png    (save_aligned_images) the optical image warped onto the thermal frame, channel by channel
                                       with the fp32 warp of utils.alignment.warp_image, rounded to 8 bit; pixels that take part of
                                       the border are 0
@@ -42,6 +43,10 @@ def build_parser():
     parser.add_argument('--batch', default=8, type=int, help='(extension) pairs aligned together in one batch')
     parser.add_argument('--save-candidates', action='store_true', help='(extension) also write aligned/all/<index>_optical_<i>.png, '
                         'the optical image under every valid candidate, for check_alignment.py')
+    parser.add_argument('--transform', default=None, choices=['homography', 'similarity', 'affine'],
+                        help='(extension) motion model the optimiser searches in; overrides the yaml key alignment/model (default '
+                        'homography: all nine matrix entries).  similarity: rotation, scale and two translations; affine: the six '
+                        'entries of the top two rows.  Both stay 3x3 matrices with last row (0, 0, 1) under the same warp')
     return parser
 
 
@@ -107,6 +112,9 @@ def main(argv=None):
     from multipoint_amd.utils import alignment
     if not params.get('perspective', True):
         raise NotImplementedError('perspective: false -- ' + alignment._AFFINE)
+    if args.transform is not None:
+        params['alignment/model'] = args.transform
+    model = params.get('alignment/model', 'homography')
     os.makedirs(args.output_dir, exist_ok=True)
     names = sorted(f for f in os.listdir(args.input_dir)
                    if os.path.isfile(os.path.join(args.input_dir, f)) and 'optical' in f)
@@ -145,6 +153,8 @@ def main(argv=None):
                 failed.append(name)
                 continue
             transforms[index] = {'transform': T.tolist(), 'type': kind}
+            if model != 'homography':
+                transforms[index]['model'] = model
             if params.get('save_aligned_images', False):
                 save_aligned(alignment, os.path.join(best_dir, index + '_optical.png'), opt, T, th.shape[0], th.shape[1])
                 shutil.copyfile(thermal_path, os.path.join(best_dir, index + '_thermal.png'))

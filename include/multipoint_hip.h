@@ -692,6 +692,7 @@ int mp_shapes_finish(mp_handle* h, float* canvas, int n, int H, int W, const int
  * mp_mi_workspace_bytes: n_thermal_maps = distinct (pair, bins) among the evaluations, max_bins their largest bin count,
  * smoothing != 0 when sigma > 0.  A refinement of P problems counts MP_MI_SLOTS evaluations per problem. */
 #define MP_MI_SLOTS 10
+#define MP_MI_PARAMS_MAX 9      /* parameters of the largest motion model of a refinement (mp_mi_refine_begin_model) */
 int mp_mi_workspace_bytes(int n_evals, int n_pairs, int n_thermal_maps, int H, int W, int max_bins, int smoothing,
                           long long* bytes);
 
@@ -738,6 +739,31 @@ int mp_mi_refine_begin(mp_handle* h, const float* optical, int Ho, int Wo, const
 int mp_mi_refine_step(mp_handle* h, void* workspace, int n_iters, int* live, void* stream);
 int mp_mi_refine_result(mp_handle* h, void* workspace, double* transforms, double* values, int* iterations,
                         int* function_calls, int* success, void* stream);
+
+/* The same refinement over the n parameters of a motion model (MP_MODEL_*) with a simplex of n + 1 vertices;
+ * the objective reads the 3x3 matrix of a parameter vector p, through the same perspective warp:
+ *   MP_MODEL_HOMOGRAPHY  n = 9  the nine entries
+ *   MP_MODEL_SIMILARITY  n = 4  p = (angle, scale, dx, dy): [[s cos a, s sin a, dx], [-s sin a, s cos a, dy], [0, 0, 1]], the
+ *                               reference's decomposed form (create_dataset/helper_functions/align.py:137-139)
+ *   MP_MODEL_AFFINE      n = 6  the six entries of the top two rows, row-major; last row (0, 0, 1)
+ * Parameters are mapped as they are (no clamping).  scipy's rules are those of mp_mi_refine_begin with n in the place of 9:
+ * initial vertex k + 1 = 1.05 x0[k] (0.00025 where x0[k] == 0), the centroid summed vertex by vertex and divided by n.  With
+ * `regularize` the Frobenius norm of (matrix of the start parameters - matrix of the candidate) over the nine entries is added.
+ *   mp_mi_refine_begin_model   mp_mi_refine_begin's arguments, then `model` and init_params device double [n_problems][n], the
+ *                              start.  init_transforms is read only when init_params is NULL and the model is the homography
+ *                              (whose parameters are the matrix entries); mp_mi_refine_begin is this with model 0.
+ *                              MP_EINVAL also for an unknown model (mp_last_error names it)
+ *   mp_mi_refine_result_model  mp_mi_refine_result's arguments, then params double [n_problems][n]: the best vertex itself;
+ *                              transforms is its matrix
+ *   mp_mi_model_transform      the map alone: transforms double [n_rows][9] of params double [n_rows][n], both on the device
+ * mp_mi_refine_step serves every model.  A workspace of the size mp_mi_workspace_bytes returns suffices for every model. */
+int mp_mi_refine_begin_model(mp_handle* h, const float* optical, int Ho, int Wo, const float* thermal, int H, int W, int n_pairs,
+                             const mp_mi_problem* problems, const double* init_transforms, int n_problems, double sigma,
+                             int normalized, int regularize, void* workspace, long long workspace_bytes, void* stream, int model,
+                             const double* init_params);
+int mp_mi_refine_result_model(mp_handle* h, void* workspace, double* transforms, double* values, int* iterations,
+                              int* function_calls, int* success, void* stream, double* params);
+int mp_mi_model_transform(mp_handle* h, int model, const double* params, int n_rows, double* transforms, void* stream);
 
 /* ---- image pyramid of the staged alignment (create_dataset/align_images.py:163-171, helper_functions/align.py:485-489;
  * DESIGN.md 3.8.3) ----

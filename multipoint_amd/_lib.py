@@ -70,6 +70,7 @@ class MiProblem(ctypes.Structure):
 
 
 MP_MI_SLOTS = 10
+MP_MI_PARAMS_MAX = 9
 MP_FRAMES_U8, MP_FRAMES_BGR8, MP_FRAMES_U16 = 0, 1, 2
 MP_DRAW_MAX_RADIUS = 64
 MP_DRAW_KINDS = {'ring': 0, 'disc': 1, 'cross': 2}
@@ -192,6 +193,12 @@ SIGNATURES = {
                                    c_void_p, c_int, ctypes.c_double, c_int, c_int, c_void_p, c_ll, c_void_p]),
     'mp_mi_refine_step': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'mp_mi_refine_result': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'mp_mi_refine_begin_model': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                         ctypes.POINTER(MiProblem), c_void_p, c_int, ctypes.c_double, c_int, c_int, c_void_p,
+                                         c_ll, c_void_p, c_int, c_void_p]),
+    'mp_mi_refine_result_model': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p]),
+    'mp_mi_model_transform': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     'mp_gaussian_weights': (c_int, [c_int, ctypes.POINTER(c_float)]),
     'mp_gaussian_blur': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'mp_frames_to_float': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -10,6 +10,8 @@
 using namespace mp_host;
 
 static_assert(MI_SLOTS == MP_MI_SLOTS, "the kernels' slots per problem and the public header's must agree");
+static_assert(MI_PARAMS_MAX == MP_MI_PARAMS_MAX && MI_PARAMS_MAX + 1 <= MI_SLOTS,
+              "the largest simplex must fit a problem's evaluation slots");
 
 namespace {
 
@@ -17,8 +19,8 @@ size_t up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // where the pieces of a call lie in its workspace (byte offsets)
 struct MiLayout {
-    size_t ev, slots, nact, M, keys, tkeys, tmap, warped, counts, smooth_a, smooth_b, part, rowsum, colpart, values, cand, state,
-        opts, tinit, live, total;
+    size_t ev, slots, nact, M, keys, tkeys, tmap, warped, counts, smooth_a, smooth_b, part, rowsum, colpart, values, cand, candp,
+        state, opts, tinit, live, total;
 };
 
 MiLayout mi_layout(long long E, long long B, long long S, long long H, long long W, long long max_bins, bool smoothing)
@@ -43,6 +45,7 @@ MiLayout mi_layout(long long E, long long B, long long S, long long H, long long
     l.colpart = take((size_t)E * MI_PARTS * 512 * 8);
     l.values = take((size_t)E * 8);
     l.cand = take((size_t)E * 72);
+    l.candp = take((size_t)E * MI_PARAMS_MAX * 8);
     l.state = take(P * sizeof(MiNmState));
     l.opts = take(P * sizeof(MiNmOptions));
     l.tinit = take(P * 72);
@@ -121,7 +124,59 @@ void refine_iteration(const MiRefine& r, int* live, hipStream_t s)
 {
     launch_mi_histograms(r.L, r.counts, r.warped, nullptr, 0, s);
     launch_mi_score(r.L, r.counts, r.sigma, r.normalized, r.reg_init, MI_SLOTS, r.smooth_stride, r.smooth_a, r.smooth_b, r.values, s);
-    launch_mi_nm_decide(r.state, r.P, r.cand, r.values, r.nact, live, s);
+    launch_mi_nm_decide(r.state, r.model, r.P, r.candp, r.cand, r.values, r.nact, live, s);
+}
+
+// mp_mi_refine_begin and mp_mi_refine_begin_model: `start` device double [n_problems][n], the start parameters of `model`
+int mi_refine_begin(mp_handle* h, const std::string& fn, const float* optical, int Ho, int Wo, const float* thermal, int H, int W,
+                    int n_pairs, const mp_mi_problem* problems, const double* start, int n_problems, double sigma, int normalized,
+                    int regularize, int model, void* workspace, long long workspace_bytes, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    h->mi = MiRefine{};
+    if (mi_model_params(model) == 0)
+        return fail(h, MP_EINVAL, fn + ": unknown model " + std::to_string(model) +
+                                      " (MP_MODEL_HOMOGRAPHY, MP_MODEL_SIMILARITY or MP_MODEL_AFFINE)");
+    if (!problems || !start) return fail(h, MP_EINVAL, fn + ": NULL tensor");
+    if (n_problems <= 0 || n_problems > 65535 / MI_SLOTS)
+        return fail(h, MP_EINVAL, fn + ": need 0 < n_problems <= " + std::to_string(65535 / MI_SLOTS));
+    int rc = sigma_check(h, fn, sigma);
+    if (rc != MP_OK) return rc;
+    const int P = n_problems, E = P * MI_SLOTS;
+    std::vector<int> pair((size_t)E), bins((size_t)E);
+    std::vector<MiNmOptions> opts((size_t)P);
+    for (int q = 0; q < P; ++q) {
+        const mp_mi_problem& pr = problems[q];
+        if (pr.maxiter < 1 || pr.maxfun < 1 || !(pr.xatol >= 0.0) || !(pr.fatol >= 0.0))
+            return fail(h, MP_EINVAL, fn + ": maxiter and maxfun must be positive, xatol and fatol non-negative");
+        for (int v = 0; v < MI_SLOTS; ++v) { pair[q * MI_SLOTS + v] = pr.pair; bins[q * MI_SLOTS + v] = pr.bins; }
+        opts[q] = MiNmOptions{pr.maxiter, pr.maxfun, pr.xatol, pr.fatol};
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    MiCall c;
+    rc = mi_stage(h, fn, optical, Ho, Wo, thermal, H, W, n_pairs, pair.data(), bins.data(), E, MI_SLOTS, false, sigma > 0.0,
+                  workspace, workspace_bytes, s, c);
+    if (rc != MP_OK) return rc;
+    MiRefine r;
+    r.workspace = workspace;
+    r.L = c.L;
+    r.P = P; r.normalized = normalized != 0; r.model = model; r.sigma = sigma; r.smooth_stride = c.stride;
+    r.counts = c.at<unsigned>(c.lay.counts);
+    r.warped = c.at<float>(c.lay.warped);
+    r.smooth_a = c.at<double>(c.lay.smooth_a); r.smooth_b = c.at<double>(c.lay.smooth_b);
+    r.candp = c.at<double>(c.lay.candp); r.cand = c.at<double>(c.lay.cand); r.values = c.at<double>(c.lay.values);
+    r.state = c.at<MiNmState>(c.lay.state);
+    r.nact = c.at<int>(c.lay.nact);
+    r.L.T = r.cand;
+    r.L.nact = r.nact;
+    // the matrices of the problems' start parameters are kept in the workspace: the regulariser reads them at every evaluation
+    double* init = c.at<double>(c.lay.tinit);
+    MP_HIP(hipMemcpyAsync(c.ws + c.lay.opts, opts.data(), opts.size() * sizeof(MiNmOptions), hipMemcpyHostToDevice, s));
+    launch_mi_nm_begin(r.state, c.at<MiNmOptions>(c.lay.opts), model, start, P, r.candp, r.cand, init, r.nact, s);
+    MP_HIP(hipStreamSynchronize(s));
+    r.reg_init = regularize ? init : nullptr;
+    h->mi = r;
+    return launch_status(h);
 }
 
 }  // namespace
@@ -186,49 +241,20 @@ int mp_mi_refine_begin(mp_handle* h, const float* optical, int Ho, int Wo, const
                        const mp_mi_problem* problems, const double* init_transforms, int n_problems, double sigma,
                        int normalized, int regularize, void* workspace, long long workspace_bytes, void* stream)
 {
+    return mi_refine_begin(h, "mp_mi_refine_begin", optical, Ho, Wo, thermal, H, W, n_pairs, problems, init_transforms, n_problems,
+                           sigma, normalized, regularize, MP_MODEL_HOMOGRAPHY, workspace, workspace_bytes, stream);
+}
+
+int mp_mi_refine_begin_model(mp_handle* h, const float* optical, int Ho, int Wo, const float* thermal, int H, int W, int n_pairs,
+                             const mp_mi_problem* problems, const double* init_transforms, int n_problems, double sigma,
+                             int normalized, int regularize, void* workspace, long long workspace_bytes, void* stream, int model,
+                             const double* init_params)
+{
     if (!h) return MP_EINVAL;
-    h->mi = MiRefine{};
-    if (!problems || !init_transforms) return fail(h, MP_EINVAL, "mp_mi_refine_begin: NULL tensor");
-    if (n_problems <= 0 || n_problems > 65535 / MI_SLOTS)
-        return fail(h, MP_EINVAL, "mp_mi_refine_begin: need 0 < n_problems <= " + std::to_string(65535 / MI_SLOTS));
-    int rc = sigma_check(h, "mp_mi_refine_begin", sigma);
-    if (rc != MP_OK) return rc;
-    const int P = n_problems, E = P * MI_SLOTS;
-    std::vector<int> pair((size_t)E), bins((size_t)E);
-    std::vector<MiNmOptions> opts((size_t)P);
-    for (int q = 0; q < P; ++q) {
-        const mp_mi_problem& pr = problems[q];
-        if (pr.maxiter < 1 || pr.maxfun < 1 || !(pr.xatol >= 0.0) || !(pr.fatol >= 0.0))
-            return fail(h, MP_EINVAL, "mp_mi_refine_begin: maxiter and maxfun must be positive, xatol and fatol non-negative");
-        for (int v = 0; v < MI_SLOTS; ++v) { pair[q * MI_SLOTS + v] = pr.pair; bins[q * MI_SLOTS + v] = pr.bins; }
-        opts[q] = MiNmOptions{pr.maxiter, pr.maxfun, pr.xatol, pr.fatol};
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    MiCall c;
-    rc = mi_stage(h, "mp_mi_refine_begin", optical, Ho, Wo, thermal, H, W, n_pairs, pair.data(), bins.data(), E, MI_SLOTS, false,
-                  sigma > 0.0, workspace, workspace_bytes, s, c);
-    if (rc != MP_OK) return rc;
-    MiRefine r;
-    r.workspace = workspace;
-    r.L = c.L;
-    r.P = P; r.normalized = normalized != 0; r.sigma = sigma; r.smooth_stride = c.stride;
-    r.counts = c.at<unsigned>(c.lay.counts);
-    r.warped = c.at<float>(c.lay.warped);
-    r.smooth_a = c.at<double>(c.lay.smooth_a); r.smooth_b = c.at<double>(c.lay.smooth_b);
-    r.cand = c.at<double>(c.lay.cand); r.values = c.at<double>(c.lay.values);
-    r.state = c.at<MiNmState>(c.lay.state);
-    r.nact = c.at<int>(c.lay.nact);
-    r.L.T = r.cand;
-    r.L.nact = r.nact;
-    // the problems' initial transforms are kept in the workspace: the regulariser reads them at every evaluation
-    double* init = c.at<double>(c.lay.tinit);
-    MP_HIP(hipMemcpyAsync(init, init_transforms, (size_t)P * 72, hipMemcpyDeviceToDevice, s));
-    MP_HIP(hipMemcpyAsync(c.ws + c.lay.opts, opts.data(), opts.size() * sizeof(MiNmOptions), hipMemcpyHostToDevice, s));
-    launch_mi_nm_begin(r.state, c.at<MiNmOptions>(c.lay.opts), init, P, r.cand, r.nact, s);
-    MP_HIP(hipStreamSynchronize(s));
-    r.reg_init = regularize ? init : nullptr;
-    h->mi = r;
-    return launch_status(h);
+    // the homography's parameters are the matrix entries: its caller may hand them in either argument
+    const double* start = init_params ? init_params : (model == MP_MODEL_HOMOGRAPHY ? init_transforms : nullptr);
+    return mi_refine_begin(h, "mp_mi_refine_begin_model", optical, Ho, Wo, thermal, H, W, n_pairs, problems, start, n_problems,
+                           sigma, normalized, regularize, model, workspace, workspace_bytes, stream);
 }
 
 int mp_mi_refine_step(mp_handle* h, void* workspace, int n_iters, int* live, void* stream)
@@ -253,8 +279,35 @@ int mp_mi_refine_result(mp_handle* h, void* workspace, double* transforms, doubl
     if (!h->mi.workspace || h->mi.workspace != workspace)
         return fail(h, MP_ESTATE, "mp_mi_refine_result: no refinement was begun in this workspace");
     MP_HIP(hipSetDevice(h->device));
-    launch_mi_nm_result(h->mi.state, h->mi.P, transforms, values, iterations, function_calls, success,
+    launch_mi_nm_result(h->mi.state, h->mi.model, h->mi.P, transforms, nullptr, values, iterations, function_calls, success,
                         static_cast<hipStream_t>(stream));
+    return launch_status(h);
+}
+
+int mp_mi_refine_result_model(mp_handle* h, void* workspace, double* transforms, double* values, int* iterations,
+                              int* function_calls, int* success, void* stream, double* params)
+{
+    if (!h) return MP_EINVAL;
+    if (!workspace || !transforms || !values || !iterations || !function_calls || !success || !params)
+        return fail(h, MP_EINVAL, "mp_mi_refine_result_model: NULL tensor");
+    if (!h->mi.workspace || h->mi.workspace != workspace)
+        return fail(h, MP_ESTATE, "mp_mi_refine_result_model: no refinement was begun in this workspace");
+    MP_HIP(hipSetDevice(h->device));
+    launch_mi_nm_result(h->mi.state, h->mi.model, h->mi.P, transforms, params, values, iterations, function_calls, success,
+                        static_cast<hipStream_t>(stream));
+    return launch_status(h);
+}
+
+int mp_mi_model_transform(mp_handle* h, int model, const double* params, int n_rows, double* transforms, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (mi_model_params(model) == 0)
+        return fail(h, MP_EINVAL, "mp_mi_model_transform: unknown model " + std::to_string(model) +
+                                      " (MP_MODEL_HOMOGRAPHY, MP_MODEL_SIMILARITY or MP_MODEL_AFFINE)");
+    if (!params || !transforms) return fail(h, MP_EINVAL, "mp_mi_model_transform: NULL tensor");
+    if (n_rows <= 0) return fail(h, MP_EINVAL, "mp_mi_model_transform: n_rows must be positive");
+    MP_HIP(hipSetDevice(h->device));
+    launch_mi_model_transform(model, params, n_rows, transforms, static_cast<hipStream_t>(stream));
     return launch_status(h);
 }
 

@@ -96,12 +96,13 @@ struct MiRefine {
     void* workspace = nullptr;
     MiLaunch L{};
     int P = 0, normalized = 0;
+    int model = 0;                        // MP_MODEL_*: what the candidate points in candp parametrise
     double sigma = 0.0;
     long long smooth_stride = 0;
     unsigned* counts = nullptr;
     float* warped = nullptr;
-    double *smooth_a = nullptr, *smooth_b = nullptr, *cand = nullptr, *values = nullptr;
-    const double* reg_init = nullptr;     // the problems' initial transforms when the objective is regularised
+    double *smooth_a = nullptr, *smooth_b = nullptr, *candp = nullptr, *cand = nullptr, *values = nullptr;
+    const double* reg_init = nullptr;     // the matrices of the problems' start parameters when the objective is regularised
     MiNmState* state = nullptr;
     int* nact = nullptr;
 };

@@ -527,11 +527,13 @@ void launch_photometric_shade_mask(int n, int H, int W, const mp_photometric_pla
 // ---------------------------------------------------------------------------------------------
 #define MI_PARTS 16            // row blocks of the score's first pass
 #define MI_MAX_RADIUS 64       // of the smoothing kernel: int(4 sigma + 0.5)
-#define MI_SLOTS 10            // candidate slots of a Nelder-Mead problem: the 9 + 1 vertices of its simplex
+#define MI_SLOTS 10            // candidate slots of a Nelder-Mead problem: the 9 + 1 vertices of its largest simplex
+#define MI_PARAMS_MAX 9        // parameters of the largest motion model (the homography's nine entries)
 struct MiEval { int pair, bins, tslot, pad; long long off; };
 struct MiNmOptions { int maxiter, maxfun; double xatol, fatol; };
+// a simplex of n + 1 vertices over the n parameters of the refinement's motion model: rows and columns beyond stay unused
 struct MiNmState {
-    double sim[MI_SLOTS][9], fsim[MI_SLOTS];
+    double sim[MI_SLOTS][MI_PARAMS_MAX], fsim[MI_SLOTS];
     MiNmOptions opt;
     int iterations, fcalls, phase, done, status, pad;
 };
@@ -555,11 +557,20 @@ void launch_mi_histograms(const MiLaunch& L, unsigned* counts, float* warped, fl
 // values [E] = -MI (+ |Tinit[e / tg] - T[e]|_F when Tinit); smooth_a / smooth_b [E][smooth_stride] doubles when sigma > 0
 void launch_mi_score(const MiLaunch& L, const unsigned* counts, double sigma, int normalized, const double* Tinit, int tg,
                      long long smooth_stride, double* smooth_a, double* smooth_b, double* values, hipStream_t s);
-void launch_mi_nm_begin(MiNmState* state, const MiNmOptions* opt, const double* Tinit, int P, double* cand, int* nact,
-                        hipStream_t s);
-void launch_mi_nm_decide(MiNmState* state, int P, double* cand, const double* values, int* nact, int* live, hipStream_t s);
-void launch_mi_nm_result(const MiNmState* state, int P, double* T, double* value, int* iterations, int* fcalls, int* success,
-                         hipStream_t s);
+// The motion model of a refinement (MP_MODEL_*): n parameters per point (mi_model_params: 9, 4 or 6; 0 for an unknown
+// model) and the map from a parameter vector to the 3x3 matrix the objective reads.  A problem's candidate points lie in
+// candp [P][MI_SLOTS][MI_PARAMS_MAX] (n used per row); their matrices in cand [P][MI_SLOTS][9], which is MiLaunch::T.
+int mi_model_params(int model);
+// transforms [rows][9] = map(params [rows][n])
+void launch_mi_model_transform(int model, const double* params, int rows, double* transforms, hipStream_t s);
+// x0 [P][n]: the start parameters; tinit [P][9] receives their matrices (what the regulariser measures from)
+void launch_mi_nm_begin(MiNmState* state, const MiNmOptions* opt, int model, const double* x0, int P, double* candp, double* cand,
+                        double* tinit, int* nact, hipStream_t s);
+void launch_mi_nm_decide(MiNmState* state, int model, int P, double* candp, double* cand, const double* values, int* nact,
+                         int* live, hipStream_t s);
+// T [P][9]: the matrix of the best vertex; params [P][n]: the vertex itself, or NULL
+void launch_mi_nm_result(const MiNmState* state, int model, int P, double* T, double* params, double* value, int* iterations,
+                         int* fcalls, int* success, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // 2-D FFT (fft.hip) and the LGHD baseline (lghd.hip; reference multipoint/models/ClassicDetectors.py, class LGHD).

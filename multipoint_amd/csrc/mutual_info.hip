@@ -19,7 +19,9 @@
 //  * partial_kernel      per block of rows: sum x log x, the row sums, the block's column sums  (x = count + 2^-52)
 //  * final_kernel        S, sum r log r, sum c log c -> the score (see below), negated, plus |T_init - T|_F
 //  * nm_begin / nm_decide / nm_result   scipy's Nelder-Mead, one thread per problem, on the values the kernels above
-//                        wrote for the problem's candidate points
+//                        wrote for the problem's candidate points: over the n parameters of a motion model (9 matrix
+//                        entries, 4 of a similarity, 6 of an affine transform), mapped to matrices by model_matrix
+//  * model_transform_kernel             that map alone
 //
 // The score without a second pass over the histogram: with x the un-normalised entries and S their sum,
 //     sum (x/S) log (x/S) = (sum x log x) / S - log S,
@@ -29,6 +31,7 @@
 // step = (b - a) / n, e[i] = fl(fl(i * step) + a), e[n] = b; bin = (number of edges <= v) - 1, v == e[n] in bin n - 1.
 // The bin is guessed by a multiply and a truncation and then walked to where the edges put it.
 #include "mp_common.h"
+#include "../../include/multipoint_hip.h"
 
 namespace {
 
@@ -377,13 +380,49 @@ __global__ __launch_bounds__(256) void final_kernel(const MiEval* __restrict__ e
     values[e] = v;
 }
 
+// ---- the motion model: n parameters -> the 3x3 matrix the objective reads (MP_MODEL_*; no clamping, as in the reference) ----
+//   homography  the nine entries
+//   similarity  (angle, scale, dx, dy) -> [[s cos a, s sin a, dx], [-s sin a, s cos a, dy], [0, 0, 1]]  (align.py:137-139)
+//   affine      the six entries of the top two rows, last row (0, 0, 1)
+__device__ __forceinline__ int model_params(int model)
+{
+    return model == MP_MODEL_SIMILARITY ? 4 : (model == MP_MODEL_AFFINE ? 6 : 9);
+}
+
+__device__ __forceinline__ void model_matrix(int model, const double* __restrict__ p, double* __restrict__ t)
+{
+#pragma clang fp contract(off)
+    if (model == MP_MODEL_SIMILARITY) {
+        const double c = p[1] * cos(p[0]), s = p[1] * sin(p[0]);
+        t[0] = c; t[1] = s; t[2] = p[2];
+        t[3] = -s; t[4] = c; t[5] = p[3];
+        t[6] = 0.0; t[7] = 0.0; t[8] = 1.0;
+    } else if (model == MP_MODEL_AFFINE) {
+        for (int k = 0; k < 6; ++k) t[k] = p[k];
+        t[6] = 0.0; t[7] = 0.0; t[8] = 1.0;
+    } else {
+        for (int k = 0; k < 9; ++k) t[k] = p[k];
+    }
+}
+
+__global__ __launch_bounds__(64) void model_transform_kernel(int model, const double* __restrict__ params, int rows,
+                                                             double* __restrict__ T)
+{
+    const int r = blockIdx.x * 64 + threadIdx.x;
+    if (r >= rows) return;
+    model_matrix(model, params + (size_t)r * model_params(model), T + (size_t)r * 9);
+}
+
 // ---- Nelder-Mead (scipy.optimize._optimize._minimize_neldermead, adaptive=False, no bounds), one thread per problem ----
+// over the ND parameters of the motion model with a simplex of NV = ND + 1 vertices.  A problem's candidate points are rows
+// of MI_PARAMS_MAX doubles in candp; nm_emit turns the first `count` of them into the matrices of its evaluation slots.
 enum { NM_INIT = 0, NM_STEP = 1, NM_SHRINK = 2 };
-constexpr int NV = 10, ND = 9;
+constexpr int CS = MI_PARAMS_MAX;      // stride of a candidate point
 
 // stable insertion sort of the simplex by value (scipy: np.argsort + np.take; ties keep their order here)
-__device__ void nm_sort(MiNmState& st)
+__device__ void nm_sort(MiNmState& st, int ND)
 {
+    const int NV = ND + 1;
     for (int i = 1; i < NV; ++i) {
         for (int j = i; j > 0 && st.fsim[j] < st.fsim[j - 1]; --j) {
             const double f = st.fsim[j]; st.fsim[j] = st.fsim[j - 1]; st.fsim[j - 1] = f;
@@ -394,37 +433,47 @@ __device__ void nm_sort(MiNmState& st)
     }
 }
 
-__device__ __forceinline__ void nm_take(MiNmState& st, const double* x, double f)
+__device__ __forceinline__ void nm_take(MiNmState& st, int ND, const double* x, double f)
 {
-    for (int k = 0; k < ND; ++k) st.sim[NV - 1][k] = x[k];
-    st.fsim[NV - 1] = f;
+    for (int k = 0; k < ND; ++k) st.sim[ND][k] = x[k];
+    st.fsim[ND] = f;
 }
 
-// one thread per problem: the initial simplex into the problem's candidate slots
+__device__ __forceinline__ void nm_emit(int model, const double* c, int count, double* T)
+{
+    for (int v = 0; v < count; ++v) model_matrix(model, c + v * CS, T + v * 9);
+}
+
+// one thread per problem: the initial simplex into the problem's candidate slots, the start's matrix into tinit
 __global__ __launch_bounds__(64) void nm_begin_kernel(MiNmState* __restrict__ state, const MiNmOptions* __restrict__ opt,
-                                                      const double* __restrict__ Tinit, int P, double* __restrict__ cand,
-                                                      int* __restrict__ nact)
+                                                      int model, const double* __restrict__ start, int P,
+                                                      double* __restrict__ candp, double* __restrict__ cand,
+                                                      double* __restrict__ tinit, int* __restrict__ nact)
 {
 #pragma clang fp contract(off)
     const int q = blockIdx.x * 64 + threadIdx.x;
     if (q >= P) return;
+    const int ND = model_params(model), NV = ND + 1;
     MiNmState& st = state[q];
-    const double* x0 = Tinit + (size_t)q * 9;
-    double* c = cand + (size_t)q * NV * ND;
+    const double* x0 = start + (size_t)q * ND;
+    double* c = candp + (size_t)q * MI_SLOTS * CS;
     for (int v = 0; v < NV; ++v)
         for (int k = 0; k < ND; ++k) {
             double y = x0[k];
             if (v == k + 1) y = y != 0.0 ? (1.0 + 0.05) * y : 0.00025;
-            c[v * ND + k] = y;
+            c[v * CS + k] = y;
             st.sim[v][k] = y;
         }
+    nm_emit(model, c, NV, cand + (size_t)q * MI_SLOTS * 9);
+    model_matrix(model, c, tinit + (size_t)q * 9);
     st.opt = opt[q];
     st.iterations = 0; st.fcalls = 0; st.phase = NM_INIT; st.done = 0; st.status = 0;
     nact[q] = NV;
 }
 
 // consumes the values of the problem's candidate slots, applies scipy's rules and writes the next candidates
-__global__ __launch_bounds__(64) void nm_decide_kernel(MiNmState* __restrict__ state, int P, double* __restrict__ cand,
+__global__ __launch_bounds__(64) void nm_decide_kernel(MiNmState* __restrict__ state, int model, int P,
+                                                       double* __restrict__ candp, double* __restrict__ cand,
                                                        const double* __restrict__ fc, int* __restrict__ nact,
                                                        int* __restrict__ live)
 {
@@ -433,8 +482,10 @@ __global__ __launch_bounds__(64) void nm_decide_kernel(MiNmState* __restrict__ s
     if (q >= P) return;
     MiNmState& st = state[q];
     if (st.done) return;
-    double* c = cand + (size_t)q * NV * ND;
-    const double* f = fc + (size_t)q * NV;
+    const int ND = model_params(model), NV = ND + 1;
+    double* c = candp + (size_t)q * MI_SLOTS * CS;
+    double* T = cand + (size_t)q * MI_SLOTS * 9;
+    const double* f = fc + (size_t)q * MI_SLOTS;
     const int maxfun = st.opt.maxfun;
     // func(): scipy's wrapper refuses the call (and the iteration ends uncounted) once maxfun calls were made
     auto call = [&]() { if (st.fcalls >= maxfun) return false; ++st.fcalls; return true; };
@@ -449,23 +500,23 @@ __global__ __launch_bounds__(64) void nm_decide_kernel(MiNmState* __restrict__ s
         if (ok) {
             if (fxr < st.fsim[0]) {
                 ok = call();
-                if (ok) { if (f[1] < fxr) nm_take(st, c + ND, f[1]); else nm_take(st, c, fxr); }
+                if (ok) { if (f[1] < fxr) nm_take(st, ND, c + CS, f[1]); else nm_take(st, ND, c, fxr); }
             } else if (fxr < st.fsim[NV - 2]) {
-                nm_take(st, c, fxr);
+                nm_take(st, ND, c, fxr);
             } else if (fxr < st.fsim[NV - 1]) {
                 ok = call();
-                if (ok) { if (f[2] <= fxr) nm_take(st, c + 2 * ND, f[2]); else shrink = true; }
+                if (ok) { if (f[2] <= fxr) nm_take(st, ND, c + 2 * CS, f[2]); else shrink = true; }
             } else {
                 ok = call();
-                if (ok) { if (f[3] < st.fsim[NV - 1]) nm_take(st, c + 3 * ND, f[3]); else shrink = true; }
+                if (ok) { if (f[3] < st.fsim[NV - 1]) nm_take(st, ND, c + 3 * CS, f[3]); else shrink = true; }
             }
         }
         if (ok && !shrink) ++st.iterations;
     } else {
-        // the shrunk vertices 1 .. 9 in the candidate slots 0 .. 8: vertex j moves before its value is asked for
+        // the shrunk vertices 1 .. ND in the candidate slots 0 .. ND - 1: vertex j moves before its value is asked for
         bool ok = true;
         for (int j = 1; j < NV && ok; ++j) {
-            for (int k = 0; k < ND; ++k) st.sim[j][k] = c[(j - 1) * ND + k];
+            for (int k = 0; k < ND; ++k) st.sim[j][k] = c[(j - 1) * CS + k];
             ok = call();
             if (ok) st.fsim[j] = f[j - 1];
         }
@@ -473,13 +524,14 @@ __global__ __launch_bounds__(64) void nm_decide_kernel(MiNmState* __restrict__ s
     }
     if (shrink) {
         for (int j = 1; j < NV; ++j)
-            for (int k = 0; k < ND; ++k) c[(j - 1) * ND + k] = st.sim[0][k] + 0.5 * (st.sim[j][k] - st.sim[0][k]);
+            for (int k = 0; k < ND; ++k) c[(j - 1) * CS + k] = st.sim[0][k] + 0.5 * (st.sim[j][k] - st.sim[0][k]);
+        nm_emit(model, c, NV - 1, T);
         st.phase = NM_SHRINK;
         nact[q] = NV - 1;
         atomicAdd(live, 1);
         return;
     }
-    nm_sort(st);
+    nm_sort(st, ND);
     bool go = st.fcalls < maxfun && st.iterations < st.opt.maxiter;
     if (go) {
         double dx = 0.0, df = 0.0;
@@ -498,27 +550,32 @@ __global__ __launch_bounds__(64) void nm_decide_kernel(MiNmState* __restrict__ s
     for (int k = 0; k < ND; ++k) {
         double xbar = st.sim[0][k];
         for (int j = 1; j < NV - 1; ++j) xbar = xbar + st.sim[j][k];
-        xbar = xbar / 9.0;
+        xbar = xbar / (double)ND;
         const double last = st.sim[NV - 1][k];
         c[k] = 2.0 * xbar - 1.0 * last;
-        c[ND + k] = 3.0 * xbar - 2.0 * last;
-        c[2 * ND + k] = 1.5 * xbar - 0.5 * last;
-        c[3 * ND + k] = 0.5 * xbar + 0.5 * last;
+        c[CS + k] = 3.0 * xbar - 2.0 * last;
+        c[2 * CS + k] = 1.5 * xbar - 0.5 * last;
+        c[3 * CS + k] = 0.5 * xbar + 0.5 * last;
     }
+    nm_emit(model, c, 4, T);
     st.phase = NM_STEP;
     nact[q] = 4;
     atomicAdd(live, 1);
 }
 
-__global__ __launch_bounds__(64) void nm_result_kernel(const MiNmState* __restrict__ state, int P, double* __restrict__ T,
+__global__ __launch_bounds__(64) void nm_result_kernel(const MiNmState* __restrict__ state, int model, int P,
+                                                       double* __restrict__ T, double* __restrict__ params,
                                                        double* __restrict__ value, int* __restrict__ iterations,
                                                        int* __restrict__ fcalls, int* __restrict__ success)
 {
     const int q = blockIdx.x * 64 + threadIdx.x;
     if (q >= P) return;
     const MiNmState& st = state[q];
+    const int ND = model_params(model);
     // (a problem still running reports the best vertex of its latest sort and success 0)
-    for (int k = 0; k < ND; ++k) T[(size_t)q * 9 + k] = st.sim[0][k];
+    model_matrix(model, st.sim[0], T + (size_t)q * 9);
+    if (params)
+        for (int k = 0; k < ND; ++k) params[(size_t)q * ND + k] = st.sim[0][k];
     value[q] = st.fsim[0];
     iterations[q] = st.iterations;
     fcalls[q] = st.fcalls;
@@ -568,20 +625,31 @@ void launch_mi_score(const MiLaunch& L, const unsigned* counts, double sigma, in
     final_kernel<<<L.E, 256, 0, s>>>(L.ev, L.nact, L.G, L.part, L.rowsum, L.colpart, normalized, L.T, Tinit, tg, values);
 }
 
-void launch_mi_nm_begin(MiNmState* state, const MiNmOptions* opt, const double* Tinit, int P, double* cand, int* nact,
-                        hipStream_t s)
+int mi_model_params(int model)
 {
-    nm_begin_kernel<<<(P + 63) / 64, 64, 0, s>>>(state, opt, Tinit, P, cand, nact);
+    return model == MP_MODEL_HOMOGRAPHY ? 9 : (model == MP_MODEL_SIMILARITY ? 4 : (model == MP_MODEL_AFFINE ? 6 : 0));
 }
 
-void launch_mi_nm_decide(MiNmState* state, int P, double* cand, const double* values, int* nact, int* live, hipStream_t s)
+void launch_mi_model_transform(int model, const double* params, int rows, double* transforms, hipStream_t s)
+{
+    model_transform_kernel<<<(rows + 63) / 64, 64, 0, s>>>(model, params, rows, transforms);
+}
+
+void launch_mi_nm_begin(MiNmState* state, const MiNmOptions* opt, int model, const double* x0, int P, double* candp, double* cand,
+                        double* tinit, int* nact, hipStream_t s)
+{
+    nm_begin_kernel<<<(P + 63) / 64, 64, 0, s>>>(state, opt, model, x0, P, candp, cand, tinit, nact);
+}
+
+void launch_mi_nm_decide(MiNmState* state, int model, int P, double* candp, double* cand, const double* values, int* nact,
+                         int* live, hipStream_t s)
 {
     (void)hipMemsetAsync(live, 0, 4, s);
-    nm_decide_kernel<<<(P + 63) / 64, 64, 0, s>>>(state, P, cand, values, nact, live);
+    nm_decide_kernel<<<(P + 63) / 64, 64, 0, s>>>(state, model, P, candp, cand, values, nact, live);
 }
 
-void launch_mi_nm_result(const MiNmState* state, int P, double* T, double* value, int* iterations, int* fcalls, int* success,
-                         hipStream_t s)
+void launch_mi_nm_result(const MiNmState* state, int model, int P, double* T, double* params, double* value, int* iterations,
+                         int* fcalls, int* success, hipStream_t s)
 {
-    nm_result_kernel<<<(P + 63) / 64, 64, 0, s>>>(state, P, T, value, iterations, fcalls, success);
+    nm_result_kernel<<<(P + 63) / 64, 64, 0, s>>>(state, model, P, T, params, value, iterations, fcalls, success);
 }

@@ -16,6 +16,11 @@ fp32 grey frame is pyramided.  Both are linear: only the 8-bit rounding of each 
 Import this module as multipoint_amd.utils.alignment: its refine_alignment is NOT the guided refine_alignment that
 multipoint_amd.utils exports.
 
+The motion model of the optimiser (extension): refine_alignment_batch(model=...) and the yaml key
+alignment/model search over the nine matrix entries ('homography', the default and the reference's perspective path), over
+(angle, scale, dx, dy) ('similarity', the reference's decomposed form) or over the six entries of the top two rows ('affine').
+Every model is a 3x3 matrix under the same perspective warp; model_parameters and model_transform go between the two forms.
+
 Not implemented (NotImplementedError): 2x3 affine transforms and `decompose_transformation` (cv2.warpAffine is another
 fixed-point path that has no restatement here), and the geometric part of check_perspective_transformation
 (cv2.decomposeHomographyMat).
@@ -26,12 +31,14 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .evaluation import decompose_similarity, transform_model
 
 __all__ = ['warp_image', 'mutual_information_2d', 'calculate_negative_mutual_information', 'refine_alignment',
            'negative_mutual_information_batch', 'refine_alignment_batch', 'align_images', 'joint_histograms',
            'rank_candidates', 'check_perspective_transformation', 'alignment_type_name', 'gaussian_blur', 'frames_to_float',
            'gaussian_weights', 'pyramid_levels', 'scale_transform', 'run_alignment_stages',
-           'align_images_mutual_information']
+           'align_images_mutual_information', 'MODEL_PARAMETERS', 'default_limit', 'model_parameters', 'model_transform',
+           'check_affine_geometry']
 
 _AFFINE = ('2x3 affine transforms are not implemented: cv2.warpAffine is a different fixed-point path than '
            'cv2.warpPerspective and has no restatement in this project')
@@ -221,13 +228,76 @@ def calculate_negative_mutual_information(transform, optical, thermal, init_tran
     return float(v.item())
 
 
+MODEL_PARAMETERS = {'homography': 9, 'similarity': 4, 'affine': 6}       # n: the simplex has n + 1 vertices
+
+
+def default_limit(model):
+    """scipy's default for maxiter and maxfun: 200 times the number of parameters of the motion model."""
+    transform_model(model)
+    return 200 * MODEL_PARAMETERS[model]
+
+
+def model_parameters(T, model):
+    """The parameter vector the optimiser searches from for a 3x3 matrix T (or (P, 3, 3) / (P, 9)) under a motion model, on
+    the host in float64: (n,) for one matrix, (P, n) for several.
+      'homography'  the nine entries as given (its scale is a parameter of its own: nothing is divided)
+      'similarity'  (angle, scale, dx, dy) of T / T[2,2] as decompose_similarity gives them: angle = arctan2(T01, T00), scale =
+                    hypot(T00, T01), dx = T02, dy = T12 -- ROW 0 and the translations; the second row is not read, so a matrix
+                    that is no similarity is projected onto one
+      'affine'      the six entries of the top two rows of T / T[2,2]
+    ValueError: an unknown model, T[2,2] == 0 or a non-finite matrix under a constrained model."""
+    transform_model(model)
+    M = _transforms(T)
+    shape = tuple(T.shape) if hasattr(T, 'shape') else np.shape(T)
+    single = len(shape) == 1 or shape == (3, 3)
+    if model == 'homography':
+        out = M.copy()
+    else:
+        if not (np.isfinite(M).all() and (M[:, 8] != 0.0).all()):
+            raise ValueError('model_parameters: need finite 3x3 matrices with T[2,2] != 0')
+        if model == 'similarity':
+            out = np.array([decompose_similarity(m.reshape(3, 3)) for m in M], np.float64).reshape(-1, 4)
+        else:
+            out = (M / M[:, 8:9])[:, :6].copy()
+    return out[0] if single else out
+
+
+def model_transform(params, model, device=None):
+    """The 3x3 matrix of a parameter vector (n,) -> (3, 3), or of (P, n) -> (P, 3, 3), as float64 numpy: computed on the
+    device by the function the optimiser's kernels use (mp_mi_model_transform).
+      'similarity'  [[s cos a, s sin a, dx], [-s sin a, s cos a, dy], [0, 0, 1]] (utils.compose_similarity)
+      'affine'      the six entries over the row (0, 0, 1);  'homography'  the nine entries
+    Parameters are mapped as they are: a negative scale or an angle beyond pi is not clamped."""
+    mid, n = transform_model(model), MODEL_PARAMETERS[model]
+    p = params.detach().cpu().numpy() if isinstance(params, torch.Tensor) else params
+    p = np.asarray(p, np.float64)
+    if p.ndim not in (1, 2) or p.shape[-1] != n:
+        raise ValueError('%s parameters must be (%d,) or (P, %d), got %s' % (model, n, n, p.shape))
+    rows = np.ascontiguousarray(p.reshape(-1, n))
+    dev = _lib.require_cuda(device)
+    if rows.shape[0] == 0:
+        return np.zeros((0, 3, 3))
+    h = _lib.get_handle(dev)
+    pd = torch.from_numpy(rows).to(dev)
+    out = torch.empty((rows.shape[0], 9), dtype=torch.float64, device=dev)
+    h.check(h.lib.mp_mi_model_transform(h.ptr, mid, _lib.ptr(pd), rows.shape[0], _lib.ptr(out), _lib.stream_ptr(dev)))
+    out = out.cpu().numpy().reshape(-1, 3, 3)
+    return out[0] if p.ndim == 1 else out
+
+
 def refine_alignment_batch(optical, thermal, pair_index, bins, init_transforms, regularize=False, normalized_mi=False,
-                           smoothing_sigma=0, xatol=1e-6, fatol=1e-6, maxiter=None, maxfun=None, chunk=32):
+                           smoothing_sigma=0, xatol=1e-6, fatol=1e-6, maxiter=None, maxfun=None, chunk=32, model='homography'):
     """Nelder-Mead maximisation of the mutual information for a batch of problems (pair_index[q], bins[q],
     init_transforms[q]) as scipy runs it for the reference (align.py:202-207).  xatol, fatol, maxiter, maxfun: scalars or one
-    value per problem (None: scipy's 200 * 9).  The iterations are enqueued `chunk` at a time; between chunks one integer, the
-    number of problems still running, is read back.  Returns dict(transform (P, 3, 3), value (P,), nit, nfev, success) of
-    numpy arrays, plus 'rounds', the number of objective launches that were enqueued (a multiple of `chunk`)."""
+    value per problem (None: scipy's 200 * n).  The iterations are enqueued `chunk` at a time; between chunks one integer, the
+    number of problems still running, is read back.
+    model: what the simplex moves over -- the n = 9 entries of the matrix ('homography'), n = 4 (angle, scale, dx, dy)
+    ('similarity') or the n = 6 entries of the top two rows ('affine'); the start is model_parameters(init_transforms, model),
+    and with `regularize` the distance is measured from the matrix of that start.
+    Returns dict(transform (P, 3, 3), params (P, n), value (P,), nit, nfev, success) of numpy arrays -- params the best
+    vertex, transform its matrix -- plus 'rounds', the number of objective launches that were enqueued (a multiple of
+    `chunk`)."""
+    mid, n = transform_model(model), MODEL_PARAMETERS[model]
     T = _transforms(init_transforms)
     P = T.shape[0]
     pair, bins = [int(p) for p in pair_index], [int(b) for b in bins]
@@ -238,17 +308,17 @@ def refine_alignment_batch(optical, thermal, pair_index, bins, init_transforms, 
         v = default if v is None else v
         return [v] * P if np.ndim(v) == 0 else list(v)
     if maxiter is None and maxfun is None:
-        maxiter = maxfun = 200 * 9
+        maxiter = maxfun = default_limit(model)
     big = 2 ** 31 - 1
     it, fn, xa, fa = per(maxiter, big), per(maxfun, big), per(xatol, 1e-6), per(fatol, 1e-6)
     S = _lib.MP_MI_SLOTS
     c = _Call(optical, thermal, pair, bins, n_evals=S * P, smoothing=smoothing_sigma > 0)
     problems = (_lib.MiProblem * P)(*[_lib.MiProblem(pair[q], bins[q], int(min(it[q], big)), int(min(fn[q], big)),
                                                      float(xa[q]), float(fa[q])) for q in range(P)])
-    Td = torch.from_numpy(T).to(c.dev)
+    Xd = torch.from_numpy(np.ascontiguousarray(model_parameters(T, model).reshape(P, n))).to(c.dev)
     lib = c.h.lib
-    c.h.check(lib.mp_mi_refine_begin(*c.head(), problems, _lib.ptr(Td), P, float(smoothing_sigma), int(bool(normalized_mi)),
-                                     int(bool(regularize)), *c.tail()))
+    c.h.check(lib.mp_mi_refine_begin_model(*c.head(), problems, None, P, float(smoothing_sigma), int(bool(normalized_mi)),
+                                           int(bool(regularize)), *c.tail(), mid, _lib.ptr(Xd)))
     live = torch.zeros(1, dtype=torch.int32, device=c.dev)
     rounds = 0
     while True:
@@ -257,12 +327,13 @@ def refine_alignment_batch(optical, thermal, pair_index, bins, init_transforms, 
         if int(live.item()) == 0:
             break
     out_T = torch.empty((P, 9), dtype=torch.float64, device=c.dev)
+    out_X = torch.empty((P, n), dtype=torch.float64, device=c.dev)
     value = torch.empty(P, dtype=torch.float64, device=c.dev)
     nit, nfev, ok = (torch.empty(P, dtype=torch.int32, device=c.dev) for _ in range(3))
-    c.h.check(lib.mp_mi_refine_result(c.h.ptr, _lib.ptr(c.workspace), _lib.ptr(out_T), _lib.ptr(value), _lib.ptr(nit),
-                                      _lib.ptr(nfev), _lib.ptr(ok), c.stream))
-    return {'transform': out_T.cpu().numpy().reshape(P, 3, 3), 'value': value.cpu().numpy(), 'nit': nit.cpu().numpy(),
-            'nfev': nfev.cpu().numpy(), 'success': ok.cpu().numpy().astype(bool), 'rounds': rounds}
+    c.h.check(lib.mp_mi_refine_result_model(c.h.ptr, _lib.ptr(c.workspace), _lib.ptr(out_T), _lib.ptr(value), _lib.ptr(nit),
+                                            _lib.ptr(nfev), _lib.ptr(ok), c.stream, _lib.ptr(out_X)))
+    return {'transform': out_T.cpu().numpy().reshape(P, 3, 3), 'params': out_X.cpu().numpy(), 'value': value.cpu().numpy(),
+            'nit': nit.cpu().numpy(), 'nfev': nfev.cpu().numpy(), 'success': ok.cpu().numpy().astype(bool), 'rounds': rounds}
 
 
 def refine_alignment(optical, thermal, init_transform, decompose_transformation, regularize, bins=256, normalized_mi=False,
@@ -282,9 +353,42 @@ def check_perspective_transformation(*args, **kwargs):
                               'project; align_images applies the mutual-information check only')
 
 
-def alignment_type_name(bins, normalized_mi, smoothing_sigma):
-    """wrapper_refine_alignement's name of a perspective alignment (align.py:249-259)."""
-    return 'bin' + str(bins) + ('_normalized' if normalized_mi else '') + '_s' + str(smoothing_sigma)
+AFFINE_CHECK_KEYS = ('alignment/check/both/max_diff_dx', 'alignment/check/both/max_diff_dy',
+                     'alignment/check/affine/max_diff_scale', 'alignment/check/affine/max_diff_rotation',
+                     'alignment/check/affine/max_diff_shear')
+
+
+def check_affine_geometry(init_transformation, transformation, params):
+    """The geometric part of the reference's check_affine_transformation (align.py:391-404, :423-429) on the top two rows of
+    two 3x3 matrices with last row (0, 0, 1) (each divided by its [2,2] first), in numpy float64: |d dx|, |d dy| below
+    alignment/check/both/max_diff_dx, .../max_diff_dy; |d s_x|, |d s_y| below alignment/check/affine/max_diff_scale; |d rot|,
+    |d shear| below .../max_diff_rotation, .../max_diff_shear (degrees), with rot = arctan2(T01, T00), shear = arctan2(T11, T10)
+    - pi / 2 - rot, s_x = sqrt(T10^2 + T00^2), s_y = sqrt(T11^2 + T01^2) cos(shear).  A missing key is a KeyError naming it.
+    Returns a bool."""
+    lim = {k: params[k] for k in AFFINE_CHECK_KEYS}
+
+    def parts(T):
+        T = np.asarray(T, np.float64).reshape(3, 3)
+        T = T / T[2, 2]
+        rot = np.arctan2(T[0, 1], T[0, 0])
+        shear = np.arctan2(T[1, 1], T[1, 0]) - np.pi * 0.5 - rot
+        s_x = np.sqrt(T[1, 0] ** 2 + T[0, 0] ** 2)
+        s_y = np.sqrt(T[1, 1] ** 2 + T[0, 1] ** 2) * np.cos(shear)
+        return rot, shear, s_x, s_y, T[0, 2], T[1, 2]
+    a, b = parts(init_transformation), parts(transformation)
+    return bool(abs(a[4] - b[4]) < lim['alignment/check/both/max_diff_dx'] and
+                abs(a[5] - b[5]) < lim['alignment/check/both/max_diff_dy'] and
+                abs(b[2] - a[2]) < lim['alignment/check/affine/max_diff_scale'] and
+                abs(b[3] - a[3]) < lim['alignment/check/affine/max_diff_scale'] and
+                abs(b[0] - a[0]) < np.radians(lim['alignment/check/affine/max_diff_rotation']) and
+                abs(b[1] - a[1]) < np.radians(lim['alignment/check/affine/max_diff_shear']))
+
+
+def alignment_type_name(bins, normalized_mi, smoothing_sigma, model=None):
+    """wrapper_refine_alignement's name of a perspective alignment (align.py:249-259); a constrained motion model
+    ('similarity', 'affine') is appended as '_<model>'."""
+    name = 'bin' + str(bins) + ('_normalized' if normalized_mi else '') + '_s' + str(smoothing_sigma)
+    return name if model in (None, 'homography') else name + '_' + str(model)
 
 
 def rank_candidates(scores, method):
@@ -374,14 +478,24 @@ def align_images(optical, thermal, init_transform, params, geometric_checks=Fals
     one objective call and ranked by alignment/ranking_method.
 
     optical (Ho, Wo) or (B, 1, Ho, Wo), thermal (H, W) or (B, 1, H, W), init_transform (3, 3) or (B, 3, 3).
+    alignment/model (extension; 'homography' by default, 'similarity', 'affine'): the motion model the optimiser searches in
+    (refine_alignment_batch); with another one than the default the candidates' types end in '_<model>'.  The 'init'
+    candidate stays the given matrix.
     geometric_checks=True asks for the rotation / translation limits of check_perspective_transformation as well, which are
-    not implemented: it raises NotImplementedError (the default applies the mutual-information check only).
+    not implemented: with the homography it raises NotImplementedError (the default applies the mutual-information check
+    only).  With a constrained model it applies check_affine_geometry -- the limits of the reference's
+    check_affine_transformation -- to every optimised candidate; a missing limit is a KeyError naming the key.
     filter_images=True blurs both frames with gaussian_blur(., alignment/filter_size) first (align.py:487-489).
     Returns (transform, type, candidates) for one pair, lists of them for a batch; transform and type are None where no
     candidate is valid.  A candidate is dict(type, transform, mi={bins: score}, value, init_value, nit, nfev).  stats: a dict
     whose 'rounds' grows by the objective launches the optimisation enqueued (refine_alignment_batch)."""
+    model = params.get('alignment/model', 'homography')
+    transform_model(model)
     if geometric_checks:
-        check_perspective_transformation()
+        if model == 'homography':
+            check_perspective_transformation()
+        for key in AFFINE_CHECK_KEYS:
+            params[key]
     if params.get('alignment/decomposed_transformation', False):
         raise NotImplementedError('alignment/decomposed_transformation: ' + _AFFINE)
     single = optical.dim() == 2
@@ -402,7 +516,7 @@ def align_images(optical, thermal, init_transform, params, geometric_checks=Fals
             cands[b].append({'type': 'init', 'transform': T0[b].reshape(3, 3).copy()})
     if params.get('alignment/run_optimization', True) and sizes:
         pair = [b for b in range(B) for _ in sizes]
-        r = refine_alignment_batch(opt, th, pair, sizes * B, T0[pair], False, normalized, sigma)
+        r = refine_alignment_batch(opt, th, pair, sizes * B, T0[pair], False, normalized, sigma, model=model)
         if stats is not None:
             stats['rounds'] = stats.get('rounds', 0) + r['rounds']
         # the check of check_perspective_transformation that needs no decomposition: |MI(init) - MI(new)| at 100 bins
@@ -416,8 +530,10 @@ def align_images(optical, thermal, init_transform, params, geometric_checks=Fals
             inside = mm[:, 0].cpu().numpy() != -1.0
         for q in range(P):
             valid = abs(mi100[q] - mi100[P + q]) < params['alignment/check/both/max_diff_mi'] and inside[q]
+            if valid and geometric_checks:
+                valid = check_affine_geometry(T0[pair[q]], r['transform'][q], params)
             if valid and r['success'][q]:
-                cands[pair[q]].append({'type': alignment_type_name(sizes[q % len(sizes)], normalized, sigma),
+                cands[pair[q]].append({'type': alignment_type_name(sizes[q % len(sizes)], normalized, sigma, model),
                                        'transform': r['transform'][q].copy(), 'value': float(r['value'][q]),
                                        'init_value': float(own[q]), 'nit': int(r['nit'][q]), 'nfev': int(r['nfev'][q])})
     # the ranking scores are the plain negative mutual information, as align.py:531-535 and :551-555 call it
@@ -497,7 +613,11 @@ def run_alignment_stages(optical, thermal, t_init, params, align, blur):
                  call over those pairs only
     Every stage is ONE call of `align` with a start per pair.  Returns per pair (success, transform, type, candidates, stages);
     stages lists dict(name, shape (of the optical frame), start, type, success) for each stage the pair went through: name
-    'pyramid<i>' (level i of pyramid_levels, 1 = half size), 'smoothing', 'final', 'retry'."""
+    'pyramid<i>' (level i of pyramid_levels, 1 = half size), 'smoothing', 'final', 'retry'.
+    alignment/model reaches `align` with the other keys.  scale_transform is the same for every model: on a level with an odd
+    side the scaled start of a similarity is not exactly one, and the optimiser's start is what model_parameters reads from it
+    -- row 0 and the translations."""
+    transform_model(params.get('alignment/model', 'homography'))
     if not params.get('perspective', True):
         raise NotImplementedError('perspective: false -- ' + _AFFINE)
     if params.get('alignment/decomposed_transformation', False):
@@ -557,7 +677,8 @@ def align_images_mutual_information(optical, thermal, t_init, params, stats=None
     -- optical (Ho, Wo), thermal (H, W), t_init (3, 3) -- or B pairs -- (B, 1, Ho, Wo) or (B, Ho, Wo), (B, 1, H, W) or (B, H, W),
     t_init (3, 3) or (B, 3, 3): run_alignment_stages over align_images and gaussian_blur.  params: the reference's yaml keys --
     use_image_pyramid, use_smoothing_stage (both default off), alignment/n_pyramid_levels (2), alignment/filter_size (5) and
-    what align_images reads; `perspective: false` and alignment/decomposed_transformation raise NotImplementedError;
+    what align_images reads, alignment/model among them; `perspective: false` and alignment/decomposed_transformation raise
+    NotImplementedError;
     alignment/use_multiprocess, alignment/optimization_timeout, show_results and verbose are accepted and ignored.
     Returns (success, transform, type, candidates, stages) for one pair, a list of them for a batch; transform and type
     are None without success.  stats: see align_images."""

@@ -49,6 +49,9 @@ def build_parser():
                         'the pair under the identity, the estimated and (with --refine) the refined homography')
     parser.add_argument('--mi-refine', action='store_true', help='(extension) maximise the mutual information from the estimated '
                         'homography (utils.alignment.align_images; yaml block prediction.mi_alignment) and print the result')
+    parser.add_argument('--mi-transform', default=None, choices=['homography', 'similarity', 'affine'],
+                        help='(extension) with --mi-refine: motion model the mutual-information optimiser searches in; overrides '
+                        "prediction.mi_alignment['alignment/model'] (default homography)")
     parser.add_argument('--transform', default=None, choices=['homography', 'similarity', 'affine'],
                         help='(extension) motion model of the estimate (default: prediction.transform_model, else homography): a '
                         'similarity (rotation, scale, two translations) or an affine transform are determined by fewer inliers '
@@ -175,13 +178,15 @@ def mi_report(optical, thermal, named):
     print('Negative normalised MI (100 bins): ' + ', '.join('{} {:.6f}'.format(n, x) for (n, _), x in zip(named, v)))
 
 
-def mi_refine(optical, thermal, H_est, pred):
+def mi_refine(optical, thermal, H_est, pred, model=None):
     """--mi-refine: utils.alignment.align_images from the estimate -- with use_image_pyramid or use_smoothing_stage in the
     yaml block the staged align_images_mutual_information, which prints one line per stage.  Prints the winning candidate's
     type, its negative normalised mutual information at 100 bins and its matrix in the direction of the estimate (optical ->
-    thermal)."""
+    thermal).  model: --mi-transform, the optimiser's motion model in the place of the block's alignment/model."""
     from multipoint_amd.utils import alignment
     params = dict(MI_ALIGNMENT_DEFAULTS, **(pred.get('mi_alignment') or {}))
+    if model is not None:
+        params['alignment/model'] = model
     if params['use_image_pyramid'] or params['use_smoothing_stage']:
         _, T, kind, _, stages = alignment.align_images_mutual_information(optical[0, 0], thermal[0, 0],
                                                                           estimate_to_transform(H_est), params)
@@ -342,7 +347,7 @@ def main(argv=None):
                           [('identity', np.eye(3)), ('estimated', H_first)] + ([('refined', H_est)] if args.refine else []))
             H_mi = None
             if args.mi_refine:
-                H_mi = mi_refine(data['optical']['image'][:1], data['thermal']['image'][:1], H_est, pred)
+                H_mi = mi_refine(data['optical']['image'][:1], data['thermal']['image'][:1], H_est, pred, args.mi_transform)
             print('Ground Truth Homography:')
             print(H_gt)
             print('--------------------------------------------------------')
