@@ -933,6 +933,57 @@ int mp_lghd_orientation(mp_handle* h, const unsigned char* u8, const float* bank
 int mp_lghd_describe(mp_handle* h, const unsigned char* orientation, int B, int H, int W, const int* kp_yx, const int* kp_count,
                      int K, float* raw, float* unit, void* stream);
 
+/* ---- SIFT baseline (Lowe 2004 with the constants of opencv-contrib 4.2's sift.cpp; DESIGN.md 3.19, not verified against OpenCV) ----
+ * u8 [B][H][W] is the quantised frame (mp_lghd_quantize).  Every intermediate buffer lies in ONE caller-provided workspace of
+ * mp_sift_workspace_bytes(B, H, W, capacity) bytes; `capacity` is the number of slots per image of the candidate list and of the
+ * oriented-keypoint list, and every call on one workspace passes the same (B, H, W, capacity).  Nothing is read back between
+ * the stages, and results are bit-identical from run to run.
+ * MP_EINVAL (all entries): H or W below 16 or above 4096, B outside [1, 65535], capacity outside [1, 2^24], a workspace that is
+ * too small, NULL tensors.
+ *
+ * mp_sift_layout: where the tests find the stages' results in the workspace -- layout[0] octaves; layout[1..4] byte offsets of the
+ * candidate list int32 [B][capacity][4] (octave, layer, row, column), its counts int32 [B], the oriented list fp32 [B][capacity][6]
+ * (the record below in doubled-base coordinates) and its counts int32 [B] (both counts may exceed the capacity: overflow);
+ * layout[5..7] per candidate slot: fp32 [B][capacity][5] x, y, size, response, octave * 8 + layer; int32 [B][capacity] emitted
+ * orientations (0: rejected or no peak); int32 [B][capacity][4] final row, final column, peak bins 0..17 and 18..35 as bit masks;
+ * layout[8 + 4 o ..]: height, width of octave o and the byte offsets of its Gaussian planes fp32 [B][6][h][w] and difference
+ * planes fp32 [B][5][h][w].  layout holds 8 + 4 * 16 values.
+ *
+ * mp_sift_scale_space: the Gaussian and difference-of-Gaussian pyramids of u8 into the workspace.
+ *
+ * mp_sift_detect: scale space (skipped when u8 is NULL: the workspace's pyramids are used), candidates, refinement + orientation,
+ * duplicate removal and the nfeatures largest responses in list order (octave, layer, row, column of the candidate, then
+ * orientation bin; a tie at the cut goes to the earlier entry).  1 <= nfeatures <= N.
+ *   keypoints  fp32 [B][N][6]: x, y, size (frame coordinates), angle (degrees), response, octave * 8 + layer; rows beyond count zero
+ *   count      int32 [B]
+ *   flags      int32 [B]: MP_SIFT_FLAG_CANDIDATES (1) / MP_SIFT_FLAG_KEYPOINTS (2) when a list outgrew the capacity; its entries
+ *              beyond the capacity were dropped from the end
+ *
+ * mp_sift_select: the selection step alone on records fp32 [B][M][6] in doubled-base coordinates (rec_count [B], clipped to M):
+ * an entry whose x, y, size and angle equal an earlier one's is dropped, then the nfeatures largest responses are kept in list
+ * order and x, y, size are halved.  scratch: B * M bytes.
+ *
+ * mp_sift_describe: desc fp32 [B][N][128], the 4 x 4 x 8 histograms of the records in keypoints [B][N][6] (as mp_sift_detect writes
+ * them), read from the Gaussian pyramid in the workspace: values 0 .. 255, laid out [row][column][orientation]; rows beyond
+ * count [b] are zero.
+ *
+ * mp_sift_scatter: prob fp32 [B][1][H][W] = 1.0 at (round(y), round(x)) of every keypoint, 0 elsewhere; owner int32 [B][H][W] = the
+ * largest list index that rounds to the pixel, -1 elsewhere (the last in list order owns the pixel's descriptor). */
+#define MP_SIFT_FLAG_CANDIDATES 1
+#define MP_SIFT_FLAG_KEYPOINTS 2
+int mp_sift_workspace_bytes(int B, int H, int W, int capacity, long long* bytes);
+int mp_sift_layout(int B, int H, int W, int capacity, long long* layout);
+int mp_sift_scale_space(mp_handle* h, const unsigned char* u8, int B, int H, int W, int capacity, void* workspace,
+                        long long workspace_bytes, void* stream);
+int mp_sift_detect(mp_handle* h, const unsigned char* u8, int B, int H, int W, int capacity, int nfeatures, void* workspace,
+                   long long workspace_bytes, float* keypoints, int* count, int* flags, int N, void* stream);
+int mp_sift_select(mp_handle* h, const float* records, const int* rec_count, int B, int M, int nfeatures, float* keypoints, int* count,
+                   int N, void* scratch, long long scratch_bytes, void* stream);
+int mp_sift_describe(mp_handle* h, int B, int H, int W, int capacity, const void* workspace, long long workspace_bytes,
+                     const float* keypoints, const int* count, int N, float* desc, void* stream);
+int mp_sift_scatter(mp_handle* h, const float* keypoints, const int* count, int B, int N, int H, int W, float* prob, int* owner,
+                    void* stream);
+
 /* per-launch timing of mp_forward with hipEvents on the caller's stream (bench.py roofline leg).
  * mp_profile_read synchronises; names[i] points to static strings. */
 int mp_profile_enable(mp_handle* h, int enable);

@@ -224,6 +224,16 @@ SIGNATURES = {
     'mp_lghd_orientation': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_ll, c_void_p]),
     'mp_lghd_describe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                  c_void_p]),
+    'mp_sift_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
+    'mp_sift_layout': (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
+    'mp_sift_scale_space': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_ll, c_void_p]),
+    'mp_sift_detect': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_ll, c_void_p, c_void_p, c_void_p,
+                               c_int, c_void_p]),
+    'mp_sift_select': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_ll,
+                               c_void_p]),
+    'mp_sift_describe': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_ll, c_void_p, c_void_p, c_int, c_void_p,
+                                 c_void_p]),
+    'mp_sift_scatter': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'mp_profile_enable': (c_int, [c_void_p, c_int]),
     'mp_profile_read': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_float),
                                 ctypes.POINTER(ctypes.c_double), c_int, ctypes.POINTER(c_int)]),

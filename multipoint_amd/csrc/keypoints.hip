@@ -6,13 +6,14 @@
 //   * scatter into zeros_like(prob)        multipoint/utils/utils.py:119-120
 //   * torch.nonzero(prob > thr)            predict_align_image_pair.py:170-171, evaluation.py:262-263
 //     -> (N,2) (y,x) rows in row-major order
-// Ballot/shuffle prefix scans give every kept pixel its row-major rank without atomics (so the output order is
+// Ballot/shuffle prefix scans (mp_select.h, shared with sift.hip) give every kept pixel its row-major rank without atomics (so the output order is
 // deterministic and equals nonzero()).  The dense map is compacted by MANY workgroups per image in two passes over
 // 16 Ki-pixel segments -- count, then ordered write at the segment's prefix (a single workgroup per image streams a
 // 1024x1280 map at only ~260 GB/s) -- and one 1024-thread workgroup per image then works on the short list only:
 // a 4-pass 8-bit radix select over the fp32 score bits finds the exact k-th score; ties at the threshold are
 // admitted in row-major order.
 #include "mp_common.h"
+#include "mp_select.h"
 
 namespace {
 
@@ -20,37 +21,6 @@ namespace {
 // F(4x4,3x3) workgroups of rounds 2 / 3 own their CU -- 512 threads x 231-256 registers, 158 KiB of LDS -- so these kernels now
 // run at launch boundaries and beside the head tail)
 constexpr int BT = 256;                       // threads per workgroup (4 waves)
-
-__device__ __forceinline__ int wave_incl_scan(int v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int n = __shfl_up(v, off);
-        if (lane >= off) v += n;
-    }
-    return v;
-}
-
-// exclusive prefix of `c` over a workgroup of NT threads in thread order; returns block total via *total
-template <int NT = BT>
-__device__ __forceinline__ int block_excl_scan(int c, int* s_wave, int* total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int inc = wave_incl_scan(c, lane);
-    if (lane == 63) s_wave[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < NT / 64; ++i) {
-        const int x = s_wave[i];
-        if (i < w) base += x;
-        tot += x;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - c;
-}
-
 constexpr int BTS = 1024;                     // threads of the per-image selection workgroup
 
 constexpr int SEG = 16384;                    // pixels per segment (a multiple of BT * 4)
@@ -90,7 +60,7 @@ __global__ __launch_bounds__(BT) void count_segments_kernel(const float* __restr
         if (zero_fill) *reinterpret_cast<f32x4*>(zero_fill + (long long)b * n + i) = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     int tot;
-    block_excl_scan(c, s_wave, &tot);
+    block_excl_scan<BT>(c, s_wave, &tot);
     if (threadIdx.x == 0) seg_count[b * nseg + sg] = tot;
 }
 
@@ -133,7 +103,7 @@ __global__ __launch_bounds__(BT) void compact_segments_kernel(const float* __res
 #pragma unroll
         for (int e = 0; e < 4; ++e) { k[e] = (i < hi) && keep_px<MODE>(v[e], thr) && mk[e]; c += k[e]; }
         int tot;
-        int pos = base + block_excl_scan(c, s_wave, &tot);
+        int pos = base + block_excl_scan<BT>(c, s_wave, &tot);
 #pragma unroll
         for (int e = 0; e < 4; ++e)
             if (k[e]) {
@@ -176,37 +146,7 @@ __global__ __launch_bounds__(BTS) void select_keypoints_kernel(
     int need = 0;
     const bool select = nk > k;
     if (select) {
-        unsigned prefix = 0, mask = 0;
-        int kk = k;
-        for (int pass = 0; pass < 4; ++pass) {
-            const int shift = 24 - 8 * pass;
-            if (tid < 256) s_hist[tid] = 0;
-            __syncthreads();
-            for (int i = tid; i < nk; i += BTS) {
-                const unsigned key = __float_as_uint(lsc[i]);
-                if ((key & mask) == prefix) atomicAdd(&s_hist[(key >> shift) & 255u], 1u);
-            }
-            __syncthreads();
-            // the digit d with (#keys of a larger digit) < kk <= (#keys of digit >= d), found by all 256 threads at once (thread t
-            // holds bin t; suffix count = total - exclusive prefix): a single thread walking the bins down took a dependent LDS
-            // read per bin, 256 x 4 passes = half of the kernel's 66 us
-            {
-                const int hcnt = tid < 256 ? (int)s_hist[tid] : 0;
-                int tot;
-                const int before = block_excl_scan<BTS>(hcnt, s_wave, &tot);      // bins 0 .. t-1
-                const int ge = tot - before;                                 // bins t .. 255
-                if (tid == 0) { s_sel[0] = 0u; s_sel[1] = (unsigned)(tot - hcnt); }      // (fewer than kk keys: digit 0, as the walk did)
-                __syncthreads();
-                if (tid > 0 && tid < 256 && ge >= kk && ge - hcnt < kk) { s_sel[0] = (unsigned)tid; s_sel[1] = (unsigned)(ge - hcnt); }
-            }
-            __syncthreads();
-            prefix |= s_sel[0] << shift;
-            mask |= 255u << shift;
-            kk -= (int)s_sel[1];
-            __syncthreads();
-        }
-        T = prefix;
-        need = kk;
+        radix_select_cut<BTS>([&](int i) { return __float_as_uint(lsc[i]); }, nk, k, s_hist, s_wave, s_sel, &T, &need);
     }
 
     // ordered output (row-major, == torch.nonzero order of the NMS'ed map)

@@ -611,3 +611,39 @@ size_t thermal_rescale_workspace_bytes(int n);
 // workspace: thermal_rescale_workspace_bytes(n) zeroed bytes on s; clipped (may be `in`) and saved may be NULL
 void launch_thermal_rescale(const unsigned short* in, int n, int H, int W, const FramesRanks& rk, unsigned short* clipped,
                             float* rescaled, unsigned short* saved, void* workspace, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
+// SIFT baseline (sift.hip; Lowe 2004 with the constants of opencv-contrib 4.2's sift.cpp).  Every buffer lies
+// in one caller-provided workspace; SiftLayout says where (sift_api.hip: sift_layout()).
+// ---------------------------------------------------------------------------------------------
+#define MP_SIFT_MAX_OCTAVES 16
+#define MP_SIFT_LAYERS 6           // Gaussian layers per octave (nOctaveLayers + 3); 5 difference layers
+#define MP_SIFT_MAX_TAPS 27        // widest Gaussian of the chain: round(8 sigma + 1) | 1 at sigma = 3.09
+#define MP_SIFT_MAX_ORI 18         // strict peaks of a circular 36-bin histogram
+#define MP_SIFT_BORDER 5
+#define MP_SIFT_FLAG_CANDIDATES 1  // flags: more candidates than the capacity (dropped from the end)
+#define MP_SIFT_FLAG_KEYPOINTS 2   // ... more oriented keypoints than the capacity
+struct SiftLayout {
+    int B, H, W, noct, cap;
+    int h[MP_SIFT_MAX_OCTAVES], w[MP_SIFT_MAX_OCTAVES];
+    long long gauss[MP_SIFT_MAX_OCTAVES];      // float offset of [B][6][h][w]
+    long long dog[MP_SIFT_MAX_OCTAVES];        // float offset of [B][5][h][w]
+    long long flat[MP_SIFT_MAX_OCTAVES + 1];   // candidate positions (3 layers x h x w) of the octaves before o
+    long long tmp;                             // float offset of [B][2H][2W]: the row pass of a blur
+    int nblk;                                  // candidate workgroups per image (1024 positions each)
+    // byte offsets
+    long long cmask, seg_count, seg_base, cand, cand_count, crec, cn, cang, cinfo, list, list_count, dup, bytes;
+};
+struct SiftTaps { int n; float w[MP_SIFT_MAX_TAPS]; };
+// the Gaussian and difference pyramids of u8 [B][H][W]
+void launch_sift_scale_space(const unsigned char* u8, const SiftLayout& L, void* ws, hipStream_t s);
+// candidates -> refinement + orientation -> ordered list [B][cap][6] (doubled-base coordinates) in the workspace; flags |= MP_SIFT_FLAG_*
+void launch_sift_detect(const SiftLayout& L, void* ws, int* flags, hipStream_t s);
+// records [B][M][6] -> duplicates removed, the nfeatures largest responses in list order, x / y / size halved: keypoints [B][N][6]
+// (rows beyond count zero); dup: B * M bytes of scratch
+void launch_sift_select(const float* records, const int* rec_count, int B, int M, int nfeatures, int N, float* keypoints,
+                        int* count, unsigned char* dup, hipStream_t s);
+void launch_sift_describe(const SiftLayout& L, const void* ws, const float* keypoints, const int* count, int N, float* desc,
+                          hipStream_t s);
+void launch_sift_scatter(const float* keypoints, const int* count, int B, int N, int H, int W, float* prob, int* owner,
+                         hipStream_t s);

@@ -1,5 +1,7 @@
 """ClassicDetectors (reference multipoint/models/ClassicDetectors.py) for `method: LGHD`: FAST-9/16 keypoints and log-Gabor
-histogram descriptors, every stage a HIP kernel (csrc/lghd.hip, csrc/fft.hip).  PyTorch only holds the memory.
+histogram descriptors, every stage a HIP kernel (csrc/lghd.hip, csrc/fft.hip), and -- opt-in through
+`implementation: restated` -- for `method: SIFT`: Lowe's detector and descriptor restated from the published algorithm
+(csrc/sift.hip).  PyTorch only holds the memory.
 
 The reference runs one image at a time on the host and returns a dense [1,384,H,W] descriptor map with the raw counts
 scattered at the keypoints.  Here `forward` takes any batch and returns, besides `prob`, the `orientation` maps the
@@ -15,6 +17,8 @@ from ..utils import utils as U
 from ..utils.homographies import gaussian_filter
 
 DESCRIPTOR_SIZE = 384
+SIFT_DESCRIPTOR_SIZE = 128
+SIFT_NFEATURES = 1000           # the reference's cv2.xfeatures2d.SIFT_create(1000)
 
 
 def fft_length_ok(n):
@@ -128,6 +132,161 @@ def describe(orientation, kp_yx, kp_count, raw=False):
     return out
 
 
+def sift_capacity(H, W):
+    """list slots per image the model asks for: one per 8 pixels, at least 4096 (flags report an overflow)"""
+    return max(4096, (H * W) // 8)
+
+
+class SiftWorkspace:
+    """The one buffer every SIFT stage of a batch works in (mp_sift_workspace_bytes), and views of the stages' results in it."""
+
+    def __init__(self, B, H, W, capacity, device):
+        self.dev = _lib.require_cuda(device)
+        self.B, self.H, self.W, self.capacity = B, H, W, int(capacity)
+        self.h = _lib.get_handle(self.dev)
+        nbytes = ctypes.c_longlong(0)
+        if self.h.lib.mp_sift_workspace_bytes(B, H, W, self.capacity, ctypes.byref(nbytes)) != _lib.MP_OK:
+            raise ValueError('SIFT: need 1 <= B <= 65535, frames of 16 x 16 to 4096 x 4096 and 1 <= capacity <= 2^24 (got B = %d, '
+                             '%d x %d, capacity %d)' % (B, H, W, self.capacity))
+        self.nbytes = nbytes.value
+        self.buf = torch.empty((self.nbytes,), dtype=torch.uint8, device=self.dev)
+        lay = (ctypes.c_longlong * (8 + 4 * 16))()
+        _lib.check(self.h.lib.mp_sift_layout(B, H, W, self.capacity, lay))
+        self.layout = list(lay)
+        self.octaves = self.layout[0]
+
+    def _view(self, offset, dtype, shape):
+        n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+        return self.buf[offset:offset + n].view(dtype).reshape(shape)
+
+    def pyramids(self):
+        """([gauss [B,6,h,w] per octave], [dog [B,5,h,w] per octave]) as views of the workspace"""
+        g, d = [], []
+        for o in range(self.octaves):
+            h, w, go, do = self.layout[8 + 4 * o:12 + 4 * o]
+            g.append(self._view(go, torch.float32, (self.B, 6, h, w)))
+            d.append(self._view(do, torch.float32, (self.B, 5, h, w)))
+        return g, d
+
+    def candidates(self):
+        """(int32 [B,capacity,4] octave, layer, row, column; int32 [B] counts, which may exceed the capacity)"""
+        return (self._view(self.layout[1], torch.int32, (self.B, self.capacity, 4)), self._view(self.layout[2], torch.int32, (self.B,)))
+
+    def refined(self):
+        """per candidate slot: (float32 [B,capacity,5] x, y, size, response, octave * 8 + layer in doubled-base coordinates; int32
+        [B,capacity] emitted orientations; int32 [B,capacity,4] final row, final column, peak bins 0..17 / 18..35 as bit masks)"""
+        shape = (self.B, self.capacity)
+        return (self._view(self.layout[5], torch.float32, shape + (5,)), self._view(self.layout[6], torch.int32, shape),
+                self._view(self.layout[7], torch.int32, shape + (4,)))
+
+    def oriented(self):
+        """(float32 [B,capacity,6] records in doubled-base coordinates; int32 [B] counts, which may exceed the capacity)"""
+        return (self._view(self.layout[3], torch.float32, (self.B, self.capacity, 6)), self._view(self.layout[4], torch.int32, (self.B,)))
+
+
+def sift_scale_space(u8, capacity=None, workspace=None):
+    """u8 [B,H,W] uint8 -> SiftWorkspace holding the Gaussian and difference-of-Gaussian pyramids (`.pyramids()`)."""
+    dev = _lib.require_cuda(u8.device)
+    B, H, W = u8.shape
+    ws = workspace or SiftWorkspace(B, H, W, capacity or sift_capacity(H, W), dev)
+    with torch.cuda.device(dev):
+        ws.h.check(ws.h.lib.mp_sift_scale_space(ws.h.ptr, _lib.ptr(u8.contiguous()), B, H, W, ws.capacity, _lib.ptr(ws.buf), ws.nbytes,
+                                                _lib.stream_ptr(dev)))
+    return ws
+
+
+def sift_detect(u8, nfeatures=SIFT_NFEATURES, capacity=None, workspace=None, N=None):
+    """u8 [B,H,W] uint8 (None: the pyramids `workspace` already holds) -> (keypoints float32 [B,N,6] = x, y, size, angle,
+    response, octave * 8 + layer; count int32 [B]; flags int32 [B]; the SiftWorkspace)."""
+    if u8 is None:
+        ws = workspace
+        B, H, W, dev = ws.B, ws.H, ws.W, ws.dev
+    else:
+        dev = _lib.require_cuda(u8.device)
+        B, H, W = u8.shape
+        ws = workspace or SiftWorkspace(B, H, W, capacity or sift_capacity(H, W), dev)
+        u8 = u8.contiguous()
+    N = int(N or nfeatures)
+    kp = torch.empty((B, N, 6), dtype=torch.float32, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    flags = torch.empty((B,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        ws.h.check(ws.h.lib.mp_sift_detect(ws.h.ptr, _lib.ptr(u8), B, H, W, ws.capacity, int(nfeatures), _lib.ptr(ws.buf), ws.nbytes,
+                                           _lib.ptr(kp), _lib.ptr(count), _lib.ptr(flags), N, _lib.stream_ptr(dev)))
+    return kp, count, flags, ws
+
+
+def sift_select(records, rec_count, nfeatures=SIFT_NFEATURES, N=None):
+    """records float32 [B,M,6] in doubled-base coordinates, rec_count int32 [B] -> (keypoints [B,N,6], count [B]): exact
+    duplicates (x, y, size, angle) dropped, the nfeatures largest responses kept in list order, x / y / size halved."""
+    dev = _lib.require_cuda(records.device)
+    B, M, _ = records.shape
+    N = int(N or nfeatures)
+    kp = torch.empty((B, N, 6), dtype=torch.float32, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    scratch = torch.empty((B * M,), dtype=torch.uint8, device=dev)
+    h = _lib.get_handle(dev)
+    with torch.cuda.device(dev):
+        h.check(h.lib.mp_sift_select(h.ptr, _lib.ptr(records.to(torch.float32).contiguous()), _lib.ptr(rec_count.to(dev, torch.int32).contiguous()),
+                                     B, M, int(nfeatures), _lib.ptr(kp), _lib.ptr(count), N, _lib.ptr(scratch), B * M, _lib.stream_ptr(dev)))
+    return kp, count
+
+
+def sift_describe(workspace, keypoints, count):
+    """keypoints float32 [B,N,6] (as sift_detect returns them), count int32 [B] -> float32 [B,N,128]: the descriptors (values
+    0 .. 255) from the Gaussian pyramid `workspace` holds; rows beyond count[b] are zero."""
+    ws = workspace
+    B, N, _ = keypoints.shape
+    out = torch.empty((B, N, SIFT_DESCRIPTOR_SIZE), dtype=torch.float32, device=ws.dev)
+    with torch.cuda.device(ws.dev):
+        ws.h.check(ws.h.lib.mp_sift_describe(ws.h.ptr, ws.B, ws.H, ws.W, ws.capacity, _lib.ptr(ws.buf), ws.nbytes,
+                                             _lib.ptr(keypoints.to(torch.float32).contiguous()), _lib.ptr(count.to(ws.dev, torch.int32).contiguous()),
+                                             N, _lib.ptr(out), _lib.stream_ptr(ws.dev)))
+    return out
+
+
+def sift_scatter(keypoints, count, H, W):
+    """-> (prob float32 [B,1,H,W]: 1.0 at (round(y), round(x)) of every keypoint; owner int32 [B,H,W]: the last list index that
+    rounds to the pixel, -1 elsewhere)"""
+    dev = _lib.require_cuda(keypoints.device)
+    B, N, _ = keypoints.shape
+    prob = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+    owner = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    h = _lib.get_handle(dev)
+    with torch.cuda.device(dev):
+        h.check(h.lib.mp_sift_scatter(h.ptr, _lib.ptr(keypoints.to(torch.float32).contiguous()), _lib.ptr(count.to(dev, torch.int32).contiguous()),
+                                      B, N, H, W, _lib.ptr(prob), _lib.ptr(owner), _lib.stream_ptr(dev)))
+    return prob, owner
+
+
+def sift_dense_map(sift_desc, owner):
+    """B == 1: the reference's dense map [1,128,H,W] with the raw row of every pixel's owner, [1,1,H,W] zeros without any keypoint"""
+    _, H, W = owner.shape
+    yx = torch.nonzero(owner[0] >= 0)
+    if not yx.shape[0]:
+        return torch.zeros((1, 1, H, W), dtype=torch.float32, device=owner.device)
+    dense = torch.zeros((1, SIFT_DESCRIPTOR_SIZE, H, W), dtype=torch.float32, device=owner.device)
+    dense[0, :, yx[:, 0], yx[:, 1]] = sift_desc[0, owner[0, yx[:, 0], yx[:, 1]].long()].t()
+    return dense
+
+
+def sift_owner_rows(sift_desc, owner, kp_yx, kp_count):
+    """The owner's descriptor row, L2-normalised, for every listed pixel: sift_desc [B,N,128], owner int32 [B,H,W], kp_yx int32
+    [B,K,2], kp_count [B] -> float32 [B,K,128]; rows beyond the count and pixels without an owner are zero."""
+    B, K = kp_yx.shape[:2]
+    dev = sift_desc.device
+    if K == 0:
+        return torch.zeros((B, 0, SIFT_DESCRIPTOR_SIZE), dtype=torch.float32, device=dev)
+    H, W = owner.shape[1:]
+    yx = kp_yx.to(dev).long()
+    y, x = yx[..., 0].clamp(0, H - 1), yx[..., 1].clamp(0, W - 1)
+    idx = owner[torch.arange(B, device=dev)[:, None], y, x].long()                                  # [B,K]
+    live = (idx >= 0) & (torch.arange(K, device=dev)[None, :] < kp_count.to(dev)[:, None])
+    rows = torch.gather(sift_desc, 1, idx.clamp(min=0)[..., None].expand(B, K, SIFT_DESCRIPTOR_SIZE))
+    rows = rows / rows.norm(dim=2, keepdim=True).clamp(min=1e-12)
+    return torch.where(live[..., None], rows, torch.zeros_like(rows))
+
+
 class ClassicDetectors:
     default_config = {
         'method': 'SURF',
@@ -138,14 +297,23 @@ class ClassicDetectors:
         'image_W': 640,
     }
 
+    describes_keypoints = True      # pipeline.py: descriptors come from `describe(out, kp, cnt)`, not from sampling a dense map
+
     def __init__(self, config=None):
         given = dict(config or {})
+        # `implementation` (an extension, read from the given configuration only): dict_update would copy a key the defaults lack
+        # into self.config, so it is taken out first -- the configuration keeps the reference's six keys
+        implementation = given.pop('implementation', None)
+        if implementation not in (None, 'restated'):
+            raise ValueError("ClassicDetectors: implementation must be 'restated' or absent, got %r" % (implementation,))
         self.config = U.dict_update(dict(self.default_config), given)
         method = self.config['method']
-        if method in ('SURF', 'SIFT'):
-            raise NotImplementedError('ClassicDetectors: %s lives inside opencv-contrib and is not rebuilt here; only LGHD is' % method)
-        if method != 'LGHD':
+        if method == 'SURF' or (method == 'SIFT' and implementation is None):
+            raise NotImplementedError('ClassicDetectors: %s lives inside opencv-contrib and is not rebuilt here; LGHD is, and SIFT as '
+                                      'a restatement of the published algorithm behind `implementation: restated`' % method)
+        if method not in ('LGHD', 'SIFT'):
             raise ValueError('Unknown alignment method: ' + str(method))
+        self.method = method
         if self.config['prob_smoothing'] and self.config['smoothing_kernel_size'] % 2 == 0:
             raise ValueError('smoothing_kernel_size needs to be uneven')
         # the reference sizes its filter bank by image_H / image_W; here the bank follows the frame, and the two keys only
@@ -204,12 +372,14 @@ class ClassicDetectors:
         if image.device != self.device:
             raise RuntimeError('input image is on %s but the model is on %s' % (image.device, self.device))
         B, _, H, W = image.shape
-        if not (fft_length_ok(H) and fft_length_ok(W)):
+        if self.method == 'LGHD' and not (fft_length_ok(H) and fft_length_ok(W)):
             raise ValueError('LGHD: frame of %d x %d: both sizes must be 2^a 3^b 5^c in [8, 4096]' % (H, W))
         for name, want, got in (('image_H', self._frame[0], H), ('image_W', self._frame[1], W)):
             if want is not None and int(want) != got:
                 raise ValueError('ClassicDetectors: the configuration says %s = %d, the frame has %d' % (name, int(want), got))
         u8 = quantize(image).reshape(B, H, W)
+        if self.method == 'SIFT':
+            return self._smooth(self._forward_sift(u8))
         _, _, prob = fast_detect(u8)
         orientation = orientation_maps(u8, self.filter_bank(H, W, self.device))
         out = {'prob': prob, 'orientation': orientation}
@@ -224,6 +394,22 @@ class ClassicDetectors:
             else:
                 desc = torch.zeros((1, 1, H, W), dtype=torch.float32, device=self.device)
             out['desc'] = desc
+        return self._smooth(out)
+
+    def _forward_sift(self, u8):
+        """detect + describe + scatter.  The reference's second detector, SIFT_create(1500) when fewer than
+        min_keypoints are found, only raises a cap that fewer than 100 keypoints never reach: there is no second pass."""
+        B, H, W = u8.shape
+        kp, count, flags, ws = sift_detect(u8)
+        desc = sift_describe(ws, kp, count)
+        prob, owner = sift_scatter(kp, count, H, W)
+        out = {'prob': prob, 'sift_keypoints': kp, 'sift_count': count, 'sift_desc': desc, 'sift_owner': owner, 'sift_flags': flags}
+        if B == 1:
+            out['desc'] = sift_dense_map(desc, owner)
+        return out
+
+    def _smooth(self, out):
+        prob = out['prob']
         if self.config['prob_smoothing']:
             # self.filter(F.pad(prob, padding)): zero padding, then the k x k filter over the padded map's interior
             k = int(self.config['smoothing_kernel_size'])
@@ -240,4 +426,8 @@ class ClassicDetectors:
         """[B,K,384] unit rows for the keypoint lists of a forward's output.  This is what the reference's
         interpolate_descriptors yields on the dense map: its sample at (y, x) blends in (y-1, x), (y, x-1) and (y-1, x-1), which
         FAST's strict non-maximum suppression keeps free of keypoints, so the normalised sample is the normalised raw row."""
+        if 'sift_owner' in out:
+            # SIFT: the row of the keypoint that owns the pixel.  The reference's blend with (y-1, x), (y, x-1), (y-1, x-1) mixes
+            # descriptors of DIFFERENT keypoints where one of those pixels holds one; that artefact is not reproduced
+            return sift_owner_rows(out['sift_desc'], out['sift_owner'], kp_yx, kp_count)
         return describe(out['orientation'], kp_yx, kp_count)

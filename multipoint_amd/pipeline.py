@@ -14,6 +14,12 @@ from .utils import utils as U
 from .utils.matching import match_pairs, nearest_pairs
 
 
+def describes_keypoints(net):
+    """True for models whose descriptors come from `net.describe(out, kp_yx, kp_count)` (ClassicDetectors: LGHD patch
+    histograms, SIFT owner rows) instead of sampling a dense descriptor map."""
+    return bool(getattr(net, 'describes_keypoints', False))
+
+
 class PairResults:
     def __init__(self, kp_yx, kp_score, kp_count, desc, match_idx, match_dist, match_count, H, W, match_mode='mutual', *,
                  kp_sub=None):
@@ -99,7 +105,7 @@ class PairPipeline:
         if unknown:
             raise ValueError('subpixel: unknown key(s) %s' % sorted(unknown))
         self.subpixel = bool(sub.get('enable', False))
-        if self.subpixel and hasattr(net, 'describe'):
+        if self.subpixel and describes_keypoints(net):
             raise ValueError('subpixel: ClassicDetectors models have no sub-pixel keypoints (LGHD descriptors are patch '
                              'histograms at integer centres)')
         m = config.get('matching', {'method': 'bfmatcher', 'method_kwargs': {'crossCheck': True},
@@ -192,7 +198,8 @@ class PairPipeline:
                 if t is not None:
                     t.record_stream(fwd)
             post.wait_stream(fwd)      # (a forward the caller enqueues next on ITS stream is ordered behind this one by the model itself)
-            for t in (out['prob'], out.get('desc'), out.get('orientation'), valid_mask):
+            for t in (out['prob'], out.get('desc'), out.get('orientation'), out.get('sift_keypoints'), out.get('sift_count'),
+                      out.get('sift_desc'), out.get('sift_owner'), valid_mask):
                 if t is not None:
                     t.record_stream(post)
         else:
@@ -234,9 +241,9 @@ class PairPipeline:
         K = kp.shape[1]
         # (on this stream right behind the lists; from the map they were made from -- a map the tie guard redid included)
         kp_sub = U.refine_keypoints(prob, kp, cnt) if self.subpixel else None
-        if 'orientation' in out:
-            # ClassicDetectors: the patch histograms of the keypoints straight from the orientation maps -- what sampling the
-            # reference's dense map yields, without the map
+        if describes_keypoints(self.net):
+            # ClassicDetectors: the patch histograms of the keypoints straight from the orientation maps (LGHD), or the row of the
+            # keypoint that owns the pixel (SIFT) -- what sampling the reference's dense map yields, without the map
             desc = self.net.describe(out, kp, cnt)                                  # [B,K,384]
         else:
             desc = U.interpolate_descriptors_batched(kp if kp_sub is None else kp_sub, cnt, out['desc'], H, W)        # [B,K,D]
@@ -295,7 +302,7 @@ class PairPipeline:
         descs, subs = [], []
         for (out, mask, h, w), (kp, sc, cnt) in zip(sides, lists):
             subs.append(U.refine_keypoints(out['prob'], kp, cnt) if self.subpixel else None)
-            descs.append(self.net.describe(out, kp, cnt) if 'orientation' in out
+            descs.append(self.net.describe(out, kp, cnt) if describes_keypoints(self.net)
                          else U.interpolate_descriptors_batched(kp if subs[-1] is None else subs[-1], cnt, out['desc'], h, w))
         kp_sub = torch.stack(subs, dim=1).reshape(2 * P, K, 2).contiguous() if self.subpixel else None
         kp, sc, cnt, desc = (torch.stack((a, b), dim=1).reshape(2 * P, *a.shape[1:]).contiguous()
@@ -324,7 +331,7 @@ class PairPipeline:
         out = self.net(data)
         res = self._settle(self._post(out, valid_mask, dev, B, H, W), out, valid_mask, dev, B, H, W)
         self.tie_redone = 0
-        if self.tie_robust and self.nms > 0 and 'orientation' not in out:      # (ClassicDetectors: no convolution algorithm to switch)
+        if self.tie_robust and self.nms > 0 and not describes_keypoints(self.net):      # (ClassicDetectors: no convolution algorithm to switch)
             # tie guards (include/multipoint_hip.h), evaluated on the CONVERGED pass -- the flags of the latest detect call, i.e. of
             # the lists `res` holds: images whose top-k cut fell inside a plateau of scores tied within the default convolution
             # algorithm's rounding noise (or whose NMS decided many such near-ties, whatever `topk`) are re-evaluated ONCE with the
