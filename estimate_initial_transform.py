@@ -25,6 +25,14 @@ refine_transform_pooled; fewest inliers 3 | 4).  The yaml stays a 3x3 `perspecti
 last row is then (0, 0, 1)); the report gains `transform` and, for a similarity, `similarity`: the angle, scale, dx and dy of
 the optical -> thermal estimate in the convention of multipoint_amd.utils.decompose_similarity.
 
+--method fourier estimates a similarity without keypoints, descriptors or a network (-m and -v are ignored; --transform must
+be similarity and is set to it when omitted): Fourier-Mellin phase correlation of the frames' gradient magnitudes, the
+normalised cross-power spectra of all pairs added (multipoint_amd.utils.FourierEstimator).  The files are read
+twice in --batch chunks, once for the angle and scale and once for the translation.  The report then holds the pairs read /
+used, `similarity`, and per stage the peak of the pooled correlation surface, the second-highest value outside its 3 x 3 block
+and their ratio, and `branch_180`, whether the theta + pi candidate won.  When either ratio is below --min-peak-ratio nothing is
+written and the exit status is 1.  The default floor of 1.1 is a guess: no recording was available to set it on.
+
 Not known: how well this works on real thermal / optical recordings -- no such data and no trained weights are in this
 repository; everything is verified on synthetic and planted data.  Look at the report (and at check_alignment.py's pictures)
 before trusting the file."""
@@ -41,6 +49,14 @@ YAML_NAME = 'initial_transform.yaml'
 REPORT_NAME = 'initial_transform_report.json'
 
 
+class _ExplicitTransform(argparse.Action):
+    """--transform, remembering that it was given: --method fourier sets an omitted one to similarity and refuses another."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        namespace.transform_explicit = True
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description='Estimate initial_transform.yaml of a directory of image pairs from their pooled matches')
     parser.add_argument('-y', '--yaml-config', default='configs/config_image_pair_dataset_prediction.yaml', help='YAML config file')
@@ -54,10 +70,17 @@ def build_parser():
     parser.add_argument('--max-iters', default=2000, type=int, help='RANSAC hypotheses')
     parser.add_argument('--subpixel', action='store_true', help='Refine the keypoints to sub-pixel positions on the detector map '
                         '(prediction.subpixel.enable): the pooled matches then hold float positions')
-    parser.add_argument('--transform', default='homography', choices=['homography', 'similarity', 'affine'],
+    parser.add_argument('--transform', default='homography', choices=['homography', 'similarity', 'affine'], action=_ExplicitTransform,
                         help='Motion model of the estimate: the 8-parameter homography, a similarity (rotation, scale, two translations: '
                         'what a rigid rig is close to, and what few inliers still determine) or an affine transform')
     parser.add_argument('--force', action='store_true', help='Overwrite an existing yaml file (it may be hand-measured)')
+    parser.add_argument('--method', default='matches', choices=['matches', 'fourier'],
+                        help='matches: pooled keypoint matches of a network or baseline; fourier: keypoint-free Fourier-Mellin phase '
+                        'correlation of the gradient magnitudes, a similarity only (no network: -m and -v are ignored)')
+    parser.add_argument('--min-peak-ratio', default=1.1, type=float,
+                        help='--method fourier: write nothing when the highest value of a correlation surface is below this many times '
+                        'the second-highest (a guess: not set on a real recording)')
+    parser.set_defaults(transform_explicit=False)
     return parser
 
 
@@ -157,8 +180,103 @@ def estimate_on_gpu(args, config, names):
     return H[0].cpu().numpy(), mask.cpu().numpy(), pair_offsets, int(nin[0]), (float(cost[0]), float(cost[1]))
 
 
-def main(argv=None, estimator=estimate_on_gpu):
+def _ratio(peak, second):
+    """peak / second of a correlation surface; 0 for a surface without a positive peak."""
+    peak, second = float(peak), float(second)
+    if not peak > 0.0:
+        return 0.0
+    return peak / max(second, 1e-30)
+
+
+def build_fourier_report(names_read, names_used, H, info):
+    """The report of --method fourier: H the optical -> thermal similarity, info the estimator's peak1, second1 (angle and scale),
+    peak2, second2 (translation) and branch (1: the theta + pi candidate won)."""
+    from multipoint_amd.utils import decompose_similarity
+    report = {
+        'method': 'fourier',
+        'transform': 'similarity',
+        'pairs_read': len(names_read),
+        'pairs_used': len(names_used),
+        'stage1': {'peak': float(info['peak1']), 'second': float(info['second1']), 'ratio': _ratio(info['peak1'], info['second1'])},
+        'stage2': {'peak': float(info['peak2']), 'second': float(info['second2']), 'ratio': _ratio(info['peak2'], info['second2'])},
+        'branch_180': bool(info['branch']),
+    }
+    H = np.asarray(H, np.float64).reshape(3, 3)
+    if np.isfinite(H).all() and H.any():
+        report['similarity'] = dict(zip(('angle', 'scale', 'dx', 'dy'), decompose_similarity(H)))
+    return report
+
+
+def estimate_fourier_on_gpu(args, names):
+    """The pooled Fourier-Mellin estimate of the pairs `names`, read in --batch chunks: one pass over the files accumulates the
+    cross-power sums of the angle-and-scale stage, a second pass those of the translation stage under the estimated similarity and
+    its theta + pi twin.  Returns (H 3x3 float64 optical -> thermal, dict(peak1, second1, peak2, second2, branch))."""
+    import torch
+
+    from multipoint_amd import _lib
+    from multipoint_amd.datasets.image_file_pairs import read_png_pair
+    from multipoint_amd.utils import FourierEstimator, alignment
+    device = _lib.require_cuda()
+    print('Estimating on device: {}'.format(device))
+    batch = max(args.batch, 1)
+
+    def chunks():
+        for at in range(0, len(names), batch):
+            pairs = [read_png_pair(args.input_dir, n) for n in names[at:at + batch]]
+            optical = torch.stack([alignment.frames_to_float(p[0], device, single_bgr=p[0].ndim == 3) for p in pairs])
+            thermal = alignment.frames_to_float(np.stack([p[1] for p in pairs]), device).reshape(len(pairs), *pairs[0][1].shape)
+            yield optical.contiguous(), thermal.contiguous()
+
+    est = None
+    for optical, thermal in chunks():
+        if est is None:
+            est = FourierEstimator(optical.shape[1:], thermal.shape[1:])
+        est.add_stage1(optical, thermal)
+    est.finish_stage1()
+    for optical, thermal in chunks():
+        est.add_stage2(optical, thermal)
+    T, rep = est.finish()
+    return T[0], dict(peak1=rep.peak1[0], second1=rep.second1[0], peak2=rep.peak2[0], second2=rep.second2[0], branch=int(rep.branch[0]))
+
+
+def main_fourier(args, out_yaml, out_report, estimator):
+    from multipoint_amd.datasets.image_file_pairs import ImageFilePairs
+    names_read = ImageFilePairs({'directory': args.input_dir}).memberslist
+    names = select_pairs(names_read, args.max_pairs)
+    if not names:
+        print('no <index>_optical.png / <index>_thermal.png pairs in %s' % args.input_dir, file=sys.stderr)
+        return 1
+    print('Using {} of {} pairs'.format(len(names), len(names_read)))
+    H, info = estimator(args, names)
+    report = build_fourier_report(names_read, names, H, info)
+    for stage in ('stage1', 'stage2'):
+        print('{}: peak {peak:.4f}  second {second:.4f}  ratio {ratio:.3f}'.format(stage, **report[stage]))
+    low = [stage for stage in ('stage1', 'stage2') if not report[stage]['ratio'] >= args.min_peak_ratio]
+    if low or 'similarity' not in report:
+        print('the correlation peak of %s is below %g times the second-highest value: nothing written'
+              % (' and '.join(low) or 'no stage', args.min_peak_ratio), file=sys.stderr)
+        return 1
+    T = perspective_from_estimate(H)
+    print('Similarity: angle {angle:.6f} rad  scale {scale:.6f}  dx {dx:.3f}  dy {dy:.3f}'.format(**report['similarity']))
+    print('Estimated similarity transform (optical -> thermal):')
+    print(np.asarray(H))
+    print('perspective (thermal -> optical):')
+    print(T)
+    with open(out_yaml, 'wt') as fh:
+        yaml.safe_dump({'perspective': [[float(v) for v in row] for row in T]}, fh)
+    with open(out_report, 'wt') as fh:
+        json.dump(report, fh, indent=1, sort_keys=True)
+    print('Wrote {} and {}'.format(out_yaml, out_report))
+    return 0
+
+
+def main(argv=None, estimator=estimate_on_gpu, fourier_estimator=estimate_fourier_on_gpu):
     args = build_parser().parse_args(argv)
+    if args.method == 'fourier':
+        if args.transform_explicit and args.transform != 'similarity':
+            print('--method fourier estimates a similarity: --transform %s is not available' % args.transform, file=sys.stderr)
+            return 2
+        args.transform = 'similarity'
     random.seed(args.seed)
     np.random.seed(args.seed)
     out_yaml = args.output or os.path.join(args.input_dir, YAML_NAME)
@@ -166,6 +284,8 @@ def main(argv=None, estimator=estimate_on_gpu):
     if os.path.exists(out_yaml) and not args.force:
         print('%s exists (it may be hand-measured): pass --force to overwrite it' % out_yaml, file=sys.stderr)
         return 2
+    if args.method == 'fourier':
+        return main_fourier(args, out_yaml, out_report, fourier_estimator)
     with open(args.yaml_config, 'r') as f:
         config = yaml.load(f, Loader=yaml.FullLoader)
     with open(os.path.join(args.model_dir, 'params.yaml'), 'r') as f:

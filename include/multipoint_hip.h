@@ -984,6 +984,45 @@ int mp_sift_describe(mp_handle* h, int B, int H, int W, int capacity, const void
 int mp_sift_scatter(mp_handle* h, const float* keypoints, const int* count, int B, int N, int H, int W, float* prob, int* owner,
                     void* stream);
 
+/* ---- Fourier-Mellin registration: a keypoint-free similarity between two frames ----
+ * The stages around mp_fft2d.  Complex planes are interleaved fp32 (re, im); every table is the caller's, computed in double
+ * and rounded once to fp32.  No entry uses float atomics: results are bit-identical from run to run.
+ *
+ * mp_register_prepare: frames fp32 [n][H][W] -> out complex [n][N][N], N >= max(H, W), imaginary part 0.  The H x W window sits at
+ * row (N - H) / 2, column (N - W) / 2 (integer divisions) of a zeroed plane.  For a window pixel (x, y) the taps (x +- 1, y) and
+ * (x, y +- 1) are mapped through the frame's similarity about its centre (cx, cy) = ((W - 1) / 2, (H - 1) / 2) --
+ *   sx = fmaf(c, px - cx, fmaf(-s, py - cy, cx)),  sy = fmaf(s, px - cx, fmaf(c, py - cy, cy)),  (c, s) = cs[frame] or (1, 0)
+ * for cs == NULL -- and sampled bilinearly; the pixel is sqrt(gx^2 + gy^2) wy[y] wx[x] with gx, gy half the tap differences, or
+ * 0 when one of the 16 source samples lies outside the frame (floor(sx) outside [0, W - 2], floor(sy) outside [0, H - 2]).
+ * wy [H], wx [W]: the window tables.
+ *
+ * mp_register_logpolar: spectrum complex [n][N][N] in FFT order -> out complex [n][A][R], imaginary part 0:
+ * log1p|F| of the fftshifted spectrum (value i of it is bin (i - N / 2) mod N) sampled bilinearly, indices modulo N, at
+ * x = fmaf(rho[r], ca[a], N / 2), y = fmaf(rho[r], sa[a], N / 2), times wr[r].  ca, sa [A]; rho, wr [R].
+ *
+ * mp_register_cross_power: a, b complex [P][hh][ww], group_offsets int32 [G + 1] non-decreasing (as mp_pool_matches writes
+ * them; clamped to [0, P]) -> out complex [G][hh][ww]: per bin the sum, in pair order, of X / |X| with X = a conj(b) over the
+ * group's pairs (0 where |X| == 0).  Bin (0, 0) is 0; an empty group gives zeros.  accumulate != 0: the sums start from the
+ * values in `out`, so a batch fed in several calls gives the bits of one call.
+ *
+ * mp_register_peak: planes [G][hh][ww], 3 <= hh, ww <= 4096, values `stride` floats apart (1: real planes, 2: the real part of
+ * complex planes).  out_i int32 [G][2]: row and column of the maximum, the first in row-major order on a tie.  out_f fp32
+ * [G][6]: the row and column offsets 0.5 (l - r) / (l - 2 c + r) of a parabola through the maximum and its wrapped neighbours
+ * (0 where the second difference is 0); row and column folded to signed form (an index above hh / 2 or ww / 2 has the size
+ * subtracted) plus the offset; the maximum; the largest value outside the wrapped 3 x 3 block around it (-inf if there is
+ * none).  Two-stage reduction over chunks of 16384 values with the same tie rule in both; the workspace holds the chunks'
+ * results (mp_register_peak_workspace_bytes).
+ * MP_EINVAL (all entries): NULL tensors, n, G outside [1, 65535], sizes outside the ranges above. */
+int mp_register_prepare(mp_handle* h, const float* frames, const float* cs, const float* wy, const float* wx, int n, int H, int W,
+                        int N, float* out, void* stream);
+int mp_register_logpolar(mp_handle* h, const float* spectrum, int n, int N, const float* ca, const float* sa, const float* rho,
+                         const float* wr, int A, int R, float* out, void* stream);
+int mp_register_cross_power(mp_handle* h, const float* a, const float* b, const int* group_offsets, int P, int G, int hh, int ww,
+                            int accumulate, float* out, void* stream);
+int mp_register_peak_workspace_bytes(int G, int hh, int ww, long long* bytes);
+int mp_register_peak(mp_handle* h, const float* planes, int G, int hh, int ww, int stride, int* out_i, float* out_f,
+                     void* workspace, long long workspace_bytes, void* stream);
+
 /* per-launch timing of mp_forward with hipEvents on the caller's stream (bench.py roofline leg).
  * mp_profile_read synchronises; names[i] points to static strings. */
 int mp_profile_enable(mp_handle* h, int enable);

@@ -592,6 +592,24 @@ void launch_lghd_describe(const unsigned char* ori, int B, int H, int W, const i
                           float* unit, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// Fourier-Mellin registration (register.hip).  Complex planes are interleaved fp32, as the FFT takes them.
+// ---------------------------------------------------------------------------------------------
+#define MP_REGISTER_PEAK_CHUNK 16384      // plane values one workgroup of the peak search reduces
+// frames [n][H][W] -> out complex [n][N][N]; cs [n][2] or NULL; wy [H], wx [W]
+void launch_register_prepare(const float* frames, const float* cs, const float* wy, const float* wx, int n, int H, int W, int N,
+                             float* out, hipStream_t s);
+// spectrum complex [n][N][N] -> out complex [n][A][R]; ca, sa [A]; rho, wr [R]
+void launch_register_logpolar(const float* spectrum, int n, int N, const float* ca, const float* sa, const float* rho,
+                              const float* wr, int A, int R, float* out, hipStream_t s);
+// a, b complex [P][h][w], group_offsets [G+1] -> out complex [G][h][w] (accumulate: the sums start from out)
+void launch_register_cross_power(const float* a, const float* b, const int* group_offsets, int P, int G, int h, int w,
+                                 int accumulate, float* out, hipStream_t s);
+int register_peak_chunks(int h, int w);
+// planes [G][h][w] values `stride` floats apart -> out_i [G][2], out_f [G][6]; partial: G * chunks (float, int) pairs
+void launch_register_peak(const float* planes, int G, int h, int w, int stride, int* out_i, float* out_f, void* partial,
+                          hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // Frame preparation (frames.hip; reference create_dataset/extract_images.py:167-242).
 // ---------------------------------------------------------------------------------------------
 struct FramesCamera {

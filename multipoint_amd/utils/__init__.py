@@ -5,3 +5,4 @@ from .evaluation import *  # noqa: F401,F403  (compute_descriptor_metrics, pair_
 from .homographies import *  # noqa: F401,F403  (homographic adaptation: export_keypoints.py)
 from .frames import *  # noqa: F401,F403  (frame preparation: prepare_images.py)
 from .drawing import *  # noqa: F401,F403  (results as pictures: keypoint, match and alignment views)
+from .registration import *  # noqa: F401,F403  (keypoint-free initial transform: Fourier-Mellin phase correlation)
