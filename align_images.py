@@ -19,6 +19,10 @@ initial_transform.yaml with the key `perspective` (3x3, thermal pixel -> optical
 
 and the method counters are printed in the reference's format (every stage that finds an alignment counts, as there).
 
+Extension: `alignment_method: ecc` (or --method ecc) runs the same stages with the Nelder-Mead search switched
+off and the gradient-based ECC candidate of multipoint_amd.utils.ecc in its place (type ecc_<feature>_<model>, the
+alignment/ecc/ keys of the yaml); --ecc keeps the search and adds that candidate next to its results.
+
 Differences: PNGs are read and written with PIL; a pair with a frame of one single value (no contrast: the mutual
 information is the same for every transform) is not handed to the optimiser but logged as failed; the affine path
 (`perspective: false`) is refused; the averaged rotation and translation the reference prints at the end are left out, they
@@ -47,6 +51,11 @@ def build_parser():
                         help='(extension) motion model the optimiser searches in; overrides the yaml key alignment/model (default '
                         'homography: all nine matrix entries).  similarity: rotation, scale and two translations; affine: the six '
                         'entries of the top two rows.  Both stay 3x3 matrices with last row (0, 0, 1) under the same warp')
+    parser.add_argument('--method', default=None, choices=['mi', 'ecc'],
+                        help='(extension) overrides the yaml key alignment_method.  ecc: the staged procedure with the Nelder-Mead '
+                        'search switched off and the ECC candidate (gradient-based, multipoint_amd.utils.ecc) in its place')
+    parser.add_argument('--ecc', action='store_true', help='(extension) with the method mi: add the ECC candidate next to the '
+                        'mutual-information ones (yaml: alignment/ecc/enable and the other alignment/ecc/ keys)')
     return parser
 
 
@@ -106,8 +115,16 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     with open(args.yaml_config, 'rt') as fh:
         params = yaml.safe_load(fh)
-    if params.get('alignment_method', 'mi') != 'mi':
+    if args.method is not None:
+        params['alignment_method'] = args.method
+    method = params.get('alignment_method', 'mi')
+    if method not in ('mi', 'ecc'):
         raise ValueError('Unkown alignment method: ' + str(params['alignment_method']))
+    if method == 'ecc':                                     # the same stages, the ECC candidate in place of the Nelder-Mead ones
+        params['alignment/run_optimization'] = False
+        params['alignment/ecc/enable'] = True
+    elif args.ecc:
+        params['alignment/ecc/enable'] = True
     import torch
     from multipoint_amd.utils import alignment
     if not params.get('perspective', True):

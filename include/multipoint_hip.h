@@ -1023,6 +1023,57 @@ int mp_register_peak_workspace_bytes(int G, int hh, int ww, long long* bytes);
 int mp_register_peak(mp_handle* h, const float* planes, int G, int hh, int ww, int stride, int* out_i, float* out_f,
                      void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- ECC direct alignment: Gauss-Newton maximisation of the enhanced correlation coefficient ----
+ * A transform is a 3x3 float64 matrix, row-major, that maps a template (thermal) pixel to an image (optical) pixel.
+ *
+ * mp_ecc_prepare: blurred fp32 [n][H][W] -> feat fp32 [n][H][W] and, if packed != NULL, packed fp32 [n][H][W][4] (16-byte
+ * aligned).  feature MP_ECC_GRADIENT: feat = sqrtf(fmaf(gx, gx, gy * gy)) with gx = 0.5f * (f[x + 1] - f[x - 1]), gy likewise
+ * along rows, BORDER_REFLECT_101 (both 0 on the border lines); MP_ECC_INTENSITY: feat = blurred.  packed holds (feat, gx, gy, 0)
+ * per pixel, gx and gy taken from feat by the same rule: the image side of the sums pass, one 16-byte load per bilinear tap.
+ *
+ * mp_ecc_sums: the raw sums of n_problems (pair[q] host int32, transforms[q] device float64 [9]) -> sums device float64
+ * [n_problems][S], S = 6 + K + K (K + 1) / 2 + 2 K for the K parameters of `model` (MP_MODEL_HOMOGRAPHY 8, _AFFINE 6, _SIMILARITY
+ * 4: a, b, tx, ty of [[a, -b, tx], [b, a, ty]], _TRANSLATION 2).  The nine entries are rounded once to fp32; for template pixel
+ * (x, y): X = fmaf(T00, x, fmaf(T01, y, T02)), Y and D likewise from rows 1 and 2, xs = X / D, ys = Y / D.  The pixel is valid iff
+ * 0 <= floor(xs) <= Wo - 2 and 0 <= floor(ys) <= Ho - 2 (a NaN fails).  w, gx, gy: the bilinear sample of packed (per component
+ * top = fmaf(fx, p01 - p00, p00), bot likewise, fmaf(fy, bot - top, top)); r the template value; G_k the fp32 Jacobian columns
+ * of DESIGN.md 3.21.  Order of the sums: n, w, r, w w, r r, w r, G_k (K), G_k G_l for k <= l row by row, G_k w (K), G_k r (K);
+ * every product is the exact float64 product of its fp32 factors, added in float64.  One workgroup adds MP_ECC_CHUNK = 4096
+ * consecutive template pixels; the order depends on (problem, pixel index) alone, so a problem has the same bits in any batch.
+ *
+ * mp_ecc_begin / mp_ecc_step / mp_ecc_result: the batched refinement.  begin takes the start matrices (device float64
+ * [n_problems][9], divided by their T22 here; a constrained model reads its parameters from them: similarity a = T00, b = T10).
+ * step enqueues n_iters iterations -- one sums launch, one solve launch -- without synchronising and then writes the number of
+ * problems still running to *live (device int32).  result: transforms [P][9], rho [P] float64; nit, status, converged int32 [P].
+ * A problem stops with status MP_ECC_OK when |rho - rho_prev| < eps (converged = 1) or after maxiter updates (converged = 0);
+ * with MP_ECC_FEW_VALID when fewer than min_valid H W pixels are valid, MP_ECC_NOT_POSITIVE when the Cholesky factorisation of
+ * G^T G fails, MP_ECC_LAMBDA when lambda's denominator is <= 0, MP_ECC_NONFINITE on a non-finite value; it keeps its last iterate.
+ * The workspace (mp_ecc_workspace_bytes) must stay untouched between begin and result.
+ * MP_EINVAL: a NULL tensor, frames outside 8 x 8 .. 4096 x 4096, n, n_pairs outside [1, 65535], n_problems outside
+ * [1, MP_ECC_MAX_PROBLEMS], a pair index outside [0, n_pairs), an unknown model or feature, eps < 0 or NaN, maxiter < 1, min_valid
+ * outside [0, 1], n_iters outside [1, 100000], a small workspace.  MP_ESTATE: step / result on a workspace other than the one of
+ * the handle's latest begin. */
+#define MP_MODEL_TRANSLATION 3      /* mp_ecc_* only */
+#define MP_ECC_GRADIENT 0
+#define MP_ECC_INTENSITY 1
+#define MP_ECC_MAX_PROBLEMS 4096
+#define MP_ECC_OK 0
+#define MP_ECC_FEW_VALID 1
+#define MP_ECC_NOT_POSITIVE 2
+#define MP_ECC_LAMBDA 3
+#define MP_ECC_NONFINITE 4
+int mp_ecc_workspace_bytes(int n_problems, int H, int W, long long* bytes);
+int mp_ecc_prepare(mp_handle* h, const float* blurred, int n, int H, int W, int feature, float* feat, float* packed, void* stream);
+int mp_ecc_sums(mp_handle* h, const float* packed, int Ho, int Wo, const float* thermal, int H, int W, int n_pairs, const int* pair,
+                const double* transforms, int n_problems, int model, double* sums, void* workspace, long long workspace_bytes,
+                void* stream);
+int mp_ecc_begin(mp_handle* h, const float* packed, int Ho, int Wo, const float* thermal, int H, int W, int n_pairs,
+                 const int* pair, const double* init_transforms, int n_problems, int model, double eps, int maxiter,
+                 double min_valid, void* workspace, long long workspace_bytes, void* stream);
+int mp_ecc_step(mp_handle* h, void* workspace, int n_iters, int* live, void* stream);
+int mp_ecc_result(mp_handle* h, void* workspace, double* transforms, double* rho, int* iterations, int* status, int* converged,
+                  void* stream);
+
 /* per-launch timing of mp_forward with hipEvents on the caller's stream (bench.py roofline leg).
  * mp_profile_read synchronises; names[i] points to static strings. */
 int mp_profile_enable(mp_handle* h, int enable);

@@ -241,6 +241,14 @@ SIGNATURES = {
                                         c_void_p]),
     'mp_register_peak_workspace_bytes': (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
     'mp_register_peak': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
+    'mp_ecc_workspace_bytes': (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
+    'mp_ecc_prepare': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'mp_ecc_sums': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_int), c_void_p, c_int,
+                            c_int, c_void_p, c_void_p, c_ll, c_void_p]),
+    'mp_ecc_begin': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_int), c_void_p, c_int,
+                             c_int, ctypes.c_double, c_int, ctypes.c_double, c_void_p, c_ll, c_void_p]),
+    'mp_ecc_step': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'mp_ecc_result': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'mp_profile_enable': (c_int, [c_void_p, c_int]),
     'mp_profile_read': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_float),
                                 ctypes.POINTER(ctypes.c_double), c_int, ctypes.POINTER(c_int)]),

@@ -107,6 +107,16 @@ struct MiRefine {
     int* nact = nullptr;
 };
 
+// the refinement mp_ecc_begin started (ecc_api.hip)
+struct EccRefine {
+    void* workspace = nullptr;
+    const float *packed = nullptr, *thermal = nullptr;
+    int Ho = 0, Wo = 0, H = 0, W = 0, P = 0, K = 0;
+    EccOptions opt{};
+    EccState* state = nullptr;
+    double* partial = nullptr;
+};
+
 }  // namespace mp_host
 
 struct mp_handle {
@@ -145,7 +155,8 @@ struct mp_handle {
     mp_host::DevBuf f16_dummy;      // scratch line for masked-off store lanes of the fp16 kernels
     int* pinned = nullptr;          // small pinned host scratch (img lists, counters)
     mp_host::MiRefine mi;           // the running mutual-information refinement (mp_mi_refine_*)
-    std::map<int, mp_host::DevBuf> fft_tw;     // FFT twiddle tables by line length (lghd_api.hip)
+    mp_host::EccRefine ecc;         // the running ECC refinement (mp_ecc_*)
+    std::map<int, mp_host::DevBuf> fft_tw;    // FFT twiddle tables by line length (lghd_api.hip)
     mp_host::DevBuf draw_ws;        // owner map of mp_draw_matches: one uint32 per canvas pixel, grow-only (draw.hip)
     std::vector<mp_host::DevBuf> draw_retired;   // ... the buffers it outgrew: a launch on another stream may still use one, so
                                                  // they live as long as the handle (each at most half its successor's size)

@@ -610,6 +610,39 @@ void launch_register_peak(const float* planes, int G, int h, int w, int stride, 
                           hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// ECC direct alignment (ecc.hip): Gauss-Newton maximisation of the enhanced correlation coefficient.
+// ---------------------------------------------------------------------------------------------
+#define MP_ECC_CHUNK 4096                 // template pixels one workgroup of the sums pass reduces
+#define MP_ECC_MAX_SUMS 66                // 6 + K + K (K + 1) / 2 + 2 K at K = 8
+#define MP_ECC_RUNNING (-1)               // EccState::status of a problem whose iterations go on
+// one problem of a running refinement
+struct EccState {
+    double T[9];                          // the current iterate (T22 == 1)
+    double rho, rho_prev;                 // the correlation at T, and at the iterate before (NaN: none)
+    int pair, nit, status, converged;     // status: MP_ECC_RUNNING or an MP_ECC_* result code
+};
+struct EccOptions { double eps, min_valid; int maxiter, pad; };
+// parameters of a motion model (MP_MODEL_*): 8, 4, 6, 2; 0 for an unknown one.  ecc_sum_count: the sums of one problem
+int ecc_model_params(int model);
+int ecc_sum_count(int K);
+int ecc_chunks(int H, int W);
+// blurred [n][H][W] -> feat [n][H][W] (gradient != 0: the magnitude of the central differences, else a copy)
+void launch_ecc_feature(const float* blurred, int n, int H, int W, int gradient, float* feat, hipStream_t s);
+// feat [n][H][W] -> packed [n][H][W][4]: (f, gx, gy, 0)
+void launch_ecc_pack(const float* feat, int n, int H, int W, float* packed, hipStream_t s);
+// One sums pass: partial [P][chunks][sums].  T != NULL: the transforms [P][9] and pair [P] of a diagnostic call; else those of
+// `state`, whose finished problems are skipped.
+void launch_ecc_sums(int K, const float* packed, int Ho, int Wo, const float* thermal, int H, int W, const int* pair,
+                     const double* T, const EccState* state, int P, double* partial, hipStream_t s);
+// partial [P][chunks][sums] -> sums [P][sums], added in chunk order
+void launch_ecc_reduce(int K, const double* partial, int P, int chunks, double* sums, hipStream_t s);
+void launch_ecc_begin(const int* pair, const double* T0, int P, EccState* state, hipStream_t s);
+// one Gauss-Newton decision per running problem from its partial sums
+void launch_ecc_solve(int K, const double* partial, int P, int chunks, int HW, EccOptions o, EccState* state, hipStream_t s);
+void launch_ecc_live(const EccState* state, int P, int* live, hipStream_t s);
+void launch_ecc_result(const EccState* state, int P, double* T, double* rho, int* nit, int* status, int* converged, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // Frame preparation (frames.hip; reference create_dataset/extract_images.py:167-242).
 // ---------------------------------------------------------------------------------------------
 struct FramesCamera {

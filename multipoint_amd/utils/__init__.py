@@ -6,3 +6,4 @@ from .homographies import *  # noqa: F401,F403  (homographic adaptation: export_
 from .frames import *  # noqa: F401,F403  (frame preparation: prepare_images.py)
 from .drawing import *  # noqa: F401,F403  (results as pictures: keypoint, match and alignment views)
 from .registration import *  # noqa: F401,F403  (keypoint-free initial transform: Fourier-Mellin phase correlation)
+from .ecc import *  # noqa: F401,F403  (ECC direct alignment on gradient images)

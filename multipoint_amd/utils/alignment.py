@@ -485,6 +485,10 @@ def align_images(optical, thermal, init_transform, params, geometric_checks=Fals
     not implemented: with the homography it raises NotImplementedError (the default applies the mutual-information check
     only).  With a constrained model it applies check_affine_geometry -- the limits of the reference's
     check_affine_transformation -- to every optimised candidate; a missing limit is a KeyError naming the key.
+    alignment/ecc/enable (extension, absent by default): each pair gets one more candidate of type
+    'ecc_<feature>_<model>' from utils.ecc.refine_alignment_ecc_batch started at its initial transform -- alignment/ecc/feature
+    ('gradient'), alignment/ecc/filter_size (5), alignment/ecc/model (alignment/model), alignment/ecc/eps (1e-6),
+    alignment/ecc/max_iterations (50) -- under the same checks and the same ranking; stats['ecc_rounds'] grows by its iterations.
     filter_images=True blurs both frames with gaussian_blur(., alignment/filter_size) first (align.py:487-489).
     Returns (transform, type, candidates) for one pair, lists of them for a batch; transform and type are None where no
     candidate is valid.  A candidate is dict(type, transform, mi={bins: score}, value, init_value, nit, nfev).  stats: a dict
@@ -536,8 +540,10 @@ def align_images(optical, thermal, init_transform, params, geometric_checks=Fals
                 cands[pair[q]].append({'type': alignment_type_name(sizes[q % len(sizes)], normalized, sigma, model),
                                        'transform': r['transform'][q].copy(), 'value': float(r['value'][q]),
                                        'init_value': float(own[q]), 'nit': int(r['nit'][q]), 'nfev': int(r['nfev'][q])})
+    if params.get('alignment/ecc/enable', False):
+        _ecc_candidates(opt, th, T0, params, model, normalized, sigma, geometric_checks, cands, stats)
     # the ranking scores are the plain negative mutual information, as align.py:531-535 and :551-555 call it
-    flat = [(b, c) for b in range(B) for c in cands[b]]
+    flat =[(b, c) for b in range(B) for c in cands[b]]
     if flat and sizes:
         pair = [b for b, _ in flat for _ in sizes]
         Ts = np.stack([c['transform'].reshape(9) for _, c in flat for _ in sizes])
@@ -554,6 +560,36 @@ def align_images(optical, thermal, init_transform, params, geometric_checks=Fals
     if single:
         return best_T[0], best_type[0], cands[0]
     return best_T, best_type, cands
+
+
+def _ecc_candidates(opt, th, T0, params, model, normalized, sigma, geometric_checks, cands, stats):
+    """alignment/ecc/enable (extension): one more candidate per pair, 'ecc_<feature>_<model>', from the ECC
+    refinement of utils.ecc started at the pair's T0.  It passes the checks of the optimised candidates -- the solver's success,
+    |MI(init) - MI(new)| at 100 bins below alignment/check/both/max_diff_mi, alignment/check/invalid_pixels, and with
+    geometric_checks and a constrained model check_affine_geometry -- and is ranked with them."""
+    from .ecc import refine_alignment_ecc_batch
+    feature = params.get('alignment/ecc/feature', 'gradient')
+    ecc_model = params.get('alignment/ecc/model', model)
+    B = opt.shape[0]
+    pair = list(range(B))
+    r = refine_alignment_ecc_batch(opt, th, pair, T0, model=ecc_model, feature=feature,
+                                   ksize=params.get('alignment/ecc/filter_size', 5), eps=params.get('alignment/ecc/eps', 1e-6),
+                                   maxiter=params.get('alignment/ecc/max_iterations', 50))
+    if stats is not None:
+        stats['ecc_rounds'] = stats.get('ecc_rounds', 0) + r['rounds']
+    both = np.concatenate([T0, r['transform'].reshape(B, 9)])
+    mi100 = _objective(opt, th, pair * 2, [100] * (2 * B), both, None, normalized, sigma).cpu().numpy()
+    inside = np.ones(B, bool)
+    if params.get('alignment/check/invalid_pixels', False):
+        _, mm, _ = joint_histograms(opt, th, pair, [1] * B, r['transform'])
+        inside = mm[:, 0].cpu().numpy() != -1.0
+    for b in range(B):
+        valid = abs(mi100[b] - mi100[B + b]) < params['alignment/check/both/max_diff_mi'] and inside[b]
+        if valid and geometric_checks and ecc_model in ('similarity', 'affine'):
+            valid = check_affine_geometry(T0[b], r['transform'][b], params)
+        if valid and r['success'][b]:
+            cands[b].append({'type': 'ecc_%s_%s' % (feature, ecc_model), 'transform': r['transform'][b].copy(),
+                             'value': float(r['rho'][b]), 'nit': int(r['nit'][b]), 'converged': bool(r['converged'][b])})
 
 
 # ---- the staged procedure of create_dataset/align_images.py:151-248 ----

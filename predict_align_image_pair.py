@@ -49,6 +49,12 @@ def build_parser():
                         'the pair under the identity, the estimated and (with --refine) the refined homography')
     parser.add_argument('--mi-refine', action='store_true', help='(extension) maximise the mutual information from the estimated '
                         'homography (utils.alignment.align_images; yaml block prediction.mi_alignment) and print the result')
+    parser.add_argument('--ecc-refine', action='store_true', help='(extension) polish the estimated homography by ECC maximisation '
+                        'on gradient images (utils.ecc.refine_alignment_ecc_batch; yaml block prediction.ecc_alignment) and print '
+                        'the result')
+    parser.add_argument('--ecc-transform', default=None, choices=['translation', 'similarity', 'affine', 'homography'],
+                        help="(extension) with --ecc-refine: the motion model; overrides prediction.ecc_alignment['model'] "
+                        '(default homography)')
     parser.add_argument('--mi-transform', default=None, choices=['homography', 'similarity', 'affine'],
                         help='(extension) with --mi-refine: motion model the mutual-information optimiser searches in; overrides '
                         "prediction.mi_alignment['alignment/model'] (default homography)")
@@ -205,6 +211,34 @@ def mi_refine(optical, thermal, H_est, pred, model=None):
     return H_mi
 
 
+ECC_ALIGNMENT_DEFAULTS = {'model': 'homography', 'feature': 'gradient', 'filter_size': 5, 'eps': 1e-6, 'max_iterations': 50,
+                          'min_valid': 0.25}
+ECC_STATUS = ('ok', 'too few valid pixels', 'G^T G not positive definite', "lambda's denominator <= 0", 'a non-finite value')
+
+
+def ecc_refine(optical, thermal, H_est, pred, model=None):
+    """--ecc-refine: utils.ecc.refine_alignment_ecc_batch from the estimate.  Prints the outcome, the correlation coefficient, the
+    iterations and the matrix in the direction of the estimate (optical -> thermal); a failed refinement returns None.  model:
+    --ecc-transform in the place of the block's model."""
+    from multipoint_amd.utils import ecc
+    params = dict(ECC_ALIGNMENT_DEFAULTS, **(pred.get('ecc_alignment') or {}))
+    if model is not None:
+        params['model'] = model
+    r = ecc.refine_alignment_ecc_batch(optical[0, 0], thermal[0, 0], [0], estimate_to_transform(H_est)[None], params['model'],
+                                       params['feature'], params['filter_size'], params['eps'], params['max_iterations'],
+                                       params['min_valid'])
+    if not r['success'][0]:
+        print('ECC alignment: none ({} after {} iterations)'.format(ECC_STATUS[int(r['status'][0])], int(r['nit'][0])))
+        return None
+    print('ECC alignment: {} {} rho {:.6f} after {} iterations ({})'.format(
+        params['feature'], params['model'], float(r['rho'][0]), int(r['nit'][0]),
+        'converged' if r['converged'][0] else 'iteration limit'))
+    H_ecc = estimate_to_transform(r['transform'][0])
+    print('ECC-aligned Homography:')
+    print(H_ecc)
+    return H_ecc
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     random.seed(args.seed)
@@ -290,7 +324,7 @@ def main(argv=None):
         print('Two forward passes took: {} s'.format(t_2 - t_1))
         print('Box nms: {} s'.format(t_3 - t_2))
 
-        if args.plot or args.save_npz or args.refine or args.mi or args.mi_refine:
+        if args.plot or args.save_npz or args.refine or args.mi or args.mi_refine or args.ecc_refine:
             H, W = data['optical']['image'].shape[2:]
             thr = pred['detection_threshold']
             pred_optical = torch.nonzero((out_optical['prob'][0].squeeze() > thr).float())
@@ -348,6 +382,10 @@ def main(argv=None):
             H_mi = None
             if args.mi_refine:
                 H_mi = mi_refine(data['optical']['image'][:1], data['thermal']['image'][:1], H_est, pred, args.mi_transform)
+            if args.ecc_refine:
+                H_ecc = ecc_refine(data['optical']['image'][:1], data['thermal']['image'][:1], H_est if H_mi is None else H_mi,
+                                   pred, args.ecc_transform)
+                H_mi = H_mi if H_ecc is None else H_ecc
             print('Ground Truth Homography:')
             print(H_gt)
             print('--------------------------------------------------------')
@@ -371,7 +409,7 @@ def main(argv=None):
                                     **({'kp_optical_sub': kpo_est.astype(np.float32), 'kp_thermal_sub': kpt_est.astype(np.float32)}
                                        if subpixel else {}))
             if args.plot and args.plot_dir:
-                # under the final estimate: the refined one with --refine, the MI-aligned one with --mi-refine
+                # under the final estimate: the refined one with --refine, the MI- or ECC-aligned one with --mi-refine / --ecc-refine
                 names = write_plots(args.plot_dir, data['optical']['image'][:1], data['thermal']['image'][:1], kpo, kpt, matches,
                                     mask, H_est if H_mi is None else H_mi, args.radius)
                 print('Wrote {} to {}'.format(', '.join(names), args.plot_dir))
