@@ -33,6 +33,22 @@ used, `similarity`, and per stage the peak of the pooled correlation surface, th
 and their ratio, and `branch_180`, whether the theta + pi candidate won.  When either ratio is below --min-peak-ratio nothing is
 written and the exit status is 1.  The default floor of 1.1 is a guess: no recording was available to set it on.
 
+--ecc-refine refines the estimate of either method over ALL selected pairs at once: the pooled ECC refinement of
+multipoint_amd.utils.estimate_shared_transform_ecc, one group, started from the float64 inverse of the estimate
+(thermal -> optical), under --ecc-transform similarity | affine | homography (default homography: many pairs under one transform
+determine the eight parameters a single pair does not) on gradient magnitudes blurred with --ecc-filter-size.  The pairs are read
+once more in --batch chunks into resident feature planes.  --method ecc --init YAML does the same from an existing
+initial_transform.yaml, a hand measurement for instance (-m and -v are ignored).  --auto-mask excludes the pixels of each camera
+whose value never changes over the pairs read (the black margin undistortion leaves, a burnt-in overlay), --thermal-mask PNG /
+--optical-mask PNG give such masks as 8-bit images (nonzero = use; with --auto-mask the two are intersected); the excluded sets
+are grown by the features' support.  After the first run the pairs whose own correlation is below --ecc-reject-ratio times the
+median are dropped and the rest runs once more (0: off; the default of 0.5 is a guess like --min-peak-ratio).  The yaml is
+written from the refined transform when the refinement succeeded, else from the estimate as without the flag (--method ecc
+then writes nothing and exits with 1); the exit status stays that of the estimate.  The report gains `ecc`: model, feature,
+filter_size, rho_start, rho_end, iterations, status, rounds, success, per pair rho, valid_share and rejected, the share of
+pixels each mask keeps after growth, and corner_shift, the largest displacement in optical pixels of a thermal corner
+between the estimate and the refined transform.
+
 Not known: how well this works on real thermal / optical recordings -- no such data and no trained weights are in this
 repository; everything is verified on synthetic and planted data.  Look at the report (and at check_alignment.py's pictures)
 before trusting the file."""
@@ -74,12 +90,25 @@ def build_parser():
                         help='Motion model of the estimate: the 8-parameter homography, a similarity (rotation, scale, two translations: '
                         'what a rigid rig is close to, and what few inliers still determine) or an affine transform')
     parser.add_argument('--force', action='store_true', help='Overwrite an existing yaml file (it may be hand-measured)')
-    parser.add_argument('--method', default='matches', choices=['matches', 'fourier'],
+    parser.add_argument('--method', default='matches', choices=['matches', 'fourier', 'ecc'],
                         help='matches: pooled keypoint matches of a network or baseline; fourier: keypoint-free Fourier-Mellin phase '
-                        'correlation of the gradient magnitudes, a similarity only (no network: -m and -v are ignored)')
+                        'correlation of the gradient magnitudes, a similarity only (no network: -m and -v are ignored); ecc: the '
+                        'pooled ECC refinement of the transform in --init (no network either)')
     parser.add_argument('--min-peak-ratio', default=1.1, type=float,
                         help='--method fourier: write nothing when the highest value of a correlation surface is below this many times '
                         'the second-highest (a guess: not set on a real recording)')
+    parser.add_argument('--ecc-refine', action='store_true', help='Refine the estimate over all selected pairs with the pooled ECC '
+                        'refinement (implied by --method ecc)')
+    parser.add_argument('--ecc-transform', default='homography', choices=['similarity', 'affine', 'homography'],
+                        help='Motion model of the ECC refinement')
+    parser.add_argument('--ecc-filter-size', default=5, type=int, help='Gaussian blur in front of the gradient magnitude (odd, 1: none)')
+    parser.add_argument('--ecc-reject-ratio', default=0.5, type=float,
+                        help='Drop the pairs whose correlation is below this many times the median after the first run and run once '
+                        'more (0: off; a guess: not set on a real recording)')
+    parser.add_argument('--init', default=None, help='--method ecc: the yaml file whose `perspective` the refinement starts from')
+    parser.add_argument('--auto-mask', action='store_true', help='ECC: exclude the pixels of each camera that never change over the pairs read')
+    parser.add_argument('--thermal-mask', default=None, help='ECC: 8-bit image of the thermal size, nonzero = use')
+    parser.add_argument('--optical-mask', default=None, help='ECC: 8-bit image of the optical size, nonzero = use')
     parser.set_defaults(transform_explicit=False)
     return parser
 
@@ -239,7 +268,102 @@ def estimate_fourier_on_gpu(args, names):
     return T[0], dict(peak1=rep.peak1[0], second1=rep.second1[0], peak2=rep.peak2[0], second2=rep.second2[0], branch=int(rep.branch[0]))
 
 
-def main_fourier(args, out_yaml, out_report, estimator):
+def read_mask(path):
+    """An 8-bit mask image as a uint8 array (H, W), nonzero = use."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return (np.array(im.convert('L'), np.uint8) != 0).astype(np.uint8)
+
+
+def refine_ecc_on_gpu(args, names, T_est):
+    """The pooled ECC refinement of T_est (3x3 float64, thermal -> optical) over the pairs `names`, read once in --batch chunks
+    into resident feature planes, one group.  Returns (T refined 3x3 float64 with h22 = 1, the report's `ecc` object)."""
+    import torch
+
+    from multipoint_amd import _lib
+    from multipoint_amd.datasets.image_file_pairs import read_png_pair
+    from multipoint_amd.utils import SharedEccProblem, alignment
+    device = _lib.require_cuda()
+    print('Refining on device: {}'.format(device))
+    batch = max(args.batch, 1)
+    prob = SharedEccProblem('gradient', args.ecc_filter_size, auto_mask=args.auto_mask)
+    for at in range(0, len(names), batch):
+        pairs = [read_png_pair(args.input_dir, n) for n in names[at:at + batch]]
+        if len({p[0].shape[:2] for p in pairs}) != 1 or len({p[1].shape for p in pairs}) != 1:
+            raise ValueError('all optical frames of a directory must have one size, and all thermal frames one size')
+        optical = torch.stack([alignment.frames_to_float(p[0], device, single_bgr=p[0].ndim == 3) for p in pairs])
+        thermal = alignment.frames_to_float(np.stack([p[1] for p in pairs]), device).reshape(len(pairs), *pairs[0][1].shape)
+        prob.add(optical.contiguous(), thermal.contiguous())
+    prob.finish(None if args.thermal_mask is None else read_mask(args.thermal_mask),
+                None if args.optical_mask is None else read_mask(args.optical_mask))
+    rho_start = prob.correlation(T_est)[0][0]
+    r = prob.refine(T_est, args.ecc_transform, reject_ratio=args.ecc_reject_ratio)
+    T = r.transform[0] / r.transform[0][2, 2]
+    H, W = prob.thw
+    corners = np.array([[0, 0, 1], [W - 1, 0, 1], [0, H - 1, 1], [W - 1, H - 1, 1]], np.float64).T
+    a, b = np.asarray(T_est, np.float64) @ corners, T @ corners
+    kept = float(H * W) * prob.thermal_kept[0]
+
+    def number(v):
+        return float(v) if np.isfinite(v) else None
+
+    report = {
+        'model': args.ecc_transform, 'feature': 'gradient', 'filter_size': int(args.ecc_filter_size),
+        'rho_start': number(rho_start), 'rho_end': number(r.rho[0]), 'iterations': int(r.nit[0]), 'status': int(r.status[0]),
+        'success': bool(r.success[0]), 'converged': bool(r.converged[0]), 'rounds': int(r.rounds),
+        'reject_ratio': float(args.ecc_reject_ratio),
+        'pairs': {n: {'rho': number(r.rho_pair[i]), 'valid_share': float(r.valid_pair[i]) / max(kept, 1.0),
+                      'rejected': bool(r.rejected[i])} for i, n in enumerate(names)},
+        'thermal_mask_kept': float(prob.thermal_kept[0]), 'optical_mask_kept': float(prob.optical_kept[0]),
+        'corner_shift': float(np.max(np.hypot(*(a[:2] / a[2] - b[:2] / b[2])))) if r.success[0] else None,
+    }
+    return T, report
+
+
+def apply_ecc(args, names, T_est, refiner):
+    """(the transform to write, the report's `ecc` object): the refined transform when the refinement succeeded, else T_est."""
+    T, ecc = refiner(args, names, T_est)
+    print('ECC {model}: rho {rho_start} -> {rho_end}  iterations {iterations}  status {status}  rounds {rounds}'.format(**ecc))
+    rejected = [n for n, v in ecc['pairs'].items() if v['rejected']]
+    if rejected:
+        print('ECC rejected pairs: {}'.format(' '.join(rejected)))
+    if not ecc['success']:
+        print('the ECC refinement failed (status %d): the estimate is kept' % ecc['status'], file=sys.stderr)
+        return T_est, ecc
+    print('ECC moved the thermal corners by at most {:.3f} optical px'.format(ecc['corner_shift']))
+    return np.asarray(T, np.float64), ecc
+
+
+def main_ecc(args, out_yaml, out_report, refiner):
+    """--method ecc: the refinement alone, from the `perspective` of --init."""
+    from multipoint_amd.datasets.image_file_pairs import ImageFilePairs
+    with open(args.init, 'r') as fh:
+        T_est = np.array(yaml.safe_load(fh)['perspective'], np.float64)
+    if T_est.shape != (3, 3) or not np.isfinite(T_est).all() or T_est[2, 2] == 0:
+        print('%s holds no 3x3 `perspective`' % args.init, file=sys.stderr)
+        return 2
+    names_read = ImageFilePairs({'directory': args.input_dir}).memberslist
+    names = select_pairs(names_read, args.max_pairs)
+    if not names:
+        print('no <index>_optical.png / <index>_thermal.png pairs in %s' % args.input_dir, file=sys.stderr)
+        return 1
+    print('Using {} of {} pairs'.format(len(names), len(names_read)))
+    T, ecc = apply_ecc(args, names, T_est / T_est[2, 2], refiner)
+    report = {'method': 'ecc', 'transform': args.ecc_transform, 'pairs_read': len(names_read), 'pairs_used': len(names), 'ecc': ecc}
+    if not ecc['success']:
+        print('nothing written', file=sys.stderr)
+        return 1
+    print('perspective (thermal -> optical):')
+    print(T)
+    with open(out_yaml, 'wt') as fh:
+        yaml.safe_dump({'perspective': [[float(v) for v in row] for row in T]}, fh)
+    with open(out_report, 'wt') as fh:
+        json.dump(report, fh, indent=1, sort_keys=True)
+    print('Wrote {} and {}'.format(out_yaml, out_report))
+    return 0
+
+
+def main_fourier(args, out_yaml, out_report, estimator, refiner=refine_ecc_on_gpu):
     from multipoint_amd.datasets.image_file_pairs import ImageFilePairs
     names_read = ImageFilePairs({'directory': args.input_dir}).memberslist
     names = select_pairs(names_read, args.max_pairs)
@@ -260,6 +384,8 @@ def main_fourier(args, out_yaml, out_report, estimator):
     print('Similarity: angle {angle:.6f} rad  scale {scale:.6f}  dx {dx:.3f}  dy {dy:.3f}'.format(**report['similarity']))
     print('Estimated similarity transform (optical -> thermal):')
     print(np.asarray(H))
+    if args.ecc_refine:
+        T, report['ecc'] = apply_ecc(args, names, T, refiner)
     print('perspective (thermal -> optical):')
     print(T)
     with open(out_yaml, 'wt') as fh:
@@ -270,8 +396,23 @@ def main_fourier(args, out_yaml, out_report, estimator):
     return 0
 
 
-def main(argv=None, estimator=estimate_on_gpu, fourier_estimator=estimate_fourier_on_gpu):
+def main(argv=None, estimator=estimate_on_gpu, fourier_estimator=estimate_fourier_on_gpu, ecc_refiner=refine_ecc_on_gpu):
     args = build_parser().parse_args(argv)
+    if args.method == 'ecc':
+        if not args.init:
+            print('--method ecc refines an existing transform: --init YAML is required', file=sys.stderr)
+            return 2
+        args.ecc_refine = True
+    elif args.init:
+        print('--init belongs to --method ecc', file=sys.stderr)
+        return 2
+    if not args.ecc_refine and (args.auto_mask or args.thermal_mask or args.optical_mask):
+        print('--auto-mask, --thermal-mask and --optical-mask belong to --ecc-refine and --method ecc', file=sys.stderr)
+        return 2
+    if args.ecc_refine and (args.ecc_filter_size % 2 == 0 or not 1 <= args.ecc_filter_size <= 31
+                            or not 0.0 <= args.ecc_reject_ratio <= 1.0):
+        print('--ecc-filter-size must be odd and in [1, 31], --ecc-reject-ratio in [0, 1]', file=sys.stderr)
+        return 2
     if args.method == 'fourier':
         if args.transform_explicit and args.transform != 'similarity':
             print('--method fourier estimates a similarity: --transform %s is not available' % args.transform, file=sys.stderr)
@@ -285,7 +426,9 @@ def main(argv=None, estimator=estimate_on_gpu, fourier_estimator=estimate_fourie
         print('%s exists (it may be hand-measured): pass --force to overwrite it' % out_yaml, file=sys.stderr)
         return 2
     if args.method == 'fourier':
-        return main_fourier(args, out_yaml, out_report, fourier_estimator)
+        return main_fourier(args, out_yaml, out_report, fourier_estimator, ecc_refiner)
+    if args.method == 'ecc':
+        return main_ecc(args, out_yaml, out_report, ecc_refiner)
     with open(args.yaml_config, 'r') as f:
         config = yaml.load(f, Loader=yaml.FullLoader)
     with open(os.path.join(args.model_dir, 'params.yaml'), 'r') as f:
@@ -312,6 +455,8 @@ def main(argv=None, estimator=estimate_on_gpu, fourier_estimator=estimate_fourie
     print('Estimated Homography (optical -> thermal):' if args.transform == 'homography' else
           'Estimated %s transform (optical -> thermal):' % args.transform)
     print(np.asarray(H))
+    if args.ecc_refine:
+        T, report['ecc'] = apply_ecc(args, names, T, ecc_refiner)
     print('perspective (thermal -> optical):')
     print(T)
     with open(out_yaml, 'wt') as fh:

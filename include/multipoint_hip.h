@@ -1074,6 +1074,59 @@ int mp_ecc_step(mp_handle* h, void* workspace, int n_iters, int* live, void* str
 int mp_ecc_result(mp_handle* h, void* workspace, double* transforms, double* rho, int* iterations, int* status, int* converged,
                   void* stream);
 
+/* ---- Pooled ECC: one transform per group of pairs, static masks, per-pair correlations ----
+ * Features, motion models, per-pixel terms, the raw sums and their order are those of mp_ecc_*.  A pair is one optical and one
+ * thermal frame with the same index; group[p] (host int32 [n_pairs]) names the group whose transform T_g it shares.  Every mask
+ * is a uint8 plane, nonzero = use.
+ *
+ * mp_ecc_mask_grow: masks [n][H][W] -> out [n][H][W], 0 at every pixel within Chebyshev distance `radius` of a 0 of the input
+ * (clipped at the frame, no reflection; radius 0 copies zero / nonzero as 0 / 1; a radius larger than the frame is allowed), else
+ * 1.  tmp [n][H][W] holds the row pass.  The template's masks are grown by R_t = ksize / 2 + 1 for MP_ECC_GRADIENT, ksize / 2 for
+ * MP_ECC_INTENSITY, the image's by R_t + 1 (the packed plane differentiates the feature frame once more).
+ * mp_ecc_static_update: the running minimum lo and maximum hi (fp32 [H][W]) of every pixel over frames fp32 [n][H][W]; first != 0
+ * starts them from frames[0], so the frames of a recording may arrive in any number of batches.  mp_ecc_static_finish: mask =
+ * 0 where lo == hi, else 1: a pixel that never changed is excluded.
+ * mp_ecc_flag_packed: writes 1.0f into the fourth component of packed [n][H][W][4] where the mask of the frame is 0: masks
+ * [n_masks][H][W], mask_of_frame host int32 [n] (-1: the frame has none).  Run it after mp_ecc_prepare, with grown masks.
+ *
+ * mp_ecc_pooled_sums: the raw sums of every pair at the transform of its group (transforms device float64 [n_groups][9]) -> sums
+ * device float64 [n_pairs][S] as mp_ecc_sums, over the valid pixels whose template pixel is kept by the group's thermal mask
+ * (thermal_masks [n_masks][H][W] grown, mask_of_group host int32 [n_groups], -1 or a NULL list: none) and whose four bilinear taps
+ * all have a zero fourth component.  Skipped pixels count in no sum.  With no mask the sums of a pair have the bits of mp_ecc_sums.
+ *
+ * mp_ecc_pooled_begin / _step / _result: the refinement.  At every evaluation, per pair (over its own pixels): wbar = Sw / n, rbar =
+ * Sr / n, ww = Sww - n wbar^2, rr = Srr - n rbar^2, corr = Swr - n wbar rbar, A = S G_k G_l, ip_k = S G_k w - wbar S G_k, tp_k = S G_k r -
+ * rbar S G_k.  A pair is included iff it is active (active host int32 [n_pairs], NULL: all), n >= min_valid M (M: the template
+ * pixels its group's mask keeps, H W without one), all its sums are finite, ww > 0 and rr > 0; rho_i = corr / (sqrt ww sqrt rr),
+ * NaN for a pair that is not included.  Per group the included pairs' quantities are added in ascending pair index, rho = C /
+ * (sqrt WW sqrt RR), and the step, its order of decisions and the status codes are those of mp_ecc_step, with MP_ECC_FEW_VALID for a
+ * group without an included pair.  step enqueues n_iters iterations -- a sums launch over (chunk, pair), a pair launch, a group
+ * launch -- without synchronising, then writes the number of groups still running to *live (device int32).  result, per group:
+ * transforms [G][9], rho [G] float64; iterations, status, converged, n_included int32 [G]; per pair at the group's latest
+ * evaluation: rho_pair, n_pair float64 [n_pairs], included int32 [n_pairs].  A group's bits depend on its own ordered pair list
+ * alone; an excluded pair adds nothing.
+ * MP_EINVAL: the limits of mp_ecc_*, n_groups outside [1, MP_ECC_MAX_PROBLEMS], a group index outside [0, n_groups), a group
+ * without a pair, a mask index outside [-1, n_masks), a negative radius, tmp aliasing, a small workspace
+ * (mp_ecc_pooled_workspace_bytes).  MP_ESTATE: step / result on a workspace other than the one of the handle's latest
+ * mp_ecc_pooled_begin. */
+int mp_ecc_mask_grow(mp_handle* h, const unsigned char* masks, int n, int H, int W, int radius, unsigned char* tmp, unsigned char* out,
+                     void* stream);
+int mp_ecc_static_update(mp_handle* h, const float* frames, int n, int H, int W, int first, float* lo, float* hi, void* stream);
+int mp_ecc_static_finish(mp_handle* h, const float* lo, const float* hi, int H, int W, unsigned char* mask, void* stream);
+int mp_ecc_flag_packed(mp_handle* h, float* packed, int n, int H, int W, const unsigned char* masks, int n_masks,
+                       const int* mask_of_frame, void* stream);
+int mp_ecc_pooled_workspace_bytes(int n_pairs, int n_groups, int H, int W, long long* bytes);
+int mp_ecc_pooled_sums(mp_handle* h, const float* packed, int Ho, int Wo, const float* thermal, int H, int W, int n_pairs,
+                       const int* group, int n_groups, const double* transforms, const unsigned char* thermal_masks, int n_masks,
+                       const int* mask_of_group, int model, double* sums, void* workspace, long long workspace_bytes, void* stream);
+int mp_ecc_pooled_begin(mp_handle* h, const float* packed, int Ho, int Wo, const float* thermal, int H, int W, int n_pairs,
+                        const int* group, const int* active, int n_groups, const double* init_transforms,
+                        const unsigned char* thermal_masks, int n_masks, const int* mask_of_group, int model, double eps, int maxiter,
+                        double min_valid, void* workspace, long long workspace_bytes, void* stream);
+int mp_ecc_pooled_step(mp_handle* h, void* workspace, int n_iters, int* live, void* stream);
+int mp_ecc_pooled_result(mp_handle* h, void* workspace, double* transforms, double* rho, int* iterations, int* status, int* converged,
+                         int* n_included, double* rho_pair, double* n_pair, int* included, void* stream);
+
 /* per-launch timing of mp_forward with hipEvents on the caller's stream (bench.py roofline leg).
  * mp_profile_read synchronises; names[i] points to static strings. */
 int mp_profile_enable(mp_handle* h, int enable);

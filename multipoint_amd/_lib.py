@@ -249,6 +249,19 @@ SIGNATURES = {
                              c_int, ctypes.c_double, c_int, ctypes.c_double, c_void_p, c_ll, c_void_p]),
     'mp_ecc_step': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'mp_ecc_result': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'mp_ecc_mask_grow': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'mp_ecc_static_update': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'mp_ecc_static_finish': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    'mp_ecc_flag_packed': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, ctypes.POINTER(c_int), c_void_p]),
+    'mp_ecc_pooled_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
+    'mp_ecc_pooled_sums': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int,
+                                   c_void_p, c_void_p, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_ll, c_void_p]),
+    'mp_ecc_pooled_begin': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_int),
+                                    ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int), c_int,
+                                    ctypes.c_double, c_int, ctypes.c_double, c_void_p, c_ll, c_void_p]),
+    'mp_ecc_pooled_step': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'mp_ecc_pooled_result': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p]),
     'mp_profile_enable': (c_int, [c_void_p, c_int]),
     'mp_profile_read': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_float),
                                 ctypes.POINTER(ctypes.c_double), c_int, ctypes.POINTER(c_int)]),

@@ -117,6 +117,19 @@ struct EccRefine {
     double* partial = nullptr;
 };
 
+// the pooled refinement mp_ecc_pooled_begin started (ecc_pooled_api.hip)
+struct EccPooledRefine {
+    void* workspace = nullptr;
+    const float *packed = nullptr, *thermal = nullptr;
+    const unsigned char* tmasks = nullptr;
+    int Ho = 0, Wo = 0, H = 0, W = 0, P = 0, G = 0, K = 0;
+    EccOptions opt{};
+    const int *group = nullptr, *active = nullptr, *offsets = nullptr, *list = nullptr, *tmask = nullptr;
+    EccGroup* groups = nullptr;
+    EccPairRec* recs = nullptr;
+    double *partial = nullptr, *quant = nullptr;
+};
+
 }  // namespace mp_host
 
 struct mp_handle {
@@ -156,6 +169,7 @@ struct mp_handle {
     int* pinned = nullptr;          // small pinned host scratch (img lists, counters)
     mp_host::MiRefine mi;           // the running mutual-information refinement (mp_mi_refine_*)
     mp_host::EccRefine ecc;         // the running ECC refinement (mp_ecc_*)
+    mp_host::EccPooledRefine ecc_pooled;   // the running pooled ECC refinement (mp_ecc_pooled_*)
     std::map<int, mp_host::DevBuf> fft_tw;    // FFT twiddle tables by line length (lghd_api.hip)
     mp_host::DevBuf draw_ws;        // owner map of mp_draw_matches: one uint32 per canvas pixel, grow-only (draw.hip)
     std::vector<mp_host::DevBuf> draw_retired;   // ... the buffers it outgrew: a launch on another stream may still use one, so

@@ -643,6 +643,45 @@ void launch_ecc_live(const EccState* state, int P, int* live, hipStream_t s);
 void launch_ecc_result(const EccState* state, int P, double* T, double* rho, int* nit, int* status, int* converged, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// Pooled ECC (ecc_pooled.hip): one transform per group of pairs, static masks.
+// ---------------------------------------------------------------------------------------------
+#define MP_ECC_POOLED_MAX_Q 55            // centred quantities of one pair: ww, rr, corr, A (K (K + 1) / 2), ip (K), tp (K) at K = 8
+// one group of a running pooled refinement
+struct EccGroup {
+    EccState s;                           // the group's iterate and stop state (s.pair: the group's index)
+    int M;                                // template pixels the group's thermal mask keeps (H W without one)
+    int n_included;                       // pairs included at the latest evaluation
+};
+// one pair at the latest evaluation of its group
+struct EccPairRec { double rho, n; int included, pad; };
+// use-masks in [n][H][W] (nonzero: use) -> out: 0 within Chebyshev distance R of a zero of `in`, else 1; tmp [n][H][W]
+void launch_ecc_mask_grow(const unsigned char* in, int n, int H, int W, int R, unsigned char* tmp, unsigned char* out, hipStream_t s);
+// running minimum and maximum per pixel over frames [n][HW]; first != 0 starts them from the first frame
+void launch_ecc_static_update(const float* frames, int n, int HW, int first, float* lo, float* hi, hipStream_t s);
+// mask = lo == hi ? 0 : 1
+void launch_ecc_static_finish(const float* lo, const float* hi, int HW, unsigned char* mask, hipStream_t s);
+// packed [n][HW][4]: .w = 1.0f where mask [HW] is 0 (the same mask for the n frames)
+void launch_ecc_flag_packed(float* packed, int n, int HW, const unsigned char* mask, hipStream_t s);
+// One pooled sums pass: partial [P][chunks][sums] of pair p at the transform of its group.  T != NULL: the transforms [G][9] of a
+// diagnostic call; else those of `groups`, whose finished groups and inactive pairs are skipped.  tmasks [.][H][W] use-masks of
+// the template, tmask [G] the plane of every group (-1: none).
+void launch_ecc_pooled_sums(int K, const float* packed, int Ho, int Wo, const float* thermal, int H, int W,
+                            const unsigned char* tmasks, const int* tmask, const int* group, const int* active, const double* T,
+                            const EccGroup* groups, int P, double* partial, hipStream_t s);
+void launch_ecc_pooled_begin(const double* T0, const unsigned char* tmasks, const int* tmask, int HW, int G, int P, EccGroup* groups,
+                             EccPairRec* recs, hipStream_t s);
+// per pair: the chunks added in order, the centred quantities quant [P][MP_ECC_POOLED_MAX_Q], the inclusion decision, recs
+void launch_ecc_pooled_pair(int K, const double* partial, int P, int chunks, const int* group, const int* active, EccOptions o,
+                            const EccGroup* groups, EccPairRec* recs, double* quant, hipStream_t s);
+// per group: the included pairs' quantities added in list order (offsets [G + 1], list [P]), then the decision of 3.21
+void launch_ecc_pooled_solve(int K, const int* offsets, const int* list, const EccPairRec* recs, const double* quant, int G,
+                             EccOptions o, EccGroup* groups, hipStream_t s);
+void launch_ecc_pooled_live(const EccGroup* groups, int G, int* live, hipStream_t s);
+void launch_ecc_pooled_result(const EccGroup* groups, int G, const EccPairRec* recs, int P, double* T, double* rho, int* nit,
+                              int* status, int* converged, int* n_included, double* rho_pair, double* n_pair, int* included,
+                              hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // Frame preparation (frames.hip; reference create_dataset/extract_images.py:167-242).
 // ---------------------------------------------------------------------------------------------
 struct FramesCamera {
