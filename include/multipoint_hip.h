@@ -880,6 +880,19 @@ int mp_draw_matches(mp_handle* h, const int* kp_a, const int* kp_b, const int* c
                     const unsigned char* draw_mask, int P, int K, int ya, int xa, int yb, int xb, int radius, int thickness,
                     const unsigned char* palette, int n_colors, unsigned char* canvas, int Hc, int Wc, void* stream);
 
+/* mp_segments_draw: a list of line segments per canvas (the needle map of the residual field).  segments int32
+ * [B][N][MP_DRAW_SEGMENT_INTS] rows of (y0, x0, y1, x1, colour), seg_count int32 [B]: the first min(seg_count[b], N) rows of canvas b
+ * exist.  Segment i covers, for every pixel (x, y) of mp_draw_matches' line walk from (x0, y0) to (x1, y1) -- clipLine to the canvas,
+ * then the LineIterator from the left end; a zero-length segment is its one pixel -- the box [x - (t - 1) / 2, x + t / 2] x
+ * [y - (t - 1) / 2, y + t / 2] for thickness t, clipped to the canvas.  A pixel takes palette[colour mod n_colors] of the HIGHEST i
+ * covering it, through the owner map of mp_draw_matches (one call at a time per handle).
+ * MP_EINVAL: a NULL tensor, B outside [1, 65535], a canvas side outside [1, 32767], N outside [1, 2^20], thickness outside
+ * [1, MP_DRAW_MAX_THICKNESS], n_colors < 1.  MP_ENOMEM: the owner map. */
+#define MP_DRAW_SEGMENT_INTS 5
+#define MP_DRAW_MAX_THICKNESS 15
+int mp_segments_draw(mp_handle* h, const int* segments, const int* seg_count, int B, int N, int thickness,
+                     const unsigned char* palette, int n_colors, unsigned char* canvas, int Hc, int Wc, void* stream);
+
 /* mp_draw_compose: alignment views of a warped optical frame and a thermal frame, both fp32 [B][H][W], at canvas offset
  * (y0, x0).  T = u8(thermal); a pixel with warped < 0 (the -1 border of mp_mi_joint_histogram's warp) is outside: A = 0 there,
  * A = u8(warped) elsewhere.
@@ -1126,6 +1139,36 @@ int mp_ecc_pooled_begin(mp_handle* h, const float* packed, int Ho, int Wo, const
 int mp_ecc_pooled_step(mp_handle* h, void* workspace, int n_iters, int* live, void* stream);
 int mp_ecc_pooled_result(mp_handle* h, void* workspace, double* transforms, double* rho, int* iterations, int* status, int* converged,
                          int* n_included, double* rho_pair, double* n_pair, int* included, void* stream);
+
+/* ---- Local residual field: windowed correlation of an aligned pair ----
+ * optical_feat (the aligned optical frames) and thermal_feat: fp32 [B][H][W] outputs of mp_ecc_prepare; mask: uint8 [mask_frames][H][W]
+ * on the optical side with mask_frames 1 (one plane for every frame) or B, nonzero = use, or NULL (all ones).
+ * Windows of window x window pixels have their origins at y0 = radius + i stride for every i with y0 + window + radius <= H, and
+ * likewise in x: mp_residual_grid gives their counts gy, gx.  The score of a displacement d = (dy, dx), |dy|, |dx| <= radius, is
+ * taken over S_d = {p in the window: mask[p + d] != 0}, n = |S_d|: the zero-mean normalised cross-correlation of thermal_feat[p]
+ * and optical_feat[p + d] from the sums St, So, Stt, Soo, Sto (fp32 products, float64 sums): mt = St / n, mo = So / n,
+ * ctt = Stt - mt St, coo = Soo - mo So, cto = Sto - mt So, score = cto / (sqrt(ctt) sqrt(coo)).  It is undefined when
+ * n < min_valid window^2 or when ctt or coo is <= var_floor n.  thermal_feat[p] ~ optical_feat[p + d]: d is the residual
+ * misalignment of the optical frame at that window, in pixels.
+ * Per window (row-major over (frame, window row, window column)): out_d float64 [..][5] = (dy, dx, rho, rho0, second), out_i int32
+ * [..][2] = (n, status).  d* is the defined displacement with the largest score, ties to the first in row-major (dy, dx) order from
+ * -radius; an axis on which |d*| < radius and both neighbours' scores a, c are defined is refined by 0.5 (a - c) / (a - 2 rho + c)
+ * (0 when the denominator is not negative, clamped to +-0.5); rho is the score at d*, rho0 the one at d = 0 (NaN if undefined), second
+ * the largest defined score outside the 3 x 3 block around d* (-inf when there is none), n the count at d*.
+ * status: MP_RES_FEW_VALID when d = 0 has n < min_valid window^2; else MP_RES_FLAT when no displacement is defined; else
+ * MP_RES_AT_EDGE when d* touches the search border on some axis, else MP_RES_OK.  The first two leave NaN in out_d and the count of
+ * d = 0 in n.  A window's bits depend on its own pixels and the parameters alone.
+ * MP_EINVAL: window outside {8, 16, 24, 32, 48, 64}, stride < 1, radius outside [1, 8], min_valid outside (0, 1], var_floor negative or
+ * not finite, B outside [1, 65535], frames outside 8 x 8 .. 4096 x 4096, a frame that holds no window, mask_frames other than 1 or
+ * B.  Nothing is launched then. */
+#define MP_RES_OK 0
+#define MP_RES_FEW_VALID 1
+#define MP_RES_FLAT 2
+#define MP_RES_AT_EDGE 3
+int mp_residual_grid(int H, int W, int window, int stride, int radius, int* gy, int* gx);
+int mp_residual_field(mp_handle* h, const float* optical_feat, const float* thermal_feat, const unsigned char* mask, int mask_frames,
+                      int B, int H, int W, int window, int stride, int radius, double min_valid, double var_floor, double* out_d,
+                      int* out_i, void* stream);
 
 /* per-launch timing of mp_forward with hipEvents on the caller's stream (bench.py roofline leg).
  * mp_profile_read synchronises; names[i] points to static strings. */

@@ -8,6 +8,8 @@
 //   draw_matches_scatter_kernel   one workgroup per match: its two rings (the lanes share the rows) and its LINE_8 segment
 //                          (lane 0 walks it) are written as atomicMax(index + 1) into the handle's owner map
 //   draw_resolve_kernel    every canvas pixel with an owner takes that match's colour
+//   draw_segments_scatter_kernel / draw_segments_resolve_kernel   the same two steps for a list of segments per canvas: the
+//                          LineIterator walk, every pixel widened to a t x t box, each segment in the colour it names
 // Every pixel write is checked against the canvas; centres and offsets are added in 64 bits.
 #include "host.h"
 #include "mp_raster.h"
@@ -228,6 +230,37 @@ __global__ __launch_bounds__(256) void draw_resolve_kernel(const unsigned* owner
     d[0] = c[0], d[1] = c[1], d[2] = c[2];
 }
 
+// one workgroup per segment: lane 0 walks it and tags the t x t box of every pixel of the walk in the owner map
+__global__ __launch_bounds__(64) void draw_segments_scatter_kernel(const int* seg, const int* counts, int N, int t, unsigned* owner,
+                                                                   int Hc, int Wc)
+{
+    const int b = blockIdx.y, i = blockIdx.x;
+    if (threadIdx.x != 0 || i >= min(max(counts[b], 0), N)) return;
+    const int* e = seg + ((long long)b * N + i) * MP_DRAW_SEGMENT_INTS;
+    unsigned* map = owner + (long long)b * Hc * Wc;
+    const unsigned tag = (unsigned)i + 1u;
+    const int lo = (t - 1) / 2, hi = t / 2;
+    thin_line(Hc, Wc, e[1], e[0], e[3], e[2], [&](int x, int y) {
+        for (int yy = max(y - lo, 0); yy <= min(y + hi, Hc - 1); ++yy)
+            for (int xx = max(x - lo, 0); xx <= min(x + hi, Wc - 1); ++xx) atomicMax(map + (long long)yy * Wc + xx, tag);
+    });
+}
+
+// every canvas pixel with an owner takes the colour that segment names
+__global__ __launch_bounds__(256) void draw_segments_resolve_kernel(const unsigned* owner, const int* seg, int N, long long per_canvas,
+                                                                    long long pixels, const unsigned char* palette, int npal,
+                                                                    unsigned char* canvas)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pixels) return;
+    const unsigned o = owner[i];
+    if (!o) return;
+    const int ci = seg[((i / per_canvas) * N + (o - 1u)) * MP_DRAW_SEGMENT_INTS + 4];
+    const unsigned char* c = palette + 3 * (((ci % npal) + npal) % npal);
+    unsigned char* d = canvas + 3 * i;
+    d[0] = c[0], d[1] = c[1], d[2] = c[2];
+}
+
 bool frames_ok(int n, int H, int W) { return n > 0 && n <= 65535 && H > 0 && W > 0 && H <= 32767 && W <= 32767; }
 
 unsigned blocks_of(long long items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
@@ -316,6 +349,29 @@ int mp_draw_matches(mp_handle* h, const int* kp_a, const int* kp_b, const int* c
     hipLaunchKernelGGL(draw_matches_scatter_kernel, dim3(K, P), dim3(64), 0, s, kp_a, kp_b, count_a, count_b, match_idx, draw_mask,
                        K, ya, xa, yb, xb, ro, ri, owner, Hc, Wc);
     hipLaunchKernelGGL(draw_resolve_kernel, dim3(blocks_of(pixels, 256)), dim3(256), 0, s, owner, pixels, palette, n_colors, canvas);
+    return launch_status(h);
+}
+
+int mp_segments_draw(mp_handle* h, const int* segments, const int* seg_count, int B, int N, int thickness,
+                     const unsigned char* palette, int n_colors, unsigned char* canvas, int Hc, int Wc, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!segments || !seg_count || !palette || !canvas) return fail(h, MP_EINVAL, "mp_segments_draw: NULL tensor");
+    if (!frames_ok(B, Hc, Wc) || N < 1 || N > MAX_LIST)
+        return fail(h, MP_EINVAL, "mp_segments_draw: 1 to 65535 canvases of 1 x 1 to 32767 x 32767 pixels, N in [1, 2^20]");
+    if (n_colors < 1) return fail(h, MP_EINVAL, "mp_segments_draw: empty palette");
+    if (thickness < 1 || thickness > MP_DRAW_MAX_THICKNESS)
+        return fail(h, MP_EINVAL, "mp_segments_draw: thickness in [1, " + std::to_string(MP_DRAW_MAX_THICKNESS) + "]");
+    MP_HIP(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long long pixels = (long long)B * Hc * Wc;
+    const int rc = owner_map(h, (size_t)pixels * sizeof(unsigned));
+    if (rc != MP_OK) return rc;
+    unsigned* owner = static_cast<unsigned*>(h->draw_ws.p);
+    MP_HIP(hipMemsetAsync(owner, 0, (size_t)pixels * sizeof(unsigned), s));
+    hipLaunchKernelGGL(draw_segments_scatter_kernel, dim3(N, B), dim3(64), 0, s, segments, seg_count, N, thickness, owner, Hc, Wc);
+    hipLaunchKernelGGL(draw_segments_resolve_kernel, dim3(blocks_of(pixels, 256)), dim3(256), 0, s, owner, segments, N,
+                       (long long)Hc * Wc, pixels, palette, n_colors, canvas);
     return launch_status(h);
 }
 

@@ -682,6 +682,28 @@ void launch_ecc_pooled_result(const EccGroup* groups, int G, const EccPairRec* r
                               hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// Local residual field (residual.hip): windowed zero-mean normalised cross-correlation of two feature frames.
+// ---------------------------------------------------------------------------------------------
+// status of a window (include/multipoint_hip.h repeats them for the callers)
+#define MP_RES_OK 0                       // a best displacement inside the search border
+#define MP_RES_FEW_VALID 1                // the mask leaves displacement 0 fewer than min_valid w^2 pixels
+#define MP_RES_FLAT 2                     // no displacement has a defined score
+#define MP_RES_AT_EDGE 3                  // a best displacement that touches the search border on some axis
+#define MP_RES_MAX_RADIUS 8
+struct ResidualParams {
+    const float* fo;                      // [B][H][W] optical feature frames (the search side)
+    const float* ft;                      // [B][H][W] thermal feature frames (the template side)
+    const unsigned char* mask;            // [mask_frames][H][W] on the optical side, nonzero = use, or NULL
+    int mask_frames;                      // 1: one plane for every frame, else B
+    int H, W, w, s, r, gy, gx;            // window edge, stride, search radius, windows per column / row
+    double min_valid, var_floor;
+    double* out_d;                        // [B][gy gx][5]: dy, dx, rho, rho0, second
+    int* out_i;                           // [B][gy gx][2]: n, status
+};
+size_t residual_lds_bytes(int w, int r);
+void launch_residual_field(const ResidualParams& p, int B, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // Frame preparation (frames.hip; reference create_dataset/extract_images.py:167-242).
 // ---------------------------------------------------------------------------------------------
 struct FramesCamera {

@@ -7,3 +7,4 @@ from .frames import *  # noqa: F401,F403  (frame preparation: prepare_images.py)
 from .drawing import *  # noqa: F401,F403  (results as pictures: keypoint, match and alignment views)
 from .registration import *  # noqa: F401,F403  (keypoint-free initial transform: Fourier-Mellin phase correlation)
 from .ecc import *  # noqa: F401,F403  (ECC direct alignment on gradient images)
+from .residual import *  # noqa: F401,F403  (local residual field: windowed correlation to pre-screen aligned pairs)

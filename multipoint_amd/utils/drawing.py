@@ -8,6 +8,7 @@ machines have no display).  The drawing rules are DESIGN.md 3.14 and include/mul
     draw_matches(optical, thermal, kp_optical, kp_thermal, match_idx, ...)       -> (P, H, 2 W, 3), optical | thermal
     draw_pair_results(res, images, mask=None, ...)                                the same from a PairResults, all on the device
     compose(a, t, mode, alpha=128, cell=32) / alignment_views(optical, thermal, transform, modes, ...)
+    draw_segments(canvas, segments, ...) / draw_residual_field(canvas, field, frame, scale=4, ...)   needle maps
     match_palette(n=64), save_png(path, rgb), save_gif(path, frames, dt_ms)
 
 Marks are 8-connected (OpenCV's Circle() and LineIterator), one colour per mark, the highest index on top; the reference's
@@ -22,7 +23,7 @@ from .. import _lib
 from . import alignment
 
 __all__ = ['gray_to_rgb', 'draw_keypoints', 'draw_matches', 'draw_pair_results', 'match_palette', 'alignment_views', 'compose',
-           'save_png', 'save_gif']
+           'save_png', 'save_gif', 'draw_segments', 'draw_residual_field']
 
 _palettes = {}
 
@@ -238,6 +239,56 @@ def alignment_views(optical, thermal, transform, modes=('checker', 'anaglyph'), 
     o = alignment._frames(optical, 'optical')
     warped = alignment.warp_image(o[:, None], transform, t.shape[1], t.shape[2])[:, 0]
     return {mode: compose(warped, t, mode, alpha, cell) for mode in modes}
+
+
+def draw_segments(canvas, segments, seg_count=None, thickness=1, palette=((0, 255, 0),)):
+    """Line segments, in place; returns `canvas` (uint8 CUDA (B, H, W, 3) or (H, W, 3)).  segments: (B, N, 5) rows of
+    (y0, x0, y1, x1, colour) with seg_count (B,) rows in use (None: all N), or one (N, 5) list for a single canvas.  Segment i
+    is the 8-connected walk of draw_matches' lines (clipped to the canvas; a zero-length segment is one pixel), every pixel
+    widened to a thickness x thickness box, in palette[colour % n] with the highest i on top.  ValueError: thickness outside
+    [1, 15], an empty palette."""
+    c = _canvas(canvas)
+    seg = _int32(segments, c.device)
+    if seg.dim() == 2 and seg.shape[1] == 5 and c.shape[0] == 1:
+        seg = seg[None]
+    if seg.dim() != 3 or seg.shape[0] != c.shape[0] or seg.shape[2] != 5:
+        raise ValueError('segments must be (B, N, 5) for the %d canvases, or one (N, 5) list for a single canvas, got %s'
+                         % (c.shape[0], tuple(seg.shape)))
+    B, N = seg.shape[:2]
+    pal = _palette(palette, c.device)
+    if N == 0 and pal.shape[0]:
+        return canvas
+    cnt = _counts(seg_count, B, N, c.device, 'seg_count')
+    h = _lib.get_handle(c.device)
+    h.check(h.lib.mp_segments_draw(h.ptr, _lib.ptr(seg), _lib.ptr(cnt), B, N, int(thickness), _lib.ptr(pal) if pal.shape[0] else None,
+                                   pal.shape[0], _lib.ptr(c), c.shape[1], c.shape[2], _lib.stream_ptr(c.device)))
+    return canvas
+
+
+def draw_residual_field(canvas, field, frame=0, scale=4, min_rho=None, min_margin=None, tol_px=None, thickness=1, offset=(0, 0)):
+    """The needle map of frame `frame` of a residual field (utils.residual.residual_field) on one canvas (uint8 CUDA (H, W, 3)),
+    in place: every confident window (utils.residual.confident_windows) gets a segment from its centre c = origin + window // 2
+    to c + rint(scale * d), green when |d| <= tol_px and red otherwise; every other window a grey ring of radius 2 at c.  The
+    thresholds default to utils.residual.RESIDUAL_THRESHOLDS; `offset` = (y0, x0) is added to every centre."""
+    from . import residual
+    t = residual.RESIDUAL_THRESHOLDS
+    min_rho, min_margin, tol_px = (t[k] if v is None else v for k, v in (('min_rho', min_rho), ('min_margin', min_margin),
+                                                                           ('tol_px', tol_px)))
+    c = _canvas(canvas)
+    if c.shape[0] != 1:
+        raise ValueError('draw_residual_field draws one frame on one canvas (H, W, 3)')
+    conf = residual.confident_windows(field, min_rho, min_margin)[frame].reshape(-1)
+    centre = (np.asarray(field['origin']).reshape(-1, 2) + int(field['window']) // 2 + np.asarray(offset, np.int64)).astype(np.int64)
+    d = np.asarray(field['d'], np.float64)[frame].reshape(-1, 2)
+    if (~conf).any():
+        draw_keypoints(c, centre[~conf][None], radius=2, color=(128, 128, 128), kind='ring')
+    if conf.any():
+        dc = d[conf]
+        tip = centre[conf] + np.rint(float(scale) * dc).astype(np.int64)
+        colour = (np.hypot(dc[:, 0], dc[:, 1]) > float(tol_px)).astype(np.int64)
+        seg = np.concatenate([centre[conf], tip, colour[:, None]], 1)
+        draw_segments(c, seg[None], thickness=thickness, palette=((0, 255, 0), (255, 0, 0)))
+    return canvas
 
 
 def _host_image(rgb):
