@@ -86,6 +86,11 @@ def build_parser():
     parser.add_argument('--max-iters', default=2000, type=int, help='RANSAC hypotheses')
     parser.add_argument('--subpixel', action='store_true', help='Refine the keypoints to sub-pixel positions on the detector map '
                         '(prediction.subpixel.enable): the pooled matches then hold float positions')
+    parser.add_argument('--topk-mode', default=None, choices=['score', 'anms'],
+                        help="--method matches: which prediction.topk keypoints are kept -- 'score' the highest scores (default), "
+                        "'anms' the largest suppression radii, spread over the frame; overrides prediction.topk_mode")
+    parser.add_argument('--anms-robust', default=None, type=float,
+                        help="with topk_mode 'anms': the robustness factor in (0, 1]; overrides prediction.anms_robust (default 1.0)")
     parser.add_argument('--transform', default='homography', choices=['homography', 'similarity', 'affine'], action=_ExplicitTransform,
                         help='Motion model of the estimate: the 8-parameter homography, a similarity (rotation, scale, two translations: '
                         'what a rigid rig is close to, and what few inliers still determine) or an affine transform')
@@ -178,6 +183,11 @@ def estimate_on_gpu(args, config, names):
     pred = config['prediction']
     if getattr(args, 'subpixel', False):
         pred = dict(pred, subpixel=dict(pred.get('subpixel') or {}, enable=True))
+    if getattr(args, 'topk_mode', None) is not None:
+        pred = dict(pred, topk_mode=args.topk_mode)
+    if getattr(args, 'anms_robust', None) is not None:
+        pred = dict(pred, anms_robust=args.anms_robust)
+    utils.topk_selection(pred)              # (refuses an unknown mode, or 'anms' with topk 0, before the network is loaded)
     net = load_network(config, args.model_dir, args.version, device, args.seed)
     pipe = PairPipeline(net, pred)
     pts, counts = [], []

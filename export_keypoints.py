@@ -17,7 +17,7 @@ import yaml
 
 import multipoint_amd.datasets as datasets
 import multipoint_amd.utils as utils
-from predict_align_image_pair import load_network, select_device
+from predict_align_image_pair import add_topk_mode_arguments, apply_topk_mode_arguments, load_network, select_device
 
 
 def build_parser():
@@ -29,6 +29,7 @@ def build_parser():
     parser.add_argument('-snms', '--single-nms', action='store_true', help='Do the nms calculation for each sample separately')
     parser.add_argument('-skip', dest='skip_processed', action='store_true', help='Skip already processed samples')
     parser.add_argument('-s', '--seed', default=None, type=int, help='Seed of the homography sampler (numpy)')
+    add_topk_mode_arguments(parser)
     return parser
 
 
@@ -85,6 +86,7 @@ def main(argv=None):
         config = yaml.load(f, Loader=yaml.FullLoader)
     with open(os.path.join(args.model_dir, 'params.yaml'), 'r') as f:
         config['model'] = yaml.load(f, Loader=yaml.FullLoader)['model']      # overwrite the model params
+    select = apply_topk_mode_arguments(args, config['prediction'])          # (refuses a bad mode before any work)
     if args.seed is not None:
         np.random.seed(args.seed)
 
@@ -112,7 +114,7 @@ def main(argv=None):
             # the suppression, so -snms gives the same lists as the batched call
             if pred['nms'] > 0:
                 kp, _, cnt = utils.detect_keypoints(prob_ha, pred['nms'], pred['detection_threshold'],
-                                                    keep_top_k=pred['topk'])
+                                                    keep_top_k=pred['topk'], **select)
             else:
                 kp, _, cnt = utils.extract_keypoints(prob_ha, pred['detection_threshold'])
             kp, cnt = kp.cpu().numpy(), cnt.cpu().numpy()

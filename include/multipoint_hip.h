@@ -149,6 +149,36 @@ int mp_detect_keypoints(mp_handle* h, const float* prob, const unsigned char* va
                         int W, float size, float min_prob, double iou, int keep_top_k, int K,
                         int* kp_yx, float* kp_score, int* kp_count, int max_rounds, void* stream);
 
+/* ---- spatially uniform top-k: adaptive non-maximal suppression (an extension; Brown, Szeliski and Winder 2005) ----
+ * The reference keeps the keep_top_k highest scores, which all land in one corner when the texture does.  The spread entries
+ * keep the keep_top_k candidates with the largest suppression radius instead.  Per image, with the NMS survivors in row-major
+ * order (y_i, x_i, s_i), i < n, and c = robust (fp32, 0 < c <= 1):
+ *   dominance  j dominates i iff s_i < c * s_j, the product being ONE fp32 multiply; equal scores never dominate each other,
+ *              and with c < 1 a score exactly equal to c * s_j is not dominated
+ *   radius     R_i = min over the dominators j of (y_i - y_j)^2 + (x_i - x_j)^2 as a uint32 (< 2^25 at 4096 x 4096);
+ *              R_i = 0xFFFFFFFF when nothing dominates i
+ *   selection  order by (R descending, score bits descending, row-major index ascending) and keep the first min(keep_top_k, n);
+ *              n <= keep_top_k keeps every survivor, as the score entries do
+ * The output contract is that of mp_box_nms / mp_detect_keypoints: kept keypoints in row-major order, kp_score their scores,
+ * kp_count their number, rows at or beyond K not stored, the dense prob_nms the kept scores and zeros elsewhere.
+ *   kp_radius2  uint32 [B][K] or NULL: R of every stored keypoint
+ * Refused with MP_EINVAL before any launch, outputs untouched: robust outside (0, 1] or not finite, keep_top_k <= 0, and what
+ * mp_box_nms / mp_detect_keypoints refuse.
+ * Tie guards: of the three conditions behind mp_topk_ambiguous, the plateau at the score cut and the exact-tie split describe
+ * a cut on scores and are NOT evaluated by the spread entries; the footprint tie guard is, unchanged.
+ * mp_suppression_radii: R alone for any integer keypoint list (mp_detect_keypoints', mp_extract_keypoints', a classic
+ * detector's): kp_yx [B][K][2] with 0 <= y, x < 32768, kp_score [B][K] positive, kp_count [B] (a count above K is clamped), 0 < B <= 65535;
+ * radius2 uint32 [B][K], rows at or beyond the count are not written.  No result depends on B or on the launch geometry. */
+int mp_box_nms_spread(mp_handle* h, const float* prob, const unsigned char* valid_mask, int B, int H, int W,
+                      float size, float min_prob, double iou, int keep_top_k, float* prob_nms,
+                      int max_rounds, float robust, void* stream);
+int mp_detect_keypoints_spread(mp_handle* h, const float* prob, const unsigned char* valid_mask, int B, int H,
+                               int W, float size, float min_prob, double iou, int keep_top_k, int K,
+                               int* kp_yx, float* kp_score, int* kp_count, int max_rounds, float robust,
+                               unsigned* kp_radius2, void* stream);
+int mp_suppression_radii(mp_handle* h, const int* kp_yx, const float* kp_score, const int* kp_count, int B, int K,
+                         float robust, unsigned* radius2, void* stream);
+
 /* number of still-undecided NMS candidates summed over all mp_box_nms / mp_detect_keypoints calls since
  * the previous mp_nms_unresolved (0 = every result exact); resets the counter.  Synchronises `stream`. */
 int mp_nms_unresolved(mp_handle* h, int* unresolved, void* stream);

@@ -94,6 +94,12 @@ SIGNATURES = {
                            c_int, c_void_p, c_int, c_void_p]),
     'mp_detect_keypoints': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
                                     ctypes.c_double, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    'mp_box_nms_spread': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, ctypes.c_double,
+                                  c_int, c_void_p, c_int, c_float, c_void_p]),
+    'mp_detect_keypoints_spread': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
+                                           ctypes.c_double, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float,
+                                           c_void_p, c_void_p]),
+    'mp_suppression_radii': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
     'mp_nms_unresolved': (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
     'mp_topk_tie_guard': (c_int, [c_void_p, c_float, c_int]),
     'mp_nms_tie_guard': (c_int, [c_void_p, c_int]),

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ_DIR = os.path.join(CSRC, '_build')
 LIB_PATH = os.path.join(HERE, 'libmultipoint_hip.so')
-SOURCES = ['conv_mfma.hip', 'conv_wino43.hip', 'conv_wino43b.hip', 'conv_split.hip', 'conv_f16.hip', 'conv_f16_res.hip', 'conv_first.hip', 'heads_post.hip', 'head_tail.hip', 'head_tail_f16.hip', 'nms.hip', 'keypoints.hip', 'keypoints_subpixel.hip',
+SOURCES = ['conv_mfma.hip', 'conv_wino43.hip', 'conv_wino43b.hip', 'conv_split.hip', 'conv_f16.hip', 'conv_f16_res.hip', 'conv_first.hip', 'heads_post.hip', 'head_tail.hip', 'head_tail_f16.hip', 'nms.hip', 'keypoints.hip', 'keypoints_subpixel.hip', 'keypoints_spread.hip',
            'sample_desc.hip', 'match_mfma.hip', 'match_guided.hip', 'match_extra.hip', 'pair_metrics.hip', 'detector_metrics.hip', 'homography.hip', 'homography_f.hip', 'homography_pooled.hip', 'transform.hip', 'transform_f.hip', 'transform_pooled.hip', 'homog_adapt.hip', 'losses.hip', 'batchnorm_stats.hip', 'photometric.hip', 'shapes.hip', 'api.hip',
            'model_load.hip', 'forward.hip', 'post_api.hip', 'mutual_info.hip', 'align_api.hip', 'pyramid.hip', 'fft.hip', 'lghd.hip', 'lghd_api.hip', 'sift.hip', 'sift_api.hip', 'frames.hip',
            'frames_api.hip', 'draw.hip', 'register.hip', 'register_api.hip', 'ecc.hip', 'ecc_api.hip', 'ecc_pooled.hip', 'ecc_pooled_api.hip',
@@ -87,7 +87,8 @@ def check_dma_hazards(asm_path, wait_states=5):
 SCRATCH_CAPS = {'conv_mfma.hip': 0, 'conv_wino43.hip': 0, 'conv_wino43b.hip': 136, 'conv_split.hip': 0, 'conv_f16.hip': 12,
                 'conv_f16_res.hip': 0, 'conv_first.hip': 0, 'head_tail.hip': 0, 'head_tail_f16.hip': 0, 'losses.hip': 0,
                 'batchnorm_stats.hip': 0, 'photometric.hip': 0, 'shapes.hip': 0, 'match_mfma.hip': 0, 'match_guided.hip': 0, 'mutual_info.hip': 0, 'pyramid.hip': 0, 'fft.hip': 0, 'lghd.hip': 0, 'sift.hip': 0,
-                'frames.hip': 0, 'draw.hip': 0, 'register.hip': 0, 'ecc.hip': 0, 'ecc_pooled.hip': 0, 'residual.hip': 0}
+                'frames.hip': 0, 'draw.hip': 0, 'register.hip': 0, 'ecc.hip': 0, 'ecc_pooled.hip': 0, 'residual.hip': 0,
+                'keypoints_spread.hip': 0}
 
 
 def check_scratch(asm_path, cap):

@@ -335,6 +335,18 @@ size_t keypoint_scratch_ints(int B, int H, int W);
 void launch_extract_threshold(const float* map, const unsigned char* mask, int B, int H, int W, float thr, int K, int* kp_yx,
                               float* kp_score, int* kp_count, int* seg_scratch, hipStream_t s);
 
+// spatially uniform top-k (keypoints_spread.hip): adaptive non-maximal suppression.  radius2 [B][K] uint32 of a keypoint list
+// (kp_yx [B][K][2], kp_score [B][K], kp_count [B]): squared distance to the nearest entry j with s_i < robust * s_j (one fp32
+// multiply), 0xFFFFFFFF without one; rows beyond min(kp_count[b], K) are not written
+void launch_suppression_radii(const int* kp_yx, const float* kp_score, const int* kp_count, int B, int K, float robust,
+                              unsigned* radius2, hipStream_t s);
+// ... and the selection on the row-major survivor list launch_select_keypoints left behind (list_idx / list_score / list_count;
+// list_r2 [B][list_cap] is scratch): the topk entries first by (radius desc, score desc, index asc), outputs as
+// launch_select_keypoints' plus kp_radius2 [B][K] (may be NULL).  prob_nms must already be zero.
+void launch_select_spread(int B, int H, int W, int topk, int K, const int* list_idx, const float* list_score, unsigned* list_r2,
+                          int list_cap, const int* list_count, float robust, int* kp_yx, float* kp_score, unsigned* kp_radius2,
+                          int* kp_count, float* prob_nms, int Wout, hipStream_t s);
+
 // sub-pixel keypoints (keypoints_subpixel.hip): a separable log-parabola fit on the detector map around every list entry;
 // kp_sub_yx [B][K][2] fp32 (y, x), rows beyond min(kp_count[b], K) zero
 void launch_refine_keypoints(const float* prob, int B, int H, int W, const int* kp_yx, const int* kp_count, int K,

@@ -37,12 +37,24 @@ bool footprint(float size, double iou, NmsFootprint& fp)
     return true;
 }
 
+// how the survivors of the suppression are cut down to keep_top_k
+enum SelectMode {
+    SELECT_SCORE = 0,       // the k highest scores (keypoints.hip)
+    SELECT_SPREAD = 1       // the k largest suppression radii (adaptive non-maximal suppression, keypoints_spread.hip)
+};
+
+bool robust_ok(float robust) { return std::isfinite(robust) && robust > 0.f && robust <= 1.f; }
+
 int nms_common(mp_handle* h, const float* prob, const unsigned char* mask, int B, int H, int Wc,
                float size, float min_prob, double iou, int topk, int K, int* kp_yx, float* kp_score,
-               int* kp_count, float* prob_nms, int max_rounds, hipStream_t s)
+               int* kp_count, float* prob_nms, int max_rounds, hipStream_t s, SelectMode mode = SELECT_SCORE, float robust = 1.f,
+               unsigned* kp_radius2 = nullptr)
 {
     if (B <= 0 || H <= 0 || Wc <= 0)
         return fail(h, MP_EINVAL, "box_nms: need B,H,W > 0");
+    const bool spread = mode == SELECT_SPREAD;
+    if (spread && !robust_ok(robust)) return fail(h, MP_EINVAL, "box_nms (spread): robust must be in (0, 1]");
+    if (spread && topk <= 0) return fail(h, MP_EINVAL, "box_nms (spread): keep_top_k must be positive");
     NmsFootprint fp{};
     if (!footprint(size, iou, fp))
         return fail(h, MP_EINVAL, "box_nms: box size > " + std::to_string(MP_NMS_MAX_R + 1) + " unsupported");
@@ -52,8 +64,8 @@ int nms_common(mp_handle* h, const float* prob, const unsigned char* mask, int B
     const int W = (Wc + 3) & ~3;
     const long long n = (long long)B * H * W;
     const int ntiles = B * ((W + 31) / 32) * ((H + 31) / 32);
-    // workspace: work map | list_idx | list_score
-    const size_t bytes = (size_t)n * 4 * 3;
+    // workspace: work map | list_idx | list_score | (spread mode) list_r2
+    const size_t bytes = (size_t)n * 4 * (spread ? 4 : 3);
     int rc;
     if ((rc = ensure(h, h->nms_ws, bytes))) return rc;
     if ((rc = ensure(h, h->nms_state, (size_t)(64 + 2 * ntiles) * 4))) return rc;
@@ -94,16 +106,29 @@ int nms_common(mp_handle* h, const float* prob, const unsigned char* mask, int B
     if ((rc = ensure_zeroed(h, h->nms_total, 4, s))) return rc;
     launch_nms_accumulate(remaining, B, H, W, round - 1, static_cast<int*>(h->nms_total.p), s);
     int* tie = nullptr;
-    if ((topk > 0 && h->tie_min > 0) || pairs) {
+    // (spread mode: the plateau and exact-tie conditions describe a score cut and are not evaluated; the footprint guard is)
+    if ((!spread && topk > 0 && h->tie_min > 0) || pairs) {
         if ((rc = ensure_zeroed(h, h->tie_state, (1 + MP_TIE_MAX_IMAGES) * 4, s))) return rc;
         tie = static_cast<int*>(h->tie_state.p);
         h->tie_last_B = B < MP_TIE_MAX_IMAGES ? B : MP_TIE_MAX_IMAGES;
     } else {
         h->tie_last_B = 0;
     }
-    launch_select_keypoints(work, B, H, W, topk, K, list_idx, list_score, H * W, kp_yx, kp_score, kp_count,
-                            prob_nms, static_cast<int*>(h->kp_scratch.p), s, h->tie_eps, topk > 0 ? h->tie_min : 0, tie, Wc,
-                            pairs, h->tie_pairs_min);
+    if (!spread) {
+        launch_select_keypoints(work, B, H, W, topk, K, list_idx, list_score, H * W, kp_yx, kp_score, kp_count,
+                                prob_nms, static_cast<int*>(h->kp_scratch.p), s, h->tie_eps, topk > 0 ? h->tie_min : 0, tie, Wc,
+                                pairs, h->tie_pairs_min);
+    } else {
+        // keypoints.hip's compaction with its own selection idle (no cut, no outputs): it leaves the row-major survivor list and
+        // its length (the last B ints of the scratch) and evaluates the footprint guard; the spread kernels select from that list
+        int* scratch = static_cast<int*>(h->kp_scratch.p);
+        launch_select_keypoints(work, B, H, W, 0, 0, list_idx, list_score, H * W, nullptr, nullptr, nullptr, nullptr, scratch, s,
+                                h->tie_eps, 0, tie, Wc, pairs, h->tie_pairs_min);
+        if (prob_nms) MP_HIP(hipMemsetAsync(prob_nms, 0, (size_t)B * H * Wc * sizeof(float), s));
+        launch_select_spread(B, H, W, topk, K, list_idx, list_score, reinterpret_cast<unsigned*>(work + 3 * n), H * W,
+                             scratch + keypoint_scratch_ints(B, H, W) - B, robust, kp_yx, kp_score, kp_radius2, kp_count, prob_nms,
+                             Wc, s);
+    }
     MP_HIP(hipGetLastError());
     if (max_rounds == 0 && round >= cap) {
         MP_HIP(hipMemcpyAsync(h->pinned, remaining + ((round - 1) & 63), 4, hipMemcpyDeviceToHost, s));
@@ -137,6 +162,41 @@ int mp_detect_keypoints(mp_handle* h, const float* prob, const unsigned char* va
     MP_HIP(hipSetDevice(h->device));
     return nms_common(h, prob, valid_mask, B, H, W, size, min_prob, iou, keep_top_k, K, kp_yx, kp_score,
                       kp_count, nullptr, max_rounds, static_cast<hipStream_t>(stream));
+}
+
+int mp_box_nms_spread(mp_handle* h, const float* prob, const unsigned char* valid_mask, int B, int H, int W,
+                      float size, float min_prob, double iou, int keep_top_k, float* prob_nms, int max_rounds,
+                      float robust, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!prob || !prob_nms) return fail(h, MP_EINVAL, "mp_box_nms_spread: NULL tensor");
+    MP_HIP(hipSetDevice(h->device));
+    return nms_common(h, prob, valid_mask, B, H, W, size, min_prob, iou, keep_top_k, 0, nullptr, nullptr,
+                      nullptr, prob_nms, max_rounds, static_cast<hipStream_t>(stream), SELECT_SPREAD, robust);
+}
+
+int mp_detect_keypoints_spread(mp_handle* h, const float* prob, const unsigned char* valid_mask, int B, int H,
+                               int W, float size, float min_prob, double iou, int keep_top_k, int K, int* kp_yx,
+                               float* kp_score, int* kp_count, int max_rounds, float robust, unsigned* kp_radius2,
+                               void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!prob || !kp_yx || !kp_count || K <= 0) return fail(h, MP_EINVAL, "mp_detect_keypoints_spread: bad argument");
+    MP_HIP(hipSetDevice(h->device));
+    return nms_common(h, prob, valid_mask, B, H, W, size, min_prob, iou, keep_top_k, K, kp_yx, kp_score,
+                      kp_count, nullptr, max_rounds, static_cast<hipStream_t>(stream), SELECT_SPREAD, robust, kp_radius2);
+}
+
+int mp_suppression_radii(mp_handle* h, const int* kp_yx, const float* kp_score, const int* kp_count, int B, int K,
+                         float robust, unsigned* radius2, void* stream)
+{
+    if (!h) return MP_EINVAL;
+    if (!kp_yx || !kp_score || !kp_count || !radius2) return fail(h, MP_EINVAL, "mp_suppression_radii: NULL tensor");
+    if (B <= 0 || B > 65535 || K <= 0) return fail(h, MP_EINVAL, "mp_suppression_radii: need 0 < B <= 65535 and K > 0");
+    if (!robust_ok(robust)) return fail(h, MP_EINVAL, "mp_suppression_radii: robust must be in (0, 1]");
+    MP_HIP(hipSetDevice(h->device));
+    launch_suppression_radii(kp_yx, kp_score, kp_count, B, K, robust, radius2, static_cast<hipStream_t>(stream));
+    return launch_status(h);
 }
 
 int mp_nms_unresolved(mp_handle* h, int* unresolved, void* stream)

@@ -96,6 +96,13 @@ class PairPipeline:
         self.nms = config.get('nms', 4)
         self.thr = config.get('detection_threshold', 0.015)
         self.topk = config.get('topk', 0)
+        # prediction.topk_mode: score | anms (an extension): which `topk` survivors are kept -- the highest scores, or the largest
+        # suppression radii (adaptive non-maximal suppression with prediction.anms_robust in (0, 1], utils.detect_keypoints)
+        self._select = U.topk_selection(config)         # (keyword arguments of detect_keypoints; none in the score mode)
+        self.topk_mode = self._select.get('topk_mode', 'score')
+        self.anms_robust = self._select.get('anms_robust', 1.0)
+        if self._select and self.nms <= 0:
+            raise ValueError("topk_mode 'anms' selects among the NMS survivors: it needs nms above 0")
         self.capacity = capacity
         self.nms_rounds = nms_rounds
         # prediction.subpixel: {enable: false} (an extension): the keypoint lists are refined on the forward's map
@@ -233,7 +240,7 @@ class PairPipeline:
             K = capacity or self.capacity or (self.topk if self.topk > 0 else 4096)
             kp, sc, cnt = U.detect_keypoints(prob, self.nms, self.thr, keep_top_k=self.topk, capacity=K,
                                              valid_mask=valid_mask,
-                                             max_rounds=self.nms_rounds if nms_rounds is None else nms_rounds)
+                                             max_rounds=self.nms_rounds if nms_rounds is None else nms_rounds, **self._select)
         else:
             kp, sc, cnt = U.extract_keypoints(prob, self.thr, capacity=capacity or self.capacity or 4096, valid_mask=valid_mask)
         if mark is not None:
@@ -292,7 +299,8 @@ class PairPipeline:
             lists = []
             for out, mask, h, w in sides:
                 if self.nms > 0:
-                    lists.append(U.detect_keypoints(out['prob'], self.nms, self.thr, keep_top_k=self.topk, capacity=K, valid_mask=mask))
+                    lists.append(U.detect_keypoints(out['prob'], self.nms, self.thr, keep_top_k=self.topk, capacity=K, valid_mask=mask,
+                                                    **self._select))
                 else:
                     lists.append(U.extract_keypoints(out['prob'], self.thr, capacity=K, valid_mask=mask))
             need = 0 if self._capacity_is_exact(K) else max(int(l[2].max()) for l in lists)

@@ -11,7 +11,7 @@ from .. import _lib
 __all__ = ['dict_update', 'data_to_device', 'data_unsqueeze', 'fix_model_weigth_keys', 'depth_to_space',
            'space_to_depth', 'box_nms', 'detect_keypoints', 'extract_keypoints', 'refine_keypoints', 'nms_unresolved',
            'interpolate_descriptors', 'interpolate_descriptors_batched', 'topk_ambiguous', 'topk_tie_guard', 'nms_tie_guard',
-           'tie_robust_redo', 'box_nms_tie_robust']
+           'tie_robust_redo', 'box_nms_tie_robust', 'suppression_radii', 'check_topk_mode', 'topk_selection', 'TOPK_MODES']
 
 
 def dict_update(d, u):
@@ -87,7 +87,31 @@ def _prep_prob(prob, valid_mask):
     return p, m, dev, B, H, W
 
 
-def box_nms(prob, size, min_prob, iou=0.1, keep_top_k=0, on_cpu=False, valid_mask=None):
+TOPK_MODES = ('score', 'anms')
+
+
+def check_topk_mode(topk_mode, keep_top_k=None):
+    """The selection behind keep_top_k: 'score' (the k highest scores, the reference's rule) or 'anms' (the k largest suppression
+    radii, include/multipoint_hip.h: mp_detect_keypoints_spread).  Returns True for 'anms'; an unknown mode, and 'anms' without a
+    positive keep_top_k (when one is given), are a ValueError."""
+    if topk_mode not in TOPK_MODES:
+        raise ValueError("topk_mode must be one of %s; got %r" % (', '.join(TOPK_MODES), topk_mode))
+    if topk_mode == 'anms' and keep_top_k is not None and int(keep_top_k) <= 0:
+        raise ValueError("topk_mode 'anms' ranks the candidates to keep a number of them: it needs a top-k above 0")
+    return topk_mode == 'anms'
+
+
+def topk_selection(pred):
+    """The keyword arguments box_nms / detect_keypoints take for a `prediction:` block's `topk_mode: score | anms` and
+    `anms_robust` (default 1.0): none for the score mode, so that a block without the keys makes the calls it always made.
+    An unknown mode, and 'anms' with `topk: 0`, are a ValueError."""
+    mode = pred.get('topk_mode', 'score')
+    if not check_topk_mode(mode, pred.get('topk', 0)):
+        return {}
+    return dict(topk_mode=mode, anms_robust=float(pred.get('anms_robust', 1.0)))
+
+
+def box_nms(prob, size, min_prob, iou=0.1, keep_top_k=0, on_cpu=False, valid_mask=None, *, topk_mode='score', anms_robust=1.0):
     """Non maximum suppression on the heatmap with hypothetical boxes of side `size` centred on
     each pixel; optionally only the top k detections are kept (multipoint/utils/utils.py:78-122).
 
@@ -95,32 +119,81 @@ def box_nms(prob, size, min_prob, iou=0.1, keep_top_k=0, on_cpu=False, valid_mas
     the GPU (the reference default cpu_nms=true only works around a slow GPU path).  The result is
     returned on the device of `prob`.  `valid_mask` (extension) fuses the callers'
     `prob * valid_mask` (predict_align_image_pair.py:128).
-    Tie-break: (score descending, row-major pixel index ascending)."""
+    Tie-break: (score descending, row-major pixel index ascending).
+    `topk_mode='anms'` (extension) keeps the keep_top_k survivors with the largest suppression radius instead of the highest
+    scores (adaptive non-maximal suppression with robustness `anms_robust` in (0, 1]; mp_box_nms_spread)."""
+    spread = check_topk_mode(topk_mode)
     p, m, dev, B, H, W = _prep_prob(prob, valid_mask)
     out = torch.empty_like(p)
     h = _lib.get_handle(dev)
     with torch.cuda.device(dev):
-        h.check(h.lib.mp_box_nms(h.ptr, _lib.ptr(p), _lib.ptr(m), B, H, W, float(size), float(min_prob),
-                                 float(iou), int(keep_top_k), _lib.ptr(out), 0, _lib.stream_ptr(dev)))
+        if spread:
+            h.check(h.lib.mp_box_nms_spread(h.ptr, _lib.ptr(p), _lib.ptr(m), B, H, W, float(size), float(min_prob),
+                                            float(iou), int(keep_top_k), _lib.ptr(out), 0, float(anms_robust),
+                                            _lib.stream_ptr(dev)))
+        else:
+            h.check(h.lib.mp_box_nms(h.ptr, _lib.ptr(p), _lib.ptr(m), B, H, W, float(size), float(min_prob),
+                                     float(iou), int(keep_top_k), _lib.ptr(out), 0, _lib.stream_ptr(dev)))
     return out.to(prob.device)
 
 
 def detect_keypoints(prob, size, min_prob, iou=0.1, keep_top_k=0, capacity=None, valid_mask=None,
-                     max_rounds=0):
+                     max_rounds=0, *, topk_mode='score', anms_robust=1.0, return_radius=False):
     """Fused box_nms + torch.nonzero(prob_nms > min_prob) (predict_align_image_pair.py:127-137,170-171):
     returns (kp_yx int32 [B,K,2], kp_score f32 [B,K], kp_count int32 [B]) on the GPU, rows in
-    row-major order.  K = keep_top_k, or `capacity` when keep_top_k == 0."""
+    row-major order.  K = keep_top_k, or `capacity` when keep_top_k == 0.
+    `topk_mode='anms'` selects by suppression radius (box_nms); with `return_radius` a fourth tensor follows, the squared radius
+    int64 [B,K] of every stored keypoint (4294967295: no candidate dominates it)."""
+    spread = check_topk_mode(topk_mode)
+    if return_radius and not spread:
+        raise ValueError("return_radius needs topk_mode='anms' (utils.suppression_radii gives the radii of any list)")
     p, m, dev, B, H, W = _prep_prob(prob, valid_mask)
     K = int(capacity) if capacity else (int(keep_top_k) if keep_top_k > 0 else H * W // 4)
     kp = torch.empty((B, K, 2), dtype=torch.int32, device=dev)
     sc = torch.empty((B, K), dtype=torch.float32, device=dev)
     cnt = torch.empty((B,), dtype=torch.int32, device=dev)
     h = _lib.get_handle(dev)
+    if spread:
+        r2 = torch.empty((B, K), dtype=torch.int32, device=dev) if return_radius else None
+        with torch.cuda.device(dev):
+            h.check(h.lib.mp_detect_keypoints_spread(h.ptr, _lib.ptr(p), _lib.ptr(m), B, H, W, float(size),
+                                                     float(min_prob), float(iou), int(keep_top_k), K, _lib.ptr(kp),
+                                                     _lib.ptr(sc), _lib.ptr(cnt), int(max_rounds), float(anms_robust),
+                                                     _lib.ptr(r2), _lib.stream_ptr(dev)))
+        return (kp, sc, cnt, _radius_int64(r2)) if return_radius else (kp, sc, cnt)
     with torch.cuda.device(dev):
         h.check(h.lib.mp_detect_keypoints(h.ptr, _lib.ptr(p), _lib.ptr(m), B, H, W, float(size),
                                           float(min_prob), float(iou), int(keep_top_k), K, _lib.ptr(kp),
                                           _lib.ptr(sc), _lib.ptr(cnt), int(max_rounds), _lib.stream_ptr(dev)))
     return kp, sc, cnt
+
+
+def _radius_int64(r2):
+    """the library's uint32 radii (held in an int32 tensor) as int64 values"""
+    return r2.to(torch.int64) & 0xFFFFFFFF
+
+
+def suppression_radii(kp, score, count, robust=1.0):
+    """Squared suppression radius of every entry of a keypoint list (mp_suppression_radii): the squared distance to the nearest
+    entry j of the same image with score_i < robust * score_j (one fp32 multiply), 4294967295 where there is none.
+    kp [B,K,2] integer (y, x) below 32768, score [B,K] positive, count [B]; returns int64 [B,K] on the GPU, rows at or beyond
+    count[b] zero."""
+    dev = kp.device if kp.device.type == 'cuda' else _lib.require_cuda(None)
+    k = kp.to(dev, torch.int32).contiguous()
+    s = score.to(dev, torch.float32).contiguous()
+    c = count.to(dev, torch.int32).contiguous()
+    if k.dim() != 3 or k.shape[2] != 2 or s.shape != k.shape[:2] or c.shape != k.shape[:1]:
+        raise ValueError('suppression_radii: need kp [B,K,2], score [B,K] and count [B]; got %s, %s and %s'
+                         % (tuple(kp.shape), tuple(score.shape), tuple(count.shape)))
+    B, K = s.shape
+    r2 = torch.zeros((B, K), dtype=torch.int32, device=dev)
+    if B == 0 or K == 0:
+        return r2.to(torch.int64)
+    h = _lib.get_handle(dev)
+    with torch.cuda.device(dev):
+        h.check(h.lib.mp_suppression_radii(h.ptr, _lib.ptr(k), _lib.ptr(s), _lib.ptr(c), B, K, float(robust), _lib.ptr(r2),
+                                           _lib.stream_ptr(dev)))
+    return _radius_int64(r2)
 
 
 def nms_unresolved(device=None):
@@ -181,16 +254,19 @@ def tie_robust_redo(net, data, out, flags):
     return len(idx)
 
 
-def box_nms_tie_robust(net, data, out, size, min_prob, iou=0.1, keep_top_k=0, on_cpu=False, valid_mask=None):
+def box_nms_tie_robust(net, data, out, size, min_prob, iou=0.1, keep_top_k=0, on_cpu=False, valid_mask=None, *,
+                       topk_mode='score', anms_robust=1.0):
     """box_nms(out['prob'], ...) for the output `out = net(data)` with the top-k tie guard applied: images whose top-k cut fell
     inside a plateau of (near-)tied scores are re-evaluated with the tie-exact convolution algorithm (`out` is updated in place
     for them) and suppressed again, so the kept indices follow the reference's exact score order (utils.py:97-116) where the
-    default algorithm's rounding noise would have picked other members of the plateau.  What the predict_* CLIs call."""
-    res = box_nms(out['prob'], size, min_prob, iou, keep_top_k, on_cpu, valid_mask)
+    default algorithm's rounding noise would have picked other members of the plateau.  What the predict_* CLIs call.
+    `topk_mode` / `anms_robust` are box_nms's; with 'anms' only the footprint guard can flag an image."""
+    mode = dict(topk_mode=topk_mode, anms_robust=anms_robust)
+    res = box_nms(out['prob'], size, min_prob, iou, keep_top_k, on_cpu, valid_mask, **mode)
     B = out['prob'].shape[0] if out['prob'].dim() == 4 else 1
     flags, _ = topk_ambiguous(out['prob'].device, B)         # (keep_top_k == 0: the footprint guard's flags)
     if any(flags) and tie_robust_redo(net, data, out, flags):
-        res = box_nms(out['prob'], size, min_prob, iou, keep_top_k, on_cpu, valid_mask)
+        res = box_nms(out['prob'], size, min_prob, iou, keep_top_k, on_cpu, valid_mask, **mode)
         topk_ambiguous(out['prob'].device, B)                # the redone call flags the same plateaus again: read and drop
     return res
 

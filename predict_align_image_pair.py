@@ -64,7 +64,30 @@ def build_parser():
                         'than the 8-parameter homography')
     parser.add_argument('--plot-dir', default=None, help='(extension) with -p: write matches.png, matches_inliers.png, '
                         'warped_optical.png, overlay_checker.png and overlay_anaglyph.png into this directory')
+    add_topk_mode_arguments(parser)
     return parser
+
+
+def add_topk_mode_arguments(parser):
+    """--topk-mode / --anms-robust, shared by the command lines that cut their keypoint lists to prediction.topk."""
+    parser.add_argument('--topk-mode', default=None, choices=list(utils.TOPK_MODES),
+                        help="(extension) which prediction.topk keypoints are kept: 'score' the highest scores (default), 'anms' "
+                        'the largest suppression radii -- adaptive non-maximal suppression, spread over the frame; overrides '
+                        'prediction.topk_mode')
+    parser.add_argument('--anms-robust', default=None, type=float,
+                        help="(extension) with topk_mode 'anms': a keypoint is dominated by scores above its own divided by this "
+                        'value in (0, 1]; overrides prediction.anms_robust (default 1.0)')
+
+
+def apply_topk_mode_arguments(args, pred):
+    """Write --topk-mode / --anms-robust into the prediction block (where PairPipeline and the evaluation drivers read them) and
+    return the keyword arguments utils.box_nms / detect_keypoints take for it: none in the score mode.  An unknown mode, and
+    'anms' with `topk: 0`, are a ValueError before any work."""
+    if args.topk_mode is not None:
+        pred['topk_mode'] = args.topk_mode
+    if args.anms_robust is not None:
+        pred['anms_robust'] = args.anms_robust
+    return utils.topk_selection(pred)
 
 
 def write_plots(plot_dir, optical, thermal, kp_optical, kp_thermal, matches, inlier_mask, H_final, radius):
@@ -249,6 +272,7 @@ def main(argv=None):
         config = yaml.load(f, Loader=yaml.FullLoader)
     with open(os.path.join(args.model_dir, 'params.yaml'), 'r') as f:
         config['model'] = yaml.load(f, Loader=yaml.FullLoader)['model']      # overwrite the model params
+    select = apply_topk_mode_arguments(args, config['prediction'])          # (refuses a bad mode before any work)
 
     device = select_device(config)
     print('Predicting on device: {}'.format(device))
@@ -311,10 +335,10 @@ def main(argv=None):
             # with the tie-exact convolution algorithm, so the kept indices follow the reference's exact score order)
             out_optical['prob'] = utils.box_nms_tie_robust(net, data['optical'], out_optical, pred['nms'], pred['detection_threshold'],
                                                            keep_top_k=pred['topk'], on_cpu=pred['cpu_nms'],
-                                                           valid_mask=data['optical']['valid_mask'])
+                                                           valid_mask=data['optical']['valid_mask'], **select)
             out_thermal['prob'] = utils.box_nms_tie_robust(net, data['thermal'], out_thermal, pred['nms'], pred['detection_threshold'],
                                                            keep_top_k=pred['topk'], on_cpu=pred['cpu_nms'],
-                                                           valid_mask=data['thermal']['valid_mask'])
+                                                           valid_mask=data['thermal']['valid_mask'], **select)
         else:
             out_optical['prob'] = out_optical['prob'] * data['optical']['valid_mask']
             out_thermal['prob'] = out_thermal['prob'] * data['thermal']['valid_mask']

@@ -16,7 +16,7 @@ import yaml
 
 import multipoint_amd.datasets as datasets
 import multipoint_amd.utils as utils
-from predict_align_image_pair import load_network, select_device
+from predict_align_image_pair import add_topk_mode_arguments, apply_topk_mode_arguments, load_network, select_device
 
 
 def build_parser():
@@ -34,6 +34,7 @@ def build_parser():
     parser.add_argument('-s', '--seed', default=0, type=int, help='Seed of the random generators')
     parser.add_argument('--plot-dir', default=None, help='(extension) with -p: write the pictures the reference shows in windows '
                         'into this directory as <i>_image[_optical|_thermal].png, <i>_prob*.png and <i>_prob_masked*.png')
+    add_topk_mode_arguments(parser)
     return parser
 
 
@@ -75,6 +76,7 @@ def main(argv=None):
         config = yaml.load(f, Loader=yaml.FullLoader)
     with open(os.path.join(args.model_dir, 'params.yaml'), 'r') as f:
         config['model'] = yaml.load(f, Loader=yaml.FullLoader)['model']
+    select = apply_topk_mode_arguments(args, config['prediction'])          # (refuses a bad mode before any work)
     device = select_device(config)
     print('Predicting on device: {}'.format(device))
     dataset = getattr(datasets, config['dataset']['type'])(config['dataset'])
@@ -119,7 +121,7 @@ def main(argv=None):
         def nms(out, data):
             if pred['nms'] > 0:      # (with the top-k tie guard: utils.box_nms_tie_robust)
                 return utils.box_nms_tie_robust(net, data, out, pred['nms'], pred['detection_threshold'], keep_top_k=pred['topk'],
-                                                on_cpu=pred['cpu_nms'])
+                                                on_cpu=pred['cpu_nms'], **select)
             return out['prob']
 
         outs = {}
