@@ -209,12 +209,8 @@ def estimate_on_gpu(args, config, names):
         return np.zeros((3, 3)), np.zeros(n, np.uint8), pair_offsets, 0, None
     allp = utils.PooledMatches(torch.cat(pts).contiguous(), None, None, torch.tensor([0, n], dtype=torch.int32, device=device))
     thr = float(pred.get('reprojection_threshold', 3))
-    if model == 'homography':
-        H0, _, _ = utils.find_homography_pooled(allp, thr, max_iters=args.max_iters, seed=args.seed)
-        H, mask, nin, cost = utils.refine_homography_pooled(allp, H0, thr)
-    else:
-        H0, _, _ = utils.find_transform_pooled(allp, model, thr, max_iters=args.max_iters, seed=args.seed)
-        H, mask, nin, cost = utils.refine_transform_pooled(allp, H0, model, thr)
+    H0, _, _ = utils.find_transform_pooled(allp, model, thr, max_iters=args.max_iters, seed=args.seed)
+    H, mask, nin, cost = utils.refine_transform_pooled(allp, H0, model, thr)
     cost = cost[0].cpu().numpy()
     return H[0].cpu().numpy(), mask.cpu().numpy(), pair_offsets, int(nin[0]), (float(cost[0]), float(cost[1]))
 

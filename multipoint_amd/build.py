@@ -16,10 +16,10 @@ OBJ_DIR = os.path.join(CSRC, '_build')
 LIB_PATH = os.path.join(HERE, 'libmultipoint_hip.so')
 SOURCES = ['conv_mfma.hip', 'conv_wino43.hip', 'conv_wino43b.hip', 'conv_split.hip', 'conv_f16.hip', 'conv_f16_res.hip', 'conv_first.hip', 'heads_post.hip', 'head_tail.hip', 'head_tail_f16.hip', 'nms.hip', 'keypoints.hip', 'keypoints_subpixel.hip', 'keypoints_spread.hip',
            'sample_desc.hip', 'match_mfma.hip', 'match_guided.hip', 'match_extra.hip', 'pair_metrics.hip', 'detector_metrics.hip', 'homography.hip', 'homography_f.hip', 'homography_pooled.hip', 'transform.hip', 'transform_f.hip', 'transform_pooled.hip', 'homog_adapt.hip', 'losses.hip', 'batchnorm_stats.hip', 'photometric.hip', 'shapes.hip', 'api.hip',
-           'model_load.hip', 'forward.hip', 'post_api.hip', 'mutual_info.hip', 'align_api.hip', 'pyramid.hip', 'fft.hip', 'lghd.hip', 'lghd_api.hip', 'sift.hip', 'sift_api.hip', 'frames.hip',
+           'model_load.hip', 'forward.hip', 'post_api.hip', 'estimate_api.hip', 'mutual_info.hip', 'align_api.hip', 'pyramid.hip', 'fft.hip', 'lghd.hip', 'lghd_api.hip', 'sift.hip', 'sift_api.hip', 'frames.hip',
            'frames_api.hip', 'draw.hip', 'register.hip', 'register_api.hip', 'ecc.hip', 'ecc_api.hip', 'ecc_pooled.hip', 'ecc_pooled_api.hip',
            'residual.hip', 'residual_api.hip']
-HEADERS = [os.path.join(CSRC, h) for h in ('mp_common.h', 'mp_device.h', 'mp_tile.h', 'mp_head.h', 'mp_f16.h', 'mp_match.h', 'mp_select.h', 'mp_fft.h', 'mp_raster.h', 'mp_homography.h', 'mp_transform.h', 'mp_ecc.h', 'mp_f16_store_pooled.inc',
+HEADERS = [os.path.join(CSRC, h) for h in ('mp_common.h', 'mp_device.h', 'mp_tile.h', 'mp_head.h', 'mp_f16.h', 'mp_match.h', 'mp_select.h', 'mp_fft.h', 'mp_raster.h', 'mp_ransac.h', 'mp_homography.h', 'mp_transform.h', 'mp_ecc.h', 'mp_f16_store_pooled.inc',
                                             'mp_f16_store_lines.inc', 'host.h')] + [
     os.path.join(HERE, '..', 'include', 'multipoint_hip.h')]
 # sources that include another source (the same kernels compiled for a second keypoint type)

@@ -1,6 +1,6 @@
 // C ABI of libmultipoint_hip.so (declared in include/multipoint_hip.h): the handle's life cycle, the device shape, the MP_DEBUG
 // switches and profiling.  The model is loaded in model_load.hip, the forward runs in forward.hip, the rest of the ABI is
-// post_api.hip; host.h holds the handle.
+// post_api.hip and the *_api.hip files; host.h holds the handle.
 #include "host.h"
 
 using namespace mp_host;

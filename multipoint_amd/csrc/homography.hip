@@ -8,8 +8,9 @@
 //   best = most inliers (lowest hypothesis index on ties), final model = normalised DLT over the best inlier set.
 // One thread per hypothesis (the matches of the pair sit in LDS); the winner is picked with a 64-bit atomicMax.
 // OpenCV's last step, the Levenberg-Marquardt polish of the refitted model, is a launch of its own (refine_kernel).
-// A pair's matches are located by gather (ordered compaction into LDS) and handed out as a PairView by PairSource; these, the
-// refit and the polish are the templates of mp_homography.h, which homography_pooled.hip runs on a group's rows in global memory.
+// A pair's matches are located by gather (ordered compaction into LDS) and handed out as a PairView by PairSource; these and the
+// scoring kernel are the templates of mp_ransac.h, the refit and the polish those of mp_homography.h, which homography_pooled.hip
+// runs on a group's rows in global memory.
 // The kernels and launchers are templates on the keypoint type KP -- int pixels, or float sub-pixel positions
 // (mp_refine_keypoints) -- which only decides what gather reads.  A translation unit instantiates them for ONE type,
 // MP_HOMOGRAPHY_KP: int here, float in homography_f.hip, which includes this file.  Two instantiations side by side change what
@@ -23,37 +24,13 @@
 #define MP_HOMOGRAPHY_KP int
 #endif
 
-namespace {
-
-template <class KP>
-__global__ __launch_bounds__(256) void ransac_kernel(const KP* __restrict__ kp_yx, const int* __restrict__ kp_count,
-                                                     const int* __restrict__ match_idx, int K, int T, double thr,
-                                                     unsigned long long seed, unsigned long long* __restrict__ best)
-{
-    extern __shared__ float pts[];            // [K][4]
-    const int p = blockIdx.y;
-    const int n = gather(kp_yx, kp_count, match_idx, p, K, pts, nullptr);
-    if (n < 4) return;
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= T) return;
-    double h[9];
-    if (!hypothesis(PairView{pts, nullptr, nullptr, n}, seed, p, t, h)) return;
-    const double thr2 = thr * thr;
-    int cnt = 0;
-    for (int i = 0; i < n; ++i) cnt += inlier(h, pts[i * 4], pts[i * 4 + 1], pts[i * 4 + 2], pts[i * 4 + 3], thr2);
-    // most inliers, then the LOWEST hypothesis index
-    atomicMax(&best[p], ((unsigned long long)cnt << 32) | (unsigned long long)(0x7fffffff - t));
-}
-
-}  // namespace
-
 template <class KP>
 void launch_ransac_homography(const KP* kp_yx, const int* kp_count, const int* match_idx, int P, int K, int T, double thr,
                               unsigned long long seed, unsigned long long* best, double* H_out, unsigned char* mask,
                               int* n_inliers, hipStream_t s)
 {
     const size_t lds1 = (size_t)K * 4 * sizeof(float), lds2 = lds1 + (size_t)K * sizeof(int);
-    hipLaunchKernelGGL(ransac_kernel<KP>, dim3((T + 255) / 256, P), dim3(256), lds1, s, kp_yx, kp_count, match_idx, K, T, thr, seed, best);
+    hipLaunchKernelGGL((ransac_kernel<Homography, KP>), dim3((T + 255) / 256, P), dim3(256), lds1, s, kp_yx, kp_count, match_idx, K, T, thr, seed, best);
     hipLaunchKernelGGL(refit_kernel<PairSource<KP>>, dim3(P), dim3(256), lds2, s, PairSource<KP>{kp_yx, kp_count, match_idx, K, mask}, thr,
                        seed, best, H_out, n_inliers);
 }

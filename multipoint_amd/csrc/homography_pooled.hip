@@ -2,24 +2,22 @@
 // mp_refine_homography_pooled): the estimator for a rig whose optical -> thermal transform is the same for a whole recording,
 // where a single cross-spectral pair has too few good matches and many pairs together have thousands.
 // The algorithm is the one homography.hip documents, with the group index in the place of the pair index: counter-based
-// sampling sample4(seed, g, t, n_g), exact 4-point solve, forward reprojection test, most inliers wins (lowest hypothesis index
-// on ties), normalised-DLT refit, Levenberg-Marquardt polish.  The refit and the polish are the kernel templates of
-// mp_homography.h that the per-pair route launches too; what differs is the point view they are given.  The per-pair route
-// keeps a pair's list in LDS (at most 3200, PairView); here the lists of all pairs are compacted once into global memory,
+// sampling sample_distinct<4>(seed, g, t, n_g), exact 4-point solve, forward reprojection test, most inliers wins (lowest
+// hypothesis index on ties), normalised-DLT refit, Levenberg-Marquardt polish.  The refit and the polish are the kernel
+// templates of mp_homography.h that the per-pair route launches too; what differs is the point view they are given.  The
+// per-pair route keeps a pair's list in LDS (at most 3200, PairView); here the lists of all pairs are compacted once into
+// global memory,
 //   pts [N][4] fp32 (x, y, u, v), pair-major, query order inside a pair (compact_matches, as for the per-pair list),
 // and a group is a contiguous range of it (group_offsets [G + 1], PooledView).  Scoring, the only step whose cost grows as
-// T x N, runs
-// on a grid of hypothesis blocks x point splits x groups: a thread owns one hypothesis (its 9 coefficients in registers), the
-// group's points pass through LDS in chunks of POOL_CHUNK that every lane reads at the same address (a broadcast), and the
-// splits' partial counts are added with integer atomics -- order-independent, so every run gives the same bits.
+// T x N, runs on a grid of hypothesis blocks x point splits x groups (pooled_score_kernel, mp_ransac.h, which the similarity /
+// affine route launches too): a thread owns one hypothesis (its 9 coefficients in registers), the group's points pass through
+// LDS in chunks of POOL_CHUNK that every lane reads at the same address (a broadcast), and the splits' partial counts are added
+// with integer atomics -- order-independent, so every run gives the same bits.
 #include "mp_common.h"
 #include "mp_device.h"
 #include "mp_homography.h"
 
 namespace {
-
-constexpr int POOL_CHUNK = MP_POOLED_CHUNK;            // points per staged chunk: 16 KB of LDS
-constexpr int POOL_MAX_SPLITS = MP_POOLED_MAX_SPLITS;  // most blocks that share the points of one (hypothesis block, group)
 
 // a pair's number of usable matches (usable_match: the filter of the ordered compaction)
 __global__ __launch_bounds__(256) void pool_count_kernel(const int* __restrict__ kp_count, const int* __restrict__ match_idx, int K,
@@ -100,41 +98,6 @@ __global__ __launch_bounds__(256) void pool_write_kernel(const KP* __restrict__ 
     });
 }
 
-// grid (hypothesis blocks, point splits, groups).  Block (bx, s, g) scores hypotheses bx * 256 .. + 255 of group g on the
-// chunks s, s + splits, ... of its points and adds the counts to counts[g][t].  A thread without a hypothesis (t >= T, or a
-// singular sample) still takes part in every staging barrier: the only early exits are the same for the whole workgroup.
-__global__ __launch_bounds__(256) void pooled_score_kernel(const float4* __restrict__ pts, const int* __restrict__ group_offsets,
-                                                           int N, int T, double thr, unsigned long long seed,
-                                                           unsigned int* __restrict__ counts)
-{
-    __shared__ float4 chunk[POOL_CHUNK];
-    const int g = blockIdx.z, tid = threadIdx.x;
-    int start;
-    const int n = group_range(group_offsets, g, N, start);
-    if (n < 4) return;                                       // (sample4 needs 4 points; the whole workgroup leaves)
-    const int nchunks = (n + POOL_CHUNK - 1) / POOL_CHUNK;
-    if ((int)blockIdx.y >= nchunks) return;                  // (no chunk for this split; the whole workgroup leaves)
-    pts += start;
-    const int t = blockIdx.x * 256 + tid;
-    double h[9];
-    bool ok = t < T;
-    if (ok) ok = hypothesis(PooledView{pts, nullptr, n}, seed, g, t, h);
-    const double thr2 = thr * thr;
-    int cnt = 0;
-    for (int c = blockIdx.y; c < nchunks; c += gridDim.y) {
-        const int base = c * POOL_CHUNK, m = min(POOL_CHUNK, n - base);
-        __syncthreads();                                     // the previous chunk has been read by every thread
-        for (int i = tid; i < m; i += 256) chunk[i] = pts[base + i];
-        __syncthreads();
-        if (ok)
-            for (int i = 0; i < m; ++i) {
-                const float4 q = chunk[i];
-                cnt += inlier(h, q.x, q.y, q.z, q.w, thr2);
-            }
-    }
-    if (ok && cnt > 0) atomicAdd(&counts[(size_t)g * T + t], (unsigned int)cnt);
-}
-
 // best[g] = max over t of (count << 32) | (0x7fffffff - t): most inliers, then the LOWEST hypothesis index
 __global__ __launch_bounds__(256) void pooled_select_kernel(const unsigned int* __restrict__ counts, int T,
                                                             unsigned long long* __restrict__ best)
@@ -178,8 +141,7 @@ void launch_find_homography_pooled(const float* pts, const int* group_offsets, i
                                    unsigned char* mask, int* n_inliers, hipStream_t s)
 {
     const float4* p4 = reinterpret_cast<const float4*>(pts);
-    const int splits = min(max((N + POOL_CHUNK - 1) / POOL_CHUNK, 1), POOL_MAX_SPLITS);
-    hipLaunchKernelGGL(pooled_score_kernel, dim3((T + 255) / 256, splits, G), dim3(256), 0, s, p4, group_offsets, N, T, thr, seed,
+    hipLaunchKernelGGL(pooled_score_kernel<Homography>, dim3((T + 255) / 256, pool_splits(N), G), dim3(256), 0, s, p4, group_offsets, N, T, thr, seed,
                        counts);
     hipLaunchKernelGGL(pooled_select_kernel, dim3(G), dim3(256), 0, s, counts, T, best);
     hipLaunchKernelGGL(refit_kernel<PooledSource>, dim3(G), dim3(256), 0, s, PooledSource{p4, group_offsets, N, mask}, thr, seed, best,

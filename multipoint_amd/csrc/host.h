@@ -1,6 +1,6 @@
 // Host-side state of libmultipoint_hip.so shared by the C ABI's translation units (api.hip, model_load.hip, forward.hip,
-// post_api.hip, align_api.hip): the handle, its layers and device buffers, and the error helpers.  Internal: the public C ABI is
-// include/multipoint_hip.h.
+// post_api.hip, estimate_api.hip, align_api.hip): the handle, its layers and device buffers, and the error helpers.  Internal:
+// the public C ABI is include/multipoint_hip.h.
 #pragma once
 #include "../../include/multipoint_hip.h"
 #include "mp_common.h"

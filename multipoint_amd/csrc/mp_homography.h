@@ -1,33 +1,13 @@
 // The homography estimators' device code, written once (homography.hip: one model per pair; homography_pooled.hip: one model
-// per group of pairs): the ordered compaction of a pair's usable matches, counter-based sampling, the exact 4-point solve, the
-// forward reprojection test, the normalised-DLT refit and the Levenberg-Marquardt polish.
-// One body, two views.  refit_kernel, refine_kernel, lm_sums and hypothesis are templates on where the correspondences live
-// and how an outlier is marked: PairView (a pair's list in LDS) or PooledView (a group's rows in global memory).  A kernel gets
-// its view from a Source, the struct of launch arguments that locates the points of pair / group `index` (PairSource gathers
-// them into LDS, PooledSource looks up the group's range).  Every floating-point operation, reduction and barrier is in the
-// shared body, so the same correspondences give the same bits on either route.
-// The model-free pieces -- compaction, match_point, the views and sources, block_sum -- also serve the similarity / affine
-// estimators (mp_transform.h), by inclusion: the bodies below have no caller and no template parameter from there.
+// per group of pairs): the exact 4-point solve and the forward reprojection test -- the Homography model of the scoring kernels
+// in mp_ransac.h --, the normalised-DLT refit and the Levenberg-Marquardt polish.
+// refit_kernel, refine_kernel and lm_sums are templates on the point view (mp_ransac.h: PairView, a pair's list in LDS, or
+// PooledView, a group's rows in global memory).  Every floating-point operation, reduction and barrier is in the shared body, so
+// the same correspondences give the same bits on either route.
 #pragma once
-#include "mp_common.h"
-#include "mp_device.h"
+#include "mp_ransac.h"
 
 namespace {
-
-// 4 distinct indices in [0, n) for hypothesis t of pair p.  Never terminates for n < 4: callers leave before it.
-__device__ __forceinline__ void sample4(unsigned long long seed, int p, int t, int n, int idx[4])
-{
-    unsigned long long ctr = mix64(seed ^ ((unsigned long long)p << 32) ^ (unsigned long long)t);
-    for (int k = 0; k < 4; ++k) {
-        for (;;) {
-            ctr = mix64(ctr);
-            const int c = (int)(ctr % (unsigned long long)n);
-            bool dup = false;
-            for (int j = 0; j < k; ++j) dup |= (idx[j] == c);
-            if (!dup) { idx[k] = c; break; }
-        }
-    }
-}
 
 // exact homography through 4 correspondences (x,y) -> (u,v); h[8] = 1.  false if (near-)singular.
 __device__ bool solve4(const double* x, const double* y, const double* u, const double* v, double* h)
@@ -71,148 +51,15 @@ __device__ __forceinline__ bool inlier(const double* h, double x, double y, doub
     return du * du + dv * dv <= thr2;
 }
 
-// ---- a pair's usable matches ----
-// the partner j = match_idx[p][i] of query i if the match is usable (i < no, 0 <= j < nt), else -1
-__device__ __forceinline__ int usable_match(const int* match_idx, int p, int K, int i, int no, int nt)
-{
-    if (i >= no) return -1;
-    const int j = match_idx[(size_t)p * K + i];
-    return (j >= 0 && j < nt) ? j : -1;
-}
-
-// the correspondence (x, y) -> (u, v) of query i and partner j of pair p (kp_yx: [2P][K] (y, x), slot 2p optical, 2p + 1 thermal)
-// KP: int (pixel keypoints) or float (sub-pixel ones, mp_refine_keypoints): everything behind this cast is one body
-template <class KP>
-__device__ __forceinline__ float4 match_point(const KP* kp_yx, int p, int K, int i, int j)
-{
-    const KP* o = kp_yx + ((size_t)(2 * p) * K + i) * 2;
-    const KP* t = kp_yx + ((size_t)(2 * p + 1) * K + j) * 2;
-    return make_float4((float)o[1], (float)o[0], (float)t[1], (float)t[0]);
-}
-
-// Ordered compaction of pair p's usable matches by a workgroup of 256 threads (all of them call it): the queries are walked in
-// steps of 256, a survivor's position comes from the wave's ballot and the prefix of the four waves' counts -- query order, as
-// the reference's list comprehension keeps it, and no atomics.  put(pos, i, j) is called once per usable match; returns their
-// number.
-template <class Put>
-__device__ int compact_matches(const int* kp_count, const int* match_idx, int p, int K, Put put)
-{
-    __shared__ int run_s;
-    __shared__ int wave_base[4];
-    const int tid = threadIdx.x, wv = tid >> 6, ln = tid & 63;
-    if (tid == 0) run_s = 0;
-    __syncthreads();
-    const int no = min(kp_count[2 * p], K), nt = min(kp_count[2 * p + 1], K);
-    for (int i0 = 0; i0 < no; i0 += 256) {
-        const int i = i0 + tid;
-        const int j = usable_match(match_idx, p, K, i, no, nt);
-        const unsigned long long bal = __ballot(j >= 0);
-        if (ln == 0) wave_base[wv] = __popcll(bal);
-        __syncthreads();
-        if (tid == 0) {
-            int run = run_s;
-            for (int w = 0; w < 4; ++w) { const int c = wave_base[w]; wave_base[w] = run; run += c; }
-            run_s = run;
-        }
-        __syncthreads();
-        if (j >= 0) put(wave_base[wv] + __popcll(bal & ((1ull << ln) - 1ull)), i, j);
-        __syncthreads();
-    }
-    return run_s;
-}
-
-// ---- the two point views ----
-// a pair's list in LDS: pts [n][4] floats (x, y, u, v), qidx [n] the query index of each match, mask_row the pair's row of the
-// mask (one byte per optical keypoint).  An outlier is marked by a NaN x.
-struct PairView {
-    float* pts;
-    const int* qidx;
-    unsigned char* mask_row;
-    int n;
-    __device__ float4 get(int i) const { return make_float4(pts[i * 4], pts[i * 4 + 1], pts[i * 4 + 2], pts[i * 4 + 3]); }
-    __device__ bool is_inlier(int i) const { return pts[i * 4] == pts[i * 4]; }
-    __device__ void set_inlier(int i, bool in) const
-    {
-        mask_row[qidx[i]] = in ? 1 : 0;
-        if (!in) pts[i * 4] = __int_as_float(0x7fc00000);
-    }
+// The homography as a model of the scoring kernels (mp_ransac.h): nine coefficients, h[8] = 1 from the minimal solve.  The two
+// functions are NAMED here, not wrapped: a forwarding member in front of solve4 changes the order in which the compiler meets the
+// functions of a unit, and with it the fp64 contractions of refit_kernel (the note in front of that kernel).
+struct Homography {
+    static constexpr int S = 4;          // minimal sample
+    static constexpr int COEFFS = 9;
+    static constexpr auto minimal = solve4;
+    static constexpr auto inlier = ::inlier;
 };
-
-// a group's rows in global memory, pts and mask advanced by the group's start.  An outlier is known by its mask byte; a thread
-// reads only bytes it wrote itself (the bodies walk i = tid, tid + 256, ... in every pass).
-struct PooledView {
-    const float4* pts;
-    unsigned char* mask;
-    int n;
-    __device__ float4 get(int i) const { return pts[i]; }
-    __device__ bool is_inlier(int i) const { return mask[i] != 0; }
-    __device__ void set_inlier(int i, bool in) const { mask[i] = in ? 1 : 0; }
-};
-
-// ---- the two sources: what locates the view of pair / group `index` ----
-// gather the matched (x,y)->(u,v) pairs of pair p into LDS in query order; returns their number
-// pts: [n][4] floats in LDS order x, y, u, v; qidx (may be NULL): [n] the query index of each match
-template <class KP>
-__device__ int gather(const KP* kp_yx, const int* kp_count, const int* match_idx, int p, int K, float* pts, int* qidx)
-{
-    return compact_matches(kp_count, match_idx, p, K, [&](int pos, int i, int j) {
-        const float4 q = match_point(kp_yx, p, K, i, j);
-        pts[pos * 4 + 0] = q.x; pts[pos * 4 + 1] = q.y; pts[pos * 4 + 2] = q.z; pts[pos * 4 + 3] = q.w;
-        if (qidx) qidx[pos] = i;
-    });
-}
-
-// what refit_kernel / refine_kernel are launched with: the view of pair p is its gathered list in LDS
-// (dynamic LDS: [K][4] floats, then [K] ints) and its row of the mask.  KP: the keypoint type (int pixels or float sub-pixel
-// positions); it only decides what gather reads
-template <class KP>
-struct PairSource {
-    const KP* kp_yx;
-    const int* kp_count;
-    const int* match_idx;
-    int K;
-    unsigned char* mask;
-    __device__ PairView view(int p) const
-    {
-        extern __shared__ float pts[];
-        int* qidx = reinterpret_cast<int*>(pts + (size_t)K * 4);
-        const int n = gather(kp_yx, kp_count, match_idx, p, K, pts, qidx);
-        return PairView{pts, qidx, mask + (size_t)p * K, n};
-    }
-};
-
-// the rows [start, start + n) of group g, clamped to [0, N] (the offsets are device data: nothing they hold may lead outside pts)
-__device__ __forceinline__ int group_range(const int* group_offsets, int g, int N, int& start)
-{
-    const int a = min(max(group_offsets[g], 0), N), b = min(max(group_offsets[g + 1], 0), N);
-    start = a;
-    return max(b - a, 0);
-}
-
-// what refit_kernel / refine_kernel are launched with: the view of group g is its range of pts and mask
-struct PooledSource {
-    const float4* pts;
-    const int* group_offsets;
-    int N;
-    unsigned char* mask;
-    __device__ PooledView view(int g) const
-    {
-        int start;
-        const int n = group_range(group_offsets, g, N, start);
-        return PooledView{pts + start, mask + start, n};
-    }
-};
-
-// hypothesis t of pair / group `index` from 4 sampled points of the view; false if the 4-point system is singular
-template <class View>
-__device__ __forceinline__ bool hypothesis(View pv, unsigned long long seed, int index, int t, double* h)
-{
-    int idx[4];
-    sample4(seed, index, t, pv.n, idx);
-    double x[4], y[4], u[4], v[4];
-    for (int k = 0; k < 4; ++k) { const float4 q = pv.get(idx[k]); x[k] = q.x; y[k] = q.y; u[k] = q.z; v[k] = q.w; }
-    return solve4(x, y, u, v, h);
-}
 
 // symmetric 9x9 eigen-decomposition by cyclic Jacobi; returns the eigenvector of the smallest eigenvalue
 __device__ void smallest_eigvec9(double a[9][9], double* out)
@@ -273,18 +120,6 @@ __device__ void dlt_finish(const double* ata, double cx, double cy, double cu, d
     for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) H_out[r * 3 + c] = out[r][c] * nrm;
 }
 
-// the sum of v over the 256 threads of the workgroup (a tree in LDS: the same bits on every run).  All 256 threads call it.
-__device__ __forceinline__ double block_sum(double v, double* red /* [256] LDS */)
-{
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 // One workgroup of 256 threads per pair / group: re-derive the winning hypothesis best[index], mark its inliers in the view,
 // refit by normalised DLT over them.  H_out[index] and n_inliers[index] are zero if there is no model.
 // (The body is the kernel itself and not a function that two kernels call: how the compiler contracts a sum of two products
@@ -308,7 +143,7 @@ __global__ __launch_bounds__(256) void refit_kernel(Source src, double thr, unsi
     }
     if (tid == 0) {
         double h[9];
-        hypothesis(pv, seed, index, 0x7fffffff - (int)(b & 0xffffffffull), h);
+        hypothesis<Homography>(pv, seed, index, 0x7fffffff - (int)(b & 0xffffffffull), h);
         for (int k = 0; k < 9; ++k) hsh[k] = h[k];
     }
     __syncthreads();

@@ -1,15 +1,14 @@
 // The similarity and affine estimators' device code (transform.hip: one model per pair; transform_pooled.hip: one model per
-// group of pairs), next to the homography's in mp_homography.h and on the same routes: the same ordered compaction, point
-// views and sources, counter-based sampling, fixed-order block sums and packed winner key.  What differs is the model:
+// group of pairs), next to the homography's in mp_homography.h and on the same routes: the ordered compaction, point views and
+// sources, counter-based sampling, fixed-order block sums and scoring kernels of mp_ransac.h.  What differs is the model:
 //   Similarity  [[a, -b, tx], [b, a, ty], [0, 0, 1]]   minimal sample 2 distinct points, closed form
 //   Affine      [[a,  b, tx], [c, d, ty], [0, 0, 1]]   minimal sample 3 non-collinear points, 3x3 elimination
 // Both are carried as the six coefficients m[0..5] of the top two rows, so one inlier test (no division) serves both.  The
 // refit over a consensus set is the exact least-squares minimiser of the summed squared forward error (closed form on centred
 // points / 3x3 normal equations on centred source points), so there is no Levenberg-Marquardt polish: "refine" is local
 // optimisation, rounds of { mark the inliers of the current model, refit over them } until the set stops changing.
-// None of this touches the bodies of mp_homography.h (their bits are pinned by tests); only its model-free pieces are used.
 #pragma once
-#include "mp_homography.h"
+#include "mp_ransac.h"
 
 namespace {
 
@@ -21,23 +20,6 @@ __device__ __forceinline__ bool in_set(const PairView& pv, int i) { return pv.ma
 __device__ __forceinline__ void put_set(const PairView& pv, int i, bool in) { pv.mask_row[pv.qidx[i]] = in ? 1 : 0; }
 __device__ __forceinline__ bool in_set(const PooledView& pv, int i) { return pv.mask[i] != 0; }
 __device__ __forceinline__ void put_set(const PooledView& pv, int i, bool in) { pv.mask[i] = in ? 1 : 0; }
-
-// S distinct indices in [0, n) for hypothesis t of pair / group p: sample4's counter scheme.  Never terminates for n < S:
-// callers leave before it.
-template <int S>
-__device__ __forceinline__ void sample_distinct(unsigned long long seed, int p, int t, int n, int* idx)
-{
-    unsigned long long ctr = mix64(seed ^ ((unsigned long long)p << 32) ^ (unsigned long long)t);
-    for (int k = 0; k < S; ++k) {
-        for (;;) {
-            ctr = mix64(ctr);
-            const int c = (int)(ctr % (unsigned long long)n);
-            bool dup = false;
-            for (int j = 0; j < k; ++j) dup |= (idx[j] == c);
-            if (!dup) { idx[k] = c; break; }
-        }
-    }
-}
 
 // squared forward error of (x, y) -> (u, v) under m
 __device__ __forceinline__ double error2(const double* m, double x, double y, double u, double v)
@@ -73,7 +55,16 @@ __device__ bool solve3(double a[3][5], double* z0, double* z1)
     return true;
 }
 
-struct Similarity {
+// what the two models share as models of the scoring kernels (mp_ransac.h)
+struct TopTwoRows {
+    static constexpr int COEFFS = 6;
+    __device__ __forceinline__ static bool inlier(const double* m, double x, double y, double u, double v, double thr2)
+    {
+        return error2(m, x, y, u, v) <= thr2;
+    }
+};
+
+struct Similarity : TopTwoRows {
     static constexpr int S = 2;          // minimal sample
     static constexpr int SUMS = 3;       // centred sums of the refit
     // exact model through 2 correspondences: with d = p1 - p0, e = q1 - q0, (a + ib) = e conj(d) / |d|^2
@@ -105,7 +96,7 @@ struct Similarity {
     }
 };
 
-struct Affine {
+struct Affine : TopTwoRows {
     static constexpr int S = 3;
     static constexpr int SUMS = 11;
     // exact model through 3 correspondences: rows (x, y, 1) against u and v
@@ -134,17 +125,6 @@ struct Affine {
         return true;
     }
 };
-
-// hypothesis t of pair / group `index` from S sampled points of the view; false if the sample is degenerate
-template <class Model, class View>
-__device__ __forceinline__ bool transform_hypothesis(View pv, unsigned long long seed, int index, int t, double* m)
-{
-    int idx[Model::S];
-    sample_distinct<Model::S>(seed, index, t, pv.n, idx);
-    double x[Model::S], y[Model::S], u[Model::S], v[Model::S];
-    for (int k = 0; k < Model::S; ++k) { const float4 q = pv.get(idx[k]); x[k] = q.x; y[k] = q.y; u[k] = q.z; v[k] = q.w; }
-    return Model::minimal(x, y, u, v, m);
-}
 
 // ---- pieces of the refit and the refinement; all 256 threads of the workgroup call each of them ----
 // Marks the inliers of m in the view.  Returns their number; changed: whether any mask byte flipped.
@@ -238,7 +218,7 @@ __global__ __launch_bounds__(256) void transform_refit_kernel(Source src, double
     }
     if (tid == 0) {
         double m0[6];
-        transform_hypothesis<Model>(pv, seed, index, 0x7fffffff - (int)(b & 0xffffffffull), m0);
+        hypothesis<Model>(pv, seed, index, 0x7fffffff - (int)(b & 0xffffffffull), m0);
         for (int k = 0; k < 6; ++k) msh[k] = m0[k];
     }
     __syncthreads();

@@ -1,8 +1,7 @@
 // C ABI, everything after the forward: NMS and keypoints with their tie guards, descriptor sampling, matching, pair and
-// detector metrics, homography estimation and warps, homographic adaptation, losses and photometric augmentation.
+// detector metrics, warps, homographic adaptation, losses and photometric augmentation.  (The RANSAC estimators' entries are in
+// estimate_api.hip.)
 #include "host.h"
-
-#include <algorithm>
 
 using namespace mp_host;
 
@@ -446,346 +445,6 @@ int mp_repeatability(mp_handle* h, const int* kp_yx, const int* kp_count, const 
     MP_HIP(hipMemsetAsync(counts, 0, (size_t)P * 4 * sizeof(int), s));
     launch_repeatability(kp_yx, kp_count, homography, P, K, H, W, distance_thresh, static_cast<long long*>(h->metrics_ws.p),
                          counts, s);
-    return launch_status(h);
-}
-
-// mp_find_homography / mp_find_homography_f: the same checks and launches on int or float keypoints
-extern "C++" {          // (a template cannot have C linkage)
-template <class KP>
-static int find_homography(mp_handle* h, const std::string& fn, const KP* kp_yx, const int* kp_count, const int* match_idx, int P,
-                           int K, double reproj_threshold, int max_iters, unsigned long long seed, double* homography,
-                           unsigned char* inlier_mask, int* n_inliers, void* stream)
-{
-    if (!h) return MP_EINVAL;
-    if (!kp_yx || !kp_count || !match_idx || !homography || !inlier_mask || !n_inliers)
-        return fail(h, MP_EINVAL, fn + ": NULL tensor");
-    if (P <= 0 || K <= 0 || K > 3200) return fail(h, MP_EINVAL, fn + ": need P > 0 and 0 < K <= 3200");
-    if (max_iters <= 0 || max_iters > (1 << 20)) return fail(h, MP_EINVAL, fn + ": max_iters out of range");
-    if (!(reproj_threshold > 0.0)) return fail(h, MP_EINVAL, fn + ": threshold must be positive");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    MP_HIP(hipSetDevice(h->device));
-    int rc;
-    if ((rc = ensure(h, h->metrics_ws, (size_t)P * sizeof(unsigned long long)))) return rc;
-    unsigned long long* best = static_cast<unsigned long long*>(h->metrics_ws.p);
-    MP_HIP(hipMemsetAsync(best, 0, (size_t)P * sizeof(unsigned long long), s));
-    MP_HIP(hipMemsetAsync(inlier_mask, 0, (size_t)P * K, s));
-    launch_ransac_homography(kp_yx, kp_count, match_idx, P, K, max_iters, reproj_threshold, seed, best, homography,
-                             inlier_mask, n_inliers, s);
-    return launch_status(h);
-}
-}
-
-int mp_find_homography(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K,
-                       double reproj_threshold, int max_iters, unsigned long long seed, double* homography,
-                       unsigned char* inlier_mask, int* n_inliers, void* stream)
-{
-    return find_homography(h, "mp_find_homography", kp_yx, kp_count, match_idx, P, K, reproj_threshold, max_iters, seed, homography,
-                           inlier_mask, n_inliers, stream);
-}
-
-int mp_find_homography_f(mp_handle* h, const float* kp_sub_yx, const int* kp_count, const int* match_idx, int P, int K,
-                         double reproj_threshold, int max_iters, unsigned long long seed, double* homography,
-                         unsigned char* inlier_mask, int* n_inliers, void* stream)
-{
-    return find_homography(h, "mp_find_homography_f", kp_sub_yx, kp_count, match_idx, P, K, reproj_threshold, max_iters, seed,
-                           homography, inlier_mask, n_inliers, stream);
-}
-
-// mp_refine_homography / mp_refine_homography_f
-extern "C++" {          // (a template cannot have C linkage)
-template <class KP>
-static int refine_homography(mp_handle* h, const std::string& fn, const KP* kp_yx, const int* kp_count, const int* match_idx, int P,
-                             int K, double reproj_threshold, int iters, double* homography, unsigned char* inlier_mask,
-                             int* n_inliers, double* cost, void* stream)
-{
-    if (!h) return MP_EINVAL;
-    if (!kp_yx || !kp_count || !match_idx || !homography || !inlier_mask || !n_inliers)
-        return fail(h, MP_EINVAL, fn + ": NULL tensor");
-    if (P <= 0 || K <= 0 || K > 3200) return fail(h, MP_EINVAL, fn + ": need P > 0 and 0 < K <= 3200");
-    if (iters < 0 || iters > 1000) return fail(h, MP_EINVAL, fn + ": iters must be in [0, 1000]");
-    if (!(reproj_threshold > 0.0)) return fail(h, MP_EINVAL, fn + ": threshold must be positive");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    MP_HIP(hipSetDevice(h->device));
-    MP_HIP(hipMemsetAsync(inlier_mask, 0, (size_t)P * K, s));
-    launch_refine_homography(kp_yx, kp_count, match_idx, P, K, reproj_threshold, iters, homography, inlier_mask, n_inliers, cost,
-                             s);
-    return launch_status(h);
-}
-}
-
-int mp_refine_homography(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K,
-                         double reproj_threshold, int iters, double* homography, unsigned char* inlier_mask, int* n_inliers,
-                         double* cost, void* stream)
-{
-    return refine_homography(h, "mp_refine_homography", kp_yx, kp_count, match_idx, P, K, reproj_threshold, iters, homography,
-                             inlier_mask, n_inliers, cost, stream);
-}
-
-int mp_refine_homography_f(mp_handle* h, const float* kp_sub_yx, const int* kp_count, const int* match_idx, int P, int K,
-                           double reproj_threshold, int iters, double* homography, unsigned char* inlier_mask, int* n_inliers,
-                           double* cost, void* stream)
-{
-    return refine_homography(h, "mp_refine_homography_f", kp_sub_yx, kp_count, match_idx, P, K, reproj_threshold, iters, homography,
-                             inlier_mask, n_inliers, cost, stream);
-}
-
-// ---- pooled homography: one model per group of pairs (homography_pooled.hip) ----
-namespace {
-
-constexpr long long POOLED_MAX_N = 1ll << 24;
-
-// the workspace is scratch without state between calls: pooling uses pair_cnt [P] int, the estimate counts [G][T] uint32 |
-// best [G] uint64 (16-byte aligned), both from its start
-size_t pooled_best_offset(int G, int T) { return (((size_t)G * T * sizeof(unsigned int)) + 15) & ~(size_t)15; }
-size_t pooled_find_bytes(int G, int T) { return pooled_best_offset(G, T) + (size_t)G * sizeof(unsigned long long); }
-size_t pooled_pool_bytes(int P) { return (size_t)P * sizeof(int); }
-
-// the checks mp_find_homography_pooled and mp_refine_homography_pooled share
-int pooled_check(mp_handle* h, const std::string& fn, const float* pts, const int* group_offsets, long long N, int G,
-                 double reproj_threshold, const double* homography, const unsigned char* inlier_mask, const int* n_inliers)
-{
-    if (!group_offsets || !homography || !n_inliers) return fail(h, MP_EINVAL, fn + ": NULL tensor");
-    if (N < 0 || N >= POOLED_MAX_N) return fail(h, MP_EINVAL, fn + ": need 0 <= N < 2^24 correspondences per call");
-    if (N > 0 && (!pts || !inlier_mask)) return fail(h, MP_EINVAL, fn + ": NULL tensor");
-    if ((reinterpret_cast<uintptr_t>(pts) & 15) != 0) return fail(h, MP_EINVAL, fn + ": pts must be 16-byte aligned");
-    if (G <= 0 || G > 65535) return fail(h, MP_EINVAL, fn + ": need 0 < G <= 65535 groups");
-    if (!(reproj_threshold > 0.0)) return fail(h, MP_EINVAL, fn + ": threshold must be positive");
-    return MP_OK;
-}
-
-}  // namespace
-
-int mp_pooled_chunk(int* chunk_points, int* max_splits)
-{
-    if (!chunk_points || !max_splits) return MP_EINVAL;
-    *chunk_points = MP_POOLED_CHUNK;
-    *max_splits = MP_POOLED_MAX_SPLITS;
-    return MP_OK;
-}
-
-int mp_pooled_workspace_bytes(int P, int G, int max_iters, long long* bytes)
-{
-    if (!bytes || P < 0 || G <= 0 || G > 65535 || max_iters <= 0 || max_iters > (1 << 20)) return MP_EINVAL;
-    *bytes = (long long)std::max(pooled_pool_bytes(P), pooled_find_bytes(G, max_iters));
-    return MP_OK;
-}
-
-// mp_pool_matches / mp_pool_matches_f
-extern "C++" {          // (a template cannot have C linkage)
-template <class KP>
-static int pool_matches(mp_handle* h, const std::string& fn, const KP* kp_yx, const int* kp_count, const int* match_idx,
-                        const int* groups, int P, int K, int G, float* pts, int* query_index, long long capacity, int* pair_offsets,
-                        int* group_offsets, void* workspace, long long workspace_bytes, void* stream)
-{
-    if (!h) return MP_EINVAL;
-    if (!kp_yx || !kp_count || !match_idx || !pair_offsets || !group_offsets)
-        return fail(h, MP_EINVAL, fn + ": NULL tensor");
-    if (P <= 0 || K <= 0 || (long long)P * K > 0x7fffffffLL) return fail(h, MP_EINVAL, fn + ": need P > 0, K > 0 and P * K < 2^31");
-    if (G <= 0 || G > 65535) return fail(h, MP_EINVAL, fn + ": need 0 < G <= 65535 groups");
-    if (!groups && G != 1) return fail(h, MP_EINVAL, fn + ": without group ids there is one group (G = 1)");
-    if (capacity < 0 || (capacity > 0 && (!pts || !query_index))) return fail(h, MP_EINVAL, fn + ": NULL tensor");
-    if ((reinterpret_cast<uintptr_t>(pts) & 15) != 0) return fail(h, MP_EINVAL, fn + ": pts must be 16-byte aligned");
-    if (!workspace || workspace_bytes < (long long)pooled_pool_bytes(P))
-        return fail(h, MP_EINVAL, fn + ": workspace smaller than mp_pooled_workspace_bytes");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    MP_HIP(hipSetDevice(h->device));
-    launch_pool_matches(kp_yx, kp_count, match_idx, groups, P, K, G, pts, query_index, capacity, pair_offsets, group_offsets,
-                        static_cast<int*>(workspace), s);
-    return launch_status(h);
-}
-}
-
-int mp_pool_matches(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, const int* groups, int P, int K,
-                    int G, float* pts, int* query_index, long long capacity, int* pair_offsets, int* group_offsets,
-                    void* workspace, long long workspace_bytes, void* stream)
-{
-    return pool_matches(h, "mp_pool_matches", kp_yx, kp_count, match_idx, groups, P, K, G, pts, query_index, capacity, pair_offsets,
-                        group_offsets, workspace, workspace_bytes, stream);
-}
-
-int mp_pool_matches_f(mp_handle* h, const float* kp_sub_yx, const int* kp_count, const int* match_idx, const int* groups, int P, int K,
-                      int G, float* pts, int* query_index, long long capacity, int* pair_offsets, int* group_offsets,
-                      void* workspace, long long workspace_bytes, void* stream)
-{
-    return pool_matches(h, "mp_pool_matches_f", kp_sub_yx, kp_count, match_idx, groups, P, K, G, pts, query_index, capacity,
-                        pair_offsets, group_offsets, workspace, workspace_bytes, stream);
-}
-
-int mp_find_homography_pooled(mp_handle* h, const float* pts, const int* group_offsets, long long N, int G,
-                              double reproj_threshold, int max_iters, unsigned long long seed, double* homography,
-                              unsigned char* inlier_mask, int* n_inliers, void* workspace, long long workspace_bytes, void* stream)
-{
-    if (!h) return MP_EINVAL;
-    const int rc = pooled_check(h, "mp_find_homography_pooled", pts, group_offsets, N, G, reproj_threshold, homography, inlier_mask,
-                                n_inliers);
-    if (rc) return rc;
-    if (max_iters <= 0 || max_iters > (1 << 20)) return fail(h, MP_EINVAL, "mp_find_homography_pooled: max_iters must be in [1, 2^20]");
-    if (!workspace || workspace_bytes < (long long)pooled_find_bytes(G, max_iters))
-        return fail(h, MP_EINVAL, "mp_find_homography_pooled: workspace smaller than mp_pooled_workspace_bytes");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    MP_HIP(hipSetDevice(h->device));
-    unsigned int* counts = static_cast<unsigned int*>(workspace);
-    unsigned long long* best = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + pooled_best_offset(G, max_iters));
-    MP_HIP(hipMemsetAsync(counts, 0, (size_t)G * max_iters * sizeof(unsigned int), s));
-    if (N > 0) MP_HIP(hipMemsetAsync(inlier_mask, 0, (size_t)N, s));
-    launch_find_homography_pooled(pts, group_offsets, (int)N, G, max_iters, reproj_threshold, seed, counts, best, homography,
-                                  inlier_mask, n_inliers, s);
-    return launch_status(h);
-}
-
-int mp_refine_homography_pooled(mp_handle* h, const float* pts, const int* group_offsets, long long N, int G,
-                                double reproj_threshold, int iters, double* homography, unsigned char* inlier_mask, int* n_inliers,
-                                double* cost, void* stream)
-{
-    if (!h) return MP_EINVAL;
-    const int rc = pooled_check(h, "mp_refine_homography_pooled", pts, group_offsets, N, G, reproj_threshold, homography,
-                                inlier_mask, n_inliers);
-    if (rc) return rc;
-    if (iters < 0 || iters > 1000) return fail(h, MP_EINVAL, "mp_refine_homography_pooled: iters must be in [0, 1000]");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    MP_HIP(hipSetDevice(h->device));
-    if (N > 0) MP_HIP(hipMemsetAsync(inlier_mask, 0, (size_t)N, s));
-    launch_refine_homography_pooled(pts, group_offsets, (int)N, G, reproj_threshold, iters, homography, inlier_mask, n_inliers,
-                                    cost, s);
-    return launch_status(h);
-}
-
-// ---- similarity / affine models on the three routes (transform.hip, transform_f.hip, transform_pooled.hip) ----
-// mp_find_transform / mp_find_transform_f: MP_MODEL_HOMOGRAPHY is the existing entry itself; the other models get the same
-// checks, buffers and memsets in front of their own launch
-extern "C++" {          // (a template cannot have C linkage)
-static bool transform_model_known(int model)
-{
-    return model == MP_MODEL_HOMOGRAPHY || model == MP_MODEL_SIMILARITY || model == MP_MODEL_AFFINE;
-}
-
-template <class KP>
-static int find_transform(mp_handle* h, const std::string& fn, const KP* kp_yx, const int* kp_count, const int* match_idx, int P,
-                          int K, int model, double reproj_threshold, int max_iters, unsigned long long seed, double* transform,
-                          unsigned char* inlier_mask, int* n_inliers, void* stream)
-{
-    if (!h) return MP_EINVAL;
-    if (!transform_model_known(model)) return fail(h, MP_EINVAL, fn + ": unknown model " + std::to_string(model));
-    if (model == MP_MODEL_HOMOGRAPHY)
-        return find_homography(h, fn, kp_yx, kp_count, match_idx, P, K, reproj_threshold, max_iters, seed, transform, inlier_mask,
-                               n_inliers, stream);
-    if (!kp_yx || !kp_count || !match_idx || !transform || !inlier_mask || !n_inliers)
-        return fail(h, MP_EINVAL, fn + ": NULL tensor");
-    if (P <= 0 || K <= 0 || K > 3200) return fail(h, MP_EINVAL, fn + ": need P > 0 and 0 < K <= 3200");
-    if (max_iters <= 0 || max_iters > (1 << 20)) return fail(h, MP_EINVAL, fn + ": max_iters out of range");
-    if (!(reproj_threshold > 0.0)) return fail(h, MP_EINVAL, fn + ": threshold must be positive");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    MP_HIP(hipSetDevice(h->device));
-    int rc;
-    if ((rc = ensure(h, h->metrics_ws, (size_t)P * sizeof(unsigned long long)))) return rc;
-    unsigned long long* best = static_cast<unsigned long long*>(h->metrics_ws.p);
-    MP_HIP(hipMemsetAsync(best, 0, (size_t)P * sizeof(unsigned long long), s));
-    MP_HIP(hipMemsetAsync(inlier_mask, 0, (size_t)P * K, s));
-    launch_find_transform(model, kp_yx, kp_count, match_idx, P, K, max_iters, reproj_threshold, seed, best, transform, inlier_mask,
-                          n_inliers, s);
-    return launch_status(h);
-}
-
-template <class KP>
-static int refine_transform(mp_handle* h, const std::string& fn, const KP* kp_yx, const int* kp_count, const int* match_idx, int P,
-                            int K, int model, double reproj_threshold, int rounds, double* transform, unsigned char* inlier_mask,
-                            int* n_inliers, double* cost, void* stream)
-{
-    if (!h) return MP_EINVAL;
-    if (!transform_model_known(model)) return fail(h, MP_EINVAL, fn + ": unknown model " + std::to_string(model));
-    if (model == MP_MODEL_HOMOGRAPHY)
-        return refine_homography(h, fn, kp_yx, kp_count, match_idx, P, K, reproj_threshold, rounds, transform, inlier_mask, n_inliers,
-                                 cost, stream);
-    if (!kp_yx || !kp_count || !match_idx || !transform || !inlier_mask || !n_inliers)
-        return fail(h, MP_EINVAL, fn + ": NULL tensor");
-    if (P <= 0 || K <= 0 || K > 3200) return fail(h, MP_EINVAL, fn + ": need P > 0 and 0 < K <= 3200");
-    if (rounds < 0 || rounds > 1000) return fail(h, MP_EINVAL, fn + ": rounds must be in [0, 1000]");
-    if (!(reproj_threshold > 0.0)) return fail(h, MP_EINVAL, fn + ": threshold must be positive");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    MP_HIP(hipSetDevice(h->device));
-    MP_HIP(hipMemsetAsync(inlier_mask, 0, (size_t)P * K, s));
-    launch_refine_transform(model, kp_yx, kp_count, match_idx, P, K, reproj_threshold, rounds, transform, inlier_mask, n_inliers, cost,
-                            s);
-    return launch_status(h);
-}
-}
-
-int mp_find_transform(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K, int model,
-                      double reproj_threshold, int max_iters, unsigned long long seed, double* transform,
-                      unsigned char* inlier_mask, int* n_inliers, void* stream)
-{
-    return find_transform(h, "mp_find_transform", kp_yx, kp_count, match_idx, P, K, model, reproj_threshold, max_iters, seed, transform,
-                          inlier_mask, n_inliers, stream);
-}
-
-int mp_find_transform_f(mp_handle* h, const float* kp_sub_yx, const int* kp_count, const int* match_idx, int P, int K, int model,
-                        double reproj_threshold, int max_iters, unsigned long long seed, double* transform,
-                        unsigned char* inlier_mask, int* n_inliers, void* stream)
-{
-    return find_transform(h, "mp_find_transform_f", kp_sub_yx, kp_count, match_idx, P, K, model, reproj_threshold, max_iters, seed,
-                          transform, inlier_mask, n_inliers, stream);
-}
-
-int mp_refine_transform(mp_handle* h, const int* kp_yx, const int* kp_count, const int* match_idx, int P, int K, int model,
-                        double reproj_threshold, int rounds, double* transform, unsigned char* inlier_mask, int* n_inliers,
-                        double* cost, void* stream)
-{
-    return refine_transform(h, "mp_refine_transform", kp_yx, kp_count, match_idx, P, K, model, reproj_threshold, rounds, transform,
-                            inlier_mask, n_inliers, cost, stream);
-}
-
-int mp_refine_transform_f(mp_handle* h, const float* kp_sub_yx, const int* kp_count, const int* match_idx, int P, int K, int model,
-                          double reproj_threshold, int rounds, double* transform, unsigned char* inlier_mask, int* n_inliers,
-                          double* cost, void* stream)
-{
-    return refine_transform(h, "mp_refine_transform_f", kp_sub_yx, kp_count, match_idx, P, K, model, reproj_threshold, rounds,
-                            transform, inlier_mask, n_inliers, cost, stream);
-}
-
-int mp_find_transform_pooled(mp_handle* h, const float* pts, const int* group_offsets, long long N, int G, int model,
-                             double reproj_threshold, int max_iters, unsigned long long seed, double* transform,
-                             unsigned char* inlier_mask, int* n_inliers, void* workspace, long long workspace_bytes, void* stream)
-{
-    if (!h) return MP_EINVAL;
-    if (!transform_model_known(model)) return fail(h, MP_EINVAL, "mp_find_transform_pooled: unknown model " + std::to_string(model));
-    if (model == MP_MODEL_HOMOGRAPHY)
-        return mp_find_homography_pooled(h, pts, group_offsets, N, G, reproj_threshold, max_iters, seed, transform, inlier_mask,
-                                         n_inliers, workspace, workspace_bytes, stream);
-    const int rc = pooled_check(h, "mp_find_transform_pooled", pts, group_offsets, N, G, reproj_threshold, transform, inlier_mask,
-                                n_inliers);
-    if (rc) return rc;
-    if (max_iters <= 0 || max_iters > (1 << 20)) return fail(h, MP_EINVAL, "mp_find_transform_pooled: max_iters must be in [1, 2^20]");
-    if (!workspace || workspace_bytes < (long long)pooled_find_bytes(G, max_iters))
-        return fail(h, MP_EINVAL, "mp_find_transform_pooled: workspace smaller than mp_pooled_workspace_bytes");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    MP_HIP(hipSetDevice(h->device));
-    unsigned int* counts = static_cast<unsigned int*>(workspace);
-    unsigned long long* best = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + pooled_best_offset(G, max_iters));
-    MP_HIP(hipMemsetAsync(counts, 0, (size_t)G * max_iters * sizeof(unsigned int), s));
-    if (N > 0) MP_HIP(hipMemsetAsync(inlier_mask, 0, (size_t)N, s));
-    launch_find_transform_pooled(model, pts, group_offsets, (int)N, G, max_iters, reproj_threshold, seed, counts, best, transform,
-                                 inlier_mask, n_inliers, s);
-    return launch_status(h);
-}
-
-int mp_refine_transform_pooled(mp_handle* h, const float* pts, const int* group_offsets, long long N, int G, int model,
-                               double reproj_threshold, int rounds, double* transform, unsigned char* inlier_mask, int* n_inliers,
-                               double* cost, void* stream)
-{
-    if (!h) return MP_EINVAL;
-    if (!transform_model_known(model)) return fail(h, MP_EINVAL, "mp_refine_transform_pooled: unknown model " + std::to_string(model));
-    if (model == MP_MODEL_HOMOGRAPHY)
-        return mp_refine_homography_pooled(h, pts, group_offsets, N, G, reproj_threshold, rounds, transform, inlier_mask, n_inliers,
-                                           cost, stream);
-    const int rc = pooled_check(h, "mp_refine_transform_pooled", pts, group_offsets, N, G, reproj_threshold, transform, inlier_mask,
-                                n_inliers);
-    if (rc) return rc;
-    if (rounds < 0 || rounds > 1000) return fail(h, MP_EINVAL, "mp_refine_transform_pooled: rounds must be in [0, 1000]");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    MP_HIP(hipSetDevice(h->device));
-    if (N > 0) MP_HIP(hipMemsetAsync(inlier_mask, 0, (size_t)N, s));
-    launch_refine_transform_pooled(model, pts, group_offsets, (int)N, G, reproj_threshold, rounds, transform, inlier_mask, n_inliers,
-                                   cost, s);
     return launch_status(h);
 }
 

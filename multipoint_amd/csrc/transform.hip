@@ -6,10 +6,11 @@
 //   T hypotheses per pair, each from S = 2 / 3 distinct random matches (counter-based RNG -> reproducible), exact minimal solve
 //   in fp64, score = number of matches with forward error <= threshold, best = most inliers (lowest hypothesis index on ties),
 //   final model = least squares over the best consensus set.
-// One thread per hypothesis (the matches of the pair sit in LDS); the winner is picked with a 64-bit atomicMax.  The refit and
-// the refinement are the kernel templates of mp_transform.h, which transform_pooled.hip runs on a group's rows in global
-// memory.  As in homography.hip a translation unit instantiates everything for ONE keypoint type, MP_TRANSFORM_KP: int here,
-// float in transform_f.hip, which includes this file -- so that whole-number float lists give the bits of the int entries.
+// One thread per hypothesis (the matches of the pair sit in LDS); the winner is picked with a 64-bit atomicMax (ransac_kernel,
+// mp_ransac.h).  The refit and the refinement are the kernel templates of mp_transform.h, which transform_pooled.hip runs on a
+// group's rows in global memory.  As in homography.hip a translation unit instantiates everything for ONE keypoint type,
+// MP_TRANSFORM_KP: int here, float in transform_f.hip, which includes this file -- so that whole-number float lists give the
+// bits of the int entries.
 #include "../../include/multipoint_hip.h"
 #include "mp_common.h"
 #include "mp_device.h"
@@ -22,31 +23,11 @@
 namespace {
 
 template <class Model, class KP>
-__global__ __launch_bounds__(256) void transform_ransac_kernel(const KP* __restrict__ kp_yx, const int* __restrict__ kp_count,
-                                                               const int* __restrict__ match_idx, int K, int T, double thr,
-                                                               unsigned long long seed, unsigned long long* __restrict__ best)
-{
-    extern __shared__ float pts[];            // [K][4]
-    const int p = blockIdx.y;
-    const int n = gather(kp_yx, kp_count, match_idx, p, K, pts, nullptr);
-    if (n < Model::S) return;
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= T) return;
-    double m[6];
-    if (!transform_hypothesis<Model>(PairView{pts, nullptr, nullptr, n}, seed, p, t, m)) return;
-    const double thr2 = thr * thr;
-    int cnt = 0;
-    for (int i = 0; i < n; ++i) cnt += error2(m, pts[i * 4], pts[i * 4 + 1], pts[i * 4 + 2], pts[i * 4 + 3]) <= thr2;
-    // most inliers, then the LOWEST hypothesis index
-    atomicMax(&best[p], ((unsigned long long)cnt << 32) | (unsigned long long)(0x7fffffff - t));
-}
-
-template <class Model, class KP>
 void find(const KP* kp_yx, const int* kp_count, const int* match_idx, int P, int K, int T, double thr, unsigned long long seed,
           unsigned long long* best, double* H_out, unsigned char* mask, int* n_inliers, hipStream_t s)
 {
     const size_t lds1 = (size_t)K * 4 * sizeof(float), lds2 = lds1 + (size_t)K * sizeof(int);
-    hipLaunchKernelGGL((transform_ransac_kernel<Model, KP>), dim3((T + 255) / 256, P), dim3(256), lds1, s, kp_yx, kp_count, match_idx,
+    hipLaunchKernelGGL((ransac_kernel<Model, KP>), dim3((T + 255) / 256, P), dim3(256), lds1, s, kp_yx, kp_count, match_idx,
                        K, T, thr, seed, best);
     hipLaunchKernelGGL((transform_refit_kernel<Model, PairSource<KP>>), dim3(P), dim3(256), lds2, s,
                        PairSource<KP>{kp_yx, kp_count, match_idx, K, mask}, thr, seed, best, H_out, n_inliers);

@@ -78,6 +78,80 @@ def _keypoints_for_estimate(res, h, entry):
     return getattr(h.lib, entry), res.kp_yx.contiguous()
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# the motion models of the estimators (MP_MODEL_*)
+# ----------------------------------------------------------------------------------------------------------------------
+TRANSFORM_MODELS = {'homography': 0, 'similarity': 1, 'affine': 2}       # MP_MODEL_*
+TRANSFORM_MIN_POINTS = {'homography': 4, 'similarity': 2, 'affine': 3}   # the minimal sample S of a model
+
+
+def transform_model(model):
+    """The MP_MODEL_* number of a model name ('homography', 'similarity', 'affine')."""
+    if model not in TRANSFORM_MODELS:
+        raise ValueError('unknown transform model %r: expected one of %s' % (model, sorted(TRANSFORM_MODELS)))
+    return TRANSFORM_MODELS[model]
+
+
+def transform_min_inliers(model):
+    """The fewest inliers a model of this kind is reported with: 4 for a homography, S + 1 for the others (a model that explains
+    only its own minimal sample is no model)."""
+    transform_model(model)
+    return 4 if model == 'homography' else TRANSFORM_MIN_POINTS[model] + 1
+
+
+# Every estimator below is one private body that two public functions call: the *_homography* one with model None -- it goes
+# through the mp_*_homography* entries, which take no model -- and the *_transform* one with the model's name, through the
+# mp_*_transform* entries.  `fn` is the public function's name, for the messages of the bodies that have any.
+def _entry(step, model, suffix=''):
+    """The name of the C entry of `step` ('find', 'refine') and the model arguments it takes."""
+    if model is None:
+        return 'mp_%s_homography%s' % (step, suffix), ()
+    return 'mp_%s_transform%s' % (step, suffix), (transform_model(model),)
+
+
+def _pair_find(res, model, reproj_threshold, max_iters, seed):
+    name, margs = _entry('find', model)
+    res.wait()
+    dev = res.kp_yx.device
+    P, K = res.num_pairs, res.kp_yx.shape[1]
+    Hm = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
+    mask = torch.empty((P, K), dtype=torch.uint8, device=dev)
+    nin = torch.empty((P,), dtype=torch.int32, device=dev)
+    h = _lib.get_handle(dev)
+    entry, kp = _keypoints_for_estimate(res, h, name)
+    with torch.cuda.device(dev):
+        h.check(entry(h.ptr, _lib.ptr(kp), _lib.ptr(res.kp_count.contiguous()), _lib.ptr(res.match_idx.contiguous()), P, K, *margs,
+                      float(reproj_threshold), int(max_iters), int(seed), _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin),
+                      _lib.stream_ptr(dev)))
+    return Hm, mask, nin
+
+
+def _pair_refine(fn, res, H, model, reproj_threshold, count, count_name):
+    name, margs = _entry('refine', model)
+    count = int(count)
+    if not float(reproj_threshold) > 0.0:
+        raise ValueError('%s: reproj_threshold must be positive' % fn)
+    if not 0 <= count <= 1000:
+        raise ValueError('%s: %s must be in [0, 1000]' % (fn, count_name))
+    P, K = res.num_pairs, res.kp_yx.shape[1]
+    Hm = torch.as_tensor(H, dtype=torch.float64)
+    if Hm.numel() != P * 9:
+        raise ValueError('%s: need one 3x3 matrix per pair (%d), got %d values' % (fn, P, Hm.numel()))
+    res.wait()
+    dev = res.kp_yx.device
+    Hm = Hm.to(dev).reshape(P, 3, 3).clone().contiguous()                    # (refined in place: never the caller's tensor)
+    mask = torch.empty((P, K), dtype=torch.uint8, device=dev)
+    nin = torch.empty((P,), dtype=torch.int32, device=dev)
+    cost = torch.empty((P, 2), dtype=torch.float64, device=dev)
+    h = _lib.get_handle(dev)
+    entry, kp = _keypoints_for_estimate(res, h, name)
+    with torch.cuda.device(dev):
+        h.check(entry(h.ptr, _lib.ptr(kp), _lib.ptr(res.kp_count.contiguous()), _lib.ptr(res.match_idx.contiguous()), P, K, *margs,
+                      float(reproj_threshold), count, _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin), _lib.ptr(cost),
+                      _lib.stream_ptr(dev)))
+    return Hm, mask, nin, cost
+
+
 def find_homography(res, reproj_threshold=3.0, max_iters=2000, seed=0):
     """Batched cv2.findHomography(optical_pts, thermal_pts, cv2.RANSAC, reproj_threshold) for the pairs of a PairResults
     (predict_align_image_pair.py:205-216).  NOT OpenCV's algorithm bit for bit: every pair evaluates `max_iters` 4-point
@@ -92,19 +166,7 @@ def find_homography(res, reproj_threshold=3.0, max_iters=2000, seed=0):
     where the reference would get None --, inlier mask [P,K] uint8 per optical keypoint, n_inliers [P] int32).
     Results that carry sub-pixel keypoints (res.kp_sub, prediction.subpixel) are estimated from those (mp_find_homography_f);
     so are refine_homography, refine_alignment's estimates and polish, pool_matches and estimate_shared_homography."""
-    res.wait()
-    dev = res.kp_yx.device
-    P, K = res.num_pairs, res.kp_yx.shape[1]
-    Hm = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
-    mask = torch.empty((P, K), dtype=torch.uint8, device=dev)
-    nin = torch.empty((P,), dtype=torch.int32, device=dev)
-    h = _lib.get_handle(dev)
-    entry, kp = _keypoints_for_estimate(res, h, 'mp_find_homography')
-    with torch.cuda.device(dev):
-        h.check(entry(h.ptr, _lib.ptr(kp), _lib.ptr(res.kp_count.contiguous()),
-                      _lib.ptr(res.match_idx.contiguous()), P, K, float(reproj_threshold), int(max_iters),
-                      int(seed), _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin), _lib.stream_ptr(dev)))
-    return Hm, mask, nin
+    return _pair_find(res, None, reproj_threshold, max_iters, seed)
 
 
 def refine_homography(res, H, reproj_threshold=3.0, iters=10):
@@ -114,28 +176,7 @@ def refine_homography(res, H, reproj_threshold=3.0, iters=10):
     Returns (H [P,3,3] float64 (h22 = 1; all zeros where the input is all zeros or fewer than 4 matches are inliers),
     mask [P,K] uint8 and n_inliers [P] int32 of that inlier set, cost [P,2] float64: the sum of squared residuals over it
     before / after)."""
-    iters = int(iters)
-    if not float(reproj_threshold) > 0.0:
-        raise ValueError('refine_homography: reproj_threshold must be positive')
-    if not 0 <= iters <= 1000:
-        raise ValueError('refine_homography: iters must be in [0, 1000]')
-    P, K = res.num_pairs, res.kp_yx.shape[1]
-    Hm = torch.as_tensor(H, dtype=torch.float64)
-    if Hm.numel() != P * 9:
-        raise ValueError('refine_homography: need one 3x3 matrix per pair (%d), got %d values' % (P, Hm.numel()))
-    res.wait()
-    dev = res.kp_yx.device
-    Hm = Hm.to(dev).reshape(P, 3, 3).clone().contiguous()                    # (polished in place: never the caller's tensor)
-    mask = torch.empty((P, K), dtype=torch.uint8, device=dev)
-    nin = torch.empty((P,), dtype=torch.int32, device=dev)
-    cost = torch.empty((P, 2), dtype=torch.float64, device=dev)
-    h = _lib.get_handle(dev)
-    entry, kp = _keypoints_for_estimate(res, h, 'mp_refine_homography')
-    with torch.cuda.device(dev):
-        h.check(entry(h.ptr, _lib.ptr(kp), _lib.ptr(res.kp_count.contiguous()),
-                      _lib.ptr(res.match_idx.contiguous()), P, K, float(reproj_threshold), iters,
-                      _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin), _lib.ptr(cost), _lib.stream_ptr(dev)))
-    return Hm, mask, nin, cost
+    return _pair_refine('refine_homography', res, H, None, reproj_threshold, iters, 'iters')
 
 
 def refine_alignment(res, reproj_threshold=3.0, radius=None, rounds=1, polish=True, max_iters=2000, seed=0, threshold=-1.0,
@@ -162,14 +203,8 @@ def refine_alignment(res, reproj_threshold=3.0, radius=None, rounds=1, polish=Tr
     radius = 2.0 * float(reproj_threshold) if radius is None else float(radius)
     if not (radius > 0.0 and np.isfinite(radius)):
         raise ValueError('refine_alignment: radius must be finite and positive, got %r' % radius)
-    if model == 'homography':
-        def find(r):
-            return find_homography(r, reproj_threshold, max_iters, seed)
-    else:
-        transform_model(model)
-
-        def find(r):
-            return find_transform(r, model, reproj_threshold, max_iters, seed)
+    def find(r):
+        return find_transform(r, model, reproj_threshold, max_iters, seed)
     H, mask, nin = find(res)
     cur = res
     if rounds > 0:
@@ -188,29 +223,26 @@ def refine_alignment(res, reproj_threshold=3.0, radius=None, rounds=1, polish=Tr
         cur = PairResults(res.kp_yx, res.kp_score, res.kp_count, res.desc, res.match_idx, res.match_dist, res.match_count,
                           res.H, res.W, 'guided', kp_sub=getattr(res, 'kp_sub', None))
     if polish:
-        if model == 'homography':
-            H, mask, nin, _ = refine_homography(cur, H, reproj_threshold)
-        else:
-            H, mask, nin, _ = refine_transform(cur, H, model, reproj_threshold)
+        H, mask, nin, _ = refine_transform(cur, H, model, reproj_threshold)
     return cur, H, mask, nin
 
 
 MAX_RANSAC_MATCHES = 3200        # mp_find_homography keeps a pair's correspondences in LDS
 
 
-def find_homography_points(optical_pts, thermal_pts, reproj_threshold=3.0, max_iters=2000, seed=0, device=None):
-    """cv2.findHomography(optical_pts, thermal_pts, cv2.RANSAC, reproj_threshold) for ONE set of corresponding (x, y)
-    points.  Integer input (pixel positions, as torch.nonzero's keypoints are) goes through mp_find_homography; floating
-    input (sub-pixel positions) is kept as float32 and goes through mp_find_homography_f, as cv2.findHomography takes float
-    points.  Returns (H 3x3 float64 numpy or None, mask (N,) uint8)."""
+def _points_find(fn, optical_pts, thermal_pts, model, reproj_threshold, max_iters, seed, device):
     from ..pipeline import PairResults
+    kind = 'homography' if model is None else model
+    min_inliers = transform_min_inliers(kind)
     a = np.asarray(optical_pts).reshape(-1, 2); b = np.asarray(thermal_pts).reshape(-1, 2)
     n = len(a)
-    if n < 4:
+    if len(b) != n:
+        raise ValueError('%s: %d optical and %d thermal points' % (fn, n, len(b)))
+    if n < TRANSFORM_MIN_POINTS[kind]:
         return None, np.zeros(n, np.uint8)
     if n > MAX_RANSAC_MATCHES:
-        raise ValueError('find_homography_points: at most %d correspondences per call (the pair\'s matches live in LDS); '
-                         'got %d -- keep the closest ones' % (MAX_RANSAC_MATCHES, n))
+        raise ValueError('%s: at most %d correspondences per call (the pair\'s matches live in LDS); '
+                         'got %d -- keep the closest ones' % (fn, MAX_RANSAC_MATCHES, n))
     dev = _lib.require_cuda(device)
     kp = torch.zeros((2, n, 2), dtype=torch.int32)
     kp[0] = torch.from_numpy(np.ascontiguousarray(a[:, ::-1]).astype(np.int32)); kp[1] = torch.from_numpy(np.ascontiguousarray(b[:, ::-1]).astype(np.int32))
@@ -219,10 +251,18 @@ def find_homography_points(optical_pts, thermal_pts, reproj_threshold=3.0, max_i
         sub = torch.from_numpy(np.stack([a[:, ::-1], b[:, ::-1]]).astype(np.float32)).to(dev)
     res = PairResults(kp.to(dev), None, torch.tensor([n, n], dtype=torch.int32, device=dev), None,
                       torch.arange(n, dtype=torch.int32, device=dev).reshape(1, n), None, None, 0, 0, kp_sub=sub)
-    Hm, mask, nin = find_homography(res, reproj_threshold, max_iters, seed)
-    if int(nin[0]) < 4:
+    Hm, mask, nin = _pair_find(res, model, reproj_threshold, max_iters, seed)
+    if int(nin[0]) < min_inliers:
         return None, np.zeros(n, np.uint8)
     return Hm[0].cpu().numpy(), mask[0].cpu().numpy()
+
+
+def find_homography_points(optical_pts, thermal_pts, reproj_threshold=3.0, max_iters=2000, seed=0, device=None):
+    """cv2.findHomography(optical_pts, thermal_pts, cv2.RANSAC, reproj_threshold) for ONE set of corresponding (x, y)
+    points.  Integer input (pixel positions, as torch.nonzero's keypoints are) goes through mp_find_homography; floating
+    input (sub-pixel positions) is kept as float32 and goes through mp_find_homography_f, as cv2.findHomography takes float
+    points.  Returns (H 3x3 float64 numpy or None, mask (N,) uint8)."""
+    return _points_find('find_homography_points', optical_pts, thermal_pts, None, reproj_threshold, max_iters, seed, device)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -310,16 +350,12 @@ def _check_pooled(fn, pooled, reproj_threshold):
     return pts.shape[0], go.numel() - 1
 
 
-def find_homography_pooled(pooled, reproj_threshold=3.0, max_iters=2000, seed=0):
-    """One RANSAC homography per group of a PooledMatches (mp_find_homography_pooled): find_homography's algorithm with the
-    group in the place of the pair -- `max_iters` hypotheses per group from 4 of its correspondences, the most inliers win, the
-    winner's inliers are refitted by the normalised DLT -- on lists of any length.  Returns (H [G,3,3] float64 optical (x,y,1)
-    -> thermal, all zeros for a group with fewer than 4 correspondences or without a model; mask [N] uint8, one per row of
-    pooled.pts; n_inliers [G] int32).  The same input gives the same bits on every run."""
+def _pooled_find(fn, pooled, model, reproj_threshold, max_iters, seed):
+    name, margs = _entry('find', model, '_pooled')
     max_iters = int(max_iters)
-    N, G = _check_pooled('find_homography_pooled', pooled, reproj_threshold)
+    N, G = _check_pooled(fn, pooled, reproj_threshold)
     if not 0 < max_iters <= MAX_POOLED_ITERS:
-        raise ValueError('find_homography_pooled: max_iters must be in [1, %d]' % MAX_POOLED_ITERS)
+        raise ValueError('%s: max_iters must be in [1, %d]' % (fn, MAX_POOLED_ITERS))
     dev = pooled.pts.device
     pts = pooled.pts.contiguous()
     Hm = torch.empty((G, 3, 3), dtype=torch.float64, device=dev)
@@ -328,10 +364,58 @@ def find_homography_pooled(pooled, reproj_threshold=3.0, max_iters=2000, seed=0)
     h = _lib.get_handle(dev)
     with torch.cuda.device(dev):
         ws = _pooled_workspace(h, 0, G, max_iters, dev)
-        h.check(h.lib.mp_find_homography_pooled(h.ptr, _lib.ptr(pts), _lib.ptr(pooled.group_offsets.contiguous()), N, G,
-                                                float(reproj_threshold), max_iters, int(seed), _lib.ptr(Hm), _lib.ptr(mask),
-                                                _lib.ptr(nin), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        h.check(getattr(h.lib, name)(h.ptr, _lib.ptr(pts), _lib.ptr(pooled.group_offsets.contiguous()), N, G, *margs,
+                                     float(reproj_threshold), max_iters, int(seed), _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin),
+                                     _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
     return Hm, mask, nin
+
+
+def _pooled_refine(fn, pooled, H, model, reproj_threshold, count, count_name):
+    name, margs = _entry('refine', model, '_pooled')
+    count = int(count)
+    N, G = _check_pooled(fn, pooled, reproj_threshold)
+    if not 0 <= count <= 1000:
+        raise ValueError('%s: %s must be in [0, 1000]' % (fn, count_name))
+    Hm = torch.as_tensor(H, dtype=torch.float64)
+    if Hm.numel() != G * 9:
+        raise ValueError('%s: need one 3x3 matrix per group (%d), got %d values' % (fn, G, Hm.numel()))
+    dev = pooled.pts.device
+    pts = pooled.pts.contiguous()
+    Hm = Hm.to(dev).reshape(G, 3, 3).clone().contiguous()                    # (refined in place: never the caller's tensor)
+    mask = torch.empty((N,), dtype=torch.uint8, device=dev)
+    nin = torch.empty((G,), dtype=torch.int32, device=dev)
+    cost = torch.empty((G, 2), dtype=torch.float64, device=dev)
+    h = _lib.get_handle(dev)
+    with torch.cuda.device(dev):
+        h.check(getattr(h.lib, name)(h.ptr, _lib.ptr(pts), _lib.ptr(pooled.group_offsets.contiguous()), N, G, *margs,
+                                     float(reproj_threshold), count, _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin), _lib.ptr(cost),
+                                     _lib.stream_ptr(dev)))
+    return Hm, mask, nin, cost
+
+
+def _shared_estimate(fn, res, groups, model, reproj_threshold, max_iters, seed, polish, count, count_name):
+    _entry('find', model)                                                    # (an unknown model is refused first)
+    if not float(reproj_threshold) > 0.0:
+        raise ValueError('%s: reproj_threshold must be positive' % fn)
+    if not 0 < int(max_iters) <= MAX_POOLED_ITERS:
+        raise ValueError('%s: max_iters must be in [1, %d]' % (fn, MAX_POOLED_ITERS))
+    if not 0 <= int(count) <= 1000:
+        raise ValueError('%s: %s must be in [0, 1000]' % (fn, count_name))
+    pooled = pool_matches(res, groups)
+    H, mask, nin = _pooled_find(fn, pooled, model, reproj_threshold, max_iters, seed)
+    cost = None
+    if polish:
+        H, mask, nin, cost = _pooled_refine(fn, pooled, H, model, reproj_threshold, count, count_name)
+    return SharedHomography(H, mask, nin, cost, pooled)
+
+
+def find_homography_pooled(pooled, reproj_threshold=3.0, max_iters=2000, seed=0):
+    """One RANSAC homography per group of a PooledMatches (mp_find_homography_pooled): find_homography's algorithm with the
+    group in the place of the pair -- `max_iters` hypotheses per group from 4 of its correspondences, the most inliers win, the
+    winner's inliers are refitted by the normalised DLT -- on lists of any length.  Returns (H [G,3,3] float64 optical (x,y,1)
+    -> thermal, all zeros for a group with fewer than 4 correspondences or without a model; mask [N] uint8, one per row of
+    pooled.pts; n_inliers [G] int32).  The same input gives the same bits on every run."""
+    return _pooled_find('find_homography_pooled', pooled, None, reproj_threshold, max_iters, seed)
 
 
 def refine_homography_pooled(pooled, H, reproj_threshold=3.0, iters=10):
@@ -339,25 +423,7 @@ def refine_homography_pooled(pooled, H, reproj_threshold=3.0, iters=10):
     polished over the group's correspondences within reproj_threshold of it.  Returns (H [G,3,3] float64 with h22 = 1, all zeros
     where the input is all zeros or has fewer than 4 inliers; mask [N] uint8 and n_inliers [G] int32 of the INPUT estimate's
     inlier set; cost [G,2] float64: the sum of squared residuals over it before / after)."""
-    iters = int(iters)
-    N, G = _check_pooled('refine_homography_pooled', pooled, reproj_threshold)
-    if not 0 <= iters <= 1000:
-        raise ValueError('refine_homography_pooled: iters must be in [0, 1000]')
-    Hm = torch.as_tensor(H, dtype=torch.float64)
-    if Hm.numel() != G * 9:
-        raise ValueError('refine_homography_pooled: need one 3x3 matrix per group (%d), got %d values' % (G, Hm.numel()))
-    dev = pooled.pts.device
-    pts = pooled.pts.contiguous()
-    Hm = Hm.to(dev).reshape(G, 3, 3).clone().contiguous()                    # (polished in place: never the caller's tensor)
-    mask = torch.empty((N,), dtype=torch.uint8, device=dev)
-    nin = torch.empty((G,), dtype=torch.int32, device=dev)
-    cost = torch.empty((G, 2), dtype=torch.float64, device=dev)
-    h = _lib.get_handle(dev)
-    with torch.cuda.device(dev):
-        h.check(h.lib.mp_refine_homography_pooled(h.ptr, _lib.ptr(pts), _lib.ptr(pooled.group_offsets.contiguous()), N, G,
-                                                  float(reproj_threshold), iters, _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin),
-                                                  _lib.ptr(cost), _lib.stream_ptr(dev)))
-    return Hm, mask, nin, cost
+    return _pooled_refine('refine_homography_pooled', pooled, H, None, reproj_threshold, iters, 'iters')
 
 
 def estimate_shared_homography(res, groups=None, reproj_threshold=3.0, max_iters=2000, seed=0, polish=True, iters=10):
@@ -365,18 +431,7 @@ def estimate_shared_homography(res, groups=None, reproj_threshold=3.0, max_iters
     find_homography_pooled and, with `polish`, refine_homography_pooled.  Returns a SharedHomography: H [G,3,3] float64, mask [N]
     uint8 per pooled match, n_inliers [G] int32, cost [G,2] float64 before / after the polish (None without it) and the
     PooledMatches (its pair_offsets / query_index lead from a mask byte back to the pair and the optical keypoint)."""
-    if not float(reproj_threshold) > 0.0:
-        raise ValueError('estimate_shared_homography: reproj_threshold must be positive')
-    if not 0 < int(max_iters) <= MAX_POOLED_ITERS:
-        raise ValueError('estimate_shared_homography: max_iters must be in [1, %d]' % MAX_POOLED_ITERS)
-    if not 0 <= int(iters) <= 1000:
-        raise ValueError('estimate_shared_homography: iters must be in [0, 1000]')
-    pooled = pool_matches(res, groups)
-    H, mask, nin = find_homography_pooled(pooled, reproj_threshold, max_iters, seed)
-    cost = None
-    if polish:
-        H, mask, nin, cost = refine_homography_pooled(pooled, H, reproj_threshold, iters)
-    return SharedHomography(H, mask, nin, cost, pooled)
+    return _shared_estimate('estimate_shared_homography', res, groups, None, reproj_threshold, max_iters, seed, polish, iters, 'iters')
 
 
 def find_homography_pooled_points(optical_xy, thermal_xy, reproj_threshold=3.0, max_iters=2000, seed=0, device=None):
@@ -405,26 +460,8 @@ def find_homography_pooled_points(optical_xy, thermal_xy, reproj_threshold=3.0, 
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# similarity and affine models on the same routes (mp_find_transform*, mp_refine_transform*)
+# the same routes with a choice of motion model (mp_find_transform*, mp_refine_transform*)
 # ----------------------------------------------------------------------------------------------------------------------
-TRANSFORM_MODELS = {'homography': 0, 'similarity': 1, 'affine': 2}       # MP_MODEL_*
-TRANSFORM_MIN_POINTS = {'homography': 4, 'similarity': 2, 'affine': 3}   # the minimal sample S of a model
-
-
-def transform_model(model):
-    """The MP_MODEL_* number of a model name ('homography', 'similarity', 'affine')."""
-    if model not in TRANSFORM_MODELS:
-        raise ValueError('unknown transform model %r: expected one of %s' % (model, sorted(TRANSFORM_MODELS)))
-    return TRANSFORM_MODELS[model]
-
-
-def transform_min_inliers(model):
-    """The fewest inliers a model of this kind is reported with: 4 for a homography, S + 1 for the others (a model that explains
-    only its own minimal sample is no model)."""
-    transform_model(model)
-    return 4 if model == 'homography' else TRANSFORM_MIN_POINTS[model] + 1
-
-
 def find_transform(res, model, reproj_threshold=3.0, max_iters=2000, seed=0):
     """find_homography with a choice of motion model (mp_find_transform): 'homography' (find_homography itself, the same bits),
     'similarity' [[a, -b, tx], [b, a, ty], [0, 0, 1]] (rotation, scale, two translations: what the reference's manual
@@ -435,20 +472,7 @@ def find_transform(res, model, reproj_threshold=3.0, max_iters=2000, seed=0):
     Returns what find_homography returns: (H [P,3,3] float64 optical (x,y,1) -> thermal, all zeros where there is no model
     (fewer than transform_min_inliers(model) inliers); mask [P,K] uint8 per optical keypoint; n_inliers [P] int32).  Sub-pixel
     keypoints on `res` (kp_sub) are read as find_homography reads them."""
-    m = transform_model(model)
-    res.wait()
-    dev = res.kp_yx.device
-    P, K = res.num_pairs, res.kp_yx.shape[1]
-    Hm = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
-    mask = torch.empty((P, K), dtype=torch.uint8, device=dev)
-    nin = torch.empty((P,), dtype=torch.int32, device=dev)
-    h = _lib.get_handle(dev)
-    entry, kp = _keypoints_for_estimate(res, h, 'mp_find_transform')
-    with torch.cuda.device(dev):
-        h.check(entry(h.ptr, _lib.ptr(kp), _lib.ptr(res.kp_count.contiguous()), _lib.ptr(res.match_idx.contiguous()), P, K, m,
-                      float(reproj_threshold), int(max_iters), int(seed), _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin),
-                      _lib.stream_ptr(dev)))
-    return Hm, mask, nin
+    return _pair_find(res, model, reproj_threshold, max_iters, seed)
 
 
 def refine_transform(res, H, model, reproj_threshold=3.0, rounds=10):
@@ -459,105 +483,26 @@ def refine_transform(res, H, model, reproj_threshold=3.0, rounds=10):
     the returned model was fitted to, the input's own with rounds = 0 --, cost [P,2] float64: the summed squared error over
     that set before / after the last refit).  All zeros where the input is all zeros or a set has fewer than
     transform_min_inliers(model) members."""
-    m = transform_model(model)
-    rounds = int(rounds)
-    if not float(reproj_threshold) > 0.0:
-        raise ValueError('refine_transform: reproj_threshold must be positive')
-    if not 0 <= rounds <= 1000:
-        raise ValueError('refine_transform: rounds must be in [0, 1000]')
-    P, K = res.num_pairs, res.kp_yx.shape[1]
-    Hm = torch.as_tensor(H, dtype=torch.float64)
-    if Hm.numel() != P * 9:
-        raise ValueError('refine_transform: need one 3x3 matrix per pair (%d), got %d values' % (P, Hm.numel()))
-    res.wait()
-    dev = res.kp_yx.device
-    Hm = Hm.to(dev).reshape(P, 3, 3).clone().contiguous()                    # (refined in place: never the caller's tensor)
-    mask = torch.empty((P, K), dtype=torch.uint8, device=dev)
-    nin = torch.empty((P,), dtype=torch.int32, device=dev)
-    cost = torch.empty((P, 2), dtype=torch.float64, device=dev)
-    h = _lib.get_handle(dev)
-    entry, kp = _keypoints_for_estimate(res, h, 'mp_refine_transform')
-    with torch.cuda.device(dev):
-        h.check(entry(h.ptr, _lib.ptr(kp), _lib.ptr(res.kp_count.contiguous()), _lib.ptr(res.match_idx.contiguous()), P, K, m,
-                      float(reproj_threshold), rounds, _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin), _lib.ptr(cost),
-                      _lib.stream_ptr(dev)))
-    return Hm, mask, nin, cost
+    return _pair_refine('refine_transform', res, H, model, reproj_threshold, rounds, 'rounds')
 
 
 def find_transform_points(optical_pts, thermal_pts, model, reproj_threshold=3.0, max_iters=2000, seed=0, device=None):
     """find_homography_points with a choice of motion model: ONE set of corresponding (x, y) points, integer input through
     mp_find_transform and floating input, kept as float32, through mp_find_transform_f.  Returns (H 3x3 float64 numpy or None,
     mask (N,) uint8); None with fewer points than the model's minimal sample or without a model."""
-    from ..pipeline import PairResults
-    transform_model(model)
-    a = np.asarray(optical_pts).reshape(-1, 2); b = np.asarray(thermal_pts).reshape(-1, 2)
-    n = len(a)
-    if len(b) != n:
-        raise ValueError('find_transform_points: %d optical and %d thermal points' % (n, len(b)))
-    if n < TRANSFORM_MIN_POINTS[model]:
-        return None, np.zeros(n, np.uint8)
-    if n > MAX_RANSAC_MATCHES:
-        raise ValueError('find_transform_points: at most %d correspondences per call (the pair\'s matches live in LDS); '
-                         'got %d -- keep the closest ones' % (MAX_RANSAC_MATCHES, n))
-    dev = _lib.require_cuda(device)
-    kp = torch.zeros((2, n, 2), dtype=torch.int32)
-    kp[0] = torch.from_numpy(np.ascontiguousarray(a[:, ::-1]).astype(np.int32)); kp[1] = torch.from_numpy(np.ascontiguousarray(b[:, ::-1]).astype(np.int32))
-    sub = None
-    if a.dtype.kind == 'f' or b.dtype.kind == 'f':
-        sub = torch.from_numpy(np.stack([a[:, ::-1], b[:, ::-1]]).astype(np.float32)).to(dev)
-    res = PairResults(kp.to(dev), None, torch.tensor([n, n], dtype=torch.int32, device=dev), None,
-                      torch.arange(n, dtype=torch.int32, device=dev).reshape(1, n), None, None, 0, 0, kp_sub=sub)
-    Hm, mask, nin = find_transform(res, model, reproj_threshold, max_iters, seed)
-    if int(nin[0]) < transform_min_inliers(model):
-        return None, np.zeros(n, np.uint8)
-    return Hm[0].cpu().numpy(), mask[0].cpu().numpy()
+    return _points_find('find_transform_points', optical_pts, thermal_pts, model, reproj_threshold, max_iters, seed, device)
 
 
 def find_transform_pooled(pooled, model, reproj_threshold=3.0, max_iters=2000, seed=0):
     """find_homography_pooled with a choice of motion model (mp_find_transform_pooled): one model per group of a PooledMatches.
     Returns (H [G,3,3] float64, mask [N] uint8 per row of pooled.pts, n_inliers [G] int32)."""
-    m = transform_model(model)
-    max_iters = int(max_iters)
-    N, G = _check_pooled('find_transform_pooled', pooled, reproj_threshold)
-    if not 0 < max_iters <= MAX_POOLED_ITERS:
-        raise ValueError('find_transform_pooled: max_iters must be in [1, %d]' % MAX_POOLED_ITERS)
-    dev = pooled.pts.device
-    pts = pooled.pts.contiguous()
-    Hm = torch.empty((G, 3, 3), dtype=torch.float64, device=dev)
-    mask = torch.empty((N,), dtype=torch.uint8, device=dev)
-    nin = torch.empty((G,), dtype=torch.int32, device=dev)
-    h = _lib.get_handle(dev)
-    with torch.cuda.device(dev):
-        ws = _pooled_workspace(h, 0, G, max_iters, dev)
-        h.check(h.lib.mp_find_transform_pooled(h.ptr, _lib.ptr(pts), _lib.ptr(pooled.group_offsets.contiguous()), N, G, m,
-                                               float(reproj_threshold), max_iters, int(seed), _lib.ptr(Hm), _lib.ptr(mask),
-                                               _lib.ptr(nin), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-    return Hm, mask, nin
+    return _pooled_find('find_transform_pooled', pooled, model, reproj_threshold, max_iters, seed)
 
 
 def refine_transform_pooled(pooled, H, model, reproj_threshold=3.0, rounds=10):
     """refine_transform on the groups of a PooledMatches (mp_refine_transform_pooled).  Returns (H [G,3,3] float64, mask [N]
     uint8, n_inliers [G] int32, cost [G,2] float64), as refine_transform describes them."""
-    m = transform_model(model)
-    rounds = int(rounds)
-    N, G = _check_pooled('refine_transform_pooled', pooled, reproj_threshold)
-    if not 0 <= rounds <= 1000:
-        raise ValueError('refine_transform_pooled: rounds must be in [0, 1000]')
-    Hm = torch.as_tensor(H, dtype=torch.float64)
-    if Hm.numel() != G * 9:
-        raise ValueError('refine_transform_pooled: need one 3x3 matrix per group (%d), got %d values' % (G, Hm.numel()))
-    dev = pooled.pts.device
-    pts = pooled.pts.contiguous()
-    Hm = Hm.to(dev).reshape(G, 3, 3).clone().contiguous()                    # (refined in place: never the caller's tensor)
-    mask = torch.empty((N,), dtype=torch.uint8, device=dev)
-    nin = torch.empty((G,), dtype=torch.int32, device=dev)
-    cost = torch.empty((G, 2), dtype=torch.float64, device=dev)
-    h = _lib.get_handle(dev)
-    with torch.cuda.device(dev):
-        h.check(h.lib.mp_refine_transform_pooled(h.ptr, _lib.ptr(pts), _lib.ptr(pooled.group_offsets.contiguous()), N, G, m,
-                                                 float(reproj_threshold), rounds, _lib.ptr(Hm), _lib.ptr(mask), _lib.ptr(nin),
-                                                 _lib.ptr(cost), _lib.stream_ptr(dev)))
-    return Hm, mask, nin, cost
+    return _pooled_refine('refine_transform_pooled', pooled, H, model, reproj_threshold, rounds, 'rounds')
 
 
 def estimate_shared_transform(res, groups=None, model='similarity', reproj_threshold=3.0, max_iters=2000, seed=0, polish=True,
@@ -565,19 +510,8 @@ def estimate_shared_transform(res, groups=None, model='similarity', reproj_thres
     """estimate_shared_homography with a choice of motion model: pool_matches, find_transform_pooled and, with `polish`,
     refine_transform_pooled (`rounds` of local optimisation; the polish's iterations for 'homography').  Returns a
     SharedHomography, as estimate_shared_homography does."""
-    transform_model(model)
-    if not float(reproj_threshold) > 0.0:
-        raise ValueError('estimate_shared_transform: reproj_threshold must be positive')
-    if not 0 < int(max_iters) <= MAX_POOLED_ITERS:
-        raise ValueError('estimate_shared_transform: max_iters must be in [1, %d]' % MAX_POOLED_ITERS)
-    if not 0 <= int(rounds) <= 1000:
-        raise ValueError('estimate_shared_transform: rounds must be in [0, 1000]')
-    pooled = pool_matches(res, groups)
-    H, mask, nin = find_transform_pooled(pooled, model, reproj_threshold, max_iters, seed)
-    cost = None
-    if polish:
-        H, mask, nin, cost = refine_transform_pooled(pooled, H, model, reproj_threshold, rounds)
-    return SharedHomography(H, mask, nin, cost, pooled)
+    return _shared_estimate('estimate_shared_transform', res, groups, model, reproj_threshold, max_iters, seed, polish, rounds,
+                            'rounds')
 
 
 def decompose_similarity(H):
@@ -676,10 +610,7 @@ def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoi
             est = PairResults(res.kp_yx, res.kp_score, res.kp_count, res.desc, mm[0], mm[1], mm[2], res.H, res.W,
                               sel.match_mode, kp_sub=res.kp_sub)
         if est is not None:
-            if model == 'homography':
-                h_est, _, n_in = find_homography(est, config.get('reprojection_threshold', 3))
-            else:
-                h_est, _, n_in = find_transform(est, model, config.get('reprojection_threshold', 3))
+            h_est, _, n_in = find_transform(est, model, config.get('reprojection_threshold', 3))
             h_est = h_est.cpu().numpy(); n_in = n_in.cpu().numpy()
         else:
             # one-to-many matchers (thresholdmatcher) and lists longer than one RANSAC launch holds: per pair through
@@ -699,10 +630,7 @@ def compute_descriptor_metrics(net, dataloader, device, config, threshold_keypoi
                     matches = sorted(matches, key=lambda mm: mm.distance)[:MAX_RANSAC_MATCHES]
                 opts = np.array([kp_all[2 * p, mm.queryIdx][::-1] for mm in matches])
                 tpts = np.array([kp_all[2 * p + 1, mm.trainIdx][::-1] for mm in matches])
-                if model == 'homography':
-                    hp, mask = find_homography_points(opts, tpts, config.get('reprojection_threshold', 3), device=device)
-                else:
-                    hp, mask = find_transform_points(opts, tpts, model, config.get('reprojection_threshold', 3), device=device)
+                hp, mask = find_transform_points(opts, tpts, model, config.get('reprojection_threshold', 3), device=device)
                 if hp is not None:
                     h_est[p] = hp; n_in[p] = int(mask.sum())
         if refine is not None:

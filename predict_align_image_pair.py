@@ -169,8 +169,7 @@ def refine_estimate(kp_optical, kp_thermal, desc_optical, desc_thermal, matches,
                       torch.tensor([len(matches)], dtype=torch.int32, device=dev), H, W, kp_sub=kp_sub)
     res2, H_ref, _, n_in = utils.refine_alignment(res, pred['reprojection_threshold'],
                                                   threshold=pred['matching']['method_kwargs'].get('threshold', -1.0)
-                                                  if pred['matching']['method'] == 'nnmatcher' else -1.0,
-                                                  **({} if model == 'homography' else {'model': model}))
+                                                  if pred['matching']['method'] == 'nnmatcher' else -1.0, model=model)
     if int(n_in[0]) < utils.transform_min_inliers(model):
         print(before + ' -> no refined estimate')
         return H_est
@@ -381,11 +380,7 @@ def main(argv=None):
             kpt_est = kpt if sub_thermal is None else sub_thermal.cpu().numpy()
             optical_pts = np.array([kpo_est[m.queryIdx][::-1] for m in matches]).reshape(-1, 2)
             thermal_pts = np.array([kpt_est[m.trainIdx][::-1] for m in matches]).reshape(-1, 2)
-            if model == 'homography':
-                H_est, mask = utils.find_homography_points(optical_pts, thermal_pts, pred['reprojection_threshold'], device=device)
-            else:
-                H_est, mask = utils.find_transform_points(optical_pts, thermal_pts, model, pred['reprojection_threshold'],
-                                                          device=device)
+            H_est, mask = utils.find_transform_points(optical_pts, thermal_pts, model, pred['reprojection_threshold'], device=device)
             if H_est is None:
                 H_est = np.eye(3, 3)
             eye = torch.eye(3)

@@ -454,13 +454,16 @@ def test_c_abi_refusals():
     nin = torch.zeros(P, dtype=torch.int32, device=DEV); cost = torch.zeros((P, 2), dtype=torch.float64, device=DEV)
     st = _lib.stream_ptr(dev)
 
+    def margs(entry, model):                               # (the *_homography* entries take no model)
+        return () if 'homography' in entry else (model,)
+
     def find(entry='mp_find_transform', k=kp, P=P, K=K, model=1, thr=3.0, T_=256, H=Hm):
-        return getattr(h.lib, entry)(h.ptr, _lib.ptr(k), _lib.ptr(cnt), _lib.ptr(midx), P, K, model, thr, T_, 0, _lib.ptr(H),
-                                     _lib.ptr(mask), _lib.ptr(nin), st)
+        return getattr(h.lib, entry)(h.ptr, _lib.ptr(k), _lib.ptr(cnt), _lib.ptr(midx), P, K, *margs(entry, model), thr, T_, 0,
+                                     _lib.ptr(H), _lib.ptr(mask), _lib.ptr(nin), st)
 
     def refine(entry='mp_refine_transform', k=kp, P=P, K=K, model=2, thr=3.0, rounds=3, H=Hm):
-        return getattr(h.lib, entry)(h.ptr, _lib.ptr(k), _lib.ptr(cnt), _lib.ptr(midx), P, K, model, thr, rounds, _lib.ptr(H),
-                                     _lib.ptr(mask), _lib.ptr(nin), _lib.ptr(cost), st)
+        return getattr(h.lib, entry)(h.ptr, _lib.ptr(k), _lib.ptr(cnt), _lib.ptr(midx), P, K, *margs(entry, model), thr, rounds,
+                                     _lib.ptr(H), _lib.ptr(mask), _lib.ptr(nin), _lib.ptr(cost), st)
     bad = ((dict(model=3), 'model'), (dict(model=-1), 'model'), (dict(thr=0.0), 'threshold'), (dict(K=0), 'K'), (dict(K=3201), 'K'),
            (dict(P=0), 'P'), (dict(H=None), 'NULL'))
     for entry, k in (('mp_find_transform', kp), ('mp_find_transform_f', kpf)):
@@ -475,18 +478,31 @@ def test_c_abi_refusals():
             assert refine(entry, k, **kw) == -1, kw
             msg = h.lib.mp_last_error(h.ptr).decode()
             assert word in msg and entry in msg, (kw, msg)
+    # the *_homography* entries are the same bodies at MP_MODEL_HOMOGRAPHY: the same tables without the model rows
+    for entry, k in (('mp_find_homography', kp), ('mp_find_homography_f', kpf)):
+        assert find(entry, k) == 0
+        for kw, word in bad[2:] + ((dict(T_=0), 'max_iters'), (dict(T_=(1 << 20) + 1), 'max_iters')):
+            assert find(entry, k, **kw) == -1, kw
+            msg = h.lib.mp_last_error(h.ptr).decode()
+            assert word in msg and entry in msg, (kw, msg)
+    for entry, k in (('mp_refine_homography', kp), ('mp_refine_homography_f', kpf)):
+        assert refine(entry, k) == 0
+        for kw, word in bad[2:] + ((dict(rounds=-1), 'iters'), (dict(rounds=1001), 'iters')):
+            assert refine(entry, k, **kw) == -1, kw
+            msg = h.lib.mp_last_error(h.ptr).decode()
+            assert word in msg and entry in msg, (kw, msg)
     # pooled
     pts = torch.zeros((64, 4), dtype=torch.float32, device=DEV); go = torch.tensor([0, 16], dtype=torch.int32, device=DEV)
     H1 = torch.zeros(9, dtype=torch.float64, device=DEV); pmask = torch.zeros(64, dtype=torch.uint8, device=DEV)
     n1 = torch.zeros(1, dtype=torch.int32, device=DEV); ws = torch.zeros(1 << 16, dtype=torch.uint8, device=DEV)
 
-    def pfind(p=pts, N=16, G=1, model=1, thr=3.0, T_=256, wsb=ws.numel()):
-        return h.lib.mp_find_transform_pooled(h.ptr, ctypes.c_void_p(p.data_ptr()), _lib.ptr(go), N, G, model, thr, T_, 0, _lib.ptr(H1),
-                                              _lib.ptr(pmask), _lib.ptr(n1), _lib.ptr(ws), wsb, st)
+    def pfind(p=pts, N=16, G=1, model=1, thr=3.0, T_=256, wsb=ws.numel(), entry='mp_find_transform_pooled'):
+        return getattr(h.lib, entry)(h.ptr, ctypes.c_void_p(p.data_ptr()), _lib.ptr(go), N, G, *margs(entry, model), thr, T_, 0,
+                                     _lib.ptr(H1), _lib.ptr(pmask), _lib.ptr(n1), _lib.ptr(ws), wsb, st)
 
-    def prefine(p=pts, N=16, G=1, model=2, thr=3.0, rounds=3):
-        return h.lib.mp_refine_transform_pooled(h.ptr, ctypes.c_void_p(p.data_ptr()), _lib.ptr(go), N, G, model, thr, rounds,
-                                                _lib.ptr(H1), _lib.ptr(pmask), _lib.ptr(n1), None, st)
+    def prefine(p=pts, N=16, G=1, model=2, thr=3.0, rounds=3, entry='mp_refine_transform_pooled'):
+        return getattr(h.lib, entry)(h.ptr, ctypes.c_void_p(p.data_ptr()), _lib.ptr(go), N, G, *margs(entry, model), thr, rounds,
+                                     _lib.ptr(H1), _lib.ptr(pmask), _lib.ptr(n1), None, st)
     assert pfind() == 0 and pfind(model=0) == 0 and pfind(model=2) == 0 and prefine() == 0 and prefine(model=0) == 0
     pbad = ((dict(model=7), 'model'), (dict(N=1 << 24), '2^24'), (dict(G=0), 'G'), (dict(G=65536), 'G'), (dict(thr=-1.0), 'threshold'),
             (dict(p=pts.reshape(-1)[1:]), 'aligned'))
@@ -496,4 +512,16 @@ def test_c_abi_refusals():
     for kw, word in pbad + ((dict(rounds=-1), 'rounds'), (dict(rounds=1001), 'rounds')):
         assert prefine(**kw) == -1, kw
         assert word in h.lib.mp_last_error(h.ptr).decode(), kw
+    entry = 'mp_find_homography_pooled'
+    assert pfind(entry=entry) == 0
+    for kw, word in pbad[1:] + ((dict(T_=0), 'max_iters'), (dict(T_=(1 << 20) + 1), 'max_iters'), (dict(wsb=512), 'workspace')):
+        assert pfind(entry=entry, **kw) == -1, kw
+        msg = h.lib.mp_last_error(h.ptr).decode()
+        assert word in msg and entry in msg, (kw, msg)
+    entry = 'mp_refine_homography_pooled'
+    assert prefine(entry=entry) == 0
+    for kw, word in pbad[1:] + ((dict(rounds=-1), 'iters'), (dict(rounds=1001), 'iters')):
+        assert prefine(entry=entry, **kw) == -1, kw
+        msg = h.lib.mp_last_error(h.ptr).decode()
+        assert word in msg and entry in msg, (kw, msg)
     torch.cuda.synchronize()
