@@ -6,57 +6,43 @@
 // x up to 8 ranges a thread needs are ONE round trip of independent loads.  (Round 3 did the same inside the convolution launch --
 // the last range to arrive, found through a device-scope counter, gathered the shares: 64 values x 8 ranges per thread are 8-16
 // dependent ~1.5 us trips behind a write-through / counter / barrier hand-off, which was most of what a small launch cost.)
+// What an item is, which tile and channels a thread of the convolution workgroup owns and where its shares lie is mp_wino43.h's,
+// as it is the convolution kernels': the item shape, the item decode, the tile numbering and the share index are the same calls.
 #include "mp_common.h"
 #include "mp_device.h"
 #include "mp_tile.h"
+#include "mp_wino43.h"
 
 namespace {
 
-// GEN 1: conv_wino43.hip (512 threads per item, 32 values each: [h][a][b]); GEN 2: conv_wino43b.hip (256 threads, 64 values:
-// [m][h][a][b]).  The index arithmetic below is the epilogues' own (lane = tile, register quad = 4 consecutive output channels).
+// GEN 1: conv_wino43.hip, GEN 2: conv_wino43b.hip
 template <int GEN, bool POOL, bool BNF, int TC4>
 __global__ __launch_bounds__(256) void split_reduce_kernel(const ConvParams p)
 {
-    constexpr int T = GEN == 1 ? 512 : 256;            // threads of a convolution workgroup
-    constexpr int NV = GEN == 1 ? 32 : 64;             // shares (f32x2) per thread
-    constexpr int NQ = NV / 8;                         // (m,) h, row pair
-    constexpr int OY = 4 * (32 / TC4), OX = 4 * TC4;   // output pixels of an item
+    using Share = W43Share<GEN>;
+    constexpr int T = Share::T;
+    constexpr int NQ = Share::NV / 8;                  // (m,) h, row pair
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
     const int tid = (int)(gid % T), q = (int)((gid / T) % NQ);
     const int g = (int)(gid / (T * NQ));               // (tile block, slice)
     if (g >= p.nitems) return;
-    const int tile = (int)udiv((unsigned)g, p.magic_slices, (unsigned)p.nslices);
-    const int slice = g - tile * p.nslices;
-    const int trow = (int)udiv((unsigned)tile, p.magic_tx, (unsigned)p.tiles_x);
-    const int tx0 = tile - trow * p.tiles_x;
-    const int bi = (int)udiv((unsigned)trow, p.magic_ty, (unsigned)p.tiles_y);
-    const int ty0 = trow - bi * p.tiles_y;
-    const int img = p.img_list ? p.img_list[bi] : bi;
-    const int lane = tid & 63, wave = tid >> 6, tb = wave & 1;
-    const int tl = tb * 16 + (lane & 15);              // tile of the item
-    int t_ty, t_tx, cl, h, idx0;
+    const W43Item at = w43_item<TC4>(p, g);
+    const int lane = tid & 63, wave = tid >> 6;
+    int t_ty, t_tx;
+    w43_tile_pos<GEN, TC4>(w43_lane_tile(wave & 1, lane), t_ty, t_tx);
     const int ap = q & 1;                              // output rows 2 ap, 2 ap + 1 of the 4 x 4 tile
-    if (GEN == 1) {
-        t_ty = tl / TC4; t_tx = tl % TC4;
-        cl = (wave >> 1) * 16 + 4 * (lane >> 4);
-        h = q >> 1; idx0 = h * 16;
-    } else {
-        t_ty = TC4 == 8 ? (tl >> 2) & 3 : tl >> 2; t_tx = TC4 == 8 ? 4 * (tl >> 4) + (tl & 3) : tl & 3;
-        const int m = q >> 2;
-        cl = (wave >> 1) * 32 + m * 16 + 4 * (lane >> 4);
-        h = (q >> 1) & 1; idx0 = (m * 2 + h) * 16;
-    }
+    const int h = (q >> 1) & 1, m = q >> 2;            // channel pair of the lane's quad, column block (generation 2)
     const int KS = 1 << p.ks_shift;
     const unsigned long long* const part = reinterpret_cast<const unsigned long long*>(p.split_scratch) +
-                                           ((long long)g << p.ks_shift) * (NV * T) + (long long)(idx0 + 8 * ap) * T + tid;
+                                           ((long long)g << p.ks_shift) * Share::ITEM + w43_share_index<GEN>(m, h, 2 * ap, 0) + tid;
     unsigned long long rawv[8][8];
 #pragma unroll
     for (int k = 0; k < 8; ++k)
         if (k < KS) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) rawv[k][i] = part[(long long)k * (NV * T) + i * T];
+            for (int i = 0; i < 8; ++i) rawv[k][i] = part[(long long)k * Share::ITEM + w43_share_index<GEN>(0, 0, i >> 2, i & 3)];
         }
-    const int ch = slice * 64 + cl + 2 * h;            // this thread's two output channels
+    const int ch = at.slice * 64 + w43_lane_channel<GEN>(wave >> 1, lane, m) + 2 * h;            // this thread's two output channels
     const f32x2 bb = {p.bias[ch], p.bias[ch + 1]}, ss = {p.scale[ch], p.scale[ch + 1]}, tt = {p.shift[ch], p.shift[ch + 1]};
     f32x2 yv[2][4];
 #pragma unroll
@@ -65,18 +51,15 @@ __global__ __launch_bounds__(256) void split_reduce_kernel(const ConvParams p)
 #pragma unroll
         for (int k = 1; k < 8; ++k)
             if (k < KS) v += __builtin_bit_cast(f32x2, rawv[k][i]);         // range order: deterministic
-        v = w43_add_bias(v, 2 * ap + (i >> 2), i & 3, bb);          // (the shares are the SCALED transform's values: at6s, mp_common.h)
-        if (BNF) { v = v * ss + tt; v = f32x2{relu_bits(v[0]), relu_bits(v[1])}; }
-        else { v = f32x2{relu_bits(v[0]), relu_bits(v[1])}; v = v * ss + tt; }
-        yv[i >> 2][i & 3] = v;
+        yv[i >> 2][i & 3] = w43_act<BNF>(v, 2 * ap + (i >> 2), i & 3, bb, ss, tt);
     }
     if (ch >= p.cout) return;
-    const int oy = ty0 * OY + 4 * t_ty, ox = tx0 * OX + 4 * t_tx;
+    const int oy = at.y0 + 4 * t_ty, ox = at.x0 + 4 * t_tx;
     const int Ho = POOL ? p.H >> 1 : p.H, Wo = POOL ? p.W >> 1 : p.W;
     const int cs = p.out_cstride;
     // NHWC: pixel stride cs floats; planar [B][cout/4][Ho][Wo][4]: the channel pair is floats 2h, 2h+1 of plane ch / 4
-    float* const img_base = p.out_planar ? p.out + (long long)img * (p.cout / 4) * Ho * Wo * 4 + ((long long)(ch >> 2) * Ho * Wo) * 4 + (ch & 3)
-                                         : p.out + (long long)img * Ho * Wo * cs + p.out_coff + ch;
+    float* const img_base = p.out_planar ? p.out + (long long)at.img * (p.cout / 4) * Ho * Wo * 4 + ((long long)(ch >> 2) * Ho * Wo) * 4 + (ch & 3)
+                                         : p.out + (long long)at.img * Ho * Wo * cs + p.out_coff + ch;
     const int ps = p.out_planar ? 4 : cs;
     if (POOL) {
         const int py = (oy >> 1) + ap;
@@ -100,35 +83,25 @@ __global__ __launch_bounds__(256) void split_reduce_kernel(const ConvParams p)
     }
 }
 
-template <int GEN, bool POOL, int TC4>
-void launch_r(const ConvParams& q, hipStream_t s)
+template <int GEN>
+int launch_r(const ConvParams& p, bool pool, hipStream_t s)
 {
-    const long long threads = (long long)q.nitems * (GEN == 1 ? 512 * 4 : 256 * 8);
-    const unsigned grid = (unsigned)((threads + 255) / 256);
-    if (q.bn_first) hipLaunchKernelGGL((split_reduce_kernel<GEN, POOL, true, TC4>), dim3(grid), dim3(256), 0, s, q);
-    else hipLaunchKernelGGL((split_reduce_kernel<GEN, POOL, false, TC4>), dim3(grid), dim3(256), 0, s, q);
+    const int tc4 = w43_cover(p.H, p.W).tc4;
+    ConvParams q = p;
+    if (w43_launch_items(q, tc4, false)) return 1;
+    if (q.nitems == 0) return 0;
+    const long long threads = (long long)q.nitems * W43Share<GEN>::ITEM / 8;        // a thread sums 8 values of every range
+    w43_dispatch(tc4, pool, p.bn_first, [&](auto pool_tag, auto bnf_tag, auto tc4_tag) {
+        hipLaunchKernelGGL((split_reduce_kernel<GEN, decltype(pool_tag)::value, decltype(bnf_tag)::value, decltype(tc4_tag)::value>),
+                           dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, q);
+    });
+    return 0;
 }
 
 }  // namespace
 
-// p: the layer's parameters as forward.hip built them (REAL slices, ks_shift > 0); gen: 1 conv_wino43.hip, 2 conv_wino43b.hip.  The item
-// shape is the one the convolution launchers pick (fewer items; 16 x 32 pixels on a tie)
+// p: the layer's parameters as forward.hip built them (REAL slices, ks_shift > 0); gen: 1 conv_wino43.hip, 2 conv_wino43b.hip
 int launch_split_reduce(const ConvParams& p, int gen, bool pool, hipStream_t s)
 {
-    const long long wide = (long long)((p.W + 31) / 32) * ((p.H + 15) / 16), tall = (long long)((p.W + 15) / 16) * ((p.H + 31) / 32);
-    const int tc4 = tall < wide ? 4 : 8;
-    const int OY = 4 * (32 / tc4), OX = 4 * tc4;
-    ConvParams q = p;
-    q.tiles_x = (p.W + OX - 1) / OX; q.tiles_y = (p.H + OY - 1) / OY;
-    const long long nitems = (long long)p.B * q.tiles_x * q.tiles_y * p.nslices;
-    if (nitems <= 0) return 0;
-    if (tile_items(q, nitems)) return 1;
-    if (gen == 1) {
-        if (tc4 == 4) { if (pool) launch_r<1, true, 4>(q, s); else launch_r<1, false, 4>(q, s); }
-        else { if (pool) launch_r<1, true, 8>(q, s); else launch_r<1, false, 8>(q, s); }
-    } else {
-        if (tc4 == 4) { if (pool) launch_r<2, true, 4>(q, s); else launch_r<2, false, 4>(q, s); }
-        else { if (pool) launch_r<2, true, 8>(q, s); else launch_r<2, false, 8>(q, s); }
-    }
-    return 0;
+    return gen == 1 ? launch_r<1>(p, pool, s) : launch_r<2>(p, pool, s);
 }

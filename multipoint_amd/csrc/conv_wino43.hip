@@ -37,6 +37,7 @@
 #include "mp_common.h"
 #include "mp_device.h"
 #include "mp_tile.h"
+#include "mp_wino43.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -48,10 +49,11 @@ MP_TIMING_HEIGHT(g_timing_q_sel, 480, mp_debug_select_height_wino43)
 namespace {
 
 // an item's 32 tiles are 4 rows x 8 columns (16 x 32 output pixels, raw patch 18 x 34) or -- TC4 = 4 -- 8 rows x 4 columns (32 x 16
-// pixels, patch 34 x 18): launch_q picks the shape with fewer phantom tiles (60 x 80 layers: 8 instead of 12 items per image)
+// pixels, patch 34 x 18): w43_cover() (mp_wino43.h, where everything this source shares with conv_wino43b.hip and conv_split.hip
+// stands) picks the shape with fewer phantom tiles (60 x 80 layers: 10 instead of 12 items per image)
 constexpr int NPIX = 18 * 34;                      // 612 patch pixels = 16-byte granules (4 channels each), either shape
-constexpr int UC4 = 4;                             // input channels per unit
-constexpr int VB4 = UC4 * 32 * 36;                 // floats per V buffer  [ch][tile][pos]   (18 KiB)
+constexpr int UC4 = W43_UC;                        // input channels per unit
+constexpr int VB4 = W43_VUNIT;                     // floats per V buffer  [ch][tile][pos]   (18 KiB): a (tile block, unit) of vglobal as it is
 constexpr int UB4 = UC4 * 64 * 36;                 // floats per U buffer  [ch][cout][pos]   (36 KiB)
 constexpr int NRB = (NPIX + 63) / 64;              // raw DMA blocks of 64 granules (10)
 constexpr int RB4 = NRB * 64 * 4;                  // floats per raw buffer: 10 blocks (10 KiB); one dummy block behind the three
@@ -90,9 +92,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
 {
     static_assert(!(F1 && SPLIT), "the fused first block is never split");
     static_assert(!(VIN && (F1 || SPLIT)), "pre-transformed input: plain launches only");
-    constexpr int TR4 = 32 / TC4;                      // tile rows x tile columns of an item
-    constexpr int OY = 4 * TR4, OX = 4 * TC4;          // output pixels of an item
-    constexpr int PY = OY + 2, PX = OX + 2;            // raw patch
+    constexpr int OY = W43Shape<TC4>::OY, OX = W43Shape<TC4>::OX;      // output pixels of an item
+    constexpr int PY = W43Shape<TC4>::PY, PX = W43Shape<TC4>::PX;      // raw patch
     static_assert(PY * PX == NPIX, "item shape");
     __shared__ __attribute__((aligned(16))) float Vs[(VIN ? 4 : 2) * VB4];
     __shared__ __attribute__((aligned(16))) float Us[2 * UB4];
@@ -118,6 +119,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
 
     struct Where { int slice, img, y0, x0, tile; const float* in_base; };
     auto decode = [&](int it) __attribute__((always_inline)) -> Where {
+        // w43_item<TC4> (mp_wino43.h) written out: with any form of the call the SPLIT instantiations compile differently, and
+        // the split 128 -> 128 layer at 120 x 160 then misses the A/B margin (figures: DESIGN.md, "What the F(4x4,3x3) sources share")
         Where w{};
         const int tile = (int)udiv((unsigned)it, p.magic_slices, (unsigned)p.nslices);
         w.slice = it - tile * p.nslices;
@@ -242,7 +245,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
     // ---- input transform V = B^T d B of one unit: 8 lanes per window (tile, channel pair); lanes 0-5 work ----
     const int win = tid >> 3, sub = tid & 7;             // window 0..63 of the unit: tile = win >> 1, channel pair = win & 1
     const int w_tile = win >> 1, w_cp = win & 1;
-    const int w_ty = w_tile / TC4, w_tx = w_tile % TC4;  // tile row / column inside the item
+    int w_ty, w_tx;                                      // tile row / column inside the item
+    w43_tile_pos<1, TC4>(w_tile, w_ty, w_tx);
     const int sub6 = sub < 6 ? sub : 5;                  // lanes 6, 7 repeat lane 5's work (results identical, harmless)
     // pass 1: column `sub6` of the window: patch pixels (4*w_ty + i, 4*w_tx + sub6), i = 0..5, channels 2*w_cp, 2*w_cp+1
     const int p1_read = ((4 * w_ty) * PX + 4 * w_tx + sub6) * 4 + 2 * w_cp;             // floats into raw[]
@@ -554,8 +558,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
         f32x4 acc[36];
         const int item_next = item + stride;
         const bool has_next = item_next < item_end;
-        const int next_slice = has_next ? (int)(item_next - (int)udiv((unsigned)item_next, p.magic_slices, (unsigned)p.nslices) * p.nslices)
-                                        : cur.slice;
+        const int next_slice = has_next ? w43_slice(p, item_next) : cur.slice;
         const float* unext = u_ptr(next_slice);
         // schedule of the input transform inside a unit (group g, slot e behind the e-th MFMA of the group)
         auto tf_at = [&](const int g, const int e, const int vb) __attribute__((always_inline)) {
@@ -707,6 +710,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
         if constexpr (F1) { if (item_next + stride < item_end) patch_dma(decode(item_next + stride), cur_par); }
         // ---- output transform Y = A^T M A in registers, bias / ReLU / BN, [2x2 max-pool], store ----
         // lane = tile (lane & 15) of the wave's tile block, registers r = output channels 4 * (lane >> 4) + r of its channel block
+        // (tile, channels and tile position written out -- w43_lane_tile, w43_lane_channel<1>, w43_tile_pos<1> of mp_wino43.h: as calls they
+        // change the register allocation of the 14 instantiations that have this epilogue; DESIGN.md as above)
         const int tl = tb * 16 + (lane & 15);                       // tile of the item: row tl / TC4, column tl % TC4
         const int cl = cb * 16 + 4 * (lane >> 4);                   // first of this lane's 4 output channels in the slice
         const f32x4 b4 = *reinterpret_cast<const f32x4*>(&prm[cl]);
@@ -722,35 +727,11 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
         f32x2 keep[NO][NO];
         // SPLIT: this item's share of the sum over input channels leaves as pre-bias output tiles; split_reduce_kernel (conv_split.hip),
         // the next launch on the stream, adds the ranges' shares up in range order (deterministic) and runs the rest of the epilogue
-        if constexpr (SPLIT) {
-            unsigned long long* const part = reinterpret_cast<unsigned long long*>(p.split_scratch) + (long long)item * (2 * 16 * 512) + tid;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                f32x2 tcol[4][6];
-#pragma unroll
-                for (int j = 0; j < 6; ++j) {
-                    f32x2 m[6], y[4];
-#pragma unroll
-                    for (int i = 0; i < 6; ++i) m[i] = f32x2{acc[6 * i + j][2 * h], acc[6 * i + j][2 * h + 1]};
-                    at6s(m, y);
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) tcol[a][j] = y[a];
-                }
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    f32x2 y[4];
-                    at6s(tcol[a], y);
-#pragma unroll
-                    for (int b = 0; b < 4; ++b)
-                        part[(h * 16 + a * 4 + b) * 512] = __builtin_bit_cast(unsigned long long, y[b]);
-                }
-            }
-        }
-        if constexpr (!SPLIT) {
+        unsigned long long* const part =
+            SPLIT ? reinterpret_cast<unsigned long long*>(p.split_scratch) + (long long)item * W43Share<1>::ITEM + tid : nullptr;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             f32x2 tcol[4][6];                                       // T[a][j] = sum_i A^T[a][i] M[i][j]
-            if constexpr (!SPLIT) {
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
                 f32x2 m[6], y[4];
@@ -760,7 +741,15 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
 #pragma unroll
                 for (int a = 0; a < 4; ++a) tcol[a][j] = y[a];
             }
-            }
+            if constexpr (SPLIT) {
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    f32x2 y[4];
+                    at6s(tcol[a], y);
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) part[w43_share_index<1>(0, h, a, b)] = __builtin_bit_cast(unsigned long long, y[b]);
+                }
+            } else {
             const f32x2 bb = {b4[2 * h], b4[2 * h + 1]}, ss = {s4[2 * h], s4[2 * h + 1]}, tt = {t4[2 * h], t4[2 * h + 1]};
             f32x2 res[NO][NO];
             if constexpr (POOL) {
@@ -818,12 +807,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
                 f32x2 y[4];
                 at6s(tcol[a], y);
 #pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    f32x2 v = w43_add_bias(y[b], a, b, bb);
-                    if (BNF) { v = v * ss + tt; v = f32x2{relu_bits(v[0]), relu_bits(v[1])}; }
-                    else { v = f32x2{relu_bits(v[0]), relu_bits(v[1])}; v = v * ss + tt; }
-                    yv[a][b] = v;
-                }
+                for (int b = 0; b < 4; ++b) yv[a][b] = w43_act<BNF>(y[b], a, b, bb, ss, tt);
             }
 #pragma unroll
             for (int a = 0; a < NO; ++a)
@@ -865,7 +849,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
                         }
                 }
             }
-        }
+            }
         }
         MP_CLOCK(t_e1);
         MP_CLOCK_ADD(2, t_e0, t_e1);                                        // epilogue
@@ -892,12 +876,11 @@ __global__ __launch_bounds__(512, 2) void conv_wino43_kernel(const ConvParams p)
 // the in-kernel transform runs (column pass first), so V has the same bits.  HBM/L2 streaming: reads 2.25x the input (the windows
 // of adjacent tiles overlap) coalesced over the channel pairs of a pixel, writes 2.25x the input as 144-byte runs.
 template <int TC4>
-__global__ __launch_bounds__(256) void wino43_vprod_kernel(const ConvParams p, long long ntb)
+__global__ __launch_bounds__(256) void wino43_vprod_kernel(const ConvParams p)
 {
     // A block = TL consecutive tiles of a tile block x every channel pair (256 threads = TL x cin / 2).  The reads stay coalesced over
     // the channel pairs of a pixel; the results are transposed through LDS so that they leave as 16-byte pieces of TL x 144-byte runs
     // (the first version stored each lane's 144-byte run directly: 64 pieces 9 KiB apart per store instruction, 0.18 ms).
-    constexpr int TR4 = 32 / TC4, OY = 4 * TR4, OX = 4 * TC4;
     __shared__ __attribute__((aligned(16))) float st[19456];      // cin x (TL x 36 + 4) floats: 18432 + 4 cin, cin <= 256
     const int ncp = p.cin >> 1, NC = p.cin / UC4;
     const int TL = 256 / ncp;                            // tiles per block (4 for cin = 128)
@@ -907,14 +890,11 @@ __global__ __launch_bounds__(256) void wino43_vprod_kernel(const ConvParams p, l
     const int cp = tid % ncp, tlc = tid / ncp;
     const long long tb = (long long)blockIdx.x / groups;
     const int t0 = ((int)((long long)blockIdx.x % groups)) * TL, t = t0 + tlc;
-    (void)ntb;
-    const int tx = (int)(tb % p.tiles_x);
-    const long long trow = tb / p.tiles_x;
-    const int ty = (int)(trow % p.tiles_y);
-    const int bi = (int)(trow / p.tiles_y);
-    const int img = p.img_list ? p.img_list[bi] : bi;
-    const int wy = ty * OY + 4 * (t / TC4) - 1, wx = tx * OX + 4 * (t % TC4) - 1;      // frame position of the window's corner
-    const float* const base = p.in + (long long)img * p.H * p.W * p.in_cstride + p.in_coff + 2 * cp;
+    const W43Item blk = w43_block<TC4>(p, (int)tb);
+    int t_ty, t_tx;
+    w43_tile_pos<1, TC4>(t, t_ty, t_tx);
+    const int wy = blk.y0 + 4 * t_ty - 1, wx = blk.x0 + 4 * t_tx - 1;      // frame position of the window's corner
+    const float* const base = p.in + (long long)blk.img * p.H * p.W * p.in_cstride + p.in_coff + 2 * cp;
     int gx[6];
 #pragma unroll
     for (int j = 0; j < 6; ++j) gx[j] = reflect_clamp(wx + j, p.W);
@@ -953,48 +933,30 @@ __global__ __launch_bounds__(256) void wino43_vprod_kernel(const ConvParams p, l
     }
 }
 
-template <bool POOL, int TC4, bool F1 = false, bool SPLIT = false>
-int launch_q(const ConvParams& p, hipStream_t s)
+// one launch with items of shape tc4.  F1: the fused first block (pooled, 16 x 32-pixel items); VIN (un-pooled): two passes -- the
+// input transform into p.vglobal, then the GEMMs + output transform per (tile block, slice) with V by DMA
+template <bool F1, bool SPLIT, bool VIN>
+int launch_q(const ConvParams& p, int tc4, bool pool, hipStream_t s)
 {
-    constexpr int OY = 4 * (32 / TC4), OX = 4 * TC4;
     ConvParams q = p;
-    if (SPLIT) q.nslices = p.nslices << p.ks_shift;         // virtual slices: (slice, range of input channels)
-    q.tiles_x = (p.W + OX - 1) / OX; q.tiles_y = (p.H + OY - 1) / OY;
-    const long long nitems = (long long)p.B * q.tiles_x * q.tiles_y * q.nslices;
-    if (nitems <= 0) return 0;
-    if (tile_items(q, nitems)) return 1;
-    const unsigned grid = persistent_grid(nitems, p.ncu, p.xcd_shift);
-    const ConvParams& pp = q;
-    if (p.bn_first) hipLaunchKernelGGL((conv_wino43_kernel<POOL, true, TC4, F1, SPLIT>), dim3(grid), dim3(512), 0, s, pp);
-    else hipLaunchKernelGGL((conv_wino43_kernel<POOL, false, TC4, F1, SPLIT>), dim3(grid), dim3(512), 0, s, pp);
-    return 0;
-}
-
-// two passes: the input transform into p.vglobal, then the GEMMs + output transform per (tile block, slice) with V by DMA
-template <int TC4>
-int launch_vin(const ConvParams& p, hipStream_t s)
-{
-    constexpr int OY = 4 * (32 / TC4), OX = 4 * TC4;
-    ConvParams q = p;
-    q.tiles_x = (p.W + OX - 1) / OX; q.tiles_y = (p.H + OY - 1) / OY;
-    const long long ntb = (long long)p.B * q.tiles_x * q.tiles_y, nitems = ntb * q.nslices;
-    if (nitems <= 0) return 0;
-    if (tile_items(q, nitems)) return 1;
-    const ConvParams& pp = q;
-    const int tl = 256 / (p.cin / 2);                    // tiles per producer block (launch_conv_wino43 checked the divisibility)
-    hipLaunchKernelGGL((wino43_vprod_kernel<TC4>), dim3((unsigned)(ntb * (32 / tl))), dim3(256), 0, s, pp, ntb);
-    const unsigned grid = persistent_grid(nitems, p.ncu, p.xcd_shift);
-    if (p.bn_first) hipLaunchKernelGGL((conv_wino43_kernel<false, true, TC4, false, false, true>), dim3(grid), dim3(512), 0, s, pp);
-    else hipLaunchKernelGGL((conv_wino43_kernel<false, false, TC4, false, false, true>), dim3(grid), dim3(512), 0, s, pp);
-    return 0;
-}
-
-// the item shape that covers the frame with fewer items (16 x 32 pixels on a tie: longer contiguous patch rows)
-template <bool POOL, bool SPLIT = false>
-int launch_shape(const ConvParams& p, hipStream_t s)
-{
-    const long long wide = (long long)((p.W + 31) / 32) * ((p.H + 15) / 16), tall = (long long)((p.W + 15) / 16) * ((p.H + 31) / 32);
-    return tall < wide ? launch_q<POOL, 4, false, SPLIT>(p, s) : launch_q<POOL, 8, false, SPLIT>(p, s);
+    if (w43_launch_items(q, tc4, SPLIT)) return 1;
+    if (q.nitems == 0) return 0;
+    const unsigned grid = persistent_grid(q.nitems, p.ncu, p.xcd_shift);
+    int rc = 0;
+    w43_dispatch(tc4, pool, p.bn_first, [&](auto pool_tag, auto bnf_tag, auto tc4_tag) {
+        constexpr bool POOL = decltype(pool_tag)::value, BNF = decltype(bnf_tag)::value;
+        constexpr int TC4 = decltype(tc4_tag)::value;
+        if constexpr (F1 ? !POOL || TC4 != 8 : VIN && POOL) {       // not an instantiation: shape not covered
+            rc = 2;
+        } else {
+            if constexpr (VIN) {
+                const int tl = 256 / (p.cin / 2);            // tiles per producer block (launch_conv_wino43 checked the divisibility)
+                hipLaunchKernelGGL((wino43_vprod_kernel<TC4>), dim3((unsigned)(q.nitems / q.nslices * (32 / tl))), dim3(256), 0, s, q);
+            }
+            hipLaunchKernelGGL((conv_wino43_kernel<POOL, BNF, TC4, F1, SPLIT, VIN>), dim3(grid), dim3(512), 0, s, q);
+        }
+    });
+    return rc;
 }
 
 }  // namespace
@@ -1008,19 +970,12 @@ bool conv_wino43_supports(const ConvParams& p)
            p.in_cstride % 4 == 0 && p.in_coff % 4 == 0 && p.out_cstride % 4 == 0 && p.out_coff % 4 == 0;
 }
 
-// work items of a launch (the larger of the two item shapes' counts is never chosen): what forward.hip sizes the split by
 // floats of p.vglobal a pre-transformed launch of this layer needs: tile blocks x (cin / 4) units x 18 KiB
-long long conv_wino43_vglobal_floats(const ConvParams& p)
-{
-    const long long wide = (long long)((p.W + 31) / 32) * ((p.H + 15) / 16), tall = (long long)((p.W + 15) / 16) * ((p.H + 31) / 32);
-    return (long long)p.B * std::min(wide, tall) * (p.cin / UC4) * VB4;
-}
+long long conv_wino43_vglobal_floats(const ConvParams& p) { return w43_vglobal_floats(p); }
 
-long long conv_wino43_items(const ConvParams& p)
-{
-    const long long wide = (long long)((p.W + 31) / 32) * ((p.H + 15) / 16), tall = (long long)((p.W + 15) / 16) * ((p.H + 31) / 32);
-    return (long long)p.B * std::min(wide, tall) * p.nslices;
-}
+// work items (tile block, slice) of an un-split launch of either generation, in the item shape mp_wino43.h's w43_cover() picks:
+// what forward.hip sizes the split and its scratch by
+long long conv_wino43_items(const ConvParams& p) { return (long long)p.B * w43_cover(p.H, p.W).blocks * p.nslices; }
 
 // p.wpack must point at the F(4x4,3x3) weights packed by pack_wino43_weights() (model_load.hip).  fuse_first: the input is the
 // first encoder block of p.img (p.w1 / b1 / s1 / t1, 64 channels), evaluated inside the kernel; the layer must be the pooled
@@ -1031,17 +986,17 @@ int launch_conv_wino43(const ConvParams& p, bool pool, hipStream_t s, bool fuse_
     // x-planar tensors: written by un-pooled launches only (a pooled tile's 2 columns are no whole 16-byte step), never split
     if (p.out_planar == MP_LAYOUT_XPLANAR && pool) return 2;
     if ((p.in_planar == MP_LAYOUT_XPLANAR || p.out_planar == MP_LAYOUT_XPLANAR) && p.ks_shift > 0) return 2;
-    if (fuse_first) return pool && p.cin == 64 ? launch_q<true, 8, true>(p, s) : 2;          // 2: shape not covered
+    if (fuse_first) return pool && p.cin == 64 ? launch_q<true, false, false>(p, 8, true, s) : 2;          // 2: shape not covered
+    const int tc4 = w43_cover(p.H, p.W).tc4;
     if (p.vglobal) {       // pre-transformed input (forward.hip: un-pooled layers with >= 4 output slices; cin a multiple of 16, NHWC)
         if (pool || p.ks_shift > 0 || p.cin % 16 != 0 || p.in_planar || p.cin > 256 || 256 % (p.cin / 2) != 0 || (p.cin / 2) < 8) return 2;
-        const long long wide = (long long)((p.W + 31) / 32) * ((p.H + 15) / 16), tall = (long long)((p.W + 15) / 16) * ((p.H + 31) / 32);
-        return tall < wide ? launch_vin<4>(p, s) : launch_vin<8>(p, s);
+        return launch_q<false, false, true>(p, tc4, false, s);
     }
     if (p.ks_shift > 0) {
         const int ncs = (p.cin / 4) >> p.ks_shift;
         if (ncs < 4 || (ncs & 1) || (ncs << p.ks_shift) * 4 != p.cin || !p.split_scratch) return 2;
-        const int rc = pool ? launch_shape<true, true>(p, s) : launch_shape<false, true>(p, s);
+        const int rc = launch_q<false, true, false>(p, tc4, pool, s);
         return rc ? rc : launch_split_reduce(p, 1, pool, s);
     }
-    return pool ? launch_shape<true>(p, s) : launch_shape<false>(p, s);
+    return launch_q<false, false, false>(p, tc4, pool, s);
 }

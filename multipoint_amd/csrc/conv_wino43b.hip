@@ -30,13 +30,14 @@
 #include "mp_common.h"
 #include "mp_device.h"
 #include "mp_tile.h"
+#include "mp_wino43.h"
 
 #include <algorithm>
 #include <type_traits>
 
 namespace {
 
-constexpr int UC4 = 4;                             // input channels per unit
+constexpr int UC4 = W43_UC;                        // input channels per unit
 constexpr int UB4 = UC4 * 64 * 36;                 // floats per U buffer  [ch][cout][pos]   (36 KiB)
 constexpr int VR4 = 36 * 64 + 1;                   // floats per channel region of a V' buffer: [pos][lane], odd so that the two channels of a pair sit one bank apart
 constexpr int VB4 = 2 * VR4 + 2;                   // floats per V' buffer (16-byte multiple)
@@ -83,9 +84,8 @@ __device__ __forceinline__ float acc_read(float a)
 template <bool POOL, bool BNF, int TC4, bool ZPAD, bool SPLIT = false>
 __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p)
 {
-    constexpr int TR4 = 32 / TC4;                      // tile rows x tile columns of an item
-    constexpr int OY = 4 * TR4, OX = 4 * TC4;          // output pixels of an item
-    constexpr int PY = OY + 2, PX = OX + 2;            // raw patch
+    constexpr int OY = W43Shape<TC4>::OY, OX = W43Shape<TC4>::OX;      // output pixels of an item
+    constexpr int PY = W43Shape<TC4>::PY, PX = W43Shape<TC4>::PX;      // raw patch
     // raw patch in LDS: granule slot(y, x) = y * P + (y >> 2) + x -- rows stay contiguous (a DMA instruction's 64 lanes read runs of
     // consecutive pixels: 9-10 cache lines from a planar tensor), and the row skew y >> 2 makes the column pass conflict-free: a
     // 32-lane read group is 16 windows (4 tile rows x 4 tile columns, both channel pairs), whose pixels (4 ty + k, 4 tx + c) sit at
@@ -123,17 +123,9 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
     int item = xr.item;
     if (item >= item_end) return;
 
-    struct Where { int slice, img, y0, x0; const float* in_base; };
+    struct Where : W43Item { const float* in_base; };
     auto decode = [&](int it) __attribute__((always_inline)) -> Where {
-        Where w{};
-        const int tile = (int)udiv((unsigned)it, p.magic_slices, (unsigned)p.nslices);
-        w.slice = it - tile * p.nslices;
-        const int trow = (int)udiv((unsigned)tile, p.magic_tx, (unsigned)p.tiles_x);
-        const int tx = tile - trow * p.tiles_x;
-        const int bi = (int)udiv((unsigned)trow, p.magic_ty, (unsigned)p.tiles_y);
-        const int ty = trow - bi * p.tiles_y;
-        w.img = p.img_list ? p.img_list[bi] : bi;
-        w.y0 = ty * OY; w.x0 = tx * OX;
+        Where w{w43_item<TC4>(p, it), nullptr};
         w.in_base = p.in_planar ? p.in + (long long)w.img * (p.cin / 4) * p.H * p.W * 4
                                 : p.in + (long long)w.img * p.H * p.W * p.in_cstride + p.in_coff;
         if constexpr (SPLIT)      // first unit of the item's range of input channels
@@ -276,8 +268,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
         int ln = lane;
         asm volatile("" : "+v"(ln));                                           // (opaque: not hoisted out of the item loop)
         lane16 = (unsigned)ln * 16u;
-        // tile number T of the item: 16 consecutive tiles = 4 tile rows x 4 tile columns (TC4 = 8: T = 16 (tx >> 2) + 4 ty + (tx & 3);
-        // TC4 = 4: T = 4 ty + tx)
+        // tile row / column of the window's tile: w43_tile_pos<2, TC4> (mp_wino43.h) written out -- as a call, the shifts no longer fold
+        // with the lane's (ln >> 1) and every instantiation changes
         const int w_tile = ln >> 1, w_cp = ln & 1;
         const int w_ty = TC4 == 8 ? (w_tile >> 2) & 3 : w_tile >> 2, w_tx = TC4 == 8 ? 4 * (w_tile >> 4) + (w_tile & 3) : w_tile & 3;
         tf_rd = raw_lds + (unsigned)((((4 * w_ty) * P + w_ty + 4 * w_tx) * 4 + 2 * w_cp) * 4);
@@ -362,8 +354,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
         f32x4 acc[36][2];
         const int item_next = item + stride;
         const bool has_next = item_next < item_end;
-        const int next_slice = has_next ? (int)(item_next - (int)udiv((unsigned)item_next, p.magic_slices, (unsigned)p.nslices) * p.nslices)
-                                        : cur.slice;
+        const int next_slice = has_next ? w43_slice(p, item_next) : cur.slice;
         const float* unext = u_ptr(next_slice);
         // one unit: 72 MFMAs and everything that rides in their shadow -- one basic block.  ROLE 0: column pass of unit n+2 (reads
         // raw(n+2)), ROLE 1: row pass of unit n+1 (writes V'[vb ^ 1]).  Slot (g, q): behind MFMA q = 2 e + m of group g.
@@ -456,20 +447,21 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");               // the last MFMAs' results (asm statements: no hazard tracking)
         int eln = lane;
         asm volatile("" : "+v"(eln));                            // (opaque: the epilogue's lane constants are not hoisted out of the item loop)
-        const int tl = tb * 16 + (eln & 15);                        // tile T of the item (numbering: lane_values())
-        const int t_ty = TC4 == 8 ? (tl >> 2) & 3 : tl >> 2, t_tx = TC4 == 8 ? 4 * (tl >> 4) + (tl & 3) : tl & 3;
+        const int tl = w43_lane_tile(tb, eln);                    // tile of the item
+        int t_ty, t_tx;
+        w43_tile_pos<2, TC4>(tl, t_ty, t_tx);
         const int oy = cur.y0 + 4 * t_ty, ox = cur.x0 + 4 * t_tx;
         const int cs = p.out_cstride;
         constexpr int NO = POOL ? 2 : 4;                            // output rows / columns per tile
         const int Ho = POOL ? p.H >> 1 : p.H, Wo = POOL ? p.W >> 1 : p.W;
         const int py0 = POOL ? oy >> 1 : oy, px0 = POOL ? ox >> 1 : ox;
         // MODE 0: the ordinary epilogue; 1 (SPLIT): this range's pre-bias output tiles -> split_scratch
-        unsigned long long* const part = SPLIT ? reinterpret_cast<unsigned long long*>(p.split_scratch) + (long long)item * (64 * 256) + tid : nullptr;
+        unsigned long long* const part = SPLIT ? reinterpret_cast<unsigned long long*>(p.split_scratch) + (long long)item * W43Share<2>::ITEM + tid : nullptr;
         auto epilogue = [&](auto mode_tag) __attribute__((always_inline)) {
         constexpr int MODE = decltype(mode_tag)::value;
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
-        const int cl = cbb * 32 + m * 16 + 4 * (eln >> 4);          // first of this lane's 4 output channels in the slice
+        const int cl = w43_lane_channel<2>(cbb, eln, m);           // first of this lane's 4 output channels in the slice
         const f32x4 b4 = *reinterpret_cast<const f32x4*>(&prm[cl]);
         const f32x4 s4 = *reinterpret_cast<const f32x4*>(&prm[64 + cl]);
         const f32x4 t4 = *reinterpret_cast<const f32x4*>(&prm[128 + cl]);
@@ -501,17 +493,14 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
                     f32x2 y[4];
                     at6s(tcol[a], y);
 #pragma unroll
-                    for (int b = 0; b < 4; ++b) part[((m * 2 + h) * 16 + a * 4 + b) * 256] = __builtin_bit_cast(unsigned long long, y[b]);
+                    for (int b = 0; b < 4; ++b) part[w43_share_index<2>(m, h, a, b)] = __builtin_bit_cast(unsigned long long, y[b]);
                 }
             } else {
             const f32x2 bb = {b4[2 * h], b4[2 * h + 1]}, ss = {s4[2 * h], s4[2 * h + 1]}, tt = {t4[2 * h], t4[2 * h + 1]};
             // row a of the 4x4 output tile, pre-bias
             auto out_row = [&](const int a, f32x2 (&y)[4]) __attribute__((always_inline)) { at6s(tcol[a], y); };
             auto act = [&](f32x2 v, const int r, const int c) __attribute__((always_inline)) -> f32x2 {
-                v = w43_add_bias(v, r, c, bb);
-                if (BNF) { v = v * ss + tt; return f32x2{relu_bits(v[0]), relu_bits(v[1])}; }
-                v = f32x2{relu_bits(v[0]), relu_bits(v[1])};
-                return v * ss + tt;
+                return w43_act<BNF>(v, r, c, bb, ss, tt);
             };
             // a uniform per-image base + 32-bit byte offsets (an image's output is far below 4 GB).  NHWC: pixel stride
             // cs floats; planar [B][cout/4][Ho][Wo][4]: this lane's quad is plane ch0 / 4, pixel stride 16 bytes
@@ -588,29 +577,19 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
     if (cbb == 0) item_loop(std::integral_constant<int, 0>{}); else item_loop(std::integral_constant<int, 1>{});
 }
 
-template <bool POOL, int TC4, bool ZPAD, bool SPLIT = false>
-int launch_q(const ConvParams& p, hipStream_t s)
+template <bool ZPAD, bool SPLIT>
+int launch_q(const ConvParams& p, bool pool, hipStream_t s)
 {
-    constexpr int OY = 4 * (32 / TC4), OX = 4 * TC4;
+    const int tc4 = w43_cover(p.H, p.W).tc4;
     ConvParams q = p;
-    if (SPLIT) q.nslices = p.nslices << p.ks_shift;         // virtual slices: (slice, range of input channels)
-    q.tiles_x = (p.W + OX - 1) / OX; q.tiles_y = (p.H + OY - 1) / OY;
-    const long long nitems = (long long)p.B * q.tiles_x * q.tiles_y * q.nslices;
-    if (nitems <= 0) return 0;
-    if (tile_items(q, nitems)) return 1;
-    const unsigned grid = persistent_grid(nitems, p.ncu, p.xcd_shift);
-    const ConvParams& pp = q;
-    if (p.bn_first) hipLaunchKernelGGL((conv_wino43b_kernel<POOL, true, TC4, ZPAD, SPLIT>), dim3(grid), dim3(256), 0, s, pp);
-    else hipLaunchKernelGGL((conv_wino43b_kernel<POOL, false, TC4, ZPAD, SPLIT>), dim3(grid), dim3(256), 0, s, pp);
+    if (w43_launch_items(q, tc4, SPLIT)) return 1;
+    if (q.nitems == 0) return 0;
+    const unsigned grid = persistent_grid(q.nitems, p.ncu, p.xcd_shift);
+    w43_dispatch(tc4, pool, p.bn_first, [&](auto pool_tag, auto bnf_tag, auto tc4_tag) {
+        hipLaunchKernelGGL((conv_wino43b_kernel<decltype(pool_tag)::value, decltype(bnf_tag)::value, decltype(tc4_tag)::value, ZPAD, SPLIT>),
+                           dim3(grid), dim3(256), 0, s, q);
+    });
     return 0;
-}
-
-// the item shape that covers the frame with fewer items (16 x 32 pixels on a tie: longer contiguous patch rows)
-template <bool POOL, bool ZPAD, bool SPLIT = false>
-int launch_shape(const ConvParams& p, hipStream_t s)
-{
-    const long long wide = (long long)((p.W + 31) / 32) * ((p.H + 15) / 16), tall = (long long)((p.W + 15) / 16) * ((p.H + 31) / 32);
-    return tall < wide ? launch_q<POOL, 4, ZPAD, SPLIT>(p, s) : launch_q<POOL, 8, ZPAD, SPLIT>(p, s);
 }
 
 }  // namespace
@@ -630,10 +609,8 @@ int launch_conv_wino43b(const ConvParams& p, bool pool, hipStream_t s)
     if (p.ks_shift > 0) {        // forward.hip: single-pair launches with fewer items than CUs
         const int ncs = (p.cin / UC4) >> p.ks_shift;
         if (ncs < 2 || (ncs & 1) || (ncs << p.ks_shift) * UC4 != p.cin || !p.split_scratch) return 2;
-        const int rc = p.pad_zero ? (pool ? launch_shape<true, true, true>(p, s) : launch_shape<false, true, true>(p, s))
-                                  : (pool ? launch_shape<true, false, true>(p, s) : launch_shape<false, false, true>(p, s));
+        const int rc = p.pad_zero ? launch_q<true, true>(p, pool, s) : launch_q<false, true>(p, pool, s);
         return rc ? rc : launch_split_reduce(p, 2, pool, s);
     }
-    if (p.pad_zero) return pool ? launch_shape<true, true>(p, s) : launch_shape<false, true>(p, s);
-    return pool ? launch_shape<true, false>(p, s) : launch_shape<false, false>(p, s);
+    return p.pad_zero ? launch_q<true, false>(p, pool, s) : launch_q<false, false>(p, pool, s);
 }

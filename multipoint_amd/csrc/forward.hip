@@ -1,6 +1,7 @@
 // C ABI, the forward: the launch plan of the hot path, its executors, and the batch-statistics forward (mp_forward,
 // mp_forward_batch_stats).
 #include "host.h"
+#include "mp_wino43.h"
 
 using namespace mp_host;
 
@@ -219,7 +220,7 @@ int run_conv(mp_handle* h, const ConvLayer& L, const ConvLaunch& c, const T* in,
             p.wpack = L.u43pack_f1; p.bias = L.bias_f1; p.w1 = first->w_f1; p.b1 = first->bias_f1; p.s1 = nullptr; p.t1 = nullptr;
         }
         if (c.ks_shift) {
-            const int rc = ensure(h, h->split_ws, (size_t)(conv_wino43_items(p) << c.ks_shift) * (2 * 16 * 512 * 8));
+            const int rc = ensure(h, h->split_ws, w43_split_bytes(conv_wino43_items(p) << c.ks_shift));
             if (rc) return rc;
             p.ks_shift = c.ks_shift; p.split_scratch = static_cast<float*>(h->split_ws.p);
         }

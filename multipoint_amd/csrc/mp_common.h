@@ -57,7 +57,7 @@ struct ConvParams {
     // run as separate items; their pre-bias output tiles meet in split_scratch, and split_reduce_kernel (conv_split.hip, the next
     // launch on the stream) sums them in range order and runs the rest of the epilogue.  ks_shift = 0: off.
     int ks_shift;
-    float* split_scratch;     // [virtual item][32 or 64 values][512 or 256 threads] f32x2 (128 KiB per virtual item)
+    float* split_scratch;     // [virtual item][32 or 64 values][512 or 256 threads] f32x2 (128 KiB per virtual item; mp_wino43.h: W43Share)
     // conv_wino43.hip, layers with many output slices (the 3x3 head convolutions): the input transform runs as a pass of its own
     // into vglobal [tile block][cin / 4][4][32][36] (conv_wino43_vglobal_floats()) and every slice's launch items DMA V from there
     // instead of transforming the same windows again.  nullptr: the transform runs inside the kernel, per slice.
