@@ -104,6 +104,36 @@ int mp_load_weights(mp_handle* h, const mp_model_config* cfg, const mp_tensor* t
 int mp_forward(mp_handle* h, const float* images, const unsigned char* is_optical, int B, int H,
                int W, float* prob, float* logits, float* desc, void* stream);
 
+/* The launch plan of mp_forward for a B x H x W forward of the loaded model, read-only: one record per convolution launch the
+ * planner decides on -- each encoder's first block (when it is a launch of its own), its 3x3 layers, and the launch of both 3x3 head
+ * convolutions -- in launch order (multispectral: the thermal encoder's, then the optical one's).  The 1x1 head layers are not
+ * planned: they run in the fused head tail or on the direct / streaming kernels for every shape.  Nothing is launched or allocated;
+ * the records come from the functions mp_forward itself plans and sizes its launches with.  No reference counterpart: the
+ * reference leaves kernel selection to ATen.  For tests and tools that must know which kernel instantiation a shape reaches. */
+#define MP_PLAN_FIRST 0             /* the first block (Cin = 1) as a launch of its own */
+#define MP_PLAN_DIRECT 1            /* direct implicit-GEMM fp32 kernel */
+#define MP_PLAN_WINO43 2            /* fp32 F(4x4,3x3), frames that are multiples of the 4x4 tile, reflection padding */
+#define MP_PLAN_WINO43B 3           /* fp32 F(4x4,3x3), any frame, either padding */
+#define MP_PLAN_F16 4               /* fp16 streaming kernel */
+#define MP_PLAN_F16_RES 5           /* fp16 kernel with LDS-resident weights */
+#define MP_PLAN_F16_RES_SLICES 6    /* ... launched once per 64-channel output slice */
+typedef struct mp_plan_launch {
+    const char* name;           /* the launch's profile name (mp_profile_read), e.g. "enc.conv1+2", "enc.conv5", "heads.conv3x3" */
+    int kernel;                 /* MP_PLAN_* */
+    int images, H, W;           /* the launch's input: images of this encoder (heads: of the forward), frame of this layer */
+    int pooled;                 /* the launch applies the 2x2 max-pool that follows the layer */
+    int tc4;                    /* F(4x4,3x3): tile columns of an item, 8 (16 x 32 pixels) or 4 (32 x 16 pixels); else 0 */
+    int ks_shift;               /* F(4x4,3x3): the input channels run as 2^ks_shift ranges (forwards of one or two images) */
+    int vin;                    /* F(4x4,3x3): the input is transformed once, by a pass of its own, in front of the launch */
+    int fuse_first;             /* the first block is evaluated inside this launch */
+    int in_layout, out_layout;  /* 0 NHWC, 1 channel-quad planar, 2 column-interleaved planar */
+    int workgroups;             /* F(4x4,3x3): workgroups of the persistent launch; else 0 */
+    long long items;            /* F(4x4,3x3): work items (tile block, slice [, range]) the workgroups walk; else 0 */
+} mp_plan_launch;
+/*   n_optical  images the optical encoder receives (multispectral models; ignored otherwise)
+ *   out        capacity records or NULL; *n receives the number of records of the plan (only the first `capacity` are written) */
+int mp_forward_plan(mp_handle* h, int B, int H, int W, int n_optical, mp_plan_launch* out, int capacity, int* n);
+
 /* replaces MultiPoint.forward in TRAINING mode, forward only (the reference's train.py never calls net.eval(), so its validation
  * loop, train.py:127-150, runs this): every BatchNorm2d normalises with the mean and biased variance of this batch (eps 1e-5);
  * the detector head returns logits only (MultiPoint.py:150-158).  fp32 models with BatchNorm only: mixed_precision models and

@@ -40,6 +40,15 @@ class Tensor(ctypes.Structure):
     _fields_ = [('name', ctypes.c_char_p), ('data', c_void_p), ('numel', c_ll)]
 
 
+class PlanLaunch(ctypes.Structure):
+    _fields_ = [('name', ctypes.c_char_p)] + [(n, c_int) for n in (
+        'kernel', 'images', 'H', 'W', 'pooled', 'tc4', 'ks_shift', 'vin', 'fuse_first', 'in_layout', 'out_layout',
+        'workgroups')] + [('items', c_ll)]
+
+
+MP_PLAN_KERNELS = ('first', 'direct', 'wino43', 'wino43b', 'f16', 'f16_res', 'f16_res_slices')
+MP_LAYOUTS = ('nhwc', 'planar', 'xplanar')
+
 MP_PHOTO_MAX_OPS, MP_PHOTO_MAX_TAPS, MP_PHOTO_MAX_BLUR = 16, 11, 801
 
 
@@ -86,6 +95,7 @@ SIGNATURES = {
     'mp_load_weights': (c_int, [c_void_p, ctypes.POINTER(ModelConfig), ctypes.POINTER(Tensor), c_int]),
     'mp_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                            c_void_p, c_void_p]),
+    'mp_forward_plan': (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(PlanLaunch), c_int, ctypes.POINTER(c_int)]),
     'mp_forward_batch_stats': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                        c_void_p]),
     'mp_batch_stats_count': (c_int, [c_void_p, ctypes.POINTER(c_int)]),
@@ -351,6 +361,24 @@ class Handle:
         a, b, c = c_int(), c_int(), c_int()
         self.check(self.lib.mp_device_shape(self.ptr, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return a.value, b.value, c.value
+
+    def forward_plan(self, B, H, W, n_optical=None):
+        """The launch plan of mp_forward for a B x H x W forward of the loaded model (n_optical: images the optical encoder of a
+        multispectral model receives; default B): a list of dicts, one per planned convolution launch in launch order, with the
+        fields of mp_plan_launch (kernel and layouts as names).  Launches nothing."""
+        n = c_int()
+        no = B if n_optical is None else int(n_optical)
+        self.check(self.lib.mp_forward_plan(self.ptr, B, H, W, no, None, 0, ctypes.byref(n)))
+        recs = (PlanLaunch * max(n.value, 1))()
+        self.check(self.lib.mp_forward_plan(self.ptr, B, H, W, no, recs, n.value, ctypes.byref(n)))
+        out = []
+        for r in recs[:n.value]:
+            d = {k: getattr(r, k) for k, _ in PlanLaunch._fields_}
+            d['name'] = r.name.decode()
+            d['kernel'] = MP_PLAN_KERNELS[r.kernel]
+            d['in_layout'], d['out_layout'] = MP_LAYOUTS[r.in_layout], MP_LAYOUTS[r.out_layout]
+            out.append(d)
+        return out
 
     def __del__(self):
         try:

@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256) void split_reduce_kernel(const ConvParams p)
 template <int GEN>
 int launch_r(const ConvParams& p, bool pool, hipStream_t s)
 {
-    const int tc4 = w43_cover(p.H, p.W).tc4;
+    const int tc4 = w43_launch_tc4(p.H, p.W, false);
     ConvParams q = p;
     if (w43_launch_items(q, tc4, false)) return 1;
     if (q.nitems == 0) return 0;

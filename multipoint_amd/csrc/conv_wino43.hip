@@ -938,10 +938,10 @@ __global__ __launch_bounds__(256) void wino43_vprod_kernel(const ConvParams p)
 template <bool F1, bool SPLIT, bool VIN>
 int launch_q(const ConvParams& p, int tc4, bool pool, hipStream_t s)
 {
-    ConvParams q = p;
-    if (w43_launch_items(q, tc4, SPLIT)) return 1;
+    ConvParams q;
+    unsigned grid;
+    if (w43_launch_shape(p, tc4, SPLIT, q, grid)) return 1;
     if (q.nitems == 0) return 0;
-    const unsigned grid = persistent_grid(q.nitems, p.ncu, p.xcd_shift);
     int rc = 0;
     w43_dispatch(tc4, pool, p.bn_first, [&](auto pool_tag, auto bnf_tag, auto tc4_tag) {
         constexpr bool POOL = decltype(pool_tag)::value, BNF = decltype(bnf_tag)::value;
@@ -986,8 +986,8 @@ int launch_conv_wino43(const ConvParams& p, bool pool, hipStream_t s, bool fuse_
     // x-planar tensors: written by un-pooled launches only (a pooled tile's 2 columns are no whole 16-byte step), never split
     if (p.out_planar == MP_LAYOUT_XPLANAR && pool) return 2;
     if ((p.in_planar == MP_LAYOUT_XPLANAR || p.out_planar == MP_LAYOUT_XPLANAR) && p.ks_shift > 0) return 2;
-    if (fuse_first) return pool && p.cin == 64 ? launch_q<true, false, false>(p, 8, true, s) : 2;          // 2: shape not covered
-    const int tc4 = w43_cover(p.H, p.W).tc4;
+    if (fuse_first) return pool && p.cin == 64 ? launch_q<true, false, false>(p, w43_launch_tc4(p.H, p.W, true), true, s) : 2;   // 2: shape not covered
+    const int tc4 = w43_launch_tc4(p.H, p.W, false);
     if (p.vglobal) {       // pre-transformed input (forward.hip: un-pooled layers with >= 4 output slices; cin a multiple of 16, NHWC)
         if (pool || p.ks_shift > 0 || p.cin % 16 != 0 || p.in_planar || p.cin > 256 || 256 % (p.cin / 2) != 0 || (p.cin / 2) < 8) return 2;
         return launch_q<false, false, true>(p, tc4, false, s);

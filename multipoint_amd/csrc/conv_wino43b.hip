@@ -580,11 +580,11 @@ __global__ __launch_bounds__(256, 1) void conv_wino43b_kernel(const ConvParams p
 template <bool ZPAD, bool SPLIT>
 int launch_q(const ConvParams& p, bool pool, hipStream_t s)
 {
-    const int tc4 = w43_cover(p.H, p.W).tc4;
-    ConvParams q = p;
-    if (w43_launch_items(q, tc4, SPLIT)) return 1;
+    const int tc4 = w43_launch_tc4(p.H, p.W, false);
+    ConvParams q;
+    unsigned grid;
+    if (w43_launch_shape(p, tc4, SPLIT, q, grid)) return 1;
     if (q.nitems == 0) return 0;
-    const unsigned grid = persistent_grid(q.nitems, p.ncu, p.xcd_shift);
     w43_dispatch(tc4, pool, p.bn_first, [&](auto pool_tag, auto bnf_tag, auto tc4_tag) {
         hipLaunchKernelGGL((conv_wino43b_kernel<decltype(pool_tag)::value, decltype(bnf_tag)::value, decltype(tc4_tag)::value, ZPAD, SPLIT>),
                            dim3(grid), dim3(256), 0, s, q);

@@ -52,7 +52,8 @@ int launch_failed(mp_handle* h, int code, const char* name, int B, int H, int W)
 }
 
 // ---- the launch plan: which kernel runs which convolution ----------------------------------------------------------------------
-// plan_encoder() (run_forward() for the heads) makes every kernel choice of a forward; run_conv() executes one record.
+// plan_encoder() and plan_heads() make every kernel choice of a forward; run_conv() executes one record, mp_forward_plan() reports
+// the records without launching anything.
 
 enum class Kernel { direct, wino43, wino43b, f16, f16_res, f16_res_slices };
 
@@ -164,6 +165,18 @@ EncoderPlan plan_encoder(const mp_handle* h, const Encoder& E, int nb, int fwd_b
         if (L.pool) { hh /= 2; ww /= 2; }
     }
     return P;
+}
+
+// the launch of both 3x3 head convolutions over the B images of a forward at Hc x Wc = H/8 x W/8 (input: the encoder output, NHWC)
+ConvLaunch plan_heads(const mp_handle* h, int B, int Hc, int Wc)
+{
+    ConvLaunch c;
+    const ConvLayer& L = h->heads3;
+    if (h->cfg.mixed_precision) { c.kernel = f16_kind(h, L, L.cin, 0, false); return c; }
+    const int headc = h->cfg.descriptor_head ? 2 * h->head_channels : h->head_channels;
+    c.kernel = wino43_kind(h, L, Hc, Wc, L.cin, 0, headc, 0);
+    plan_split_vin(h, L, B, Hc, Wc, B, c);
+    return c;
 }
 
 // ---- executors ------------------------------------------------------------------------------------------------------------------
@@ -359,14 +372,9 @@ int run_forward(mp_handle* h, const float* images, const ImageRoute& route, int 
     const int hc = h->head_channels;                                 // 256 (channel_version 0) or descriptor_size
     const int headc = h->cfg.descriptor_head ? 2 * hc : hc;
     const int encc = h->heads3.cin;                                  // encoder output channels incl. padding: 128 (64 for channel_version 2)
-    ConvLaunch c3, c1x1;            // both 3x3 head convolutions in one launch; the 1x1 ones: the direct / streaming fp16 kernel
-    if constexpr (f16) {
-        c3.kernel = f16_kind(h, h->heads3, encc, 0, false);
-        c1x1.kernel = Kernel::f16;
-    } else {
-        c3.kernel = wino43_kind(h, h->heads3, Hc, Wc, encc, 0, headc, 0);
-        plan_split_vin(h, h->heads3, B, Hc, Wc, B, c3);
-    }
+    const ConvLaunch c3 = plan_heads(h, B, Hc, Wc);     // both 3x3 head convolutions in one launch
+    ConvLaunch c1x1;                                    // the 1x1 ones: the direct / streaming fp16 kernel
+    if constexpr (f16) c1x1.kernel = Kernel::f16;
     if ((rc = run_conv(h, h->heads3, c3, X, encc, 0, P, headc, 0, B, Hc, Wc, nullptr, s))) return rc;
     if (h->dbg.head_fuse && (!f16 || prob || logits || desc)) {
         // both 1x1 convolutions + BN + softmax / shuffle + normalisation in ONE launch that reads P once (head_tail*.hip).  Not
@@ -412,6 +420,67 @@ int run_forward(mp_handle* h, const float* images, const ImageRoute& route, int 
         prof_end(h, s);
     }
     return launch_status(h);
+}
+
+// ---- the plan as records (mp_forward_plan) ---------------------------------------------------------------------------------------
+
+int plan_kernel_code(Kernel k)
+{
+    switch (k) {
+    case Kernel::direct: return MP_PLAN_DIRECT;
+    case Kernel::wino43: return MP_PLAN_WINO43;
+    case Kernel::wino43b: return MP_PLAN_WINO43B;
+    case Kernel::f16: return MP_PLAN_F16;
+    case Kernel::f16_res: return MP_PLAN_F16_RES;
+    default: return MP_PLAN_F16_RES_SLICES;
+    }
+}
+
+// the record of launch c of layer L over B images at H x W: what run_conv() hands to the launcher, and for the F(4x4,3x3) kernels
+// the item shape, item count and workgroups their launchers derive from it (w43_launch_tc4, w43_launch_items, persistent_grid)
+mp_plan_launch plan_record(const mp_handle* h, const ConvLayer& L, const ConvLaunch& c, int B, int H, int W)
+{
+    mp_plan_launch r{};
+    r.name = c.fuse_first ? "enc.conv1+2" : L.name;
+    r.kernel = plan_kernel_code(c.kernel);
+    r.images = B; r.H = H; r.W = W;
+    r.pooled = L.pool ? 1 : 0;
+    r.ks_shift = c.ks_shift; r.vin = c.vin ? 1 : 0; r.fuse_first = c.fuse_first ? 1 : 0;
+    r.in_layout = c.in_planar; r.out_layout = c.out_planar;
+    if (c.kernel == Kernel::wino43 || c.kernel == Kernel::wino43b) {
+        ConvParams q{};
+        conv_geometry(h, L, q, (const float*)nullptr, L.cin, 0, (float*)nullptr, L.cout, 0, B, H, W);     // as run_conv() fills it
+        q.ks_shift = c.ks_shift;
+        ConvParams launch;
+        unsigned grid;
+        r.tc4 = w43_launch_tc4(H, W, c.fuse_first);
+        if (w43_launch_shape(q, r.tc4, c.ks_shift > 0, launch, grid) == 0) { r.items = launch.nitems; r.workgroups = (int)grid; }
+    }
+    return r;
+}
+
+// every record of run_forward(h, ..., route, B, H, W, ...), in launch order
+std::vector<mp_plan_launch> forward_plan(const mp_handle* h, const ImageRoute& route, int B, int H, int W)
+{
+    std::vector<mp_plan_launch> out;
+    for (int e = 0; e < 2; ++e) {
+        const int nb = route.counts[e];
+        if (nb == 0) continue;
+        const Encoder& E = h->enc[e];
+        const EncoderPlan plan = plan_encoder(h, E, nb, B, H, W);
+        if (!plan.conv[0].fuse_first) {
+            mp_plan_launch r{};
+            r.name = "enc.conv1"; r.kernel = MP_PLAN_FIRST; r.images = nb; r.H = H; r.W = W; r.pooled = E.first_pool ? 1 : 0;
+            r.out_layout = h->cfg.mixed_precision ? MP_LAYOUT_NHWC : plan.conv[0].in_planar;
+            out.push_back(r);
+        }
+        for (int i = 0, hh = E.first_pool ? H / 2 : H, ww = E.first_pool ? W / 2 : W; i < E.nconv; ++i) {
+            out.push_back(plan_record(h, E.conv[i], plan.conv[i], nb, hh, ww));
+            if (E.conv[i].pool) { hh /= 2; ww /= 2; }
+        }
+    }
+    out.push_back(plan_record(h, h->heads3, plan_heads(h, B, H / 8, W / 8), B, H / 8, W / 8));
+    return out;
 }
 
 // ---- the batch-statistics forward (mp_forward_batch_stats): MultiPoint.forward in training mode, forward only -------------------
@@ -623,6 +692,24 @@ int mp_forward(mp_handle* h, const float* images, const unsigned char* is_optica
     MP_HIP(hipSetDevice(h->device));
     return h->cfg.mixed_precision ? run_forward<_Float16>(h, images, route, B, H, W, prob, logits, desc, s)
                                   : run_forward<float>(h, images, route, B, H, W, prob, logits, desc, s);
+}
+
+int mp_forward_plan(mp_handle* h, int B, int H, int W, int n_optical, mp_plan_launch* out, int capacity, int* n)
+{
+    if (!h) return MP_EINVAL;
+    if (!n || capacity < 0 || (capacity > 0 && !out)) return fail(h, MP_EINVAL, "mp_forward_plan: NULL argument");
+    *n = 0;
+    if (!h->loaded) return fail(h, MP_ESTATE, "mp_forward_plan: no weights loaded (call mp_load_weights)");
+    if (B <= 0 || H <= 0 || W <= 0 || (H % 8) != 0 || (W % 8) != 0)
+        return fail(h, MP_EINVAL, "mp_forward_plan: B, H and W must be positive, H and W divisible by 8");
+    if (n_optical < 0 || n_optical > B) return fail(h, MP_EINVAL, "mp_forward_plan: n_optical must lie in 0..B");
+    ImageRoute route;
+    route.counts[0] = h->cfg.multispectral ? B - n_optical : B;
+    route.counts[1] = h->cfg.multispectral ? n_optical : 0;
+    const std::vector<mp_plan_launch> plan = forward_plan(h, route, B, H, W);
+    *n = (int)plan.size();
+    for (int i = 0; i < *n && i < capacity; ++i) out[i] = plan[i];
+    return MP_OK;
 }
 
 int mp_batch_stats_count(const mp_handle* h, int* count)

@@ -49,6 +49,8 @@ inline W43Cover w43_cover(int H, int W)
     const long long wide = (long long)((W + 31) / 32) * ((H + 15) / 16), tall = (long long)((W + 15) / 16) * ((H + 31) / 32);
     return tall < wide ? W43Cover{4, tall} : W43Cover{8, wide};
 }
+// the item shape of a launch: the fused first block (conv_wino43.hip F1) is instantiated for 16 x 32-pixel items only
+inline int w43_launch_tc4(int H, int W, bool fuse_first) { return fuse_first ? 8 : w43_cover(H, W).tc4; }
 // bytes of split_scratch for `vitems` virtual items, floats of vglobal for the layer p
 inline size_t w43_split_bytes(long long vitems) { return (size_t)vitems * W43Share<1>::ITEM * sizeof(f32x2); }
 inline long long w43_vglobal_floats(const ConvParams& p) { return (long long)p.B * w43_cover(p.H, p.W).blocks * (p.cin / W43_UC) * W43_VUNIT; }
@@ -64,6 +66,17 @@ inline int w43_launch_items(ConvParams& q, int tc4, bool vslices)
     const long long nitems = (long long)q.B * q.tiles_x * q.tiles_y * q.nslices;
     q.nitems = 0;
     return nitems <= 0 ? 0 : tile_items(q, nitems);
+}
+
+// One launch of layer p with items of shape tc4, as the launchers of both generations AND mp_forward_plan size it: q = the launch's
+// copy of the parameters (w43_launch_items), grid = its persistent workgroups (0: no items, nothing to launch).  Returns
+// w43_launch_items' code.
+inline int w43_launch_shape(const ConvParams& p, int tc4, bool vslices, ConvParams& q, unsigned& grid)
+{
+    q = p; grid = 0;
+    if (w43_launch_items(q, tc4, vslices)) return 1;
+    if (q.nitems > 0) grid = persistent_grid(q.nitems, p.ncu, p.xcd_shift);
+    return 0;
 }
 
 // runtime (tc4, pool, bn_first) -> f(POOL, BNF, TC4) with the three as std::integral_constant values

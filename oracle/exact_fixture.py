@@ -54,11 +54,13 @@ def config(name, **upd):
     return cfg
 
 
-def exact_images(seed, B, H, W):
-    """(B,1,H,W) fp32: integers 0..8 / 8; image B-1 of the batch is flat (constant)."""
+def exact_images(seed, B, H, W, flat_last=True):
+    """(B,1,H,W) fp32: integers 0..8 / 8; image B-1 of the batch is flat (constant) unless flat_last is false (a flat image cannot
+    show where a kernel read or wrote: the other images are the same either way)."""
     rng = np.random.default_rng([int(seed), 4242])
     x = rng.integers(0, 9, size=(B, 1, H, W)).astype(np.float32)
-    x[B - 1] = float(rng.integers(1, 9))
+    if flat_last:
+        x[B - 1] = float(rng.integers(1, 9))
     return torch.from_numpy(x / 8.0)
 
 
@@ -275,7 +277,13 @@ def magicleap64(sd, img):
     return O.forward_magicleap(sd64, img.double())
 
 
-MUTATIONS = ('corner', 'drop16', 'last_row', 'pool_preact_max')
+MUTATIONS = ('corner', 'drop16', 'last_row', 'pool_preact_max', 'last_col', 'block_edge')
+
+
+def default_block_edge(h, w):
+    """Where 'block_edge' lands in an h x w block output when the caller names no place: the first pixel of the last block of
+    16 rows x 32 columns (an F(4x4,3x3) item of 4 x 8 tiles)."""
+    return (h - 1) // 16 * 16, (w - 1) // 32 * 32
 
 
 def layer_outputs(sd, img, cfg=None, mixed=None, dtype=torch.float32, mutate=None, encoder_name='encoder'):
@@ -283,7 +291,9 @@ def layer_outputs(sd, img, cfg=None, mixed=None, dtype=torch.float32, mutate=Non
     oracle's arithmetic (fp16 restatement when `mixed`).  mutate = (layer name, mutation) injects one of MUTATIONS into that block,
     the way a kernel bug would: +1/8 at the bottom-right pixel of every channel ('corner'), the last 16 input channels ignored
     ('drop16'), the last output row a copy of the row above ('last_row'), max-pooling BEFORE the activation for every channel
-    ('pool_preact_max', the wrong order for negative BatchNorm scales)."""
+    ('pool_preact_max', the wrong order for negative BatchNorm scales), the last output column a copy of the column to its left
+    ('last_col'), +1/8 at ONE pixel of every channel ('block_edge': mutate = (layer, 'block_edge', (y, x)) in the block's output
+    frame, the first pixel of a tile block of the launch that computes it; default_block_edge() without a place)."""
     cfg = O.full_config(cfg)
     if mixed is not None:
         cfg['mixed_precision'] = bool(mixed)
@@ -317,6 +327,11 @@ def layer_outputs(sd, img, cfg=None, mixed=None, dtype=torch.float32, mutate=Non
             y = y.clone(); y[:, :, -1, -1] += 0.125
         elif mut == 'last_row':
             y = y.clone(); y[:, :, -1, :] = y[:, :, -2, :]
+        elif mut == 'last_col':
+            y = y.clone(); y[:, :, :, -1] = y[:, :, :, -2]
+        elif mut == 'block_edge':
+            at = mutate[2] if len(mutate) > 2 else default_block_edge(y.shape[2], y.shape[3])
+            y = y.clone(); y[:, :, at[0], at[1]] += 0.125
         return y
 
     with torch.no_grad():

@@ -56,13 +56,14 @@ def _iso(B):
     return torch.tensor([[b % 2 == 0] for b in range(B)])
 
 
-def _case(name, seed, B, H, W, spread='narrow'):
-    """(cfg, sd, img, is_optical, truth), the truth computed once per (config, seed, shape, spread)."""
-    key = (name, seed, B, H, W, spread)
+def _case(name, seed, B, H, W, spread='narrow', flat_last=True):
+    """(cfg, sd, img, is_optical, truth), the truth computed once per (config, seed, shape, spread).  flat_last false: no flat image
+    in the batch (exact_images makes image B - 1 flat, so a B = 1 case is ONE constant image, which cannot see where a kernel reads)."""
+    key = (name, seed, B, H, W, spread, flat_last)
     if key not in _TRUTH:
         cfg = X.config(name)
         sd = X.exact_weights(seed, cfg, spread)
-        img = X.exact_images(seed + 10 * H + W, B, H, W)
+        img = X.exact_images(seed + 10 * H + W, B, H, W, flat_last=flat_last)
         iso = _iso(B) if cfg['multispectral'] else None
         t = X.truth(sd, img, cfg, is_optical=iso, fp32=B * H * W > 3 * 72 * 104)
         _TRUTH[key] = (cfg, sd, img, iso, t)
@@ -141,11 +142,12 @@ def test_routings_are_bit_exact(monkeypatch, fam, upd, env, B, H, W, name):
     """Every direct fp32 and every fp16 launch (and two emulated machine shapes) on every shape: logits and raw descriptors
     equal the float64 forward; prob and descriptors within PROB_REL / PROB_ABS / DESC_ABS of float64 tails."""
     seed = (H + W) % 3
-    cfg, sd, img, iso, t = _case(name, seed, B, H, W)
-    got = _run(monkeypatch, cfg, sd, img, iso, env, upd)
-    ctx = (fam, env, name, seed, B, H, W)
-    _check_exact(got, t, ctx)
-    _check_tails(got, t, ctx, _tag(upd, env))
+    for flat_last in ((True, False) if B == 1 else (True,)):            # B = 1: the flat image, and a non-flat one
+        cfg, sd, img, iso, t = _case(name, seed, B, H, W, flat_last=flat_last)
+        got = _run(monkeypatch, cfg, sd, img, iso, env, upd)
+        ctx = (fam, env, name, seed, B, H, W, flat_last)
+        _check_exact(got, t, ctx)
+        _check_tails(got, t, ctx, _tag(upd, env))
 
 
 @pytest.mark.parametrize('name', list(X.CONFIGS))
@@ -234,8 +236,9 @@ def test_winograd_routings_against_exact_truth(monkeypatch, env, B, H, W):
     """The fp32 Winograd routings (default, the any-frame kernel everywhere, split input channels at B <= 2) round inside their
     transforms: the existing bars of tests/test_gpu_parity.py, measured against the exact truth."""
     seed = W % 3
-    cfg, sd, img, iso, t = _case('shipped', seed, B, H, W)
-    got = _run(monkeypatch, cfg, sd, img, iso, env, {})
-    assert float((got['logits'] - t['logits']).abs().max()) <= LOGITS_TOL
-    assert float((got['prob'].double() - t['prob']).abs().max()) <= PROB_TOL
-    assert float((got['desc'].double() - t['desc']).abs().max()) <= DESC_TOL
+    for flat_last in ((True, False) if B == 1 else (True,)):            # B = 1: the flat image, and a non-flat one
+        cfg, sd, img, iso, t = _case('shipped', seed, B, H, W, flat_last=flat_last)
+        got = _run(monkeypatch, cfg, sd, img, iso, env, {})
+        assert float((got['logits'] - t['logits']).abs().max()) <= LOGITS_TOL, flat_last
+        assert float((got['prob'].double() - t['prob']).abs().max()) <= PROB_TOL, flat_last
+        assert float((got['desc'].double() - t['desc']).abs().max()) <= DESC_TOL, flat_last
