@@ -52,21 +52,47 @@ int launch_failed(mp_handle* h, int code, const char* name, int B, int H, int W)
 }
 
 // ---- the launch plan: which kernel runs which convolution ----------------------------------------------------------------------
-// plan_encoder() and plan_heads() make every kernel choice of a forward; run_conv() executes one record, mp_forward_plan() reports
-// the records without launching anything.
+// plan_encoder() and plan_heads() make every kernel choice of a forward; plan_forward() walks the encoders once and lists the
+// convolution launches in order (PlannedLaunch).  run_forward() executes that list with run_first() / run_conv() and
+// mp_forward_plan() reports it (plan_record()) without launching anything, so what is reported is what runs.  The launches behind
+// the list (the fused head tail or the 1x1 head layers, softmax, normalisation) are straight code in run_forward().
 
-enum class Kernel { direct, wino43, wino43b, f16, f16_res, f16_res_slices };
+// the values are the codes mp_plan_launch::kernel reports
+enum class Kernel {
+    direct = MP_PLAN_DIRECT, wino43 = MP_PLAN_WINO43, wino43b = MP_PLAN_WINO43B,
+    f16 = MP_PLAN_F16, f16_res = MP_PLAN_F16_RES, f16_res_slices = MP_PLAN_F16_RES_SLICES
+};
 
 struct ConvLaunch {
     Kernel kernel = Kernel::direct;
     bool fuse_first = false;                    // the encoder's first block is evaluated inside this launch (enc.conv2)
-    int in_planar = MP_LAYOUT_NHWC, out_planar = MP_LAYOUT_NHWC;    // layout of the input / output tensor (fp32 F(4x4,3x3) launches only)
+    int in_layout = MP_LAYOUT_NHWC, out_layout = MP_LAYOUT_NHWC;    // MP_LAYOUT_* of the input / output tensor (fp32 F(4x4,3x3) launches only)
     int ks_shift = 0;                           // split-K: the input channels run as 2^ks_shift ranges (split_ws)
     bool vin = false;                           // the input is transformed once, by a pass of its own (vin_ws)
 };
 
-// conv[0].fuse_first false: the encoder's first block is a launch of its own (enc.conv1)
-struct EncoderPlan { ConvLaunch conv[7]; };
+// conv[0].fuse_first false: the encoder's first block is a launch of its own (enc.conv1).  H, W: each layer's input frame
+struct EncoderPlan { ConvLaunch conv[7]; int H[7], W[7]; };
+
+// one convolution launch of a forward.  The workspace buffers and the image-id lists are named, not pointed to: the plan is made
+// without a workspace, and run_forward<T>() resolves the names to pointers of its element type
+enum class Buf { images, P, Q, X };
+enum class Ids { none, thermal, optical };
+struct PlannedLaunch {
+    const ConvLayer* layer = nullptr;           // nullptr: the first block of `enc` as a launch of its own (c.out_layout alone is read)
+    const Encoder* enc = nullptr;               // the encoder of the layer (its first block: read when c.fuse_first); heads: nullptr
+    ConvLaunch c;
+    int images = 0, H = 0, W = 0;               // the launch's input
+    int in_cstride = 0, in_coff = 0, out_cstride = 0, out_coff = 0;
+    Buf in = Buf::images, out = Buf::P;         // a fused first block reads the images; its `in` is the buffer a launch of its own writes
+    Ids ids = Ids::none;
+};
+
+// 2 encoders x (first block + 7 layers) + the heads' 3x3 launch
+struct ForwardPlan { PlannedLaunch launch[17]; int n = 0; };
+
+// the profile name of a launch (mp_profile_read, mp_plan_launch::name)
+const char* launch_name(const PlannedLaunch& e) { return !e.layer ? "enc.conv1" : e.c.fuse_first ? "enc.conv1+2" : e.layer->name; }
 
 // which F(4x4,3x3) kernel a 3x3 layer at H x W goes to: wino43 = conv_wino43.hip (two waves per SIMD; reflection padding and
 // frames that are multiples of the 4x4 tile; the only one that evaluates the first block inside the launch), wino43b =
@@ -82,7 +108,7 @@ Kernel wino43_kind(const mp_handle* h, const ConvLayer& L, int H, int W, int in_
     return Kernel::direct;
 }
 
-// split-K and the pre-transformed input of an fp32 launch whose kernel, fuse_first and in_planar are decided
+// split-K and the pre-transformed input of an fp32 launch whose kernel, fuse_first and in_layout are decided
 void plan_split_vin(const mp_handle* h, const ConvLayer& L, int B, int H, int W, int fwd_batch, ConvLaunch& c)
 {
     if ((c.kernel != Kernel::wino43 && c.kernel != Kernel::wino43b) || c.fuse_first) return;
@@ -105,7 +131,7 @@ void plan_split_vin(const mp_handle* h, const ConvLayer& L, int B, int H, int W,
     // many output slices over one input (heads: 512 couts = 8 slices): transform the input ONCE (conv_wino43.hip VIN), from 4
     // slices on -- GEMM pass 0.865 ms at 75 % of the matrix pipe + 0.106 ms for the producer against 1.03 ms with the in-kernel
     // transform per slice
-    c.vin = c.kernel == Kernel::wino43 && !L.pool && c.ks_shift == 0 && !c.in_planar && L.cin % 16 == 0 && L.cin <= 256 &&
+    c.vin = c.kernel == Kernel::wino43 && !L.pool && c.ks_shift == 0 && !c.in_layout && L.cin % 16 == 0 && L.cin <= 256 &&
             256 % (L.cin / 2) == 0 && L.cin >= 16 && h->dbg.vin && L.nslices >= 4;
 }
 
@@ -131,13 +157,15 @@ EncoderPlan plan_encoder(const mp_handle* h, const Encoder& E, int nb, int fwd_b
         // the first block inside the conv2 launch (conv_f16_res.hip F1): reflection padding, the LDS-resident-weights kernel
         P.conv[0].fuse_first = h->dbg.f16_res && h->dbg.f16_fuse1 && h->cfg.reflection_pad && !E.first_pool && L0.pool &&
                                L0.cin == 64 && L0.cout == 64 && L0.nslices == 1;
-        for (int i = 0; i < E.nconv; ++i) P.conv[i].kernel = f16_kind(h, E.conv[i], E.conv[i].cin, 0, P.conv[i].fuse_first);
-        return P;
     }
+    // the one walk over a forward's frame sizes: the first block's pool, then every pooled layer halves them
     for (int i = 0, hh = E.first_pool ? H / 2 : H, ww = E.first_pool ? W / 2 : W; i < E.nconv; ++i) {
         const ConvLayer& L = E.conv[i];
         ConvLaunch& c = P.conv[i];
-        c.kernel = wino43_kind(h, L, hh, ww, L.cin, 0, L.cout, 0);
+        P.H[i] = hh; P.W[i] = ww;
+        if (L.pool) { hh /= 2; ww /= 2; }       // from here on: the next layer's frame
+        if (h->cfg.mixed_precision) { c.kernel = f16_kind(h, L, L.cin, 0, c.fuse_first); continue; }
+        c.kernel = wino43_kind(h, L, P.H[i], P.W[i], L.cin, 0, L.cout, 0);
         if (i == 0) {
             // the first block evaluated inside the conv2 launch: by conv_wino43.hip for the pooled 64 -> 64 layer with 64 real
             // channels; the direct kernels' fused loader is a 64-channel direct convolution, and with Winograd on, the standalone
@@ -152,41 +180,65 @@ EncoderPlan plan_encoder(const mp_handle* h, const Encoder& E, int nb, int fwd_b
         // costs the producer more than the consumer's patch DMAs gain: conv3 1.29 vs 1.17 ms.)  The encoder output stays NHWC
         // (a planar one was measured for the head convolution: slower).
         const bool producer = i == 0 ? !E.first_pool : P.conv[i - 1].kernel != Kernel::direct && E.conv[i - 1].pool;
-        c.in_planar = h->dbg.planar && c.kernel != Kernel::direct && producer ? MP_LAYOUT_PLANAR : MP_LAYOUT_NHWC;
-        plan_split_vin(h, L, nb, hh, ww, fwd_batch, c);
+        c.in_layout = h->dbg.planar && c.kernel != Kernel::direct && producer ? MP_LAYOUT_PLANAR : MP_LAYOUT_NHWC;
+        plan_split_vin(h, L, nb, P.H[i], P.W[i], fwd_batch, c);
         // ... and column-interleaved planar behind an UN-POOLED layer, when both ends are plain conv_wino43.hip launches (the
         // any-frame kernel, the split-K reduction and the pre-transformed-input pass read and write the other two layouts only): the
         // tile columns of an item are then consecutive 16-byte pieces, so a store instruction of the producer writes whole cache
         // lines instead of 16 half lines, and the consumer's patch rows are four runs instead of 34 pieces 256 bytes or more apart
         if (i > 0 && h->dbg.xplanar && !E.conv[i - 1].pool && P.conv[i - 1].kernel == Kernel::wino43 && P.conv[i - 1].ks_shift == 0 &&
             c.kernel == Kernel::wino43 && c.ks_shift == 0 && !c.vin)
-            c.in_planar = MP_LAYOUT_XPLANAR;
-        if (i > 0) P.conv[i - 1].out_planar = c.in_planar;
-        if (L.pool) { hh /= 2; ww /= 2; }
+            c.in_layout = MP_LAYOUT_XPLANAR;
+        if (i > 0) P.conv[i - 1].out_layout = c.in_layout;
     }
     return P;
 }
 
 // the launch of both 3x3 head convolutions over the B images of a forward at Hc x Wc = H/8 x W/8 (input: the encoder output, NHWC)
-ConvLaunch plan_heads(const mp_handle* h, int B, int Hc, int Wc)
+PlannedLaunch plan_heads(const mp_handle* h, int B, int Hc, int Wc)
 {
-    ConvLaunch c;
+    PlannedLaunch l;
     const ConvLayer& L = h->heads3;
-    if (h->cfg.mixed_precision) { c.kernel = f16_kind(h, L, L.cin, 0, false); return c; }
-    const int headc = h->cfg.descriptor_head ? 2 * h->head_channels : h->head_channels;
-    c.kernel = wino43_kind(h, L, Hc, Wc, L.cin, 0, headc, 0);
-    plan_split_vin(h, L, B, Hc, Wc, B, c);
-    return c;
+    // X -> P; L.cin: the encoder output channels incl. padding, 128 (64 for channel_version 2)
+    l.layer = &L; l.images = B; l.H = Hc; l.W = Wc; l.in = Buf::X; l.out = Buf::P; l.in_cstride = L.cin;
+    l.out_cstride = h->cfg.descriptor_head ? 2 * h->head_channels : h->head_channels;
+    if (h->cfg.mixed_precision) { l.c.kernel = f16_kind(h, L, L.cin, 0, false); return l; }
+    l.c.kernel = wino43_kind(h, L, Hc, Wc, L.cin, 0, l.out_cstride, 0);
+    plan_split_vin(h, L, B, Hc, Wc, B, l.c);
+    return l;
+}
+
+// every convolution launch of a B x H x W forward up to the heads' 3x3 one, in launch order; counts: the images of the thermal /
+// only encoder and of the optical one.  An encoder ping-pongs P and Q and leaves its last layer in X (its images' share of it)
+ForwardPlan plan_forward(const mp_handle* h, const int counts[2], int B, int H, int W)
+{
+    ForwardPlan plan;
+    for (int e = 0; e < 2; ++e) {
+        if (counts[e] == 0) continue;
+        const Encoder& E = h->enc[e];
+        const EncoderPlan ep = plan_encoder(h, E, counts[e], B, H, W);
+        PlannedLaunch l;                        // first the encoder's first block
+        l.enc = &E; l.images = counts[e]; l.H = H; l.W = W; l.c.out_layout = ep.conv[0].in_layout;
+        l.ids = !h->cfg.multispectral ? Ids::none : e == 0 ? Ids::thermal : Ids::optical;
+        if (!ep.conv[0].fuse_first) plan.launch[plan.n++] = l;
+        for (int i = 0; i < E.nconv; ++i) {
+            l.layer = &E.conv[i]; l.c = ep.conv[i]; l.H = ep.H[i]; l.W = ep.W[i]; l.in_cstride = l.layer->cin; l.out_cstride = l.layer->cout;
+            l.in = i % 2 ? Buf::Q : Buf::P; l.out = i == E.nconv - 1 ? Buf::X : i % 2 ? Buf::P : Buf::Q;
+            plan.launch[plan.n++] = l;
+        }
+    }
+    plan.launch[plan.n++] = plan_heads(h, B, H / 8, W / 8);
+    return plan;
 }
 
 // ---- executors ------------------------------------------------------------------------------------------------------------------
 
-// the ConvParams / ConvParamsH fields of a launch of layer L that every executor sets alike; returns the tile width
-template <typename P, typename T>
-int conv_geometry(const mp_handle* h, const ConvLayer& L, P& p, const T* in, int in_cstride, int in_coff, T* out, int out_cstride,
-                  int out_coff, int B, int H, int W)
+// the pointer-free ConvParams / ConvParamsH fields of a launch of layer L that every executor sets alike; returns the tile width
+template <typename P>
+int conv_geometry(const mp_handle* h, const ConvLayer& L, P& p, int in_cstride, int in_coff, int out_cstride, int out_coff, int B,
+                  int H, int W)
 {
-    p.in = in; p.out = out; p.B = B; p.H = H; p.W = W;
+    p.B = B; p.H = H; p.W = W;
     p.in_cstride = in_cstride; p.in_coff = in_coff; p.cin = L.cin;
     p.out_cstride = out_cstride; p.out_coff = out_coff; p.cout = L.cout; p.nslices = L.nslices;
     p.pad_zero = h->cfg.reflection_pad ? 0 : 1; p.bn_first = h->cfg.bn_first;
@@ -205,37 +257,48 @@ void conv1_geometry(const mp_handle* h, P& c1, const float* images, T* out, int 
     c1.pad_zero = h->cfg.reflection_pad ? 0 : 1; c1.bn_first = h->cfg.bn_first;
 }
 
-// one convolution launch as planned, either precision.  first: the encoder's first block (read when c.fuse_first), images: the
-// forward's input
+// everything of a planned launch's parameters that needs no workspace: what the launchers size the launch from, so also what
+// plan_record() asks them with; returns the tile width
+template <typename P>
+int conv_params(const mp_handle* h, const PlannedLaunch& e, P& p)
+{
+    if constexpr (std::is_same<P, ConvParams>::value) {
+        p.relu = e.layer->relu ? 1 : 0; p.persist = h->dbg.persist;
+        p.in_planar = e.c.in_layout; p.out_planar = e.c.out_layout; p.ks_shift = e.c.ks_shift;
+    } else {
+        p.res_groups = h->dbg.f16_res_groups;
+    }
+    return conv_geometry(h, *e.layer, p, e.in_cstride, e.in_coff, e.out_cstride, e.out_coff, e.images, e.H, e.W);
+}
+
+// one convolution launch as planned, either precision.  ids: the image ids of e.ids, images: the forward's input (read when
+// e.c.fuse_first)
 template <typename T>
-int run_conv(mp_handle* h, const ConvLayer& L, const ConvLaunch& c, const T* in, int in_cstride, int in_coff, T* out,
-             int out_cstride, int out_coff, int B, int H, int W, const int* img_list, hipStream_t s,
-             const FirstLayer* first = nullptr, const float* images = nullptr)
+int run_conv(mp_handle* h, const PlannedLaunch& e, const T* in, T* out, const int* ids, const float* images, hipStream_t s)
 {
     constexpr bool f16 = std::is_same<T, _Float16>::value;
+    const ConvLayer& L = *e.layer;
+    const ConvLaunch& c = e.c;
     typename std::conditional<f16, ConvParamsH, ConvParams>::type p{};
-    const int mbw = conv_geometry(h, L, p, in, in_cstride, in_coff, out, out_cstride, out_coff, B, H, W);
-    p.scale = L.scale; p.shift = L.shift; p.img_list = img_list;
-    if (c.fuse_first) {
+    const int mbw = conv_params(h, e, p);
+    p.in = in; p.out = out; p.scale = L.scale; p.shift = L.shift; p.img_list = ids;
+    const FirstLayer* first = c.fuse_first ? &e.enc->first : nullptr;
+    if (first) {
         p.img = images; p.w1 = f16 ? first->w_h : first->w; p.b1 = f16 ? first->bias_h : first->bias;
         p.s1 = first->scale; p.t1 = first->shift;
     }
     if constexpr (f16) {
         p.wpack = L.wpack_h; p.bias = L.bias_h;
         p.dummy = static_cast<_Float16*>(h->f16_dummy.p);
-        p.res_groups = h->dbg.f16_res_groups;
     } else {
         p.wpack = c.kernel == Kernel::direct ? L.wpack : L.u43pack; p.bias = L.bias;
-        p.relu = L.relu ? 1 : 0;
-        p.persist = h->dbg.persist;
-        p.in_planar = c.in_planar; p.out_planar = c.out_planar;
-        if (c.fuse_first && c.kernel != Kernel::direct) {      // the fused F(4x4,3x3) launch: the first block's BatchNorm is folded away (build_encoder)
+        if (first && c.kernel != Kernel::direct) {      // the fused F(4x4,3x3) launch: the first block's BatchNorm is folded away (build_encoder)
             p.wpack = L.u43pack_f1; p.bias = L.bias_f1; p.w1 = first->w_f1; p.b1 = first->bias_f1; p.s1 = nullptr; p.t1 = nullptr;
         }
         if (c.ks_shift) {
             const int rc = ensure(h, h->split_ws, w43_split_bytes(conv_wino43_items(p) << c.ks_shift));
             if (rc) return rc;
-            p.ks_shift = c.ks_shift; p.split_scratch = static_cast<float*>(h->split_ws.p);
+            p.split_scratch = static_cast<float*>(h->split_ws.p);
         }
         if (c.vin) {
             // The pre-transformed input is an OPTIONAL workspace (2.25 x the layer's input, linear in B): without it the kernel
@@ -244,8 +307,8 @@ int run_conv(mp_handle* h, const ConvLayer& L, const ConvLaunch& c, const T* in,
             else { (void)hipGetLastError(); h->err.clear(); }
         }
     }
-    prof_begin(h, c.fuse_first ? "enc.conv1+2" : L.name,
-               2.0 * L.taps * L.cin * L.cout * (double)B * H * W + (c.fuse_first ? 2.0 * 9 * 64 * (double)B * H * W : 0.0), s);
+    prof_begin(h, launch_name(e), 2.0 * L.taps * L.cin * L.cout * (double)e.images * e.H * e.W +
+                                      (c.fuse_first ? 2.0 * 9 * 64 * (double)e.images * e.H * e.W : 0.0), s);
     int big = 0;
     if constexpr (f16) {
         if (c.kernel == Kernel::f16_res) {
@@ -255,7 +318,7 @@ int run_conv(mp_handle* h, const ConvLayer& L, const ConvLaunch& c, const T* in,
                 ConvParamsH q = p;
                 q.wpack = p.wpack + (size_t)sl * 36 * 2 * 64 * 8;
                 q.bias = p.bias + 64 * sl; q.scale = p.scale + 64 * sl; q.shift = p.shift + 64 * sl;
-                q.out_coff = out_coff + 64 * sl; q.cout = 64; q.nslices = 1;
+                q.out_coff = e.out_coff + 64 * sl; q.cout = 64; q.nslices = 1;
                 big = conv_f16_res_supports(q, L.taps) ? launch_conv_f16_res(q, mbw, L.pool, s) : 2;
             }
         } else {
@@ -267,25 +330,25 @@ int run_conv(mp_handle* h, const ConvLayer& L, const ConvLaunch& c, const T* in,
                                           : launch_conv_mfma(p, L.taps, mbw, L.pool, c.fuse_first, s);
     }
     prof_end(h, s);
-    return big ? launch_failed(h, big, L.name, B, H, W) : MP_OK;
+    return big ? launch_failed(h, big, L.name, e.images, e.H, e.W) : MP_OK;
 }
 
-// the first block as a launch of its own; out_planar: its consumer reads channel-quad-planar (fp32 only)
+// the first block as a launch of its own (e.layer == nullptr)
 template <typename T>
-void run_first(mp_handle* h, const Encoder& E, bool out_planar, const float* images, T* out, int B, int H, int W,
-               const int* img_list, hipStream_t s)
+void run_first(mp_handle* h, const PlannedLaunch& e, const float* images, T* out, const int* ids, hipStream_t s)
 {
     constexpr bool f16 = std::is_same<T, _Float16>::value;
+    const Encoder& E = *e.enc;
     typename std::conditional<f16, Conv1ParamsH, Conv1Params>::type c1{};
-    conv1_geometry(h, c1, images, out, B, H, W);
+    conv1_geometry(h, c1, images, out, e.images, e.H, e.W);
     c1.w = f16 ? E.first.w_h : E.first.w; c1.bias = f16 ? E.first.bias_h : E.first.bias;
-    c1.scale = E.first.scale; c1.shift = E.first.shift; c1.img_list = img_list;
+    c1.scale = E.first.scale; c1.shift = E.first.shift; c1.img_list = ids;
     c1.pool = E.first_pool ? 1 : 0;                          // double_convolution: false -- MaxPool2d follows the block directly
-    prof_begin(h, "enc.conv1", 2.0 * 9 * 64 * (double)B * H * W, s);
+    prof_begin(h, launch_name(e), 2.0 * 9 * 64 * (double)e.images * e.H * e.W, s);
     if constexpr (f16) {
         launch_conv_first_f16(c1, s);
     } else {
-        c1.channels = E.first.channels; c1.out_planar = out_planar ? 1 : 0;
+        c1.channels = E.first.channels; c1.out_planar = e.c.out_layout == MP_LAYOUT_PLANAR ? 1 : 0;      // for a planar consumer
         launch_conv_first(c1, s);
     }
     prof_end(h, s);
@@ -346,36 +409,29 @@ int run_forward(mp_handle* h, const float* images, const ImageRoute& route, int 
 
     if (h->cfg.multispectral)       // pageable source: the runtime stages it before returning, so `ids` may die after this
         MP_HIP(hipMemcpyAsync(lists, route.ids.data(), 1024 * 4, hipMemcpyHostToDevice, s));
-    for (int e = 0; e < 2; ++e) {
-        const int nb = route.counts[e];
-        if (nb == 0) continue;
-        const Encoder& E = h->enc[e];
-        const int* list = h->cfg.multispectral ? lists + 512 * e : nullptr;
-        const EncoderPlan plan = plan_encoder(h, E, nb, B, H, W);
-        if (!plan.conv[0].fuse_first) run_first(h, E, plan.conv[0].in_planar == MP_LAYOUT_PLANAR, images, P, nb, H, W, list, s);
-        int hh = E.first_pool ? H / 2 : H, ww = E.first_pool ? W / 2 : W;
-        T* src = P;
-        T* dst = Q;
-        for (int i = 0; i < E.nconv; ++i) {
-            const ConvLayer& L = E.conv[i];
-            if ((rc = run_conv(h, L, plan.conv[i], src, L.cin, 0, i == E.nconv - 1 ? X : dst, L.cout, 0, nb, hh, ww, list, s,
-                               &E.first, images))) return rc;
-            if (L.pool) { hh /= 2; ww /= 2; }
-            T* t = src; src = dst; dst = t;
-        }
+    // the planned launches: the encoders and both 3x3 head convolutions (into P)
+    const ForwardPlan plan = plan_forward(h, route.counts, B, H, W);
+    T* const buf[] = {nullptr, P, Q, X};                // by Buf
+    const int* const ids[] = {nullptr, lists, lists + 512};     // by Ids
+    for (int i = 0; i < plan.n; ++i) {
+        const PlannedLaunch& e = plan.launch[i];
+        if (!e.layer) run_first(h, e, images, buf[(int)e.out], ids[(int)e.ids], s);
+        else if ((rc = run_conv(h, e, buf[(int)e.in], buf[(int)e.out], ids[(int)e.ids], images, s))) return rc;
     }
 
-    // heads
+    // the heads' tail, not planned: it is the same for every shape, and the fused launch falls back at run time
     const int Hc = H / 8, Wc = W / 8, lstride = f16 ? 128 : 80;
     const long long npx = (long long)B * Hc * Wc;
     const int D = h->cfg.descriptor_size;
     const int hc = h->head_channels;                                 // 256 (channel_version 0) or descriptor_size
-    const int headc = h->cfg.descriptor_head ? 2 * hc : hc;
-    const int encc = h->heads3.cin;                                  // encoder output channels incl. padding: 128 (64 for channel_version 2)
-    const ConvLaunch c3 = plan_heads(h, B, Hc, Wc);     // both 3x3 head convolutions in one launch
-    ConvLaunch c1x1;                                    // the 1x1 ones: the direct / streaming fp16 kernel
-    if constexpr (f16) c1x1.kernel = Kernel::f16;
-    if ((rc = run_conv(h, h->heads3, c3, X, encc, 0, P, headc, 0, B, Hc, Wc, nullptr, s))) return rc;
+    const int headc = plan.launch[plan.n - 1].out_cstride;
+    // a 1x1 head layer's launch (no part of the plan): the direct / streaming fp16 kernel on channels of P from in_coff on
+    auto launch1x1 = [&](const ConvLayer& L, int in_coff, int out_cstride) {
+        PlannedLaunch l;
+        l.layer = &L; l.c.kernel = f16 ? Kernel::f16 : Kernel::direct; l.images = B; l.H = Hc; l.W = Wc;
+        l.in_cstride = headc; l.in_coff = in_coff; l.out_cstride = out_cstride;
+        return l;
+    };
     if (h->dbg.head_fuse && (!f16 || prob || logits || desc)) {
         // both 1x1 convolutions + BN + softmax / shuffle + normalisation in ONE launch that reads P once (head_tail*.hip).  Not
         // instantiated for every model: then its profile entry is taken back, the separate launches below are profiled instead,
@@ -403,7 +459,7 @@ int run_forward(mp_handle* h, const float* images, const ImageRoute& route, int 
                             "using the separate 1x1 convolution, softmax and normalisation launches\n", hc, D);
         }
     }
-    if ((rc = run_conv(h, h->det1, c1x1, P, headc, 0, Lg, lstride, 0, B, Hc, Wc, nullptr, s))) return rc;
+    if ((rc = run_conv(h, launch1x1(h->det1, 0, lstride), P, Lg, nullptr, nullptr, s))) return rc;
     if (prob || logits) {
         prof_begin(h, "det.softmax_shuffle", 0.0, s);
         if constexpr (f16) launch_det_post_f16(Lg, lstride, B, Hc, Wc, prob, logits, h->cfg.softmax_mode, s);
@@ -413,7 +469,7 @@ int run_forward(mp_handle* h, const float* images, const ImageRoute& route, int 
     if (desc) {
         T* raw;                      // fp32: the descriptors are normalised in place
         if constexpr (f16) raw = R; else raw = desc;
-        if ((rc = run_conv(h, h->desc1, c1x1, P, headc, hc, raw, D, 0, B, Hc, Wc, nullptr, s))) return rc;
+        if ((rc = run_conv(h, launch1x1(h->desc1, hc, D), P, raw, nullptr, nullptr, s))) return rc;
         prof_begin(h, "desc.l2norm", 0.0, s);
         if constexpr (f16) launch_desc_l2norm_f16(R, desc, npx, D, h->cfg.normalize_descriptors ? 1 : 0, s);
         else if (h->cfg.normalize_descriptors) launch_desc_l2norm(desc, desc, npx, D, 1, s);
@@ -424,63 +480,26 @@ int run_forward(mp_handle* h, const float* images, const ImageRoute& route, int 
 
 // ---- the plan as records (mp_forward_plan) ---------------------------------------------------------------------------------------
 
-int plan_kernel_code(Kernel k)
+// the record of a planned launch, and for the F(4x4,3x3) kernels the item shape, item count and workgroups their launchers derive
+// from run_conv()'s parameters (w43_launch_tc4, w43_launch_items, persistent_grid)
+mp_plan_launch plan_record(const mp_handle* h, const PlannedLaunch& e)
 {
-    switch (k) {
-    case Kernel::direct: return MP_PLAN_DIRECT;
-    case Kernel::wino43: return MP_PLAN_WINO43;
-    case Kernel::wino43b: return MP_PLAN_WINO43B;
-    case Kernel::f16: return MP_PLAN_F16;
-    case Kernel::f16_res: return MP_PLAN_F16_RES;
-    default: return MP_PLAN_F16_RES_SLICES;
-    }
-}
-
-// the record of launch c of layer L over B images at H x W: what run_conv() hands to the launcher, and for the F(4x4,3x3) kernels
-// the item shape, item count and workgroups their launchers derive from it (w43_launch_tc4, w43_launch_items, persistent_grid)
-mp_plan_launch plan_record(const mp_handle* h, const ConvLayer& L, const ConvLaunch& c, int B, int H, int W)
-{
+    const ConvLaunch& c = e.c;
     mp_plan_launch r{};
-    r.name = c.fuse_first ? "enc.conv1+2" : L.name;
-    r.kernel = plan_kernel_code(c.kernel);
-    r.images = B; r.H = H; r.W = W;
-    r.pooled = L.pool ? 1 : 0;
+    r.name = launch_name(e);
+    r.kernel = e.layer ? (int)c.kernel : MP_PLAN_FIRST;
+    r.images = e.images; r.H = e.H; r.W = e.W;
+    r.pooled = (e.layer ? e.layer->pool : e.enc->first_pool) ? 1 : 0;
     r.ks_shift = c.ks_shift; r.vin = c.vin ? 1 : 0; r.fuse_first = c.fuse_first ? 1 : 0;
-    r.in_layout = c.in_planar; r.out_layout = c.out_planar;
+    r.in_layout = c.in_layout; r.out_layout = c.out_layout;
     if (c.kernel == Kernel::wino43 || c.kernel == Kernel::wino43b) {
-        ConvParams q{};
-        conv_geometry(h, L, q, (const float*)nullptr, L.cin, 0, (float*)nullptr, L.cout, 0, B, H, W);     // as run_conv() fills it
-        q.ks_shift = c.ks_shift;
-        ConvParams launch;
+        ConvParams q{}, launch;
+        conv_params(h, e, q);
         unsigned grid;
-        r.tc4 = w43_launch_tc4(H, W, c.fuse_first);
+        r.tc4 = w43_launch_tc4(e.H, e.W, c.fuse_first);
         if (w43_launch_shape(q, r.tc4, c.ks_shift > 0, launch, grid) == 0) { r.items = launch.nitems; r.workgroups = (int)grid; }
     }
     return r;
-}
-
-// every record of run_forward(h, ..., route, B, H, W, ...), in launch order
-std::vector<mp_plan_launch> forward_plan(const mp_handle* h, const ImageRoute& route, int B, int H, int W)
-{
-    std::vector<mp_plan_launch> out;
-    for (int e = 0; e < 2; ++e) {
-        const int nb = route.counts[e];
-        if (nb == 0) continue;
-        const Encoder& E = h->enc[e];
-        const EncoderPlan plan = plan_encoder(h, E, nb, B, H, W);
-        if (!plan.conv[0].fuse_first) {
-            mp_plan_launch r{};
-            r.name = "enc.conv1"; r.kernel = MP_PLAN_FIRST; r.images = nb; r.H = H; r.W = W; r.pooled = E.first_pool ? 1 : 0;
-            r.out_layout = h->cfg.mixed_precision ? MP_LAYOUT_NHWC : plan.conv[0].in_planar;
-            out.push_back(r);
-        }
-        for (int i = 0, hh = E.first_pool ? H / 2 : H, ww = E.first_pool ? W / 2 : W; i < E.nconv; ++i) {
-            out.push_back(plan_record(h, E.conv[i], plan.conv[i], nb, hh, ww));
-            if (E.conv[i].pool) { hh /= 2; ww /= 2; }
-        }
-    }
-    out.push_back(plan_record(h, h->heads3, plan_heads(h, B, H / 8, W / 8), B, H / 8, W / 8));
-    return out;
 }
 
 // ---- the batch-statistics forward (mp_forward_batch_stats): MultiPoint.forward in training mode, forward only -------------------
@@ -545,8 +564,8 @@ int bs_conv(mp_handle* h, const ConvLayer& L, const float* in, int in_cstride, i
             int W, hipStream_t s)
 {
     ConvParams p{};
-    const int mbw = conv_geometry(h, L, p, in, in_cstride, in_coff, out, out_cstride, 0, B, H, W);
-    p.wpack = L.wpack; p.bias = L.bias; p.scale = h->bn_ident; p.shift = h->bn_ident + 512;
+    const int mbw = conv_geometry(h, L, p, in_cstride, in_coff, out_cstride, 0, B, H, W);
+    p.in = in; p.out = out; p.wpack = L.wpack; p.bias = L.bias; p.scale = h->bn_ident; p.shift = h->bn_ident + 512;
     p.relu = L.taps == 9 && !h->cfg.bn_first;
     p.persist = h->dbg.persist;
     prof_begin(h, L.name, 2.0 * L.taps * L.cin * L.cout * (double)B * H * W, s);
@@ -703,12 +722,10 @@ int mp_forward_plan(mp_handle* h, int B, int H, int W, int n_optical, mp_plan_la
     if (B <= 0 || H <= 0 || W <= 0 || (H % 8) != 0 || (W % 8) != 0)
         return fail(h, MP_EINVAL, "mp_forward_plan: B, H and W must be positive, H and W divisible by 8");
     if (n_optical < 0 || n_optical > B) return fail(h, MP_EINVAL, "mp_forward_plan: n_optical must lie in 0..B");
-    ImageRoute route;
-    route.counts[0] = h->cfg.multispectral ? B - n_optical : B;
-    route.counts[1] = h->cfg.multispectral ? n_optical : 0;
-    const std::vector<mp_plan_launch> plan = forward_plan(h, route, B, H, W);
-    *n = (int)plan.size();
-    for (int i = 0; i < *n && i < capacity; ++i) out[i] = plan[i];
+    const int counts[2] = {h->cfg.multispectral ? B - n_optical : B, h->cfg.multispectral ? n_optical : 0};
+    const ForwardPlan plan = plan_forward(h, counts, B, H, W);
+    *n = plan.n;
+    for (int i = 0; i < plan.n && i < capacity; ++i) out[i] = plan_record(h, plan.launch[i]);
     return MP_OK;
 }
 
