@@ -1230,6 +1230,63 @@ int mp_residual_field(mp_handle* h, const float* optical_feat, const float* ther
                       int B, int H, int W, int window, int stride, int radius, double min_valid, double var_floor, double* out_d,
                       int* out_i, void* stream);
 
+/* ---- Local alignment correction: fit and apply a smooth displacement field ----
+ * mp_field_fit: d float64 [B][gy][gx][2] = (dy, dx), the displacements measured at the nodes of a gy x gx lattice (sides 1..256), and
+ * weight float64 [B][gy][gx].  Per frame and axis the fit minimises sum_k w_k (u_k - d_k)^2 + lambda sum_(k,l) (u_k - u_l)^2 over the
+ * edges of the 4-neighbour lattice: (W + lambda L) u = W d, L the lattice's graph Laplacian.  A node counts with weight 0, and its d
+ * is never read (it may be NaN), unless its weight is positive and finite; a node with such a weight and a non-finite d counts with
+ * weight 0 as well and is counted in out_info.  No node left: u = 0, status MP_FIELD_NO_DATA.
+ * Solver: conjugate gradients preconditioned by the diagonal, float64, both axes at once as two right-hand sides, each with its own
+ * step lengths; an axis stops at r^T r <= tol^2 b^T b (b = W d, r the recurrence's residual), the solve after max_iter iterations at
+ * the latest (or when p^T A p of a running axis is not positive).  Status MP_FIELD_MAX_ITER says that the last solve ended without
+ * MEETING that rule: at max_iter, at such a breakdown, or because r^T r or b^T b is not finite -- weights so large that w d or its
+ * square overflows give no solution, and this status instead of a wrong MP_FIELD_OK.
+ * Robust rounds (robust_px > 0 and rounds > 0): after solve t < rounds, e_k = |u_k - d_k| (Euclidean over both axes) and
+ * w_k = w0_k (1 - (e_k / robust_px)^2)^2 for e_k < robust_px, else 0, from the INPUT weight w0; then the system is solved again,
+ * started at the previous solution.  The first solve starts at u = 0.  If a round leaves no weight, the previous solution and
+ * its weights stay, with status MP_FIELD_ALL_REJECTED.
+ *   workspace   device memory of mp_field_fit_workspace's size (that entry touches no device), 16-byte aligned
+ *   out_u       float64 [B][gy][gx][2]
+ *   out_info    int32 [B][MP_FIELD_INFO_INTS]: status, iterations of the last solve, nodes with a non-zero weight in the system of
+ *               the returned solution, nodes with a usable weight and a non-finite d
+ *   out_res     float64 [B]: sqrt(r^T r / b^T b) at the end of the last solve, the larger of the two axes (0 for an axis with b = 0)
+ *   out_w       float64 [B][gy][gx] or NULL: the weights of the system of the returned solution
+ * One workgroup per frame, every sum in a fixed order: a frame's bits depend on its own lattice and the parameters alone.
+ * out_u is the solver's working vector, written before d is read for the last time: no output and not the workspace may be the
+ * buffer of d or weight, and out_u, out_w and the workspace are three different buffers.
+ * MP_EINVAL, before any launch and with the outputs untouched: a NULL tensor, B outside [1, 65535], a lattice side outside [1, 256],
+ * lambda not positive or not finite, robust_px or tol negative or not finite, rounds outside [0, 16], max_iter outside [1, 2^20], a
+ * workspace that is too small or not 16-byte aligned, buffers that are one where the line above wants two.
+ *
+ * mp_field_warp: dst fp32 [B][H][W] (and valid uint8 [B][H][W], or NULL) sampled from src fp32 [n_src][Hs][Ws] (n_src 1: every frame
+ * reads the same source, or B) through the field u float64 [B][gy][gx][2] (16-byte aligned: a node is read as one double2) whose
+ * node (0, 0) has its centre at pixel (y0, x0) and whose nodes are `step` pixels apart.  Per output pixel (y, x), in float64 with no contraction:
+ *   ty = (y - y0) / step, i = clamp(floor(ty), 0, max(gy - 2, 0)), fy = ty - i, clamped to [0, 1] with extrapolate = 0 (1: linear
+ *   continuation of the border cells); gy = 1: row 0 and fy = 0; likewise j, fx in x.
+ *   u(p) = (u[i][j] (1 - fx) + u[i][j+1] fx) (1 - fy) + (u[i+1][j] (1 - fx) + u[i+1][j+1] fx) fy per component
+ *   q = (y + u_y, x + u_x); with hom (float64 [B][9], row-major on (x, y, 1), or NULL): (X, Y, Z) = hom (q_x, q_y, 1) with each
+ *   row as (a q_x + b q_y) + c, and q = (Y / Z, X / Z)
+ *   the pixel is invalid (dst 0, valid 0) when Z <= 0, when any of these values is not finite, or when |q_y| or |q_x| > 2^30
+ *   else the bilinear sample of src at q: integer parts by floor, the fractions rounded to fp32, taps outside the source read 0,
+ *   dst = (s00 (1 - fx) + s01 fx) (1 - fy) + (s10 (1 - fx) + s11 fx) fy in fp32, and valid = 1 iff every tap whose two weight
+ *   factors are both non-zero lies inside the source
+ * So u = 0 without hom on a source of dst's size returns the source (for a finite source without negative zeros: its bits) and
+ * a mask of ones.
+ * MP_EINVAL, before any launch: a NULL src, u or dst, src == dst, a u that is not 16-byte aligned, B outside [1, 65535], n_src other than 1 or B, a frame outside
+ * 8 x 8 .. 4096 x 4096, a lattice side outside [1, 256], a non-finite origin, a step that is not positive and finite, extrapolate
+ * other than 0 or 1. */
+#define MP_FIELD_OK 0
+#define MP_FIELD_NO_DATA 1
+#define MP_FIELD_ALL_REJECTED 2
+#define MP_FIELD_MAX_ITER 3
+#define MP_FIELD_INFO_INTS 4
+int mp_field_fit_workspace(int B, int gy, int gx, long long* bytes);
+int mp_field_fit(mp_handle* h, const double* d, const double* weight, int B, int gy, int gx, double lambda, double robust_px, int rounds,
+                 double tol, int max_iter, void* workspace, long long workspace_bytes, double* out_u, int* out_info, double* out_res,
+                 double* out_w, void* stream);
+int mp_field_warp(mp_handle* h, const float* src, int n_src, int Hs, int Ws, const double* u, int gy, int gx, double y0, double x0,
+                  double step, int extrapolate, const double* hom, int B, int H, int W, float* dst, unsigned char* valid, void* stream);
+
 /* per-launch timing of mp_forward with hipEvents on the caller's stream (bench.py roofline leg).
  * mp_profile_read synchronises; names[i] points to static strings. */
 int mp_profile_enable(mp_handle* h, int enable);

@@ -283,6 +283,11 @@ SIGNATURES = {
     'mp_residual_grid': (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     'mp_residual_field': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                   ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p]),
+    'mp_field_fit_workspace': (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
+    'mp_field_fit': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_int,
+                             ctypes.c_double, c_int, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'mp_field_warp': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double,
+                              ctypes.c_double, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'mp_profile_enable': (c_int, [c_void_p, c_int]),
     'mp_profile_read': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_float),
                                 ctypes.POINTER(ctypes.c_double), c_int, ctypes.POINTER(c_int)]),

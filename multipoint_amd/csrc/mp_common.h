@@ -716,6 +716,44 @@ size_t residual_lds_bytes(int w, int r);
 void launch_residual_field(const ResidualParams& p, int B, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// Local alignment correction (field.hip): a smooth displacement field fitted to a lattice of measured
+// displacements, and frames sampled through such a field.
+// ---------------------------------------------------------------------------------------------
+// status of a fitted frame (include/multipoint_hip.h repeats them for the callers)
+#define MP_FIELD_OK 0                     // the last solve met its stopping rule
+#define MP_FIELD_NO_DATA 1                // no node has a positive weight: u = 0
+#define MP_FIELD_ALL_REJECTED 2           // a robust round left no weight: the solution before it is kept
+#define MP_FIELD_MAX_ITER 3               // the last solve ended at max_iter
+#define MP_FIELD_MAX_SIDE 256
+#define MP_FIELD_MAX_ROUNDS 16
+#define MP_FIELD_INFO_INTS 4              // status, iterations of the last solve, nodes with a non-zero final weight, non-finite d
+#define MP_FIELD_WS_DOUBLES 7             // per node of the workspace: the weight, and r, p, A p of both axes
+struct FieldFitParams {
+    const double* d;                      // [B][gy][gx][2]
+    const double* weight;                 // [B][gy][gx]
+    double* ws;                           // [B][MP_FIELD_WS_DOUBLES gy gx]
+    double* out_u;                        // [B][gy][gx][2]
+    int* out_info;                        // [B][MP_FIELD_INFO_INTS]
+    double* out_res;                      // [B]: the last solve's final relative residual, the larger of the two axes
+    double* out_w;                        // [B][gy][gx] the final weights, or NULL
+    int gy, gx, rounds, max_iter, p_in_lds;
+    double lambda, robust_px, tol;
+};
+size_t field_fit_lds_bytes(int nodes);    // 0: the search direction does not fit and stays in the workspace
+hipError_t launch_field_fit(const FieldFitParams& p, int B, hipStream_t s);   // an error: the LDS attribute was refused, nothing launched
+
+struct FieldWarpParams {
+    const float* src;                     // [n_src][Hs][Ws]
+    const double* u;                      // [B][gy][gx][2]
+    const double* hom;                    // [B][9] or NULL
+    float* dst;                           // [B][H][W]
+    unsigned char* valid;                 // [B][H][W] or NULL
+    int n_src, Hs, Ws, H, W, gy, gx, extrapolate;
+    double y0, x0, step;
+};
+void launch_field_warp(const FieldWarpParams& p, int B, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // Frame preparation (frames.hip; reference create_dataset/extract_images.py:167-242).
 // ---------------------------------------------------------------------------------------------
 struct FramesCamera {

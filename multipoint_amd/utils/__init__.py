@@ -8,3 +8,4 @@ from .drawing import *  # noqa: F401,F403  (results as pictures: keypoint, match
 from .registration import *  # noqa: F401,F403  (keypoint-free initial transform: Fourier-Mellin phase correlation)
 from .ecc import *  # noqa: F401,F403  (ECC direct alignment on gradient images)
 from .residual import *  # noqa: F401,F403  (local residual field: windowed correlation to pre-screen aligned pairs)
+from .field import *  # noqa: F401,F403  (local alignment correction: fit and apply a smooth displacement field)
