@@ -1292,6 +1292,52 @@ int mp_field_warp(mp_handle* h, const float* src, int n_src, int Hs, int Ws, con
 int mp_profile_enable(mp_handle* h, int enable);
 int mp_profile_read(mp_handle* h, const char** names, float* ms, double* flop, int capacity, int* n);
 
+/* ---- RIFT baseline (Li, Hu, Ai, IEEE TIP 2020; DESIGN.md 3.26: restated from the paper, not verified against the authors' code) ----
+ * u8 [B][H][W] is the quantised frame (mp_lghd_quantize), bank fp32 [24][H][W] the log-Gabor bank of mp_lghd_orientation (4
+ * scales x 6 orientations, scale-major), H and W lengths of the FFT.
+ *
+ * mp_phase_congruency.  R[s][o] = ifft2(fft2(u8) * bank[6 s + o]) / (H W), E = Re R, O = Im R, A = |R|, all in fp32; eps = 1e-4.
+ * Per orientation o (theta = o pi / 6), sums over the four scales in ascending s:
+ *   sumE, sumO, sumA, maxA;  X = sqrt(sumE^2 + sumO^2) + eps, mE = sumE / X, mO = sumO / X
+ *   En = sum_s (E_s mE + O_s mO - |E_s mO - O_s mE|)
+ *   En = max(En - T[b][o], 0), width = (sumA / (maxA + eps) - 1) / 3, weight = 1 / (1 + exp((cutoff - width) g))
+ *   PC = weight En / (sumA + eps),  cx = PC cos theta, cy = PC sin theta
+ * and over the orientations in ascending o: cx2 = sum cx^2 / 3, cy2 = sum cy^2 / 3, cxy = (sum cx cy) 4 / 6,
+ *   d = sqrt(cxy^2 + (cx2 - cy2)^2) + eps,  M = (cy2 + cx2 + d) / 2,  m = (cy2 + cx2 - d) / 2
+ *   mim = the first o with the largest sumA
+ * T fp32 [B][6]: with the median of the H W values of A[0][o] (exact order statistics of the fp32 plane, the mean of the two
+ * middle ones for an even count), in float64 with every operation rounded on its own and the result rounded once to fp32:
+ *   tau = median / sqrt(ln 4), tot = tau (1 - q q q q) / (1 - q) with q = 1 / 1.6, T = tot sqrt(pi / 2) + (k tot) sqrt((4 - pi) / 2)
+ * M, m fp32 [B][H][W], mim u8 [B][H][W]; amp fp32 [B][6][H][W] or NULL: the planes A[0][o] the medians were taken from.
+ * Every sum runs in a fixed order without atomics: the maps of an image have the same bits in any batch and with any workspace.
+ * The workspace holds the spectrum, the 24 half-transformed planes and the six amplitude planes of as many images as fit (at
+ * least one; 224 H W bytes each): mp_rift_workspace_bytes sizes it for min(B, 4).
+ * MP_EINVAL: H or W outside the FFT's lengths, B outside [1, 65535], k negative or not finite, g or cutoff not finite, a
+ * workspace smaller than one image needs.
+ *
+ * mp_rift_detect.  range fp32 [B][2] = (min, max) of M[b]; u8m u8 [B][H][W] = (uint8) floor(255 ((M - min) / (max - min))), the
+ * subtraction, the correctly rounded division and the multiplication each rounded to fp32, all 0 where max == min; then
+ * mp_lghd_detect's FAST on u8m with `fast_threshold` in place of 10: score and corners as there, prob fp32 [B][H][W] or NULL
+ * = score / 255 at corners with patch_size / 2 <= y <= H - patch_size / 2 and likewise in x, 0 elsewhere (everywhere on a frame
+ * smaller than the patch).
+ * MP_EINVAL: fast_threshold outside [1, 255], patch_size not a positive multiple of 12 or above MP_RIFT_MAX_PATCH.
+ *
+ * mp_rift_describe.  Rows [y - p/2, y + p/2) x columns [x - p/2, x + p/2) of mim, p = patch_size, in 6 x 6 cells of p / 6 pixels
+ * with 6 bins, laid out [cell row][cell col][bin]: raw fp32 [B][K][256] holds the 216 exact counts, unit the same rows
+ * L2-normalised (the sum of squares is an exact integer below 2^24 up to MP_RIFT_MAX_PATCH); columns 216..255 are 0; either may
+ * be NULL.  kp_yx int32 [B][K][2], kp_count int32 [B].  Rows beyond kp_count, and keypoints whose patch leaves the frame, are zero.
+ * MP_EINVAL: patch_size as above, or larger than H or W. */
+#define MP_RIFT_MAX_PATCH 156
+#define MP_RIFT_DESCRIPTOR_SIZE 256
+int mp_rift_workspace_bytes(int B, int H, int W, long long* bytes);
+int mp_phase_congruency(mp_handle* h, const unsigned char* u8, const float* bank, int B, int H, int W, float k, float g, float cutoff,
+                        float* M, float* m, unsigned char* mim, float* T, float* amp, void* workspace, long long workspace_bytes,
+                        void* stream);
+int mp_rift_detect(mp_handle* h, const float* M, int B, int H, int W, int fast_threshold, int patch_size, unsigned char* u8m,
+                   float* range, unsigned char* score, unsigned char* corners, float* prob, void* stream);
+int mp_rift_describe(mp_handle* h, const unsigned char* mim, int B, int H, int W, int patch_size, const int* kp_yx,
+                     const int* kp_count, int K, float* raw, float* unit, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -240,6 +240,13 @@ SIGNATURES = {
     'mp_lghd_orientation': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_ll, c_void_p]),
     'mp_lghd_describe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                  c_void_p]),
+    'mp_rift_workspace_bytes': (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
+    'mp_phase_congruency': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
+    'mp_rift_detect': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p]),
+    'mp_rift_describe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                 c_void_p]),
     'mp_sift_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
     'mp_sift_layout': (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
     'mp_sift_scale_space': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_ll, c_void_p]),

@@ -16,7 +16,7 @@ OBJ_DIR = os.path.join(CSRC, '_build')
 LIB_PATH = os.path.join(HERE, 'libmultipoint_hip.so')
 SOURCES = ['conv_mfma.hip', 'conv_wino43.hip', 'conv_wino43b.hip', 'conv_split.hip', 'conv_f16.hip', 'conv_f16_res.hip', 'conv_first.hip', 'heads_post.hip', 'head_tail.hip', 'head_tail_f16.hip', 'nms.hip', 'keypoints.hip', 'keypoints_subpixel.hip', 'keypoints_spread.hip',
            'sample_desc.hip', 'match_mfma.hip', 'match_guided.hip', 'match_extra.hip', 'pair_metrics.hip', 'detector_metrics.hip', 'homography.hip', 'homography_f.hip', 'homography_pooled.hip', 'transform.hip', 'transform_f.hip', 'transform_pooled.hip', 'homog_adapt.hip', 'losses.hip', 'batchnorm_stats.hip', 'photometric.hip', 'shapes.hip', 'api.hip',
-           'model_load.hip', 'forward.hip', 'post_api.hip', 'estimate_api.hip', 'mutual_info.hip', 'align_api.hip', 'pyramid.hip', 'fft.hip', 'lghd.hip', 'lghd_api.hip', 'sift.hip', 'sift_api.hip', 'frames.hip',
+           'model_load.hip', 'forward.hip', 'post_api.hip', 'estimate_api.hip', 'mutual_info.hip', 'align_api.hip', 'pyramid.hip', 'fft.hip', 'lghd.hip', 'lghd_api.hip', 'rift.hip', 'rift_api.hip', 'sift.hip', 'sift_api.hip', 'frames.hip',
            'frames_api.hip', 'draw.hip', 'register.hip', 'register_api.hip', 'ecc.hip', 'ecc_api.hip', 'ecc_pooled.hip', 'ecc_pooled_api.hip',
            'residual.hip', 'residual_api.hip', 'field.hip', 'field_api.hip']
 HEADERS = [os.path.join(CSRC, h) for h in ('mp_common.h', 'mp_device.h', 'mp_tile.h', 'mp_wino43.h', 'mp_head.h', 'mp_f16.h', 'mp_match.h', 'mp_select.h', 'mp_fft.h', 'mp_raster.h', 'mp_ransac.h', 'mp_homography.h', 'mp_transform.h', 'mp_ecc.h', 'mp_f16_store_pooled.inc',
@@ -86,7 +86,7 @@ def check_dma_hazards(asm_path, wait_states=5):
 #                      32-wide ones every benchmark shape runs have none since round 6
 SCRATCH_CAPS = {'conv_mfma.hip': 0, 'conv_wino43.hip': 0, 'conv_wino43b.hip': 136, 'conv_split.hip': 0, 'conv_f16.hip': 12,
                 'conv_f16_res.hip': 0, 'conv_first.hip': 0, 'head_tail.hip': 0, 'head_tail_f16.hip': 0, 'losses.hip': 0,
-                'batchnorm_stats.hip': 0, 'photometric.hip': 0, 'shapes.hip': 0, 'match_mfma.hip': 0, 'match_guided.hip': 0, 'mutual_info.hip': 0, 'pyramid.hip': 0, 'fft.hip': 0, 'lghd.hip': 0, 'sift.hip': 0,
+                'batchnorm_stats.hip': 0, 'photometric.hip': 0, 'shapes.hip': 0, 'match_mfma.hip': 0, 'match_guided.hip': 0, 'mutual_info.hip': 0, 'pyramid.hip': 0, 'fft.hip': 0, 'lghd.hip': 0, 'rift.hip': 0, 'sift.hip': 0,
                 'frames.hip': 0, 'draw.hip': 0, 'register.hip': 0, 'ecc.hip': 0, 'ecc_pooled.hip': 0, 'residual.hip': 0,
                 'keypoints_spread.hip': 0, 'field.hip': 0}
 

@@ -225,4 +225,7 @@ inline int launch_status(mp_handle* h)
     return MP_OK;
 }
 
+// the FFT's twiddle table of length n on the device, cached in the handle (lghd_api.hip)
+int fft_twiddle_table(mp_handle* h, int n, const float** table);
+
 }  // namespace mp_host

@@ -1,6 +1,7 @@
 // LGHD baseline (reference multipoint/models/ClassicDetectors.py, class LGHD): image quantisation, the FAST-9/16
 // detector and the patch-histogram descriptor.  The log-Gabor orientation maps come from fft.hip.  Integer arithmetic throughout:
-// every output here is bit-exact.
+// every output here is bit-exact.  The FAST kernels and the patch histogram take the threshold, the validity border and the patch
+// geometry as arguments: rift.hip runs the same bodies on its own maps.
 #include "mp_common.h"
 
 namespace {
@@ -18,7 +19,7 @@ __global__ __launch_bounds__(256) void quantize_kernel(const float* __restrict__
 
 // score(p) = the largest t for which 9 contiguous circle pixels are all > p + t or all < p - t; 0 below the threshold and
 // outside 3 <= y <= H - 4, 3 <= x <= W - 4
-__global__ __launch_bounds__(256) void fast_score_kernel(const unsigned char* __restrict__ u8, int H, int W,
+__global__ __launch_bounds__(256) void fast_score_kernel(const unsigned char* __restrict__ u8, int H, int W, int threshold,
                                                         unsigned char* __restrict__ score)
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -41,13 +42,14 @@ __global__ __launch_bounds__(256) void fast_score_kernel(const unsigned char* __
             for (int k = 1; k < 9; ++k) { mn = min(mn, d[(s + k) & 15]); mx = max(mx, d[(s + k) & 15]); }
             best = max(best, max(mn - 1, -mx - 1));
         }
-        sc = best >= FAST_THRESHOLD ? best : 0;
+        sc = best >= threshold ? best : 0;
     }
     score[plane + (long long)y * W + x] = (unsigned char)sc;
 }
 
-// corner: score strictly above all 8 neighbours; prob = 1 at corners whose 40 x 40 patch lies inside the frame
-__global__ __launch_bounds__(256) void fast_nms_kernel(const unsigned char* __restrict__ score, int H, int W,
+// corner: score strictly above all 8 neighbours; prob = 1 (scored: score / 255) at corners whose patch of 2 half x 2 half lies
+// inside the frame
+__global__ __launch_bounds__(256) void fast_nms_kernel(const unsigned char* __restrict__ score, int H, int W, int half, int scored,
                                                       unsigned char* __restrict__ corners, float* __restrict__ prob)
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -63,46 +65,53 @@ __global__ __launch_bounds__(256) void fast_nms_kernel(const unsigned char* __re
             }
     }
     corners[at] = keep ? 1 : 0;
-    if (prob) prob[at] = (keep && y >= LGHD_HALF && y <= H - LGHD_HALF && x >= LGHD_HALF && x <= W - LGHD_HALF) ? 1.f : 0.f;
+    if (prob) prob[at] = (keep && y >= half && y <= H - half && x >= half && x <= W - half) ? (scored ? __fdiv_rn((float)s, 255.f) : 1.f) : 0.f;
 }
 
-// one workgroup per keypoint slot: 4 scales x 40 x 40 orientation indices -> 384 counts in LDS
-__global__ __launch_bounds__(256) void lghd_describe_kernel(const unsigned char* __restrict__ ori, int H, int W,
-                                                           const int* __restrict__ kp_yx, const int* __restrict__ kp_count, int K,
-                                                           float* __restrict__ raw, float* __restrict__ unit)
+// one workgroup per keypoint slot: the patch of S planes of orientation indices in G x G cells of cell x cell pixels -> S G G 6
+// counts in LDS (LGHD: 4 scales x 40 x 40 -> 384; RIFT: the one maximum index map, 6 x 6 cells -> 216).  CELL = 0: the cell edge
+// is the argument.  Rows are `width` floats apart and zero behind the counts.
+template <int S, int G, int CELL>
+__global__ __launch_bounds__(256) void patch_describe_kernel(const unsigned char* __restrict__ ori, int H, int W, int cell_arg,
+                                                            int width, const int* __restrict__ kp_yx,
+                                                            const int* __restrict__ kp_count, int K, float* __restrict__ raw,
+                                                            float* __restrict__ unit)
 {
-    __shared__ int hist[LGHD_D];
+    constexpr int D = S * G * G * 6;
+    const int cell = CELL ? CELL : cell_arg, P = G * cell, half = P / 2;
+    __shared__ int hist[D];
     __shared__ int wsum[4];
     const int k = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const long long row = ((long long)b * K + k) * LGHD_D;
+    const long long row = ((long long)b * K + k) * width;
+    for (int i = D + tid; i < width; i += 256) { if (raw) raw[row + i] = 0.f; if (unit) unit[row + i] = 0.f; }
     const int cnt = min(kp_count[b], K);
     int y = 0, x = 0;
     bool live = k < cnt;
     if (live) {
         y = kp_yx[((long long)b * K + k) * 2]; x = kp_yx[((long long)b * K + k) * 2 + 1];
-        live = y >= LGHD_HALF && y <= H - LGHD_HALF && x >= LGHD_HALF && x <= W - LGHD_HALF;     // a patch outside the frame: zeros
+        live = y >= half && y <= H - half && x >= half && x <= W - half;     // a patch outside the frame: zeros
     }
     if (!live) {                // (uniform over the workgroup)
-        for (int i = tid; i < LGHD_D; i += 256) { if (raw) raw[row + i] = 0.f; if (unit) unit[row + i] = 0.f; }
+        for (int i = tid; i < D; i += 256) { if (raw) raw[row + i] = 0.f; if (unit) unit[row + i] = 0.f; }
         return;
     }
-    for (int i = tid; i < LGHD_D; i += 256) hist[i] = 0;
+    for (int i = tid; i < D; i += 256) hist[i] = 0;
     __syncthreads();
-    const unsigned char* base = ori + (long long)b * 4 * H * W;
-    for (int i = tid; i < 4 * 40 * 40; i += 256) {
-        const int s = i / 1600, r = i - s * 1600, py = r / 40, px = r - py * 40;
-        const int o = base[((long long)s * H + (y - LGHD_HALF + py)) * W + (x - LGHD_HALF + px)];
-        if (o < 6) atomicAdd(&hist[((s * 4 + py / 10) * 4 + px / 10) * 6 + o], 1);
+    const unsigned char* base = ori + (long long)b * S * H * W;
+    for (int i = tid; i < S * P * P; i += 256) {
+        const int s = i / (P * P), r = i - s * (P * P), py = r / P, px = r - py * P;
+        const int o = base[((long long)s * H + (y - half + py)) * W + (x - half + px)];
+        if (o < 6) atomicAdd(&hist[((s * G + py / cell) * G + px / cell) * 6 + o], 1);
     }
     __syncthreads();
     int ss = 0;
-    for (int i = tid; i < LGHD_D; i += 256) ss += hist[i] * hist[i];
+    for (int i = tid; i < D; i += 256) ss += hist[i] * hist[i];
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) ss += __shfl_xor(ss, off);
     if ((tid & 63) == 0) wsum[tid >> 6] = ss;
     __syncthreads();
     const float norm = sqrtf((float)(wsum[0] + wsum[1] + wsum[2] + wsum[3]));      // the sum of squares is an exact integer < 2^24
-    for (int i = tid; i < LGHD_D; i += 256) {
+    for (int i = tid; i < D; i += 256) {
         const float v = (float)hist[i];
         if (raw) raw[row + i] = v;
         if (unit) unit[row + i] = v / norm;
@@ -117,16 +126,30 @@ void launch_lghd_quantize(const float* image, unsigned char* u8, long long n, hi
     hipLaunchKernelGGL(quantize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, image, u8, n);
 }
 
+void launch_fast_detect(const unsigned char* u8, int B, int H, int W, int threshold, int half, int scored, unsigned char* score,
+                        unsigned char* corners, float* prob, hipStream_t s)
+{
+    const dim3 g((W + 63) / 64, (H + 3) / 4, B);
+    hipLaunchKernelGGL(fast_score_kernel, g, dim3(256), 0, s, u8, H, W, threshold, score);
+    hipLaunchKernelGGL(fast_nms_kernel, g, dim3(256), 0, s, score, H, W, half, scored, corners, prob);
+}
+
 void launch_lghd_detect(const unsigned char* u8, int B, int H, int W, unsigned char* score, unsigned char* corners, float* prob,
                         hipStream_t s)
 {
-    const dim3 g((W + 63) / 64, (H + 3) / 4, B);
-    hipLaunchKernelGGL(fast_score_kernel, g, dim3(256), 0, s, u8, H, W, score);
-    hipLaunchKernelGGL(fast_nms_kernel, g, dim3(256), 0, s, score, H, W, corners, prob);
+    launch_fast_detect(u8, B, H, W, FAST_THRESHOLD, LGHD_HALF, 0, score, corners, prob, s);
 }
 
 void launch_lghd_describe(const unsigned char* ori, int B, int H, int W, const int* kp_yx, const int* kp_count, int K, float* raw,
                           float* unit, hipStream_t s)
 {
-    hipLaunchKernelGGL(lghd_describe_kernel, dim3(K, B), dim3(256), 0, s, ori, H, W, kp_yx, kp_count, K, raw, unit);
+    hipLaunchKernelGGL((patch_describe_kernel<4, 4, 10>), dim3(K, B), dim3(256), 0, s, ori, H, W, 10, LGHD_D, kp_yx, kp_count, K, raw,
+                       unit);
+}
+
+void launch_rift_describe(const unsigned char* mim, int B, int H, int W, int patch, const int* kp_yx, const int* kp_count, int K,
+                          float* raw, float* unit, hipStream_t s)
+{
+    hipLaunchKernelGGL((patch_describe_kernel<1, 6, 0>), dim3(K, B), dim3(256), 0, s, mim, H, W, patch / 6, 256, kp_yx, kp_count, K,
+                       raw, unit);
 }

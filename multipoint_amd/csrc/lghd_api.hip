@@ -5,10 +5,8 @@
 
 using namespace mp_host;
 
-namespace {
-
 // the device table of length n (built on first use: one synchronous upload per length and handle)
-int twiddles(mp_handle* h, int n, const float** table)
+int mp_host::fft_twiddle_table(mp_handle* h, int n, const float** table)
 {
     auto it = h->fft_tw.find(n);
     if (it == h->fft_tw.end()) {
@@ -23,6 +21,10 @@ int twiddles(mp_handle* h, int n, const float** table)
     *table = static_cast<const float*>(it->second.p);
     return MP_OK;
 }
+
+namespace {
+
+int twiddles(mp_handle* h, int n, const float** table) { return fft_twiddle_table(h, n, table); }
 
 bool frame_ok(int B, int H, int W) { return B > 0 && B <= 65535 && H > 0 && W > 0 && H <= 32767 && W <= 32767; }
 

@@ -604,6 +604,25 @@ void launch_lghd_describe(const unsigned char* ori, int B, int H, int W, const i
                           float* unit, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// The RIFT baseline (fft.hip, rift.hip, lghd.hip).
+// ---------------------------------------------------------------------------------------------
+// FAST-9/16 of lghd.hip with its threshold and validity border as arguments; scored: prob = score / 255 instead of 1
+void launch_fast_detect(const unsigned char* u8, int B, int H, int W, int threshold, int half, int scored, unsigned char* score,
+                        unsigned char* corners, float* prob, hipStream_t s);
+// M, m fp32 and mim u8 [nb][H][W], T fp32 [nb][6]; spectrum: nb complex frames, tmp: nb * 24 complex frames, amp: nb * 6 real frames
+void launch_rift_phase_congruency(const unsigned char* u8, const float* bank, int nb, int H, int W, float k, float g, float cutoff,
+                                  float* spectrum, float* tmp, float* amp, float* T, float* M, float* m, unsigned char* mim,
+                                  const float* tw_rows, const float* tw_cols, hipStream_t s);
+// T[p] from the exact median of amp[p][0 .. HW), p < planes
+void launch_rift_noise_threshold(const float* amp, int planes, long long HW, float k, float* T, hipStream_t s);
+// u8m [B][H][W] from M, range fp32 [B][2] = (min, max) of M, then FAST on u8m
+void launch_rift_detect(const float* M, int B, int H, int W, int threshold, int patch, unsigned char* u8m, float* range,
+                        unsigned char* score, unsigned char* corners, float* prob, hipStream_t s);
+// raw / unit fp32 [B][K][256]: 216 counts of the 6 x 6 cells of patch / 6 pixels, then zeros; either may be NULL
+void launch_rift_describe(const unsigned char* mim, int B, int H, int W, int patch, const int* kp_yx, const int* kp_count, int K,
+                          float* raw, float* unit, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // Fourier-Mellin registration (register.hip).  Complex planes are interleaved fp32, as the FFT takes them.
 // ---------------------------------------------------------------------------------------------
 #define MP_REGISTER_PEAK_CHUNK 16384      // plane values one workgroup of the peak search reduces

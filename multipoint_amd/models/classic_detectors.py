@@ -1,7 +1,9 @@
 """ClassicDetectors (reference multipoint/models/ClassicDetectors.py) for `method: LGHD`: FAST-9/16 keypoints and log-Gabor
 histogram descriptors, every stage a HIP kernel (csrc/lghd.hip, csrc/fft.hip), and -- opt-in through
 `implementation: restated` -- for `method: SIFT`: Lowe's detector and descriptor restated from the published algorithm
-(csrc/sift.hip).  PyTorch only holds the memory.
+(csrc/sift.hip).  `method: RIFT` (an extension; csrc/rift.hip, csrc/fft.hip) is Li, Hu and
+Ai's phase-congruency keypoints and maximum-index-map histograms, restated from the paper and not verified against the authors'
+code.  PyTorch only holds the memory.
 
 The reference runs one image at a time on the host and returns a dense [1,384,H,W] descriptor map with the raw counts
 scattered at the keypoints.  Here `forward` takes any batch and returns, besides `prob`, the `orientation` maps the
@@ -18,6 +20,8 @@ from ..utils.homographies import gaussian_filter
 
 DESCRIPTOR_SIZE = 384
 SIFT_DESCRIPTOR_SIZE = 128
+RIFT_DESCRIPTOR_SIZE = 256      # 216 counts (6 x 6 cells x 6 bins), zero-padded to a width the sampler and the matchers take
+RIFT_MAX_PATCH = 156            # 36 (patch / 6)^4 stays below 2^24: the sum of squares of a row is exact in fp32
 SIFT_NFEATURES = 1000           # the reference's cv2.xfeatures2d.SIFT_create(1000)
 
 
@@ -124,10 +128,72 @@ def describe(orientation, kp_yx, kp_count, raw=False):
     if K == 0:
         return out
     h = _lib.get_handle(dev)
+    # (named, so that a converted copy lives until the launch is queued: a temporary's block is free for the next one to take)
+    orientation, kp_yx, kp_count = orientation.contiguous(), kp_yx.to(dev, torch.int32).contiguous(), kp_count.to(dev, torch.int32).contiguous()
     with torch.cuda.device(dev):
-        h.check(h.lib.mp_lghd_describe(h.ptr, _lib.ptr(orientation.contiguous()), B, H, W,
-                                       _lib.ptr(kp_yx.to(dev, torch.int32).contiguous()),
-                                       _lib.ptr(kp_count.to(dev, torch.int32).contiguous()), K,
+        h.check(h.lib.mp_lghd_describe(h.ptr, _lib.ptr(orientation), B, H, W, _lib.ptr(kp_yx), _lib.ptr(kp_count), K,
+                                       _lib.ptr(out) if raw else None, None if raw else _lib.ptr(out), _lib.stream_ptr(dev)))
+    return out
+
+
+def phase_congruency(u8, bank, k=1.0, g=3.0, cutoff=0.5, want_amplitudes=False):
+    """u8 [B,H,W] uint8, bank float32 [24,H,W] -> (M float32 [B,H,W], m float32 [B,H,W], mim uint8 [B,H,W], T float32 [B,6]):
+    the maximum and minimum moments of phase congruency over the 6 orientations, the maximum index map (the first orientation
+    with the largest summed amplitude) and the noise thresholds (mp_phase_congruency).  want_amplitudes: a fifth
+    result, float32 [B,6,H,W], the scale-0 amplitude planes the thresholds' medians were taken from."""
+    dev = _lib.require_cuda(u8.device)
+    B, H, W = u8.shape
+    if not (fft_length_ok(H) and fft_length_ok(W)):
+        raise ValueError('RIFT: frame of %d x %d: both sizes must be 2^a 3^b 5^c in [8, 4096]' % (H, W))
+    nbytes = ctypes.c_longlong(0)
+    h = _lib.get_handle(dev)
+    h.check(h.lib.mp_rift_workspace_bytes(B, H, W, ctypes.byref(nbytes)))
+    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
+    M = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    m = torch.empty_like(M)
+    mim = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    T = torch.empty((B, 6), dtype=torch.float32, device=dev)
+    amp = torch.empty((B, 6, H, W), dtype=torch.float32, device=dev) if want_amplitudes else None
+    with torch.cuda.device(dev):
+        u8, bank = u8.contiguous(), bank.contiguous()
+        h.check(h.lib.mp_phase_congruency(h.ptr, _lib.ptr(u8), _lib.ptr(bank), B, H, W, float(k), float(g), float(cutoff),
+                                          _lib.ptr(M), _lib.ptr(m), _lib.ptr(mim), _lib.ptr(T), _lib.ptr(amp), _lib.ptr(ws),
+                                          nbytes.value, _lib.stream_ptr(dev)))
+    return (M, m, mim, T, amp) if want_amplitudes else (M, m, mim, T)
+
+
+def rift_detect(M, fast_threshold=13, patch_size=96, want_prob=True):
+    """M float32 [B,H,W] -> (u8m uint8 [B,H,W], score uint8, corners uint8, prob float32 [B,1,H,W] or None): M stretched to
+    0..255 per image, FAST-9/16 with `fast_threshold` and strict 3 x 3 non-maximum suppression on it; prob = score / 255 at the
+    corners whose patch lies inside the frame."""
+    dev = _lib.require_cuda(M.device)
+    B, H, W = M.shape
+    M = M.to(torch.float32).contiguous()
+    u8m = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    score, corners = torch.empty_like(u8m), torch.empty_like(u8m)
+    rng = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    prob = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev) if want_prob else None
+    h = _lib.get_handle(dev)
+    with torch.cuda.device(dev):
+        h.check(h.lib.mp_rift_detect(h.ptr, _lib.ptr(M), B, H, W, int(fast_threshold), int(patch_size), _lib.ptr(u8m), _lib.ptr(rng),
+                                     _lib.ptr(score), _lib.ptr(corners), _lib.ptr(prob), _lib.stream_ptr(dev)))
+    return u8m, score, corners, prob
+
+
+def rift_describe(mim, kp_yx, kp_count, patch_size=96, raw=False):
+    """mim uint8 [B,H,W], kp_yx int32 [B,K,2], kp_count int32 [B] -> float32 [B,K,256]: the L2-normalised histograms of the
+    patch's 6 x 6 cells (raw=True: the counts) in columns 0..215, zeros behind them.  Rows beyond kp_count[b] are zero."""
+    dev = _lib.require_cuda(mim.device)
+    B, H, W = mim.shape
+    K = kp_yx.shape[1]
+    out = torch.empty((B, K, RIFT_DESCRIPTOR_SIZE), dtype=torch.float32, device=dev)
+    if K == 0:
+        return out
+    h = _lib.get_handle(dev)
+    # (named, so that a converted copy lives until the launch is queued: a temporary's block is free for the next one to take)
+    mim, kp_yx, kp_count = mim.contiguous(), kp_yx.to(dev, torch.int32).contiguous(), kp_count.to(dev, torch.int32).contiguous()
+    with torch.cuda.device(dev):
+        h.check(h.lib.mp_rift_describe(h.ptr, _lib.ptr(mim), B, H, W, int(patch_size), _lib.ptr(kp_yx), _lib.ptr(kp_count), K,
                                        _lib.ptr(out) if raw else None, None if raw else _lib.ptr(out), _lib.stream_ptr(dev)))
     return out
 
@@ -306,12 +372,25 @@ class ClassicDetectors:
         implementation = given.pop('implementation', None)
         if implementation not in (None, 'restated'):
             raise ValueError("ClassicDetectors: implementation must be 'restated' or absent, got %r" % (implementation,))
+        # `patch_size`, `fast_threshold` (extensions of `method: RIFT`): taken out the same way
+        rift_keys = {key: given.pop(key) for key in ('patch_size', 'fast_threshold') if key in given}
         self.config = U.dict_update(dict(self.default_config), given)
         method = self.config['method']
+        if rift_keys and method != 'RIFT':
+            raise ValueError('ClassicDetectors: %s belong(s) to method RIFT, not %s' % (sorted(rift_keys), method))
+        self.patch_size, self.fast_threshold = rift_keys.get('patch_size', 96), rift_keys.get('fast_threshold', 13)
+        for name, v in (('patch_size', self.patch_size), ('fast_threshold', self.fast_threshold)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError('ClassicDetectors: %s must be an integer, got %r' % (name, v))
+        if self.patch_size <= 0 or self.patch_size % 12 or self.patch_size > RIFT_MAX_PATCH:
+            raise ValueError('ClassicDetectors: patch_size must be a positive multiple of 12, at most %d, got %d'
+                             % (RIFT_MAX_PATCH, self.patch_size))
+        if not 1 <= self.fast_threshold <= 255:
+            raise ValueError('ClassicDetectors: fast_threshold must lie in [1, 255], got %d' % self.fast_threshold)
         if method == 'SURF' or (method == 'SIFT' and implementation is None):
             raise NotImplementedError('ClassicDetectors: %s lives inside opencv-contrib and is not rebuilt here; LGHD is, and SIFT as '
                                       'a restatement of the published algorithm behind `implementation: restated`' % method)
-        if method not in ('LGHD', 'SIFT'):
+        if method not in ('LGHD', 'SIFT', 'RIFT'):
             raise ValueError('Unknown alignment method: ' + str(method))
         self.method = method
         if self.config['prob_smoothing'] and self.config['smoothing_kernel_size'] % 2 == 0:
@@ -372,14 +451,18 @@ class ClassicDetectors:
         if image.device != self.device:
             raise RuntimeError('input image is on %s but the model is on %s' % (image.device, self.device))
         B, _, H, W = image.shape
-        if self.method == 'LGHD' and not (fft_length_ok(H) and fft_length_ok(W)):
-            raise ValueError('LGHD: frame of %d x %d: both sizes must be 2^a 3^b 5^c in [8, 4096]' % (H, W))
+        if self.method in ('LGHD', 'RIFT') and not (fft_length_ok(H) and fft_length_ok(W)):
+            raise ValueError('%s: frame of %d x %d: both sizes must be 2^a 3^b 5^c in [8, 4096]' % (self.method, H, W))
+        if self.method == 'RIFT' and self.patch_size > min(H, W):
+            raise ValueError('RIFT: a frame of %d x %d holds no patch of %d' % (H, W, self.patch_size))
         for name, want, got in (('image_H', self._frame[0], H), ('image_W', self._frame[1], W)):
             if want is not None and int(want) != got:
                 raise ValueError('ClassicDetectors: the configuration says %s = %d, the frame has %d' % (name, int(want), got))
         u8 = quantize(image).reshape(B, H, W)
         if self.method == 'SIFT':
             return self._smooth(self._forward_sift(u8))
+        if self.method == 'RIFT':
+            return self._smooth(self._forward_rift(u8))
         _, _, prob = fast_detect(u8)
         orientation = orientation_maps(u8, self.filter_bank(H, W, self.device))
         out = {'prob': prob, 'orientation': orientation}
@@ -408,6 +491,27 @@ class ClassicDetectors:
             out['desc'] = sift_dense_map(desc, owner)
         return out
 
+    def _forward_rift(self, u8):
+        """phase congruency -> FAST on the maximum-moment map.  `prob` carries the FAST score, so the
+        pipeline's top-k is RIFT's "select strongest"."""
+        B, H, W = u8.shape
+        M, m, mim, _ = phase_congruency(u8, self.filter_bank(H, W, self.device))
+        _, _, _, prob = rift_detect(M, self.fast_threshold, self.patch_size)
+        out = {'prob': prob, 'mim': mim, 'pc_max': M, 'pc_min': m}
+        if B == 1:
+            # the dense map callers written against the reference's LGHD expect: raw counts at the keypoints
+            kp = torch.nonzero(prob[0, 0] > 0).to(torch.int32)
+            n = kp.shape[0]
+            if n:
+                raw = rift_describe(mim, kp.reshape(1, n, 2), torch.tensor([n], dtype=torch.int32, device=self.device),
+                                    self.patch_size, raw=True)
+                desc = torch.zeros((1, RIFT_DESCRIPTOR_SIZE, H, W), dtype=torch.float32, device=self.device)
+                desc[0, :, kp[:, 0].long(), kp[:, 1].long()] = raw[0].t()
+            else:
+                desc = torch.zeros((1, 1, H, W), dtype=torch.float32, device=self.device)
+            out['desc'] = desc
+        return out
+
     def _smooth(self, out):
         prob = out['prob']
         if self.config['prob_smoothing']:
@@ -430,4 +534,7 @@ class ClassicDetectors:
             # SIFT: the row of the keypoint that owns the pixel.  The reference's blend with (y-1, x), (y, x-1), (y-1, x-1) mixes
             # descriptors of DIFFERENT keypoints where one of those pixels holds one; that artefact is not reproduced
             return sift_owner_rows(out['sift_desc'], out['sift_owner'], kp_yx, kp_count)
+        if 'mim' in out:
+            # RIFT: [B,K,256] histograms of the maximum index map around each keypoint
+            return rift_describe(out['mim'], kp_yx, kp_count, self.patch_size)
         return describe(out['orientation'], kp_yx, kp_count)

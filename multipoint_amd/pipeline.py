@@ -205,8 +205,8 @@ class PairPipeline:
                 if t is not None:
                     t.record_stream(fwd)
             post.wait_stream(fwd)      # (a forward the caller enqueues next on ITS stream is ordered behind this one by the model itself)
-            for t in (out['prob'], out.get('desc'), out.get('orientation'), out.get('sift_keypoints'), out.get('sift_count'),
-                      out.get('sift_desc'), out.get('sift_owner'), valid_mask):
+            for t in (out['prob'], out.get('desc'), out.get('orientation'), out.get('mim'), out.get('sift_keypoints'),
+                      out.get('sift_count'), out.get('sift_desc'), out.get('sift_owner'), valid_mask):
                 if t is not None:
                     t.record_stream(post)
         else:
