@@ -19,7 +19,7 @@ SOURCES = ['conv_mfma.hip', 'conv_wino43.hip', 'conv_wino43b.hip', 'conv_split.h
            'model_load.hip', 'forward.hip', 'post_api.hip', 'estimate_api.hip', 'mutual_info.hip', 'align_api.hip', 'pyramid.hip', 'fft.hip', 'lghd.hip', 'lghd_api.hip', 'rift.hip', 'rift_api.hip', 'sift.hip', 'sift_api.hip', 'frames.hip',
            'frames_api.hip', 'draw.hip', 'register.hip', 'register_api.hip', 'ecc.hip', 'ecc_api.hip', 'ecc_pooled.hip', 'ecc_pooled_api.hip',
            'residual.hip', 'residual_api.hip', 'field.hip', 'field_api.hip']
-HEADERS = [os.path.join(CSRC, h) for h in ('mp_common.h', 'mp_device.h', 'mp_tile.h', 'mp_wino43.h', 'mp_head.h', 'mp_f16.h', 'mp_match.h', 'mp_select.h', 'mp_fft.h', 'mp_raster.h', 'mp_ransac.h', 'mp_homography.h', 'mp_transform.h', 'mp_ecc.h', 'mp_f16_store_pooled.inc',
+HEADERS = [os.path.join(CSRC, h) for h in ('mp_common.h', 'mp_device.h', 'mp_tile.h', 'mp_wino43.h', 'mp_head.h', 'mp_f16.h', 'mp_match.h', 'mp_select.h', 'mp_fft.h', 'mp_raster.h', 'mp_ransac.h', 'mp_homography.h', 'mp_transform.h', 'mp_ecc.h', 'mp_workspace.h', 'mp_f16_store_pooled.inc',
                                             'mp_f16_store_lines.inc', 'host.h')] + [
     os.path.join(HERE, '..', 'include', 'multipoint_hip.h')]
 # sources that include another source (the same kernels compiled for a second keypoint type)

@@ -15,51 +15,42 @@ static_assert(MI_PARAMS_MAX == MP_MI_PARAMS_MAX && MI_PARAMS_MAX + 1 <= MI_SLOTS
 
 namespace {
 
-size_t up(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// where the pieces of a call lie in its workspace (byte offsets)
-struct MiLayout {
-    size_t ev, slots, nact, M, keys, tkeys, tmap, warped, counts, smooth_a, smooth_b, part, rowsum, colpart, values, cand, candp,
-        state, opts, tinit, live, total;
-};
-
-MiLayout mi_layout(long long E, long long B, long long S, long long H, long long W, long long max_bins, bool smoothing)
+// the arrays of a call with E evaluations of B pairs, S thermal bin maps and histograms of at most max_bins bins per side
+MiWorkspace mi_workspace(void* base, long long E, long long B, long long S, long long H, long long W, long long max_bins,
+                         bool smoothing)
 {
-    MiLayout l{};
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += up(bytes); return o; };
-    const size_t hist = (size_t)(2 * max_bins * max_bins), P = (size_t)((E + MI_SLOTS - 1) / MI_SLOTS);
-    l.ev = take((size_t)E * sizeof(MiEval));
-    l.slots = take((size_t)S * sizeof(int2));
-    l.nact = take(P * 4);
-    l.M = take((size_t)E * 72);
-    l.keys = take((size_t)E * 8);
-    l.tkeys = take((size_t)B * 8);
-    l.tmap = take((size_t)S * H * W * 2);
-    l.warped = take((size_t)E * H * W * 4);
-    l.counts = take((size_t)E * hist * 4);
-    l.smooth_a = take(smoothing ? (size_t)E * hist * 8 : 0);
-    l.smooth_b = take(smoothing ? (size_t)E * hist * 8 : 0);
-    l.part = take((size_t)E * MI_PARTS * 8);
-    l.rowsum = take((size_t)E * 256 * 8);
-    l.colpart = take((size_t)E * MI_PARTS * 512 * 8);
-    l.values = take((size_t)E * 8);
-    l.cand = take((size_t)E * 72);
-    l.candp = take((size_t)E * MI_PARAMS_MAX * 8);
-    l.state = take(P * sizeof(MiNmState));
-    l.opts = take(P * sizeof(MiNmOptions));
-    l.tinit = take(P * 72);
-    l.live = take(4);
-    l.total = at;
-    return l;
+    const size_t hist = (size_t)(2 * max_bins * max_bins), P = (size_t)((E + MI_SLOTS - 1) / MI_SLOTS), px = (size_t)(H * W);
+    Carver c(base);
+    MiWorkspace w{};
+    w.ev = c.take<MiEval>(E);
+    w.slots = c.take<int2>(S);
+    w.nact = c.take<int>(P);
+    w.M = c.take<double>(E * 9);
+    w.keys = c.take<unsigned>(E * 2);
+    w.tkeys = c.take<unsigned>(B * 2);
+    w.tmap = c.take<unsigned short>(S * px);
+    w.warped = c.take<float>(E * px);
+    w.counts = c.take<unsigned>(E * hist);
+    w.smooth_a = c.take<double>(smoothing ? E * hist : 0);
+    w.smooth_b = c.take<double>(smoothing ? E * hist : 0);
+    w.part = c.take<double>(E * MI_PARTS);
+    w.rowsum = c.take<double>(E * 256);
+    w.colpart = c.take<double>((size_t)E * MI_PARTS * 512);
+    w.values = c.take<double>(E);
+    w.cand = c.take<double>(E * 9);
+    w.candp = c.take<double>(E * MI_PARAMS_MAX);
+    w.state = c.take<MiNmState>(P);
+    w.opts = c.take<MiNmOptions>(P);
+    w.tinit = c.take<double>(P * 9);
+    w.live = c.take<int>(1);
+    w.bytes = c.bytes();
+    return w;
 }
 
 struct MiCall {
-    MiLayout lay{};
+    MiWorkspace w{};
     MiLaunch L{};
-    char* ws = nullptr;
     long long stride = 0;          // counters per evaluation inside the workspace: 2 max_bins^2
-    template <typename T> T* at(size_t off) const { return reinterpret_cast<T*>(ws + off); }
 };
 
 // Checks the arguments the three entry points share, writes the evaluation list and the thermal bin maps into the workspace and
@@ -70,11 +61,11 @@ int mi_stage(mp_handle* h, const std::string& fn, const float* optical, int Ho, 
              hipStream_t s, MiCall& c)
 {
     if (!optical || !thermal || !pair || !bins || !workspace) return fail(h, MP_EINVAL, fn + ": NULL tensor");
-    if (B > 65535) return fail(h, MP_EINVAL, fn + ": at most 65535 pairs per call");
+    if (B > MAX_GRID_Y) return fail(h, MP_EINVAL, fn + ": at most 65535 pairs per call");
     if (B <= 0 || E <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return fail(h, MP_EINVAL, fn + ": sizes must be positive");
     if (H > 32767 || W > 32767 || Ho > 32767 || Wo > 32767 || (long long)H * W > 0x3fffffffLL || (long long)Ho * Wo > 0x3fffffffLL)
         return fail(h, MP_EINVAL, fn + ": frames of at most 32767 x 32767 and 2^30 pixels");
-    if (E > 65535) return fail(h, MP_EINVAL, fn + ": at most 65535 evaluations per call (" + std::to_string(MI_SLOTS) + " per problem)");
+    if (E > MAX_GRID_Y) return fail(h, MP_EINVAL, fn + ": at most 65535 evaluations per call (" + std::to_string(MI_SLOTS) + " per problem)");
     std::vector<MiEval> ev((size_t)E);
     std::vector<int2> slots;
     std::map<std::pair<int, int>, int> slot_of;
@@ -95,20 +86,15 @@ int mi_stage(mp_handle* h, const std::string& fn, const float* optical, int Ho, 
     }
     c.stride = 2LL * maxb * maxb;
     if (!packed) for (int e = 0; e < E; ++e) ev[e].off = e * c.stride;
-    c.lay = mi_layout(E, B, (long long)slots.size(), H, W, maxb, smoothing);
-    if (bytes < (long long)c.lay.total)
-        return fail(h, MP_EINVAL, fn + ": workspace of " + std::to_string(bytes) + " B, needs " + std::to_string(c.lay.total) +
-                                      " B (mp_mi_workspace_bytes)");
-    c.ws = static_cast<char*>(workspace);
+    const MiWorkspace w = c.w = mi_workspace(workspace, E, B, (long long)slots.size(), H, W, maxb, smoothing);
+    const int rc = need_workspace(h, fn, bytes, w.bytes, "mp_mi_workspace_bytes");
+    if (rc != MP_OK) return rc;
     MP_HIP(hipSetDevice(h->device));
-    MP_HIP(hipMemcpyAsync(c.ws + c.lay.ev, ev.data(), ev.size() * sizeof(MiEval), hipMemcpyHostToDevice, s));
-    MP_HIP(hipMemcpyAsync(c.ws + c.lay.slots, slots.data(), slots.size() * sizeof(int2), hipMemcpyHostToDevice, s));
-    launch_mi_thermal(thermal, B, H * W, c.at<int2>(c.lay.slots), (int)slots.size(), c.at<unsigned>(c.lay.tkeys),
-                      c.at<unsigned short>(c.lay.tmap), s);
+    MP_HIP(hipMemcpyAsync(w.ev, ev.data(), ev.size() * sizeof(MiEval), hipMemcpyHostToDevice, s));
+    MP_HIP(hipMemcpyAsync(w.slots, slots.data(), slots.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+    launch_mi_thermal(thermal, B, H * W, w.slots, (int)slots.size(), w.tkeys, w.tmap, s);
     MP_HIP(hipStreamSynchronize(s));
-    c.L = MiLaunch{optical, Ho, Wo, H, W, E, G, lds_bins, c.at<MiEval>(c.lay.ev), nullptr, nullptr, c.at<double>(c.lay.M),
-                   c.at<unsigned>(c.lay.keys), c.at<unsigned short>(c.lay.tmap), c.at<double>(c.lay.part),
-                   c.at<double>(c.lay.rowsum), c.at<double>(c.lay.colpart)};
+    c.L = MiLaunch{optical, Ho, Wo, H, W, E, G, lds_bins, w.ev, nullptr, nullptr, w.M, w.keys, w.tmap, w.part, w.rowsum, w.colpart};
     return MP_OK;
 }
 
@@ -122,9 +108,10 @@ int sigma_check(mp_handle* h, const std::string& fn, double sigma)
 // one objective launch of the running refinement followed by scipy's decision rules
 void refine_iteration(const MiRefine& r, int* live, hipStream_t s)
 {
-    launch_mi_histograms(r.L, r.counts, r.warped, nullptr, 0, s);
-    launch_mi_score(r.L, r.counts, r.sigma, r.normalized, r.reg_init, MI_SLOTS, r.smooth_stride, r.smooth_a, r.smooth_b, r.values, s);
-    launch_mi_nm_decide(r.state, r.model, r.P, r.candp, r.cand, r.values, r.nact, live, s);
+    const MiWorkspace& w = r.w;
+    launch_mi_histograms(r.L, w.counts, w.warped, nullptr, 0, s);
+    launch_mi_score(r.L, w.counts, r.sigma, r.normalized, r.reg_init, MI_SLOTS, r.smooth_stride, w.smooth_a, w.smooth_b, w.values, s);
+    launch_mi_nm_decide(w.state, r.model, r.P, w.candp, w.cand, w.values, w.nact, live, s);
 }
 
 // mp_mi_refine_begin and mp_mi_refine_begin_model: `start` device double [n_problems][n], the start parameters of `model`
@@ -138,8 +125,8 @@ int mi_refine_begin(mp_handle* h, const std::string& fn, const float* optical, i
         return fail(h, MP_EINVAL, fn + ": unknown model " + std::to_string(model) +
                                       " (MP_MODEL_HOMOGRAPHY, MP_MODEL_SIMILARITY or MP_MODEL_AFFINE)");
     if (!problems || !start) return fail(h, MP_EINVAL, fn + ": NULL tensor");
-    if (n_problems <= 0 || n_problems > 65535 / MI_SLOTS)
-        return fail(h, MP_EINVAL, fn + ": need 0 < n_problems <= " + std::to_string(65535 / MI_SLOTS));
+    if (n_problems <= 0 || n_problems > MAX_GRID_Y / MI_SLOTS)
+        return fail(h, MP_EINVAL, fn + ": need 0 < n_problems <= " + std::to_string(MAX_GRID_Y / MI_SLOTS));
     int rc = sigma_check(h, fn, sigma);
     if (rc != MP_OK) return rc;
     const int P = n_problems, E = P * MI_SLOTS;
@@ -159,22 +146,16 @@ int mi_refine_begin(mp_handle* h, const std::string& fn, const float* optical, i
     if (rc != MP_OK) return rc;
     MiRefine r;
     r.workspace = workspace;
+    const MiWorkspace& w = r.w = c.w;
     r.L = c.L;
     r.P = P; r.normalized = normalized != 0; r.model = model; r.sigma = sigma; r.smooth_stride = c.stride;
-    r.counts = c.at<unsigned>(c.lay.counts);
-    r.warped = c.at<float>(c.lay.warped);
-    r.smooth_a = c.at<double>(c.lay.smooth_a); r.smooth_b = c.at<double>(c.lay.smooth_b);
-    r.candp = c.at<double>(c.lay.candp); r.cand = c.at<double>(c.lay.cand); r.values = c.at<double>(c.lay.values);
-    r.state = c.at<MiNmState>(c.lay.state);
-    r.nact = c.at<int>(c.lay.nact);
-    r.L.T = r.cand;
-    r.L.nact = r.nact;
-    // the matrices of the problems' start parameters are kept in the workspace: the regulariser reads them at every evaluation
-    double* init = c.at<double>(c.lay.tinit);
-    MP_HIP(hipMemcpyAsync(c.ws + c.lay.opts, opts.data(), opts.size() * sizeof(MiNmOptions), hipMemcpyHostToDevice, s));
-    launch_mi_nm_begin(r.state, c.at<MiNmOptions>(c.lay.opts), model, start, P, r.candp, r.cand, init, r.nact, s);
+    r.L.T = w.cand;
+    r.L.nact = w.nact;
+    // the matrices of the problems' start parameters are kept in the workspace (tinit): the regulariser reads them at every evaluation
+    MP_HIP(hipMemcpyAsync(w.opts, opts.data(), opts.size() * sizeof(MiNmOptions), hipMemcpyHostToDevice, s));
+    launch_mi_nm_begin(w.state, w.opts, model, start, P, w.candp, w.cand, w.tinit, w.nact, s);
     MP_HIP(hipStreamSynchronize(s));
-    r.reg_init = regularize ? init : nullptr;
+    r.reg_init = regularize ? w.tinit : nullptr;
     h->mi = r;
     return launch_status(h);
 }
@@ -186,10 +167,10 @@ extern "C" {
 int mp_mi_workspace_bytes(int n_evals, int n_pairs, int n_thermal_maps, int H, int W, int max_bins, int smoothing,
                           long long* bytes)
 {
-    if (!bytes || n_evals <= 0 || n_evals > 65535 || n_pairs <= 0 || n_pairs > 65535 || n_thermal_maps <= 0 || H <= 0 || W <= 0 || H > 32767 ||
-        W > 32767 || (long long)H * W > 0x3fffffffLL || max_bins < 1 || max_bins > 256)
+    if (!bytes || !count_ok(n_evals) || !count_ok(n_pairs) || n_thermal_maps <= 0 || !sides_ok(H, W, 1, 32767) ||
+        (long long)H * W > 0x3fffffffLL || max_bins < 1 || max_bins > 256)
         return MP_EINVAL;
-    *bytes = (long long)mi_layout(n_evals, n_pairs, n_thermal_maps, H, W, max_bins, smoothing != 0).total;
+    *bytes = (long long)mi_workspace(nullptr, n_evals, n_pairs, n_thermal_maps, H, W, max_bins, smoothing != 0).bytes;
     return MP_OK;
 }
 
@@ -211,7 +192,7 @@ int mp_mi_joint_histogram(mp_handle* h, const float* optical, int Ho, int Wo, co
                             true, false, workspace, workspace_bytes, s, c);
     if (rc != MP_OK) return rc;
     c.L.T = transforms;
-    launch_mi_histograms(c.L, counts, warped ? warped : c.at<float>(c.lay.warped), minmax, strategy, s);
+    launch_mi_histograms(c.L, counts, warped ? warped : c.w.warped, minmax, strategy, s);
     return launch_status(h);
 }
 
@@ -230,10 +211,8 @@ int mp_mi_objective(mp_handle* h, const float* optical, int Ho, int Wo, const fl
                   sigma > 0.0, workspace, workspace_bytes, s, c);
     if (rc != MP_OK) return rc;
     c.L.T = transforms;
-    unsigned* counts = c.at<unsigned>(c.lay.counts);
-    launch_mi_histograms(c.L, counts, c.at<float>(c.lay.warped), nullptr, 0, s);
-    launch_mi_score(c.L, counts, sigma, normalized != 0, init_transforms, 1, c.stride, c.at<double>(c.lay.smooth_a),
-                    c.at<double>(c.lay.smooth_b), values, s);
+    launch_mi_histograms(c.L, c.w.counts, c.w.warped, nullptr, 0, s);
+    launch_mi_score(c.L, c.w.counts, sigma, normalized != 0, init_transforms, 1, c.stride, c.w.smooth_a, c.w.smooth_b, values, s);
     return launch_status(h);
 }
 
@@ -261,8 +240,7 @@ int mp_mi_refine_step(mp_handle* h, void* workspace, int n_iters, int* live, voi
 {
     if (!h) return MP_EINVAL;
     if (!workspace || !live) return fail(h, MP_EINVAL, "mp_mi_refine_step: NULL tensor");
-    if (!h->mi.workspace || h->mi.workspace != workspace)
-        return fail(h, MP_ESTATE, "mp_mi_refine_step: no refinement was begun in this workspace");
+    if (const int rc = begun_in(h, "mp_mi_refine_step", h->mi.workspace, workspace)) return rc;
     if (n_iters < 1 || n_iters > 100000) return fail(h, MP_EINVAL, "mp_mi_refine_step: n_iters must be in [1, 100000]");
     MP_HIP(hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -276,10 +254,9 @@ int mp_mi_refine_result(mp_handle* h, void* workspace, double* transforms, doubl
     if (!h) return MP_EINVAL;
     if (!workspace || !transforms || !values || !iterations || !function_calls || !success)
         return fail(h, MP_EINVAL, "mp_mi_refine_result: NULL tensor");
-    if (!h->mi.workspace || h->mi.workspace != workspace)
-        return fail(h, MP_ESTATE, "mp_mi_refine_result: no refinement was begun in this workspace");
+    if (const int rc = begun_in(h, "mp_mi_refine_result", h->mi.workspace, workspace)) return rc;
     MP_HIP(hipSetDevice(h->device));
-    launch_mi_nm_result(h->mi.state, h->mi.model, h->mi.P, transforms, nullptr, values, iterations, function_calls, success,
+    launch_mi_nm_result(h->mi.w.state, h->mi.model, h->mi.P, transforms, nullptr, values, iterations, function_calls, success,
                         static_cast<hipStream_t>(stream));
     return launch_status(h);
 }
@@ -290,10 +267,9 @@ int mp_mi_refine_result_model(mp_handle* h, void* workspace, double* transforms,
     if (!h) return MP_EINVAL;
     if (!workspace || !transforms || !values || !iterations || !function_calls || !success || !params)
         return fail(h, MP_EINVAL, "mp_mi_refine_result_model: NULL tensor");
-    if (!h->mi.workspace || h->mi.workspace != workspace)
-        return fail(h, MP_ESTATE, "mp_mi_refine_result_model: no refinement was begun in this workspace");
+    if (const int rc = begun_in(h, "mp_mi_refine_result_model", h->mi.workspace, workspace)) return rc;
     MP_HIP(hipSetDevice(h->device));
-    launch_mi_nm_result(h->mi.state, h->mi.model, h->mi.P, transforms, params, values, iterations, function_calls, success,
+    launch_mi_nm_result(h->mi.w.state, h->mi.model, h->mi.P, transforms, params, values, iterations, function_calls, success,
                         static_cast<hipStream_t>(stream));
     return launch_status(h);
 }

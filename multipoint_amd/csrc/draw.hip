@@ -261,8 +261,6 @@ __global__ __launch_bounds__(256) void draw_segments_resolve_kernel(const unsign
     d[0] = c[0], d[1] = c[1], d[2] = c[2];
 }
 
-bool frames_ok(int n, int H, int W) { return n > 0 && n <= 65535 && H > 0 && W > 0 && H <= 32767 && W <= 32767; }
-
 unsigned blocks_of(long long items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
 
 // the outer and inner radius of a mark; false when the mark is refused
@@ -298,7 +296,7 @@ int mp_draw_gray_to_rgb(mp_handle* h, const float* images, const float* mask, in
 {
     if (!h) return MP_EINVAL;
     if (!images || !canvas) return fail(h, MP_EINVAL, "mp_draw_gray_to_rgb: NULL tensor");
-    if (!frames_ok(B, H, W) || !frames_ok(B, Hc, Wc) || (long long)B * H * W > MAX_PIXELS)
+    if (!frames_ok(B, H, W, 1, 32767) || !frames_ok(B, Hc, Wc, 1, 32767) || (long long)B * H * W > MAX_PIXELS)
         return fail(h, MP_EINVAL, "mp_draw_gray_to_rgb: 1 to 65535 frames, frame and canvas of 1 x 1 to 32767 x 32767 pixels");
     MP_HIP(hipSetDevice(h->device));
     const long long groups = (long long)B * H * ((W + 3) / 4);
@@ -312,7 +310,7 @@ int mp_draw_marks(mp_handle* h, const int* kp_yx, const int* kp_count, int B, in
 {
     if (!h) return MP_EINVAL;
     if (!kp_yx || !kp_count || !palette || !canvas) return fail(h, MP_EINVAL, "mp_draw_marks: NULL tensor");
-    if (!frames_ok(B, Hc, Wc) || K < 1 || K > MAX_LIST)
+    if (!frames_ok(B, Hc, Wc, 1, 32767) || K < 1 || K > MAX_LIST)
         return fail(h, MP_EINVAL, "mp_draw_marks: 1 to 65535 canvases of 1 x 1 to 32767 x 32767 pixels, K in [1, 2^20]");
     if (n_colors < 1) return fail(h, MP_EINVAL, "mp_draw_marks: empty palette");
     int ro, ri;
@@ -332,7 +330,7 @@ int mp_draw_matches(mp_handle* h, const int* kp_a, const int* kp_b, const int* c
     if (!h) return MP_EINVAL;
     if (!kp_a || !kp_b || !count_a || !count_b || !match_idx || !palette || !canvas)
         return fail(h, MP_EINVAL, "mp_draw_matches: NULL tensor");
-    if (!frames_ok(P, Hc, Wc) || K < 1 || K > MAX_LIST)
+    if (!frames_ok(P, Hc, Wc, 1, 32767) || K < 1 || K > MAX_LIST)
         return fail(h, MP_EINVAL, "mp_draw_matches: 1 to 65535 canvases of 1 x 1 to 32767 x 32767 pixels, K in [1, 2^20]");
     if (n_colors < 1) return fail(h, MP_EINVAL, "mp_draw_matches: empty palette");
     int ro, ri;
@@ -357,7 +355,7 @@ int mp_segments_draw(mp_handle* h, const int* segments, const int* seg_count, in
 {
     if (!h) return MP_EINVAL;
     if (!segments || !seg_count || !palette || !canvas) return fail(h, MP_EINVAL, "mp_segments_draw: NULL tensor");
-    if (!frames_ok(B, Hc, Wc) || N < 1 || N > MAX_LIST)
+    if (!frames_ok(B, Hc, Wc, 1, 32767) || N < 1 || N > MAX_LIST)
         return fail(h, MP_EINVAL, "mp_segments_draw: 1 to 65535 canvases of 1 x 1 to 32767 x 32767 pixels, N in [1, 2^20]");
     if (n_colors < 1) return fail(h, MP_EINVAL, "mp_segments_draw: empty palette");
     if (thickness < 1 || thickness > MP_DRAW_MAX_THICKNESS)
@@ -380,7 +378,7 @@ int mp_draw_compose(mp_handle* h, const float* warped, const float* thermal, int
 {
     if (!h) return MP_EINVAL;
     if (!warped || !thermal || !canvas) return fail(h, MP_EINVAL, "mp_draw_compose: NULL tensor");
-    if (!frames_ok(B, H, W) || !frames_ok(B, Hc, Wc) || (long long)B * H * W > MAX_PIXELS)
+    if (!frames_ok(B, H, W, 1, 32767) || !frames_ok(B, Hc, Wc, 1, 32767) || (long long)B * H * W > MAX_PIXELS)
         return fail(h, MP_EINVAL, "mp_draw_compose: 1 to 65535 frames, frame and canvas of 1 x 1 to 32767 x 32767 pixels");
     if (mode < MP_DRAW_BLEND || mode > MP_DRAW_DIFFERENCE)
         return fail(h, MP_EINVAL, "mp_draw_compose: mode MP_DRAW_BLEND, _CHECKER, _ANAGLYPH or _DIFFERENCE");

@@ -106,12 +106,12 @@ __device__ void ecc_decide(const double* s, int HW, const EccOptions& o, EccStat
     if (n < o.min_valid * (double)HW) { st.status = MP_ECC_FEW_VALID; return; }
     bool ok = true;
 #pragma unroll
-    for (int i = 0; i < S::N; ++i) ok = ok && finite_d(s[i]);
+    for (int i = 0; i < S::N; ++i) ok = ok && finite64(s[i]);
     if (!ok) { st.status = MP_ECC_NONFINITE; return; }
     const double mw = s[1] / n, mr = s[2] / n;
     const double ww = s[3] - n * mw * mw, rr = s[4] - n * mr * mr, corr = s[5] - n * mw * mr;
     const double rho = corr / (sqrt(ww) * sqrt(rr));
-    if (!finite_d(rho)) { st.status = MP_ECC_NONFINITE; return; }
+    if (!finite64(rho)) { st.status = MP_ECC_NONFINITE; return; }
     if (converged(rho, o, st)) return;
 
     double A[K][K], ip[K], tp[K];
@@ -210,31 +210,23 @@ void launch_ecc_pack(const float* feat, int n, int H, int W, float* packed, hipS
     hipLaunchKernelGGL(ecc_pack_kernel, grid, dim3(THREADS), 0, s, feat, H, W, reinterpret_cast<float4*>(packed));
 }
 
-#define MP_ECC_BY_K(K, CALL)            \
-    switch (K) {                        \
-    case 2: { CALL(2); break; }         \
-    case 4: { CALL(4); break; }         \
-    case 6: { CALL(6); break; }         \
-    default: { CALL(8); break; }        \
-    }
-
 void launch_ecc_sums(int K, const float* packed, int Ho, int Wo, const float* thermal, int H, int W, const int* pair,
                      const double* T, const EccState* state, int P, double* partial, hipStream_t s)
 {
     const dim3 grid((unsigned)ecc_chunks(H, W), (unsigned)P);
     const float4* img = reinterpret_cast<const float4*>(packed);
-#define MP_ECC_CALL(KK) \
-    hipLaunchKernelGGL(ecc_sums_kernel<KK>, grid, dim3(THREADS), 0, s, img, Ho, Wo, thermal, H, W, pair, T, state, partial)
-    MP_ECC_BY_K(K, MP_ECC_CALL)
-#undef MP_ECC_CALL
+    for_params(K, [&](auto k) {
+        hipLaunchKernelGGL(ecc_sums_kernel<decltype(k)::value>, grid, dim3(THREADS), 0, s, img, Ho, Wo, thermal, H, W, pair, T, state,
+                           partial);
+    });
 }
 
 void launch_ecc_reduce(int K, const double* partial, int P, int chunks, double* sums, hipStream_t s)
 {
     const dim3 grid((unsigned)((P * ecc_sum_count(K) + THREADS - 1) / THREADS));
-#define MP_ECC_CALL(KK) hipLaunchKernelGGL(ecc_reduce_kernel<KK>, grid, dim3(THREADS), 0, s, partial, P, chunks, sums)
-    MP_ECC_BY_K(K, MP_ECC_CALL)
-#undef MP_ECC_CALL
+    for_params(K, [&](auto k) {
+        hipLaunchKernelGGL(ecc_reduce_kernel<decltype(k)::value>, grid, dim3(THREADS), 0, s, partial, P, chunks, sums);
+    });
 }
 
 void launch_ecc_begin(const int* pair, const double* T0, int P, EccState* state, hipStream_t s)
@@ -245,9 +237,9 @@ void launch_ecc_begin(const int* pair, const double* T0, int P, EccState* state,
 void launch_ecc_solve(int K, const double* partial, int P, int chunks, int HW, EccOptions o, EccState* state, hipStream_t s)
 {
     const dim3 grid((unsigned)((P + WAVES - 1) / WAVES));
-#define MP_ECC_CALL(KK) hipLaunchKernelGGL(ecc_solve_kernel<KK>, grid, dim3(THREADS), 0, s, partial, P, chunks, HW, o, state)
-    MP_ECC_BY_K(K, MP_ECC_CALL)
-#undef MP_ECC_CALL
+    for_params(K, [&](auto k) {
+        hipLaunchKernelGGL(ecc_solve_kernel<decltype(k)::value>, grid, dim3(THREADS), 0, s, partial, P, chunks, HW, o, state);
+    });
 }
 
 void launch_ecc_live(const EccState* state, int P, int* live, hipStream_t s)

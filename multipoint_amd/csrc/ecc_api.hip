@@ -8,32 +8,25 @@ using namespace mp_host;
 
 namespace {
 
-size_t up(size_t v) { return (v + 255) & ~(size_t)255; }
-
-struct EccLayout { size_t pair, state, partial, total; };
-
-EccLayout ecc_layout(long long P, long long H, long long W)
+EccWorkspace ecc_workspace(void* base, size_t P, int H, int W)
 {
-    EccLayout l{};
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += up(bytes); return o; };
-    l.pair = take((size_t)P * sizeof(int));
-    l.state = take((size_t)P * sizeof(EccState));
-    l.partial = take((size_t)P * ecc_chunks((int)H, (int)W) * MP_ECC_MAX_SUMS * sizeof(double));
-    l.total = at;
-    return l;
+    Carver c(base);
+    EccWorkspace w{};
+    w.pair = c.take<int>(P);
+    w.state = c.take<EccState>(P);
+    w.partial = c.take<double>(P * ecc_chunks(H, W) * MP_ECC_MAX_SUMS);
+    w.bytes = c.bytes();
+    return w;
 }
-
-bool frame_ok(int H, int W) { return H >= 8 && W >= 8 && H <= 4096 && W <= 4096; }
 
 // the checks mp_ecc_sums and mp_ecc_begin share; copies the pair list into the workspace
 int ecc_stage(mp_handle* h, const std::string& fn, const float* packed, int Ho, int Wo, const float* thermal, int H, int W,
               int n_pairs, const int* pair, const double* transforms, int P, int model, void* workspace, long long bytes,
-              hipStream_t s, EccLayout& lay)
+              hipStream_t s, EccWorkspace& w)
 {
     if (!packed || !thermal || !pair || !transforms || !workspace) return fail(h, MP_EINVAL, fn + ": NULL tensor");
-    if (!frame_ok(H, W) || !frame_ok(Ho, Wo)) return fail(h, MP_EINVAL, fn + ": frames must be 8 x 8 to 4096 x 4096");
-    if (n_pairs < 1 || n_pairs > 65535) return fail(h, MP_EINVAL, fn + ": n_pairs must be in [1, 65535]");
+    if (!sides_ok(H, W, 8, 4096) || !sides_ok(Ho, Wo, 8, 4096)) return fail(h, MP_EINVAL, fn + ": frames must be 8 x 8 to 4096 x 4096");
+    if (!count_ok(n_pairs)) return fail(h, MP_EINVAL, fn + ": n_pairs must be in [1, 65535]");
     if (P < 1 || P > MP_ECC_MAX_PROBLEMS)
         return fail(h, MP_EINVAL, fn + ": n_problems must be in [1, " + std::to_string(MP_ECC_MAX_PROBLEMS) + "]");
     if (ecc_model_params(model) == 0)
@@ -42,12 +35,11 @@ int ecc_stage(mp_handle* h, const std::string& fn, const float* packed, int Ho, 
     for (int q = 0; q < P; ++q)
         if (pair[q] < 0 || pair[q] >= n_pairs) return fail(h, MP_EINVAL, fn + ": pair index outside [0, n_pairs)");
     if (((size_t)packed & 15) != 0) return fail(h, MP_EINVAL, fn + ": packed must be 16-byte aligned");
-    lay = ecc_layout(P, H, W);
-    if (bytes < (long long)lay.total)
-        return fail(h, MP_EINVAL, fn + ": workspace of " + std::to_string(bytes) + " B, needs " + std::to_string(lay.total) +
-                                      " B (mp_ecc_workspace_bytes)");
+    w = ecc_workspace(workspace, P, H, W);
+    const int rc = need_workspace(h, fn, bytes, w.bytes, "mp_ecc_workspace_bytes");
+    if (rc != MP_OK) return rc;
     MP_HIP(hipSetDevice(h->device));
-    MP_HIP(hipMemcpyAsync(static_cast<char*>(workspace) + lay.pair, pair, (size_t)P * sizeof(int), hipMemcpyHostToDevice, s));
+    MP_HIP(hipMemcpyAsync(w.pair, pair, (size_t)P * sizeof(int), hipMemcpyHostToDevice, s));
     MP_HIP(hipStreamSynchronize(s));
     return MP_OK;
 }
@@ -58,8 +50,8 @@ extern "C" {
 
 int mp_ecc_workspace_bytes(int n_problems, int H, int W, long long* bytes)
 {
-    if (!bytes || n_problems < 1 || n_problems > MP_ECC_MAX_PROBLEMS || !frame_ok(H, W)) return MP_EINVAL;
-    *bytes = (long long)ecc_layout(n_problems, H, W).total;
+    if (!bytes || n_problems < 1 || n_problems > MP_ECC_MAX_PROBLEMS || !sides_ok(H, W, 8, 4096)) return MP_EINVAL;
+    *bytes = (long long)ecc_workspace(nullptr, n_problems, H, W).bytes;
     return MP_OK;
 }
 
@@ -68,8 +60,8 @@ int mp_ecc_prepare(mp_handle* h, const float* blurred, int n, int H, int W, int 
     if (!h) return MP_EINVAL;
     if (!blurred || !feat) return fail(h, MP_EINVAL, "mp_ecc_prepare: NULL tensor");
     if (blurred == feat) return fail(h, MP_EINVAL, "mp_ecc_prepare: feat must not alias blurred");
-    if (n < 1 || n > 65535) return fail(h, MP_EINVAL, "mp_ecc_prepare: n must be in [1, 65535]");
-    if (!frame_ok(H, W)) return fail(h, MP_EINVAL, "mp_ecc_prepare: frames must be 8 x 8 to 4096 x 4096");
+    if (!count_ok(n)) return fail(h, MP_EINVAL, "mp_ecc_prepare: n must be in [1, 65535]");
+    if (!sides_ok(H, W, 8, 4096)) return fail(h, MP_EINVAL, "mp_ecc_prepare: frames must be 8 x 8 to 4096 x 4096");
     if (feature != MP_ECC_GRADIENT && feature != MP_ECC_INTENSITY)
         return fail(h, MP_EINVAL, "mp_ecc_prepare: feature must be MP_ECC_GRADIENT or MP_ECC_INTENSITY");
     if (((size_t)packed & 15) != 0) return fail(h, MP_EINVAL, "mp_ecc_prepare: packed must be 16-byte aligned");
@@ -87,16 +79,13 @@ int mp_ecc_sums(mp_handle* h, const float* packed, int Ho, int Wo, const float* 
     if (!h) return MP_EINVAL;
     if (!sums) return fail(h, MP_EINVAL, "mp_ecc_sums: NULL tensor");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    EccLayout lay;
+    EccWorkspace w;
     const int rc = ecc_stage(h, "mp_ecc_sums", packed, Ho, Wo, thermal, H, W, n_pairs, pair, transforms, n_problems, model,
-                             workspace, workspace_bytes, s, lay);
+                             workspace, workspace_bytes, s, w);
     if (rc != MP_OK) return rc;
-    char* ws = static_cast<char*>(workspace);
     const int K = ecc_model_params(model);
-    double* partial = reinterpret_cast<double*>(ws + lay.partial);
-    launch_ecc_sums(K, packed, Ho, Wo, thermal, H, W, reinterpret_cast<const int*>(ws + lay.pair), transforms, nullptr, n_problems,
-                    partial, s);
-    launch_ecc_reduce(K, partial, n_problems, ecc_chunks(H, W), sums, s);
+    launch_ecc_sums(K, packed, Ho, Wo, thermal, H, W, w.pair, transforms, nullptr, n_problems, w.partial, s);
+    launch_ecc_reduce(K, w.partial, n_problems, ecc_chunks(H, W), sums, s);
     return launch_status(h);
 }
 
@@ -109,19 +98,15 @@ int mp_ecc_begin(mp_handle* h, const float* packed, int Ho, int Wo, const float*
     if (!(eps >= 0.0) || maxiter < 1 || !(min_valid >= 0.0 && min_valid <= 1.0))
         return fail(h, MP_EINVAL, "mp_ecc_begin: eps must be non-negative, maxiter positive, min_valid in [0, 1]");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    EccLayout lay;
-    const int rc = ecc_stage(h, "mp_ecc_begin", packed, Ho, Wo, thermal, H, W, n_pairs, pair, init_transforms, n_problems, model,
-                             workspace, workspace_bytes, s, lay);
-    if (rc != MP_OK) return rc;
-    char* ws = static_cast<char*>(workspace);
     EccRefine r;
+    const int rc = ecc_stage(h, "mp_ecc_begin", packed, Ho, Wo, thermal, H, W, n_pairs, pair, init_transforms, n_problems, model,
+                             workspace, workspace_bytes, s, r.w);
+    if (rc != MP_OK) return rc;
     r.workspace = workspace;
     r.packed = packed; r.thermal = thermal;
     r.Ho = Ho; r.Wo = Wo; r.H = H; r.W = W; r.P = n_problems; r.K = ecc_model_params(model);
     r.opt = EccOptions{eps, min_valid, maxiter, 0};
-    r.state = reinterpret_cast<EccState*>(ws + lay.state);
-    r.partial = reinterpret_cast<double*>(ws + lay.partial);
-    launch_ecc_begin(reinterpret_cast<const int*>(ws + lay.pair), init_transforms, n_problems, r.state, s);
+    launch_ecc_begin(r.w.pair, init_transforms, n_problems, r.w.state, s);
     h->ecc = r;
     return launch_status(h);
 }
@@ -130,17 +115,16 @@ int mp_ecc_step(mp_handle* h, void* workspace, int n_iters, int* live, void* str
 {
     if (!h) return MP_EINVAL;
     if (!workspace || !live) return fail(h, MP_EINVAL, "mp_ecc_step: NULL tensor");
-    if (!h->ecc.workspace || h->ecc.workspace != workspace)
-        return fail(h, MP_ESTATE, "mp_ecc_step: no refinement was begun in this workspace");
+    if (const int rc = begun_in(h, "mp_ecc_step", h->ecc.workspace, workspace)) return rc;
     if (n_iters < 1 || n_iters > 100000) return fail(h, MP_EINVAL, "mp_ecc_step: n_iters must be in [1, 100000]");
     MP_HIP(hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const EccRefine& r = h->ecc;
     for (int i = 0; i < n_iters; ++i) {
-        launch_ecc_sums(r.K, r.packed, r.Ho, r.Wo, r.thermal, r.H, r.W, nullptr, nullptr, r.state, r.P, r.partial, s);
-        launch_ecc_solve(r.K, r.partial, r.P, ecc_chunks(r.H, r.W), r.H * r.W, r.opt, r.state, s);
+        launch_ecc_sums(r.K, r.packed, r.Ho, r.Wo, r.thermal, r.H, r.W, nullptr, nullptr, r.w.state, r.P, r.w.partial, s);
+        launch_ecc_solve(r.K, r.w.partial, r.P, ecc_chunks(r.H, r.W), r.H * r.W, r.opt, r.w.state, s);
     }
-    launch_ecc_live(r.state, r.P, live, s);
+    launch_ecc_live(r.w.state, r.P, live, s);
     return launch_status(h);
 }
 
@@ -150,10 +134,9 @@ int mp_ecc_result(mp_handle* h, void* workspace, double* transforms, double* rho
     if (!h) return MP_EINVAL;
     if (!workspace || !transforms || !rho || !iterations || !status || !converged)
         return fail(h, MP_EINVAL, "mp_ecc_result: NULL tensor");
-    if (!h->ecc.workspace || h->ecc.workspace != workspace)
-        return fail(h, MP_ESTATE, "mp_ecc_result: no refinement was begun in this workspace");
+    if (const int rc = begun_in(h, "mp_ecc_result", h->ecc.workspace, workspace)) return rc;
     MP_HIP(hipSetDevice(h->device));
-    launch_ecc_result(h->ecc.state, h->ecc.P, transforms, rho, iterations, status, converged, static_cast<hipStream_t>(stream));
+    launch_ecc_result(h->ecc.w.state, h->ecc.P, transforms, rho, iterations, status, converged, static_cast<hipStream_t>(stream));
     return launch_status(h);
 }
 

@@ -183,7 +183,7 @@ __global__ __launch_bounds__(THREADS) void ecc_pooled_pair_kernel(const double* 
     if (!live) return;
     const double* s = lds[wave];
     bool ok = true;
-    for (int i = lane; i < S::N; i += 64) ok = ok && finite_d(s[i]);
+    for (int i = lane; i < S::N; i += 64) ok = ok && finite64(s[i]);
     ok = __all(ok);
     const double n = s[0];
     const double mw = s[1] / n, mr = s[2] / n;                                     // (n == 0: never used, the pair is out)
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(THREADS) void ecc_pooled_solve_kernel(const int* __
     const double* s = lds[wave];
     const double ww = s[0], rr = s[1], corr = s[2];
     const double rho = corr / (sqrt(ww) * sqrt(rr));
-    if (!finite_d(rho)) { st.status = MP_ECC_NONFINITE; return; }
+    if (!finite64(rho)) { st.status = MP_ECC_NONFINITE; return; }
     if (converged(rho, o, st)) return;
     double A[K][K], ip[K], tp[K];
     {
@@ -334,25 +334,16 @@ void launch_ecc_flag_packed(float* packed, int n, int HW, const unsigned char* m
     hipLaunchKernelGGL(ecc_flag_kernel, dim3(blocks(HW), (unsigned)n), dim3(THREADS), 0, s, reinterpret_cast<float4*>(packed), HW, mask);
 }
 
-#define MP_ECC_BY_K(K, CALL)            \
-    switch (K) {                        \
-    case 2: { CALL(2); break; }         \
-    case 4: { CALL(4); break; }         \
-    case 6: { CALL(6); break; }         \
-    default: { CALL(8); break; }        \
-    }
-
 void launch_ecc_pooled_sums(int K, const float* packed, int Ho, int Wo, const float* thermal, int H, int W,
                             const unsigned char* tmasks, const int* tmask, const int* group, const int* active, const double* T,
                             const EccGroup* groups, int P, double* partial, hipStream_t s)
 {
     const dim3 grid((unsigned)ecc_chunks(H, W), (unsigned)P);
     const float4* img = reinterpret_cast<const float4*>(packed);
-#define MP_ECC_CALL(KK)                                                                                                          \
-    hipLaunchKernelGGL(ecc_pooled_sums_kernel<KK>, grid, dim3(THREADS), 0, s, img, Ho, Wo, thermal, H, W, tmasks, tmask, group, \
-                       active, T, groups, partial)
-    MP_ECC_BY_K(K, MP_ECC_CALL)
-#undef MP_ECC_CALL
+    for_params(K, [&](auto k) {
+        hipLaunchKernelGGL(ecc_pooled_sums_kernel<decltype(k)::value>, grid, dim3(THREADS), 0, s, img, Ho, Wo, thermal, H, W, tmasks,
+                           tmask, group, active, T, groups, partial);
+    });
 }
 
 void launch_ecc_pooled_begin(const double* T0, const unsigned char* tmasks, const int* tmask, int HW, int G, int P, EccGroup* groups,
@@ -366,20 +357,20 @@ void launch_ecc_pooled_pair(int K, const double* partial, int P, int chunks, con
                             const EccGroup* groups, EccPairRec* recs, double* quant, hipStream_t s)
 {
     const dim3 grid((unsigned)((P + WAVES - 1) / WAVES));
-#define MP_ECC_CALL(KK) \
-    hipLaunchKernelGGL(ecc_pooled_pair_kernel<KK>, grid, dim3(THREADS), 0, s, partial, P, chunks, group, active, o, groups, recs, quant)
-    MP_ECC_BY_K(K, MP_ECC_CALL)
-#undef MP_ECC_CALL
+    for_params(K, [&](auto k) {
+        hipLaunchKernelGGL(ecc_pooled_pair_kernel<decltype(k)::value>, grid, dim3(THREADS), 0, s, partial, P, chunks, group, active, o,
+                           groups, recs, quant);
+    });
 }
 
 void launch_ecc_pooled_solve(int K, const int* offsets, const int* list, const EccPairRec* recs, const double* quant, int G,
                              EccOptions o, EccGroup* groups, hipStream_t s)
 {
     const dim3 grid((unsigned)((G + WAVES - 1) / WAVES));
-#define MP_ECC_CALL(KK) \
-    hipLaunchKernelGGL(ecc_pooled_solve_kernel<KK>, grid, dim3(THREADS), 0, s, offsets, list, recs, quant, G, o, groups)
-    MP_ECC_BY_K(K, MP_ECC_CALL)
-#undef MP_ECC_CALL
+    for_params(K, [&](auto k) {
+        hipLaunchKernelGGL(ecc_pooled_solve_kernel<decltype(k)::value>, grid, dim3(THREADS), 0, s, offsets, list, recs, quant, G, o,
+                           groups);
+    });
 }
 
 void launch_ecc_pooled_live(const EccGroup* groups, int G, int* live, hipStream_t s)

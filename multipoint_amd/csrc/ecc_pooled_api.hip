@@ -11,39 +11,32 @@ using namespace mp_host;
 
 namespace {
 
-size_t up(size_t v) { return (v + 255) & ~(size_t)255; }
-
-struct PooledLayout { size_t group, active, offsets, list, tmask, groups, recs, quant, partial, total; };
-
-PooledLayout pooled_layout(long long P, long long G, long long H, long long W)
+EccPooledWorkspace pooled_workspace(void* base, size_t P, size_t G, int H, int W)
 {
-    PooledLayout l{};
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += up(bytes); return o; };
-    l.group = take((size_t)P * sizeof(int));
-    l.active = take((size_t)P * sizeof(int));
-    l.offsets = take((size_t)(G + 1) * sizeof(int));
-    l.list = take((size_t)P * sizeof(int));
-    l.tmask = take((size_t)G * sizeof(int));
-    l.groups = take((size_t)G * sizeof(EccGroup));
-    l.recs = take((size_t)P * sizeof(EccPairRec));
-    l.quant = take((size_t)P * MP_ECC_POOLED_MAX_Q * sizeof(double));
-    l.partial = take((size_t)P * ecc_chunks((int)H, (int)W) * MP_ECC_MAX_SUMS * sizeof(double));
-    l.total = at;
-    return l;
+    Carver c(base);
+    EccPooledWorkspace w{};
+    w.group = c.take<int>(P);
+    w.active = c.take<int>(P);
+    w.offsets = c.take<int>(G + 1);
+    w.list = c.take<int>(P);
+    w.tmask = c.take<int>(G);
+    w.groups = c.take<EccGroup>(G);
+    w.recs = c.take<EccPairRec>(P);
+    w.quant = c.take<double>(P * MP_ECC_POOLED_MAX_Q);
+    w.partial = c.take<double>(P * ecc_chunks(H, W) * MP_ECC_MAX_SUMS);
+    w.bytes = c.bytes();
+    return w;
 }
-
-bool frame_ok(int H, int W) { return H >= 8 && W >= 8 && H <= 4096 && W <= 4096; }
 
 // the checks mp_ecc_pooled_sums and mp_ecc_pooled_begin share; copies the lists into the workspace
 int pooled_stage(mp_handle* h, const std::string& fn, const float* packed, int Ho, int Wo, const float* thermal, int H, int W,
                  int P, const int* group, const int* active, int G, const double* transforms, const unsigned char* masks,
                  int n_masks, const int* mask_of_group, int model, void* workspace, long long bytes, hipStream_t s,
-                 PooledLayout& lay)
+                 EccPooledWorkspace& w)
 {
     if (!packed || !thermal || !group || !transforms || !workspace) return fail(h, MP_EINVAL, fn + ": NULL tensor");
-    if (!frame_ok(H, W) || !frame_ok(Ho, Wo)) return fail(h, MP_EINVAL, fn + ": frames must be 8 x 8 to 4096 x 4096");
-    if (P < 1 || P > 65535) return fail(h, MP_EINVAL, fn + ": n_pairs must be in [1, 65535]");
+    if (!sides_ok(H, W, 8, 4096) || !sides_ok(Ho, Wo, 8, 4096)) return fail(h, MP_EINVAL, fn + ": frames must be 8 x 8 to 4096 x 4096");
+    if (!count_ok(P)) return fail(h, MP_EINVAL, fn + ": n_pairs must be in [1, 65535]");
     if (G < 1 || G > MP_ECC_MAX_PROBLEMS)
         return fail(h, MP_EINVAL, fn + ": n_groups must be in [1, " + std::to_string(MP_ECC_MAX_PROBLEMS) + "]");
     if (ecc_model_params(model) == 0)
@@ -71,17 +64,15 @@ int pooled_stage(mp_handle* h, const std::string& fn, const float* packed, int H
         for (int p = 0; p < P; ++p) list[at[group[p]]++] = p;                          // ascending pair index inside a group
     }
     if (((size_t)packed & 15) != 0) return fail(h, MP_EINVAL, fn + ": packed must be 16-byte aligned");
-    lay = pooled_layout(P, G, H, W);
-    if (bytes < (long long)lay.total)
-        return fail(h, MP_EINVAL, fn + ": workspace of " + std::to_string(bytes) + " B, needs " + std::to_string(lay.total) +
-                                      " B (mp_ecc_pooled_workspace_bytes)");
+    w = pooled_workspace(workspace, P, G, H, W);
+    const int rc = need_workspace(h, fn, bytes, w.bytes, "mp_ecc_pooled_workspace_bytes");
+    if (rc != MP_OK) return rc;
     MP_HIP(hipSetDevice(h->device));
-    char* ws = static_cast<char*>(workspace);
-    MP_HIP(hipMemcpyAsync(ws + lay.group, group, (size_t)P * sizeof(int), hipMemcpyHostToDevice, s));
-    MP_HIP(hipMemcpyAsync(ws + lay.active, act.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice, s));
-    MP_HIP(hipMemcpyAsync(ws + lay.offsets, offsets.data(), (size_t)(G + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-    MP_HIP(hipMemcpyAsync(ws + lay.list, list.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice, s));
-    MP_HIP(hipMemcpyAsync(ws + lay.tmask, tmask.data(), (size_t)G * sizeof(int), hipMemcpyHostToDevice, s));
+    MP_HIP(hipMemcpyAsync(w.group, group, (size_t)P * sizeof(int), hipMemcpyHostToDevice, s));
+    MP_HIP(hipMemcpyAsync(w.active, act.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice, s));
+    MP_HIP(hipMemcpyAsync(w.offsets, offsets.data(), (size_t)(G + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+    MP_HIP(hipMemcpyAsync(w.list, list.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice, s));
+    MP_HIP(hipMemcpyAsync(w.tmask, tmask.data(), (size_t)G * sizeof(int), hipMemcpyHostToDevice, s));
     MP_HIP(hipStreamSynchronize(s));
     return MP_OK;
 }
@@ -96,8 +87,8 @@ int mp_ecc_mask_grow(mp_handle* h, const unsigned char* mask, int n, int H, int 
     if (!h) return MP_EINVAL;
     if (!mask || !tmp || !out) return fail(h, MP_EINVAL, "mp_ecc_mask_grow: NULL tensor");
     if (tmp == mask || tmp == out) return fail(h, MP_EINVAL, "mp_ecc_mask_grow: tmp must not alias mask or out");
-    if (n < 1 || n > 65535) return fail(h, MP_EINVAL, "mp_ecc_mask_grow: n must be in [1, 65535]");
-    if (!frame_ok(H, W)) return fail(h, MP_EINVAL, "mp_ecc_mask_grow: frames must be 8 x 8 to 4096 x 4096");
+    if (!count_ok(n)) return fail(h, MP_EINVAL, "mp_ecc_mask_grow: n must be in [1, 65535]");
+    if (!sides_ok(H, W, 8, 4096)) return fail(h, MP_EINVAL, "mp_ecc_mask_grow: frames must be 8 x 8 to 4096 x 4096");
     if (radius < 0) return fail(h, MP_EINVAL, "mp_ecc_mask_grow: radius must not be negative");
     MP_HIP(hipSetDevice(h->device));
     launch_ecc_mask_grow(mask, n, H, W, radius, tmp, out, static_cast<hipStream_t>(stream));
@@ -108,8 +99,8 @@ int mp_ecc_static_update(mp_handle* h, const float* frames, int n, int H, int W,
 {
     if (!h) return MP_EINVAL;
     if (!frames || !lo || !hi) return fail(h, MP_EINVAL, "mp_ecc_static_update: NULL tensor");
-    if (n < 1 || n > 65535) return fail(h, MP_EINVAL, "mp_ecc_static_update: n must be in [1, 65535]");
-    if (!frame_ok(H, W)) return fail(h, MP_EINVAL, "mp_ecc_static_update: frames must be 8 x 8 to 4096 x 4096");
+    if (!count_ok(n)) return fail(h, MP_EINVAL, "mp_ecc_static_update: n must be in [1, 65535]");
+    if (!sides_ok(H, W, 8, 4096)) return fail(h, MP_EINVAL, "mp_ecc_static_update: frames must be 8 x 8 to 4096 x 4096");
     MP_HIP(hipSetDevice(h->device));
     launch_ecc_static_update(frames, n, H * W, first != 0, lo, hi, static_cast<hipStream_t>(stream));
     return launch_status(h);
@@ -119,7 +110,7 @@ int mp_ecc_static_finish(mp_handle* h, const float* lo, const float* hi, int H, 
 {
     if (!h) return MP_EINVAL;
     if (!lo || !hi || !mask) return fail(h, MP_EINVAL, "mp_ecc_static_finish: NULL tensor");
-    if (!frame_ok(H, W)) return fail(h, MP_EINVAL, "mp_ecc_static_finish: frames must be 8 x 8 to 4096 x 4096");
+    if (!sides_ok(H, W, 8, 4096)) return fail(h, MP_EINVAL, "mp_ecc_static_finish: frames must be 8 x 8 to 4096 x 4096");
     MP_HIP(hipSetDevice(h->device));
     launch_ecc_static_finish(lo, hi, H * W, mask, static_cast<hipStream_t>(stream));
     return launch_status(h);
@@ -131,8 +122,8 @@ int mp_ecc_flag_packed(mp_handle* h, float* packed, int n, int H, int W, const u
     if (!h) return MP_EINVAL;
     if (!packed || !masks || !mask_of_frame) return fail(h, MP_EINVAL, "mp_ecc_flag_packed: NULL tensor");
     if (((size_t)packed & 15) != 0) return fail(h, MP_EINVAL, "mp_ecc_flag_packed: packed must be 16-byte aligned");
-    if (n < 1 || n > 65535) return fail(h, MP_EINVAL, "mp_ecc_flag_packed: n must be in [1, 65535]");
-    if (!frame_ok(H, W)) return fail(h, MP_EINVAL, "mp_ecc_flag_packed: frames must be 8 x 8 to 4096 x 4096");
+    if (!count_ok(n)) return fail(h, MP_EINVAL, "mp_ecc_flag_packed: n must be in [1, 65535]");
+    if (!sides_ok(H, W, 8, 4096)) return fail(h, MP_EINVAL, "mp_ecc_flag_packed: frames must be 8 x 8 to 4096 x 4096");
     if (n_masks < 1) return fail(h, MP_EINVAL, "mp_ecc_flag_packed: n_masks must be positive");
     for (int i = 0; i < n; ++i)
         if (mask_of_frame[i] < -1 || mask_of_frame[i] >= n_masks)
@@ -151,8 +142,8 @@ int mp_ecc_flag_packed(mp_handle* h, float* packed, int n, int H, int W, const u
 
 int mp_ecc_pooled_workspace_bytes(int n_pairs, int n_groups, int H, int W, long long* bytes)
 {
-    if (!bytes || n_pairs < 1 || n_pairs > 65535 || n_groups < 1 || n_groups > MP_ECC_MAX_PROBLEMS || !frame_ok(H, W)) return MP_EINVAL;
-    *bytes = (long long)pooled_layout(n_pairs, n_groups, H, W).total;
+    if (!bytes || !count_ok(n_pairs) || n_groups < 1 || n_groups > MP_ECC_MAX_PROBLEMS || !sides_ok(H, W, 8, 4096)) return MP_EINVAL;
+    *bytes = (long long)pooled_workspace(nullptr, n_pairs, n_groups, H, W).bytes;
     return MP_OK;
 }
 
@@ -163,17 +154,14 @@ int mp_ecc_pooled_sums(mp_handle* h, const float* packed, int Ho, int Wo, const 
     if (!h) return MP_EINVAL;
     if (!sums) return fail(h, MP_EINVAL, "mp_ecc_pooled_sums: NULL tensor");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    PooledLayout lay;
+    EccPooledWorkspace w;
     const int rc = pooled_stage(h, "mp_ecc_pooled_sums", packed, Ho, Wo, thermal, H, W, n_pairs, group, nullptr, n_groups, transforms,
-                                thermal_masks, n_masks, mask_of_group, model, workspace, workspace_bytes, s, lay);
+                                thermal_masks, n_masks, mask_of_group, model, workspace, workspace_bytes, s, w);
     if (rc != MP_OK) return rc;
-    char* ws = static_cast<char*>(workspace);
     const int K = ecc_model_params(model);
-    double* partial = reinterpret_cast<double*>(ws + lay.partial);
-    launch_ecc_pooled_sums(K, packed, Ho, Wo, thermal, H, W, thermal_masks, reinterpret_cast<const int*>(ws + lay.tmask),
-                           reinterpret_cast<const int*>(ws + lay.group), reinterpret_cast<const int*>(ws + lay.active), transforms,
-                           nullptr, n_pairs, partial, s);
-    launch_ecc_reduce(K, partial, n_pairs, ecc_chunks(H, W), sums, s);
+    launch_ecc_pooled_sums(K, packed, Ho, Wo, thermal, H, W, thermal_masks, w.tmask, w.group, w.active, transforms, nullptr, n_pairs,
+                           w.partial, s);
+    launch_ecc_reduce(K, w.partial, n_pairs, ecc_chunks(H, W), sums, s);
     return launch_status(h);
 }
 
@@ -187,26 +175,15 @@ int mp_ecc_pooled_begin(mp_handle* h, const float* packed, int Ho, int Wo, const
     if (!(eps >= 0.0) || maxiter < 1 || !(min_valid >= 0.0 && min_valid <= 1.0))
         return fail(h, MP_EINVAL, "mp_ecc_pooled_begin: eps must be non-negative, maxiter positive, min_valid in [0, 1]");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    PooledLayout lay;
-    const int rc = pooled_stage(h, "mp_ecc_pooled_begin", packed, Ho, Wo, thermal, H, W, n_pairs, group, active, n_groups,
-                                init_transforms, thermal_masks, n_masks, mask_of_group, model, workspace, workspace_bytes, s, lay);
-    if (rc != MP_OK) return rc;
-    char* ws = static_cast<char*>(workspace);
     EccPooledRefine r;
+    const int rc = pooled_stage(h, "mp_ecc_pooled_begin", packed, Ho, Wo, thermal, H, W, n_pairs, group, active, n_groups,
+                                init_transforms, thermal_masks, n_masks, mask_of_group, model, workspace, workspace_bytes, s, r.w);
+    if (rc != MP_OK) return rc;
     r.workspace = workspace;
     r.packed = packed; r.thermal = thermal; r.tmasks = thermal_masks;
     r.Ho = Ho; r.Wo = Wo; r.H = H; r.W = W; r.P = n_pairs; r.G = n_groups; r.K = ecc_model_params(model);
     r.opt = EccOptions{eps, min_valid, maxiter, 0};
-    r.group = reinterpret_cast<const int*>(ws + lay.group);
-    r.active = reinterpret_cast<const int*>(ws + lay.active);
-    r.offsets = reinterpret_cast<const int*>(ws + lay.offsets);
-    r.list = reinterpret_cast<const int*>(ws + lay.list);
-    r.tmask = reinterpret_cast<const int*>(ws + lay.tmask);
-    r.groups = reinterpret_cast<EccGroup*>(ws + lay.groups);
-    r.recs = reinterpret_cast<EccPairRec*>(ws + lay.recs);
-    r.quant = reinterpret_cast<double*>(ws + lay.quant);
-    r.partial = reinterpret_cast<double*>(ws + lay.partial);
-    launch_ecc_pooled_begin(init_transforms, thermal_masks, r.tmask, H * W, n_groups, n_pairs, r.groups, r.recs, s);
+    launch_ecc_pooled_begin(init_transforms, thermal_masks, r.w.tmask, H * W, n_groups, n_pairs, r.w.groups, r.w.recs, s);
     h->ecc_pooled = r;
     return launch_status(h);
 }
@@ -215,20 +192,20 @@ int mp_ecc_pooled_step(mp_handle* h, void* workspace, int n_iters, int* live, vo
 {
     if (!h) return MP_EINVAL;
     if (!workspace || !live) return fail(h, MP_EINVAL, "mp_ecc_pooled_step: NULL tensor");
-    if (!h->ecc_pooled.workspace || h->ecc_pooled.workspace != workspace)
-        return fail(h, MP_ESTATE, "mp_ecc_pooled_step: no pooled refinement was begun in this workspace");
+    if (const int rc = begun_in(h, "mp_ecc_pooled_step", h->ecc_pooled.workspace, workspace)) return rc;
     if (n_iters < 1 || n_iters > 100000) return fail(h, MP_EINVAL, "mp_ecc_pooled_step: n_iters must be in [1, 100000]");
     MP_HIP(hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const EccPooledRefine& r = h->ecc_pooled;
+    const EccPooledWorkspace& w = r.w;
     const int chunks = ecc_chunks(r.H, r.W);
     for (int i = 0; i < n_iters; ++i) {
-        launch_ecc_pooled_sums(r.K, r.packed, r.Ho, r.Wo, r.thermal, r.H, r.W, r.tmasks, r.tmask, r.group, r.active, nullptr, r.groups,
-                               r.P, r.partial, s);
-        launch_ecc_pooled_pair(r.K, r.partial, r.P, chunks, r.group, r.active, r.opt, r.groups, r.recs, r.quant, s);
-        launch_ecc_pooled_solve(r.K, r.offsets, r.list, r.recs, r.quant, r.G, r.opt, r.groups, s);
+        launch_ecc_pooled_sums(r.K, r.packed, r.Ho, r.Wo, r.thermal, r.H, r.W, r.tmasks, w.tmask, w.group, w.active, nullptr, w.groups,
+                               r.P, w.partial, s);
+        launch_ecc_pooled_pair(r.K, w.partial, r.P, chunks, w.group, w.active, r.opt, w.groups, w.recs, w.quant, s);
+        launch_ecc_pooled_solve(r.K, w.offsets, w.list, w.recs, w.quant, r.G, r.opt, w.groups, s);
     }
-    launch_ecc_pooled_live(r.groups, r.G, live, s);
+    launch_ecc_pooled_live(w.groups, r.G, live, s);
     return launch_status(h);
 }
 
@@ -238,11 +215,10 @@ int mp_ecc_pooled_result(mp_handle* h, void* workspace, double* transforms, doub
     if (!h) return MP_EINVAL;
     if (!workspace || !transforms || !rho || !iterations || !status || !converged || !n_included || !rho_pair || !n_pair || !included)
         return fail(h, MP_EINVAL, "mp_ecc_pooled_result: NULL tensor");
-    if (!h->ecc_pooled.workspace || h->ecc_pooled.workspace != workspace)
-        return fail(h, MP_ESTATE, "mp_ecc_pooled_result: no pooled refinement was begun in this workspace");
+    if (const int rc = begun_in(h, "mp_ecc_pooled_result", h->ecc_pooled.workspace, workspace)) return rc;
     MP_HIP(hipSetDevice(h->device));
     const EccPooledRefine& r = h->ecc_pooled;
-    launch_ecc_pooled_result(r.groups, r.G, r.recs, r.P, transforms, rho, iterations, status, converged, n_included, rho_pair, n_pair,
+    launch_ecc_pooled_result(r.w.groups, r.G, r.w.recs, r.P, transforms, rho, iterations, status, converged, n_included, rho_pair, n_pair,
                              included, static_cast<hipStream_t>(stream));
     return launch_status(h);
 }

@@ -82,8 +82,18 @@ constexpr long long POOLED_MAX_N = 1ll << 24;
 
 // the workspace is scratch without state between calls: pooling uses pair_cnt [P] int, the estimate counts [G][T] uint32 |
 // best [G] uint64 (16-byte aligned), both from its start
-size_t pooled_best_offset(int G, int T) { return (((size_t)G * T * sizeof(unsigned int)) + 15) & ~(size_t)15; }
-size_t pooled_find_bytes(int G, int T) { return pooled_best_offset(G, T) + (size_t)G * sizeof(unsigned long long); }
+// the pooled RANSAC's inlier counts of T hypotheses per group, and behind them (on a multiple of 16 bytes) each group's best
+struct PooledFindWorkspace { unsigned int* counts; unsigned long long* best; size_t bytes; };
+PooledFindWorkspace pooled_find_workspace(void* base, int G, int T)
+{
+    Carver c(base, 16);
+    PooledFindWorkspace w{};
+    w.counts = c.take<unsigned int>((size_t)G * T);
+    c.align = alignof(unsigned long long);
+    w.best = c.take<unsigned long long>(G);
+    w.bytes = c.bytes();
+    return w;
+}
 size_t pooled_pool_bytes(int P) { return (size_t)P * sizeof(int); }
 
 // the checks the four pooled entries share, after the handle's
@@ -95,7 +105,7 @@ int pooled_check(mp_handle* h, const std::string& fn, int model, const float* pt
     if (N < 0 || N >= POOLED_MAX_N) return fail(h, MP_EINVAL, fn + ": need 0 <= N < 2^24 correspondences per call");
     if (N > 0 && (!pts || !inlier_mask)) return fail(h, MP_EINVAL, fn + ": NULL tensor");
     if ((reinterpret_cast<uintptr_t>(pts) & 15) != 0) return fail(h, MP_EINVAL, fn + ": pts must be 16-byte aligned");
-    if (G <= 0 || G > 65535) return fail(h, MP_EINVAL, fn + ": need 0 < G <= 65535 groups");
+    if (!count_ok(G)) return fail(h, MP_EINVAL, fn + ": need 0 < G <= 65535 groups");
     if (!(reproj_threshold > 0.0)) return fail(h, MP_EINVAL, fn + ": threshold must be positive");
     return MP_OK;
 }
@@ -109,19 +119,18 @@ int pooled_find(mp_handle* h, const std::string& fn, int model, const float* pts
     const int rc = pooled_check(h, fn, model, pts, group_offsets, N, G, reproj_threshold, transform, inlier_mask, n_inliers);
     if (rc) return rc;
     if (max_iters <= 0 || max_iters > (1 << 20)) return fail(h, MP_EINVAL, fn + ": max_iters must be in [1, 2^20]");
-    if (!workspace || workspace_bytes < (long long)pooled_find_bytes(G, max_iters))
+    const PooledFindWorkspace w = pooled_find_workspace(workspace, G, max_iters);
+    if (!workspace || workspace_bytes < (long long)w.bytes)
         return fail(h, MP_EINVAL, fn + ": workspace smaller than mp_pooled_workspace_bytes");
     hipStream_t s = static_cast<hipStream_t>(stream);
     MP_HIP(hipSetDevice(h->device));
-    unsigned int* counts = static_cast<unsigned int*>(workspace);
-    unsigned long long* best = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + pooled_best_offset(G, max_iters));
-    MP_HIP(hipMemsetAsync(counts, 0, (size_t)G * max_iters * sizeof(unsigned int), s));
+    MP_HIP(hipMemsetAsync(w.counts, 0, (size_t)G * max_iters * sizeof(unsigned int), s));
     if (N > 0) MP_HIP(hipMemsetAsync(inlier_mask, 0, (size_t)N, s));
     if (model == MP_MODEL_HOMOGRAPHY)
-        launch_find_homography_pooled(pts, group_offsets, (int)N, G, max_iters, reproj_threshold, seed, counts, best, transform,
+        launch_find_homography_pooled(pts, group_offsets, (int)N, G, max_iters, reproj_threshold, seed, w.counts, w.best, transform,
                                       inlier_mask, n_inliers, s);
     else
-        launch_find_transform_pooled(model, pts, group_offsets, (int)N, G, max_iters, reproj_threshold, seed, counts, best, transform,
+        launch_find_transform_pooled(model, pts, group_offsets, (int)N, G, max_iters, reproj_threshold, seed, w.counts, w.best, transform,
                                      inlier_mask, n_inliers, s);
     return launch_status(h);
 }
@@ -157,7 +166,7 @@ int pool_matches(mp_handle* h, const std::string& fn, const KP* kp_yx, const int
     if (!kp_yx || !kp_count || !match_idx || !pair_offsets || !group_offsets)
         return fail(h, MP_EINVAL, fn + ": NULL tensor");
     if (P <= 0 || K <= 0 || (long long)P * K > 0x7fffffffLL) return fail(h, MP_EINVAL, fn + ": need P > 0, K > 0 and P * K < 2^31");
-    if (G <= 0 || G > 65535) return fail(h, MP_EINVAL, fn + ": need 0 < G <= 65535 groups");
+    if (!count_ok(G)) return fail(h, MP_EINVAL, fn + ": need 0 < G <= 65535 groups");
     if (!groups && G != 1) return fail(h, MP_EINVAL, fn + ": without group ids there is one group (G = 1)");
     if (capacity < 0 || (capacity > 0 && (!pts || !query_index))) return fail(h, MP_EINVAL, fn + ": NULL tensor");
     if ((reinterpret_cast<uintptr_t>(pts) & 15) != 0) return fail(h, MP_EINVAL, fn + ": pts must be 16-byte aligned");
@@ -248,8 +257,8 @@ int mp_pooled_chunk(int* chunk_points, int* max_splits)
 
 int mp_pooled_workspace_bytes(int P, int G, int max_iters, long long* bytes)
 {
-    if (!bytes || P < 0 || G <= 0 || G > 65535 || max_iters <= 0 || max_iters > (1 << 20)) return MP_EINVAL;
-    *bytes = (long long)std::max(pooled_pool_bytes(P), pooled_find_bytes(G, max_iters));
+    if (!bytes || P < 0 || !count_ok(G) || max_iters <= 0 || max_iters > (1 << 20)) return MP_EINVAL;
+    *bytes = (long long)std::max(pooled_pool_bytes(P), pooled_find_workspace(nullptr, G, max_iters).bytes);
     return MP_OK;
 }
 

@@ -18,6 +18,7 @@
 //   No atomics; ordinary per-lane vector stores only.
 #include "../../include/multipoint_hip.h"
 #include "mp_common.h"
+#include "mp_device.h"
 
 #pragma clang fp contract(off)
 
@@ -26,16 +27,6 @@ namespace {
 constexpr int FIT_THREADS = 512, FIT_WAVES = FIT_THREADS / MP_WAVE, FIT_RED = 6;
 constexpr int FIT_LDS_NODES = 8192;                                  // 128 KiB of search direction
 constexpr double BIG = 1.7976931348623157e308;
-
-__device__ __forceinline__ bool finite64(double v) { return fabs(v) <= BIG; }
-
-__device__ __forceinline__ double wave_add(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // v[k] <- the sum of v[k] over the workgroup, the same bits in every thread.  Two buffers take turns, so one barrier is enough: a
 // buffer is written again two sums later, behind the barrier of the sum in between.
 template <int K>

@@ -6,10 +6,8 @@ using namespace mp_host;
 
 namespace {
 
-bool is_finite(double v) { return std::fabs(v) <= 1.7976931348623157e308; }
-bool lattice_ok(int gy, int gx) { return gy >= 1 && gy <= MP_FIELD_MAX_SIDE && gx >= 1 && gx <= MP_FIELD_MAX_SIDE; }
+bool lattice_ok(int gy, int gx) { return sides_ok(gy, gx, 1, MP_FIELD_MAX_SIDE); }
 long long fit_workspace_bytes(int B, int gy, int gx) { return (long long)B * gy * gx * MP_FIELD_WS_DOUBLES * (long long)sizeof(double); }
-bool frame_ok(int H, int W) { return H >= 8 && W >= 8 && H <= 4096 && W <= 4096; }
 
 }  // namespace
 
@@ -17,7 +15,7 @@ extern "C" {
 
 int mp_field_fit_workspace(int B, int gy, int gx, long long* bytes)
 {
-    if (!bytes || B < 1 || B > 65535 || !lattice_ok(gy, gx)) return MP_EINVAL;
+    if (!bytes || !count_ok(B) || !lattice_ok(gy, gx)) return MP_EINVAL;
     *bytes = fit_workspace_bytes(B, gy, gx);
     return MP_OK;
 }
@@ -28,18 +26,17 @@ int mp_field_fit(mp_handle* h, const double* d, const double* weight, int B, int
 {
     if (!h) return MP_EINVAL;
     if (!d || !weight || !workspace || !out_u || !out_info || !out_res) return fail(h, MP_EINVAL, "mp_field_fit: NULL tensor");
-    if (B < 1 || B > 65535) return fail(h, MP_EINVAL, "mp_field_fit: B must be in [1, 65535]");
+    if (!count_ok(B)) return fail(h, MP_EINVAL, "mp_field_fit: B must be in [1, 65535]");
     if (!lattice_ok(gy, gx))
         return fail(h, MP_EINVAL, "mp_field_fit: the lattice sides must be in [1, " + std::to_string(MP_FIELD_MAX_SIDE) + "]");
-    if (!(lambda > 0.0) || !is_finite(lambda)) return fail(h, MP_EINVAL, "mp_field_fit: lambda must be positive and finite");
-    if (!(robust_px >= 0.0) || !is_finite(robust_px)) return fail(h, MP_EINVAL, "mp_field_fit: robust_px must be finite and not negative");
-    if (!(tol >= 0.0) || !is_finite(tol)) return fail(h, MP_EINVAL, "mp_field_fit: tol must be finite and not negative");
+    if (!(lambda > 0.0) || !finite64(lambda)) return fail(h, MP_EINVAL, "mp_field_fit: lambda must be positive and finite");
+    if (!(robust_px >= 0.0) || !finite64(robust_px)) return fail(h, MP_EINVAL, "mp_field_fit: robust_px must be finite and not negative");
+    if (!(tol >= 0.0) || !finite64(tol)) return fail(h, MP_EINVAL, "mp_field_fit: tol must be finite and not negative");
     if (rounds < 0 || rounds > MP_FIELD_MAX_ROUNDS)
         return fail(h, MP_EINVAL, "mp_field_fit: rounds must be in [0, " + std::to_string(MP_FIELD_MAX_ROUNDS) + "]");
     if (max_iter < 1 || max_iter > (1 << 20)) return fail(h, MP_EINVAL, "mp_field_fit: max_iter must be in [1, 2^20]");
-    if (workspace_bytes < fit_workspace_bytes(B, gy, gx))
-        return fail(h, MP_EINVAL, "mp_field_fit: the workspace holds " + std::to_string(workspace_bytes) + " bytes, " +
-                                      std::to_string(fit_workspace_bytes(B, gy, gx)) + " are needed (mp_field_fit_workspace)");
+    if (const int rc = need_workspace(h, "mp_field_fit", workspace_bytes, (size_t)fit_workspace_bytes(B, gy, gx), "mp_field_fit_workspace"))
+        return rc;
     if (reinterpret_cast<uintptr_t>(workspace) % 16) return fail(h, MP_EINVAL, "mp_field_fit: the workspace must be 16-byte aligned");
     // out_u is the solver's working vector and is zeroed before d is read again; out_w is written while the inputs may be in use
     const void* outs[] = {out_u, out_info, out_res, out_w, workspace};
@@ -64,12 +61,12 @@ int mp_field_warp(mp_handle* h, const float* src, int n_src, int Hs, int Ws, con
 {
     if (!h) return MP_EINVAL;
     if (!src || !u || !dst) return fail(h, MP_EINVAL, "mp_field_warp: NULL tensor");
-    if (B < 1 || B > 65535) return fail(h, MP_EINVAL, "mp_field_warp: B must be in [1, 65535]");
+    if (!count_ok(B)) return fail(h, MP_EINVAL, "mp_field_warp: B must be in [1, 65535]");
     if (n_src != 1 && n_src != B) return fail(h, MP_EINVAL, "mp_field_warp: src holds one frame or one per output frame");
-    if (!frame_ok(H, W) || !frame_ok(Hs, Ws)) return fail(h, MP_EINVAL, "mp_field_warp: frames must be 8 x 8 to 4096 x 4096");
+    if (!sides_ok(H, W, 8, 4096) || !sides_ok(Hs, Ws, 8, 4096)) return fail(h, MP_EINVAL, "mp_field_warp: frames must be 8 x 8 to 4096 x 4096");
     if (!lattice_ok(gy, gx))
         return fail(h, MP_EINVAL, "mp_field_warp: the lattice sides must be in [1, " + std::to_string(MP_FIELD_MAX_SIDE) + "]");
-    if (!is_finite(y0) || !is_finite(x0) || !(step > 0.0) || !is_finite(step))
+    if (!finite64(y0) || !finite64(x0) || !(step > 0.0) || !finite64(step))
         return fail(h, MP_EINVAL, "mp_field_warp: the lattice origin must be finite and its step positive and finite");
     if (extrapolate != 0 && extrapolate != 1) return fail(h, MP_EINVAL, "mp_field_warp: extrapolate is 0 (clamp) or 1 (linear)");
     if (static_cast<const void*>(src) == static_cast<const void*>(dst)) return fail(h, MP_EINVAL, "mp_field_warp: src and dst are one buffer");

@@ -7,8 +7,6 @@ using namespace mp_host;
 
 namespace {
 
-bool frame_ok(int n, int H, int W) { return n > 0 && n <= 65535 && H > 0 && W > 0 && H <= 32767 && W <= 32767; }
-
 constexpr long long MAX_PIXELS = 1LL << 38;      // per call: the flat pixel index of a launch stays below 2^31 blocks
 
 bool aligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
@@ -39,7 +37,7 @@ int mp_undistort(mp_handle* h, const void* src, int dtype, int n, int H, int W, 
         return fail(h, MP_EINVAL, "mp_undistort: dtype must be MP_FRAMES_BGR8 or MP_FRAMES_U16");
     if (n_coeffs != 4 && n_coeffs != 5)
         return fail(h, MP_EINVAL, "mp_undistort: 4 or 5 distortion coefficients (k1, k2, p1, p2[, k3]), got " + std::to_string(n_coeffs));
-    if (!frame_ok(n, H, W) || (long long)n * H * W > MAX_PIXELS)
+    if (!frames_ok(n, H, W, 1, 32767) || (long long)n * H * W > MAX_PIXELS)
         return fail(h, MP_EINVAL, "mp_undistort: 1 to 65535 frames of 1 x 1 to 32767 x 32767 pixels, at most 2^38 pixels per call");
     if (!aligned(dst, 4)) return fail(h, MP_EINVAL, "mp_undistort: dst must be 4-byte aligned");
     FramesCamera c{};
@@ -60,7 +58,7 @@ int mp_resize_bgr8(mp_handle* h, const unsigned char* src, int n, int H, int W, 
     if (!h) return MP_EINVAL;
     if (!src || !dst) return fail(h, MP_EINVAL, "mp_resize_bgr8: NULL tensor");
     if (src == dst) return fail(h, MP_EINVAL, "mp_resize_bgr8: src and dst must be different buffers");
-    if (!frame_ok(n, H, W) || !frame_ok(n, oh, ow) || (long long)n * oh * ow > MAX_PIXELS)
+    if (!frames_ok(n, H, W, 1, 32767) || !frames_ok(n, oh, ow, 1, 32767) || (long long)n * oh * ow > MAX_PIXELS)
         return fail(h, MP_EINVAL, "mp_resize_bgr8: 1 to 65535 frames, source and destination of 1 x 1 to 32767 x 32767 pixels");
     if (!aligned(dst, 4)) return fail(h, MP_EINVAL, "mp_resize_bgr8: dst must be 4-byte aligned");
     MP_HIP(hipSetDevice(h->device));
@@ -70,7 +68,7 @@ int mp_resize_bgr8(mp_handle* h, const unsigned char* src, int n, int H, int W, 
 
 int mp_thermal_rescale_workspace_bytes(int n, long long* bytes)
 {
-    if (!bytes || n <= 0 || n > 65535) return MP_EINVAL;
+    if (!bytes || !count_ok(n)) return MP_EINVAL;
     *bytes = (long long)thermal_rescale_workspace_bytes(n);
     return MP_OK;
 }
@@ -80,14 +78,12 @@ int mp_thermal_rescale(mp_handle* h, const unsigned short* in, int n, int H, int
 {
     if (!h) return MP_EINVAL;
     if (!in || !rescaled || !workspace) return fail(h, MP_EINVAL, "mp_thermal_rescale: NULL tensor");
-    if (!frame_ok(n, H, W)) return fail(h, MP_EINVAL, "mp_thermal_rescale: 1 to 65535 frames of 1 x 1 to 32767 x 32767 pixels");
+    if (!frames_ok(n, H, W, 1, 32767)) return fail(h, MP_EINVAL, "mp_thermal_rescale: 1 to 65535 frames of 1 x 1 to 32767 x 32767 pixels");
     if (saved && (saved == in || saved == clipped)) return fail(h, MP_EINVAL, "mp_thermal_rescale: saved must be a buffer of its own");
     if (!aligned(in, 2) || !aligned(clipped, 2) || !aligned(saved, 2) || !aligned(rescaled, 4) || !aligned(workspace, 16))
         return fail(h, MP_EINVAL, "mp_thermal_rescale: misaligned tensor (workspace: 16 bytes)");
-    const long long need = (long long)thermal_rescale_workspace_bytes(n);
-    if (workspace_bytes < need)
-        return fail(h, MP_EINVAL, "mp_thermal_rescale: workspace of " + std::to_string(workspace_bytes) + " B, needs " +
-                                      std::to_string(need) + " B (mp_thermal_rescale_workspace_bytes)");
+    const size_t need = thermal_rescale_workspace_bytes(n);
+    if (const int rc = need_workspace(h, "mp_thermal_rescale", workspace_bytes, need, "mp_thermal_rescale_workspace_bytes")) return rc;
     const long long N = (long long)H * W;
     FramesRanks rk{};
     if (outlier_rejection) {
@@ -98,7 +94,7 @@ int mp_thermal_rescale(mp_handle* h, const unsigned short* in, int n, int H, int
         rk.rank[2] = rk.rank[3] = N - 1;
     }
     MP_HIP(hipSetDevice(h->device));
-    MP_HIP(hipMemsetAsync(workspace, 0, (size_t)need, static_cast<hipStream_t>(stream)));
+    MP_HIP(hipMemsetAsync(workspace, 0, need, static_cast<hipStream_t>(stream)));
     launch_thermal_rescale(in, n, H, W, rk, clipped, rescaled, saved, workspace, static_cast<hipStream_t>(stream));
     return launch_status(h);
 }

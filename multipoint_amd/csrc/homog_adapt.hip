@@ -13,6 +13,7 @@
 //  * finalize_kernel        prob / count, sqrt or * 0.5 for the two-spectra aggregations, min_count   (:115-127, :182-187)
 //  * gaussian_filter_kernel ReflectionPad2d + k x k depthwise filter (:55-58, utils.py:124-160)
 #include "mp_common.h"
+#include "mp_device.h"
 
 namespace {
 
@@ -117,16 +118,6 @@ __device__ __forceinline__ int cv_border_101(int p, int len)
     return p;
 }
 
-// Every product and sum below is rounded separately, as OpenCV's scalar code does: contraction is switched off for the
-// two functions (hipcc's __dmul_rn / __fadd_rn wrappers are inline operators that carry their own `contract` flag).
-__device__ __forceinline__ int cv_fixed_coord(double num, double w)
-{
-#pragma clang fp contract(off)
-    double f = num * w;
-    f = fmax(-2147483648.0, fmin(2147483647.0, f));
-    return (int)rint(f);
-}
-
 template <int BORDER>   // 0 BORDER_CONSTANT (value 0), 1 BORDER_REFLECT_101
 __global__ __launch_bounds__(256) void cv_warp_linear_kernel(const float* __restrict__ src, int H, int W,
                                                              const double* __restrict__ hom_inv, int bw0,
@@ -139,19 +130,8 @@ __global__ __launch_bounds__(256) void cv_warp_linear_kernel(const float* __rest
     if (x >= W || y >= H) return;
     const Hom h = load_hom(hom_inv + (size_t)n * 9);
     const float* img = src + (size_t)n * H * W;
-    const int xb = (x / bw0) * bw0;
-    const double dxb = (double)xb, dx1 = (double)(x - xb), dy = (double)y;
-    const double X0 = (h.m[0] * dxb + h.m[1] * dy) + h.m[2];
-    const double Y0 = (h.m[3] * dxb + h.m[4] * dy) + h.m[5];
-    const double W0 = (h.m[6] * dxb + h.m[7] * dy) + h.m[8];
-    double w = W0 + h.m[6] * dx1;
-    w = w != 0.0 ? 32.0 / w : 0.0;
-    const int X = cv_fixed_coord(X0 + h.m[0] * dx1, w);
-    const int Y = cv_fixed_coord(Y0 + h.m[3] * dx1, w);
-    const int sx = max(-32768, min(32767, X >> 5)), sy = max(-32768, min(32767, Y >> 5));
-    const float fx = (float)(X & 31) * (1.f / 32.f), fy = (float)(Y & 31) * (1.f / 32.f);
-    const float ax = 1.f - fx, ay = 1.f - fy;
-    const float w0 = ay * ax, w1 = ay * fx, w2 = fy * ax, w3 = fy * fx;
+    const CvWarpSource c = cv_warp_source(h.m, x, y, bw0);
+    const int sx = c.sx, sy = c.sy;
     float v0, v1, v2, v3;
     if (BORDER == 0) {
         const bool xa = (unsigned)sx < (unsigned)W, xc = (unsigned)(sx + 1) < (unsigned)W;
@@ -166,7 +146,7 @@ __global__ __launch_bounds__(256) void cv_warp_linear_kernel(const float* __rest
         v0 = img[(size_t)ya * W + xa]; v1 = img[(size_t)ya * W + xc];
         v2 = img[(size_t)yc * W + xa]; v3 = img[(size_t)yc * W + xc];
     }
-    const float p0 = v0 * w0, p1 = v1 * w1, p2 = v2 * w2, p3 = v3 * w3;
+    const float p0 = v0 * c.w0, p1 = v1 * c.w1, p2 = v2 * c.w2, p3 = v3 * c.w3;
     dst[((size_t)n * H + y) * W + x] = ((p0 + p1) + p2) + p3;
 }
 

@@ -4,6 +4,7 @@
 #pragma once
 #include "../../include/multipoint_hip.h"
 #include "mp_common.h"
+#include "mp_workspace.h"
 
 #include <cmath>
 #include <cstdio>
@@ -91,43 +92,70 @@ struct ConvPolicy {
     int splitk_max = 8;             // most ranges the input channels of a small launch are cut into (1: never)
 };
 
-// the refinement mp_mi_refine_begin started: where its pieces lie in the caller's workspace (align_api.hip)
+// the arrays of a mutual-information call in the caller's workspace (mi_workspace() in align_api.hip)
+struct MiWorkspace {
+    MiEval* ev;
+    int2* slots;
+    int* nact;
+    double* M;
+    unsigned *keys, *tkeys;
+    unsigned short* tmap;
+    float* warped;
+    unsigned* counts;
+    double *smooth_a, *smooth_b, *part, *rowsum, *colpart, *values, *cand, *candp;
+    MiNmState* state;
+    MiNmOptions* opts;
+    double* tinit;
+    int* live;
+    size_t bytes;
+};
+
+// the refinement mp_mi_refine_begin started (align_api.hip)
 struct MiRefine {
     void* workspace = nullptr;
+    MiWorkspace w{};
     MiLaunch L{};
     int P = 0, normalized = 0;
-    int model = 0;                        // MP_MODEL_*: what the candidate points in candp parametrise
+    int model = 0;                        // MP_MODEL_*: what the candidate points in w.candp parametrise
     double sigma = 0.0;
     long long smooth_stride = 0;
-    unsigned* counts = nullptr;
-    float* warped = nullptr;
-    double *smooth_a = nullptr, *smooth_b = nullptr, *candp = nullptr, *cand = nullptr, *values = nullptr;
     const double* reg_init = nullptr;     // the matrices of the problems' start parameters when the objective is regularised
-    MiNmState* state = nullptr;
-    int* nact = nullptr;
+};
+
+// the arrays of an ECC call in the caller's workspace (ecc_workspace() in ecc_api.hip)
+struct EccWorkspace {
+    int* pair;
+    EccState* state;
+    double* partial;
+    size_t bytes;
 };
 
 // the refinement mp_ecc_begin started (ecc_api.hip)
 struct EccRefine {
     void* workspace = nullptr;
+    EccWorkspace w{};
     const float *packed = nullptr, *thermal = nullptr;
     int Ho = 0, Wo = 0, H = 0, W = 0, P = 0, K = 0;
     EccOptions opt{};
-    EccState* state = nullptr;
-    double* partial = nullptr;
+};
+
+// the arrays of a pooled ECC call in the caller's workspace (pooled_workspace() in ecc_pooled_api.hip)
+struct EccPooledWorkspace {
+    int *group, *active, *offsets, *list, *tmask;
+    EccGroup* groups;
+    EccPairRec* recs;
+    double *quant, *partial;
+    size_t bytes;
 };
 
 // the pooled refinement mp_ecc_pooled_begin started (ecc_pooled_api.hip)
 struct EccPooledRefine {
     void* workspace = nullptr;
+    EccPooledWorkspace w{};
     const float *packed = nullptr, *thermal = nullptr;
     const unsigned char* tmasks = nullptr;
     int Ho = 0, Wo = 0, H = 0, W = 0, P = 0, G = 0, K = 0;
     EccOptions opt{};
-    const int *group = nullptr, *active = nullptr, *offsets = nullptr, *list = nullptr, *tmask = nullptr;
-    EccGroup* groups = nullptr;
-    EccPairRec* recs = nullptr;
-    double *partial = nullptr, *quant = nullptr;
 };
 
 }  // namespace mp_host
@@ -223,6 +251,39 @@ inline int launch_status(mp_handle* h)
 {
     MP_HIP(hipGetLastError());
     return MP_OK;
+}
+
+// the most workgroups a launch takes in its grid's y and z: what bounds every batch count that becomes one
+constexpr int MAX_GRID_Y = 65535;
+
+inline bool count_ok(long long n) { return n >= 1 && n <= MAX_GRID_Y; }
+inline bool sides_ok(int H, int W, int lo, int hi) { return H >= lo && W >= lo && H <= hi && W <= hi; }
+inline bool frames_ok(int n, int H, int W, int lo, int hi) { return count_ok(n) && sides_ok(H, W, lo, hi); }
+
+// MP_OK when the caller's workspace holds what `sizer` says the call (or `who`, e.g. "one image ") needs
+inline int need_workspace(mp_handle* h, const std::string& fn, long long have, size_t need, const char* sizer, const char* who = "")
+{
+    if (have >= (long long)need) return MP_OK;
+    return fail(h, MP_EINVAL, fn + ": workspace of " + std::to_string(have) + " B, " + who + "needs " + std::to_string(need) + " B (" + sizer + ")");
+}
+
+// A workspace carved per image (LGHD, RIFT) runs a batch in chunks: the images a workspace of `have` bytes holds at once
+// (the caller has refused one that holds none), and launch(first image, images) over all B in chunks of that many
+inline int workspace_images(long long have, size_t per_image, int B)
+{
+    const long long n = have / (long long)per_image;
+    return (int)(n < B ? n : B);
+}
+template <class F> void for_image_chunks(int B, int chunk, F launch)
+{
+    for (int b0 = 0; b0 < B; b0 += chunk) launch((long long)b0, B - b0 < chunk ? B - b0 : chunk);
+}
+
+// MP_OK when `workspace` is the one the handle's running refinement was begun in (`begun`: that session's pointer)
+inline int begun_in(mp_handle* h, const char* fn, const void* begun, const void* workspace)
+{
+    if (begun && begun == workspace) return MP_OK;
+    return fail(h, MP_ESTATE, std::string(fn) + ": no refinement was begun in this workspace");
 }
 
 // the FFT's twiddle table of length n on the device, cached in the handle (lghd_api.hip)

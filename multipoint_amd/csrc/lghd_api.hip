@@ -26,9 +26,19 @@ namespace {
 
 int twiddles(mp_handle* h, int n, const float** table) { return fft_twiddle_table(h, n, table); }
 
-bool frame_ok(int B, int H, int W) { return B > 0 && B <= 65535 && H > 0 && W > 0 && H <= 32767 && W <= 32767; }
+// the spectrum and the 24 half-transformed complex planes of n images
+struct LghdWorkspace { float *spectrum, *tmp; size_t bytes; };
 
-size_t lghd_image_bytes(int H, int W) { return (size_t)25 * H * W * 2 * sizeof(float); }
+LghdWorkspace lghd_workspace(void* base, size_t n, int H, int W)
+{
+    const size_t HW = (size_t)H * W;
+    Carver c(base, alignof(float));
+    LghdWorkspace w{};
+    w.spectrum = c.take<float>(n * HW * 2);
+    w.tmp = c.take<float>(n * HW * 48);
+    w.bytes = c.bytes();
+    return w;
+}
 
 }  // namespace
 
@@ -44,7 +54,7 @@ int mp_fft2d(mp_handle* h, const float* in, float* out, int planes, int H, int W
 {
     if (!h) return MP_EINVAL;
     if (!in || !out) return fail(h, MP_EINVAL, "mp_fft2d: NULL tensor");
-    if (planes <= 0 || planes > 65535 || H <= 0 || W <= 0 || axes < 1 || axes > 3)
+    if (!count_ok(planes) || H <= 0 || W <= 0 || axes < 1 || axes > 3)
         return fail(h, MP_EINVAL, "mp_fft2d: need 0 < planes <= 65535, positive sizes and axes in {1, 2, 3}");
     if (((axes & 1) && !mp_fft_supported(W)) || ((axes & 2) && !mp_fft_supported(H)) || H > MP_FFT_MAX_N || W > MP_FFT_MAX_N)
         return fail(h, MP_EINVAL, "mp_fft2d: line lengths must be 2^a 3^b 5^c in [8, 4096]");
@@ -71,7 +81,7 @@ int mp_lghd_detect(mp_handle* h, const unsigned char* u8, int B, int H, int W, u
 {
     if (!h) return MP_EINVAL;
     if (!u8 || !score || !corners) return fail(h, MP_EINVAL, "mp_lghd_detect: NULL tensor");
-    if (!frame_ok(B, H, W)) return fail(h, MP_EINVAL, "mp_lghd_detect: need 0 < B <= 65535 and frames of at most 32767 x 32767");
+    if (!frames_ok(B, H, W, 1, 32767)) return fail(h, MP_EINVAL, "mp_lghd_detect: need 0 < B <= 65535 and frames of at most 32767 x 32767");
     MP_HIP(hipSetDevice(h->device));
     launch_lghd_detect(u8, B, H, W, score, corners, prob, static_cast<hipStream_t>(stream));
     return launch_status(h);
@@ -79,8 +89,8 @@ int mp_lghd_detect(mp_handle* h, const unsigned char* u8, int B, int H, int W, u
 
 int mp_lghd_workspace_bytes(int B, int H, int W, long long* bytes)
 {
-    if (!bytes || !frame_ok(B, H, W) || !mp_fft_supported(H) || !mp_fft_supported(W)) return MP_EINVAL;
-    *bytes = (long long)(lghd_image_bytes(H, W) * (size_t)(B < 4 ? B : 4));
+    if (!bytes || !frames_ok(B, H, W, 1, 32767) || !mp_fft_supported(H) || !mp_fft_supported(W)) return MP_EINVAL;
+    *bytes = (long long)lghd_workspace(nullptr, B < 4 ? B : 4, H, W).bytes;
     return MP_OK;
 }
 
@@ -89,28 +99,23 @@ int mp_lghd_orientation(mp_handle* h, const unsigned char* u8, const float* bank
 {
     if (!h) return MP_EINVAL;
     if (!u8 || !bank || !orientation || !workspace) return fail(h, MP_EINVAL, "mp_lghd_orientation: NULL tensor");
-    if (!frame_ok(B, H, W)) return fail(h, MP_EINVAL, "mp_lghd_orientation: need 0 < B <= 65535");
+    if (!frames_ok(B, H, W, 1, 32767)) return fail(h, MP_EINVAL, "mp_lghd_orientation: need 0 < B <= 65535");
     if (!mp_fft_supported(H) || !mp_fft_supported(W))
         return fail(h, MP_EINVAL, "mp_lghd_orientation: frame of " + std::to_string(H) + " x " + std::to_string(W) +
                                       ": both sizes must be 2^a 3^b 5^c in [8, 4096]");
-    const long long per = (long long)lghd_image_bytes(H, W);
-    long long chunk = workspace_bytes / per;
-    if (chunk < 1)
-        return fail(h, MP_EINVAL, "mp_lghd_orientation: workspace of " + std::to_string(workspace_bytes) + " B, one image needs " +
-                                      std::to_string(per) + " B (mp_lghd_workspace_bytes)");
-    if (chunk > B) chunk = B;
+    const size_t per = lghd_workspace(nullptr, 1, H, W).bytes;
+    int rc = need_workspace(h, "mp_lghd_orientation", workspace_bytes, per, "mp_lghd_workspace_bytes", "one image ");
+    if (rc != MP_OK) return rc;
+    const int chunk = workspace_images(workspace_bytes, per, B);
     MP_HIP(hipSetDevice(h->device));
     const float *tr = nullptr, *tc = nullptr;
-    int rc;
     if ((rc = twiddles(h, W, &tr)) || (rc = twiddles(h, H, &tc))) return rc;
     const long long HW = (long long)H * W;
-    float* spectrum = static_cast<float*>(workspace);
-    float* tmp = spectrum + chunk * HW * 2;
-    for (long long b0 = 0; b0 < B; b0 += chunk) {
-        const int nb = (int)(B - b0 < chunk ? B - b0 : chunk);
-        launch_lghd_orientation(u8 + b0 * HW, bank, nb, H, W, spectrum, tmp, orientation + b0 * 4 * HW, tr, tc,
+    const LghdWorkspace w = lghd_workspace(workspace, chunk, H, W);
+    for_image_chunks(B, chunk, [&](long long b0, int nb) {
+        launch_lghd_orientation(u8 + b0 * HW, bank, nb, H, W, w.spectrum, w.tmp, orientation + b0 * 4 * HW, tr, tc,
                                 static_cast<hipStream_t>(stream));
-    }
+    });
     return launch_status(h);
 }
 
@@ -119,7 +124,7 @@ int mp_lghd_describe(mp_handle* h, const unsigned char* orientation, int B, int 
 {
     if (!h) return MP_EINVAL;
     if (!orientation || !kp_yx || !kp_count || (!raw && !unit)) return fail(h, MP_EINVAL, "mp_lghd_describe: NULL tensor");
-    if (!frame_ok(B, H, W) || K <= 0) return fail(h, MP_EINVAL, "mp_lghd_describe: need 0 < B <= 65535, K > 0");
+    if (!frames_ok(B, H, W, 1, 32767) || K <= 0) return fail(h, MP_EINVAL, "mp_lghd_describe: need 0 < B <= 65535, K > 0");
     MP_HIP(hipSetDevice(h->device));
     launch_lghd_describe(orientation, B, H, W, kp_yx, kp_count, K, raw, unit, static_cast<hipStream_t>(stream));
     return launch_status(h);

@@ -20,6 +20,7 @@
 //                         bit-identical from run to run (no float atomics anywhere).
 #include "mp_common.h"
 #include "mp_device.h"
+#include "mp_workspace.h"
 
 namespace {
 
@@ -579,8 +580,6 @@ __global__ __launch_bounds__(RED) void desc_loss_grad_kernel(const float* __rest
     }
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct LossWorkspace {
     float4* cells;          // [2][B][N]       warped centre (y, x), validity
     float* tile_part;       // [B][T][3]       per-tile positive, negative, corresponding pairs
@@ -594,15 +593,14 @@ LossWorkspace loss_workspace(void* base, int B, int H, int W)
 {
     const long long N = (long long)(H >> 3) * (W >> 3);
     const long long nt = (N + LT - 1) / LT, T = nt * nt, nblk = (N + RED - 1) / RED;
-    char* p = static_cast<char*>(base);
+    Carver c(base);
     LossWorkspace w;
-    size_t off = 0;
-    w.cells = reinterpret_cast<float4*>(p + off);   off += align256(sizeof(float4) * 2 * B * N);
-    w.tile_part = reinterpret_cast<float*>(p + off); off += align256(sizeof(float) * 3 * B * T);
-    w.cnt_part = reinterpret_cast<int*>(p + off);    off += align256(sizeof(int) * 2 * B * nblk);
-    w.det_sum = reinterpret_cast<float*>(p + off);   off += align256(sizeof(float) * B * nblk);
-    w.det_cnt = reinterpret_cast<int*>(p + off);     off += align256(sizeof(int) * B * nblk);
-    w.bytes = off;
+    w.cells = c.take<float4>(2 * B * N);
+    w.tile_part = c.take<float>(3 * B * T);
+    w.cnt_part = c.take<int>(2 * B * nblk);
+    w.det_sum = c.take<float>(B * nblk);
+    w.det_cnt = c.take<int>(B * nblk);
+    w.bytes = c.bytes();
     return w;
 }
 

@@ -73,66 +73,17 @@ struct RadiusGate {
     }
 };
 
-// nn_rows_kernel (match_mfma.hip) behind the gate: best[x] = min over the GATED y of (dist(x, y) bits << 32 | y), NO_KEY for a
-// row without candidates.  grid: (row-block groups, pairs, 2 directions x column shares)
-template <int D>
-__global__ __launch_bounds__(256) void guided_rows_kernel(const float* __restrict__ dA, const int* __restrict__ nA,
-                                                         const float* __restrict__ dB, const int* __restrict__ nB,
-                                                         long long pair_stride, int count_stride, int K,
-                                                         const float* __restrict__ pos, float r2,
-                                                         unsigned long long* __restrict__ bestA,
-                                                         unsigned long long* __restrict__ bestB, int* __restrict__ match_count,
-                                                         int nsplit)
-{
-    // (the pair's match counter, which guided_mutual_kernel adds to behind this launch, is zeroed here)
-    if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0) match_count[blockIdx.y] = 0;
-    const int p = blockIdx.y, dir = blockIdx.z & 1, share = blockIdx.z >> 1;
-    const float* X = (dir == 0 ? dA : dB) + (long long)p * pair_stride;
-    const float* Y = (dir == 0 ? dB : dA) + (long long)p * pair_stride;
-    const int nx = min((dir == 0 ? nA : nB)[p * count_stride], K);
-    const int ny = min((dir == 0 ? nB : nA)[p * count_stride], K);
-    const float2* xpos = reinterpret_cast<const float2*>(pos) + ((long long)dir * gridDim.y + p) * K;
-    const float2* ypos = reinterpret_cast<const float2*>(pos) + ((long long)(dir ^ 1) * gridDim.y + p) * K;
-    unsigned long long* best = (dir == 0 ? bestA : bestB) + ((long long)share * gridDim.y + p) * K;
-    const ColumnShare cs = column_share(ny, share, nsplit);
-    if ((int)blockIdx.x * 128 >= nx) return;             // (the whole workgroup)
-    const int lane = threadIdx.x & 63, li = lane & 31, half = lane >> 5;
-    const int r0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 32;
-    KeepNearest keep;
-    RadiusGate gate{ypos, xpos[min(r0 + li, nx - 1)], r2, dir == 0, {}};
-    if (!walk_tiles<D>(X, Y, nx, ny, cs.c_begin, cs.c_end, r0, li, half, keep, gate)) return;
-    // the two half-waves hold the two halves of the row's columns
-    const unsigned long long o = __shfl_xor(keep.run, 32);
-    const int row = r0 + li;
-    if (half == 0 && row < nx) best[row] = o < keep.run ? o : keep.run;
-}
-
-// mutual_kernel (match_mfma.hip) where a row or a column may have no candidate
-__global__ __launch_bounds__(256) void guided_mutual_kernel(const unsigned long long* __restrict__ bestA,
-                                                           const unsigned long long* __restrict__ bestB,
-                                                           const int* __restrict__ nA, const int* __restrict__ nB,
-                                                           int count_stride, int K, float thr,
-                                                           int* __restrict__ match_idx, float* __restrict__ match_dist,
-                                                           int* __restrict__ match_count, int nsplit)
-{
-    const int na = min(nA[blockIdx.y * count_stride], K), nb = min(nB[blockIdx.y * count_stride], K);
-    write_matches(K, match_idx, match_dist, match_count, nullptr, nullptr, [&](int p, int i) {
-        RowMatch m;
-        if (i < na && nb > 0) {
-            unsigned long long v, w, unused;
-            merge_shares<1>(bestA, (long long)p * K + i, K, nsplit, v, unused);
-            if (v != NO_KEY) {
-                const int jj = (int)(v & 0xffffffffu);
-                m.d = __uint_as_float((unsigned)(v >> 32));
-                merge_shares<1>(bestB, (long long)p * K + jj, K, nsplit, w, unused);
-                const bool mutual = (int)(w & 0xffffffffu) == i;      // (i is in j's gate, so w is a key)
-                const bool close = (thr < 0.f) || (m.d < thr);
-                if (mutual && close) m.j = jj;
-            }
-        }
-        return m;
-    });
-}
+// what nn_rows_kernel (mp_match.h) builds the gate from
+struct RadiusGateArgs {
+    const float* pos;
+    float r2;
+    __device__ __forceinline__ RadiusGate gate(int dir, int p, int K, int row) const
+    {
+        const float2* xpos = reinterpret_cast<const float2*>(pos) + ((long long)dir * gridDim.y + p) * K;
+        const float2* ypos = reinterpret_cast<const float2*>(pos) + ((long long)(dir ^ 1) * gridDim.y + p) * K;
+        return RadiusGate{ypos, xpos[row], r2, dir == 0, {}};
+    }
+};
 
 }  // namespace
 
@@ -146,10 +97,9 @@ void launch_match_guided(const float* dA, const int* nA, const float* dB, const 
     hipLaunchKernelGGL(positions_kernel, dim3((K + 255) / 256, P), dim3(256), 0, s, kpA_yx, kpB_yx, pair_stride / D, K, hom,
                        pos);
     for_width(D, [&](auto d) {
-        hipLaunchKernelGGL(guided_rows_kernel<decltype(d)::value>, dim3((K + 127) / 128, P, 2 * MATCH_SHARES), dim3(256), 0,
-                           s, dA, nA, dB, nB, pair_stride, count_stride, K, pos, radius * radius, rowbest, colbest,
-                           match_count, MATCH_SHARES);
+        hipLaunchKernelGGL((nn_rows_kernel<decltype(d)::value, RadiusGateArgs>), dim3((K + 127) / 128, P, 2 * MATCH_SHARES),
+                           dim3(256), 0, s, dA, nA, dB, nB, pair_stride, count_stride, K, rowbest, colbest, match_count,
+                           MATCH_SHARES, RadiusGateArgs{pos, radius * radius});
     });
-    hipLaunchKernelGGL(guided_mutual_kernel, dim3((K + 255) / 256, P), dim3(256), 0, s, rowbest, colbest, nA, nB,
-                       count_stride, K, thr, match_idx, match_dist, match_count, MATCH_SHARES);
+    launch_match_mutual_rows(rowbest, colbest, nA, nB, count_stride, P, K, thr, match_idx, match_dist, match_count, s);
 }

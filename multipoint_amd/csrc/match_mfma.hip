@@ -18,36 +18,6 @@
 
 namespace {
 
-// best[x] = min over y of (dist(x,y) bits << 32 | y), X rows against the share's Y rows.
-// grid: (row-block groups, pairs, 2 directions x column shares): blockIdx.z = direction + 2 * column share
-template <int D>
-__global__ __launch_bounds__(256) void nn_rows_kernel(const float* __restrict__ dA, const int* __restrict__ nA,
-                                                     const float* __restrict__ dB, const int* __restrict__ nB,
-                                                     long long pair_stride, int count_stride, int K,
-                                                     unsigned long long* __restrict__ bestA,
-                                                     unsigned long long* __restrict__ bestB, int* __restrict__ match_count,
-                                                     int nsplit)
-{
-    // (the pair's match counter, which mutual_kernel adds to behind this launch, is zeroed here: one fill launch fewer)
-    if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0) match_count[blockIdx.y] = 0;
-    const int p = blockIdx.y, dir = blockIdx.z & 1, share = blockIdx.z >> 1;
-    const float* X = (dir == 0 ? dA : dB) + (long long)p * pair_stride;
-    const float* Y = (dir == 0 ? dB : dA) + (long long)p * pair_stride;
-    const int nx = min((dir == 0 ? nA : nB)[p * count_stride], K);
-    const int ny = min((dir == 0 ? nB : nA)[p * count_stride], K);
-    unsigned long long* best = (dir == 0 ? bestA : bestB) + ((long long)share * gridDim.y + p) * K;
-    const ColumnShare cs = column_share(ny, share, nsplit);
-    if ((int)blockIdx.x * 128 >= nx) return;             // (the whole workgroup)
-    const int lane = threadIdx.x & 63, li = lane & 31, half = lane >> 5;
-    const int r0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 32;
-    KeepNearest keep;
-    if (!walk_tiles<D>(X, Y, nx, ny, cs.c_begin, cs.c_end, r0, li, half, keep)) return;
-    // the two half-waves hold the two halves of the row's columns
-    const unsigned long long o = __shfl_xor(keep.run, 32);
-    const int row = r0 + li;
-    if (half == 0 && row < nx) best[row] = o < keep.run ? o : keep.run;
-}
-
 // best2[x] = the two smallest (dist(x,y) bits << 32 | y) over the share's rows y of B, for every row x of A.
 // grid: (row-block groups, pairs, column shares)
 template <int D>
@@ -93,12 +63,14 @@ __global__ __launch_bounds__(256) void mutual_kernel(const unsigned long long* _
         if (i < na && nb > 0) {
             unsigned long long v, w, unused;
             merge_shares<1>(bestA, (long long)p * K + i, K, nsplit, v, unused);
-            const int jj = (int)(v & 0xffffffffu);
-            m.d = __uint_as_float((unsigned)(v >> 32));
-            merge_shares<1>(bestB, (long long)p * K + jj, K, nsplit, w, unused);
-            const bool mutual = (int)(w & 0xffffffffu) == i;                      // matching.py:58-59
-            const bool close = (thr < 0.f) || (m.d < thr);                         // matching.py:56
-            if (mutual && close) m.j = jj;
+            if (v != NO_KEY) {                                                         // (a gated row may have no candidate)
+                const int jj = (int)(v & 0xffffffffu);
+                m.d = __uint_as_float((unsigned)(v >> 32));
+                merge_shares<1>(bestB, (long long)p * K + jj, K, nsplit, w, unused);
+                const bool mutual = (int)(w & 0xffffffffu) == i;                  // matching.py:58-59 (i is in j's gate: w is a key)
+                const bool close = (thr < 0.f) || (m.d < thr);                     // matching.py:56
+                if (mutual && close) m.j = jj;
+            }
         }
         return m;
     });
@@ -140,11 +112,20 @@ void launch_match_impl(const float* dA, const int* nA, const float* dB, const in
 {
     if (P <= 0 || K <= 0) return;
     for_width(D, [&](auto d) {
-        hipLaunchKernelGGL(nn_rows_kernel<decltype(d)::value>, dim3((K + 127) / 128, P, 2 * MATCH_SHARES), dim3(256), 0, s, dA,
-                           nA, dB, nB, pair_stride, count_stride, K, rowbest, colbest, match_count, MATCH_SHARES);
+        hipLaunchKernelGGL((nn_rows_kernel<decltype(d)::value, NoGateArgs>), dim3((K + 127) / 128, P, 2 * MATCH_SHARES), dim3(256),
+                           0, s, dA, nA, dB, nB, pair_stride, count_stride, K, rowbest, colbest, match_count, MATCH_SHARES,
+                           NoGateArgs{});
     });
-    hipLaunchKernelGGL(mutual_kernel, dim3((K + 255) / 256, P), dim3(256), 0, s, rowbest, colbest, nA,
-                       nB, count_stride, K, thr, match_idx, match_dist, match_count, MATCH_SHARES);
+    launch_match_mutual_rows(rowbest, colbest, nA, nB, count_stride, P, K, thr, match_idx, match_dist, match_count, s);
+}
+
+// the mutual test on the two directions' best keys, with or without a gate
+void launch_match_mutual_rows(const unsigned long long* rowbest, const unsigned long long* colbest, const int* nA, const int* nB,
+                              int count_stride, int P, int K, float thr, int* match_idx, float* match_dist, int* match_count,
+                              hipStream_t s)
+{
+    hipLaunchKernelGGL(mutual_kernel, dim3((K + 255) / 256, P), dim3(256), 0, s, rowbest, colbest, nA, nB, count_stride, K, thr,
+                       match_idx, match_dist, match_count, MATCH_SHARES);
 }
 
 // best2: [MATCH_SHARES][P][K][2] packed keys; match_count is zeroed by the first launch

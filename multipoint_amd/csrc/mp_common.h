@@ -10,6 +10,9 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #define MP_WAVE 64
 
+// is v a finite double?  (one comparison; false for NaN.  The kernels and the entries that check their arguments share it)
+__host__ __device__ __forceinline__ bool finite64(double v) { return fabs(v) <= 1.7976931348623157e308; }
+
 // activation tensor layouts of the fp32 F(4x4,3x3) launches (ConvParams::in_planar / out_planar)
 enum { MP_LAYOUT_NHWC = 0, MP_LAYOUT_PLANAR = 1, MP_LAYOUT_XPLANAR = 2 };
 
@@ -635,7 +638,9 @@ void launch_register_logpolar(const float* spectrum, int n, int N, const float* 
 // a, b complex [P][h][w], group_offsets [G+1] -> out complex [G][h][w] (accumulate: the sums start from out)
 void launch_register_cross_power(const float* a, const float* b, const int* group_offsets, int P, int G, int h, int w,
                                  int accumulate, float* out, hipStream_t s);
-int register_peak_chunks(int h, int w);
+// the chunks' results in the caller's workspace: carved from `partial`, or from nullptr for the bytes a call needs
+struct RegisterPeakWorkspace { float* part_v; int* part_i; int chunks; size_t bytes; };
+RegisterPeakWorkspace register_peak_workspace(void* partial, int G, int h, int w);
 // planes [G][h][w] values `stride` floats apart -> out_i [G][2], out_f [G][6]; partial: G * chunks (float, int) pairs
 void launch_register_peak(const float* planes, int G, int h, int w, int stride, int* out_i, float* out_f, void* partial,
                           hipStream_t s);

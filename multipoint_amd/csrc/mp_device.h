@@ -31,6 +31,46 @@ __device__ __forceinline__ int reflect101(int p, int n)
     return q < n ? q : period - q;
 }
 
+// The source position of cv2.warpPerspective(INTER_LINEAR) for destination pixel (x, y) under the inverted homography m[9], as
+// OpenCV's WarpPerspectiveInvoker + remapBilinear<float> compute it: per row of a block of bw0 columns X0 = m0 xb + m1 y + m2
+// (likewise Y0, W0) in float64, per pixel 32 / (W0 + m6 x1) and the coordinates rounded half-to-even to 1/32 pixel; the source
+// pixel is that >> 5 saturated to int16, the fraction that & 31, and the four taps (sy, sx), (sy, sx + 1), (sy + 1, sx),
+// (sy + 1, sx + 1) weigh w0..w3 from the float32 table.  Every product and sum is rounded separately, as OpenCV's scalar code
+// does (hipcc's __dmul_rn / __fadd_rn wrappers are inline operators that carry their own `contract` flag, hence the pragma).
+__device__ __forceinline__ int cv_fixed(double num, double w)
+{
+#pragma clang fp contract(off)
+    double f = num * w;
+    f = fmax(-2147483648.0, fmin(2147483647.0, f));
+    return (int)rint(f);
+}
+struct CvWarpSource { int sx, sy; float w0, w1, w2, w3; };
+__device__ __forceinline__ CvWarpSource cv_warp_source(const double* m, int x, int y, int bw0)
+{
+#pragma clang fp contract(off)
+    const int xb = (x / bw0) * bw0;
+    const double dxb = (double)xb, dx1 = (double)(x - xb), dy = (double)y;
+    const double X0 = (m[0] * dxb + m[1] * dy) + m[2];
+    const double Y0 = (m[3] * dxb + m[4] * dy) + m[5];
+    const double W0 = (m[6] * dxb + m[7] * dy) + m[8];
+    double w = W0 + m[6] * dx1;
+    w = w != 0.0 ? 32.0 / w : 0.0;
+    const int X = cv_fixed(X0 + m[0] * dx1, w);
+    const int Y = cv_fixed(Y0 + m[3] * dx1, w);
+    const int sx = max(-32768, min(32767, X >> 5)), sy = max(-32768, min(32767, Y >> 5));
+    const float fx = (float)(X & 31) * (1.f / 32.f), fy = (float)(Y & 31) * (1.f / 32.f);
+    const float ax = 1.f - fx, ay = 1.f - fy;
+    return {sx, sy, ay * ax, ay * fx, fy * ax, fy * fx};
+}
+
+// the sum of v over the wave's 64 lanes, in every lane (a fixed butterfly: the same bits on every run)
+__device__ __forceinline__ double wave_add(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
 // ReLU as an integer max (finite inputs): one v_max_i32, no NaN-canonicalising v_max_f32 in front of it
 __device__ __forceinline__ float relu_bits(float v) { return __int_as_float(max(__float_as_int(v), 0)); }
 

@@ -5,6 +5,8 @@
 #include "mp_common.h"
 #include "mp_device.h"
 
+#include <type_traits>
+
 namespace mp_ecc {
 
 constexpr int THREADS = 256;
@@ -15,14 +17,22 @@ template <int K> struct Sums {
 };
 static_assert(Sums<8>::N == MP_ECC_MAX_SUMS, "the sums of the homography");
 
+// launch(std::integral_constant<int, K>{}) for the parameter count of a model: 2, 4, 6, or 8 for the homography
+template <class Launch>
+void for_params(int K, Launch launch)
+{
+    if (K == 2) launch(std::integral_constant<int, 2>{});
+    else if (K == 4) launch(std::integral_constant<int, 4>{});
+    else if (K == 6) launch(std::integral_constant<int, 6>{});
+    else launch(std::integral_constant<int, 8>{});
+}
+
 __device__ __forceinline__ float lerp2(float p00, float p01, float p10, float p11, float fx, float fy)
 {
     const float top = fmaf(fx, p01 - p00, p00);
     const float bot = fmaf(fx, p11 - p10, p10);
     return fmaf(fy, bot - top, top);
 }
-
-__device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }
 
 // The sums of one chunk of MP_ECC_CHUNK template pixels into the calling lane's accumulators: lane t takes the pixels t, t + 256,
 // ... of the chunk in that order.  MASKED: a template pixel whose `keep` byte is 0 (keep may be NULL) and an image sample with a
@@ -167,7 +177,7 @@ __device__ __forceinline__ void step(double ww, double corr, double rho, double 
         zy += tp[i] * ip[i];
     }
     const double lam_n = ww - yy, lam_d = corr - zy;
-    if (!(finite_d(lam_n) && finite_d(lam_d))) { st.status = MP_ECC_NONFINITE; return; }
+    if (!(finite64(lam_n) && finite64(lam_d))) { st.status = MP_ECC_NONFINITE; return; }
     if (lam_d <= 0.0) { st.status = MP_ECC_LAMBDA; return; }
     const double lam = lam_n / lam_d;
     // dp = L^-T (lam z - y)
@@ -194,7 +204,7 @@ __device__ __forceinline__ void step(double ww, double corr, double rho, double 
     }
     bool ok = true;
 #pragma unroll
-    for (int i = 0; i < 9; ++i) ok = ok && finite_d(T[i]);
+    for (int i = 0; i < 9; ++i) ok = ok && finite64(T[i]);
     if (!ok) { st.status = MP_ECC_NONFINITE; return; }
 #pragma unroll
     for (int i = 0; i < 9; ++i) st.T[i] = T[i];
@@ -215,7 +225,7 @@ __device__ __forceinline__ void start_state(const double* __restrict__ T0, int p
     st.status = MP_ECC_RUNNING;
     st.converged = 0;
     bool ok = true;
-    for (int i = 0; i < 9; ++i) ok = ok && finite_d(st.T[i]);
+    for (int i = 0; i < 9; ++i) ok = ok && finite64(st.T[i]);
     if (!ok) st.status = MP_ECC_NONFINITE;
 }
 

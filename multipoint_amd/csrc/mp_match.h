@@ -238,6 +238,43 @@ __device__ __forceinline__ bool walk_tiles(const float* __restrict__ X, const fl
     else return walk_tiles_whole<D>(X, Y, nx, ny, c_begin, c_end, r0, li, half, keep, gate);
 }
 
+// What a rows kernel builds its walk's gate from, handed over as one by-value kernel argument: gate(dir, p, K, row) is the
+// policy for the lane's X row `row` (clamped to the pair's rows) of pair p in direction dir.  Nothing at all for NoGate.
+struct NoGateArgs {
+    __device__ __forceinline__ NoGate gate(int, int, int, int) const { return {}; }
+};
+
+// best[x] = min over the y the gate admits of (dist(x,y) bits << 32 | y), X rows against the share's Y rows; NO_KEY for a row
+// without candidates.
+// grid: (row-block groups, pairs, 2 directions x column shares): blockIdx.z = direction + 2 * column share
+template <int D, class GateArgs>
+__global__ __launch_bounds__(256) void nn_rows_kernel(const float* __restrict__ dA, const int* __restrict__ nA,
+                                                     const float* __restrict__ dB, const int* __restrict__ nB,
+                                                     long long pair_stride, int count_stride, int K,
+                                                     unsigned long long* __restrict__ bestA,
+                                                     unsigned long long* __restrict__ bestB, int* __restrict__ match_count,
+                                                     int nsplit, GateArgs gate_args)
+{
+    // (the pair's match counter, which the mutual epilogue adds to behind this launch, is zeroed here: one fill launch fewer)
+    if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0) match_count[blockIdx.y] = 0;
+    const int p = blockIdx.y, dir = blockIdx.z & 1, share = blockIdx.z >> 1;
+    const float* X = (dir == 0 ? dA : dB) + (long long)p * pair_stride;
+    const float* Y = (dir == 0 ? dB : dA) + (long long)p * pair_stride;
+    const int nx = min((dir == 0 ? nA : nB)[p * count_stride], K);
+    const int ny = min((dir == 0 ? nB : nA)[p * count_stride], K);
+    unsigned long long* best = (dir == 0 ? bestA : bestB) + ((long long)share * gridDim.y + p) * K;
+    const ColumnShare cs = column_share(ny, share, nsplit);
+    if ((int)blockIdx.x * 128 >= nx) return;             // (the whole workgroup)
+    const int lane = threadIdx.x & 63, li = lane & 31, half = lane >> 5;
+    const int r0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 32;
+    KeepNearest keep;
+    if (!walk_tiles<D>(X, Y, nx, ny, cs.c_begin, cs.c_end, r0, li, half, keep, gate_args.gate(dir, p, K, min(r0 + li, nx - 1)))) return;
+    // the two half-waves hold the two halves of the row's columns
+    const unsigned long long o = __shfl_xor(keep.run, 32);
+    const int row = r0 + li;
+    if (half == 0 && row < nx) best[row] = o < keep.run ? o : keep.run;
+}
+
 // ---- what the epilogue kernels and the launches of match_mfma.hip and match_guided.hip share ----
 
 // the N smallest keys (k2 is untouched for N = 1) of row `at` over the column shares' arrays, which lie [share][pair][K][N]
@@ -280,6 +317,11 @@ __device__ __forceinline__ void write_matches(int K, int* __restrict__ match_idx
     const int c = __syncthreads_count(hit);
     if (threadIdx.x == 0 && c) atomicAdd(&match_count[p], c);
 }
+
+// the mutual epilogue (match_mfma.hip) behind a launch of nn_rows_kernel: rowbest / colbest [MATCH_SHARES][P][K]
+void launch_match_mutual_rows(const unsigned long long* rowbest, const unsigned long long* colbest, const int* nA, const int* nB,
+                              int count_stride, int P, int K, float thr, int* match_idx, float* match_dist, int* match_count,
+                              hipStream_t s);
 
 // the row kernels exist for the descriptor widths the C entries admit: launch(integral_constant<int, D>)
 template <class Launch>

@@ -31,6 +31,7 @@
 // step = (b - a) / n, e[i] = fl(fl(i * step) + a), e[n] = b; bin = (number of edges <= v) - 1, v == e[n] in bin n - 1.
 // The bin is guessed by a multiply and a truncation and then walked to where the edges put it.
 #include "mp_common.h"
+#include "mp_device.h"
 #include "../../include/multipoint_hip.h"
 
 namespace {
@@ -137,14 +138,6 @@ __global__ __launch_bounds__(256) void zero_kernel(const MiEval* __restrict__ ev
     for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) c[i] = 0u;
 }
 
-__device__ __forceinline__ int cv_fixed(double num, double w)
-{
-#pragma clang fp contract(off)
-    double f = num * w;
-    f = fmax(-2147483648.0, fmin(2147483647.0, f));
-    return (int)rint(f);
-}
-
 // src [B][Ho][Wo] -> dst [E][H][W]; bw0 is OpenCV's block width for the DESTINATION size
 __global__ __launch_bounds__(256) void warp_kernel(const float* __restrict__ src, int Ho, int Wo, const MiEval* __restrict__ ev,
                                                    const int* __restrict__ nact, int G, const double* __restrict__ M, int H,
@@ -157,28 +150,16 @@ __global__ __launch_bounds__(256) void warp_kernel(const float* __restrict__ src
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     float lo = INFINITY, hi = -INFINITY;
     if (x < W && y < H) {
-        const double* h = M + (size_t)e * 9;
         const float* img = src + (size_t)ev[e].pair * Ho * Wo;
-        const int xb = (x / bw0) * bw0;
-        const double dxb = (double)xb, dx1 = (double)(x - xb), dy = (double)y;
-        const double X0 = (h[0] * dxb + h[1] * dy) + h[2];
-        const double Y0 = (h[3] * dxb + h[4] * dy) + h[5];
-        const double W0 = (h[6] * dxb + h[7] * dy) + h[8];
-        double w = W0 + h[6] * dx1;
-        w = w != 0.0 ? 32.0 / w : 0.0;
-        const int X = cv_fixed(X0 + h[0] * dx1, w);
-        const int Y = cv_fixed(Y0 + h[3] * dx1, w);
-        const int sx = max(-32768, min(32767, X >> 5)), sy = max(-32768, min(32767, Y >> 5));
-        const float fx = (float)(X & 31) * (1.f / 32.f), fy = (float)(Y & 31) * (1.f / 32.f);
-        const float ax = 1.f - fx, ay = 1.f - fy;
-        const float w0 = ay * ax, w1 = ay * fx, w2 = fy * ax, w3 = fy * fx;
+        const CvWarpSource c = cv_warp_source(M + (size_t)e * 9, x, y, bw0);
+        const int sx = c.sx, sy = c.sy;
         const bool xa = (unsigned)sx < (unsigned)Wo, xc = (unsigned)(sx + 1) < (unsigned)Wo;
         const bool ya = (unsigned)sy < (unsigned)Ho, yc = (unsigned)(sy + 1) < (unsigned)Ho;
         const float v0 = (ya && xa) ? img[(size_t)sy * Wo + sx] : -1.f;
         const float v1 = (ya && xc) ? img[(size_t)sy * Wo + sx + 1] : -1.f;
         const float v2 = (yc && xa) ? img[(size_t)(sy + 1) * Wo + sx] : -1.f;
         const float v3 = (yc && xc) ? img[(size_t)(sy + 1) * Wo + sx + 1] : -1.f;
-        const float p0 = v0 * w0, p1 = v1 * w1, p2 = v2 * w2, p3 = v3 * w3;
+        const float p0 = v0 * c.w0, p1 = v1 * c.w1, p2 = v2 * c.w2, p3 = v3 * c.w3;
         const float out = ((p0 + p1) + p2) + p3;
         dst[((size_t)e * H + y) * W + x] = out;
         lo = hi = out;

@@ -22,6 +22,7 @@
 #include "mp_common.h"
 #include "mp_device.h"
 #include "mp_raster.h"
+#include "mp_workspace.h"
 #include "../../include/multipoint_hip.h"
 
 #pragma clang fp contract(off)
@@ -383,8 +384,6 @@ __global__ __launch_bounds__(256) void photo_cur_ptrs_kernel(float* out, float* 
     cur[img] = (parity ? alt : out) + img * HW;
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct PhotoWorkspace {
     mp_photometric_plan* plans;   // [n]
     int* ellipses;                // [n_ellipses][5]
@@ -399,19 +398,18 @@ struct PhotoWorkspace {
 
 PhotoWorkspace photo_workspace(void* base, int n, int H, int W, int n_ellipses)
 {
-    char* p = static_cast<char*>(base);
     const size_t px = (size_t)n * H * W;
+    Carver c(base);
     PhotoWorkspace w;
-    size_t off = 0;
-    w.plans = reinterpret_cast<mp_photometric_plan*>(p + off); off += align256(sizeof(mp_photometric_plan) * n);
-    w.ellipses = reinterpret_cast<int*>(p + off);               off += align256(sizeof(int) * 5 * (size_t)(n_ellipses > 0 ? n_ellipses : 1));
-    w.cur = reinterpret_cast<const float**>(p + off);           off += align256(sizeof(float*) * n);
-    w.mean = reinterpret_cast<float*>(p + off);                 off += align256(sizeof(float) * n);
-    w.weights = reinterpret_cast<float*>(p + off);              off += align256(sizeof(float) * MP_PHOTO_MAX_BLUR * n);
-    w.mask = reinterpret_cast<float*>(p + off);                 off += align256(sizeof(float) * px);
-    w.tmp = reinterpret_cast<float*>(p + off);                  off += align256(sizeof(float) * px);
-    w.alt = reinterpret_cast<float*>(p + off);                  off += align256(sizeof(float) * px);
-    w.bytes = off;
+    w.plans = c.take<mp_photometric_plan>(n);
+    w.ellipses = c.take<int>(5 * (size_t)(n_ellipses > 0 ? n_ellipses : 1));
+    w.cur = c.take<const float*>(n);
+    w.mean = c.take<float>(n);
+    w.weights = c.take<float>((size_t)MP_PHOTO_MAX_BLUR * n);
+    w.mask = c.take<float>(px);
+    w.tmp = c.take<float>(px);
+    w.alt = c.take<float>(px);
+    w.bytes = c.bytes();
     return w;
 }
 

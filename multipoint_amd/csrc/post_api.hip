@@ -191,7 +191,7 @@ int mp_suppression_radii(mp_handle* h, const int* kp_yx, const float* kp_score, 
 {
     if (!h) return MP_EINVAL;
     if (!kp_yx || !kp_score || !kp_count || !radius2) return fail(h, MP_EINVAL, "mp_suppression_radii: NULL tensor");
-    if (B <= 0 || B > 65535 || K <= 0) return fail(h, MP_EINVAL, "mp_suppression_radii: need 0 < B <= 65535 and K > 0");
+    if (!count_ok(B) || K <= 0) return fail(h, MP_EINVAL, "mp_suppression_radii: need 0 < B <= 65535 and K > 0");
     if (!robust_ok(robust)) return fail(h, MP_EINVAL, "mp_suppression_radii: robust must be in (0, 1]");
     MP_HIP(hipSetDevice(h->device));
     launch_suppression_radii(kp_yx, kp_score, kp_count, B, K, robust, radius2, static_cast<hipStream_t>(stream));
@@ -303,7 +303,7 @@ static int match_check(mp_handle* h, const char* fn, const void* a, const void* 
                        int P, int K, int D, bool mfma_rows)
 {
     if (!a || !b || !c || !d) return fail(h, MP_EINVAL, std::string(fn) + ": NULL tensor");
-    if (P <= 0 || P > 65535 || K <= 0) return fail(h, MP_EINVAL, std::string(fn) + ": need 0 < P <= 65535, K > 0");
+    if (!count_ok(P) || K <= 0) return fail(h, MP_EINVAL, std::string(fn) + ": need 0 < P <= 65535, K > 0");
     if (mfma_rows ? (D != 64 && D != 128 && D != 256 && D != 384) : (D <= 0 || D > 384))
         return fail(h, MP_EINVAL, std::string(fn) + (mfma_rows ? ": D must be 64, 128, 256 or 384" : ": D must be in [1, 384]"));
     return MP_OK;
@@ -455,7 +455,7 @@ int mp_detector_metrics(mp_handle* h, const float* prob, const unsigned char* ke
     if (!h) return MP_EINVAL;
     if (!prob || !keypoint_map || !work || !rec_index || !rec_prob || !rec_bits || !rec_count || !n_gt)
         return fail(h, MP_EINVAL, "mp_detector_metrics: NULL tensor");
-    if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL)
+    if (!count_ok(B) || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL)
         return fail(h, MP_EINVAL, "mp_detector_metrics: need 0 < B <= 65535, H, W > 0");
     if (!(distance_thresh >= 0.f) || !(distance_thresh < 3.f))
         return fail(h, MP_EINVAL, "mp_detector_metrics: distance_thresh must be in [0, 3) (5 x 5 window)");
@@ -475,7 +475,7 @@ int mp_warp_perspective(mp_handle* h, const float* src, int n_src, int H, int W,
 {
     if (!h) return MP_EINVAL;
     if (!src || !dst_to_src || !dst) return fail(h, MP_EINVAL, "mp_warp_perspective: NULL tensor");
-    if (n_src <= 0 || n_out <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || n_out > 65535)
+    if (n_src <= 0 || n_out <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || n_out > MAX_GRID_Y)
         return fail(h, MP_EINVAL, "mp_warp_perspective: sizes must be positive (n_out <= 65535)");
     if ((mode != 0 && mode != 1) || (padding != 0 && padding != 1))
         return fail(h, MP_EINVAL, "mp_warp_perspective: mode must be 0 (bilinear) / 1 (nearest), padding 0 (zeros) / 1 (reflection)");
@@ -489,7 +489,7 @@ int mp_warp_perspective_cv(mp_handle* h, const float* src, int n, int H, int W, 
 {
     if (!h) return MP_EINVAL;
     if (!src || !hom_inv || !dst) return fail(h, MP_EINVAL, "mp_warp_perspective_cv: NULL tensor");
-    if (n <= 0 || n > 65535 || H <= 0 || W <= 0 || H > 32767 || W > 32767)
+    if (!frames_ok(n, H, W, 1, 32767))
         return fail(h, MP_EINVAL, "mp_warp_perspective_cv: need 0 < n <= 65535 and 0 < H, W <= 32767");
     if (border != 0 && border != 1)
         return fail(h, MP_EINVAL, "mp_warp_perspective_cv: border must be 0 (BORDER_CONSTANT 0) or 1 (BORDER_REFLECT_101)");
@@ -504,7 +504,7 @@ int mp_ha_valid_mask(mp_handle* h, const double* hom_inv, int G, int H, int W, i
 {
     if (!h) return MP_EINVAL;
     if (!hom_inv || !mask) return fail(h, MP_EINVAL, "mp_ha_valid_mask: NULL tensor");
-    if (G <= 0 || G > 65535 || H <= 0 || W <= 0) return fail(h, MP_EINVAL, "mp_ha_valid_mask: need 0 < G <= 65535, H, W > 0");
+    if (!count_ok(G) || H <= 0 || W <= 0) return fail(h, MP_EINVAL, "mp_ha_valid_mask: need 0 < G <= 65535, H, W > 0");
     if (erosion_radius < 0 || erosion_radius > 16) return fail(h, MP_EINVAL, "mp_ha_valid_mask: erosion_radius must be in [0, 16]");
     MP_HIP(hipSetDevice(h->device));
     launch_ha_valid_mask(hom_inv, G, H, W, erosion_radius, mask_border != 0, mask, static_cast<hipStream_t>(stream));
@@ -515,7 +515,7 @@ static int ha_check(mp_handle* h, const char* fn, const float* pa, const float* 
 {
     if (!pa || (aggregation != 0 && !pb)) return fail(h, MP_EINVAL, std::string(fn) + ": NULL heat map");
     if (aggregation < 0 || aggregation > 2) return fail(h, MP_EINVAL, std::string(fn) + ": aggregation must be 0 (single), 1 (prod) or 2 (sum)");
-    if (B <= 0 || B > 65535 || H <= 0 || W <= 0) return fail(h, MP_EINVAL, std::string(fn) + ": need 0 < B <= 65535, H, W > 0");
+    if (!count_ok(B) || H <= 0 || W <= 0) return fail(h, MP_EINVAL, std::string(fn) + ": need 0 < B <= 65535, H, W > 0");
     return MP_OK;
 }
 
@@ -563,7 +563,7 @@ int mp_gaussian_filter(mp_handle* h, const float* in, int B, int H, int W, int k
     if (!h) return MP_EINVAL;
     if (!in || !weights || !out) return fail(h, MP_EINVAL, "mp_gaussian_filter: NULL tensor");
     if (in == out) return fail(h, MP_EINVAL, "mp_gaussian_filter: in-place filtering is not supported");
-    if (B <= 0 || B > 65535 || H <= 0 || W <= 0) return fail(h, MP_EINVAL, "mp_gaussian_filter: need 0 < B <= 65535, H, W > 0");
+    if (!count_ok(B) || H <= 0 || W <= 0) return fail(h, MP_EINVAL, "mp_gaussian_filter: need 0 < B <= 65535, H, W > 0");
     if (ksize < 1 || ksize > 31 || (ksize & 1) == 0) return fail(h, MP_EINVAL, "mp_gaussian_filter: ksize must be odd and <= 31");
     if ((ksize - 1) / 2 >= H || (ksize - 1) / 2 >= W) return fail(h, MP_EINVAL, "mp_gaussian_filter: reflection padding needs (ksize-1)/2 < H, W");
     MP_HIP(hipSetDevice(h->device));
@@ -573,7 +573,7 @@ int mp_gaussian_filter(mp_handle* h, const float* in, int B, int H, int W, int k
 
 int mp_loss_workspace_bytes(int B, int H, int W, long long* bytes)
 {
-    if (!bytes || B <= 0 || B > 65535 || H <= 0 || W <= 0 || H % 8 || W % 8) return MP_EINVAL;
+    if (!bytes || !count_ok(B) || H <= 0 || W <= 0 || H % 8 || W % 8) return MP_EINVAL;
     *bytes = (long long)loss_workspace_bytes(B, H, W);
     return MP_OK;
 }
@@ -581,7 +581,7 @@ int mp_loss_workspace_bytes(int B, int H, int W, long long* bytes)
 static int loss_check(mp_handle* h, const char* fn, int B, int Hc, int Wc, int H, int W, void* workspace,
                       long long workspace_bytes)
 {
-    if (B <= 0 || B > 65535 || Hc <= 0 || Wc <= 0)
+    if (!count_ok(B) || Hc <= 0 || Wc <= 0)
         return fail(h, MP_EINVAL, std::string(fn) + ": need 0 < B <= 65535 and Hc, Wc > 0");
     if (H % 8 || W % 8) return fail(h, MP_EINVAL, std::string(fn) + ": H and W must be multiples of 8");
     if (H != 8 * Hc || W != 8 * Wc)
@@ -675,7 +675,7 @@ int mp_descriptor_loss_backward(mp_handle* h, const float* desc1, const float* d
 
 int mp_photometric_workspace_bytes(int n, int H, int W, int n_ellipses, long long* bytes)
 {
-    if (!bytes || n <= 0 || n > 65535 || H <= 0 || W <= 0 || n_ellipses < 0 || (long long)n * H * W > (1LL << 34))
+    if (!bytes || !count_ok(n) || H <= 0 || W <= 0 || n_ellipses < 0 || (long long)n * H * W > (1LL << 34))
         return MP_EINVAL;
     *bytes = (long long)photometric_workspace_bytes(n, H, W, n_ellipses);
     return MP_OK;
@@ -687,7 +687,7 @@ static int photometric_check(mp_handle* h, const char* fn, int n, int H, int W, 
                              long long workspace_bytes)
 {
     const std::string f(fn);
-    if (n <= 0 || n > 65535 || H <= 0 || W <= 0 || H > 8192 || (long long)n * H * W > (1LL << 34))
+    if (!count_ok(n) || H <= 0 || W <= 0 || H > 8192 || (long long)n * H * W > (1LL << 34))
         return fail(h, MP_EINVAL, f + ": need 0 < n <= 65535, 0 < H <= 8192, W > 0");
     if (!plans) return fail(h, MP_EINVAL, f + ": NULL plans");
     if (n_ellipses < 0 || (n_ellipses > 0 && !ellipses)) return fail(h, MP_EINVAL, f + ": bad ellipse table");

@@ -180,7 +180,7 @@ int mp_gaussian_blur(mp_handle* h, const float* in, int n, int H, int W, int ksi
     if (ksize < 1 || ksize > MAX_K || ksize % 2 == 0)
         return fail(h, MP_EINVAL, "mp_gaussian_blur: ksize must be odd and in [1, " + std::to_string(MAX_K) + "], got " +
                                       std::to_string(ksize));
-    if (n <= 0 || n > 65535 || H <= 0 || W <= 0 || H > 32767 || W > 32767)
+    if (!frames_ok(n, H, W, 1, 32767))
         return fail(h, MP_EINVAL, "mp_gaussian_blur: 1 to 65535 frames of 1 x 1 to 32767 x 32767 pixels");
     if (ksize / 2 >= (H < W ? H : W))
         return fail(h, MP_EINVAL, "mp_gaussian_blur: ksize / 2 = " + std::to_string(ksize / 2) + " must be below the frame's "
@@ -201,7 +201,7 @@ int mp_frames_to_float(mp_handle* h, const void* in, int mode, int n, int H, int
     if (!in || !out) return fail(h, MP_EINVAL, "mp_frames_to_float: NULL tensor");
     if (mode != MP_FRAMES_U8 && mode != MP_FRAMES_BGR8 && mode != MP_FRAMES_U16)
         return fail(h, MP_EINVAL, "mp_frames_to_float: mode must be MP_FRAMES_U8, MP_FRAMES_BGR8 or MP_FRAMES_U16");
-    if (n <= 0 || n > 65535 || H <= 0 || W <= 0 || H > 32767 || W > 32767)
+    if (!frames_ok(n, H, W, 1, 32767))
         return fail(h, MP_EINVAL, "mp_frames_to_float: 1 to 65535 frames of 1 x 1 to 32767 x 32767 pixels");
     const long long total = (long long)n * H * W;
     if (total > (1LL << 38)) return fail(h, MP_EINVAL, "mp_frames_to_float: at most 2^38 pixels per call");

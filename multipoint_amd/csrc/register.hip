@@ -17,6 +17,7 @@
 //                                 around the maximum left out.
 #include "mp_common.h"
 #include "mp_device.h"
+#include "mp_workspace.h"
 
 #include <climits>
 
@@ -247,14 +248,24 @@ void launch_register_cross_power(const float* a, const float* b, const int* grou
                        reinterpret_cast<const float2*>(b), group_offsets, P, hw, accumulate, reinterpret_cast<float2*>(out));
 }
 
-int register_peak_chunks(int h, int w) { return (h * w + MP_REGISTER_PEAK_CHUNK - 1) / MP_REGISTER_PEAK_CHUNK; }
+RegisterPeakWorkspace register_peak_workspace(void* partial, int G, int h, int w)
+{
+    Carver c(partial, alignof(float));
+    RegisterPeakWorkspace ws{};
+    ws.chunks = (h * w + MP_REGISTER_PEAK_CHUNK - 1) / MP_REGISTER_PEAK_CHUNK;
+    ws.part_v = c.take<float>((size_t)G * ws.chunks);
+    ws.part_i = c.take<int>((size_t)G * ws.chunks);
+    ws.bytes = c.bytes();
+    return ws;
+}
 
 void launch_register_peak(const float* planes, int G, int h, int w, int stride, int* out_i, float* out_f, void* partial,
                           hipStream_t s)
 {
-    const int chunks = register_peak_chunks(h, w);
-    float* part_v = static_cast<float*>(partial);
-    int* part_i = reinterpret_cast<int*>(part_v + (size_t)G * chunks);
+    const RegisterPeakWorkspace ws = register_peak_workspace(partial, G, h, w);
+    const int chunks = ws.chunks;
+    float* part_v = ws.part_v;
+    int* part_i = ws.part_i;
     const dim3 grid((unsigned)chunks, (unsigned)G);
     hipLaunchKernelGGL(register_peak_chunk_kernel<false>, grid, dim3(THREADS), 0, s, planes, h, w, stride, out_i, part_v, part_i);
     hipLaunchKernelGGL(register_peak_final_kernel<false>, dim3(G), dim3(THREADS), 0, s, planes, h, w, stride, chunks, part_v, part_i,

@@ -7,7 +7,7 @@ using namespace mp_host;
 
 namespace {
 
-bool plane_ok(int n, int h, int w, int lo) { return n > 0 && n <= 65535 && h >= lo && w >= lo && h <= MP_FFT_MAX_N && w <= MP_FFT_MAX_N; }
+bool plane_ok(int n, int h, int w, int lo) { return frames_ok(n, h, w, lo, MP_FFT_MAX_N); }
 
 }  // namespace
 
@@ -52,7 +52,7 @@ int mp_register_cross_power(mp_handle* h, const float* a, const float* b, const 
 int mp_register_peak_workspace_bytes(int G, int hh, int ww, long long* bytes)
 {
     if (!bytes || !plane_ok(G, hh, ww, 3)) return MP_EINVAL;
-    *bytes = (long long)G * register_peak_chunks(hh, ww) * (long long)(sizeof(float) + sizeof(int));
+    *bytes = (long long)register_peak_workspace(nullptr, G, hh, ww).bytes;
     return MP_OK;
 }
 
@@ -64,9 +64,7 @@ int mp_register_peak(mp_handle* h, const float* planes, int G, int hh, int ww, i
     long long need = 0;
     if (stride < 1 || stride > 2 || mp_register_peak_workspace_bytes(G, hh, ww, &need) != MP_OK)
         return fail(h, MP_EINVAL, "mp_register_peak: need 0 < G <= 65535, planes of 3 .. 4096 per side and a stride of 1 or 2");
-    if (workspace_bytes < need)
-        return fail(h, MP_EINVAL, "mp_register_peak: workspace of " + std::to_string(workspace_bytes) + " B, " +
-                                      std::to_string(need) + " B needed (mp_register_peak_workspace_bytes)");
+    if (const int rc = need_workspace(h, "mp_register_peak", workspace_bytes, (size_t)need, "mp_register_peak_workspace_bytes")) return rc;
     MP_HIP(hipSetDevice(h->device));
     launch_register_peak(planes, G, hh, ww, stride, out_i, out_f, workspace, static_cast<hipStream_t>(stream));
     return launch_status(h);

@@ -16,19 +16,13 @@
 //   batch and from run to run.
 #include "../../include/multipoint_hip.h"
 #include "mp_common.h"
+#include "mp_device.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int THREADS = 256, WAVES = THREADS / MP_WAVE;
-
-__device__ __forceinline__ double wave_add(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // is candidate (sb, ib) a better peak than (sa, ia)?  NaN is "undefined"; equal scores go to the lower index
 __device__ __forceinline__ bool better(double sa, int ia, double sb, int ib)

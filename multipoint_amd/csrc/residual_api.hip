@@ -34,7 +34,7 @@ int mp_residual_field(mp_handle* h, const float* optical_feat, const float* ther
 {
     if (!h) return MP_EINVAL;
     if (!optical_feat || !thermal_feat || !out_d || !out_i) return fail(h, MP_EINVAL, "mp_residual_field: NULL tensor");
-    if (B < 1 || B > 65535) return fail(h, MP_EINVAL, "mp_residual_field: B must be in [1, 65535]");
+    if (!count_ok(B)) return fail(h, MP_EINVAL, "mp_residual_field: B must be in [1, 65535]");
     if (H < 8 || W < 8 || H > 4096 || W > 4096) return fail(h, MP_EINVAL, "mp_residual_field: frames must be 8 x 8 to 4096 x 4096");
     if (!window_ok(window)) return fail(h, MP_EINVAL, "mp_residual_field: window must be 8, 16, 24, 32, 48 or 64");
     if (stride < 1) return fail(h, MP_EINVAL, "mp_residual_field: stride must be positive");

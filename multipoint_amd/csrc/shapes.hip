@@ -368,8 +368,6 @@ __global__ __launch_bounds__(256) void shapes_resize_kernel(const float* canvas,
     out[(long long)img * oh * ow + p] = top * (1.f - fy) + bot * fy;
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct ShapesWorkspace {
     mp_shapes_cmd* cmds;      // [n_cmds]
     int* offset;              // [n + 1]
@@ -387,29 +385,28 @@ struct ShapesWorkspace {
 
 ShapesWorkspace shapes_workspace(void* base, int n, int H, int W, int n_cmds, int n_verts, int n_circles)
 {
-    char* p = static_cast<char*>(base);
     const size_t px = (size_t)n * H * W;
     const auto atleast1 = [](int v) { return (size_t)(v > 0 ? v : 1); };
+    Carver c(base);
     ShapesWorkspace w;
-    size_t off = 0;
-    w.cmds = reinterpret_cast<mp_shapes_cmd*>(p + off); off += align256(sizeof(mp_shapes_cmd) * atleast1(n_cmds));
-    w.offset = reinterpret_cast<int*>(p + off);         off += align256(sizeof(int) * (size_t)(n + 1));
-    w.verts = reinterpret_cast<int*>(p + off);          off += align256(sizeof(int) * 2 * atleast1(n_verts));
-    w.circles = reinterpret_cast<int*>(p + off);        off += align256(sizeof(int) * 3 * atleast1(n_circles));
-    w.colors = reinterpret_cast<double*>(p + off);      off += align256(sizeof(double) * 2 * atleast1(n_circles));
-    w.half = reinterpret_cast<short*>(p + off);         off += align256(sizeof(short) * HALF_STRIDE * HALF_STRIDE);
-    w.ksize = reinterpret_cast<int*>(p + off);          off += align256(sizeof(int) * 2 * (size_t)n);
-    w.partial = reinterpret_cast<double*>(p + off);     off += align256(sizeof(double) * MEAN_PARTS * (size_t)n);
-    w.weights = reinterpret_cast<float*>(p + off);      off += align256(sizeof(float) * MP_PHOTO_MAX_BLUR * (size_t)n);
-    w.aux = reinterpret_cast<float*>(p + off);          off += align256(sizeof(float) * px);
-    w.tmp = reinterpret_cast<double*>(p + off);         off += align256(sizeof(double) * px);
-    w.bytes = off;
+    w.cmds = c.take<mp_shapes_cmd>(atleast1(n_cmds));
+    w.offset = c.take<int>((size_t)n + 1);
+    w.verts = c.take<int>(2 * atleast1(n_verts));
+    w.circles = c.take<int>(3 * atleast1(n_circles));
+    w.colors = c.take<double>(2 * atleast1(n_circles));
+    w.half = c.take<short>((size_t)HALF_STRIDE * HALF_STRIDE);
+    w.ksize = c.take<int>(2 * (size_t)n);
+    w.partial = c.take<double>(MEAN_PARTS * (size_t)n);
+    w.weights = c.take<float>(MP_PHOTO_MAX_BLUR * (size_t)n);
+    w.aux = c.take<float>(px);
+    w.tmp = c.take<double>(px);
+    w.bytes = c.bytes();
     return w;
 }
 
 bool frame_ok(int n, int H, int W)
 {
-    return n > 0 && n <= 65535 && H > 0 && W > 0 && H <= 32768 && W <= 32768 && (long long)n * H * W <= (1LL << 32);
+    return frames_ok(n, H, W, 1, 32768) && (long long)n * H * W <= (1LL << 32);
 }
 
 bool coord_ok(int v) { return v >= -MP_SHAPES_MAX_COORD && v <= MP_SHAPES_MAX_COORD; }
@@ -550,7 +547,7 @@ int mp_shapes_finish(mp_handle* h, float* canvas, int n, int H, int W, const int
     if (!h) return MP_EINVAL;
     const std::string f = "mp_shapes_finish";
     if (!canvas || !out || !blur1 || !blur2) return fail(h, MP_EINVAL, f + ": NULL argument");
-    if (!frame_ok(n, H, W) || oh <= 0 || ow <= 0 || oh > 32768 || ow > 32768)
+    if (!frame_ok(n, H, W) || !sides_ok(oh, ow, 1, 32768))
         return fail(h, MP_EINVAL, f + ": need 0 < n <= 65535 frames of at most 32768 x 32768 pixels");
     int kmax[2] = {0, 0};
     for (int i = 0; i < n; ++i) {

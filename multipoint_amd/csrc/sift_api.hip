@@ -6,10 +6,6 @@ using namespace mp_host;
 
 namespace {
 
-bool sift_frame_ok(int B, int H, int W) { return B >= 1 && B <= 65535 && H >= 16 && W >= 16 && H <= 4096 && W <= 4096; }
-
-long long align256(long long v) { return (v + 255) / 256 * 256; }
-
 // where everything lies in a workspace for B frames of H x W and `cap` list slots per image
 SiftLayout sift_layout(int B, int H, int W, int cap)
 {
@@ -18,20 +14,21 @@ SiftLayout sift_layout(int B, int H, int W, int cap)
     const int m = 2 * (H < W ? H : W);
     L.noct = (int)std::lrint(std::log2((double)m) - 2.0) + 1;
     if (L.noct > MP_SIFT_MAX_OCTAVES) L.noct = MP_SIFT_MAX_OCTAVES;
-    long long at = 0;      // floats
+    Carver c(nullptr, 256 * sizeof(float));      // the pyramids start on multiples of 256 floats, the lists after them of 256 bytes
+    auto floats = [&](long long n) { const long long p = (long long)(c.at / sizeof(float)); c.take<float>((size_t)n); return p; };
+    auto take = [&](long long bytes) { const long long p = (long long)c.at; c.take<char>((size_t)bytes); return p; };
     int h = 2 * H, w = 2 * W;
     L.flat[0] = 0;
     for (int o = 0; o < L.noct; ++o) {
         L.h[o] = h; L.w[o] = w;
-        L.gauss[o] = at; at = align256(at + (long long)B * MP_SIFT_LAYERS * h * w);
-        L.dog[o] = at; at = align256(at + (long long)B * 5 * h * w);
+        L.gauss[o] = floats((long long)B * MP_SIFT_LAYERS * h * w);
+        L.dog[o] = floats((long long)B * 5 * h * w);
         L.flat[o + 1] = L.flat[o] + 3LL * h * w;
         h /= 2; w /= 2;
     }
-    L.tmp = at; at = align256(at + (long long)B * 4 * H * W);
+    L.tmp = floats((long long)B * 4 * H * W);
     L.nblk = (int)((L.flat[L.noct] + 1023) / 1024);
-    long long by = at * (long long)sizeof(float);
-    auto take = [&](long long bytes) { const long long p = by; by = align256(by + bytes); return p; };
+    c.align = 256;
     L.cmask = take((long long)B * L.nblk * 256);
     L.seg_count = take((long long)B * L.nblk * 4);
     L.seg_base = take((long long)B * L.nblk * 4);
@@ -44,20 +41,17 @@ SiftLayout sift_layout(int B, int H, int W, int cap)
     L.list = take((long long)B * cap * 6 * 4);
     L.list_count = take((long long)B * 4);
     L.dup = take((long long)B * cap);
-    L.bytes = by;
+    L.bytes = (long long)c.bytes();
     return L;
 }
 
 int sift_check(mp_handle* h, const char* who, int B, int H, int W, int cap, const void* ws, long long ws_bytes, SiftLayout* L)
 {
-    if (!sift_frame_ok(B, H, W) || cap < 1 || cap > (1 << 24))
+    if (!frames_ok(B, H, W, 16, 4096) || cap < 1 || cap > (1 << 24))
         return fail(h, MP_EINVAL, std::string(who) + ": need 1 <= B <= 65535, frames of 16 x 16 to 4096 x 4096 and 1 <= capacity <= 2^24");
     if (!ws) return fail(h, MP_EINVAL, std::string(who) + ": NULL workspace");
     *L = sift_layout(B, H, W, cap);
-    if (ws_bytes < L->bytes)
-        return fail(h, MP_EINVAL, std::string(who) + ": workspace of " + std::to_string(ws_bytes) + " B, needs " + std::to_string(L->bytes) +
-                                      " B (mp_sift_workspace_bytes)");
-    return MP_OK;
+    return need_workspace(h, who, ws_bytes, (size_t)L->bytes, "mp_sift_workspace_bytes");
 }
 
 }  // namespace
@@ -66,14 +60,14 @@ extern "C" {
 
 int mp_sift_workspace_bytes(int B, int H, int W, int capacity, long long* bytes)
 {
-    if (!bytes || !sift_frame_ok(B, H, W) || capacity < 1 || capacity > (1 << 24)) return MP_EINVAL;
+    if (!bytes || !frames_ok(B, H, W, 16, 4096) || capacity < 1 || capacity > (1 << 24)) return MP_EINVAL;
     *bytes = sift_layout(B, H, W, capacity).bytes;
     return MP_OK;
 }
 
 int mp_sift_layout(int B, int H, int W, int capacity, long long* layout)
 {
-    if (!layout || !sift_frame_ok(B, H, W) || capacity < 1 || capacity > (1 << 24)) return MP_EINVAL;
+    if (!layout || !frames_ok(B, H, W, 16, 4096) || capacity < 1 || capacity > (1 << 24)) return MP_EINVAL;
     const SiftLayout L = sift_layout(B, H, W, capacity);
     layout[0] = L.noct;
     layout[1] = L.cand; layout[2] = L.cand_count; layout[3] = L.list; layout[4] = L.list_count;
@@ -122,7 +116,7 @@ int mp_sift_select(mp_handle* h, const float* records, const int* rec_count, int
 {
     if (!h) return MP_EINVAL;
     if (!records || !rec_count || !keypoints || !count || !scratch) return fail(h, MP_EINVAL, "mp_sift_select: NULL tensor");
-    if (B < 1 || B > 65535 || M < 1 || M > (1 << 24) || nfeatures < 1 || N < nfeatures || scratch_bytes < (long long)B * M)
+    if (!count_ok(B) || M < 1 || M > (1 << 24) || nfeatures < 1 || N < nfeatures || scratch_bytes < (long long)B * M)
         return fail(h, MP_EINVAL, "mp_sift_select: need 1 <= B <= 65535, 1 <= M <= 2^24, 1 <= nfeatures <= N and B * M bytes of scratch");
     MP_HIP(hipSetDevice(h->device));
     launch_sift_select(records, rec_count, B, M, nfeatures, N, keypoints, count, static_cast<unsigned char*>(scratch),
@@ -135,7 +129,7 @@ int mp_sift_describe(mp_handle* h, int B, int H, int W, int capacity, const void
 {
     if (!h) return MP_EINVAL;
     if (!keypoints || !count || !desc) return fail(h, MP_EINVAL, "mp_sift_describe: NULL tensor");
-    if (N < 1 || N > 65535 * 64) return fail(h, MP_EINVAL, "mp_sift_describe: need 1 <= N <= 4193280");
+    if (N < 1 || N > MAX_GRID_Y * 64) return fail(h, MP_EINVAL, "mp_sift_describe: need 1 <= N <= 4193280");
     SiftLayout L;
     const int rc = sift_check(h, "mp_sift_describe", B, H, W, capacity, workspace, workspace_bytes, &L);
     if (rc != MP_OK) return rc;
@@ -149,7 +143,7 @@ int mp_sift_scatter(mp_handle* h, const float* keypoints, const int* count, int 
 {
     if (!h) return MP_EINVAL;
     if (!keypoints || !count || !prob || !owner) return fail(h, MP_EINVAL, "mp_sift_scatter: NULL tensor");
-    if (!sift_frame_ok(B, H, W) || N < 1 || N > (1 << 24))
+    if (!frames_ok(B, H, W, 16, 4096) || N < 1 || N > (1 << 24))
         return fail(h, MP_EINVAL, "mp_sift_scatter: need 1 <= B <= 65535, frames of 16 x 16 to 4096 x 4096 and 1 <= N <= 2^24");
     MP_HIP(hipSetDevice(h->device));
     launch_sift_scatter(keypoints, count, B, N, H, W, prob, owner, static_cast<hipStream_t>(stream));
