@@ -28,13 +28,14 @@ def upstream(keys, grads, lam):
 def softmax(lg):
     m = lg.max(1, keepdims=True)
     e = np.exp(lg - m)
-    return e / e.sum(1, keepdims=True)
+    return e / R._sum(e, 1, keepdims=True)
 
 
-def detector_grad(logits, keypoints, valid_mask, use_ce, gamma, noise=None, labels=None):
+def detector_grad(logits, keypoints, valid_mask, use_ce, gamma, noise=None, labels=None, dtype=np.float64):
     """d(mean_b(sum(loss * valid) / count))/d logits times gamma, float64 [B][65][Hc][Wc].  `labels` [B][Hc][Wc]
-    overrides the labels drawn from `noise` (the device hash)."""
-    lg = np.asarray(logits, np.float64)
+    overrides the labels drawn from `noise` (the device hash).  dtype=np.float32 evaluates the same formulas in float32
+    with sequential sums (R.detector_loss_sums' float32 mode); the result is widened at the end."""
+    lg = np.asarray(logits, dtype)
     B, _, Hc, Wc = lg.shape
     valid = R.cell_valid(valid_mask, B, 8 * Hc, 8 * Wc)
     count = valid.reshape(B, -1).sum(1).astype(np.float64)
@@ -45,15 +46,15 @@ def detector_grad(logits, keypoints, valid_mask, use_ce, gamma, noise=None, labe
         np.put_along_axis(y, lab[:, None], 1.0, 1)
         dz = p - y
     else:
-        kp = R.space_to_depth(np.asarray(keypoints) != 0).astype(np.float64)
+        kp = R.space_to_depth(np.asarray(keypoints) != 0).astype(dtype)
         dust = 1.0 - np.minimum(kp.sum(1, keepdims=True), 1.0)
         y = np.concatenate([kp, dust], 1)
         y = y / y.sum(1, keepdims=True)
-        gp = (p - y) / np.maximum(p * (1 - p), 1e-12)
-        dz = p * (gp - (p * gp).sum(1, keepdims=True))
+        gp = (p - y) / np.maximum(p * (1 - p), dtype(1e-12))
+        dz = p * (gp - R._sum(p * gp, 1, keepdims=True))
     with np.errstate(divide='ignore', invalid='ignore'):
-        scale = gamma / (B * count)
-        return dz * valid[:, None] * scale[:, None, None, None]
+        scale = (gamma / (B * count)).astype(dtype)
+        return (dz * valid[:, None] * scale[:, None, None, None]).astype(np.float64)
 
 
 def descriptor_grad(desc1, desc2, w1, w2, valid1, valid2, config, alpha, beta):

@@ -25,9 +25,17 @@ def cell_valid(valid_mask, B, H, W):
     return space_to_depth(np.asarray(valid_mask).reshape(B, H, W) != 0).all(1)
 
 
+def _sum(x, axis, keepdims=False):
+    """float64: numpy's sum.  float32: the terms added one after the other in float32, as a loop over them does."""
+    if x.dtype == np.float64:
+        return x.sum(axis, keepdims=keepdims)
+    s = np.take(np.cumsum(x, axis, dtype=x.dtype), -1, axis)
+    return np.expand_dims(s, axis) if keepdims else s
+
+
 def _logsumexp(x, axis):
     m = x.max(axis, keepdims=True)
-    return (m + np.log(np.exp(x - m).sum(axis, keepdims=True))).squeeze(axis)
+    return (m + np.log(_sum(np.exp(x - m), axis, keepdims=True))).squeeze(axis)
 
 
 def detector_labels(keypoints, noise):
@@ -39,24 +47,25 @@ def detector_labels(keypoints, noise):
     return v.argmax(1)
 
 
-def detector_loss_sums(logits, keypoints, valid_mask, use_ce, noise=None):
-    """Per image (sum of loss * valid, count of valid cells) in float64."""
-    lg = np.asarray(logits, np.float64)
+def detector_loss_sums(logits, keypoints, valid_mask, use_ce, noise=None, dtype=np.float64):
+    """Per image (sum of loss * valid, count of valid cells) in float64.  dtype=np.float32 evaluates the same formulas in
+    float32 with sequential sums (the measure of what float32 arithmetic alone costs); the result is widened at the end."""
+    lg = np.asarray(logits, dtype)
     B, _, Hc, Wc = lg.shape
     valid = cell_valid(valid_mask, B, 8 * Hc, 8 * Wc)
     if use_ce:
         label = detector_labels(keypoints, noise)
         loss = _logsumexp(lg, 1) - np.take_along_axis(lg, label[:, None], 1)[:, 0]
     else:
-        kp = space_to_depth(np.asarray(keypoints) != 0).astype(np.float64)
+        kp = space_to_depth(np.asarray(keypoints) != 0).astype(dtype)
         dust = 1.0 - np.minimum(kp.sum(1, keepdims=True), 1.0)
         y = np.concatenate([kp, dust], 1)
         y = y / y.sum(1, keepdims=True)
         p = np.exp(lg - _logsumexp(lg, 1)[:, None])
         with np.errstate(divide='ignore'):
-            loss = -(y * np.maximum(np.log(p), -100) + (1 - y) * np.maximum(np.log1p(-p), -100)).sum(1)
-    loss = np.where(valid, loss, 0.0)
-    return loss.reshape(B, -1).sum(1), valid.reshape(B, -1).sum(1).astype(np.float64)
+            loss = -_sum(y * np.maximum(np.log(p), -100) + (1 - y) * np.maximum(np.log1p(-p), -100), 1)
+    loss = np.where(valid, loss, 0.0).astype(dtype)
+    return _sum(loss.reshape(B, -1), 1).astype(np.float64), valid.reshape(B, -1).sum(1).astype(np.float64)
 
 
 def cell_centres(Hc, Wc):
